@@ -2,7 +2,12 @@
 """Headline benchmark: images/s of one training step (forward + rd_loss + backward + Adam step)
 of the hot path on synthetic 256x256 RGB batches, batch 32 per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|3k|2h|4|5|hmr] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|3k|2h|4|5|hmr] [--full] [--no-cpu-baseline]
+                  [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, the loss
+after the steps); nothing else runs.  `--full` adds the measurements below.  `--dump-outputs DIR` writes what the
+last timed step computed as DIR/<name>.npy (float32, see dump_outputs).
 
 N > 1 is launched by the driver as  python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N ...: one rank per GPU, images sharded (32 per rank, weak scaling), one RCCL all-reduce of
@@ -15,7 +20,7 @@ Other configs are parity-test cases that can be timed the same way: 3 = BASELINE
 (JAH(128, K=3), bf16 storage in the conv/GDN stacks), 3k / 2h = the same models in the other
 precision, 4 = configs[3]'s per-GPU work, 5 = configs[4] (16x512x512).
 
-Extra fields of the JSON line: `roofline` (dominant kernel by time, HIP events around every MFMA
+Extra fields of the JSON line with --full: `roofline` (dominant kernel by time, HIP events around every MFMA
 launch of >= 2 GFLOP in the timed region), `kernels` (per-kernel ms and TFLOP/s of those), `analysis_hyperprior_fwd`
 (the scope the north star quotes its target on, timed separately after the K steps) and
 `cpu_baseline` (oracle/torch_ref.py on the host cores, bounded sample).
@@ -150,6 +155,45 @@ def analysis_hyperprior_fwd(model, x, F_, bf16, reps=5, planned=False):
                 "planned_launches": planned_info["kernels"]} if planned_ms is not None else {})}
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger array
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(out, res, model):
+    """What a caller of the timed step receives, as float32 numpy arrays: every tensor of the model's out-dict and of
+    rd_loss's result, and the parameters and their gradients after the step (each concatenated over
+    named_parameters() in order).  Values are taken in logical (NCHW, row-major) order, so the memory layout a
+    build chooses does not matter.  An array of more than DUMP_SAMPLE elements is reduced to the values at
+    DUMP_SAMPLE sorted positions drawn with a seed derived from its name: the same positions in every run."""
+    import zlib
+
+    import numpy as np
+    params = [p for _, p in model.named_parameters()]
+    tensors = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    tensors.update({k: v for k, v in res.items() if torch.is_tensor(v) and not k.startswith("_")})
+    tensors["parameters"] = torch.cat([p.detach().float().reshape(-1) for p in params])
+    tensors["gradients"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1)
+                                      for p in params])
+    arrays = {}
+    for name, t in tensors.items():
+        t = t.detach().float().contiguous()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        arrays[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    return arrays
+
+
+def dump_outputs(arrays, directory):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -159,11 +203,20 @@ def main():
     ap.add_argument("--plan", default="auto", choices=("auto", "on", "off"),
                     help="replay the step from a launch plan (plan.StepPlan: the captured step issued on two streams by "
                          "liblic_hip.so, no Python between launches); auto = on for the host-paced bf16 configs on one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel HIP events (roofline, kernels), the "
+                         "analysis+hyperprior forward alone and the CPU baseline (each can be left out with --no-...)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile-events", action="store_true")
     ap.add_argument("--no-analysis-fwd", action="store_true",
                     help="skip the separate analysis+hyperprior forward timing (keeps a rocprofv3 trace to the K steps)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_profile_events = args.no_analysis_fwd = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -228,7 +281,7 @@ def main():
         if reducer is not None:
             reducer.finish()
         opt.step()
-        return res
+        return out, res
 
     def fence():
         if world > 1:
@@ -255,9 +308,9 @@ def main():
         plan.x.copy_(x)
 
         def step():
-            _, res = plan.step(plan.x)
+            out, res = plan.step(plan.x)
             opt.step()
-            return res
+            return out, res
 
     for _ in range(args.warmup):
         step()
@@ -280,13 +333,19 @@ def main():
             on = i % stride == 0 and len(prof) + per_step <= MAX_LIVE_PAIRS
             F_.PROFILE = prof if on else None
             bracketed_steps += int(on)
-        res = step()
+        out = None   # (the previous step's outputs are not held through this one)
+        out, res = step()
         if prof is not None and i == 0:
             per_step = len(prof)
             stride = max(1, -(-(args.steps * per_step) // MAX_LIVE_PAIRS))
     fence()
     el = time.perf_counter() - t0
     final_res = {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in res.items()}
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: a plan's output buffers are rewritten by every replay, and the eager steps
+        # of --full below move the parameters on
+        dump_outputs(output_arrays(out, res, model), args.dump_outputs)
+    del out
     if plan is not None and not args.no_profile_events:
         # a replay runs no Python between launches, so there is nothing to record events from: the per-kernel
         # brackets come from eager steps of the same model right AFTER the timed region (same kernels and launch

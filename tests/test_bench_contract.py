@@ -1,6 +1,7 @@
-"""bench.py's output contract: one JSON line with the driver's keys plus `roofline` and `cpu_baseline`.
+"""bench.py's output contract: one JSON line with the driver's keys, plus `roofline` and `cpu_baseline` with --full.
 CPU: the newest committed line under profiles/ has every key with a sane type, bench.py refuses to run
-without a GPU (no CPU fallback).  GPU: a short live run prints a conforming line."""
+without a GPU (no CPU fallback).  GPU: a short live run prints a conforming line, and --dump-outputs writes
+the same arrays in every run."""
 import glob
 import json
 import os
@@ -18,7 +19,7 @@ ROOFLINE = {"bound": str, "achieved": (int, float), "peak": (int, float), "unit"
 CPU_BASELINE = {"value": (int, float), "unit": str, "cores": int, "kind": str, "sample": str}
 
 
-def check_line(d, want_cpu):
+def check_line(d, want_cpu, full=True):
     for k, t in CONTRACT.items():
         assert k in d and isinstance(d[k], t), k
     assert "vs_baseline" in d and d["vs_baseline"] is None      # BASELINE.md publishes no number for this metric
@@ -27,6 +28,9 @@ def check_line(d, want_cpu):
     assert "workload" in d["config"] and "model" not in d["config"]
     assert d["config"]["loss"] == d["config"]["loss"] and abs(d["config"]["loss"]) < 1e6, "non-finite loss in a bench line"
     assert abs(d["value"] - d["config"]["global_batch"] / d["ms_per_step"] * 1e3) <= 0.01 * d["value"]
+    if not full:
+        assert not {"roofline", "kernels", "analysis_hyperprior_fwd", "cpu_baseline"} & set(d), "a plain run measured extras"
+        return
     r = d["roofline"]
     for k, t in ROOFLINE.items():
         assert k in r and isinstance(r[k], t), k
@@ -70,12 +74,34 @@ def test_bench_configs_cover_baseline_json():
     assert (kind, M, K, B, H, W) == ("jah", 192, 1, 32, 256, 256)
 
 
+def test_dump_arrays_are_float32_seeded_samples_within_the_limit():
+    """output_arrays on host tensors: large arrays become the same fixed sample in every call, taken in logical
+    order (a channels_last copy gives the same values), small ones stay whole; private result keys are left out."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    model = torch.nn.Linear(1000, 1000)   # (1001000 values: below DUMP_SAMPLE, kept whole)
+    model.weight.grad = torch.rand_like(model.weight)
+    x_hat = torch.rand(4, 3, 300, 300)
+    res = {"loss": torch.tensor(2.5), "psnr_per_image": torch.rand(4), "_buffer": torch.zeros(8)}
+    a = bench.output_arrays({"x_hat": x_hat, "training": True}, res, model)
+    b = bench.output_arrays({"x_hat": x_hat.contiguous(memory_format=torch.channels_last), "training": True}, res, model)
+    assert sorted(a) == ["gradients", "loss", "parameters", "psnr_per_image", "x_hat"]
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    assert a["x_hat"].shape == (bench.DUMP_SAMPLE,) and np.isin(a["x_hat"], x_hat.numpy()).all()
+    assert a["loss"] == np.float32(2.5) and a["psnr_per_image"].shape == (4,)
+    assert a["gradients"][-1000:].sum() == 0.0   # (the bias has no gradient: zeros)
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES
+
+
 @pytest.mark.gpu
 def test_live_bench_line():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--full",
                         "--no-cpu-baseline", "--no-analysis-fwd"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])
@@ -102,3 +128,31 @@ def test_two_stream_training_step_is_finite_and_repeatable(cfg):
         losses.append(json.loads(p.stdout.strip().splitlines()[-1])["config"]["loss"])
     assert losses[0] == losses[0] and abs(losses[0]) < 1e6, losses
     assert losses[0] == losses[1], losses
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain run (no --full) prints the headline line and nothing else; two runs with the same arguments write
+    bit-identical --dump-outputs (seeded inputs, deterministic kernels), float32, at most 64 MB."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, (p.stdout + p.stderr)[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        check_line(line, want_cpu=False, full=False)
+        assert line["steps"] == 3 and line["warmup"] == 1
+        arrays = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+        assert {"x_hat", "y_in", "logp_y", "loss", "parameters", "gradients"} <= set(arrays), sorted(arrays)
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        assert abs(float(arrays["loss"]) - line["config"]["loss"]) <= 1e-5 * abs(line["config"]["loss"])
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
