@@ -271,15 +271,19 @@ class ContextCodec:
                            i < 2, slopes[i] if i < 2 else 0.01))
         return layers
 
-    def _params_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers):
-        """windows [N, 12M, 1, 1], psi_px [N, 2M, 1, 1] -> (center [N, M], tables [N*M, S+1]) on the device"""
+    def _act_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers) -> torch.Tensor:
+        """windows [N, 12M, 1, 1], psi_px [N, 2M, 1, 1] -> the activated entropy parameters [N, G*K*M, 1, 1]"""
         m = self.model
         wp, b, co, _, _ = layers[0]
         x = torch.cat([F_.conv2d_prepacked(windows, wp, b, co, 1, pin_tile=True), psi_px], dim=1)
         for wp, b, co, leaky, slope in layers[1:]:
             x = F_.conv2d_prepacked(x, wp, b, co, 1, leaky=leaky, slope=slope, pin_tile=True)
-        act = F_.entropy_params_activation(x, m.M, m.K)
-        return gmm_tables(act, m.M, m.K, self.y_W)
+        return F_.entropy_params_activation(x, m.M, m.K)
+
+    def _params_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers):
+        """windows [N, 12M, 1, 1], psi_px [N, 2M, 1, 1] -> (center [N, M], tables [N*M, S+1]) on the device"""
+        m = self.model
+        return gmm_tables(self._act_at(windows, psi_px, layers), m.M, m.K, self.y_W)
 
     def _windows_all(self, y_hat: torch.Tensor) -> torch.Tensor:
         """[B, M, h, w] -> [B*h*w, 12M, 1, 1]: the live taps of every pixel (zeros outside the image)"""

@@ -146,11 +146,16 @@ def _gcdf(t):
 
 
 def forward(P: Dict[str, torch.Tensor], x: torch.Tensor, M: int, K: int, kind: str = "5x5",
-            training: bool = True, noise: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
-    """Returns the reference's 13-key dict (Models.py:92-106)."""
+            training: bool = True, noise: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+            quantized: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """Returns the reference's 13-key dict (Models.py:92-106).  `quantized` = (z_in, y_in): everything after the
+    quantisation (hyper-decoder, context, entropy parameters, likelihoods, decoder) runs on these tensors instead of
+    on round() / the noisy latents -- a device forward can then be compared downstream of its own rounding."""
     y = encoder(x, P, kind)
     z = hyper_encoder(y, P, kind)
-    if training:
+    if quantized is not None:
+        z_in, y_in = quantized
+    elif training:
         uz, uy = noise if noise is not None else (torch.rand_like(z), torch.rand_like(y))
         z_in, y_in = z + (uz - 0.5), y + (uy - 0.5)
     else:

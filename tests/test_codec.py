@@ -1,7 +1,10 @@
 """Entropy coder.  CPU: the C++ range coder against its pure-Python restatement
 (byte-identical streams), round trips incl. escapes and degenerate tables, size vs ideal.  GPU: the
-device-built tables against the numpy restatement (exact integers) and coded bpp vs estimated bpp
-of a model."""
+device-built tables against the numpy restatement (exact integers), the two table kernels against each
+other, coded bpp vs estimated bpp of a model, round trips up to real capacity, and the evaluator's
+reported numbers against the reference's formulas."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -213,6 +216,174 @@ def test_evaluator_reports_coded_bpp(codec, tmp_path):
     assert abs(m["BPP(coded)"] - m["BPP(total)"]) <= 0.02 * m["BPP(total)"] + 128.0 / (192 * 256)
     m2, _, _ = ev.evaluate(nic.rd_loss)
     assert "BPP(coded)" not in m2 and m2["BPP(total)"] == m["BPP(total)"]
+
+
+@pytest.mark.gpu
+def test_evaluator_numbers_follow_the_reference_formulas(codec, tmp_path):
+    """Every number CompressionEvaluator.evaluate reports, recomputed on the host in float64 from the same
+    x_hat.clamp(0, 1) and rd_loss outputs by the formulas of Evaluator.py:32-92: MSE(255), PSNR(RGB), PSNR(Y) with
+    BT.601 luma (1e-5 relative), MS-SSIM(RGB) / MS-SSIM(Y) against oracle/torch_ref.ms_ssim (test_msssim.py's
+    tolerance), 'BPP' = the mean of bpp_y (the reference's aggregation), BPP(y), BPP(z), BPP(total).  Two Kodak-sized
+    frames through JAH(192, K=1); and compute_metrics(x, x): PSNR inf, MS-SSIM 1."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    import neural_image_compression_amd as nic
+    from neural_image_compression_amd.evaluator import CompressionEvaluator
+    from oracle import torch_ref as TR
+    import golden_recipe as R
+    model = nic.JointAutoregressiveHierarchical(192, 1)
+    st = R.make_state([(k, tuple(v.shape)) for k, v in model.state_dict().items()], 71)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
+    model = model.cuda()
+    batches = [torch.from_numpy(R.make_image(1, 512, 768, 72 + i)).contiguous(memory_format=torch.channels_last)
+               for i in range(2)]
+    seen = []
+
+    def rd_loss(out, x, lam):
+        r = nic.rd_loss(out, x, lam)
+        seen.append((x.detach().float().cpu(), out["x_hat"].clamp(0, 1).detach().float().cpu(), r))
+        return r
+    ev = CompressionEvaluator(model, batches, torch.device("cuda:0"), 0.01, save_dir=str(tmp_path))
+    m, _, _ = ev.evaluate(rd_loss)
+    assert len(seen) == 2
+
+    def luma(t):
+        return 0.299 * t[:, 0] + 0.587 * t[:, 1] + 0.114 * t[:, 2]
+    per = []
+    for x, xh, r in seen:
+        xd, hd = x.double(), xh.double()
+        mse, mse_y = float(((xd - hd) ** 2).mean()), float(((luma(xd) - luma(hd)) ** 2).mean())
+        assert mse > 0 and mse_y > 0
+        per.append({"MSE(255)": mse * 255 ** 2, "PSNR(RGB)": 10 * math.log10(1.0 / mse),
+                    "PSNR(Y)": 10 * math.log10(1.0 / mse_y),
+                    "MS-SSIM(RGB)": float(TR.ms_ssim(xh, x, data_range=1.0)),
+                    "MS-SSIM(Y)": float(TR.ms_ssim(luma(hd).float().unsqueeze(1), luma(xd).float().unsqueeze(1),
+                                                   data_range=1.0)),
+                    "bpp_y": float(r["bpp_y"]), "bpp_z": float(r["bpp_z"]), "bpp_total": float(r["bpp_total"])})
+    want = {k: float(np.mean([p[k] for p in per], dtype=np.float64)) for k in per[0]}
+    for k in ("MSE(255)", "PSNR(RGB)", "PSNR(Y)"):
+        assert abs(m[k] - want[k]) <= 1e-5 * abs(want[k]), (k, m[k], want[k])
+    for k in ("MS-SSIM(RGB)", "MS-SSIM(Y)"):
+        assert abs(m[k] - want[k]) <= 2e-6 + 2e-5 * abs(want[k]), (k, m[k], want[k])
+    # Evaluator.py:78-83: 'BPP' is the mean of bpp_y, not of bpp_total
+    for k, src in (("BPP", "bpp_y"), ("BPP(y)", "bpp_y"), ("BPP(z)", "bpp_z"), ("BPP(total)", "bpp_total")):
+        assert abs(m[k] - want[src]) <= 1e-12 * abs(want[src]), (k, m[k], want[src])
+    assert want["bpp_z"] > 0 and m["BPP"] < m["BPP(total)"]
+    # mse == 0 -> inf (Evaluator.py:37,45), and an image is perfectly similar to itself
+    x = batches[0].cuda()
+    same = ev.compute_metrics(x, x)
+    assert same["MSE(255)"] == 0.0
+    assert same["PSNR(RGB)"] == float("inf") and same["PSNR(Y)"] == float("inf")
+    assert abs(same["MS-SSIM(RGB)"] - 1.0) <= 1e-5 and abs(same["MS-SSIM(Y)"] - 1.0) <= 1e-5
+
+
+# ---- the coder at real capacity -------------------------------------------------------------
+def _edge_raw(r, K, M, P, W):
+    """raw entropy parameters [1, G*K*M, P, 1] over the table kernels' edges: sigma at its 1e-6 floor and sigma far
+    wider than the window; for K >= 2 saturated softmax weights and components more than W + 5 away from the weighted
+    centre the window is placed on (their mass lands in the two tail symbols)"""
+    if K == 1:
+        mu = r.randn(P, M) * 8
+        sg = r.randn(P, M) * 2
+        sel = r.rand(P, M)
+        sg[sel < 0.15] = -60.0                                    # softplus -> 0: sigma = 1e-6
+        sg[sel > 0.85] = r.uniform(2e3, 1e4, size=(sel > 0.85).sum())   # sigma >> W
+        return np.concatenate([mu, sg], 1).astype(np.float32).T.reshape(1, 2 * M, P, 1)
+    wr, mus, sgs = r.randn(P, K, M), r.randn(P, K, M) * 8, r.randn(P, K, M) * 2
+    sel = r.rand(P, M)
+    sat = sel < 0.2                                               # one component takes all the weight
+    wr[:, 0][sat], wr[:, 1:][np.broadcast_to(sat[:, None], (P, K - 1, M))] = 60.0, -60.0
+    far = (sel >= 0.2) & (sel < 0.6)                              # component 0 dominant, the last one far away
+    wr[:, 0][far] = 3.0 + np.log(K)
+    side = np.where(r.rand(far.sum()) < 0.5, -1.0, 1.0)
+    mus[:, K - 1][far] = mus[:, 0][far] + side * (3 * W + 20 + 10 * r.rand(far.sum()))
+    s = r.rand(P, K, M)
+    sgs[s < 0.15] = -60.0
+    sgs[s > 0.9] = r.uniform(2e3, 1e4, size=(s > 0.9).sum())
+    raw = np.concatenate([wr.reshape(P, K * M), mus.reshape(P, K * M), sgs.reshape(P, K * M)], 1)
+    return raw.astype(np.float32).T.reshape(1, 3 * K * M, P, 1)
+
+
+def _split_act(a, K, M):
+    """host act [P, G*K*M] -> (weights, mus, sigmas) [K, P*M] in the table kernels' element order"""
+    P = a.shape[0]
+    if K == 1:
+        return np.ones((1, P * M), np.float32), a[:, :M].reshape(1, -1), a[:, M:].reshape(1, -1)
+    T = K * M
+    return tuple(a[:, i * T:(i + 1) * T].reshape(P, K, M).transpose(1, 0, 2).reshape(K, -1) for i in range(3))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 2, 3, 8])
+def test_loop_and_wave_table_kernels_agree_bit_for_bit(codec, K):
+    """lic_gmm_cdf_tables takes a thread-per-element loop above 32768 elements (the encoder: a Kodak frame at M = 192
+    has 294 912) and one wavefront per element below (the decoder: one wavefront of pixels per step).  A bitstream
+    decodes only if both build the same tables: the same parameters through both, bit for bit, over the edge cases
+    of _edge_raw; the table invariants; and <= 2 counts from oracle/codec_ref.py where the centres agree."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    from neural_image_compression_amd import functional as F_
+    M, P, W = 64, 1024, 32                     # P * M = 65536 elements: the loop kernel
+    S = 2 * W + 1
+    r = np.random.RandomState(90 + K)
+    raw = torch.from_numpy(_edge_raw(r, K, M, P, W)).cuda().contiguous(memory_format=torch.channels_last)
+    act = F_.entropy_params_activation(raw, M, K)
+    center, tabs = codec.gmm_tables(act, M, K, W)
+    rows = 32768 // M                          # 512 pixels = 32768 elements per slice: the wave kernel
+    parts = [codec.gmm_tables(act[:, :, p0:p0 + rows], M, K, W) for p0 in range(0, P, rows)]
+    assert len(parts) == 2
+    assert torch.equal(center.view(-1), torch.cat([c.view(-1) for c, _ in parts]))
+    assert torch.equal(tabs, torch.cat([t for _, t in parts])), "loop and wave kernels built different tables"
+    t = tabs.cpu().numpy().view(np.uint32).astype(np.int64)
+    assert t.shape == (P * M, S + 1)
+    assert (t[:, 0] == 0).all() and (t[:, S] == 65536).all() and (np.diff(t, axis=1) >= 1).all()
+    a = act.detach().permute(0, 2, 3, 1).reshape(P, -1).cpu().numpy()
+    w_, mu_, sg_ = _split_act(a, K, M)
+    # the edges are really there
+    assert (sg_ <= 1.0001e-6).mean() > 0.05 and (sg_ > 1e3).mean() > 0.03
+    c = center.cpu().numpy().ravel()
+    if K > 1:
+        assert ((w_ == 1.0) | (w_ == 0.0)).all(axis=0).mean() > 0.1                       # saturated softmax
+        assert (np.abs(mu_ - c[None, :]) > W + 5).any(axis=0).mean() > 0.2               # mass in the tail symbols
+        assert (t[:, 1] > 1).mean() > 0.05 and (t[:, S] - t[:, S - 1] > 1).mean() > 0.05
+    c_ref, t_ref = CR.gmm_tables(w_, mu_, sg_, W)
+    same = c == c_ref
+    assert same.mean() > 0.99
+    d = np.abs(t[same] - t_ref[same].astype(np.int64))
+    assert d.max() <= 2, d.max()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,K,precision", [(192, 1, "fp32"), (128, 3, "bf16")])
+def test_context_codec_round_trip_at_full_capacity(codec, M, K, precision):
+    """ContextCodec with its default windows on one 512x768 frame at real capacity -- JAH(192, K=1) and config 3's
+    JAH(128, K=3) in bf16 storage: the encoder's tables come from the loop kernel over all 1536 pixels, the
+    decoder's from the wave kernel one wavefront at a time.  Latents and x_hat bit for bit, CRCs pass, coded ~
+    estimated."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    import neural_image_compression_amd as nic
+    import golden_recipe as R
+    model = nic.JointAutoregressiveHierarchical(M, K)
+    st = R.make_state([(k, tuple(v.shape)) for k, v in model.state_dict().items()], 95 + K)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in st.items()})
+    model = model.cuda().eval()
+    if precision != "fp32":
+        model.set_precision(precision)
+    B, H, W = 1, 512, 768
+    x = torch.from_numpy(R.make_image(B, H, W, 97)).cuda().contiguous(memory_format=torch.channels_last)
+    cc = codec.ContextCodec(model)
+    enc = cc.compress(x)
+    assert enc["shape"] == (B, M, H // 16, W // 16) and len(enc["strings"]["y_crc32"]) == B
+    dec = cc.decompress(enc["strings"], enc["shape"], enc["z_shape"])      # raises if a CRC does not match
+    assert torch.equal(dec["z_hat"], enc["z_in"])
+    assert torch.equal(dec["y_hat"], enc["y_in"]), "decoder tables diverged from the encoder's"
+    with torch.no_grad():
+        ref = model(x, training=False)
+    assert torch.equal(dec["x_hat"], ref["x_hat"])
+    npix = B * H * W
+    assert abs(enc["bpp_coded"] - enc["bpp_est"]) <= 0.02 * enc["bpp_est"] + (64.0 * (B + 1)) / npix, \
+        (enc["bpp_coded"], enc["bpp_est"])
 
 
 @pytest.mark.parametrize("h,w", [(1, 1), (4, 4), (4, 8), (32, 48), (7, 3)])

@@ -565,3 +565,65 @@ def test_missing_cuda_input_raises(env):
     from neural_image_compression_amd._lib import LicError
     with pytest.raises(LicError):
         F_.conv2d(torch.zeros(1, 8, 4, 4), torch.zeros(8, 8, 3, 3), None, 1, 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# quantisation (Models.py:55-64): rint() in evaluation, additive noise in training
+# ---------------------------------------------------------------------------------------------
+def _quantize_inputs(n, seed):
+    """n float32 values: exact ties, one ulp either side of them, values near 2^23 / 2^24, signed zeros, then random
+    ties and random magnitudes"""
+    ties = np.array([0.5, 1.5, 2.5, 3.5, 2.0 ** 23 - 0.5, 2.0 ** 22 + 0.5], np.float32)
+    edge = [ties, np.nextafter(ties, np.float32(np.inf)), np.nextafter(ties, np.float32(0)),
+            np.array([2.0 ** 24, 2.0 ** 24 - 1, 2.0 ** 24 + 2, 2.0 ** 23, 2.0 ** 23 + 1, 2.0 ** 23 - 1, 0.49999997,
+                      1e-30, 3e38], np.float32)]
+    edge = np.concatenate(edge)
+    edge = np.concatenate([edge, -edge, np.array([0.0, -0.0], np.float32)])
+    r = np.random.RandomState(seed)
+    m = n - edge.size
+    rand = np.where(r.rand(m) < 0.3, r.randint(-300, 300, m) + 0.5, r.randn(m) * 10.0 ** r.randint(-2, 7, m))
+    v = np.concatenate([edge, rand.astype(np.float32)])
+    assert v.size == n
+    return v
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+@pytest.mark.parametrize("n", [4 * 600_000, 4 * 600_000 + 1, 4 * 600_000 + 2, 4 * 600_000 + 3])
+def test_quantize_rounds_half_to_even_and_adds_noise_exactly(env, n):
+    """lic_quantize: training=0 is torch.round on the CPU (round half to even, Models.py:62-63) bit for bit -- ties,
+    one ulp off ties, |v| near 2^23 / 2^24, -0.0 -- and training=1 is v + (u - 0.5) bit for bit, over more elements
+    than one grid of the launch covers and with every remainder mod 4."""
+    nic, F_, O, dev = env
+    from neural_image_compression_amd import _lib as L
+    v = torch.from_numpy(_quantize_inputs(n, n % 7))
+    u = torch.from_numpy(np.random.RandomState(3).rand(n).astype(np.float32))
+    dv, du = v.to(dev), u.to(dev)
+    for training, want in ((0, torch.round(v)), (1, v + (u - 0.5))):
+        out = torch.full_like(dv, float("nan"))
+        L.check(L.load().lic_quantize(F_._ptr(dv), F_._ptr(du), F_._ptr(out), n, training, F_._stream()), "lic_quantize")
+        assert torch.equal(_bits(out), want.view(torch.int32)), (training, int((_bits(out) != want.view(torch.int32)).sum()))
+
+
+@pytest.mark.parametrize("training", [0, 1])
+def test_quantize_bf16_rounds_and_casts_exactly(env, training):
+    """lic_quantize_bf16 (the same quantisation, plus the bf16 copies of its input and of its result in the same launch):
+    out as lic_quantize, v_bf16 == bf16(v) and out_bf16 == bf16(out) bit for bit (torch's round-to-nearest-even
+    conversion)."""
+    nic, F_, O, dev = env
+    from neural_image_compression_amd import _lib as L
+    n = 4 * 600_000
+    v = torch.from_numpy(_quantize_inputs(n, 11))
+    u = torch.from_numpy(np.random.RandomState(4).rand(n).astype(np.float32))
+    dv, du = v.to(dev), u.to(dev)
+    out = torch.full_like(dv, float("nan"))
+    v16 = torch.zeros(n, device=dev, dtype=torch.bfloat16)
+    o16 = torch.zeros(n, device=dev, dtype=torch.bfloat16)
+    L.check(L.load().lic_quantize_bf16(F_._ptr(dv), F_._ptr(du), F_._ptr(out), F_._ptr(v16), F_._ptr(o16), n, training,
+                                       F_._stream()), "lic_quantize_bf16")
+    want = torch.round(v) if training == 0 else v + (u - 0.5)
+    assert torch.equal(_bits(out), want.view(torch.int32))
+    assert torch.equal(v16.cpu().view(torch.int16), v.to(torch.bfloat16).view(torch.int16))
+    assert torch.equal(o16.cpu().view(torch.int16), want.to(torch.bfloat16).view(torch.int16))
