@@ -215,28 +215,6 @@ LIC_EXPORT size_t lic_colsum_workspace_bytes(int64_t P, int32_t C) {
   if (P <= 0 || C <= 0) return 0;
   return (size_t)colsum_chunks(P) * C * sizeof(float);
 }
-// stage 1 only; `job` receives stage 2 for a later lic_reduce_batch
-LIC_EXPORT int lic_colsum_partial(const float* in, int64_t ld, int64_t P, int32_t C, float scale, float* out,
-                                  void* workspace, size_t workspace_bytes, lic_reduce_job* job, lic_stream_t stream) {
-  if (!in || !out || !workspace || !job || P <= 0 || C <= 0) return LIC_ERR_INVALID;
-  const int nchunk = colsum_chunks(P);
-  if (workspace_bytes < (size_t)nchunk * C * sizeof(float)) return LIC_ERR_WORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  const int vec = (C % 4 == 0) && (ld % 4 == 0) && al16(in);
-  if (C == 3 && ld == 3 && al16(in))
-    hipLaunchKernelGGL(colsum3_stage1, dim3(nchunk), dim3(256), 0, s, in, (long)P, (float*)workspace, nchunk);
-  else
-    hipLaunchKernelGGL(colsum_stage1, dim3((C + 63) / 64, nchunk), dim3(256), 0, s, in, (long)ld, (long)P, C,
-                       (float*)workspace, nchunk, vec);
-  *job = lic_reduce_job{};
-  job->src = (const float*)workspace;
-  job->dst = out;
-  job->kind = LIC_REDUCE_COLUMNS;
-  job->splitk = nchunk;
-  job->Cn = C;
-  job->scale = scale;
-  return lic_check_launch();
-}
 LIC_EXPORT int lic_colsum(const float* in, int64_t ld, int64_t P, int32_t C, float scale, float* out,
                           void* workspace, size_t workspace_bytes, lic_stream_t stream) {
   if (!in || !out || !workspace || P <= 0 || C <= 0) return LIC_ERR_INVALID;
@@ -834,7 +812,7 @@ LIC_EXPORT int lic_gmm_cdf_tables(const float* params, int64_t P, int32_t M, int
   const long CH = (long)(K == 1 ? 2 : 3) * K * M;
   const long T = (long)K * M;
   const int S = 2 * W + 1;
-  if (P * M <= 32768 && getenv("LIC_TABLES_NO_WAVE") == nullptr) {
+  if (P * M <= 32768) {
     hipLaunchKernelGGL(gmm_cdf_tables_wave_kernel, dim3((unsigned)cdiv64(P * M, 4)), dim3(256), 0, (hipStream_t)stream,
                        params, (long)(P * M), M, K, W, center, out, CH, T);
     return lic_check_launch();

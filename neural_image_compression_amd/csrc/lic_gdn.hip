@@ -11,7 +11,6 @@
 // sums), and finishes in the 16-byte layout.  The generic lic_igemm route (prologue 1 / 2 / 3) remains
 // for other channel counts.
 #include "lic_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -33,9 +32,11 @@ struct GdnParams {
   int inverse;
 };
 
-// MODE 0 = forward, 1 = backward
+// Forward.  MODE is always 0: it stays a template parameter so that the kernel keeps its name
+// (gdn_kernel<TN, 0>) in profiles and tests.
 template <int TN, int MODE>
 __global__ __launch_bounds__(256) void gdn_kernel(const GdnParams p) {
+  static_assert(MODE == 0, "forward only");
   constexpr int C = 64 * TN;
   constexpr int LDX = C + 4;
   constexpr int NCH = C / GD_BK;
@@ -49,9 +50,9 @@ __global__ __launch_bounds__(256) void gdn_kernel(const GdnParams p) {
   const bool inv = p.inverse != 0;
 
   // ---- one sweep over the tile: whole rows, 16 bytes per lane ------------------------------------
-  if (MODE == 0) {
-    // forward: all SLOTS loads in flight at once (one HBM round trip per tile instead of SLOTS / 4: the
-    // sweep was 28 % of the waves' time in s_waitcnt, SQ_WAIT_ANY)
+  // all SLOTS loads in flight at once (one HBM round trip per tile instead of SLOTS / 4: the sweep was
+  // 28 % of the waves' time in s_waitcnt, SQ_WAIT_ANY)
+  {
     f32x4 a[SLOTS];
 #pragma unroll
     for (int u = 0; u < SLOTS; ++u) {
@@ -67,47 +68,10 @@ __global__ __launch_bounds__(256) void gdn_kernel(const GdnParams p) {
       const int row = idx / (C / 4), c4 = (idx - row * (C / 4)) * 4;
       *reinterpret_cast<f32x4*>(&smem[row * LDX + c4]) = a[u];
     }
-  } else {
-#pragma unroll
-  for (int s0 = 0; s0 < SLOTS; s0 += 4) {
-    f32x4 a[4], b[4], c[4];
-    bool ok[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int idx = (s0 + u) * 256 + tid;
-      const int row = idx / (C / 4), c4 = (idx - row * (C / 4)) * 4;
-      ok[u] = m0 + row < p.P;
-      const long off = ok[u] ? (m0 + row) * C + c4 : 0L;
-      a[u] = *reinterpret_cast<const f32x4*>(p.x + off);
-      b[u] = *reinterpret_cast<const f32x4*>(p.g + off);
-      c[u] = *reinterpret_cast<const f32x4*>(p.norm + off);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int idx = (s0 + u) * 256 + tid;
-      const int row = idx / (C / 4), c4 = (idx - row * (C / 4)) * 4;
-      f32x4 v;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float rs = __builtin_amdgcn_rsqf(c[u][e]);  // as lic_gdn_dnorm
-        const float gx = b[u][e] * a[u][e];
-        v[e] = inv ? 0.5f * gx * rs : -0.5f * gx * rs * (rs * rs);
-      }
-      if (ok[u]) *reinterpret_cast<f32x4*>(p.out2 + (m0 + row) * C + c4) = v;
-      if (!ok[u]) v = f32x4{0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(&smem[row * LDX + c4]) = v;
-    }
-  }
   }
   __syncthreads();
-  if (MODE == 1 && p.cs_t && tid < C) {  // column sums of the t tile (rows past P are zero), fixed order
-    float a = 0.0f;
-#pragma unroll 8
-    for (int r = 0; r < GD_BM; ++r) a += smem[r * LDX + tid];
-    p.cs_t[(long)blockIdx.x * C + tid] = a;
-  }
 
-  // ---- pool: acc[32 x 32*TN per wave] = A . panel, A = x^2 (forward) or t (backward) --------------
+  // ---- pool: acc[32 x 32*TN per wave] = x^2 . panel ---------------------------------------------
   f32x16 acc[TN];
 #pragma unroll
   for (int b = 0; b < TN; ++b)
@@ -127,10 +91,8 @@ __global__ __launch_bounds__(256) void gdn_kernel(const GdnParams p) {
   auto pool = [&](int c, const f32x4 (&rg)[TN][2]) {
     f32x4 a0 = *reinterpret_cast<const f32x4*>(xrow + c * GD_BK);
     f32x4 a1 = *reinterpret_cast<const f32x4*>(xrow + c * GD_BK + 4);
-    if (MODE == 0) {
-      a0 = a0 * a0;
-      a1 = a1 * a1;
-    }
+    a0 = a0 * a0;
+    a1 = a1 * a1;
 #pragma unroll
     for (int t = 0; t < 8; ++t)
 #pragma unroll
@@ -147,15 +109,13 @@ __global__ __launch_bounds__(256) void gdn_kernel(const GdnParams p) {
   }
 
   // ---- finish in the 16-byte layout: each 32x32 accumulator tile through a wave-private LDS patch --
-  // (forward keeps x in the tile; the patches live behind it only when there is room, else the tile's
-  // own rows of OTHER waves must not be overwritten: use a separate barrier-protected region)
-  // backward: the t tile is dead after the pool, so the patches alias it (50 KiB per workgroup -> three
-  // resident per CU); forward still needs x from the tile and keeps separate patches (two per CU)
-  __shared__ __attribute__((aligned(16))) float patch[MODE == 0 ? 4 : 1][MODE == 0 ? 1024 : 4];
-  if (MODE == 1) __syncthreads();
-  float* stg = MODE == 0 ? patch[wave] : smem + wave * 1024;
+  // (x is still needed from the tile, so the patches live in a separate region: two workgroups per CU)
+  __shared__ __attribute__((aligned(16))) float patch[4][1024];
+  float* stg = patch[wave];
   const int c4 = (lane & 7) * 4, r8 = lane >> 3;
-  f32x4 csum[TN];  // backward: this lane's share of the column sums of dx
+  // (never read; dropping it lets the scheduler reorder four scalar instructions of gdn_kernel<1, 0>, so it stays
+  // to keep the forward ISA as it was measured)
+  f32x4 csum[TN];
 #pragma unroll
   for (int b = 0; b < TN; ++b) csum[b] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -171,45 +131,17 @@ __global__ __launch_bounds__(256) void gdn_kernel(const GdnParams p) {
       if (pix >= p.P) continue;
       const f32x4 s4 = *reinterpret_cast<const f32x4*>(&stg[rr * 32 + c4]);
       const long off = pix * C + col;
+      const f32x4 n4 = s4 + *reinterpret_cast<const f32x4*>(p.beta + col);
+      const f32x4 x4 = *reinterpret_cast<const f32x4*>(&smem[(wm0 + rr) * LDX + col]);
       f32x4 o;
-      if (MODE == 0) {
-        const f32x4 n4 = s4 + *reinterpret_cast<const f32x4*>(p.beta + col);
-        const f32x4 x4 = *reinterpret_cast<const f32x4*>(&smem[(wm0 + rr) * LDX + col]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
-          o[e] = x4[e] * (inv ? __builtin_amdgcn_sqrtf(n4[e]) : __builtin_amdgcn_rsqf(n4[e]));
-        if (p.out2) *reinterpret_cast<f32x4*>(p.out2 + off) = n4;
-        if (p.res) o += *reinterpret_cast<const f32x4*>(p.res + off);
-      } else {
-        const f32x4 n4 = *reinterpret_cast<const f32x4*>(p.norm + off);
-        const f32x4 g4 = *reinterpret_cast<const f32x4*>(p.g + off);
-        const f32x4 x4 = *reinterpret_cast<const f32x4*>(p.x + off);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float f = inv ? __builtin_amdgcn_sqrtf(n4[e]) : __builtin_amdgcn_rsqf(n4[e]);
-          o[e] = g4[e] * f + 2.0f * x4[e] * s4[e];
-        }
-        csum[b] += o;
-      }
+      for (int e = 0; e < 4; ++e)
+        o[e] = x4[e] * (inv ? __builtin_amdgcn_sqrtf(n4[e]) : __builtin_amdgcn_rsqf(n4[e]));
+      if (p.out2) *reinterpret_cast<f32x4*>(p.out2 + off) = n4;
+      if (p.res) o += *reinterpret_cast<const f32x4*>(p.res + off);
       *reinterpret_cast<f32x4*>(p.out + off) = o;
     }
     __builtin_amdgcn_wave_barrier();
-  }
-  if (MODE == 1 && p.cs_dx) {
-    // lanes with equal lane%8 own the same 4 columns (8 row groups), the two wave rows the same columns:
-    // park the 16 partials per column in LDS and add them in a fixed order
-    __syncthreads();  // every wave is done with its patch
-    float* part = smem;  // [2 wave rows][8 row groups][C]
-#pragma unroll
-    for (int b = 0; b < TN; ++b)
-      *reinterpret_cast<f32x4*>(&part[(((wave >> 1) * 8 + r8) * C) + wn0 + b * 32 + c4]) = csum[b];
-    __syncthreads();
-    if (tid < C) {
-      float a = 0.0f;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) a += part[k * C + tid];
-      p.cs_dx[(long)blockIdx.x * C + tid] = a;
-    }
   }
 }
 
@@ -348,15 +280,14 @@ __global__ __launch_bounds__(256, 2) void gdn_bwd_reg_kernel(const GdnParams p) 
 
 bool gd_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
-template <int MODE>
-int gdn_launch(const GdnParams& p, int C, hipStream_t s) {
+int gdn_fwd_launch(const GdnParams& p, int C, hipStream_t s) {
   const unsigned grid = (unsigned)cdiv64(p.P, GD_BM);
   if (C == 192)
-    hipLaunchKernelGGL((gdn_kernel<3, MODE>), dim3(grid), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((gdn_kernel<3, 0>), dim3(grid), dim3(256), 0, s, p);
   else if (C == 128)
-    hipLaunchKernelGGL((gdn_kernel<2, MODE>), dim3(grid), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((gdn_kernel<2, 0>), dim3(grid), dim3(256), 0, s, p);
   else
-    hipLaunchKernelGGL((gdn_kernel<1, MODE>), dim3(grid), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((gdn_kernel<1, 0>), dim3(grid), dim3(256), 0, s, p);
   return lic_check_launch();
 }
 
@@ -372,7 +303,7 @@ LIC_EXPORT int lic_gdn_fwd(const float* x, const float* gammaT_packed, const flo
     return LIC_ERR_INVALID;
   if (P > 0x7FFFFFFFL * 32) return LIC_ERR_UNSUPPORTED;
   GdnParams p{x, nullptr, nullptr, gammaT_packed, beta_eff, res, y, norm, nullptr, nullptr, (long)P, inverse};
-  return gdn_launch<0>(p, C, (hipStream_t)stream);
+  return gdn_fwd_launch(p, C, (hipStream_t)stream);
 }
 
 LIC_EXPORT int64_t lic_gdn_bwd_partial_rows(int64_t P) { return P <= 0 ? 0 : cdiv64(P, GD_BM); }
@@ -386,8 +317,6 @@ LIC_EXPORT int lic_gdn_bwd(const float* g, const float* x, const float* norm, co
     return LIC_ERR_INVALID;
   if (P > 0x7FFFFFFFL * 32) return LIC_ERR_UNSUPPORTED;
   GdnParams p{x, g, norm, gamma_packed, nullptr, nullptr, dx, t, colsum_t_partial, colsum_dx_partial, (long)P, inverse};
-  const char* e = getenv("LIC_GDN_BWD_REG");
-  if (e && e[0] == '0') return gdn_launch<1>(p, C, (hipStream_t)stream);  // A/B: epilogue re-reads g, x, norm
   const unsigned grid = (unsigned)cdiv64(p.P, GD_BM);
   hipStream_t s = (hipStream_t)stream;
   if (C == 192)

@@ -282,13 +282,8 @@ static int gdn_bwd_bf16_run(const GdnBwdHParams& p, int C, bool rn, hipStream_t 
     // Fewer, longer-lived workgroups let the prefetch work between more tiles: alone the 128^2 launch runs 186 / 167 / 155 /
     // 143 us at 2048 / 1024 / 512 / 256 workgroups -- but the config-3 step does not move (9777-9814 / 9691-9739 / 9732-9763 /
     // 9768-9770 img/s): beside the other stream's launches a 256-workgroup kernel with 100 KB of LDS owns its CUs for its
-    // whole life.  The default stays at the full grid; LIC_GDN_BWD_RN_GRID caps it.
-    static const long cap = [] {
-      const char* e = getenv("LIC_GDN_BWD_RN_GRID");
-      const long v = e ? atol(e) : 2048;
-      return v >= 64 ? v : 2048;
-    }();
-    if ((long)grid > cap) grid = (unsigned)cap;
+    // whole life.  So the grid stays full up to 2048 workgroups.
+    if (grid > 2048) grid = 2048;
   }
 #define LIC_GB(nt, cs, rnv) hipLaunchKernelGGL((gdn_bwd_bf16_kernel<nt, cs, rnv>), dim3(grid), dim3(256), 0, s, p)
   const bool cs = p.cs_t != nullptr;

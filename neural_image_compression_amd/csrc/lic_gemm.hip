@@ -979,14 +979,12 @@ LIC_EXPORT int lic_igemm_fused_gdn_supported(int32_t Cin, int32_t Cout) {
 static long igemm_geo_split(const lic_igemm_desc* d, int Npad, int max_chunks, int epi, bool fuse) {
   const bool simple_epi = (epi == LIC_EPI_NONE || epi == LIC_EPI_LEAKY) && !d->res && !d->out2 && d->prologue < 2;
   const long t_img = (((long)d->Ho * d->Wo + 63) / 64) * ((Npad + 63) / 64);
-  const char* env_split = d->force_split > 0 ? nullptr : getenv("LIC_IGEMM_FORCE_SPLIT");
-  if (!(simple_epi && !fuse && d->workspace && (t_img < 40 || env_split || d->force_split > 1) && d->force_split != 1 &&
+  if (!(simple_epi && !fuse && d->workspace && (t_img < 40 || d->force_split > 1) && d->force_split != 1 &&
         (max_chunks >= 16 || d->force_split > 1)))
     return 1;
   long S = (40 + t_img - 1) / t_img;
   if (S > max_chunks / 8) S = max_chunks / 8;  // at least 8 chunks per split
   if (S > 32) S = 32;
-  if (env_split) S = atoi(env_split);  // tuning aid
   if (d->force_split > 1) S = d->force_split < max_chunks ? d->force_split : max_chunks;
   return S > 1 ? S : 1;
 }
@@ -1116,7 +1114,7 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
   // instead of 64x64 ones.
   int max_chunks0 = 0;
   for (int ph = 0; ph < p.nphase; ++ph) max_chunks0 = p.ntaps[ph] * p.cpt > max_chunks0 ? p.ntaps[ph] * p.cpt : max_chunks0;
-  const long S_geo = (getenv("LIC_IGEMM_SPLIT_AWARE") && getenv("LIC_IGEMM_SPLIT_AWARE")[0] == '0') ? 1 : igemm_geo_split(d, p.Npad, max_chunks0, epi, fuse);
+  const long S_geo = igemm_geo_split(d, p.Npad, max_chunks0, epi, fuse);
   // first pass: shapes whose N tiling comes out full (branch-free MFMA block); second: any
   for (int pass = 0; pass < 2 && !found; ++pass)
     for (int c = 0; c < 6; ++c) {
@@ -1150,13 +1148,6 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
     if (!((fb == 64 || fb == 128) && ft >= 1 && ft <= 3 && p.vec && p.Npad % (64 * ft) == 0)) return LIC_ERR_UNSUPPORTED;
     BM = fb;
     TN = ft;
-  } else if (const char* e = getenv("LIC_IGEMM_FORCE_TILE")) {  // tuning aid: "bm,tn"
-    int fb = 0, ft = 0;
-    if (sscanf(e, "%d,%d", &fb, &ft) == 2 && (fb == 64 || fb == 128) && ft >= 1 && ft <= 3 && p.vec &&
-        p.Npad % (64 * ft) == 0) {
-      BM = fb;
-      TN = ft;
-    }
   }
   // One N tile spanning every channel, 64 rows.  (A 128-row fused variant was built and measured:
   // all workgroups of a launch reach their epilogue together, so the pool is not hidden behind other
@@ -1172,7 +1163,7 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
   p.MT = (int)((maxP + BM - 1) / BM);
   p.pgroup = 0;
   p.porder = 0;
-  if (p.nphase == 4 && p.MT >= 128 && getenv("LIC_IGEMM_NO_PSORT") == nullptr) {
+  if (p.nphase == 4 && p.MT >= 128) {
     int ord[4] = {0, 1, 2, 3};
     for (int i = 0; i < 4; ++i)
       for (int j = i + 1; j < 4; ++j)
@@ -1274,7 +1265,7 @@ LIC_EXPORT int lic_igemm_kernel_name(const lic_igemm_desc* d, char* buf, size_t 
   if (!buf || n == 0) return LIC_ERR_INVALID;
   const bool full = (p.Npad % (64 * TN)) == 0;
   const bool fuse = p.epilogue == LIC_EPI_CONV_GDN || p.epilogue == LIC_EPI_CONV_IGDN;
-  const bool glds = full && p.vec && p.prologue == 0 && getenv("LIC_IGEMM_NO_GLDS") == nullptr;
+  const bool glds = full && p.vec && p.prologue == 0;
   if (!p.vec)
     snprintf(buf, n, "igemm_kernel<64, 1, false, false, false, false>");
   else
@@ -1296,7 +1287,7 @@ LIC_EXPORT int lic_igemm(const lic_igemm_desc* d, lic_stream_t stream) {
   const bool full = (p.Npad % (64 * TN)) == 0;
   // (prologues run on the register-staged loop: a select per operand element in the DMA loop's fragment
   // reads cost every launch ~30 VALU per chunk)
-  const bool glds = full && p.prologue == 0 && getenv("LIC_IGEMM_NO_GLDS") == nullptr;
+  const bool glds = full && p.prologue == 0;
 #define LIC_IGEMM_LAUNCH(bm, tn)                                                        \
   do {                                                                                  \
     if (glds)                                                                           \
@@ -1753,8 +1744,7 @@ static int wg_plan(const lic_wgrad_desc* d, WgPlan* pl) {
   // 192 x 192 tiles (LDS-DMA kernel only) when both channel counts are multiples of 192: half the
   // L2 -> LDS bytes per MFMA of the 64 x 192 tile
   const long chunks16 = ((long)d->B * d->Hs * d->Ws + 255) / 256;  // splits of >= 16 chunks available
-  if (pl->vec && pl->Cm % 192 == 0 && pl->Cn % 192 == 0 && getenv("LIC_WGRAD_NO_GLDS") == nullptr &&
-      getenv("LIC_WGRAD_NO_T33") == nullptr && chunks16 * pl->ntaps >= 512 &&  // else too few workgroups
+  if (pl->vec && pl->Cm % 192 == 0 && pl->Cn % 192 == 0 && chunks16 * pl->ntaps >= 512 &&  // else too few workgroups
       !(d->g_is_row ? d->sq_g : d->sq_p)) {  // (the DMA kernel squares the column operand only)
     pl->TM = 3;
     pl->TN = 3;
@@ -1762,8 +1752,7 @@ static int wg_plan(const lic_wgrad_desc* d, WgPlan* pl) {
   if (d->force_tm || d->force_tn) {  // descriptor override: one of the instantiated shapes
     const int tm = d->force_tm, tn = d->force_tn;
     const bool sq_row = d->g_is_row ? d->sq_g : d->sq_p;
-    const bool t33 = tm == 3 && tn == 3 && pl->Cm % 192 == 0 && pl->Cn % 192 == 0 && !sq_row &&
-                     getenv("LIC_WGRAD_NO_GLDS") == nullptr;
+    const bool t33 = tm == 3 && tn == 3 && pl->Cm % 192 == 0 && pl->Cn % 192 == 0 && !sq_row;
     const bool listed = (tm == 1 && (tn == 1 || tn == 3)) || (tm == 2 && tn >= 1 && tn <= 3);
     if (!pl->vec || !(t33 || listed)) return LIC_ERR_UNSUPPORTED;
     pl->TM = tm;
@@ -1790,7 +1779,6 @@ static int wg_plan(const lic_wgrad_desc* d, WgPlan* pl) {
   // 32 (1.56) 2.55 ms, 40 (1.95) 2.06 ms, 56 (2.73) 2.21 ms, 61 (2.98) 2.08 ms -- so take the fewest
   // rounds that fill >= 90 %, which also keeps the slab reduction small.
   if (pl->TM >= 2) sk = lic_pick_splits(base, resident, max_sk);
-  if (const char* e = getenv("LIC_WGRAD_SPLITS")) sk = atol(e) > 0 ? atol(e) : sk;  // tuning aid
   if (sk > max_sk) sk = max_sk;
   if (d->force_split > 0) sk = d->force_split < pl->nchunks ? d->force_split : pl->nchunks;  // tests: any split
   pl->cps = (int)((pl->nchunks + sk - 1) / sk);
@@ -1817,31 +1805,6 @@ LIC_EXPORT int lic_wgrad_stage(const lic_wgrad_desc* d, void* workspace, size_t 
   if (stage < 0 || stage > 2) return LIC_ERR_INVALID;
   return wgrad_run(d, workspace, workspace_bytes, stage, stream);
 }
-// the MFMA launch only; `job` receives the slab reduction for a later lic_reduce_batch (the workspace must live until then)
-LIC_EXPORT int lic_wgrad_partial(const lic_wgrad_desc* d, void* workspace, size_t workspace_bytes, lic_reduce_job* job,
-                                 lic_stream_t stream) {
-  if (!job) return LIC_ERR_INVALID;
-  WgPlan pl;
-  int rc = wg_plan(d, &pl);
-  if (rc != LIC_OK) return rc;
-  rc = wgrad_run(d, workspace, workspace_bytes, 1, stream);
-  if (rc != LIC_OK) return rc;
-  *job = lic_reduce_job{};
-  job->src = (const float*)workspace;
-  job->dst = d->dst;
-  job->kind = LIC_REDUCE_SLABS;
-  job->splitk = pl.splitk;
-  job->ntaps = pl.ntaps;
-  job->Cm = pl.Cm;
-  job->Cn = pl.Cn;
-  job->Mvalid = pl.Cm;
-  job->Nvalid = pl.Cn;
-  job->sm = d->dst_sm;
-  job->sn = d->dst_sn;
-  job->stap = d->dst_stap;
-  job->scale = d->scale;
-  return LIC_OK;
-}
 LIC_EXPORT int lic_wgrad_kernel_name(const lic_wgrad_desc* d, char* buf, size_t n) {
   WgPlan pl;
   const int rc = wg_plan(d, &pl);
@@ -1850,7 +1813,7 @@ LIC_EXPORT int lic_wgrad_kernel_name(const lic_wgrad_desc* d, char* buf, size_t 
   const bool full = (pl.Cm % (64 * pl.TM) == 0) && (pl.Cn % (64 * pl.TN) == 0);
   if (!pl.vec)
     snprintf(buf, n, "wgrad_kernel<1, 1, false, false>");
-  else if (!(d->g_is_row ? d->sq_g : d->sq_p) && getenv("LIC_WGRAD_NO_GLDS") == nullptr)
+  else if (!(d->g_is_row ? d->sq_g : d->sq_p))
     snprintf(buf, n, "wgrad_glds_kernel<%d, %d, %s, %s>", pl.TM, pl.TN,
              (d->g_is_row ? d->sq_p : d->sq_g) ? "true" : "false", full ? "true" : "false");
   else
@@ -1902,7 +1865,7 @@ static int wgrad_run(const lic_wgrad_desc* d, void* workspace, size_t workspace_
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(pl.MTt * pl.NTt * pl.ntaps * pl.splitk), block(256);
   const bool full = (pl.Cm % (64 * pl.TM) == 0) && (pl.Cn % (64 * pl.TN) == 0);
-  const bool glds = !p.row.sq && getenv("LIC_WGRAD_NO_GLDS") == nullptr;  // (vec is checked below)
+  const bool glds = !p.row.sq;  // (vec is checked below)
   if (stage != 2) {
 #define LIC_WGRAD_LAUNCH(tm, tn)                                                      \
   do {                                                                                \

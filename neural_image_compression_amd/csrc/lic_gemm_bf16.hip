@@ -820,7 +820,7 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
   // variant sums K chunk-major, the others tap-major, and an image's bits must not depend on the batch it is
   // computed in (tests/test_gpu_fullsize.py).  force_bm = 512 forces it on every
   // launch it covers (parity tests on small shapes; other launches keep their automatic tile), any other force_bm
-  // and LIC_BF16_HALO=0 keep the implicit-GEMM tiles.
+  // keeps the implicit-GEMM tiles.
   p.htx = p.hty = 0;
   {
     const bool shape_ok = !p.transposed && d->kh == 5 && d->kw == 5 && d->stride == 2 && d->pad == 2 &&
@@ -829,8 +829,6 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
                           d->Cout == 128 && d->Ho == (d->Hi - 1) / 2 + 1 &&
                           d->Wo == (d->Wi - 1) / 2 + 1 && (long)d->B * d->Hi * d->Wi * d->in_ld < 0x7FFFFFFFL;
     const int htx = (d->Wo + halo::TWD - 1) / halo::TWD, hty = (d->Ho + halo::TH - 1) / halo::TH;
-    const char* e = getenv("LIC_BF16_HALO");  // tuning aid: 0 = never
-    const bool off = e && e[0] == '0';
     // ... and the transposed layers (ConvTranspose2d forward, data gradient of the strided convolution): BM = 513,
     // tiles of 8 x 32 phase pixels (lic_halot_bf16.h)
     const bool shape_t = p.transposed && d->kh == 5 && d->kw == 5 && d->stride == 2 && d->pad == 2 &&
@@ -841,7 +839,7 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
     const int qtx = (d->Wi + halot::TWD - 1) / halot::TWD, qty = (d->Hi + halot::TH - 1) / halot::TH;
     // (at least 16 tiles per image here: a tile is 4 phases = 1024 output pixels, and with 4 tiles per image a
     // batch-32 launch has only 128 of them -- the 32 -> 64 layers measured 88 us against 44 us on the implicit GEMM)
-    if (shape_t && (d->force_bm == 512 || (!d->force_bm && !off && qtx * qty >= 16))) {
+    if (shape_t && (d->force_bm == 512 || (!d->force_bm && qtx * qty >= 16))) {
       BM = 513;
       p.htx = qtx;
       p.hty = qty;
@@ -855,7 +853,7 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
       nwg = p.MT;
       return LIC_OK;
     }
-    if (shape_ok && (d->force_bm == 512 || (!d->force_bm && !off && htx * hty >= 4))) {
+    if (shape_ok && (d->force_bm == 512 || (!d->force_bm && htx * hty >= 4))) {
       BM = 512;
       p.htx = htx;
       p.hty = hty;
@@ -1333,11 +1331,7 @@ static int wgh_plan(const lic_wgrad_desc* d, WgHPlan* pl) {
   const long base = (long)pl->MTt * pl->NTt * pl->ntaps;
   const long max_sk = (pl->nchunks + 15) / 16;  // at least 16 chunks (512 pixels) per split
   // resident workgroups per CU: 2 for the 5-6 sub-tile variants (registers / 72 KiB LDS), else 3
-  long per_cu = pl->TM + pl->TN >= 5 ? 2 : 3;
-  if (const char* e = getenv("LIC_WGRAD_BF16_ROUND")) {   // tuning aid: workgroups per CU one round of splits should fill
-    const long v = atol(e);
-    if (v >= 1 && v <= 3) per_cu = v < per_cu ? v : per_cu;
-  }
+  const long per_cu = pl->TM + pl->TN >= 5 ? 2 : 3;
   const long sk = lic_pick_splits(base, 256L * per_cu, max_sk);
   pl->cps = (int)((pl->nchunks + sk - 1) / sk);
   pl->splitk = (pl->nchunks + pl->cps - 1) / pl->cps;

@@ -232,11 +232,7 @@ LIC_EXPORT int lic_plan_create(void* hip_graph, lic_plan** out) {
         // the batched reduction forked off beside a chain (functional.flush_point) is a filler: it goes to the LAST stream --
         // the callers give the first extra stream a high priority for the chain it carries, and a high-priority launch
         // of ~6000 blocks takes the chip from the other chain's small launches (a 4 MB cast measured 69 us beside it)
-        static const bool filler_last = [] {
-          const char* e = getenv("LIC_PLAN_REDUCE_LAST");
-          return !(e && e[0] == '0');
-        }();
-        if (filler_last && avoid != NS - 1 && p->ops[k].type == hipGraphNodeTypeKernel) {
+        if (avoid != NS - 1 && p->ops[k].type == hipGraphNodeTypeKernel) {
           const char* nm = hipKernelNameRefByPtr(p->ops[k].kp.func, nullptr);
           if (nm && strstr(nm, "reduce_batch_kernel")) pick = NS - 1;
         }

@@ -260,11 +260,7 @@ LIC_EXPORT int64_t lic_prep_plan(lic_prep_job* jobs, int32_t njobs) {
       j.total = (long)j.taps * j.cpt * j.npad * bk;
       const long s_k = j.s_kq, s_n = j.s_nq;
       const bool plain = j.kdiv == 0 && j.ndiv == 0 && j.transform == 0 && j.mask == nullptr;
-      static const bool tiled_h = [] {
-        const char* e = getenv("LIC_PREP_TILED_BF16");
-        return !(e && e[0] == '0');
-      }();
-      if ((!h || (j.kind == LIC_PREP_PACK_BF16 && tiled_h)) && plain && j.s_tap == 1 && j.taps >= 4 && j.taps <= PP_MAXTAPS &&
+      if ((!h || j.kind == LIC_PREP_PACK_BF16) && plain && j.s_tap == 1 && j.taps >= 4 && j.taps <= PP_MAXTAPS &&
           (s_k == j.taps || s_n == j.taps)) {
         j.tiled = (s_k == j.taps) ? 1 : 2;
         j.v4 = (j.K % bk == 0 && j.N % PP_NS == 0 && pp_al16(j.src) && ((s_k == j.taps ? s_n : s_k) % 4 == 0)) ? 1 : 0;

@@ -227,12 +227,6 @@ def _leaky_bwd_bf16(y, dy, slope):
     return dx
 
 
-# the stem's column matrix for its weight gradient built beside the forward pass (functional.AUX_STREAM; 0: in the backward pass)
-EARLY_STEM_COLUMNS = os.environ.get("LIC_EARLY_STEM_COLUMNS", "1") != "0"
-# the bias gradient of a conv -> LeakyReLU layer out of the pass that masks its gradient (LIC_BF16_LEAKY_COLSUM=0: two passes)
-LEAKY_COLSUM = os.environ.get("LIC_BF16_LEAKY_COLSUM", "1") != "0"
-
-
 def _leaky_bwd_colsum_bf16(y, dy, slope, P, Cc, defer=False):
     """(dy through the LeakyReLU's backward, its column sums): _leaky_bwd_bf16 + _colsum_bf16 in one pass, the same bits"""
     lib = L.load()
@@ -310,7 +304,7 @@ def _conv_backward_bf16(xh, weight, g, stride, pad, transposed, in_dtype, tap_ma
     # pass when nothing can read these gradients earlier (functional.can_defer): one batched launch instead of ~40
     dfr = (need_dw or need_db) and F_.can_defer(weight)
     if leaky_y is not None:
-        if need_db and LEAKY_COLSUM and Cout % 8 == 0 and g.is_contiguous() and leaky_y.is_contiguous():
+        if need_db and Cout % 8 == 0 and g.is_contiguous() and leaky_y.is_contiguous():
             g, db = _leaky_bwd_colsum_bf16(leaky_y, g, slope, B * Ho * Wo, Cout, defer=dfr)
             need_db = False
         else:
@@ -523,8 +517,7 @@ def _gamma_eff(gamma, gamma_bound, pedestal):
 def norm_recomputed_bf16(Cc: int) -> bool:
     """True when the GDN backward of this width recomputes the pool norm instead of reading it (lic_gdn_bwd_bf16_recompute):
     the forward pass then does not store it"""
-    return os.environ.get("LIC_BF16_GDN_RECOMPUTE", "1") != "0" and os.environ.get("LIC_BF16_GDN_BWD", "1") != "0" and \
-        bool(L.load().lic_gdn_bwd_bf16_supported(int(Cc)))
+    return bool(L.load().lic_gdn_bwd_bf16_supported(int(Cc)))
 
 
 class _GDNBF16Fn(torch.autograd.Function):
@@ -580,10 +573,7 @@ def _gdn_backward_bf16(xh, norm, beta, gamma, g, inverse, beta_bound, gamma_boun
     t = torch.empty_like(xh)
     dxh = dbeta = dgamma = None
     part_t = part_dx = None
-    if norm is None and not (lib.lic_gdn_bwd_bf16_supported(Cc) and os.environ.get("LIC_BF16_GDN_BWD", "1") != "0"):
-        raise L.LicError("GDN backward without a stored norm needs the recomputing kernel (C in {64, 128}); the forward "
-                         "pass and the backward pass disagree about LIC_BF16_GDN_RECOMPUTE / LIC_BF16_GDN_BWD")
-    if (need_dx or norm is None) and lib.lic_gdn_bwd_bf16_supported(Cc) and os.environ.get("LIC_BF16_GDN_BWD", "1") != "0":
+    if (need_dx or norm is None) and lib.lic_gdn_bwd_bf16_supported(Cc):
         # one sweep: g, x, norm read once, t and dx written (lic_gdn_bf16.hip); the two-launch route below moves
         # 1.8x the bytes
         dxh = torch.empty_like(xh)
@@ -593,7 +583,7 @@ def _gdn_backward_bf16(xh, norm, beta, gamma, g, inverse, beta_bound, gamma_boun
         from . import functional as F_
         if F_.KERNEL_TRACE is not None:
             F_.KERNEL_TRACE.add(f"gdn_bwd_bf16_kernel<{Cc // 32}>")
-        if need_dbeta and os.environ.get("LIC_BF16_GDN_BWD_CS", "1") != "0":
+        if need_dbeta:
             # the kernel also leaves per-workgroup column sums of t and dx: d beta (and the convolution's d bias) need
             # one small reduction over those rows instead of a pass over the two activations
             rows = lib.lic_gdn_bwd_bf16_partial_rows(P)
@@ -728,7 +718,7 @@ class _ConvGDNBF16Fn(torch.autograd.Function):
             norm = torch.empty_like(y) if keep and not norm_recomputed_bf16(Cout) else None
             _igemm_bf16(src, wp, y, bias=bias, epilogue=epi, aux=gT, aux2=beta_e, out2=norm, out3=conv_out, **geo)
         ctx.cols = None
-        if direct and keep and EARLY_STEM_COLUMNS:
+        if direct and keep:
             from . import functional as F_
             aux = F_.AUX_STREAM
             if aux is not None:

@@ -3,7 +3,6 @@
 three one-line repairs that let it run, listed in its docstring."""
 from __future__ import annotations
 
-import os
 
 import torch
 import torch.nn as nn
@@ -76,9 +75,8 @@ class _HyperpriorContextModel(nn.Module):
             y = F_.flush_point(y, self.side_stream())
         # bf16-storage consumers of y (hyper-encoder), y_in (decoder, context model) and z_in (hyper-decoder): their bf16
         # copies come out of the quantisation launches instead of one cast launch per consumer
-        fuse = x.is_cuda and os.environ.get("LIC_QUANT_CASTS", "1") != "0"
-        lat16 = fuse and self.hyper_encoder.precision == "bf16"
-        dec16 = fuse and self.decoder.precision == "bf16"
+        lat16 = x.is_cuda and self.hyper_encoder.precision == "bf16"
+        dec16 = x.is_cuda and self.decoder.precision == "bf16"
         if training:
             if noise is None:
                 # the reference draws rand_like(z) then rand_like(y) (Models.py:57-58); z's shape is known
@@ -101,8 +99,7 @@ class _HyperpriorContextModel(nn.Module):
         z = self.hyper_encoder(y)
         z_in = F_.quantize(z, uz, True, cast_out=lat16) if training else F_.quantize(z, None, False, cast_out=lat16)
         pz_side = None
-        if _fork is not None and x.is_cuda and self.overlap_branches and F_.PLAN_RECORDING and \
-                os.environ.get("LIC_FACTORIZED_SIDE", "1") != "0":
+        if _fork is not None and x.is_cuda and self.overlap_branches and F_.PLAN_RECORDING:
             # the factorised likelihood of z_in depends on nothing else of the latent side: it goes behind the decoder on the
             # second stream (forward: into the stretch where that stream idles while this one finishes the entropy
             # parameters; backward: autograd runs its backward there too, off the longer of the two backward chains).
@@ -152,9 +149,9 @@ class _HyperpriorContextModel(nn.Module):
     # stream beside the latent-side branch (many small launches that cannot fill 256 CUs by
     # themselves), in forward and -- autograd replays each op on its forward stream -- in backward.
     overlap_branches = True
-    # all parameter-derived buffers refreshed by one launch per optimizer step (prep.StepPrep); LIC_STEP_PREP=0
-    # restores the per-layer packing launches for an A/B
-    use_step_prep = os.environ.get("LIC_STEP_PREP", "1") != "0"
+    # all parameter-derived buffers refreshed by one launch per optimizer step (prep.StepPrep); False: the layers
+    # derive them per call
+    use_step_prep = True
 
     def __getstate__(self):
         # the step preparation holds weak references and device job tables of THIS object: a pickled / deep-copied
@@ -175,8 +172,8 @@ class _HyperpriorContextModel(nn.Module):
         if getattr(self, "_side_stream", None) is None:
             # High priority: the decoder chain is the critical path of the overlapped region, the latent-side
             # launches on the main stream fill what it leaves (+0.6 % step, and the big decoder launches keep
-            # ~5 % more of their stand-alone speed).  LIC_SIDE_PRIORITY=0 for the A/B.
-            self._side_stream = torch.cuda.Stream(priority=int(os.environ.get("LIC_SIDE_PRIORITY", "-1")))
+            # ~5 % more of their stand-alone speed).
+            self._side_stream = torch.cuda.Stream(priority=-1)
         return self._side_stream
 
     def forward(self, x: torch.Tensor, training: bool = True, noise=None):

@@ -39,9 +39,9 @@ def test_header_symbols_all_exported_and_bound(lib):
     assert not extra, f"exported but undeclared: {extra}"
 
 
-def test_load_and_version(lib):
+def test_load_and_abi_version(lib):
     L = lib.load()
-    assert L.lic_version() == 3
+    assert L.lic_version() == 4
     assert L.lic_arch() == b"gfx950"
 
 
