@@ -412,6 +412,22 @@ size_t lic_msssim_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
 int lic_msssim(const float* x, const float* y, int32_t B, int32_t C, int32_t H, int32_t W, int64_t sb,
                int64_t sc, int64_t sh, int64_t sw, float data_range, float* out, float* level_out,
                void* workspace, size_t workspace_bytes, lic_stream_t stream);
+/* Gradient of lic_msssim's out[B*C] with respect to x, its first argument (none for y): what training for
+ * MS-SSIM needs.  x, y, the shape, the strides and data_range as in the forward call; level_out and
+ * fwd_workspace (fwd_workspace_bytes >= lic_msssim_workspace_bytes) are that call's outputs, unchanged since:
+ * the pooled planes of scales 1..4 are READ from the forward's workspace, not pooled again.  gout[B*C] =
+ * upstream gradient of out; dx = fp32, element (b,c,h,w) at b*sb + c*sc + h*sh + w*sw like x (every element
+ * is written; dx may not alias x or y).  workspace holds the gradients of the pooled planes.
+ * Five launches, one per scale, coarsest first; each output pixel is a gather over the coefficient maps
+ * around it (no atomics: two runs give the same bits).
+ * DEVIATION, deliberate: where any per-scale term of an image-channel is <= 0 the forward value is 0 and the
+ * derivative of relu(t)^w is undefined there (torch gives inf / NaN); dx of that image-channel is exactly 0.
+ * Other image-channels of the batch are unaffected. */
+size_t lic_msssim_bwd_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int lic_msssim_bwd(const float* x, const float* y, int32_t B, int32_t C, int32_t H, int32_t W, int64_t sb,
+                   int64_t sc, int64_t sh, int64_t sw, float data_range, const float* level_out,
+                   const void* fwd_workspace, size_t fwd_workspace_bytes, const float* gout, float* dx,
+                   void* workspace, size_t workspace_bytes, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).3 -- input pipeline and logging statistics.

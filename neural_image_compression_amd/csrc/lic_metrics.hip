@@ -257,6 +257,262 @@ LIC_EXPORT int lic_msssim(const float* x, const float* y, int32_t B, int32_t C, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Backward of lic_msssim with respect to its first argument: one launch per scale, coarsest first.
+//
+// Per image-channel v = prod_l relu(T_l)^w_l, T_l the mean cs map (l < 4) or mean ssim map (l = 4) of
+// scale l, so dv/d(one pixel of map l) = gout * w_l * v / T_l / (Ho_l * Wo_l) =: s_l.  A map pixel
+// depends on x through mu1 = G*x, e11 = G*(x*x), e12 = G*(x*y) (G: the valid separable 11-tap filter),
+// which gives three coefficient maps a_mu, a_11, a_12 and the input gradient
+// Gt[a_mu] + 2 x Gt[a_11] + y Gt[a_12], Gt the adjoint of G (full-mode correlation, zero outside the
+// map).  The gradient of scale l + 1 enters scale l through the adjoint of the 2x2 average pool.
+//
+// A gather: a workgroup owns a 32x32 INPUT tile.  It stages x / y with a 10-pixel halo on every side
+// (52x52), recomputes the five filtered planes of the 42x42 map pixels that touch the tile (rows, then
+// columns: the forward's order), forms the coefficient maps in LDS, applies the adjoint along rows, then
+// along columns, and adds a quarter of the coarser scale's gradient.  No atomics, fixed summation order.
+// LDS: 2 * 52*52 floats (x, y; later the 3 * 42*42 coefficient maps) + 5 * 52*42 (row-filtered planes;
+// later the 3 * 42*32 row-adjoint planes) = 65,312 B, two workgroups per CU.  No row padding: every
+// access has consecutive lanes on consecutive columns, so a 32-lane group falls on 32 different banks
+// except where it wraps to the next row.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int MB_T = 32;                // input tile side
+constexpr int MB_O = MB_T + MS_HALO;    // map pixels touching the tile, per side (42)
+constexpr int MB_IN = MB_O + MS_HALO;   // staged input side (52)
+constexpr int MB_S_FLOATS = 2 * MB_IN * MB_IN;
+constexpr int MB_H_FLOATS = 5 * MB_IN * MB_O;
+static_assert(3 * MB_O * MB_O <= MB_S_FLOATS, "the coefficient maps reuse the x / y tiles");
+static_assert(3 * MB_O * MB_T <= MB_H_FLOATS, "the row-adjoint planes reuse the row-filtered planes");
+static_assert((MB_S_FLOATS + MB_H_FLOATS) * sizeof(float) <= 65536, "two workgroups per CU");
+static_assert(MB_T * MB_T == 4 * 256, "four input pixels per thread");
+
+// s_l of the comment above for image-channel bc; 0 at every scale when any term is not positive (the
+// forward value is 0 there and its derivative is undefined: the gradient is DEFINED as 0)
+__device__ __forceinline__ float msssim_bwd_scale(const float* level_out, const float* gout, int BC, int bc, int level,
+                                                  float inv_count) {
+  const float wts[MS_LEVELS] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
+  float v = 1.0f, tl = 1.0f;
+  bool dead = false;
+#pragma unroll
+  for (int l = 0; l < MS_LEVELS; ++l) {
+    const float t = level_out[((long)l * BC + bc) * 2 + (l == MS_LEVELS - 1 ? 0 : 1)];
+    dead = dead || !(t > 0.0f);
+    v *= powf(t > 0.0f ? t : 1.0f, wts[l]);
+    if (l == level) tl = t;
+  }
+  return dead ? 0.0f : gout[bc] * wts[level] * (v / tl) * inv_count;
+}
+
+// dp: gradient of this scale's input, element (b, c, h, w) at b*dsb + c*dsc + h*dsh + w*dsw; gnext:
+// gradient of the next (coarser) scale's input, planar [BC][H2][W2], or null at the coarsest scale
+__global__ __launch_bounds__(256) void ssim_scale_bwd_kernel(Plane X, Plane Y, int C, int H, int W, int Ho, int Wo,
+                                                             MsWin win, float C1, float C2, int level,
+                                                             const float* level_out, const float* gout,
+                                                             const float* gnext, int H2, int W2, float* dp, long dsb,
+                                                             long dsc, long dsh, long dsw) {
+  __shared__ float smem[MB_S_FLOATS + MB_H_FLOATS];
+  float(*sx)[MB_IN] = reinterpret_cast<float(*)[MB_IN]>(smem);
+  float(*sy)[MB_IN] = reinterpret_cast<float(*)[MB_IN]>(smem + MB_IN * MB_IN);
+  float(*co)[MB_O][MB_O] = reinterpret_cast<float(*)[MB_O][MB_O]>(smem);  // once the row filter is done
+  float(*hr)[MB_IN][MB_O] = reinterpret_cast<float(*)[MB_IN][MB_O]>(smem + MB_S_FLOATS);
+  float(*ar)[MB_O][MB_T] = reinterpret_cast<float(*)[MB_O][MB_T]>(smem + MB_S_FLOATS);  // once the columns are done
+  const int bc = blockIdx.z, b = bc / C, c = bc - b * C, BC = gridDim.z;
+  const int ix0 = blockIdx.x * MB_T, iy0 = blockIdx.y * MB_T;
+  const float scale = msssim_bwd_scale(level_out, gout, BC, bc, level, 1.0f / ((float)Ho * (float)Wo));
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  if (scale != 0.0f) {  // (uniform over the workgroup: the barriers inside are safe)
+    const float* xp = X.p + b * X.sb + c * X.sc;
+    const float* yp = Y.p + b * Y.sb + c * Y.sc;
+    for (int i = threadIdx.x; i < MB_IN * MB_IN; i += 256) {
+      const int r = i / MB_IN, q = i - r * MB_IN;
+      const int h = iy0 - MS_HALO + r, w = ix0 - MS_HALO + q;
+      float vx = 0.0f, vy = 0.0f;
+      if (h >= 0 && h < H && w >= 0 && w < W) {
+        vx = xp[h * X.sh + w * X.sw];
+        vy = yp[h * Y.sh + w * Y.sw];
+      }
+      sx[r][q] = vx;
+      sy[r][q] = vy;
+    }
+    __syncthreads();
+    // rows: hr[.][r][q] belongs to map column ix0 - 10 + q
+    for (int i = threadIdx.x; i < MB_IN * MB_O; i += 256) {
+      const int r = i / MB_O, q = i - r * MB_O;
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
+#pragma unroll
+      for (int k = 0; k < MS_WIN; ++k) {
+        const float g = win.g[k], vx = sx[r][q + k], vy = sy[r][q + k];
+        a0 += g * vx;
+        a1 += g * vy;
+        a2 += g * (vx * vx);
+        a3 += g * (vy * vy);
+        a4 += g * (vx * vy);
+      }
+      hr[0][r][q] = a0;
+      hr[1][r][q] = a1;
+      hr[2][r][q] = a2;
+      hr[3][r][q] = a3;
+      hr[4][r][q] = a4;
+    }
+    // this thread's four input pixels leave LDS before the coefficient maps overwrite the tiles
+    float px[4], py[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const int i = threadIdx.x + 256 * n, r = i / MB_T, q = i - r * MB_T;
+      px[n] = sx[r + MS_HALO][q + MS_HALO];
+      py[n] = sy[r + MS_HALO][q + MS_HALO];
+    }
+    __syncthreads();
+    // columns, then the three partial derivatives of map pixel (iy0 - 10 + r, ix0 - 10 + q)
+    for (int i = threadIdx.x; i < MB_O * MB_O; i += 256) {
+      const int r = i / MB_O, q = i - r * MB_O;
+      const int oy = iy0 - MS_HALO + r, ox = ix0 - MS_HALO + q;
+      float amu = 0.f, a11 = 0.f, a12 = 0.f;
+      if (oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) {
+        float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+#pragma unroll
+        for (int k = 0; k < MS_WIN; ++k) {
+          const float g = win.g[k];
+          m1 += g * hr[0][r + k][q];
+          m2 += g * hr[1][r + k][q];
+          e11 += g * hr[2][r + k][q];
+          e22 += g * hr[3][r + k][q];
+          e12 += g * hr[4][r + k][q];
+        }
+        const float m11 = m1 * m1, m22 = m2 * m2, m12 = m1 * m2;
+        const float s11 = e11 - m11, s22 = e22 - m22, s12 = e12 - m12;
+        // cs = (2 (e12 - m1 m2) + C2) / ((e11 - m1^2) + (e22 - m2^2) + C2)
+        const float invD = 1.0f / (s11 + s22 + C2);
+        const float cs = (2.0f * s12 + C2) * invD;
+        const float cs_mu = 2.0f * (m1 * cs - m2) * invD, cs_11 = -cs * invD, cs_12 = 2.0f * invD;
+        if (level == MS_LEVELS - 1) {  // ssim = lum * cs, lum = (2 m1 m2 + C1) / (m1^2 + m2^2 + C1)
+          const float invB = 1.0f / (m11 + m22 + C1);
+          const float lum = (2.0f * m12 + C1) * invB;
+          amu = 2.0f * (m2 - lum * m1) * invB * cs + lum * cs_mu;
+          a11 = lum * cs_11;
+          a12 = lum * cs_12;
+        } else {
+          amu = cs_mu;
+          a11 = cs_11;
+          a12 = cs_12;
+        }
+      }
+      co[0][r][q] = amu;
+      co[1][r][q] = a11;
+      co[2][r][q] = a12;
+    }
+    __syncthreads();
+    // adjoint along rows: input column ix0 + q collects map columns ix0 + q - k, k = 0..10
+    for (int i = threadIdx.x; i < MB_O * MB_T; i += 256) {
+      const int r = i / MB_T, q = i - r * MB_T;
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+      for (int k = 0; k < MS_WIN; ++k) {
+        const float g = win.g[k];
+        a0 += g * co[0][r][q + MS_HALO - k];
+        a1 += g * co[1][r][q + MS_HALO - k];
+        a2 += g * co[2][r][q + MS_HALO - k];
+      }
+      ar[0][r][q] = a0;
+      ar[1][r][q] = a1;
+      ar[2][r][q] = a2;
+    }
+    __syncthreads();
+    // adjoint along columns: input row iy0 + r collects map rows iy0 + r - k
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const int i = threadIdx.x + 256 * n, r = i / MB_T, q = i - r * MB_T;
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+      for (int k = 0; k < MS_WIN; ++k) {
+        const float g = win.g[k];
+        a0 += g * ar[0][r + MS_HALO - k][q];
+        a1 += g * ar[1][r + MS_HALO - k][q];
+        a2 += g * ar[2][r + MS_HALO - k][q];
+      }
+      acc[n] = scale * (a0 + 2.0f * px[n] * a1 + py[n] * a2);
+    }
+  }
+  float* dpl = dp + b * dsb + c * dsc;
+  const int ph = H & 1, pw = W & 1;
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int i = threadIdx.x + 256 * n, r = i / MB_T, q = i - r * MB_T;
+    const int h = iy0 + r, w = ix0 + q;
+    if (h >= H || w >= W) continue;
+    float v = acc[n];
+    // adjoint of avgpool2_kernel: input (h, w) lies in the window of pooled pixel ((h + ph) / 2, (w + pw) / 2)
+    if (gnext) v += 0.25f * gnext[((long)bc * H2 + ((h + ph) >> 1)) * W2 + ((w + pw) >> 1)];
+    dpl[h * dsh + w * dsw] = v;
+  }
+}
+
+}  // namespace
+
+LIC_EXPORT size_t lic_msssim_bwd_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
+  MsPlan pl;
+  if (!ms_plan(B, C, H, W, &pl)) return 0;
+  size_t n = 0;
+  for (int l = 1; l < MS_LEVELS; ++l) n += (size_t)B * C * pl.H[l] * pl.W[l];
+  return n * sizeof(float);
+}
+
+LIC_EXPORT int lic_msssim_bwd(const float* x, const float* y, int32_t B, int32_t C, int32_t H, int32_t W, int64_t sb,
+                              int64_t sc, int64_t sh, int64_t sw, float data_range, const float* level_out,
+                              const void* fwd_workspace, size_t fwd_workspace_bytes, const float* gout, float* dx,
+                              void* workspace, size_t workspace_bytes, lic_stream_t stream) {
+  if (!x || !y || !level_out || !fwd_workspace || !gout || !dx || !workspace) return LIC_ERR_INVALID;
+  MsPlan pl;
+  if (!ms_plan(B, C, H, W, &pl)) return LIC_ERR_UNSUPPORTED;
+  if (fwd_workspace_bytes < pl.bytes) return LIC_ERR_WORKSPACE;
+  if (workspace_bytes < lic_msssim_bwd_workspace_bytes(B, C, H, W)) return LIC_ERR_WORKSPACE;
+  if ((long)B * C > 65535) return LIC_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  MsWin win;
+  {  // the window of lic_msssim
+    float sum = 0.0f;
+    for (int i = 0; i < MS_WIN; ++i) {
+      const float d = (float)(i - MS_WIN / 2);
+      win.g[i] = expf(-(d * d) / (2.0f * 1.5f * 1.5f));
+      sum += win.g[i];
+    }
+    for (int i = 0; i < MS_WIN; ++i) win.g[i] /= sum;
+  }
+  const float C1 = (0.01f * data_range) * (0.01f * data_range), C2 = (0.03f * data_range) * (0.03f * data_range);
+  const float* planes = (const float*)fwd_workspace;
+  const int BC = B * C;
+  float* grad[MS_LEVELS + 1];  // gradient of scale l's input: dx, then planar planes in the workspace
+  grad[0] = dx;
+  grad[MS_LEVELS] = nullptr;
+  {
+    float* g = (float*)workspace;
+    for (int l = 1; l < MS_LEVELS; ++l) {
+      grad[l] = g;
+      g += (size_t)BC * pl.H[l] * pl.W[l];
+    }
+  }
+  for (int l = MS_LEVELS - 1; l >= 0; --l) {
+    const int h = pl.H[l], w = pl.W[l];
+    Plane X{x, sb, sc, sh, sw}, Y{y, sb, sc, sh, sw};
+    long dsb = sb, dsc = sc, dsh = sh, dsw = sw;
+    if (l > 0) {
+      const float* px = planes + pl.plane_off[l];
+      X = Plane{px, (long)C * h * w, (long)h * w, (long)w, 1};
+      Y = Plane{px + (size_t)BC * h * w, (long)C * h * w, (long)h * w, (long)w, 1};
+      dsb = (long)C * h * w, dsc = (long)h * w, dsh = w, dsw = 1;
+    }
+    const int h2 = l + 1 < MS_LEVELS ? pl.H[l + 1] : 0, w2 = l + 1 < MS_LEVELS ? pl.W[l + 1] : 0;
+    dim3 grid((unsigned)cdiv64(w, MB_T), (unsigned)cdiv64(h, MB_T), (unsigned)BC);
+    hipLaunchKernelGGL(ssim_scale_bwd_kernel, grid, dim3(256), 0, s, X, Y, C, h, w, h - MS_HALO, w - MS_HALO, win, C1,
+                       C2, l, level_out, gout, (const float*)grad[l + 1], h2, w2, grad[l], dsb, dsc, dsh, dsw);
+    const int rc = lic_check_launch();
+    if (rc != LIC_OK) return rc;
+  }
+  return LIC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // SURVEY 8(f).3 -- input pipeline and logging statistics on the device.
 // ------------------------------------------------------------------------------------------------
 // uint8 NHWC pixels -> fp32 in [0,1]: out = float(v) / 255 (a true division: bit-identical to

@@ -1247,16 +1247,8 @@ def mask_weight_(weight: torch.Tensor, mask: torch.Tensor):
 # ------------------------------------------------------------------------------------------
 # evaluation metric: MS-SSIM as Evaluator.py:38,45 calls pytorch-msssim 0.2.1
 # ------------------------------------------------------------------------------------------
-def ms_ssim(X: torch.Tensor, Y: torch.Tensor, data_range: float = 255.0, size_average: bool = True):
-    """`pytorch_msssim.ms_ssim(X, Y, data_range, size_average)` (default window / weights / K) on the
-    device.  X, Y: [B,C,H,W] fp32 CUDA tensors (any strides), min(H,W) > 160.  Returns the mean over
-    batch and channels, or the per-image channel mean when `size_average=False`.  No gradient."""
-    _require_cuda(X, Y)
-    if X.shape != Y.shape or X.dim() != 4:
-        raise ValueError(f"Input images should have the same 4-d shape, got {tuple(X.shape)} and {tuple(Y.shape)}")
-    B, Cc, H, W = X.shape
-    if min(H, W) <= 160:
-        raise ValueError("Image size should be larger than 160 due to the 4 downsamplings in ms-ssim")
+def _msssim_operands(X, Y):
+    """fp32, detached, with one set of strides for both (lic_msssim takes a single stride quadruple)"""
     Xd = X.detach().float()
     Yd = Y.detach().float()
     if Yd.stride() != Xd.stride():
@@ -1264,12 +1256,87 @@ def ms_ssim(X: torch.Tensor, Y: torch.Tensor, data_range: float = 255.0, size_av
                            and not Xd.is_contiguous() else torch.contiguous_format)
         if Yd.stride() != Xd.stride():
             Xd, Yd = Xd.contiguous(), Yd.contiguous()
+    return Xd, Yd
+
+
+def _msssim_launch(Xd, Yd, data_range):
+    """(out [B,C], level_out [5,B*C,2], workspace, its size): one lic_msssim call"""
+    B, Cc, H, W = Xd.shape
     lib = L.load()
     nbytes = lib.lic_msssim_workspace_bytes(B, Cc, H, W)
-    ws = torch.empty((nbytes + 7) // 8, device=X.device, dtype=torch.float64)
-    out = torch.empty((B, Cc), device=X.device, dtype=torch.float32)
-    levels = torch.empty((5, B * Cc, 2), device=X.device, dtype=torch.float32)
+    ws = torch.empty((nbytes + 7) // 8, device=Xd.device, dtype=torch.float64)
+    out = torch.empty((B, Cc), device=Xd.device, dtype=torch.float32)
+    levels = torch.empty((5, B * Cc, 2), device=Xd.device, dtype=torch.float32)
     sb, sc, sh, sw = Xd.stride()
     L.check(lib.lic_msssim(_ptr(Xd), _ptr(Yd), B, Cc, H, W, sb, sc, sh, sw, float(data_range), _ptr(out),
                            _ptr(levels), _ptr(ws), nbytes, _stream()), "lic_msssim")
+    return out, levels, ws, nbytes
+
+
+def _strides_injective(t: torch.Tensor) -> bool:
+    """no two index tuples of `t` share an address (a gradient written with these strides has no collisions)"""
+    dims = sorted((st, n) for st, n in zip(t.stride(), t.shape) if n > 1)
+    reach = 0
+    for st, n in dims:
+        if st <= reach:
+            return False
+        reach += st * (n - 1)
+    return True
+
+
+class _MsSsimFn(torch.autograd.Function):
+    """ms_ssim with a gradient for its first argument: lic_msssim forward (the same call as the no-grad path, so the
+    same bits), its workspace (pooled planes) and level_out kept for lic_msssim_bwd."""
+
+    @staticmethod
+    def forward(ctx, X, Y, data_range, size_average):
+        Xd, Yd = _msssim_operands(X, Y)
+        if not _strides_injective(Xd):   # (an expanded view: dx with x's strides would collide)
+            Xd, Yd = Xd.contiguous(), Yd.contiguous()
+        out, levels, ws, nbytes = _msssim_launch(Xd, Yd, data_range)
+        ctx.save_for_backward(Xd, Yd, levels, ws)
+        ctx.cfg = (float(data_range), bool(size_average), nbytes, X.dtype)
+        return out.mean() if size_average else out.mean(1)
+
+    @staticmethod
+    def backward(ctx, g):
+        Xd, Yd, levels, ws = ctx.saved_tensors
+        data_range, size_average, nbytes, dtype = ctx.cfg
+        B, Cc, H, W = Xd.shape
+        # the channel (and batch) mean folded into the upstream gradient of out[B*C]: two small elementwise launches,
+        # no device copy (a launch plan cannot read a captured memcpy node back)
+        gout = (g.reshape(-1, 1) * (1.0 / (B * Cc if size_average else Cc))).expand(B, Cc).contiguous()
+        lib = L.load()
+        dx = torch.empty_strided(Xd.shape, Xd.stride(), device=Xd.device, dtype=torch.float32)
+        wbytes = lib.lic_msssim_bwd_workspace_bytes(B, Cc, H, W)
+        bws = torch.empty((wbytes + 3) // 4, device=Xd.device, dtype=torch.float32)
+        sb, sc, sh, sw = Xd.stride()
+        L.check(lib.lic_msssim_bwd(_ptr(Xd), _ptr(Yd), B, Cc, H, W, sb, sc, sh, sw, data_range, _ptr(levels),
+                                   _ptr(ws), nbytes, _ptr(gout), _ptr(dx), _ptr(bws), wbytes, _stream()),
+                "lic_msssim_bwd")
+        return (dx if dtype == torch.float32 else dx.to(dtype)), None, None, None
+
+
+def ms_ssim(X: torch.Tensor, Y: torch.Tensor, data_range: float = 255.0, size_average: bool = True):
+    """`pytorch_msssim.ms_ssim(X, Y, data_range, size_average)` (default window / weights / K) on the
+    device.  X, Y: [B,C,H,W] fp32 CUDA tensors (any strides), min(H,W) > 160.  Returns the mean over
+    batch and channels, or the per-image channel mean when `size_average=False`.
+
+    Differentiable in X (lic_msssim_bwd) when `X.requires_grad` under grad mode; the value is the same bits
+    either way.  No gradient for Y: `Y.requires_grad` raises ValueError (the metric is symmetric: swap the
+    arguments).  Deviation from torch autograd: an image-channel with a non-positive per-scale term has value
+    0 and an undefined derivative (inf / NaN in torch); its gradient here is exactly 0."""
+    _require_cuda(X, Y)
+    if X.shape != Y.shape or X.dim() != 4:
+        raise ValueError(f"Input images should have the same 4-d shape, got {tuple(X.shape)} and {tuple(Y.shape)}")
+    B, Cc, H, W = X.shape
+    if min(H, W) <= 160:
+        raise ValueError("Image size should be larger than 160 due to the 4 downsamplings in ms-ssim")
+    if torch.is_grad_enabled() and Y.requires_grad:
+        raise ValueError("ms_ssim has no gradient for its second argument: pass the tensor that needs one first "
+                         "(the metric is symmetric)")
+    if torch.is_grad_enabled() and X.requires_grad:
+        return _MsSsimFn.apply(X, Y, float(data_range), bool(size_average))
+    Xd, Yd = _msssim_operands(X, Y)
+    out = _msssim_launch(Xd, Yd, data_range)[0]
     return out.mean() if size_average else out.mean(1)

@@ -28,6 +28,41 @@ def rd_loss(model_out: dict, x: torch.Tensor, lambda_rd: float, sync: bool = Tru
     return res
 
 
+def rd_loss_msssim(model_out: dict, x: torch.Tensor, lambda_rd: float, sync: bool = True):
+    """loss = bpp_total + lambda_rd * (1 - ms_ssim(x_hat, x, data_range=1.0)): the MS-SSIM-optimised counterpart of
+    `rd_loss`, same signature, same result keys (the rates, `mse` and `psnr` are still reported) plus `ms_ssim` (mean
+    over batch and channels) and `ms_ssim_per_image` ([B], a device tensor like the other per-image entries).
+
+    The rates, their gradients and the reported mse / psnr come from the fused rd_loss reduction with its lambda
+    set to 0; the distortion term and d loss / d x_hat come from functional.ms_ssim (lic_msssim / lic_msssim_bwd).
+    The fused backward still writes its (all-zero) d mse / d x_hat, which autograd adds to the MS-SSIM gradient: one
+    elementwise launch kept, rather than a second variant of the reduction kernels.
+    sync=False returns 0-d device tensors and does no host synchronisation or device-to-host copy; sync=True does
+    ONE copy for all scalars."""
+    B = x.size(0)
+    x_hat = model_out['x_hat']
+    buf, rate = F_.rd_loss_buffer(model_out['logp_y'], model_out['logp_z'], x_hat, x, 0.0)   # rate = bpp_total
+    ms_img = F_.ms_ssim(x_hat, x, data_range=1.0, size_average=False)
+    ms = ms_img.mean()
+    loss = rate + lambda_rd * (1.0 - ms)
+    det, ms_det = buf.detach(), ms.detach()
+    res = {'loss': loss}
+    if sync:
+        host = torch.cat([det[:9], ms_det.reshape(1)]).tolist()
+        for i, k in enumerate(_KEYS[1:], start=1):
+            res[k] = host[i]
+        res['ms_ssim'] = host[9]
+    else:
+        for i, k in enumerate(_KEYS[1:], start=1):
+            res[k] = det[i]
+        res['ms_ssim'] = ms_det
+        res['_buffer'] = det   # (slot 0 holds bpp_total, not this loss; Trainer reads the slots after it)
+    res['mse_per_image'] = det[16:16 + B]
+    res['psnr_per_image'] = det[16 + B:16 + 2 * B]
+    res['ms_ssim_per_image'] = ms_img.detach()
+    return res
+
+
 def vision_rd_loss(model_out: dict, x: torch.Tensor, lambda_rd: float, gamma: float, frozen_activation=None, V=None):
     """RateDistortionLoss.py:52-121 for `ScalableImageCoding`: loss = bpp_y1 + bpp_y2 + bpp_z + lambda * mse (no 255^2
     factor here, :98), mse = reconstruction MSE (+ gamma * mean((frozen_activation(F_tilde) - V(x_hat))^2) when both
