@@ -15,6 +15,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib as L
+# the queue of reductions a backward pass leaves pending (the bf16 layers'; reductions.py), re-exported
+from .reductions import can_defer, defer, flush_point, flush_reductions  # noqa: F401
 
 PEDESTAL = float(2.0 ** -36)  # compressai reparam_offset ** 2
 LIKELIHOOD_BOUND = 1e-9
@@ -39,6 +41,10 @@ PREPARED = {}
 # a second stream the layers may put work on that nothing downstream waits for soon (models.py sets it around the encoder
 # when the model overlaps its branches; None otherwise): functional_bf16's early stem columns
 AUX_STREAM = None
+# True while plan.StepPlan runs the step it records (and its warm-up steps): stream placements that pay replayed but not
+# host-paced (models.py: the factorised likelihood on the second stream; flush_point, which gains the replayed step ~1 %
+# while for the eager, host-paced step no gain could be measured)
+PLAN_RECORDING = False
 
 
 # ------------------------------------------------------------------------------------------
@@ -57,102 +63,6 @@ def _stream():
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
-
-
-# ------------------------------------------------------------------------------------------
-# reductions left pending until the end of a backward pass (lic_reduce_batch, include/lic.h)
-# ------------------------------------------------------------------------------------------
-# (the bf16 path's; the fp32 path reduces right away: its slab reductions are bandwidth-sized, 60-240 MB each at config
-# 2, and run beside the other stream's kernels -- batched at the end of backward they sat on the critical path)
-DEFER_REDUCTIONS = True
-_PENDING_JOBS = []   # L.ReduceJob of the running backward pass
-_PENDING_KEEP = []   # tensors they name: partial sums, outputs, parameters
-_PENDING_SEEN = set()
-
-
-_PENDING_LATE = []   # tensors of an EARLY flush on another stream: released at the end of the pass
-# True while plan.StepPlan runs the step it records (and its warm-up steps): stream placements that pay replayed but not
-# host-paced (models.py: the factorised likelihood on the second stream; flush_point, which gains the replayed step ~1 %
-# while for the eager, host-paced step no gain could be measured)
-PLAN_RECORDING = False
-
-
-def flush_reductions(early_on=None):
-    """launch every pending reduction (one lic_reduce_batch).  Autograd calls this at the end of a backward pass, on the
-    caller's stream, after that stream has been made to wait for every stream gradients were produced on.
-    `early_on` (a stream; flush_point's backward): launch what is pending so far on THAT stream, after everything queued
-    on the current one -- the batched reduction holds no LDS and few registers, so unlike the weight-gradient launches it
-    does run beside the data-gradient chain that continues on the current stream.  The tensors it reads were allocated on
-    their producers' streams: they are kept until the end of the pass, where the engine orders the caller's stream behind
-    every stream of the pass."""
-    if _PENDING_JOBS:
-        n = len(_PENDING_JOBS)
-        arr = (L.ReduceJob * n)(*_PENDING_JOBS)
-        del _PENDING_JOBS[:]
-        try:
-            if early_on is not None:
-                early_on.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(early_on):
-                    L.check(L.load().lic_reduce_batch(arr, n, _stream()), "lic_reduce_batch")
-                _PENDING_LATE.extend(_PENDING_KEEP)
-            else:
-                L.check(L.load().lic_reduce_batch(arr, n, _stream()), "lic_reduce_batch")
-        finally:
-            del _PENDING_KEEP[:]
-    if early_on is None:
-        del _PENDING_LATE[:]
-        _PENDING_SEEN.clear()
-
-
-class _FlushPointFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, t, stream):
-        ctx.stream = stream
-        return t.view_as(t)
-
-    @staticmethod
-    def backward(ctx, g):
-        if _PENDING_JOBS and ctx.stream is not None:
-            flush_reductions(early_on=ctx.stream)
-        return g, None
-
-
-def flush_point(t: torch.Tensor, stream):
-    """identity; in the backward pass, when the gradient of `t` is complete, the reductions pending so far (those of
-    everything downstream of `t`) are launched on `stream` while the pass continues upstream of `t` on its own stream"""
-    if not (PLAN_RECORDING and DEFER_REDUCTIONS and t.requires_grad and torch.is_grad_enabled() and stream is not None) or \
-            GRAD_VIEWS:
-        return t
-    return _FlushPointFn.apply(t, stream)
-
-
-def can_defer(*params) -> bool:
-    """May the reductions behind the gradients of `params` wait for the end of this backward pass?  Only if nothing
-    reads such a gradient earlier: no data-parallel bucket hooks (they fire per gradient), the parameter has no
-    gradient yet (autograd would ADD to it on arrival) and has not been met before in this pass (two uses of one
-    parameter are summed when the second arrives: everything pending is flushed first), and we are inside a backward
-    pass of the autograd engine (the flush is its final callback).  The pending job names the gradient tensor's memory
-    but holds no reference to the tensor: autograd adopts a returned gradient as `.grad` only while nobody else holds it
-    (otherwise it would COPY it -- before the reduction has run)."""
-    if not DEFER_REDUCTIONS or GRAD_VIEWS:
-        return False
-    ps = [p for p in params if p is not None]
-    if not all(p.is_leaf for p in ps):   # a derived weight: its gradient is READ by the next backward node
-        return False
-    if any(p.grad is not None or id(p) in _PENDING_SEEN for p in ps):
-        flush_reductions()
-        return False
-    try:
-        torch.autograd.Variable._execution_engine.queue_callback(flush_reductions)
-    except RuntimeError:
-        return False
-    _PENDING_SEEN.update(id(p) for p in ps)
-    return True
-
-
-def defer(job, *keep):
-    _PENDING_JOBS.append(job)
-    _PENDING_KEEP.extend(t for t in keep if t is not None)
 
 
 def _require_cuda(*ts):
@@ -199,13 +109,10 @@ def _pack_dense(m: torch.Tensor) -> torch.Tensor:
     return _pack(m, 1, K, N, 0, N, 1)
 
 
-def _pack_conv_weight(w: torch.Tensor, transposed_weight: bool, for_dgrad: bool) -> torch.Tensor:
-    """`transposed_weight`: w is [Cin,Cout,kh,kw] (ConvTranspose2d), else [Cout,Cin,kh,kw].
-    Forward contracts over the layer's input channels, dgrad over its output channels."""
-    hit = prepared(w, "f32.dgrad" if for_dgrad else "f32.fwd")
-    if hit is not None:
-        return hit
-    w = w.contiguous()
+def _conv_weight_layout(w: torch.Tensor, transposed_weight: bool, for_dgrad: bool):
+    """(taps, K, N, s_tap, s_k, s_n) of a contiguous conv weight as a pack source.  `transposed_weight`: w is
+    [Cin,Cout,kh,kw] (ConvTranspose2d), else [Cout,Cin,kh,kw].  Forward contracts over the layer's input channels,
+    dgrad over its output channels."""
     d0, d1, kh, kw = w.shape
     taps = kh * kw
     # element (a, b, tap) of w at a*d1*taps + b*taps + tap
@@ -216,53 +123,45 @@ def _pack_conv_weight(w: torch.Tensor, transposed_weight: bool, for_dgrad: bool)
         cout, cin = d0, d1
         s_co, s_ci = d1 * taps, taps
     if for_dgrad:
-        return _pack(w, taps, cout, cin, 1, s_co, s_ci)
-    return _pack(w, taps, cin, cout, 1, s_ci, s_co)
+        return taps, cout, cin, 1, s_co, s_ci
+    return taps, cin, cout, 1, s_ci, s_co
 
 
-def _igemm(inp, w_packed, out, *, B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, transposed,
-           bias=None, prologue=0, epilogue=L.EPI_NONE, slope=0.01, tap_mask=0, out2=None, aux=None,
-           aux2=None, aux3=None, res=None, in_ld=None, out_ld=None, out3=None):
+def _pack_conv_weight(w: torch.Tensor, transposed_weight: bool, for_dgrad: bool) -> torch.Tensor:
+    hit = prepared(w, "f32.dgrad" if for_dgrad else "f32.fwd")
+    if hit is not None:
+        return hit
+    w = w.contiguous()
+    return _pack(w, *_conv_weight_layout(w, transposed_weight, for_dgrad))
+
+
+def _igemm_desc(inp, w_packed, out, B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, transposed, bias, prologue, epilogue,
+                slope, tap_mask, out2, aux, aux2, aux3, out3, out_ld, res=None, in_ld=None):
+    """the L.IgemmDesc of one lic_igemm / lic_igemm_bf16 launch (row pitches default to the channel counts)"""
     d = L.IgemmDesc()
     d.in_, d.w, d.bias, d.out, d.out2 = _ptr(inp), _ptr(w_packed), _ptr(bias), _ptr(out), _ptr(out2)
-    d.aux, d.aux2, d.aux3, d.res = _ptr(aux), _ptr(aux2), _ptr(aux3), _ptr(res)
+    d.aux, d.aux2, d.aux3, d.res, d.out3 = _ptr(aux), _ptr(aux2), _ptr(aux3), _ptr(res), _ptr(out3)
     d.in_ld = Cin if in_ld is None else in_ld
     d.out_ld = Cout if out_ld is None else out_ld
     d.out2_ld = d.aux_ld = d.aux2_ld = d.aux3_ld = d.res_ld = d.out3_ld = Cout
-    d.out3 = _ptr(out3)
     d.B, d.Hi, d.Wi, d.Cin, d.Ho, d.Wo, d.Cout = B, Hi, Wi, Cin, Ho, Wo, Cout
     d.kh, d.kw, d.stride, d.pad = kh, kw, stride, pad
     d.transposed, d.prologue, d.epilogue = int(transposed), prologue, epilogue
     d.tap_mask, d.slope = tap_mask, slope
-    lib = L.load()
-    ws = None
-    fused = epilogue in (L.EPI_CONV_GDN, L.EPI_CONV_IGDN)
-    if FORCE_IGEMM is not None:
-        d.force_bm, d.force_tn, d.force_split = FORCE_IGEMM[:3]
-    if KERNEL_TRACE is not None:
-        KERNEL_TRACE.add(_kernel_name(lib.lic_igemm_kernel_name, d))
-    if Ho * Wo <= 1024 and out2 is None and res is None:  # latent-side layers: allow split-K
-        nbytes = lib.lic_igemm_workspace_bytes(C.byref(d))
-        if nbytes:
-            ws = torch.empty(nbytes // 4, device=inp.device, dtype=torch.float32)
-            d.workspace, d.workspace_bytes = _ptr(ws), nbytes
-    if PROFILE is None or 2.0 * B * Ho * Wo * Cout * Cin * kh * kw < PROFILE_MIN_FLOP:
-        L.check(lib.lic_igemm(C.byref(d), _stream()), "lic_igemm")
-        return
-    bm, bn, macs = C.c_int32(0), C.c_int32(0), C.c_int64(0)
-    lib.lic_igemm_plan(C.byref(d), C.byref(bm), C.byref(bn), C.byref(macs))
-    nm = C.create_string_buffer(96)
-    lib.lic_igemm_kernel_name(C.byref(d), nm, 96)  # as rocprofv3 prints it
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    L.check(lib.lic_igemm(C.byref(d), _stream()), "lic_igemm")
-    e1.record()
-    act_bytes = 4 * (B * Hi * Wi * Cin + B * Ho * Wo * Cout)
-    flops = 2 * macs.value
-    if fused:  # conv + the channel pool of the GDN that follows it
-        flops += 2 * B * Ho * Wo * Cout * Cout
-        act_bytes += 4 * 2 * B * Ho * Wo * Cout
-    PROFILE.append((nm.value.decode(), flops, act_bytes, e0, e1))
+    return d
+
+
+def _wgrad_desc(p, g, dst, B, Hs, Ws, Cp, Hl, Wl, Cg, kh, kw, stride, pad, g_is_row, dst_sm, dst_sn, dst_stap, sq_p, sq_g,
+                scale):
+    """the L.WgradDesc of one lic_wgrad / lic_wgrad_bf16 launch"""
+    d = L.WgradDesc()
+    d.p, d.g, d.dst = _ptr(p), _ptr(g), _ptr(dst)
+    d.p_ld, d.g_ld = Cp, Cg
+    d.dst_sm, d.dst_sn, d.dst_stap = dst_sm, dst_sn, dst_stap
+    d.B, d.Hs, d.Ws, d.Cp, d.Hl, d.Wl, d.Cg = B, Hs, Ws, Cp, Hl, Wl, Cg
+    d.kh, d.kw, d.stride, d.pad = kh, kw, stride, pad
+    d.g_is_row, d.sq_p, d.sq_g, d.scale = int(g_is_row), sq_p, sq_g, scale
+    return d
 
 
 def _kernel_name(fn, d) -> str:
@@ -271,46 +170,81 @@ def _kernel_name(fn, d) -> str:
     return nm.value.decode()
 
 
-def _timed(name, flops, act_bytes, launch):
-    """run `launch()`; bracket it with HIP events when bench.py's PROFILE list is active"""
+def _trace(name):
+    """add a kernel variant's rocprofv3 name to KERNEL_TRACE when a test has set it; `name`: the string, or a callable
+    evaluated only then"""
+    if KERNEL_TRACE is not None:
+        KERNEL_TRACE.add(name() if callable(name) else name)
+
+
+def _timed(name, flops, act_bytes, launch, staged=None):
+    """run `launch()`; when bench.py's PROFILE list is active and the launch has at least PROFILE_MIN_FLOP `flops`, bracket
+    it with HIP events and append its row.  `name` may be a callable, evaluated only for a bracketed launch (the plain
+    path builds no name and asks the library for no plan): it returns the name, or the whole (name, FLOP, bytes) of the
+    row where the exact figures differ from `flops` or are not needed otherwise.  `staged`: what a bracketed launch runs
+    instead of `launch` -- staged(1) between the events, staged(2) behind the second."""
     if PROFILE is None or flops < PROFILE_MIN_FLOP:
         launch()
         return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    launch()
-    e1.record()
-    PROFILE.append((name, flops, act_bytes, e0, e1))
+    if staged is None:
+        launch()
+        e1.record()
+    else:
+        staged(1)
+        e1.record()
+        staged(2)
+    if callable(name):
+        name = name()
+    PROFILE.append((name, flops, act_bytes, e0, e1) if isinstance(name, str) else (*name, e0, e1))
+
+
+def _igemm(inp, w_packed, out, *, B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, transposed,
+           bias=None, prologue=0, epilogue=L.EPI_NONE, slope=0.01, tap_mask=0, out2=None, aux=None,
+           aux2=None, aux3=None, res=None, in_ld=None, out_ld=None, out3=None):
+    d = _igemm_desc(inp, w_packed, out, B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, transposed, bias, prologue,
+                    epilogue, slope, tap_mask, out2, aux, aux2, aux3, out3, out_ld, res, in_ld)
+    lib = L.load()
+    if FORCE_IGEMM is not None:
+        d.force_bm, d.force_tn, d.force_split = FORCE_IGEMM[:3]
+    _trace(lambda: _kernel_name(lib.lic_igemm_kernel_name, d))
+    if Ho * Wo <= 1024 and out2 is None and res is None:  # latent-side layers: allow split-K
+        nbytes = lib.lic_igemm_workspace_bytes(C.byref(d))
+        if nbytes:
+            ws = torch.empty(nbytes // 4, device=inp.device, dtype=torch.float32)
+            d.workspace, d.workspace_bytes = _ptr(ws), nbytes
+
+    def row():
+        bm, bn, macs = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        lib.lic_igemm_plan(C.byref(d), C.byref(bm), C.byref(bn), C.byref(macs))   # (the live taps only)
+        flops, act_bytes = 2 * macs.value, 4 * (B * Hi * Wi * Cin + B * Ho * Wo * Cout)
+        if epilogue in (L.EPI_CONV_GDN, L.EPI_CONV_IGDN):  # conv + the channel pool of the GDN that follows it
+            flops += 2 * B * Ho * Wo * Cout * Cout
+            act_bytes += 4 * 2 * B * Ho * Wo * Cout
+        return _kernel_name(lib.lic_igemm_kernel_name, d), flops, act_bytes   # (the name as rocprofv3 prints it)
+    _timed(row, 2.0 * B * Ho * Wo * Cout * Cin * kh * kw, None,
+           lambda: L.check(lib.lic_igemm(C.byref(d), _stream()), "lic_igemm"))
 
 
 def _wgrad(p, g, dst, *, B, Hs, Ws, Cp, Hl, Wl, Cg, kh, kw, stride, pad, g_is_row, dst_sm, dst_sn,
            dst_stap, sq_p=0, sq_g=0, scale=1.0):
-    d = L.WgradDesc()
-    d.p, d.g, d.dst = _ptr(p), _ptr(g), _ptr(dst)
-    d.p_ld, d.g_ld = Cp, Cg
-    d.dst_sm, d.dst_sn, d.dst_stap = dst_sm, dst_sn, dst_stap
-    d.B, d.Hs, d.Ws, d.Cp, d.Hl, d.Wl, d.Cg = B, Hs, Ws, Cp, Hl, Wl, Cg
-    d.kh, d.kw, d.stride, d.pad = kh, kw, stride, pad
-    d.g_is_row, d.sq_p, d.sq_g, d.scale = int(g_is_row), sq_p, sq_g, scale
+    d = _wgrad_desc(p, g, dst, B, Hs, Ws, Cp, Hl, Wl, Cg, kh, kw, stride, pad, g_is_row, dst_sm, dst_sn, dst_stap, sq_p,
+                    sq_g, scale)
     lib = L.load()
     if FORCE_WGRAD is not None:
         d.force_tm, d.force_tn, d.force_split = FORCE_WGRAD
-    if KERNEL_TRACE is not None:
-        KERNEL_TRACE.add(_kernel_name(lib.lic_wgrad_kernel_name, d))
+    _trace(lambda: _kernel_name(lib.lic_wgrad_kernel_name, d))
     nbytes = lib.lic_wgrad_workspace_bytes(C.byref(d))
     ws = torch.empty((max(nbytes, 4) + 3) // 4, device=p.device, dtype=torch.float32)
-    if PROFILE is None or 2.0 * B * Hs * Ws * kh * kw * Cp * Cg < PROFILE_MIN_FLOP:
-        L.check(lib.lic_wgrad(C.byref(d), _ptr(ws), nbytes, _stream()), "lic_wgrad")
-        return
-    nm = C.create_string_buffer(96)
-    lib.lic_wgrad_kernel_name(C.byref(d), nm, 96)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()  # the MFMA kernel alone; the slab reduction runs after the second event
-    L.check(lib.lic_wgrad_stage(C.byref(d), _ptr(ws), nbytes, 1, _stream()), "lic_wgrad_stage")
-    e1.record()
-    L.check(lib.lic_wgrad_stage(C.byref(d), _ptr(ws), nbytes, 2, _stream()), "lic_wgrad_stage")
-    flops = 2 * B * Hs * Ws * kh * kw * Cp * Cg
-    PROFILE.append((nm.value.decode(), flops, 4 * (B * Hs * Ws * Cp + B * Hl * Wl * Cg), e0, e1))
+
+    def stage(k):
+        L.check(lib.lic_wgrad_stage(C.byref(d), _ptr(ws), nbytes, k, _stream()), "lic_wgrad_stage")
+    # bracketed: the MFMA kernel alone; the slab reduction runs after the second event
+    _timed(lambda: _kernel_name(lib.lic_wgrad_kernel_name, d), 2 * B * Hs * Ws * kh * kw * Cp * Cg,
+           4 * (B * Hs * Ws * Cp + B * Hl * Wl * Cg),
+           lambda: L.check(lib.lic_wgrad(C.byref(d), _ptr(ws), nbytes, _stream()), "lic_wgrad"),
+           staged=stage)
 
 
 def _colsum(t2d: torch.Tensor, P: int, Cc: int, scale: float = 1.0) -> torch.Tensor:
@@ -418,8 +352,8 @@ class _ConvFn(torch.autograd.Function):
         g = _nhwc(gy)
         if leaky:
             g = _leaky_bwd(yh, g, slope)
-        elif hasattr(gy, "_lic_colsum_partial") and not has_res:
-            g._lic_colsum_partial = gy._lic_colsum_partial
+        elif not has_res:
+            _carry_partial(gy, g)
         dx, dw, db = _conv_backward(xh, weight, g, stride, pad, transposed, tap_mask,
                                     ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                     has_bias and ctx.needs_input_grad[2])
@@ -451,6 +385,14 @@ def _conv_backward(xh, weight, g, stride, pad, transposed, tap_mask, need_dx, ne
     if need_db:
         db = _bias_grad(g, B * Ho * Wo, Cout)
     return dx, dw, db
+
+
+def _carry_partial(src, dst):
+    """hand the GDN backward's partial column sums of a gradient (`_lic_colsum_partial`, see _gdn_backward) on from the
+    handle `src` to the handle `dst` of the same values"""
+    part = getattr(src, "_lic_colsum_partial", None)
+    if part is not None:
+        dst._lic_colsum_partial = part
 
 
 def _bias_grad(g, P, Cout):
@@ -609,8 +551,8 @@ class _ImageConvFn(torch.autograd.Function):
         g = _nhwc(gy)
         if leaky:
             g = _leaky_bwd(yh, g, slope)
-        elif hasattr(gy, "_lic_colsum_partial"):
-            g._lic_colsum_partial = gy._lic_colsum_partial
+        else:
+            _carry_partial(gy, g)
         dx, dw, db = _image_conv_backward(col, weight, g, stride, pad, in_shape, ctx.needs_input_grad[0],
                                           ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2])
         return dx, dw, db, None, None, None, None
@@ -764,8 +706,7 @@ class _GDNFn(torch.autograd.Function):
         resh = None if res is None else _nhwc(res)
         P = B * H * W
         if lib.lic_gdn_supported(Cc):
-            if KERNEL_TRACE is not None:
-                KERNEL_TRACE.add(f"gdn_kernel<{Cc // 64}, {int(inverse)}>")
+            _trace(lambda: f"gdn_kernel<{Cc // 64}, {int(inverse)}>")
             _timed(f"gdn_kernel<{Cc // 64}, 0>", 2 * P * Cc * Cc, 4 * 3 * P * Cc,
                    lambda: L.check(lib.lic_gdn_fwd(_ptr(xh), _ptr(gT), _ptr(beta_e), _ptr(resh), _ptr(out), _ptr(norm),
                                                    P, Cc, int(inverse), _stream()), "lic_gdn_fwd"))
@@ -785,8 +726,8 @@ class _GDNFn(torch.autograd.Function):
                                            gamma_bound, pedestal, *ctx.needs_input_grad[:3])
         dres = gy if has_res else None
         dx = None if dxh is None else _nchw_view(dxh)
-        if dx is not None and hasattr(dxh, "_lic_colsum_partial"):
-            dx._lic_colsum_partial = dxh._lic_colsum_partial  # rides along to the producing conv's backward
+        if dx is not None:
+            _carry_partial(dxh, dx)  # rides along to the producing conv's backward
         return dx, dbeta, dgamma, None, None, None, None, dres, None
 
 
@@ -847,8 +788,7 @@ def _gdn_backward(xh, norm, beta, gamma, g, inverse, beta_bound, gamma_bound, pe
         rows = lib.lic_gdn_bwd_partial_rows(P)
         pt = torch.empty((rows, Cc), device=xh.device, dtype=torch.float32)
         pdx = torch.empty((rows, Cc), device=xh.device, dtype=torch.float32)
-        if KERNEL_TRACE is not None:
-            KERNEL_TRACE.add(f"gdn_bwd_kernel<{Cc // 64}, {int(inverse)}>")
+        _trace(lambda: f"gdn_bwd_kernel<{Cc // 64}, {int(inverse)}>")
         _timed(f"gdn_bwd_reg_kernel<{Cc // 64}>", 2 * P * Cc * Cc, 4 * 5 * P * Cc,
                lambda: L.check(lib.lic_gdn_bwd(_ptr(g), _ptr(xh), _ptr(norm), _ptr(gp), _ptr(dxh), _ptr(t), _ptr(pt),
                                                _ptr(pdx), P, Cc, int(inverse), _stream()), "lic_gdn_bwd"))

@@ -14,8 +14,10 @@ import os
 import torch
 
 from . import _lib as L
+from . import functional as F_
 from .functional import (PEDESTAL, _colsum, _nchw_view, _nhwc, _permute3, _ptr, _reparam_bwd2, _stream, conv_out_size,
                          grad_like, prepared)
+from .reductions import _colsum2_bf16, _colsum_bf16, _leaky_bwd_colsum_bf16, _reparam_epilogue, _rows_sum
 
 BF16 = torch.bfloat16
 _NAMES = {}      # geometry -> kernel variant name (bench.py's event brackets)
@@ -55,30 +57,15 @@ def _pack_conv_weight_bf16(w, transposed_weight, for_dgrad):
     if hit is not None:
         return hit
     w = w.contiguous()
-    d0, d1, kh, kw = w.shape
-    taps = kh * kw
-    if transposed_weight:
-        cin, cout, s_ci, s_co = d0, d1, d1 * taps, taps
-    else:
-        cout, cin, s_co, s_ci = d0, d1, d1 * taps, taps
-    if for_dgrad:
-        return _pack_bf16(w, taps, cout, cin, 1, s_co, s_ci)
-    return _pack_bf16(w, taps, cin, cout, 1, s_ci, s_co)
+    return _pack_bf16(w, *F_._conv_weight_layout(w, transposed_weight, for_dgrad))
 
 
 def _igemm_bf16(inp, w_packed, out, *, B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, transposed, bias=None,
                 prologue=0, epilogue=L.EPI_NONE, out2=None, aux=None, aux2=None, aux3=None, slope=0.01, tap_mask=0,
                 out3=None, out_ld=None):
-    d = L.IgemmDesc()
-    d.in_, d.w, d.bias, d.out, d.out2 = _ptr(inp), _ptr(w_packed), _ptr(bias), _ptr(out), _ptr(out2)
-    d.aux, d.aux2, d.aux3, d.res, d.out3 = _ptr(aux), _ptr(aux2), _ptr(aux3), None, _ptr(out3)
-    d.in_ld, d.out_ld = Cin, (Cout if out_ld is None else out_ld)
-    d.out2_ld = d.aux_ld = d.aux2_ld = d.aux3_ld = d.res_ld = d.out3_ld = Cout
-    d.B, d.Hi, d.Wi, d.Cin, d.Ho, d.Wo, d.Cout = B, Hi, Wi, Cin, Ho, Wo, Cout
-    d.kh, d.kw, d.stride, d.pad = kh, kw, stride, pad
-    d.transposed, d.prologue, d.epilogue = int(transposed), prologue, epilogue
-    d.tap_mask, d.slope = tap_mask, slope
-    from . import functional as F_
+    d = F_._igemm_desc(inp, w_packed, out, B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, transposed, bias, prologue,
+                       epilogue, slope, tap_mask, out2, aux, aux2, aux3, out3, out_ld)
+    lib = L.load()
     if F_.FORCE_IGEMM is not None:
         d.force_bm = F_.FORCE_IGEMM[0]  # the N tile follows from the channel count on this path
         d.force_split = F_.FORCE_IGEMM[2]
@@ -89,158 +76,59 @@ def _igemm_bf16(inp, w_packed, out, *, B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, str
         key = (B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, bool(transposed), tap_mask, d.force_split, d.force_bm)
         nbytes = _SPLIT_WS.get(key)
         if nbytes is None:
-            nbytes = _SPLIT_WS[key] = L.load().lic_igemm_bf16_workspace_bytes(C.byref(d))
+            nbytes = _SPLIT_WS[key] = lib.lic_igemm_bf16_workspace_bytes(C.byref(d))
         if nbytes:
             ws = torch.empty((nbytes // 4,), device=out.device, dtype=torch.float32)
             d.workspace, d.workspace_bytes = _ptr(ws), nbytes
-    if F_.KERNEL_TRACE is not None:
-        F_.KERNEL_TRACE.add(F_._kernel_name(L.load().lic_igemm_bf16_kernel_name, d))
-    if F_.PROFILE is None or 2.0 * B * Ho * Wo * Cout * Cin * kh * kw < F_.PROFILE_MIN_FLOP:
-        L.check(L.load().lic_igemm_bf16(C.byref(d), int(out.dtype == torch.float32), _stream()), "lic_igemm_bf16")
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    L.check(L.load().lic_igemm_bf16(C.byref(d), int(out.dtype == torch.float32), _stream()), "lic_igemm_bf16")
-    e1.record()
-    if transposed and stride == 2:  # live taps per output pixel: kh*kw/4 on average
-        macs = B * Ho * Wo * (kh * kw) * Cin * Cout // 4
-    else:
-        macs = B * Ho * Wo * kh * kw * Cin * Cout
-    nkey = (B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, bool(transposed), prologue, epilogue, tap_mask, d.force_bm)
-    name = _NAMES.get(nkey)   # (planning the launch a second time for its name costs as much as the launch)
-    if name is None:
-        name = _NAMES[nkey] = F_._kernel_name(L.load().lic_igemm_bf16_kernel_name, d)
-    F_.PROFILE.append((name, 2 * macs,
-                       2 * B * Hi * Wi * Cin + out.element_size() * B * Ho * Wo * Cout, e0, e1))
+    F_._trace(lambda: F_._kernel_name(lib.lic_igemm_bf16_kernel_name, d))
+
+    def row():
+        if transposed and stride == 2:  # live taps per output pixel: kh*kw/4 on average
+            macs = B * Ho * Wo * (kh * kw) * Cin * Cout // 4
+        else:
+            macs = B * Ho * Wo * kh * kw * Cin * Cout
+        nkey = (B, Hi, Wi, Cin, Ho, Wo, Cout, kh, kw, stride, pad, bool(transposed), prologue, epilogue, tap_mask, d.force_bm)
+        name = _NAMES.get(nkey)   # (planning the launch a second time for its name costs as much as the launch)
+        if name is None:
+            name = _NAMES[nkey] = F_._kernel_name(lib.lic_igemm_bf16_kernel_name, d)
+        return name, 2 * macs, 2 * B * Hi * Wi * Cin + out.element_size() * B * Ho * Wo * Cout
+    F_._timed(row, 2.0 * B * Ho * Wo * Cout * Cin * kh * kw, None,
+              lambda: L.check(lib.lic_igemm_bf16(C.byref(d), int(out.dtype == torch.float32), _stream()), "lic_igemm_bf16"))
 
 
 def _wgrad_bf16(p, g, dst, *, B, Hs, Ws, Cp, Hl, Wl, Cg, kh, kw, stride, pad, g_is_row, dst_sm, dst_sn, dst_stap,
-                sq_g=0, job=None):
+                sq_g=0, job=None, keep=()):
     """`job` (an L.ReduceJob): launch the MFMA kernel only and fill `job` with the slab reduction, for
-    functional.defer (the caller may still set its epilogue / index-map fields); None: reduce right away"""
-    d = L.WgradDesc()
-    d.p, d.g, d.dst = _ptr(p), _ptr(g), _ptr(dst)
-    d.p_ld, d.g_ld = Cp, Cg
-    d.dst_sm, d.dst_sn, d.dst_stap = dst_sm, dst_sn, dst_stap
-    d.B, d.Hs, d.Ws, d.Cp, d.Hl, d.Wl, d.Cg = B, Hs, Ws, Cp, Hl, Wl, Cg
-    d.kh, d.kw, d.stride, d.pad = kh, kw, stride, pad
-    d.g_is_row, d.sq_p, d.sq_g, d.scale = int(g_is_row), 0, sq_g, 1.0
+    reductions.defer (the caller may still set its epilogue / index-map fields; `keep`: further tensors the job will
+    name then); None: reduce right away"""
+    d = F_._wgrad_desc(p, g, dst, B, Hs, Ws, Cp, Hl, Wl, Cg, kh, kw, stride, pad, g_is_row, dst_sm, dst_sn, dst_stap, 0,
+                       sq_g, 1.0)
     lib = L.load()
     nbytes = lib.lic_wgrad_bf16_workspace_bytes(C.byref(d))
     ws = torch.empty((max(nbytes, 4) + 3) // 4, device=p.device, dtype=torch.float32)
-    from . import functional as F_
-    if F_.KERNEL_TRACE is not None:
-        F_.KERNEL_TRACE.add(F_._kernel_name(lib.lic_wgrad_bf16_kernel_name, d))
+    F_._trace(lambda: F_._kernel_name(lib.lic_wgrad_bf16_kernel_name, d))
+
     def launch():
         if job is None:
             L.check(lib.lic_wgrad_bf16(C.byref(d), _ptr(ws), nbytes, _stream()), "lic_wgrad_bf16")
         else:
             L.check(lib.lic_wgrad_bf16_partial(C.byref(d), _ptr(ws), nbytes, C.byref(job), _stream()),
                     "lic_wgrad_bf16_partial")
-            F_.defer(job, ws, p, g)   # (not `dst`: autograd adopts a gradient tensor only if nobody else holds it)
-    if F_.PROFILE is None or 2.0 * B * Hs * Ws * kh * kw * Cp * Cg < F_.PROFILE_MIN_FLOP:
-        launch()
-        return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    launch()
-    e1.record()
-    nkey = ("w", B, Hs, Ws, Cp, Hl, Wl, Cg, kh, kw, stride, pad, bool(g_is_row), sq_g)
-    name = _NAMES.get(nkey)
-    if name is None:
-        name = _NAMES[nkey] = F_._kernel_name(lib.lic_wgrad_bf16_kernel_name, d) + "+reduce"
-    if job is not None:
-        name = name[:-len("+reduce")]
-    F_.PROFILE.append((name, 2 * B * Hs * Ws * kh * kw * Cp * Cg,
-                       2 * (B * Hs * Ws * Cp + B * Hl * Wl * Cg), e0, e1))
+            F_.defer(job, ws, p, g, *keep)   # (not `dst`: autograd adopts a gradient tensor only if nobody else holds it)
 
-
-def _reparam_epilogue(job, param_c, bound):
-    job.epilogue, job.param, job.bound = L.REDUCE_EPI_REPARAM, param_c.data_ptr(), bound
-
-
-def _colsum_bf16(t2d, P, Cc, defer=False, reparam=None):
-    """column sums; `defer`: stage 2 joins the backward pass's batched reduction (functional.defer); `reparam` =
-    (parameter, bound): followed by the GDN re-parametrisation's backward (deferred mode only)"""
-    lib = L.load()
-    nbytes = lib.lic_colsum_bf16_workspace_bytes(P, Cc)
-    ws = torch.empty((nbytes + 3) // 4, device=t2d.device, dtype=torch.float32)
-    out = torch.empty((Cc,), device=t2d.device, dtype=torch.float32)
-    if defer:
-        from . import functional as F_
-        job = L.ReduceJob()
-        L.check(lib.lic_colsum_bf16_partial(_ptr(t2d), Cc, P, Cc, 1.0, _ptr(out), _ptr(ws), nbytes, C.byref(job), _stream()),
-                "lic_colsum_bf16_partial")
-        if reparam is not None:
-            _reparam_epilogue(job, *reparam)
-        F_.defer(job, ws, t2d, reparam[0] if reparam is not None else None)
-        return out
-    L.check(lib.lic_colsum_bf16(_ptr(t2d), Cc, P, Cc, 1.0, _ptr(out), _ptr(ws), nbytes, _stream()),
-            "lic_colsum_bf16")
-    return out
-
-
-def _rows_sum(part, defer=False, reparam=None):
-    """column sums of a small fp32 [rows][C] matrix of partial sums (the per-workgroup rows lic_gdn_bwd_bf16 leaves):
-    pending (`defer`: one COLUMNS job of the pass's batched reduction, optionally with the re-parametrisation's
-    backward) or right away (a one-job lic_reduce_batch)"""
-    from . import functional as F_
-    rows, Cc = part.shape
-    out = torch.empty((Cc,), device=part.device, dtype=torch.float32)
-    job = L.ReduceJob()
-    job.src, job.dst, job.kind, job.splitk, job.Cn, job.scale = part.data_ptr(), out.data_ptr(), L.REDUCE_COLUMNS, rows, Cc, 1.0
-    if not defer:   # the same kernel, now (so that deferring changes no bit)
-        L.check(L.load().lic_reduce_batch(C.byref(job), 1, _stream()), "lic_reduce_batch")
-        return out
-    if reparam is not None:
-        _reparam_epilogue(job, *reparam)
-    F_.defer(job, part, reparam[0] if reparam is not None else None)
-    return out
-
-
-def _colsum2_bf16(a2d, b2d, P, Cc, defer=False, reparam_a=None):
-    """column sums of two bf16 [P][Cc] matrices in one launch pair (`defer` / `reparam_a`: as _colsum_bf16, the
-    re-parametrisation applies to the first matrix's sums)"""
-    lib = L.load()
-    nbytes = 2 * lib.lic_colsum_bf16_workspace_bytes(P, Cc)
-    ws = torch.empty((nbytes + 3) // 4, device=a2d.device, dtype=torch.float32)
-    out = torch.empty((2, Cc), device=a2d.device, dtype=torch.float32)
-    if defer:
-        from . import functional as F_
-        jobs = (L.ReduceJob * 2)()
-        L.check(lib.lic_colsum2_bf16_partial(_ptr(a2d), _ptr(b2d), Cc, P, Cc, 1.0, _ptr(out[0]), _ptr(out[1]), _ptr(ws),
-                                             nbytes, jobs, _stream()), "lic_colsum2_bf16_partial")
-        ja, jb = L.ReduceJob.from_buffer_copy(jobs[0]), L.ReduceJob.from_buffer_copy(jobs[1])
-        if reparam_a is not None:
-            _reparam_epilogue(ja, *reparam_a)
-        F_.defer(ja, ws, a2d, b2d, reparam_a[0] if reparam_a is not None else None)
-        F_.defer(jb)
-        return out[0], out[1]
-    L.check(lib.lic_colsum2_bf16(_ptr(a2d), _ptr(b2d), Cc, P, Cc, 1.0, _ptr(out[0]), _ptr(out[1]), _ptr(ws), nbytes,
-                                 _stream()), "lic_colsum2_bf16")
-    return out[0], out[1]
+    def name():
+        nkey = ("w", B, Hs, Ws, Cp, Hl, Wl, Cg, kh, kw, stride, pad, bool(g_is_row), sq_g)
+        nm = _NAMES.get(nkey)
+        if nm is None:
+            nm = _NAMES[nkey] = F_._kernel_name(lib.lic_wgrad_bf16_kernel_name, d) + "+reduce"
+        return nm if job is None else nm[:-len("+reduce")]
+    F_._timed(name, 2 * B * Hs * Ws * kh * kw * Cp * Cg, 2 * (B * Hs * Ws * Cp + B * Hl * Wl * Cg), launch)
 
 
 def _leaky_bwd_bf16(y, dy, slope):
     dx = torch.empty_like(y)
     L.check(L.load().lic_leaky_bwd_bf16(_ptr(y), _ptr(dy), _ptr(dx), y.numel(), slope, _stream()), "lic_leaky_bwd_bf16")
     return dx
-
-
-def _leaky_bwd_colsum_bf16(y, dy, slope, P, Cc, defer=False):
-    """(dy through the LeakyReLU's backward, its column sums): _leaky_bwd_bf16 + _colsum_bf16 in one pass, the same bits"""
-    lib = L.load()
-    dx = torch.empty_like(y)
-    nbytes = lib.lic_colsum_bf16_workspace_bytes(P, Cc)
-    ws = torch.empty((nbytes + 3) // 4, device=y.device, dtype=torch.float32)
-    out = torch.empty((Cc,), device=y.device, dtype=torch.float32)
-    job = L.ReduceJob() if defer else None
-    L.check(lib.lic_leaky_bwd_colsum_bf16(_ptr(y), _ptr(dy), _ptr(dx), P, Cc, slope, _ptr(out), _ptr(ws), nbytes,
-                                          C.byref(job) if defer else None, _stream()), "lic_leaky_bwd_colsum_bf16")
-    if defer:
-        from . import functional as F_
-        F_.defer(job, ws)
-    return dx, out
 
 
 class _ConvBF16Fn(torch.autograd.Function):
@@ -299,13 +187,12 @@ def _conv_backward_bf16(xh, weight, g, stride, pad, transposed, in_dtype, tap_ma
     kh, kw = weight.shape[2], weight.shape[3]
     taps = kh * kw
     dx = dw = db = None
-    from . import functional as F_
     # the slab reduction of the weight gradient and the second stage of the bias sum wait for the end of the backward
     # pass when nothing can read these gradients earlier (functional.can_defer): one batched launch instead of ~40
     dfr = (need_dw or need_db) and F_.can_defer(weight)
     if leaky_y is not None:
         if need_db and Cout % 8 == 0 and g.is_contiguous() and leaky_y.is_contiguous():
-            g, db = _leaky_bwd_colsum_bf16(leaky_y, g, slope, B * Ho * Wo, Cout, defer=dfr)
+            g, db = _leaky_bwd_colsum_bf16(leaky_y, g, slope, B * Ho * Wo, Cout, dfr=dfr)
             need_db = False
         else:
             g = _leaky_bwd_bf16(leaky_y, g, slope)
@@ -325,7 +212,7 @@ def _conv_backward_bf16(xh, weight, g, stride, pad, transposed, in_dtype, tap_ma
             _wgrad_bf16(g, xh, dw, B=B, Hs=Ho, Ws=Wo, Cp=Cout, Hl=Hi, Wl=Wi, Cg=Cin, kh=kh, kw=kw, stride=stride,
                         pad=pad, g_is_row=True, dst_sm=taps, dst_sn=Cin * taps, dst_stap=1, job=job)
     if need_db:
-        db = _colsum_bf16(g, B * Ho * Wo, Cout, defer=dfr)
+        db = _colsum_bf16(g, B * Ho * Wo, Cout, dfr=dfr)
     return dx, dw, db
 
 
@@ -381,7 +268,6 @@ def _stem_backward_bf16(col, weight, g, Cin, need_dw, need_db):
     _, _, kh, kw = weight.shape
     taps, Kp, P = kh * kw, col.shape[1], B * Ho * Wo
     dw = db = None
-    from . import functional as F_
     dfr = (need_dw or need_db) and F_.can_defer(weight)
     if need_dw:
         dw = grad_like(weight)
@@ -398,7 +284,7 @@ def _stem_backward_bf16(col, weight, g, Cin, need_dw, need_db):
                         g_is_row=False, dst_sm=Cout, dst_sn=1, dst_stap=0)
             _permute3(tmp, dw, (taps, Cin, Cout), (Cin * Cout, Cout, 1), (1, taps, Cin * taps))
     if need_db:
-        db = _colsum_bf16(g, P, Cout, defer=dfr)
+        db = _colsum_bf16(g, P, Cout, dfr=dfr)
     return dw, db
 
 
@@ -429,10 +315,9 @@ class _ImageConvTBF16Fn(torch.autograd.Function):
         direct = _head_direct(Cin, Cout, kh, kw, stride, pad, out_pad)
         if direct:
             # features -> image in one launch, no column matrix (lic_head_bf16.hip)
-            from . import functional as F_
-            if F_.KERNEL_TRACE is not None:
-                F_.KERNEL_TRACE.add(f"head_convt_bf16_kernel<{Cin // 16}>")
-            F_._timed(f"head_convt_bf16_kernel<{Cin // 16}>", 2 * P * Cin * taps * Cout, 2 * P * Cin + 4 * B * Ho * Wo * Cout,
+            name = f"head_convt_bf16_kernel<{Cin // 16}>"
+            F_._trace(name)
+            F_._timed(name, 2 * P * Cin * taps * Cout, 2 * P * Cin + 4 * B * Ho * Wo * Cout,
                       lambda: L.check(lib.lic_head_convt_bf16(_ptr(xh), _ptr(wpk), _ptr(bias), _ptr(out), B, Hi, Wi, Cin,
                                                               _stream()), "lic_head_convt_bf16"))
         else:
@@ -464,9 +349,7 @@ class _ImageConvTBF16Fn(torch.autograd.Function):
                 L.check(lib.lic_pack_stem_weight_bf16(_ptr(weight.contiguous()), _ptr(wp16), Cin, _stream()),
                         "lic_pack_stem_weight_bf16")
             dxh = torch.empty((B, Hi, Wi, Cin), device=g.device, dtype=BF16)
-            from . import functional as F_
-            if F_.KERNEL_TRACE is not None:
-                F_.KERNEL_TRACE.add(f"stem_gdn_bf16_kernel<{Cin // 32}, plain>")
+            F_._trace(lambda: f"stem_gdn_bf16_kernel<{Cin // 32}, plain>")
             L.check(lib.lic_stem_conv_bf16(_ptr(g), _ptr(wp16), None, _ptr(dxh), B, Ho, Wo, Cin, _stream()),
                     "lic_stem_conv_bf16")
             dx = _nchw_view(dxh)
@@ -487,7 +370,6 @@ class _ImageConvTBF16Fn(torch.autograd.Function):
                         Cout=Cin, kh=1, kw=1, stride=1, pad=0, transposed=False)
             dx = _nchw_view(dxh)
         if ctx.needs_input_grad[1]:
-            from . import functional as F_
             dw = grad_like(weight)
             if F_.can_defer(weight):
                 # pending reduction with the column -> (tap, colour) map: column n = tap * Cout + c of the [Cin][Kp] product
@@ -580,9 +462,8 @@ def _gdn_backward_bf16(xh, norm, beta, gamma, g, inverse, beta_bound, gamma_boun
         gp = prepared(gamma, "bf16.gdn_gp")
         if gp is None:
             gp = _pack_bf16(_gamma_eff(gamma, gamma_bound, pedestal), 1, Cc, Cc, 0, Cc, 1, kperm=True)
-        from . import functional as F_
-        if F_.KERNEL_TRACE is not None:
-            F_.KERNEL_TRACE.add(f"gdn_bwd_bf16_kernel<{Cc // 32}>")
+        name = f"gdn_bwd_bf16_kernel<{Cc // 32}>"
+        F_._trace(name)
         if need_dbeta:
             # the kernel also leaves per-workgroup column sums of t and dx: d beta (and the convolution's d bias) need
             # one small reduction over those rows instead of a pass over the two activations
@@ -592,12 +473,12 @@ def _gdn_backward_bf16(xh, norm, beta, gamma, g, inverse, beta_bound, gamma_boun
         if norm is None:
             # the forward pass did not store the pool: it is recomputed in the same sweep (two tensors read instead of three)
             beta_e, gTp = _gdn_operands_bf16(beta, gamma, beta_bound, gamma_bound, pedestal, kperm=True)
-            F_._timed(f"gdn_bwd_bf16_kernel<{Cc // 32}>", 4 * P * Cc * Cc, 8 * P * Cc,
+            F_._timed(name, 4 * P * Cc * Cc, 8 * P * Cc,
                       lambda: L.check(lib.lic_gdn_bwd_bf16_recompute(_ptr(g), _ptr(xh), _ptr(gp), _ptr(gTp), _ptr(beta_e),
                                                                      _ptr(dxh), _ptr(t), _ptr(part_t), _ptr(part_dx), P, Cc,
                                                                      int(inverse), _stream()), "lic_gdn_bwd_bf16_recompute"))
         else:
-            F_._timed(f"gdn_bwd_bf16_kernel<{Cc // 32}>", 2 * P * Cc * Cc, 10 * P * Cc,
+            F_._timed(name, 2 * P * Cc * Cc, 10 * P * Cc,
                       lambda: L.check(lib.lic_gdn_bwd_bf16(_ptr(g), _ptr(xh), _ptr(norm), _ptr(gp), _ptr(dxh), _ptr(t),
                                                            _ptr(part_t), _ptr(part_dx), P, Cc, int(inverse), _stream()),
                                       "lic_gdn_bwd_bf16"))
@@ -613,45 +494,30 @@ def _gdn_backward_bf16(xh, norm, beta, gamma, g, inverse, beta_bound, gamma_boun
                         kh=1, kw=1, stride=1, pad=0, transposed=False,
                         epilogue=L.EPI_IGDN_BWD if inverse else L.EPI_GDN_BWD, aux=g, aux2=xh, aux3=norm)
     dbe = dge = db_conv = None
-    from . import functional as F_
-    if (need_dbeta or need_dgamma) and F_.can_defer(beta if need_dbeta else None, gamma if need_dgamma else None):
-        # pending reductions that end in the re-parametrisation's backward: d-beta, d-gamma (and the convolution's bias
-        # gradient) come out of the backward pass's one batched launch, no lic_gdn_reparam_bwd2 launch here
-        dbeta = dgamma = None
-        if need_dbeta and part_t is not None:
-            dbeta = _rows_sum(part_t, defer=True, reparam=(beta_c, beta_bound))
-            if bias_from_dx:
-                db_conv = _rows_sum(part_dx, defer=True)
-        elif bias_from_dx and need_dbeta and dxh is not None:
-            dbeta, db_conv = _colsum2_bf16(t, dxh, P, Cc, defer=True, reparam_a=(beta_c, beta_bound))
-        elif need_dbeta:
-            dbeta = _colsum_bf16(t, P, Cc, defer=True, reparam=(beta_c, beta_bound))
-        if dbeta is not None:
-            dbeta = dbeta.view(beta_c.shape)
-        if need_dgamma:
-            dgamma = torch.empty_like(gamma_c)
-            job = L.ReduceJob()
-            _wgrad_bf16(t, xh, dgamma, B=1, Hs=1, Ws=P, Cp=Cc, Hl=1, Wl=P, Cg=Cc, kh=1, kw=1, stride=1, pad=0,
-                        g_is_row=False, dst_sm=Cc, dst_sn=1, dst_stap=0, sq_g=1, job=job)
-            _reparam_epilogue(job, gamma_c, gamma_bound)
-            F_._PENDING_KEEP.append(gamma_c)
-        if bias_from_dx:
-            return dxh, dbeta, dgamma, db_conv
-        return dxh, dbeta, dgamma
+    # deferred, the reductions below end in the re-parametrisation's backward: d-beta, d-gamma (and the convolution's bias
+    # gradient) come out of the backward pass's one batched launch, with no lic_gdn_reparam_bwd2 launch here
+    dfr = (need_dbeta or need_dgamma) and F_.can_defer(beta if need_dbeta else None, gamma if need_dgamma else None)
+    reparam = (beta_c, beta_bound) if dfr else None
     if need_dbeta and part_t is not None:
-        dbe = _rows_sum(part_t)
+        dbe = _rows_sum(part_t, dfr, reparam)
         if bias_from_dx:
-            db_conv = _rows_sum(part_dx)
+            db_conv = _rows_sum(part_dx, dfr)
     elif bias_from_dx and need_dbeta and dxh is not None:
-        dbe, db_conv = _colsum2_bf16(t, dxh, P, Cc)
+        dbe, db_conv = _colsum2_bf16(t, dxh, P, Cc, dfr, reparam)
     elif need_dbeta:
-        dbe = _colsum_bf16(t, P, Cc)
+        dbe = _colsum_bf16(t, P, Cc, dfr, reparam)
     if need_dgamma:
         dge = torch.empty_like(gamma_c)
+        job = L.ReduceJob() if dfr else None
         _wgrad_bf16(t, xh, dge, B=1, Hs=1, Ws=P, Cp=Cc, Hl=1, Wl=P, Cg=Cc, kh=1, kw=1, stride=1, pad=0,
-                    g_is_row=False, dst_sm=Cc, dst_sn=1, dst_stap=0, sq_g=1)
-    dbeta, dgamma = _reparam_bwd2(beta_c if need_dbeta else None, dbe, beta_bound,
-                                  gamma_c if need_dgamma else None, dge, gamma_bound)
+                    g_is_row=False, dst_sm=Cc, dst_sn=1, dst_stap=0, sq_g=1, job=job, keep=(gamma_c,))
+        if dfr:
+            _reparam_epilogue(job, gamma_c, gamma_bound)
+    if dfr:   # (the pending jobs write the parameters' gradients themselves)
+        dbeta, dgamma = (None if dbe is None else dbe.view(beta_c.shape)), dge
+    else:
+        dbeta, dgamma = _reparam_bwd2(beta_c if need_dbeta else None, dbe, beta_bound,
+                                      gamma_c if need_dgamma else None, dge, gamma_bound)
     if bias_from_dx:
         return dxh, dbeta, dgamma, db_conv
     return dxh, dbeta, dgamma
@@ -692,11 +558,10 @@ class _ConvGDNBF16Fn(torch.autograd.Function):
             y = torch.empty((B, Ho, Wo, Cout), device=x.device, dtype=BF16)
             conv_out = torch.empty_like(y) if keep else None
             norm = torch.empty_like(y) if keep and not norm_recomputed_bf16(Cout) else None
-            from . import functional as F_
-            if F_.KERNEL_TRACE is not None:
-                F_.KERNEL_TRACE.add(f"stem_gdn_bf16_kernel<{Cout // 32}, {8 if Cout == 192 else 4}>")
+            name = f"stem_gdn_bf16_kernel<{Cout // 32}, {8 if Cout == 192 else 4}>"
+            F_._trace(name)
             Pn = B * Ho * Wo
-            F_._timed(f"stem_gdn_bf16_kernel<{Cout // 32}, {8 if Cout == 192 else 4}>",
+            F_._timed(name,
                       2 * Pn * Cout * (kh * kw * Cin + Cout), 4 * src.numel() + 2 * Pn * Cout * (3 if keep else 1),
                       lambda: L.check(lib.lic_stem_gdn_bf16(_ptr(src), _ptr(wp), _ptr(bias), _ptr(gT), _ptr(beta_e), _ptr(y),
                                                             _ptr(conv_out), _ptr(norm), B, Hi, Wi, Cout, int(inverse),
@@ -719,7 +584,6 @@ class _ConvGDNBF16Fn(torch.autograd.Function):
             _igemm_bf16(src, wp, y, bias=bias, epilogue=epi, aux=gT, aux2=beta_e, out2=norm, out3=conv_out, **geo)
         ctx.cols = None
         if direct and keep:
-            from . import functional as F_
             aux = F_.AUX_STREAM
             if aux is not None:
                 # the image's column matrix (the operand of the stem's weight gradient) depends on the image alone: it is
@@ -766,9 +630,6 @@ class _ConvGDNBF16Fn(torch.autograd.Function):
         return dx, dw, db, dbeta, dgamma, None, None, None, None, None, None, None, None, None
 
 
-from .functional import will_backprop as _will_backprop  # noqa: E402
-
-
 def fused_gdn_supported_bf16(cin: int, cout: int) -> bool:
     return bool(L.load().lic_igemm_bf16_fused_gdn_supported(int(cin), int(cout)))
 
@@ -778,7 +639,7 @@ def conv_gdn_bf16(x, weight, bias, beta, gamma, stride, padding, inverse, beta_b
     """`gdn_bf16(conv2d_bf16(x))` / `gdn_bf16(conv_transpose2d_bf16(x))` in one launch (see _ConvGDNBF16Fn)"""
     return _ConvGDNBF16Fn.apply(x, weight, bias, beta, gamma, stride, padding, output_padding, bool(transposed),
                                 bool(inverse), float(beta_bound), float(gamma_bound), float(pedestal),
-                                _will_backprop(x, weight, bias, beta, gamma))
+                                F_.will_backprop(x, weight, bias, beta, gamma))
 
 
 def conv2d_bf16(x, weight, bias, stride, padding, out_f32=False, leaky=False, slope=0.01, tap_mask=0, out=None):
@@ -800,4 +661,4 @@ def image_conv_transpose2d_bf16(x, weight, bias, stride, padding, output_padding
 
 def gdn_bf16(x, beta, gamma, inverse, beta_bound, gamma_bound, pedestal=PEDESTAL):
     return _GDNBF16Fn.apply(x, beta, gamma, bool(inverse), float(beta_bound), float(gamma_bound), float(pedestal),
-                            _will_backprop(x, beta, gamma))
+                            F_.will_backprop(x, beta, gamma))

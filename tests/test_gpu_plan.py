@@ -183,7 +183,7 @@ def test_trainer_with_step_plan_trains_like_the_eager_trainer(tmp_path):
 
 @pytest.mark.parametrize("precision,M,K", [("bf16", 128, 3)])
 def test_deferred_reductions_change_no_bit(precision, M, K):
-    """the end-of-backward batched reduction (functional.can_defer / lic_reduce_batch) against the launch-by-launch
+    """the end-of-backward batched reduction (reductions.can_defer / lic_reduce_batch) against the launch-by-launch
     reductions: every gradient of a bf16 model step bit for bit -- first gradients, gradients accumulated onto existing ones
     (no deferral there), and a convolution applied twice in one graph (flush before the second use).  The fp32 path
     reduces right away: its backward leaves nothing pending"""
@@ -191,6 +191,7 @@ def test_deferred_reductions_change_no_bit(precision, M, K):
     import neural_image_compression_amd as nic
     from neural_image_compression_amd import functional as F_
     from neural_image_compression_amd import functional_bf16 as FB
+    from neural_image_compression_amd import reductions as R
     dev = torch.device("cuda:0")
     torch.manual_seed(4)
     m = nic.JointAutoregressiveHierarchical(M, K).to(dev)
@@ -199,7 +200,7 @@ def test_deferred_reductions_change_no_bit(precision, M, K):
     noise = (torch.rand(2, M, 2, 2, device=dev), torch.rand(2, M, 8, 8, device=dev))
 
     def grads(defer, passes):
-        F_.DEFER_REDUCTIONS = defer
+        R.DEFER_REDUCTIONS = defer
         for p in m.parameters():
             p.grad = None
         for _ in range(passes):
@@ -212,7 +213,7 @@ def test_deferred_reductions_change_no_bit(precision, M, K):
             ga, gb = grads(True, passes), grads(False, passes)
             for (n, _), a, b in zip(m.named_parameters(), ga, gb):
                 assert torch.equal(a, b), (passes, n, float((a - b).abs().max()))
-        assert not F_._PENDING_JOBS and not F_._PENDING_KEEP
+        assert not R._PENDING_JOBS and not R._PENDING_KEEP
         # one weight, two uses
         w = (torch.randn(128, 128, 3, 3, device=dev) * 0.05).requires_grad_(True)
         b = torch.zeros(128, device=dev, requires_grad=True)
@@ -221,7 +222,7 @@ def test_deferred_reductions_change_no_bit(precision, M, K):
             xin = xin.to(torch.bfloat16)
 
         def twice(defer):
-            F_.DEFER_REDUCTIONS = defer
+            R.DEFER_REDUCTIONS = defer
             w.grad = b.grad = None
             if precision == "bf16":
                 y = FB.conv2d_bf16(FB.conv2d_bf16(xin, w, b, 1, 1), w, b, 1, 1, out_f32=True)
@@ -232,12 +233,12 @@ def test_deferred_reductions_change_no_bit(precision, M, K):
             return w.grad.clone(), b.grad.clone()
         (wa, ba), (wb, bb) = twice(True), twice(False)
         assert torch.equal(wa, wb) and torch.equal(ba, bb)
-        F_.DEFER_REDUCTIONS = True
+        R.DEFER_REDUCTIONS = True
         w32, x32 = w.detach().float().requires_grad_(True), xin.float()
         F_.conv2d(x32, w32, None, 1, 1).square().mean().backward()
-        assert not F_._PENDING_JOBS and w32.grad is not None
+        assert not R._PENDING_JOBS and w32.grad is not None
     finally:
-        F_.DEFER_REDUCTIONS = True
+        R.DEFER_REDUCTIONS = True
 
 
 def test_forward_plan_equals_the_eager_forward():
