@@ -444,6 +444,41 @@ int lic_tensor_stats(const float* x, int64_t n, int32_t nbins, float lo, float h
                      uint64_t* hist, void* workspace, size_t workspace_bytes, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * lic_window -- a window of an image with a rule for what lies outside it: crop and pad as one gather.
+ *   The reference crops once, offline, on the host (preprocess.py:30-32: one fixed 256x256 window per source
+ *   image) and converts every item with ToTensor() (Dataloader.py:23-27, 39-43); a `transform` argument is its
+ *   only way to a random crop.  Here images of any size are windowed on the device:
+ *     out[b, oy, ox, c] = src_b(border(y0 + oy), border(x0 + ox'), c),   ox' = (flags & 1) ? w - 1 - ox : ox
+ *   `out` is [B][h][w][C] contiguous fp32 (16-byte aligned, at most 2^31 - 1 elements): the channels_last
+ *   memory the conv kernels read.  `border`: LIC_WINDOW_ZERO = zeros outside the image, LIC_WINDOW_REPLICATE =
+ *   the coordinate is clamped, LIC_WINDOW_REFLECT = torch's 'reflect' (the edge is not repeated), legal only
+ *   while every overhang is smaller than the source side it reflects about.
+ *   Every coordinate is resolved to an in-range index (or to a literal zero) before any load, so no address
+ *   leaves an image's [src_offset, src_offset + Hs*Ws*C) whatever the window.
+ *   lic_window_u8_to_f32: uint8 images anywhere in `pool` (any byte alignment), one job per output image in a
+ *     device-resident table (8-byte aligned); the value is float(v) / 255, the same single division as
+ *     lic_u8_to_f32, so a window that is the whole image gives lic_u8_to_f32's bits.  The table lives on the
+ *     device, so the library cannot inspect it: Hs, Ws >= 1, offsets inside the pool and the reflect rule are
+ *     the caller's to check before the upload (data.window_jobs does); an illegal reflect overhang is clamped.
+ *   lic_window_f32: one window of a strided fp32 [B, C, Hs, Ws] tensor (element strides >= 0: NCHW-contiguous,
+ *     channels_last or a view), a plain copy.  LIC_ERR_INVALID for an illegal reflect overhang.
+ *   One launch each, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+enum lic_window_border { LIC_WINDOW_ZERO = 0, LIC_WINDOW_REPLICATE = 1, LIC_WINDOW_REFLECT = 2 };
+typedef struct lic_window_job { /* 32 bytes, one per output image */
+  int64_t src_offset;           /* bytes from `pool` to this image's [Hs][Ws][C] uint8 pixels */
+  int32_t Hs, Ws;               /* source image size */
+  int32_t y0, x0;               /* window origin in source coordinates; may be negative */
+  int32_t flags;                /* bit 0: horizontal flip of the WINDOW (applied after the border rule) */
+  int32_t reserved;
+} lic_window_job;
+int lic_window_u8_to_f32(const uint8_t* pool, const lic_window_job* jobs_device, int32_t B, int32_t h, int32_t w,
+                         int32_t C, int32_t border, float* out, lic_stream_t stream);
+int lic_window_f32(const float* src, int64_t sb, int64_t sc, int64_t sh, int64_t sw, int32_t B, int32_t C,
+                   int32_t Hs, int32_t Ws, int32_t y0, int32_t x0, int32_t h, int32_t w, int32_t border, float* out,
+                   lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * lic_prep -- every parameter-derived buffer of a model refreshed by ONE launch per optimizer step.
  *   The reference keeps derived values implicit in ATen (cuDNN/oneDNN repack weights internally; compressai's
  *   GDN recomputes beta/gamma re-parametrisations in every forward, Components.py:11-44; ContextModels.py:19

@@ -12,10 +12,13 @@ EntropyModels.py:192-233) and the serial range coder runs on the host CPU
 prior, so it decodes without context) and `decode_y_with_tables` (decodes y from the tables the encoder
 used -- the coder's inverse).  `ContextCodec`: the full round trip; its decoder rebuilds the tables from
 already-decoded pixels through the masked 5x5 context model, wavefront by wavefront.
+`ContextCodec.compress_image` / `decompress_image` wrap that round trip, for images of any size, in one
+self-describing byte string (`pack_bitstream`: header, per-image lengths and checksums, streams, CRC-32).
 """
 from __future__ import annotations
 
 import ctypes as C
+import struct
 import zlib
 import os
 from typing import Dict
@@ -382,3 +385,104 @@ class ContextCodec:
         y_hat = ypad[:, p:p + h, p:p + w, :].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
         x_hat = m.decoder(y_hat)
         return {"x_hat": x_hat, "y_hat": y_hat, "z_hat": z_hat}
+
+    # ---- self-describing container: one byte string per batch, any image size ---------------------
+    def _family(self) -> int:
+        name = type(self.model).__name__
+        if name not in BITSTREAM_FAMILIES:
+            raise CodecError(f"no bitstream family id for {name}")
+        return BITSTREAM_FAMILIES[name]
+
+    @torch.no_grad()
+    def compress_image(self, x: torch.Tensor, mode: str = "replicate", align: str = "topleft") -> bytes:
+        """x [B,3,H,W] of ANY size -> one byte string that `decompress_image` decodes by itself.  The image is padded
+        to multiples of 64 (`functional.pad_to_multiple`) and the payload is exactly what `compress` produces for
+        the padded tensor; the header (`pack_bitstream`) carries everything the decoder needs to rebuild the
+        shapes and to crop back.  bpp_coded of the result is 8 * len(data) / (B * H * W): header and checksums
+        included, per ORIGINAL pixel."""
+        if x.dim() != 4:
+            raise CodecError("expected a [B,3,H,W] tensor")
+        B, _, H, W = x.shape
+        _, _, top, left = F_.pad_geometry(H, W, 64, align)
+        r = self.compress(F_.pad_to_multiple(x, 64, mode, align))
+        s = r["strings"]
+        head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
+                "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
+        return pack_bitstream(head, s["z"], s["y"], s["y_crc32"])
+
+    @torch.no_grad()
+    def decompress_image(self, data: bytes) -> torch.Tensor:
+        """The inverse of `compress_image`: x_hat [B,3,H,W] (channels_last).  Raises CodecError, before any GPU
+        work, for a bad magic, a truncated buffer, a failing CRC or a header whose family / M / K are not this
+        model's."""
+        head, z_bytes, y_streams, y_crc = unpack_bitstream(data)
+        m = self.model
+        if (head["family"], head["M"], head["K"]) != (self._family(), m.M, m.K):
+            raise CodecError(f"bitstream was written by family {head['family']} with M={head['M']}, K={head['K']}; "
+                             f"this model is family {self._family()} with M={m.M}, K={m.K}")
+        B, H, W, top, left = (head[k] for k in ("B", "H", "W", "top", "left"))
+        Hp, Wp = -(-H // 64) * 64, -(-W // 64) * 64
+        dec = self
+        if (head["z_lo"], head["z_S"], head["y_W"]) != (self.z_lo, self.z_S, self.y_W):
+            dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"])
+        out = dec.decompress({"y": y_streams, "z": z_bytes, "y_crc32": y_crc}, (B, m.M, Hp // 16, Wp // 16),
+                             (B, m.M, Hp // 64, Wp // 64))
+        return F_.crop_window(out["x_hat"], top, left, H, W)
+
+
+# ---------------------------------------------------------------------------------------------
+# Container of ContextCodec.compress_image (host only).  Little endian:
+#   magic b"LICBITS1" | uint32 family (1 = JointAutoregressiveHierarchical, 2 = HierarchicalMixtureResidual)
+#   | uint32 M, K | int32 z_lo | uint32 z_S, y_W, B, H, W, top, left | uint32 z-stream length
+#   | B x (uint32 y-stream length, uint32 CRC-32 of that image's latent symbols, `compress`'s y_crc32)
+#   | z stream | y stream of image 0 .. B-1 | uint32 CRC-32 of every byte before it
+# The padded size is the next multiple of 64 of (H, W); the latent is [B, M, Hp/16, Wp/16], z [B, M, Hp/64, Wp/64].
+# ---------------------------------------------------------------------------------------------
+BITSTREAM_MAGIC = b"LICBITS1"
+BITSTREAM_FAMILIES = {"JointAutoregressiveHierarchical": 1, "HierarchicalMixtureResidual": 2}
+_BITS_HEAD = struct.Struct("<8sIIIiIIIIIIII")
+_BITS_FIELDS = ("family", "M", "K", "z_lo", "z_S", "y_W", "B", "H", "W", "top", "left")
+
+
+def pack_bitstream(head: Dict, z_bytes: bytes, y_streams, y_crc32) -> bytes:
+    """`head`: the _BITS_FIELDS; one y stream and one symbol checksum per image"""
+    if len(y_streams) != head["B"] or len(y_crc32) != head["B"]:
+        raise CodecError("one y stream and one checksum per image expected")
+    parts = [_BITS_HEAD.pack(BITSTREAM_MAGIC, *(int(head[k]) for k in _BITS_FIELDS), len(z_bytes))]
+    parts += [struct.pack("<II", len(s), int(c) & 0xFFFFFFFF) for s, c in zip(y_streams, y_crc32)]
+    parts += [bytes(z_bytes)] + [bytes(s) for s in y_streams]
+    body = b"".join(parts)
+    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+
+
+def unpack_bitstream(data: bytes):
+    """-> (head dict, z_bytes, [y stream per image], [symbol checksum per image]); CodecError for a bad magic, a
+    truncated or over-long buffer, a failing CRC or a header that cannot be right."""
+    data = bytes(data)
+    if len(data) < _BITS_HEAD.size + 4:
+        raise CodecError("bitstream is truncated (shorter than its header)")
+    vals = _BITS_HEAD.unpack_from(data, 0)
+    if vals[0] != BITSTREAM_MAGIC:
+        raise CodecError("not a LICBITS1 bitstream (bad magic)")
+    head = dict(zip(_BITS_FIELDS, vals[1:-1]))
+    z_len, B = vals[-1], head["B"]
+    at = _BITS_HEAD.size
+    if B == 0 or len(data) < at + 8 * B + 4:
+        raise CodecError("bitstream is truncated (per-image table)")
+    table = [struct.unpack_from("<II", data, at + 8 * b) for b in range(B)]
+    at += 8 * B
+    if len(data) != at + z_len + sum(n for n, _ in table) + 4:
+        raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
+    if zlib.crc32(data[:-4]) & 0xFFFFFFFF != struct.unpack_from("<I", data, len(data) - 4)[0]:
+        raise CodecError("bitstream is damaged (CRC-32 mismatch)")
+    if not (head["H"] > 0 and head["W"] > 0 and head["top"] < 64 and head["left"] < 64
+            and head["top"] + head["H"] <= -(-head["H"] // 64) * 64 and head["left"] + head["W"] <= -(-head["W"] // 64) * 64
+            and head["M"] > 0 and head["K"] > 0 and head["z_S"] > 0 and head["y_W"] > 0):
+        raise CodecError("bitstream header is inconsistent")
+    z_bytes = data[at:at + z_len]
+    at += z_len
+    ys = []
+    for n, _ in table:
+        ys.append(data[at:at + n])
+        at += n
+    return head, z_bytes, ys, [c for _, c in table]

@@ -1280,3 +1280,60 @@ def ms_ssim(X: torch.Tensor, Y: torch.Tensor, data_range: float = 255.0, size_av
     Xd, Yd = _msssim_operands(X, Y)
     out = _msssim_launch(Xd, Yd, data_range)[0]
     return out.mean() if size_average else out.mean(1)
+
+
+# ------------------------------------------------------------------------------------------
+# windows of fp32 images: pad to the multiple of 64 the models need, crop back (lic_window_f32)
+# ------------------------------------------------------------------------------------------
+_WINDOW_BORDERS = {"zeros": L.WINDOW_ZERO, "constant": L.WINDOW_ZERO, "replicate": L.WINDOW_REPLICATE,
+                   "reflect": L.WINDOW_REFLECT}
+
+
+def pad_geometry(H: int, W: int, multiple: int = 64, align: str = "topleft"):
+    """(Hp, Wp, top, left): the padded size and where the image sits in it.  'topleft' pads below / right
+    only, 'center' splits the padding (the odd pixel goes below / right)."""
+    if align not in ("topleft", "center"):
+        raise ValueError(f"align must be 'topleft' or 'center', got {align!r}")
+    if multiple <= 0 or H <= 0 or W <= 0:
+        raise ValueError("sizes must be positive")
+    Hp, Wp = -(-H // multiple) * multiple, -(-W // multiple) * multiple
+    top, left = ((Hp - H) // 2, (Wp - W) // 2) if align == "center" else (0, 0)
+    return Hp, Wp, top, left
+
+
+@torch.no_grad()
+def window(x: torch.Tensor, y0: int, x0: int, h: int, w: int, mode: str = "zeros") -> torch.Tensor:
+    """The h x w window of x [B,C,H,W] whose origin is (y0, x0) in x's coordinates (it may overhang; `mode` says
+    what lies outside: 'zeros', 'replicate' or 'reflect' as in torch.nn.functional.pad).  x may be
+    NCHW-contiguous, channels_last or any non-overlapping view: its strides go to the kernel.  Returns a
+    channels_last tensor.  Inference only: no gradient flows through it."""
+    if x.dim() != 4:
+        raise ValueError("expected a [B,C,H,W] tensor")
+    _require_cuda(x)
+    if mode not in _WINDOW_BORDERS:
+        raise ValueError(f"unknown border mode {mode!r}: one of {sorted(_WINDOW_BORDERS)}")
+    B, Cc, H, W = x.shape
+    if h <= 0 or w <= 0:
+        raise ValueError("the window must be non-empty")
+    if any(s < 0 for s in x.stride()):
+        x = x.contiguous()
+    out = torch.empty((B, h, w, Cc), device=x.device, dtype=torch.float32)
+    sb, sc, sh, sw = x.stride()
+    L.check(L.load().lic_window_f32(_ptr(x), sb, sc, sh, sw, B, Cc, H, W, int(y0), int(x0), int(h), int(w),
+                                    _WINDOW_BORDERS[mode], _ptr(out), _stream()), "lic_window_f32")
+    return _nchw_view(out)
+
+
+def pad_to_multiple(x: torch.Tensor, multiple: int = 64, mode: str = "replicate", align: str = "topleft") -> torch.Tensor:
+    """x [B,C,H,W] padded to the next multiple of `multiple` on both sides (`pad_geometry` says where the image
+    sits), channels_last.  One lic_window_f32 launch.  Inference only (no gradient)."""
+    Hp, Wp, top, left = pad_geometry(x.shape[2], x.shape[3], multiple, align)
+    return window(x, -top, -left, Hp, Wp, mode)
+
+
+def crop_window(x: torch.Tensor, top: int, left: int, H: int, W: int) -> torch.Tensor:
+    """x[:, :, top:top+H, left:left+W] as a dense channels_last tensor (the window must lie inside x).
+    One lic_window_f32 launch.  Inference only (no gradient)."""
+    if top < 0 or left < 0 or top + H > x.shape[2] or left + W > x.shape[3]:
+        raise ValueError(f"window ({top}, {left}, {H}, {W}) leaves the {tuple(x.shape[2:])} image")
+    return window(x, top, left, H, W, "zeros")
