@@ -4,29 +4,12 @@
 // the kernels' job is to keep that pipe issuing: K is consumed in 16-deep chunks staged
 // through LDS, the next chunk's global loads are issued before the current chunk's MFMAs, and
 // 3-4 workgroups per CU cover each other's load/store phases.
-#include "lic_common.h"
+#include "lic_conv_plan.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
 thread_local int g_lic_last_hip_error = 0;
-
-// division of 0 <= n < 2^31 by a launch-constant d via multiply-high (host precomputes m, s)
-struct FastDiv {
-  unsigned m, s;
-};
-static FastDiv make_fastdiv(unsigned d) {
-  FastDiv f;
-  if (d == 0) d = 1;
-  unsigned s = 0;
-  while ((1ull << s) < d) ++s;
-  f.s = s;
-  f.m = (unsigned)(((1ull << (31 + s)) + d - 1) / d);
-  return f;
-}
-__device__ __forceinline__ int fdiv(int n, FastDiv f) {
-  return (int)(((unsigned long long)(unsigned)n * f.m) >> (31 + f.s));
-}
 
 // ------------------------------------------------------------------------------------------------
 // igemm: rows = output pixels (gathered from the NHWC input), cols = output channels.
@@ -781,7 +764,6 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   }
 }
 
-static bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // ---- weight packing: dst[tap][chunk][n/32][q][lane][4], zero padded to Npad = lic_npad_f32(N), K to 16.
 // Lane (col li = lane&31, K-half lh = lane>>5) of a wave owns k = lh*8 + q*4 + e of column
@@ -989,14 +971,24 @@ static long igemm_geo_split(const lic_igemm_desc* d, int Npad, int max_chunks, i
   return S > 1 ? S : 1;
 }
 
-// fills the kernel parameter block; returns LIC_OK, or 1 when there is nothing to launch
-static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& TN, long& nwg,
-                         int64_t& live_macs) {
-  if (!d || !d->in || !d->w || !d->out) return LIC_ERR_INVALID;
-  if (d->B <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Cin <= 0 || d->Ho <= 0 || d->Wo <= 0 ||
-      d->Cout <= 0 || d->kh <= 0 || d->kw <= 0)
-    return LIC_ERR_INVALID;
-  if (d->kh * d->kw > 28 || d->stride < 1 || d->stride > 2) return LIC_ERR_UNSUPPORTED;
+// What lic_igemm launches for a descriptor.  status: LIC_OK, 1 when there is nothing to launch, or an error.
+struct IgemmPlan {
+  int status;
+  IgemmParams p;
+  long nwg;
+  int64_t live_macs;
+  // the variant: igemm_kernel<BM, TN, vec, full, fuse, glds>
+  int BM, TN;
+  bool full;  // every N tile is live in all its 64-column pairs: the branch-free MFMA block
+  bool fuse;
+  bool glds;  // both operands by LDS-DMA.  (Prologues run on the register-staged loop: a select per operand element
+              // in the DMA loop's fragment reads cost every launch ~30 VALU per chunk.)
+};
+
+static int igemm_fill(const lic_igemm_desc* d, IgemmPlan& pl) {
+  IgemmParams& p = pl.p;
+  int rc = conv_desc_check(d);
+  if (rc != LIC_OK) return rc;
   if (!aligned16(d->w)) return LIC_ERR_INVALID;
   const int epi = d->epilogue;
   if ((epi == LIC_EPI_MUL_LEAKY_MASK || epi == LIC_EPI_GDN || epi == LIC_EPI_IGDN) && !d->aux)
@@ -1011,7 +1003,7 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
         !aligned16(d->aux2) || !aligned16(d->aux3) || !aligned16(d->out2))
       return LIC_ERR_UNSUPPORTED;
   }
-  const bool fuse = (epi == LIC_EPI_CONV_GDN || epi == LIC_EPI_CONV_IGDN);
+  const bool fuse = pl.fuse = (epi == LIC_EPI_CONV_GDN || epi == LIC_EPI_CONV_IGDN);
   if (fuse) {
     if (!d->aux || !d->aux2 || d->res || d->prologue) return LIC_ERR_INVALID;  // (out2 / out3 may be NULL: inference)
     if (!lic_igemm_fused_gdn_supported(d->Cin, d->Cout)) return LIC_ERR_UNSUPPORTED;
@@ -1063,47 +1055,16 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
       if (!p.vec || !p.vec_out) return LIC_ERR_UNSUPPORTED;
     }
   }
-  const uint32_t mask = d->tap_mask ? d->tap_mask : 0xFFFFFFFFu;
-  p.nphase = (p.transposed && d->stride > 1) ? d->stride * d->stride : 1;
-  long maxP = 0;
-  live_macs = 0;
-  for (int ph = 0; ph < 4; ++ph) {
-    p.ntaps[ph] = 0;
-    p.Hq[ph] = p.Wq[ph] = 0;
-    p.dHW[ph] = p.dW[ph] = make_fastdiv(1);
-  }
-  for (int ph = 0; ph < p.nphase; ++ph) {
-    const int py = (p.nphase > 1) ? ph / d->stride : 0, px = (p.nphase > 1) ? ph % d->stride : 0;
-    const int st = (p.nphase > 1) ? d->stride : 1;
-    p.Hq[ph] = (d->Ho - py + st - 1) / st;
-    p.Wq[ph] = (d->Wo - px + st - 1) / st;
-    if (p.Hq[ph] < 0) p.Hq[ph] = 0;
-    if (p.Wq[ph] < 0) p.Wq[ph] = 0;
-    const long Pp = (long)d->B * p.Hq[ph] * p.Wq[ph];
-    p.dHW[ph] = make_fastdiv((unsigned)(p.Hq[ph] * p.Wq[ph]));
-    p.dW[ph] = make_fastdiv((unsigned)p.Wq[ph]);
-    if (Pp > maxP) maxP = Pp;
-    int n = 0;
-    for (int r = 0; r < d->kh; ++r)
-      for (int s = 0; s < d->kw; ++s) {
-        const int t = r * d->kw + s;
-        if (!((mask >> t) & 1u)) continue;
-        if (p.nphase > 1) {
-          if (((py + d->pad - r) % d->stride) != 0 || ((px + d->pad - s) % d->stride) != 0) continue;
-        }
-        p.taps[ph][n++] = (unsigned char)t;
-      }
-    p.ntaps[ph] = n;
-    live_macs += (int64_t)Pp * n * d->Cin * d->Cout;
-  }
+  const PhaseGeometry g = phase_geometry(d, p.cpt);
+  store_phases(p, g);
+  pl.live_macs = g.live_macs;
+  const long maxP = g.maxP;
   if (maxP <= 0) return 1;
   if (maxP > 0x7FFFFFFFL / 2) return LIC_ERR_UNSUPPORTED;
 
   // Tile selection.  Dead 32-column tiles are skipped by the waves, so every BN wastes the same
   // MFMA work; prefer the widest N tile (activations are gathered once per N tile) as long as
   // the grid keeps >= 512 workgroups, else fall back towards small tiles for parallelism.
-  int max_taps = 0;
-  for (int ph = 0; ph < p.nphase; ++ph) max_taps = p.ntaps[ph] > max_taps ? p.ntaps[ph] : max_taps;
   static const int cand[6][2] = {{128, 3}, {64, 3}, {128, 2}, {64, 2}, {128, 1}, {64, 1}};
   int best = 5;
   long best_wg = -1;
@@ -1112,10 +1073,11 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
   // geometry only -- never on the tile -- so it is known here, and a full-N tile may count its splits as
   // workgroups: the 16x16 latent layers then take 64x192 tiles (activations gathered once per 192 columns)
   // instead of 64x64 ones.
-  int max_chunks0 = 0;
-  for (int ph = 0; ph < p.nphase; ++ph) max_chunks0 = p.ntaps[ph] * p.cpt > max_chunks0 ? p.ntaps[ph] * p.cpt : max_chunks0;
-  const long S_geo = igemm_geo_split(d, p.Npad, max_chunks0, epi, fuse);
-  // first pass: shapes whose N tiling comes out full (branch-free MFMA block); second: any
+  const long S_geo = igemm_geo_split(d, p.Npad, g.max_chunks, epi, fuse);
+  // first pass: shapes whose N tiling comes out full (branch-free MFMA block); second: any.  (The packed weight
+  // pitch is whole 64-column pairs above 32 columns, so the 64-column candidates are always full there and at least as
+  // many workgroups as any other: the second pass only ever picks them for Npad = 32, where nothing wider applies.
+  // Hence the ragged-N variant exists for TN = 1 alone.)
   for (int pass = 0; pass < 2 && !found; ++pass)
     for (int c = 0; c < 6; ++c) {
       const int bm = cand[c][0], tn = cand[c][1];
@@ -1125,7 +1087,7 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
       // (the K = 80 GEMMs of the RGB layers -- 5 chunks, pure streaming -- would be 13 % faster on 128-row tiles,
       // 225 vs 260 us; not taken: 0.3 % of the step, and two HBM-bound launches per step would share the kernel
       // name whose MFMA roofline the benchmark reports)
-      if (bm == 128 && max_taps * p.cpt <= 16) continue;
+      if (bm == 128 && g.max_taps * p.cpt <= 16) continue;
       if (p.Npad < 64 * tn && tn > 1 && p.Npad <= 64 * (tn - 1)) continue;  // wider than the problem
       if (pass == 0 && p.Npad % (64 * tn) != 0) continue;
       long wgs = ((maxP + bm - 1) / bm) * ((p.Npad + 64 * tn - 1) / (64 * tn)) * p.nphase;
@@ -1141,8 +1103,7 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
         best_wg = wgs;
       }
     }
-  BM = cand[best][0];
-  TN = cand[best][1];
+  int BM = cand[best][0], TN = cand[best][1];
   if (d->force_bm || d->force_tn) {  // descriptor override (parity tests, the entropy coder's pinned variant)
     const int fb = d->force_bm, ft = d->force_tn;
     if (!((fb == 64 || fb == 128) && ft >= 1 && ft <= 3 && p.vec && p.Npad % (64 * ft) == 0)) return LIC_ERR_UNSUPPORTED;
@@ -1153,69 +1114,79 @@ static int igemm_prepare(const lic_igemm_desc* d, IgemmParams& p, int& BM, int& 
   // all workgroups of a launch reach their epilogue together, so the pool is not hidden behind other
   // workgroups' K loops, and the big layers came out 15-20 % slower than conv + a separate GDN
   // launch; lic_igemm_fused_gdn_preferred tells the caller when fusing pays.)
-  const int BM_unfused = BM;
+  p.bm_unfused = BM;
   if (fuse) {
     TN = p.Npad / 64;
     BM = 64;
   }
-  p.bm_unfused = BM_unfused;
+  pl.BM = BM;
+  pl.TN = TN;
+  pl.full = p.Npad % (64 * TN) == 0;
+  pl.glds = fuse || (pl.full && p.vec && p.prologue == 0);
   p.NT = (p.Npad + 64 * TN - 1) / (64 * TN);
-  p.MT = (int)((maxP + BM - 1) / BM);
-  p.pgroup = 0;
-  p.porder = 0;
-  if (p.nphase == 4 && p.MT >= 128) {
-    int ord[4] = {0, 1, 2, 3};
-    for (int i = 0; i < 4; ++i)
-      for (int j = i + 1; j < 4; ++j)
-        if (p.ntaps[ord[j]] > p.ntaps[ord[i]]) {
-          const int t = ord[i];
-          ord[i] = ord[j];
-          ord[j] = t;
-        }
-    p.porder = ord[0] | (ord[1] << 2) | (ord[2] << 4) | (ord[3] << 6);
-    p.pgroup = 64;
-    p.MT = ((p.MT + 63) / 64) * 64;  // whole groups; the padding tiles exit at once
-  }
-  nwg = (long)p.MT * p.NT * p.nphase;
+  const PhaseOrder po = phase_order(p.nphase, p.ntaps, (int)((maxP + BM - 1) / BM));
+  p.MT = po.MT;
+  p.pgroup = po.pgroup;
+  p.porder = po.porder;
+  pl.nwg = (long)p.MT * p.NT * p.nphase;
   // Small layers (the 16x16 / 8x8 / 4x4 latent side) cannot fill 256 CUs with output tiles alone:
   // split their K loop across workgroups when the caller provided a workspace.
   p.ksplit = 1;
   p.slabs = nullptr;
-  int max_chunks = 0;
-  for (int ph = 0; ph < p.nphase; ++ph) max_chunks = p.ntaps[ph] * p.cpt > max_chunks ? p.ntaps[ph] * p.cpt : max_chunks;
-  p.cps = max_chunks > 0 ? max_chunks : 1;
-  {
-    const long S = igemm_geo_split(d, p.Npad, max_chunks, epi, fuse);
-    if (S > 1) {
-      p.cps = (int)((max_chunks + S - 1) / S);
-      p.ksplit = (max_chunks + p.cps - 1) / p.cps;
-      const size_t need = (size_t)p.ksplit * d->B * d->Ho * d->Wo * d->Cout * sizeof(float);
-      if (d->workspace_bytes < need) return LIC_ERR_WORKSPACE;
-      p.slabs = (float*)d->workspace;
-      nwg *= p.ksplit;
-    }
+  p.cps = g.max_chunks > 0 ? g.max_chunks : 1;
+  if (S_geo > 1) {
+    p.cps = (int)((g.max_chunks + S_geo - 1) / S_geo);
+    p.ksplit = (g.max_chunks + p.cps - 1) / p.cps;
+    const size_t need = (size_t)p.ksplit * d->B * d->Ho * d->Wo * d->Cout * sizeof(float);
+    if (d->workspace_bytes < need) return LIC_ERR_WORKSPACE;
+    p.slabs = (float*)d->workspace;
+    pl.nwg *= p.ksplit;
   }
-  if (nwg > 0x7FFFFFFFL) return LIC_ERR_UNSUPPORTED;
+  if (pl.nwg > 0x7FFFFFFFL) return LIC_ERR_UNSUPPORTED;
   return LIC_OK;
+}
+static IgemmPlan igemm_plan(const lic_igemm_desc* d) {
+  IgemmPlan pl = {};
+  pl.status = igemm_fill(d, pl);
+  return pl;
+}
+
+// igemm_kernel<BM, TN, VEC, FULLN, FUSE, GLDS>.  No ragged-N rows for TN > 1: see the tile selection.
+constexpr unsigned igemm_key(int BM, int TN, bool vec, bool full, bool fuse, bool glds) {
+  return lic_variant_key(BM, TN, vec, full, fuse, glds);
+}
+#define IGEMM_ROW(...) LIC_VARIANT(igemm_key(__VA_ARGS__), 256, igemm_kernel<__VA_ARGS__>)
+static const KernelVariant<IgemmParams> g_igemm_variants[] = {
+    IGEMM_ROW(64, 1, false, false, false, false),  // odd channel counts / unaligned views: scalar loads, one tile shape
+    IGEMM_ROW(64, 1, true, false, false, false),
+    IGEMM_ROW(128, 1, true, false, false, false),
+    IGEMM_ROW(64, 1, true, true, false, false),
+    IGEMM_ROW(64, 2, true, true, false, false),
+    IGEMM_ROW(64, 3, true, true, false, false),
+    IGEMM_ROW(128, 1, true, true, false, false),
+    IGEMM_ROW(128, 2, true, true, false, false),
+    IGEMM_ROW(128, 3, true, true, false, false),
+    IGEMM_ROW(64, 1, true, true, false, true),
+    IGEMM_ROW(64, 2, true, true, false, true),
+    IGEMM_ROW(64, 3, true, true, false, true),
+    IGEMM_ROW(128, 1, true, true, false, true),
+    IGEMM_ROW(128, 2, true, true, false, true),
+    IGEMM_ROW(128, 3, true, true, false, true),
+    IGEMM_ROW(64, 1, true, true, true, true),
+    IGEMM_ROW(64, 2, true, true, true, true),
+    IGEMM_ROW(64, 3, true, true, true, true),
+};
+#undef IGEMM_ROW
+static const KernelVariant<IgemmParams>* find_variant(const IgemmPlan& pl) {
+  if (!pl.p.vec) return lic_find_variant(g_igemm_variants, igemm_key(64, 1, false, false, false, false));
+  return lic_find_variant(g_igemm_variants, igemm_key(pl.BM, pl.TN, true, pl.full, pl.fuse, pl.glds));
 }
 
 LIC_EXPORT size_t lic_igemm_workspace_bytes(const lic_igemm_desc* d) {
-  if (!d) return 0;
-  lic_igemm_desc q = *d;  // plan with stand-in pointers and an unlimited workspace
-  static float dummy[4] __attribute__((aligned(16)));
-  q.in = q.w = dummy;
-  q.out = dummy;
-  q.bias = q.aux = q.aux2 = q.aux3 = q.res = nullptr;
-  q.out2 = q.out3 = nullptr;
-  if (q.epilogue != LIC_EPI_NONE && q.epilogue != LIC_EPI_LEAKY) return 0;
-  q.workspace = dummy;
-  q.workspace_bytes = ~(size_t)0;
-  IgemmParams p;
-  int bm = 0, tn = 0;
-  long nwg = 0;
-  int64_t macs = 0;
-  if (igemm_prepare(&q, p, bm, tn, nwg, macs) != LIC_OK || p.ksplit <= 1) return 0;
-  return (size_t)p.ksplit * d->B * d->Ho * d->Wo * d->Cout * sizeof(float);
+  return conv_workspace_bytes(d, [](const lic_igemm_desc& q) {
+    const IgemmPlan pl = igemm_plan(&q);
+    return pl.status == LIC_OK ? pl.p.ksplit : 0;
+  });
 }
 
 // 1 when the fused conv+GDN launch is expected to beat conv followed by a GDN contraction launch:
@@ -1233,92 +1204,35 @@ LIC_EXPORT int lic_igemm_fused_gdn_preferred(const lic_igemm_desc* d) {
   q.workspace_bytes = 0;
   q.prologue = 0;
   q.epilogue = LIC_EPI_CONV_GDN;
-  IgemmParams p;
-  int bm = 0, tn = 0;
-  long nwg = 0;
-  int64_t macs = 0;
-  if (igemm_prepare(&q, p, bm, tn, nwg, macs) != LIC_OK) return 0;
-  return p.bm_unfused == 64 ? 1 : 0;
+  const IgemmPlan pl = igemm_plan(&q);
+  return pl.status == LIC_OK && pl.p.bm_unfused == 64 ? 1 : 0;
 }
 
 LIC_EXPORT int lic_igemm_plan(const lic_igemm_desc* d, int32_t* BM, int32_t* BN, int64_t* live_macs) {
-  IgemmParams p;
-  int bm = 0, tn = 0;
-  long nwg = 0;
-  int64_t macs = 0;
-  const int rc = igemm_prepare(d, p, bm, tn, nwg, macs);
-  if (rc < 0) return rc;
-  if (BM) *BM = bm;
-  if (BN) *BN = 64 * tn;
-  if (live_macs) *live_macs = macs;
+  const IgemmPlan pl = igemm_plan(d);
+  if (pl.status < 0) return pl.status;
+  if (BM) *BM = pl.BM;
+  if (BN) *BN = 64 * pl.TN;
+  if (live_macs) *live_macs = pl.live_macs;
   return LIC_OK;
 }
 
 // name of the kernel variant lic_igemm launches for `d`, as rocprofv3 prints it (profiling aid)
 LIC_EXPORT int lic_igemm_kernel_name(const lic_igemm_desc* d, char* buf, size_t n) {
-  IgemmParams p;
-  int BM = 0, TN = 0;
-  long nwg = 0;
-  int64_t macs = 0;
-  const int rc = igemm_prepare(d, p, BM, TN, nwg, macs);
-  if (rc < 0) return rc;
-  if (!buf || n == 0) return LIC_ERR_INVALID;
-  const bool full = (p.Npad % (64 * TN)) == 0;
-  const bool fuse = p.epilogue == LIC_EPI_CONV_GDN || p.epilogue == LIC_EPI_CONV_IGDN;
-  const bool glds = full && p.vec && p.prologue == 0;
-  if (!p.vec)
-    snprintf(buf, n, "igemm_kernel<64, 1, false, false, false, false>");
-  else
-    snprintf(buf, n, "igemm_kernel<%d, %d, true, %s, %s, %s>", BM, TN, full ? "true" : "false",
-             fuse ? "true" : "false", (glds || fuse) ? "true" : "false");
-  return LIC_OK;
+  const IgemmPlan pl = igemm_plan(d);
+  if (pl.status < 0) return pl.status;
+  return lic_variant_name(find_variant(pl), buf, n);
 }
 
 LIC_EXPORT int lic_igemm(const lic_igemm_desc* d, lic_stream_t stream) {
-  IgemmParams p;
-  int BM = 0, TN = 0;
-  long nwg = 0;
-  int64_t macs = 0;
-  const int rc = igemm_prepare(d, p, BM, TN, nwg, macs);
-  if (rc < 0) return rc;
-  if (rc == 1) return LIC_OK;
+  const IgemmPlan pl = igemm_plan(d);
+  if (pl.status < 0) return pl.status;
+  if (pl.status == 1) return LIC_OK;
+  const KernelVariant<IgemmParams>* v = find_variant(pl);
+  if (!v) return LIC_ERR_UNSUPPORTED;
+  const IgemmParams& p = pl.p;
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)nwg), block(256);
-  const bool full = (p.Npad % (64 * TN)) == 0;
-  // (prologues run on the register-staged loop: a select per operand element in the DMA loop's fragment
-  // reads cost every launch ~30 VALU per chunk)
-  const bool glds = full && p.prologue == 0;
-#define LIC_IGEMM_LAUNCH(bm, tn)                                                        \
-  do {                                                                                  \
-    if (glds)                                                                           \
-      hipLaunchKernelGGL((igemm_kernel<bm, tn, true, true, false, true>), grid, block, 0, s, p); \
-    else if (full)                                                                      \
-      hipLaunchKernelGGL((igemm_kernel<bm, tn, true, true>), grid, block, 0, s, p);     \
-    else                                                                                \
-      hipLaunchKernelGGL((igemm_kernel<bm, tn, true, false>), grid, block, 0, s, p);    \
-  } while (0)
-  if (p.epilogue == LIC_EPI_CONV_GDN || p.epilogue == LIC_EPI_CONV_IGDN) {
-    if (TN == 3)
-      hipLaunchKernelGGL((igemm_kernel<64, 3, true, true, true, true>), grid, block, 0, s, p);
-    else if (TN == 2)
-      hipLaunchKernelGGL((igemm_kernel<64, 2, true, true, true, true>), grid, block, 0, s, p);
-    else
-      hipLaunchKernelGGL((igemm_kernel<64, 1, true, true, true, true>), grid, block, 0, s, p);
-  } else if (!p.vec)  // odd channel counts / unaligned views: scalar-load variant, one tile shape
-    hipLaunchKernelGGL((igemm_kernel<64, 1, false, false>), grid, block, 0, s, p);
-  else if (BM == 128 && TN == 3)
-    LIC_IGEMM_LAUNCH(128, 3);
-  else if (BM == 64 && TN == 3)
-    LIC_IGEMM_LAUNCH(64, 3);
-  else if (BM == 128 && TN == 2)
-    LIC_IGEMM_LAUNCH(128, 2);
-  else if (BM == 64 && TN == 2)
-    LIC_IGEMM_LAUNCH(64, 2);
-  else if (BM == 128 && TN == 1)
-    LIC_IGEMM_LAUNCH(128, 1);
-  else
-    LIC_IGEMM_LAUNCH(64, 1);
-#undef LIC_IGEMM_LAUNCH
+  hipLaunchKernelGGL(v->kernel, dim3((unsigned)pl.nwg), dim3(v->block), 0, s, p);
   if (p.ksplit > 1) {
     int rc2 = lic_check_launch();
     if (rc2 != LIC_OK) return rc2;
@@ -1721,14 +1635,8 @@ long lic_pick_splits(long base, long slots, long max_sk) {
   return best;
 }
 
-struct WgPlan {
-  int TM, TN, vec, MTt, NTt, ntaps, nchunks, splitk, cps;
-  int Cm, Cn;
-};
 static int wg_plan(const lic_wgrad_desc* d, WgPlan* pl) {
-  if (!d || d->B <= 0 || d->Hs <= 0 || d->Ws <= 0 || d->Cp <= 0 || d->Cg <= 0 || d->kh <= 0 ||
-      d->kw <= 0 || d->Hl <= 0 || d->Wl <= 0)
-    return LIC_ERR_INVALID;
+  if (wgrad_desc_check(d) != LIC_OK) return LIC_ERR_INVALID;
   pl->Cm = d->g_is_row ? d->Cg : d->Cp;
   pl->Cn = d->g_is_row ? d->Cp : d->Cg;
   pl->ntaps = d->kh * d->kw;
@@ -1789,11 +1697,75 @@ static int wg_plan(const lic_wgrad_desc* d, WgPlan* pl) {
 LIC_EXPORT size_t lic_wgrad_workspace_bytes(const lic_wgrad_desc* d) {
   WgPlan pl;
   if (wg_plan(d, &pl) != LIC_OK) return 0;
-  return (size_t)pl.splitk * pl.ntaps * pl.Cm * pl.Cn * sizeof(float);
+  return wgrad_slab_bytes(pl);
 }
 
+// wgrad_kernel<TM, TN, VEC, FULL> (register-staged; the only one that squares the row operand) and
+// wgrad_glds_kernel<TM, TN, SQB, FULL> (LDS-DMA).  FULL: both channel counts are whole tiles.
+constexpr unsigned wgrad_key(bool glds, int TM, int TN, bool vec_or_sqb, bool full) {
+  return lic_variant_key(TM, TN, vec_or_sqb, full, glds);
+}
+#define WGRAD_ROW(...) LIC_VARIANT(wgrad_key(false, __VA_ARGS__), 256, wgrad_kernel<__VA_ARGS__>)
+#define WGRAD_GLDS_ROW(...) LIC_VARIANT(wgrad_key(true, __VA_ARGS__), 256, wgrad_glds_kernel<__VA_ARGS__>)
+static const KernelVariant<WgradParams> g_wgrad_variants[] = {
+    WGRAD_ROW(1, 1, false, false),  // odd channel counts / unaligned views: scalar loads, one tile shape
+    WGRAD_ROW(1, 1, true, false),      WGRAD_ROW(1, 1, true, true),
+    WGRAD_ROW(1, 3, true, false),      WGRAD_ROW(1, 3, true, true),
+    WGRAD_ROW(2, 1, true, false),      WGRAD_ROW(2, 1, true, true),
+    WGRAD_ROW(2, 2, true, false),      WGRAD_ROW(2, 2, true, true),
+    WGRAD_ROW(2, 3, true, false),      WGRAD_ROW(2, 3, true, true),
+    WGRAD_GLDS_ROW(1, 1, false, false), WGRAD_GLDS_ROW(1, 1, false, true),
+    WGRAD_GLDS_ROW(1, 1, true, false),  WGRAD_GLDS_ROW(1, 1, true, true),
+    WGRAD_GLDS_ROW(1, 3, false, false), WGRAD_GLDS_ROW(1, 3, false, true),
+    WGRAD_GLDS_ROW(1, 3, true, false),  WGRAD_GLDS_ROW(1, 3, true, true),
+    WGRAD_GLDS_ROW(2, 1, false, false), WGRAD_GLDS_ROW(2, 1, false, true),
+    WGRAD_GLDS_ROW(2, 1, true, false),  WGRAD_GLDS_ROW(2, 1, true, true),
+    WGRAD_GLDS_ROW(2, 2, false, false), WGRAD_GLDS_ROW(2, 2, false, true),
+    WGRAD_GLDS_ROW(2, 2, true, false),  WGRAD_GLDS_ROW(2, 2, true, true),
+    WGRAD_GLDS_ROW(2, 3, false, false), WGRAD_GLDS_ROW(2, 3, false, true),
+    WGRAD_GLDS_ROW(2, 3, true, false),  WGRAD_GLDS_ROW(2, 3, true, true),
+    WGRAD_GLDS_ROW(3, 3, false, true),  WGRAD_GLDS_ROW(3, 3, true, true),  // (192-multiples only: always full)
+};
+#undef WGRAD_ROW
+#undef WGRAD_GLDS_ROW
+static const KernelVariant<WgradParams>* find_variant(const lic_wgrad_desc* d, const WgPlan& pl) {
+  if (!pl.vec) return lic_find_variant(g_wgrad_variants, wgrad_key(false, 1, 1, false, false));
+  const bool full = (pl.Cm % (64 * pl.TM) == 0) && (pl.Cn % (64 * pl.TN) == 0);
+  const bool sq_row = d->g_is_row ? d->sq_g : d->sq_p, sq_col = d->g_is_row ? d->sq_p : d->sq_g;
+  if (sq_row) return lic_find_variant(g_wgrad_variants, wgrad_key(false, pl.TM, pl.TN, true, full));
+  return lic_find_variant(g_wgrad_variants, wgrad_key(true, pl.TM, pl.TN, sq_col, full));
+}
+
+// name of the MFMA kernel lic_wgrad launches for `d`, as rocprofv3 prints it (profiling aid)
+LIC_EXPORT int lic_wgrad_kernel_name(const lic_wgrad_desc* d, char* buf, size_t n) {
+  WgPlan pl;
+  const int rc = wg_plan(d, &pl);
+  if (rc != LIC_OK) return rc;
+  return lic_variant_name(find_variant(d, pl), buf, n);
+}
 static int wgrad_run(const lic_wgrad_desc* d, void* workspace, size_t workspace_bytes, int stage,
-                     lic_stream_t stream);
+                     lic_stream_t stream) {
+  WgPlan pl;
+  int rc = wg_plan(d, &pl);
+  if (rc != LIC_OK) return rc;
+  rc = wgrad_launch_check(d, pl, workspace, workspace_bytes, d->stride < 1 ? LIC_ERR_UNSUPPORTED : LIC_OK);
+  if (rc != LIC_OK) return rc;
+  const KernelVariant<WgradParams>* v = find_variant(d, pl);
+  if (!v) return LIC_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (stage != 2) {
+    const WgradParams p = wgrad_fill<WgradParams>(d, pl, workspace);
+    hipLaunchKernelGGL(v->kernel, dim3(pl.MTt * pl.NTt * pl.ntaps * pl.splitk), dim3(v->block), 0, s, p);
+    rc = lic_check_launch();
+    if (rc != LIC_OK) return rc;
+  }
+  if (stage == 1) return LIC_OK;
+  const long total = (long)pl.ntaps * pl.Cm * pl.Cn;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, s,
+                     (const float*)workspace, d->dst, pl.splitk, pl.ntaps, pl.Cm, pl.Cn, (long)d->dst_sm,
+                     (long)d->dst_sn, (long)d->dst_stap, d->scale);
+  return lic_check_launch();
+}
 LIC_EXPORT int lic_wgrad(const lic_wgrad_desc* d, void* workspace, size_t workspace_bytes,
                          lic_stream_t stream) {
   return wgrad_run(d, workspace, workspace_bytes, 0, stream);
@@ -1805,112 +1777,8 @@ LIC_EXPORT int lic_wgrad_stage(const lic_wgrad_desc* d, void* workspace, size_t 
   if (stage < 0 || stage > 2) return LIC_ERR_INVALID;
   return wgrad_run(d, workspace, workspace_bytes, stage, stream);
 }
-LIC_EXPORT int lic_wgrad_kernel_name(const lic_wgrad_desc* d, char* buf, size_t n) {
-  WgPlan pl;
-  const int rc = wg_plan(d, &pl);
-  if (rc != LIC_OK) return rc;
-  if (!buf || n == 0) return LIC_ERR_INVALID;
-  const bool full = (pl.Cm % (64 * pl.TM) == 0) && (pl.Cn % (64 * pl.TN) == 0);
-  if (!pl.vec)
-    snprintf(buf, n, "wgrad_kernel<1, 1, false, false>");
-  else if (!(d->g_is_row ? d->sq_g : d->sq_p))
-    snprintf(buf, n, "wgrad_glds_kernel<%d, %d, %s, %s>", pl.TM, pl.TN,
-             (d->g_is_row ? d->sq_p : d->sq_g) ? "true" : "false", full ? "true" : "false");
-  else
-    snprintf(buf, n, "wgrad_kernel<%d, %d, true, %s>", pl.TM, pl.TN, full ? "true" : "false");
-  return LIC_OK;
-}
-static int wgrad_run(const lic_wgrad_desc* d, void* workspace, size_t workspace_bytes, int stage,
-                     lic_stream_t stream) {
-  WgPlan pl;
-  int rc = wg_plan(d, &pl);
-  if (rc != LIC_OK) return rc;
-  if (!d->p || !d->g || !d->dst || !workspace) return LIC_ERR_INVALID;
-  if (d->stride < 1) return LIC_ERR_UNSUPPORTED;
-  const size_t need = (size_t)pl.splitk * pl.ntaps * pl.Cm * pl.Cn * sizeof(float);
-  if (workspace_bytes < need) return LIC_ERR_WORKSPACE;
-  if ((long)d->B * d->Hs * d->Ws > 0x7FFFFFFFL) return LIC_ERR_UNSUPPORTED;
-  WgOperand P, G;
-  P.ptr = d->p;
-  P.ld = d->p_ld;
-  P.C = d->Cp;
-  P.gathered = 0;
-  P.sq = d->sq_p;
-  G.ptr = d->g;
-  G.ld = d->g_ld;
-  G.C = d->Cg;
-  G.gathered = !(d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->Hl == d->Hs &&
-                 d->Wl == d->Ws);
-  G.sq = d->sq_g;
-  WgradParams p;
-  p.row = d->g_is_row ? G : P;
-  p.col = d->g_is_row ? P : G;
-  p.slabs = (float*)workspace;
-  p.B = d->B;
-  p.Hs = d->Hs;
-  p.Ws = d->Ws;
-  p.Hl = d->Hl;
-  p.Wl = d->Wl;
-  p.kw = d->kw;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.ntaps = pl.ntaps;
-  p.MTt = pl.MTt;
-  p.NTt = pl.NTt;
-  p.chunks_per_split = pl.cps;
-  p.nchunks = pl.nchunks;
-  p.Ps = (long)d->B * d->Hs * d->Ws;
-  p.dHW = make_fastdiv((unsigned)(d->Hs * d->Ws));
-  p.dW = make_fastdiv((unsigned)d->Ws);
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid(pl.MTt * pl.NTt * pl.ntaps * pl.splitk), block(256);
-  const bool full = (pl.Cm % (64 * pl.TM) == 0) && (pl.Cn % (64 * pl.TN) == 0);
-  const bool glds = !p.row.sq;  // (vec is checked below)
-  if (stage != 2) {
-#define LIC_WGRAD_LAUNCH(tm, tn)                                                      \
-  do {                                                                                \
-    if (glds && p.col.sq && full)                                                     \
-      hipLaunchKernelGGL((wgrad_glds_kernel<tm, tn, true>), grid, block, 0, s, p);    \
-    else if (glds && p.col.sq)                                                        \
-      hipLaunchKernelGGL((wgrad_glds_kernel<tm, tn, true, false>), grid, block, 0, s, p); \
-    else if (glds && full)                                                            \
-      hipLaunchKernelGGL((wgrad_glds_kernel<tm, tn>), grid, block, 0, s, p);          \
-    else if (glds)                                                                    \
-      hipLaunchKernelGGL((wgrad_glds_kernel<tm, tn, false, false>), grid, block, 0, s, p); \
-    else if (full)                                                                    \
-      hipLaunchKernelGGL((wgrad_kernel<tm, tn, true, true>), grid, block, 0, s, p);   \
-    else                                                                              \
-      hipLaunchKernelGGL((wgrad_kernel<tm, tn, true, false>), grid, block, 0, s, p);  \
-  } while (0)
-  if (!pl.vec)
-    hipLaunchKernelGGL((wgrad_kernel<1, 1, false, false>), grid, block, 0, s, p);
-  else if (pl.TM == 3 && pl.TN == 3 && p.col.sq)
-    hipLaunchKernelGGL((wgrad_glds_kernel<3, 3, true>), grid, block, 0, s, p);
-  else if (pl.TM == 3 && pl.TN == 3)
-    hipLaunchKernelGGL((wgrad_glds_kernel<3, 3>), grid, block, 0, s, p);
-  else if (pl.TM == 2 && pl.TN == 3)
-    LIC_WGRAD_LAUNCH(2, 3);
-  else if (pl.TM == 2 && pl.TN == 2)
-    LIC_WGRAD_LAUNCH(2, 2);
-  else if (pl.TM == 2 && pl.TN == 1)
-    LIC_WGRAD_LAUNCH(2, 1);
-  else if (pl.TM == 1 && pl.TN == 3)
-    LIC_WGRAD_LAUNCH(1, 3);
-  else
-    LIC_WGRAD_LAUNCH(1, 1);
-#undef LIC_WGRAD_LAUNCH
-  rc = lic_check_launch();
-  if (rc != LIC_OK) return rc;
-  }
-  if (stage == 1) return LIC_OK;
-  const long total = (long)pl.ntaps * pl.Cm * pl.Cn;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, s,
-                     (const float*)workspace, d->dst, pl.splitk, pl.ntaps, pl.Cm, pl.Cn, (long)d->dst_sm,
-                     (long)d->dst_sn, (long)d->dst_stap, d->scale);
-  return lic_check_launch();
-}
 
-// kernel-variant name lic_wgrad will launch for `d` (profiling aid)
+// tile (in 64-channel units) and split-K factor lic_wgrad will use (profiling aid)
 LIC_EXPORT int lic_wgrad_plan(const lic_wgrad_desc* d, int32_t* TM, int32_t* TN, int32_t* splitk) {
   WgPlan pl;
   const int rc = wg_plan(d, &pl);

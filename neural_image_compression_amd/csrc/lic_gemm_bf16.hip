@@ -4,29 +4,13 @@
 // LDS-staged 16-byte epilogue) with 32-deep chunks.  A chunk is only TM*TN*2 MFMAs of 32 cycles per
 // wave -- shorter than a memory round trip -- so, as in the bf16 wgrad below, the DMA runs TWO
 // chunks ahead through a ring of three LDS buffers (counted `s_waitcnt vmcnt`, raw `s_barrier`).
-#include "lic_common.h"
+#include "lic_conv_plan.h"
 #include <algorithm>
 #include <type_traits>
 
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-struct FastDivB {
-  unsigned m, s;
-};
-static FastDivB make_fastdivb(unsigned d) {
-  FastDivB f;
-  if (d == 0) d = 1;
-  unsigned s = 0;
-  while ((1ull << s) < d) ++s;
-  f.s = s;
-  f.m = (unsigned)(((1ull << (31 + s)) + d - 1) / d);
-  return f;
-}
-__device__ __forceinline__ int fdivb(int n, FastDivB f) {
-  return (int)(((unsigned long long)(unsigned)n * f.m) >> (31 + f.s));
-}
 
 constexpr int HB_BK = 32;  // bf16 elements per K chunk (64-byte rows, 2 MFMA K steps)
 
@@ -57,7 +41,7 @@ struct IgemmHParams {
   int htx, hty;        // halo-resident variant (lic_halo_bf16.h): output tiles per image along x / y
   int ntaps[4];
   int Hq[4], Wq[4];
-  FastDivB dHW[4], dW[4];
+  FastDiv dHW[4], dW[4];
   unsigned char taps[4][28];
 };
 
@@ -177,9 +161,9 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
     const int prow = m0 + arow0 + 64 * j;
     a_ok[j] = prow < P;
     const int pr = a_ok[j] ? prow : 0;
-    const int b = fdivb(pr, p.dHW[phase]);
+    const int b = fdiv(pr, p.dHW[phase]);
     const int rem = pr - b * Hq * Wq;
-    const int i = fdivb(rem, p.dW[phase]), jj = rem - i * Wq;
+    const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
     const int oy = i * sph + py, ox = jj * sph + px;
     a_base[j] = b * p.Hi * p.Wi;
     if (p.transposed) {
@@ -422,9 +406,9 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
     const bool rok = prow < P;
     long opix = rok ? prow : 0;
     if (p.nphase > 1) {
-      const int bb = fdivb((int)opix, p.dHW[phase]);
+      const int bb = fdiv((int)opix, p.dHW[phase]);
       const int rem = (int)opix - bb * Hq * Wq;
-      const int i = fdivb(rem, p.dW[phase]), jj = rem - i * Wq;
+      const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
       opix = ((long)bb * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
     }
     // a lane's 16 channels of tile b as 8 bf16 pairs -> two 16-byte stores of 8 consecutive channels each
@@ -528,9 +512,9 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
         if (prow >= P) continue;
         long opix = prow;
         if (p.nphase > 1) {
-          const int bb = fdivb(prow, p.dHW[phase]);
+          const int bb = fdiv(prow, p.dHW[phase]);
           const int rem = prow - bb * Hq * Wq;
-          const int i = fdivb(rem, p.dW[phase]), jj = rem - i * Wq;
+          const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
           opix = ((long)bb * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
         }
         float v[8];
@@ -638,7 +622,6 @@ LIC_EXPORT int lic_halo_debug_read(void* dst, size_t bytes) {
   return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_halo_dbg), bytes);
 }
 #endif
-static bool al16h(const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 LIC_EXPORT int lic_igemm_bf16_fused_gdn_supported(int32_t Cin, int32_t Cout) {
   return (Cout == 64 || Cout == 128 || Cout == 192) && Cin > 0 && Cin % 8 == 0;
@@ -686,17 +669,49 @@ LIC_EXPORT int lic_pack_weight_bf16_kperm(const float* src, void* dst, int32_t t
   return pack_bf16_launch(src, dst, taps, K, N, s_tap, s_k, s_n, 1, stream);
 }
 
+// Kernel families of the bf16 convolution path
+enum ConvFamily {
+  FAM_IGEMM4 = 0,  // implicit GEMM, 4 waves (igemm_bf16_kernel<.., 4>)
+  FAM_IGEMM8,      // implicit GEMM, 8-wave ping-pong, 256-row tiles (igemm_bf16_kernel<.., 8>)
+  FAM_HALO,        // halo-resident 5x5 stride-2 convolution (lic_halo_bf16.h)
+  FAM_HALOT        // ... and its transposed twin (lic_halot_bf16.h)
+};
+// What lic_igemm_bf16 launches for a descriptor.  status: LIC_OK, 1 when there is nothing to launch, or an error.
+struct IgemmHPlan {
+  int status;
+  IgemmHParams p;
+  long nwg;
+  int64_t live_macs;
+  ConvFamily family;
+  int BM, TN;  // implicit-GEMM families: the tile (rows, 64-column units)
+  bool fuse;
+};
+
+// the halo families: one persistent workgroup per CU walks `tx * ty` output tiles per image
+static int halo_plan(IgemmHPlan& pl, ConvFamily family, int B, int tx, int ty) {
+  IgemmHParams& p = pl.p;
+  pl.family = family;
+  p.htx = tx;
+  p.hty = ty;
+  p.MT = B * tx * ty;
+  p.NT = 1;
+  p.pgroup = p.porder = 0;
+  p.ksplit = 1;
+  p.cps = 0;
+  p.slabs = nullptr;
+  p.ring = 0;
+  pl.nwg = p.MT;
+  return LIC_OK;
+}
+
 // d uses the lic_igemm_desc layout; activation / aux / out2 pointers are bf16, `w` is the bf16
 // packed weight, bias is fp32; out is bf16 unless out_f32.
-// fills the kernel parameter block and picks the tile; returns LIC_OK, or 1 when there is nothing to launch
-static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams& p, int& BM, int& TN, long& nwg) {
-  if (!d || !d->in || !d->w || !d->out) return LIC_ERR_INVALID;
-  if (d->B <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Cin <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->Cout <= 0 ||
-      d->kh <= 0 || d->kw <= 0)
-    return LIC_ERR_INVALID;
-  if (d->kh * d->kw > 28 || d->stride < 1 || d->stride > 2) return LIC_ERR_UNSUPPORTED;
+static int igemmh_fill(const lic_igemm_desc* d, int32_t out_f32, IgemmHPlan& pl) {
+  IgemmHParams& p = pl.p;
+  int rc = conv_desc_check(d);
+  if (rc != LIC_OK) return rc;
   const int epi = d->epilogue;
-  const bool fuse = (epi == LIC_EPI_CONV_GDN || epi == LIC_EPI_CONV_IGDN);
+  const bool fuse = pl.fuse = (epi == LIC_EPI_CONV_GDN || epi == LIC_EPI_CONV_IGDN);
   if (!(epi == LIC_EPI_NONE || epi == LIC_EPI_LEAKY || epi == LIC_EPI_GDN || epi == LIC_EPI_IGDN ||
         epi == LIC_EPI_GDN_BWD || epi == LIC_EPI_IGDN_BWD || fuse) || d->res)
     return LIC_ERR_UNSUPPORTED;
@@ -704,7 +719,7 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
   if (fuse) {  // aux = gamma_eff^T packed (taps 1, K = N = Cout), aux2 = beta_eff (fp32); the tile spans every channel
     if (!d->aux || !d->aux2 || d->prologue) return LIC_ERR_INVALID;
     if (!lic_igemm_bf16_fused_gdn_supported(d->Cin, d->Cout)) return LIC_ERR_UNSUPPORTED;
-    if ((d->out3 && d->out3_ld % 8) || !al16h(d->out3)) return LIC_ERR_INVALID;
+    if ((d->out3 && d->out3_ld % 8) || !null_or_aligned16(d->out3)) return LIC_ERR_INVALID;
     if (out_f32) return LIC_ERR_UNSUPPORTED;
   }
   if ((epi == LIC_EPI_GDN_BWD || epi == LIC_EPI_IGDN_BWD) && (!d->aux || !d->aux2 || !d->aux3)) return LIC_ERR_INVALID;
@@ -712,8 +727,8 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
   if (d->Cin % 8 || d->Cout % 8 || d->in_ld % 8 || d->out_ld % 8 || (d->out2 && d->out2_ld % 8) ||
       (!fuse && ((d->aux && d->aux_ld % 8) || (d->aux2 && d->aux2_ld % 8))) || (d->aux3 && d->aux3_ld % 8))
     return LIC_ERR_UNSUPPORTED;
-  if (!al16h(d->in) || !al16h(d->w) || !al16h(d->out) || !al16h(d->out2) || !al16h(d->aux) || !al16h(d->aux2) ||
-      !al16h(d->aux3))
+  if (!aligned16(d->in) || !aligned16(d->w) || !aligned16(d->out) || !null_or_aligned16(d->out2) ||
+      !null_or_aligned16(d->aux) || !null_or_aligned16(d->aux2) || !null_or_aligned16(d->aux3))
     return LIC_ERR_INVALID;
   p.in = (const bf16_t*)d->in;
   p.w = (const bf16_t*)d->w;
@@ -749,43 +764,18 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
   p.slope = d->slope;
   p.cpt = (d->Cin + HB_BK - 1) / HB_BK;
   p.Npad = ((d->Cout + 63) / 64) * 64;  // whole 64-column wave pairs: every tile is full
-  const uint32_t mask = d->tap_mask ? d->tap_mask : 0xFFFFFFFFu;
-  p.nphase = (p.transposed && d->stride > 1) ? d->stride * d->stride : 1;
-  long maxP = 0;
-  for (int ph = 0; ph < 4; ++ph) {
-    p.ntaps[ph] = 0;
-    p.Hq[ph] = p.Wq[ph] = 0;
-    p.dHW[ph] = p.dW[ph] = make_fastdivb(1);
-  }
-  for (int ph = 0; ph < p.nphase; ++ph) {
-    const int py = (p.nphase > 1) ? ph / d->stride : 0, px = (p.nphase > 1) ? ph % d->stride : 0;
-    const int st = (p.nphase > 1) ? d->stride : 1;
-    p.Hq[ph] = (d->Ho - py + st - 1) / st;
-    p.Wq[ph] = (d->Wo - px + st - 1) / st;
-    if (p.Hq[ph] < 0) p.Hq[ph] = 0;
-    if (p.Wq[ph] < 0) p.Wq[ph] = 0;
-    const long Pp = (long)d->B * p.Hq[ph] * p.Wq[ph];
-    p.dHW[ph] = make_fastdivb((unsigned)(p.Hq[ph] * p.Wq[ph]));
-    p.dW[ph] = make_fastdivb((unsigned)p.Wq[ph]);
-    if (Pp > maxP) maxP = Pp;
-    int n = 0;
-    for (int r = 0; r < d->kh; ++r)
-      for (int s = 0; s < d->kw; ++s) {
-        const int t = r * d->kw + s;
-        if (!((mask >> t) & 1u)) continue;
-        if (p.nphase > 1)
-          if (((py + d->pad - r) % d->stride) != 0 || ((px + d->pad - s) % d->stride) != 0) continue;
-        p.taps[ph][n++] = (unsigned char)t;
-      }
-    p.ntaps[ph] = n;
-  }
+  const PhaseGeometry g = phase_geometry(d, p.cpt);
+  store_phases(p, g);
+  pl.live_macs = g.live_macs;
+  const long maxP = g.maxP;
+  const int max_chunks = g.max_chunks;
   if (maxP <= 0) return 1;
   if (maxP > 0x7FFFFFFFL / 2) return LIC_ERR_UNSUPPORTED;
   // N tile: the widest of 192 / 128 / 64 columns that divides Npad; M tile: 128 rows while the grid
   // keeps >= 512 workgroups (or the descriptor's force_bm: parity tests at small sizes)
-  TN = (p.Npad % 192 == 0) ? 3 : ((p.Npad % 128 == 0) ? 2 : 1);
+  const int TN = pl.TN = (p.Npad % 192 == 0) ? 3 : ((p.Npad % 128 == 0) ? 2 : 1);
   p.NT = p.Npad / (64 * TN);
-  BM = (((maxP + 127) / 128) * p.NT * p.nphase >= 512) ? 128 : 64;
+  int BM = (((maxP + 127) / 128) * p.NT * p.nphase >= 512) ? 128 : 64;
   if (d->force_bm) {
     if (d->force_bm != 64 && d->force_bm != 128 && d->force_bm != 256 && d->force_bm != 512) return LIC_ERR_UNSUPPORTED;
     if (d->force_bm != 512) BM = d->force_bm;
@@ -794,8 +784,6 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
   // K-split candidates (the tiny latent-side layers, see below) are decided from per-image geometry BEFORE the
   // batch-dependent tile choice, so that the choice can never switch a split off: an image's bits do not depend
   // on its batch (the 8-wave tile used to disable the split once the batch made it eligible)
-  int max_chunks = 0;
-  for (int ph = 0; ph < p.nphase; ++ph) max_chunks = p.ntaps[ph] * p.cpt > max_chunks ? p.ntaps[ph] * p.cpt : max_chunks;
   const bool simple = (epi == LIC_EPI_NONE || epi == LIC_EPI_LEAKY) && !d->out2 && d->prologue == 0;
   const long t_img = (((long)d->Ho * d->Wo + 63) / 64) * (p.Npad / 64);
   const bool split_candidate = simple && d->workspace && d->force_split != 1 &&
@@ -814,7 +802,7 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
       BM = 256;
     else if (d->force_bm == 256) BM = 128;  // (the squaring prologue has no 8-wave variant)
   }
-  // Halo-resident variant (lic_halo_bf16.h; BM = 512 names it): the 5x5 stride-2 layers of the analysis / synthesis
+  // Halo-resident families (lic_halo_bf16.h): the 5x5 stride-2 layers of the analysis / synthesis
   // stacks (Components.py:12,14,41,43 -- forward convolutions and the data gradients of the transposed ones) with
   // 128 output channels and at least four 8 x 32 output tiles per IMAGE -- a rule of per-image geometry only: this
   // variant sums K chunk-major, the others tap-major, and an image's bits must not depend on the batch it is
@@ -829,7 +817,7 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
                           d->Cout == 128 && d->Ho == (d->Hi - 1) / 2 + 1 &&
                           d->Wo == (d->Wi - 1) / 2 + 1 && (long)d->B * d->Hi * d->Wi * d->in_ld < 0x7FFFFFFFL;
     const int htx = (d->Wo + halo::TWD - 1) / halo::TWD, hty = (d->Ho + halo::TH - 1) / halo::TH;
-    // ... and the transposed layers (ConvTranspose2d forward, data gradient of the strided convolution): BM = 513,
+    // ... and the transposed layers (ConvTranspose2d forward, data gradient of the strided convolution):
     // tiles of 8 x 32 phase pixels (lic_halot_bf16.h)
     const bool shape_t = p.transposed && d->kh == 5 && d->kw == 5 && d->stride == 2 && d->pad == 2 &&
                          (d->tap_mask == 0 || (d->tap_mask & 0x1FFFFFFu) == 0x1FFFFFFu) && d->prologue == 0 &&
@@ -839,53 +827,17 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
     const int qtx = (d->Wi + halot::TWD - 1) / halot::TWD, qty = (d->Hi + halot::TH - 1) / halot::TH;
     // (at least 16 tiles per image here: a tile is 4 phases = 1024 output pixels, and with 4 tiles per image a
     // batch-32 launch has only 128 of them -- the 32 -> 64 layers measured 88 us against 44 us on the implicit GEMM)
-    if (shape_t && (d->force_bm == 512 || (!d->force_bm && qtx * qty >= 16))) {
-      BM = 513;
-      p.htx = qtx;
-      p.hty = qty;
-      p.MT = d->B * qtx * qty;
-      p.NT = 1;
-      p.pgroup = p.porder = 0;
-      p.ksplit = 1;
-      p.cps = 0;
-      p.slabs = nullptr;
-      p.ring = 0;
-      nwg = p.MT;
-      return LIC_OK;
-    }
-    if (shape_ok && (d->force_bm == 512 || (!d->force_bm && htx * hty >= 4))) {
-      BM = 512;
-      p.htx = htx;
-      p.hty = hty;
-      p.MT = d->B * htx * hty;
-      p.NT = 1;
-      p.pgroup = p.porder = 0;
-      p.ksplit = 1;
-      p.cps = 0;
-      p.slabs = nullptr;
-      p.ring = 0;
-      nwg = p.MT;
-      return LIC_OK;
-    }
+    if (shape_t && (d->force_bm == 512 || (!d->force_bm && qtx * qty >= 16))) return halo_plan(pl, FAM_HALOT, d->B, qtx, qty);
+    if (shape_ok && (d->force_bm == 512 || (!d->force_bm && htx * hty >= 4))) return halo_plan(pl, FAM_HALO, d->B, htx, hty);
   }
   if (d->force_tn && d->force_tn != TN) return LIC_ERR_UNSUPPORTED;
-  p.MT = (int)((maxP + BM - 1) / BM);
-  p.pgroup = 0;
-  p.porder = 0;
-  if (p.nphase == 4 && p.MT >= 128) {
-    int ord[4] = {0, 1, 2, 3};
-    for (int i = 0; i < 4; ++i)
-      for (int j = i + 1; j < 4; ++j)
-        if (p.ntaps[ord[j]] > p.ntaps[ord[i]]) {
-          const int t = ord[i];
-          ord[i] = ord[j];
-          ord[j] = t;
-        }
-    p.porder = ord[0] | (ord[1] << 2) | (ord[2] << 4) | (ord[3] << 6);
-    p.pgroup = 64;
-    p.MT = ((p.MT + 63) / 64) * 64;
-  }
-  nwg = (long)p.MT * p.NT * p.nphase;
+  pl.family = BM == 256 ? FAM_IGEMM8 : FAM_IGEMM4;
+  pl.BM = BM;
+  const PhaseOrder po = phase_order(p.nphase, p.ntaps, (int)((maxP + BM - 1) / BM));
+  p.MT = po.MT;
+  p.pgroup = po.pgroup;
+  p.porder = po.porder;
+  pl.nwg = (long)p.MT * p.NT * p.nphase;
   // K split for layers far too small to fill the chip: the two 5x5 stride-2 layers of the hyper encoder
   // (Components.py:71-73) are 32 and 8 workgroups of 100 chunks each -- one latency-bound K loop per CU, 32 us
   // apiece; split 12 ways they take 12.5 + 5 us (partial fp32 tiles + igemm_bf16_finish_kernel).  Only where the
@@ -908,75 +860,88 @@ static int igemmh_prepare(const lic_igemm_desc* d, int32_t out_f32, IgemmHParams
       p.ksplit = (max_chunks + p.cps - 1) / p.cps;
       if (p.ksplit > 1) {
         const size_t need = (size_t)p.ksplit * d->B * d->Ho * d->Wo * d->Cout * sizeof(float);
-        if (d->workspace_bytes < need || !al16h(d->workspace)) return LIC_ERR_WORKSPACE;
+        if (d->workspace_bytes < need || !aligned16(d->workspace)) return LIC_ERR_WORKSPACE;
         p.slabs = (float*)d->workspace;
-        nwg *= p.ksplit;
+        pl.nwg *= p.ksplit;
       } else {
         p.ksplit = 1;
       }
     }
   }
-  if (nwg > 0x7FFFFFFFL) return LIC_ERR_UNSUPPORTED;
+  if (pl.nwg > 0x7FFFFFFFL) return LIC_ERR_UNSUPPORTED;
   {
     const char* e = getenv("LIC_BF16_RING");  // tuning aid: 3 = the three-buffer ring everywhere
     p.ring = (BM == 256) ? 4 : ((BM == 128 && TN <= 2 && p.prologue != 1 && !(e && e[0] == '3')) ? 4 : 3);
   }
   return LIC_OK;
 }
-
-LIC_EXPORT size_t lic_igemm_bf16_workspace_bytes(const lic_igemm_desc* d) {
-  if (!d) return 0;
-  lic_igemm_desc q = *d;  // plan with stand-in pointers and an unlimited workspace
-  static float dummy[4] __attribute__((aligned(16)));
-  q.in = q.w = dummy;
-  q.out = dummy;
-  q.bias = q.aux = q.aux2 = q.aux3 = q.res = nullptr;
-  q.out2 = q.out3 = nullptr;
-  if (q.epilogue != LIC_EPI_NONE && q.epilogue != LIC_EPI_LEAKY) return 0;
-  q.workspace = dummy;
-  q.workspace_bytes = ~(size_t)0;
-  IgemmHParams p;
-  int bm = 0, tn = 0;
-  long nwg = 0;
-  if (igemmh_prepare(&q, 0, p, bm, tn, nwg) != LIC_OK || p.ksplit <= 1) return 0;
-  return (size_t)p.ksplit * d->B * d->Ho * d->Wo * d->Cout * sizeof(float);
+static IgemmHPlan igemmh_plan(const lic_igemm_desc* d, int32_t out_f32) {
+  IgemmHPlan pl = {};
+  pl.status = igemmh_fill(d, out_f32, pl);
+  return pl;
 }
 
+// igemm_bf16_kernel<BM, TN, SQ, FUSE, RING, NWV>, halo_conv_bf16_kernel<TW, FUSE, ABL> and
+// halo_convt_bf16_kernel<TW, FUSE>.  The 128-row tiles of one or two 64-column units run on a ring of four LDS
+// buffers, on three only under the LIC_BF16_RING=3 tuning aid.  (A 192-channel halo instance, 128 x 96 per wave,
+// compiles but needs more than the 256 + 256 registers: hipcc moves fragments that are still in flight; no row.)
+constexpr unsigned igemmh_key(int BM, int TN, bool sq, bool fuse, int ring, int nwv) {
+  return lic_variant_key(BM, TN, sq, fuse, ring, nwv == 8 ? FAM_IGEMM8 : FAM_IGEMM4);
+}
+constexpr unsigned halo_key(int TW, bool fuse, int abl = 0) { return lic_variant_key(0, TW, abl, fuse, 0, FAM_HALO); }
+constexpr unsigned halot_key(int TW, bool fuse) { return lic_variant_key(0, TW, 0, fuse, 0, FAM_HALOT); }
+constexpr unsigned igemmh_block(int, int, bool, bool, int, int nwv) { return 64 * nwv; }
+#define IGEMMH_ROW(...) LIC_VARIANT(igemmh_key(__VA_ARGS__), igemmh_block(__VA_ARGS__), igemm_bf16_kernel<__VA_ARGS__>)
+#define HALO_ROW(...) LIC_VARIANT(halo_key(__VA_ARGS__), 256, halo_conv_bf16_kernel<__VA_ARGS__>)
+#define HALOT_ROW(...) LIC_VARIANT(halot_key(__VA_ARGS__), 256, halo_convt_bf16_kernel<__VA_ARGS__>)
+static const KernelVariant<IgemmHParams> g_igemmh_variants[] = {
+    IGEMMH_ROW(64, 1, false, false, 3, 4),  IGEMMH_ROW(64, 2, false, false, 3, 4),  IGEMMH_ROW(64, 3, false, false, 3, 4),
+    IGEMMH_ROW(64, 1, true, false, 3, 4),   IGEMMH_ROW(64, 2, true, false, 3, 4),   IGEMMH_ROW(64, 3, true, false, 3, 4),
+    IGEMMH_ROW(128, 1, false, false, 4, 4), IGEMMH_ROW(128, 2, false, false, 4, 4), IGEMMH_ROW(128, 3, false, false, 3, 4),
+    IGEMMH_ROW(128, 1, false, false, 3, 4), IGEMMH_ROW(128, 2, false, false, 3, 4),
+    IGEMMH_ROW(128, 1, true, false, 3, 4),  IGEMMH_ROW(128, 2, true, false, 3, 4),  IGEMMH_ROW(128, 3, true, false, 3, 4),
+    IGEMMH_ROW(128, 1, false, true, 4, 4),  IGEMMH_ROW(128, 2, false, true, 4, 4),  IGEMMH_ROW(128, 3, false, true, 3, 4),
+    IGEMMH_ROW(128, 1, false, true, 3, 4),  IGEMMH_ROW(128, 2, false, true, 3, 4),
+    IGEMMH_ROW(256, 1, false, false, 4, 8), IGEMMH_ROW(256, 2, false, false, 4, 8), IGEMMH_ROW(256, 3, false, false, 4, 8),
+    IGEMMH_ROW(256, 1, false, true, 4, 8),  IGEMMH_ROW(256, 2, false, true, 4, 8),  IGEMMH_ROW(256, 3, false, true, 4, 8),
+    HALO_ROW(2, false, 0),                  HALO_ROW(2, true, 0),
+    HALOT_ROW(2, false),                    HALOT_ROW(2, true),
+};
+#undef IGEMMH_ROW
+#undef HALO_ROW
+#undef HALOT_ROW
+static const KernelVariant<IgemmHParams>* find_variant(const IgemmHPlan& pl) {
+  const IgemmHParams& p = pl.p;
+  if (pl.family == FAM_HALO) return lic_find_variant(g_igemmh_variants, halo_key(p.Npad / 64, pl.fuse));
+  if (pl.family == FAM_HALOT) return lic_find_variant(g_igemmh_variants, halot_key(p.Npad / 64, pl.fuse));
+  return lic_find_variant(g_igemmh_variants, igemmh_key(pl.BM, pl.TN, p.prologue == 1, pl.fuse, p.ring,
+                                                        pl.family == FAM_IGEMM8 ? 8 : 4));
+}
+
+LIC_EXPORT size_t lic_igemm_bf16_workspace_bytes(const lic_igemm_desc* d) {
+  return conv_workspace_bytes(d, [](const lic_igemm_desc& q) {
+    const IgemmHPlan pl = igemmh_plan(&q, 0);
+    return pl.status == LIC_OK ? pl.p.ksplit : 0;
+  });
+}
+
+// name of the kernel variant lic_igemm_bf16 launches for `d`, with every template argument, as rocprofv3 prints it
 LIC_EXPORT int lic_igemm_bf16_kernel_name(const lic_igemm_desc* d, char* buf, size_t n) {
-  IgemmHParams p;
-  int BM = 0, TN = 0;
-  long nwg = 0;
-  const int rc = igemmh_prepare(d, 0, p, BM, TN, nwg);
-  if (rc < 0) return rc;
-  if (!buf || n == 0) return LIC_ERR_INVALID;
-  if (BM == 513) {
-    snprintf(buf, n, "halo_convt_bf16_kernel<%d, %s>", p.Npad / 64,
-             (p.epilogue == LIC_EPI_CONV_GDN || p.epilogue == LIC_EPI_CONV_IGDN) ? "true" : "false");
-    return LIC_OK;
-  }
-  if (BM == 512) {
-    snprintf(buf, n, "halo_conv_bf16_kernel<%d, %s, 0>", p.Npad / 64,
-             (p.epilogue == LIC_EPI_CONV_GDN || p.epilogue == LIC_EPI_CONV_IGDN) ? "true" : "false");
-    return LIC_OK;
-  }
-  const bool fuse = p.epilogue == LIC_EPI_CONV_GDN || p.epilogue == LIC_EPI_CONV_IGDN;
-  // (all five template arguments, as rocprofv3 prints them)
-  snprintf(buf, n, BM == 256 ? "igemm_bf16_kernel<%d, %d, %s, %s, %d, 8>" : "igemm_bf16_kernel<%d, %d, %s, %s, %d, 4>", BM, TN,
-           p.prologue == 1 ? "true" : "false", fuse ? "true" : "false", p.ring);
-  return LIC_OK;
+  const IgemmHPlan pl = igemmh_plan(d, 0);
+  if (pl.status < 0) return pl.status;
+  return lic_variant_name(find_variant(pl), buf, n);
 }
 
 LIC_EXPORT int lic_igemm_bf16(const lic_igemm_desc* d, int32_t out_f32, lic_stream_t stream) {
-  IgemmHParams p;
-  int BM = 0, TN = 0;
-  long nwg = 0;
-  const int rc = igemmh_prepare(d, out_f32, p, BM, TN, nwg);
-  if (rc < 0) return rc;
-  if (rc == 1) return LIC_OK;
+  const IgemmHPlan pl = igemmh_plan(d, out_f32);
+  if (pl.status < 0) return pl.status;
+  if (pl.status == 1) return LIC_OK;
+  const KernelVariant<IgemmHParams>* v = find_variant(pl);
+  if (!v) return LIC_ERR_UNSUPPORTED;
+  const IgemmHParams& p = pl.p;
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)nwg), block(256);
-  const bool fuse = p.epilogue == LIC_EPI_CONV_GDN || p.epilogue == LIC_EPI_CONV_IGDN;
-  if (BM == 512 || BM == 513) {  // halo-resident 5x5 stride-2 variants: persistent workgroups, one per CU
+  dim3 grid((unsigned)pl.nwg), block(v->block);
+  if (pl.family == FAM_HALO || pl.family == FAM_HALOT) {  // persistent workgroups, one per CU
     static int ncu = 0;
     if (!ncu) {
       int dev = 0, n = 0;
@@ -984,7 +949,7 @@ LIC_EXPORT int lic_igemm_bf16(const lic_igemm_desc* d, int32_t out_f32, lic_stre
         n = 256;
       ncu = n;
     }
-    grid = dim3((unsigned)(nwg < ncu ? nwg : ncu));
+    grid = dim3((unsigned)(pl.nwg < ncu ? pl.nwg : ncu));
 #ifdef LIC_HALO_ABLATE
     if (const char* e = getenv("LIC_HALO_ABL")) {
       const int a = atoi(e);
@@ -996,57 +961,8 @@ LIC_EXPORT int lic_igemm_bf16(const lic_igemm_desc* d, int32_t out_f32, lic_stre
       if (a) return lic_check_launch();
     }
 #endif
-    // (a 192-channel instance, 128 x 96 per wave, compiles but needs more than the 256 + 256 registers: hipcc moves
-    // fragments that are still in flight; not dispatched)
-    if (BM == 513) {
-      if (fuse) hipLaunchKernelGGL((halo_convt_bf16_kernel<2, true>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((halo_convt_bf16_kernel<2>), grid, block, 0, s, p);
-      return lic_check_launch();
-    }
-    if (fuse) hipLaunchKernelGGL((halo_conv_bf16_kernel<2, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((halo_conv_bf16_kernel<2>), grid, block, 0, s, p);
-    return lic_check_launch();
   }
-  if (BM == 256) {  // 8-wave ping-pong variant
-    dim3 block8(512);
-    if (fuse) {
-      if (TN == 3) hipLaunchKernelGGL((igemm_bf16_kernel<256, 3, false, true, 4, 8>), grid, block8, 0, s, p);
-      else if (TN == 2) hipLaunchKernelGGL((igemm_bf16_kernel<256, 2, false, true, 4, 8>), grid, block8, 0, s, p);
-      else hipLaunchKernelGGL((igemm_bf16_kernel<256, 1, false, true, 4, 8>), grid, block8, 0, s, p);
-    } else {
-      if (TN == 3) hipLaunchKernelGGL((igemm_bf16_kernel<256, 3, false, false, 4, 8>), grid, block8, 0, s, p);
-      else if (TN == 2) hipLaunchKernelGGL((igemm_bf16_kernel<256, 2, false, false, 4, 8>), grid, block8, 0, s, p);
-      else hipLaunchKernelGGL((igemm_bf16_kernel<256, 1, false, false, 4, 8>), grid, block8, 0, s, p);
-    }
-    return lic_check_launch();
-  }
-#define LIC_IGEMMH_LAUNCH(bm, tn)                                                           \
-  do {                                                                                      \
-    constexpr int R4 = (tn <= 2) ? 4 : 3; /* the ring p.ring asks for on 128-row tiles */   \
-    if (fuse && p.ring == 4)                                                                \
-      hipLaunchKernelGGL((igemm_bf16_kernel<128, tn, false, true, R4>), grid, block, 0, s, p); \
-    else if (fuse)                                                                          \
-      hipLaunchKernelGGL((igemm_bf16_kernel<128, tn, false, true>), grid, block, 0, s, p);  \
-    else if (p.prologue == 1)                                                               \
-      hipLaunchKernelGGL((igemm_bf16_kernel<bm, tn, true>), grid, block, 0, s, p);          \
-    else if (p.ring == 4)                                                                   \
-      hipLaunchKernelGGL((igemm_bf16_kernel<128, tn, false, false, R4>), grid, block, 0, s, p); \
-    else                                                                                    \
-      hipLaunchKernelGGL((igemm_bf16_kernel<bm, tn>), grid, block, 0, s, p);                \
-  } while (0)
-  if (BM == 128 && TN == 3)
-    LIC_IGEMMH_LAUNCH(128, 3);
-  else if (BM == 64 && TN == 3)
-    LIC_IGEMMH_LAUNCH(64, 3);
-  else if (BM == 128 && TN == 2)
-    LIC_IGEMMH_LAUNCH(128, 2);
-  else if (BM == 64 && TN == 2)
-    LIC_IGEMMH_LAUNCH(64, 2);
-  else if (BM == 128 && TN == 1)
-    LIC_IGEMMH_LAUNCH(128, 1);
-  else
-    LIC_IGEMMH_LAUNCH(64, 1);
-#undef LIC_IGEMMH_LAUNCH
+  hipLaunchKernelGGL(v->kernel, grid, block, 0, s, p);
   if (p.ksplit > 1) {
     const long npix = (long)d->B * d->Ho * d->Wo;
     hipLaunchKernelGGL(igemm_bf16_finish_kernel, dim3(ew_grid(npix * d->Cout / 8, 256)), dim3(256), 0, s,
@@ -1087,7 +1003,7 @@ struct WgradHParams {
   int MTt, NTt;
   int chunks_per_split, nchunks;
   long Ps;
-  FastDivB dHW, dW;
+  FastDiv dHW, dW;
 };
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -1146,9 +1062,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradHParams p
       const long pk = (long)cc * BK + kr + 32 * j;
       const bool inb = pk < p.Ps;
       const int pix = inb ? (int)pk : 0;
-      const int b = fdivb(pix, p.dHW);
+      const int b = fdiv(pix, p.dHW);
       const int rem = pix - b * p.Hs * p.Ws;
-      const int hs = fdivb(rem, p.dW), ws = rem - hs * p.Ws;
+      const int hs = fdiv(rem, p.dW), ws = rem - hs * p.Ws;
       const int hl = hs * p.stride - p.pad + r, wl = ws * p.stride - p.pad + s;
       const bool gok = inb && hl >= 0 && wl >= 0 && hl < p.Hl && wl < p.Wl;
       const long gpix = ((long)b * p.Hl + hl) * p.Wl + wl;
@@ -1304,16 +1220,10 @@ __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(const float* sla
   }
 }
 
-long lic_pick_splits(long base, long slots, long max_sk);  // lic_gemm.hip
-
-struct WgHPlan {
-  int TM, TN, MTt, NTt, ntaps, nchunks, splitk, cps, Cm, Cn;
-};
-static int wgh_plan(const lic_wgrad_desc* d, WgHPlan* pl) {
-  if (!d || d->B <= 0 || d->Hs <= 0 || d->Ws <= 0 || d->Cp <= 0 || d->Cg <= 0 || d->kh <= 0 || d->kw <= 0 ||
-      d->Hl <= 0 || d->Wl <= 0)
-    return LIC_ERR_INVALID;
+static int wgh_plan(const lic_wgrad_desc* d, WgPlan* pl) {
+  if (wgrad_desc_check(d) != LIC_OK) return LIC_ERR_INVALID;
   if (d->Cp % 8 || d->Cg % 8 || d->p_ld % 8 || d->g_ld % 8) return LIC_ERR_UNSUPPORTED;
+  pl->vec = 1;
   pl->Cm = d->g_is_row ? d->Cg : d->Cp;
   pl->Cn = d->g_is_row ? d->Cp : d->Cg;
   pl->ntaps = d->kh * d->kw;
@@ -1338,82 +1248,49 @@ static int wgh_plan(const lic_wgrad_desc* d, WgHPlan* pl) {
   return LIC_OK;
 }
 LIC_EXPORT size_t lic_wgrad_bf16_workspace_bytes(const lic_wgrad_desc* d) {
-  WgHPlan pl;
+  WgPlan pl;
   if (wgh_plan(d, &pl) != LIC_OK) return 0;
-  return (size_t)pl.splitk * pl.ntaps * pl.Cm * pl.Cn * sizeof(float);
+  return wgrad_slab_bytes(pl);
 }
+
+// wgrad_bf16_kernel<TM, TN, SQB>.  Only the column operand can be squared (GDN d-gamma), and only in C x C products.
+constexpr unsigned wgradh_key(int TM, int TN, bool sq_col, bool sq_row = false) {
+  return lic_variant_key(TM, TN, sq_col, sq_row);
+}
+#define WGRADH_ROW(...) LIC_VARIANT(wgradh_key(__VA_ARGS__), 256, wgrad_bf16_kernel<__VA_ARGS__>)
+static const KernelVariant<WgradHParams> g_wgradh_variants[] = {
+    WGRADH_ROW(1, 1, false), WGRADH_ROW(1, 2, false), WGRADH_ROW(1, 3, false),
+    WGRADH_ROW(2, 1, false), WGRADH_ROW(2, 2, false), WGRADH_ROW(2, 3, false),
+    WGRADH_ROW(3, 1, false), WGRADH_ROW(3, 2, false), WGRADH_ROW(3, 3, false),
+    WGRADH_ROW(1, 1, true),  WGRADH_ROW(2, 2, true),  WGRADH_ROW(3, 3, true),
+};
+#undef WGRADH_ROW
+static const KernelVariant<WgradHParams>* find_variant(const lic_wgrad_desc* d, const WgPlan& pl) {
+  const bool sq_row = d->g_is_row ? d->sq_g : d->sq_p, sq_col = d->g_is_row ? d->sq_p : d->sq_g;
+  return lic_find_variant(g_wgradh_variants, wgradh_key(pl.TM, pl.TN, sq_col, sq_row));
+}
+
+// name of the MFMA kernel lic_wgrad_bf16 launches for `d`, as rocprofv3 prints it
 LIC_EXPORT int lic_wgrad_bf16_kernel_name(const lic_wgrad_desc* d, char* buf, size_t n) {
-  WgHPlan pl;
+  WgPlan pl;
   const int rc = wgh_plan(d, &pl);
   if (rc != LIC_OK) return rc;
-  if (!buf || n == 0) return LIC_ERR_INVALID;
-  snprintf(buf, n, "wgrad_bf16_kernel<%d, %d, %s>", pl.TM, pl.TN, (d->g_is_row ? d->sq_p : d->sq_g) ? "true" : "false");
-  return LIC_OK;
+  return lic_variant_name(find_variant(d, pl), buf, n);
 }
 // p / g are bf16 activations; dst and the workspace are fp32
 static int wgrad_bf16_impl(const lic_wgrad_desc* d, void* workspace, size_t workspace_bytes, lic_reduce_job* job,
                            lic_stream_t stream) {
-  WgHPlan pl;
+  WgPlan pl;
   int rc = wgh_plan(d, &pl);
   if (rc != LIC_OK) return rc;
-  if (!d->p || !d->g || !d->dst || !workspace) return LIC_ERR_INVALID;
-  if (!al16h(d->p) || !al16h(d->g)) return LIC_ERR_INVALID;
-  const size_t need = (size_t)pl.splitk * pl.ntaps * pl.Cm * pl.Cn * sizeof(float);
-  if (workspace_bytes < need) return LIC_ERR_WORKSPACE;
-  if ((long)d->B * d->Hs * d->Ws > 0x7FFFFFFFL) return LIC_ERR_UNSUPPORTED;
-  WgHOperand P, G;
-  P.ptr = (const bf16_t*)d->p;
-  P.ld = d->p_ld;
-  P.C = d->Cp;
-  P.gathered = 0;
-  P.sq = d->sq_p;
-  G.ptr = (const bf16_t*)d->g;
-  G.ld = d->g_ld;
-  G.C = d->Cg;
-  G.gathered = !(d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->Hl == d->Hs && d->Wl == d->Ws);
-  G.sq = d->sq_g;
-  WgradHParams p;
-  p.row = d->g_is_row ? G : P;
-  p.col = d->g_is_row ? P : G;
-  p.slabs = (float*)workspace;
-  p.B = d->B;
-  p.Hs = d->Hs;
-  p.Ws = d->Ws;
-  p.Hl = d->Hl;
-  p.Wl = d->Wl;
-  p.kw = d->kw;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.ntaps = pl.ntaps;
-  p.MTt = pl.MTt;
-  p.NTt = pl.NTt;
-  p.chunks_per_split = pl.cps;
-  p.nchunks = pl.nchunks;
-  p.Ps = (long)d->B * d->Hs * d->Ws;
-  p.dHW = make_fastdivb((unsigned)(d->Hs * d->Ws));
-  p.dW = make_fastdivb((unsigned)d->Ws);
+  rc = wgrad_launch_check(d, pl, workspace, workspace_bytes,
+                          aligned16(d->p) && aligned16(d->g) ? LIC_OK : LIC_ERR_INVALID);
+  if (rc != LIC_OK) return rc;
+  const KernelVariant<WgradHParams>* v = find_variant(d, pl);
+  if (!v) return LIC_ERR_UNSUPPORTED;
+  const WgradHParams p = wgrad_fill<WgradHParams>(d, pl, workspace);
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid(pl.MTt * pl.NTt * pl.ntaps * pl.splitk), block(256);
-  if (p.row.sq) return LIC_ERR_UNSUPPORTED;  // only the column operand can be squared (GDN d-gamma)
-  if (p.col.sq) {
-    if (pl.TM != pl.TN) return LIC_ERR_UNSUPPORTED;  // C x C products only
-    if (pl.TM == 1) hipLaunchKernelGGL((wgrad_bf16_kernel<1, 1, true>), grid, block, 0, s, p);
-    if (pl.TM == 2) hipLaunchKernelGGL((wgrad_bf16_kernel<2, 2, true>), grid, block, 0, s, p);
-    if (pl.TM == 3) hipLaunchKernelGGL((wgrad_bf16_kernel<3, 3, true>), grid, block, 0, s, p);
-  } else {
-#define LIC_WGH(tm, tn) \
-  if (pl.TM == tm && pl.TN == tn) hipLaunchKernelGGL((wgrad_bf16_kernel<tm, tn>), grid, block, 0, s, p)
-  LIC_WGH(1, 1);
-  LIC_WGH(1, 2);
-  LIC_WGH(1, 3);
-  LIC_WGH(2, 1);
-  LIC_WGH(2, 2);
-  LIC_WGH(2, 3);
-  LIC_WGH(3, 1);
-  LIC_WGH(3, 2);
-  LIC_WGH(3, 3);
-#undef LIC_WGH
-  }
+  hipLaunchKernelGGL(v->kernel, dim3(pl.MTt * pl.NTt * pl.ntaps * pl.splitk), dim3(v->block), 0, s, p);
   rc = lic_check_launch();
   if (rc != LIC_OK) return rc;
   const long total = (long)pl.ntaps * pl.Cm * pl.Cn;
