@@ -398,6 +398,42 @@ int lic_gmm_cdf_tables(const float* params, int64_t P, int32_t M, int32_t K, int
                        uint32_t* out, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2 -- the device decoder of the "rANS-64" y streams (format and host coder: lic_codec.h).
+ *   lic_rans_decode_step decodes ONE wavefront step of all B images in one launch, one wave per image, from the
+ *   tables lic_gmm_cdf_tables has just built, and writes the values where the next step's gather reads them:
+ *   codec.ContextCodec's decode loop becomes a chain of asynchronous launches with no host in it.
+ *     streams       all images' streams in one buffer (4-byte aligned); image b's stream starts at byte
+ *                   stream_off[b] (a multiple of 4: pad each start in this staging buffer, not in the file) and
+ *                   is stream_bytes[b] long, stream_off[b] + stream_bytes[b] <= stream_off[b+1]; stream_off has
+ *                   B+1 entries.  The 64 leading state words are NOT read here: they seed `state`.
+ *     escapes       all images' escape lists; image b's entries are escapes[esc_off[b] .. esc_off[b+1])
+ *     state         [B][LIC_RANS_STATE_WORDS] uint32: the 64 coder states (lane 0 first), the word cursor (in
+ *                   16-bit words behind the 64 leading state words), the escape cursor and an error word (0 = fine,
+ *                   else LIC_RANS_ERR_* bits).  Read at entry and written back at exit with ordinary stores, so
+ *                   consecutive launches on one stream carry it.  Seed: the stream's 64 states, 0, 0, 0.
+ *     tables        [B][n*M][2W+2] (16-byte aligned) and center [B][n*M]: lic_gmm_cdf_tables' outputs for the
+ *                   step's n pixels per image; symbol k of the step is pixel k / M, channel k % M
+ *     dest          [n] pixel indices (device, the step's slice of the caller's index array), each in [0, pixels)
+ *     ypad          [B][pixels][M] fp32: element (b, dest[k / M], k % M) = float(idx + center - W), the escape
+ *                   excess applied at the edge symbols; no other element is touched
+ *   Before every read of a word or an escape the cursor plus the lane's rank is compared with the image's
+ *   length: out of range reads nothing, sets LIC_RANS_ERR_RANGE in the image's error word and makes every later
+ *   symbol of that image decode as its table centre.  A stream_bytes[b] below 256 or beyond its slot sets
+ *   LIC_RANS_ERR_STREAM with the same effect; a dest index outside [0, pixels) is not written and sets
+ *   LIC_RANS_ERR_RANGE.  After the last step an intact stream has word cursor == (stream_bytes - 256) / 2, escape
+ *   cursor == its escape count and every state == 2^16: the caller's to check with the error words.
+ *   W <= 64 (LIC_ERR_UNSUPPORTED above).  One launch, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define LIC_RANS_LANES 64
+#define LIC_RANS_STATE_WORDS 67
+#define LIC_RANS_ERR_RANGE 1u  /* a word, escape or destination index was out of range */
+#define LIC_RANS_ERR_STREAM 2u /* stream_bytes[b] cannot be right */
+int lic_rans_decode_step(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
+                         const uint32_t* escapes, const int64_t* esc_off, uint32_t* state, const uint32_t* tables,
+                         const int32_t* center, int32_t B, int32_t n, int32_t M, int32_t W, const int64_t* dest,
+                         float* ypad, int64_t pixels, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).1 -- evaluation metric on the device.
  * Multi-scale SSIM exactly as the reference's evaluator calls it (Evaluator.py:7,38,45:
  * `ms_ssim(recon, orig, data_range=1.0, size_average=True)` of the third-party pytorch-msssim==0.2.1,

@@ -51,6 +51,35 @@ void lic_rc_decoder_free(lic_rc_decoder* dec);
 double lic_rc_ideal_bits(const uint32_t* tables, const int32_t* table_of, int32_t S, const int32_t* idx,
                          int64_t n);
 
+/* ------------------------------------------------------------------------------------------
+ * "rANS-64": a second coder for the y streams whose decoder also runs on the device (lic_rans_decode_step in
+ * lic.h); the range coder above stays the default and codes z.  The same tables, one per symbol ([n][S+1]).
+ *   L = 64 interleaved states of 32 bits, each in [2^16, 2^32); 16-bit probabilities; renormalisation by 16-bit
+ *   little-endian words, at most one per symbol per lane.  The n symbols are split into steps (step_len[nsteps],
+ *   in symbols, summing to n: the wavefront steps of codec.ContextCodec); inside a step symbol k belongs to lane
+ *   k % 64 and round k / 64, a step's last round may be partial, and rounds never straddle steps.
+ *   Decoding a round, active lanes:  slot = x & 0xFFFF;  s: cum[s] <= slot < cum[s+1];
+ *     x = (cum[s+1] - cum[s]) * (x >> 16) + slot - cum[s];  lanes with x < 2^16 take one word each,
+ *     x = (x << 16) | word[ptr + rank]  with rank = number of such lanes with a smaller lane id;  ptr += count.
+ *   Encoding is the exact mirror: steps, rounds and lanes last to first; if x >= freq << 16 emit x & 0xFFFF and
+ *   x >>= 16; then x = ((x / freq) << 16) + x % freq + start; words go towards lower addresses; every state
+ *   starts at 2^16.  Stream = 64 little-endian uint32 final states (lane 0 first) + the words in reading order.
+ *   Escapes: idx <= 0 / idx >= S-1 code the edge symbol as above, but the excess (-idx or idx - (S-1)) goes into
+ *   a separate list of uint32, in symbol order, 32 bits each (an in-stream escape would break the lock step).
+ * lic_rans_decode returns LIC_CODEC_ERR_CORRUPT for a truncated stream, a word or escape cursor past the end,
+ * trailing unused words or escapes, and final states other than 2^16.
+ * ------------------------------------------------------------------------------------------ */
+/* upper bound of the stream of n symbols in bytes (256 + 2 n); the escape list has at most n entries */
+size_t lic_rans_bound(int64_t n);
+int lic_rans_encode(const uint32_t* tables, int32_t S, const int32_t* idx, int64_t n, const int64_t* step_len,
+                    int64_t nsteps, uint8_t* out, size_t cap, size_t* nbytes, uint32_t* esc_out, size_t esc_cap,
+                    size_t* nesc);
+int lic_rans_decode(const uint8_t* in, size_t nbytes, const uint32_t* esc, size_t nesc, const uint32_t* tables,
+                    int32_t S, int64_t n, const int64_t* step_len, int64_t nsteps, int32_t* idx_out);
+/* lic_rc_ideal_bits' definition with 32 bits per escape instead of the Elias-gamma length */
+double lic_rans_ideal_bits(const uint32_t* tables, const int32_t* table_of, int32_t S, const int32_t* idx,
+                           int64_t n);
+
 int lic_codec_version(void);
 
 #ifdef __cplusplus

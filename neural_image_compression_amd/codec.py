@@ -14,6 +14,10 @@ used -- the coder's inverse).  `ContextCodec`: the full round trip; its decoder 
 already-decoded pixels through the masked 5x5 context model, wavefront by wavefront.
 `ContextCodec.compress_image` / `decompress_image` wrap that round trip, for images of any size, in one
 self-describing byte string (`pack_bitstream`: header, per-image lengths and checksums, streams, CRC-32).
+
+`ContextCodec(..., coder="rans")` codes the y streams with the 64-lane interleaved rANS coder of lic_codec.h
+instead: its decoder is a device kernel (`lic_rans_decode_step`), so the decode loop has no host in it; the
+container of that coder is `pack_bitstream_rans` (magic LICBITS2).  The range coder stays the default and codes z.
 """
 from __future__ import annotations
 
@@ -52,6 +56,16 @@ def _codec():
         lib.lic_rc_ideal_bits.restype = C.c_double
         lib.lic_rc_ideal_bits.argtypes = [u32p, i32p, C.c_int32, i32p, C.c_int64]
         lib.lic_codec_version.restype = C.c_int
+        i64p, szp = C.POINTER(C.c_int64), C.POINTER(C.c_size_t)
+        lib.lic_rans_bound.restype, lib.lic_rans_bound.argtypes = C.c_size_t, [C.c_int64]
+        lib.lic_rans_encode.restype = C.c_int
+        lib.lic_rans_encode.argtypes = [u32p, C.c_int32, i32p, C.c_int64, i64p, C.c_int64, u8p, C.c_size_t, szp, u32p,
+                                        C.c_size_t, szp]
+        lib.lic_rans_decode.restype = C.c_int
+        lib.lic_rans_decode.argtypes = [u8p, C.c_size_t, u32p, C.c_size_t, u32p, C.c_int32, C.c_int64, i64p, C.c_int64,
+                                        i32p]
+        lib.lic_rans_ideal_bits.restype = C.c_double
+        lib.lic_rans_ideal_bits.argtypes = [u32p, i32p, C.c_int32, i32p, C.c_int64]
         _CODEC = lib
     return _CODEC
 
@@ -96,6 +110,54 @@ def rc_ideal_bits(tables: np.ndarray, idx: np.ndarray, table_of: np.ndarray = No
     tof = None if table_of is None else np.ascontiguousarray(table_of, np.int32).ravel()
     return float(_codec().lic_rc_ideal_bits(_p(tables, C.c_uint32), _p(tof, C.c_int32), tables.shape[-1] - 1,
                                             _p(idx, C.c_int32), idx.size))
+
+
+# ---- the interleaved rANS coder of the y streams (lic_codec.h "rANS-64") ---------------------
+RANS_LANES = 64
+CODERS = ("range", "rans")
+
+
+def rans_encode(tables: np.ndarray, idx: np.ndarray, step_len) -> tuple:
+    """tables [n][S+1] uint32 (one per symbol), idx [n] int32, step_len: symbols per wavefront step (sums to n)
+    -> (stream bytes, escape list bytes: little-endian uint32, in symbol order)"""
+    tables = np.ascontiguousarray(tables, np.uint32)
+    idx = np.ascontiguousarray(idx, np.int32).ravel()
+    steps = np.ascontiguousarray(step_len, np.int64).ravel()
+    S = tables.shape[-1] - 1
+    lib = _codec()
+    cap = lib.lic_rans_bound(idx.size)
+    out, esc = np.empty(cap, np.uint8), np.empty(max(idx.size, 1), np.dtype("<u4"))
+    nb, ne = C.c_size_t(0), C.c_size_t(0)
+    rc = lib.lic_rans_encode(_p(tables, C.c_uint32), S, _p(idx, C.c_int32), idx.size, _p(steps, C.c_int64), steps.size,
+                             _p(out, C.c_uint8), cap, C.byref(nb), _p(esc, C.c_uint32), idx.size, C.byref(ne))
+    if rc != 0:
+        raise CodecError(f"lic_rans_encode failed with status {rc}")
+    return out[:nb.value].tobytes(), esc[:ne.value].tobytes()
+
+
+def rans_decode(data: bytes, esc: bytes, tables: np.ndarray, step_len) -> np.ndarray:
+    """the inverse of `rans_encode` for known tables"""
+    tables = np.ascontiguousarray(tables, np.uint32)
+    steps = np.ascontiguousarray(step_len, np.int64).ravel()
+    n = int(steps.sum())
+    S = tables.shape[-1] - 1
+    if len(esc) % 4:
+        raise CodecError("escape list is not a whole number of uint32")
+    buf = np.frombuffer(data, np.uint8)
+    ebuf = np.frombuffer(esc, np.dtype("<u4")).astype(np.uint32)
+    out = np.empty(n, np.int32)
+    rc = _codec().lic_rans_decode(_p(buf, C.c_uint8), buf.size, _p(ebuf, C.c_uint32), ebuf.size, _p(tables, C.c_uint32),
+                                  S, n, _p(steps, C.c_int64), steps.size, _p(out, C.c_int32))
+    if rc != 0:
+        raise CodecError(f"lic_rans_decode failed with status {rc}")
+    return out
+
+
+def rans_ideal_bits(tables: np.ndarray, idx: np.ndarray) -> float:
+    tables = np.ascontiguousarray(tables, np.uint32)
+    idx = np.ascontiguousarray(idx, np.int32).ravel()
+    return float(_codec().lic_rans_ideal_bits(_p(tables, C.c_uint32), None, tables.shape[-1] - 1, _p(idx, C.c_int32),
+                                              idx.size))
 
 
 # ---- device side: tables --------------------------------------------------------------------
@@ -226,10 +288,17 @@ class ContextCodec:
     not depend on the batch it sits in, and their split-K choice depends on per-image geometry only --
     the property tests/test_gpu_fullsize.py pins); the encoder simply has all N = B*h*w pixels at
     once.  One y stream per image (symbols step by step, pixel by pixel, channel by channel) + one z stream
-    for the batch."""
+    for the batch.
 
-    def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32):
-        self.model, self.z_lo, self.z_S, self.y_W = model, int(z_lo), int(z_S), int(y_W)
+    `coder`: "range" (the default) codes y with the host range coder as described above; "rans" codes y with
+    the 64-lane interleaved rANS coder of lic_codec.h, whose decoder is a device kernel
+    (`lic_rans_decode_step`): the step loop is then {gather -> per-pixel layers -> tables -> decode}, all
+    asynchronous launches, and the host reads back one small block after the last step.  z keeps the range coder."""
+
+    def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range"):
+        if coder not in CODERS:
+            raise CodecError(f"unknown coder {coder!r}: expected one of {CODERS}")
+        self.model, self.z_lo, self.z_S, self.y_W, self.coder = model, int(z_lo), int(z_S), int(y_W), coder
         mc = model.context_model.masked
         k = mc.kernel_size[0]
         self.taps = [(r, s) for r in range(k) for s in range(k) if (mc._tap_mask >> (r * k + s)) & 1]
@@ -311,18 +380,27 @@ class ContextCodec:
         center, tables = self._params_at(self._windows_all(y_in), psi_px, self._prepack())
         y_sym = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
         # symbols leave in the decoder's wavefront order (see _wavefront), M channels per pixel
-        perm = torch.from_numpy(np.concatenate([ii * w + jj for ii, jj in self._wavefront(h, w)])).to(y_in.device)
+        steps = self._wavefront(h, w)
+        perm = torch.from_numpy(np.concatenate([ii * w + jj for ii, jj in steps])).to(y_in.device)
         idx = (y_sym - center + self.y_W).view(B, h * w, M)[:, perm].cpu().numpy().reshape(B, h * w * M)
         tabs = tables.view(B, h * w, M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * M, -1)
-        y_streams = [rc_encode(tabs[b], idx[b]) for b in range(B)]
+        strings = {"z": z_bytes}
+        if self.coder == "rans":
+            step_len = [len(ii) * M for ii, _ in steps]
+            pairs = [rans_encode(tabs[b], idx[b], step_len) for b in range(B)]
+            y_streams, y_esc = [p[0] for p in pairs], [p[1] for p in pairs]
+            strings.update(coder="rans", y_esc=y_esc)
+        else:
+            y_streams, y_esc = [rc_encode(tabs[b], idx[b]) for b in range(B)], []
         npix = x.shape[0] * x.shape[2] * x.shape[3]
-        coded = 8.0 * (len(z_bytes) + sum(len(s) for s in y_streams)) / npix
+        coded = 8.0 * (len(z_bytes) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
         est = float(-(out["logp_y"].double().sum() + out["logp_z"].double().sum()) / np.log(2.0) / npix)
         # CRC-32 of every image's latent symbols: a decoder whose tables differ from the encoder's by one count
         # decodes garbage silently; with the checksum it fails loudly instead
         y_crc = [zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
                  for a in y_sym.reshape(B, h * w * M).cpu().numpy().astype(np.int32)]
-        return {"strings": {"y": y_streams, "z": z_bytes, "y_crc32": y_crc}, "shape": (B, M, h, w),
+        strings.update(y=y_streams, y_crc32=y_crc)
+        return {"strings": strings, "shape": (B, M, h, w),
                 "z_shape": tuple(z_in.shape),
                 "bpp_coded": coded, "bpp_est": est, "y_in": y_in, "z_in": z_in}
 
@@ -352,6 +430,12 @@ class ContextCodec:
         yflat = ypad.view(B, -1, M)
         psi_flat = psi_h.view(B, h * w, -1)
         nt = len(self.taps)
+        coder = strings.get("coder", "range")
+        if coder not in CODERS:
+            raise CodecError(f"unknown coder {coder!r} in the strings")
+        if coder == "rans":
+            self._decode_y_rans(strings, steps, layers, yflat, psi_flat, win_idx, own_idx, psi_idx)
+            return self._finish(strings, ypad, z_hat, shape)
         pin = dev.type == "cuda"
         tabs_host = torch.empty((B, nmax * M, S1), dtype=torch.int32, pin_memory=pin)
         c_host = torch.empty((B, nmax * M), dtype=torch.int32, pin_memory=pin)
@@ -376,6 +460,64 @@ class ContextCodec:
         finally:
             for d in decs:
                 d.close()
+        return self._finish(strings, ypad, z_hat, shape)
+
+    def _decode_y_rans(self, strings, steps, layers, yflat, psi_flat, win_idx, own_idx, psi_idx):
+        """The step loop of the "rans" coder: streams, escape lists, state blocks and index arrays go up once, then
+        every step is gather -> per-pixel layers + tables -> lic_rans_decode_step, which writes the decoded values
+        into `yflat` where the next gather reads them.  Nothing in the loop waits for the device; the state blocks
+        (error words, cursors, final states) come back once, after the last step."""
+        B, npad, M = yflat.shape
+        dev = yflat.device
+        ys, escs = strings["y"], strings.get("y_esc")
+        if escs is None or len(ys) != B or len(escs) != B:
+            raise CodecError("one y stream and one escape list per image expected")
+        head = 4 * RANS_LANES
+        for b in range(B):
+            if len(ys[b]) < head or len(ys[b]) % 2 or len(escs[b]) % 4:
+                raise CodecError(f"image {b}: y stream or escape list has an impossible length")
+        # staging: every stream starts on a 4-byte boundary; offsets, lengths and seeds in one upload each
+        s_off = np.zeros(B + 1, np.int64)
+        for b in range(B):
+            s_off[b + 1] = s_off[b] + (len(ys[b]) + 3) // 4 * 4
+        s_len = np.array([len(s) for s in ys], np.int64)
+        buf = np.zeros(int(s_off[B]), np.uint8)
+        state = np.zeros((B, L.RANS_STATE_WORDS), np.uint32)
+        for b in range(B):
+            buf[s_off[b]:s_off[b] + len(ys[b])] = np.frombuffer(ys[b], np.uint8)
+            state[b, :RANS_LANES] = np.frombuffer(ys[b][:head], np.dtype("<u4"))
+        e_off = np.concatenate([[0], np.cumsum([len(e) // 4 for e in escs])]).astype(np.int64)
+        e_all = np.frombuffer(b"".join(escs) + b"\0\0\0\0", np.dtype("<u4")).astype(np.uint32)
+        d_buf, d_esc = torch.from_numpy(buf).to(dev), torch.from_numpy(e_all.view(np.int32)).to(dev)
+        d_soff, d_slen, d_eoff = (torch.from_numpy(a).to(dev) for a in (s_off, s_len, e_off))
+        d_state = torch.from_numpy(state.view(np.int32)).to(dev)
+        lib, nt = L.load(), len(self.taps)
+        off = 0
+        for ii, _ in steps:
+            n = len(ii)
+            win = yflat.index_select(1, win_idx[off * nt:(off + n) * nt])                 # [B, n*12, M]
+            center, tables = self._params_at(win.view(B * n, nt * M, 1, 1),
+                                             psi_flat.index_select(1, psi_idx[off:off + n]).view(B * n, -1, 1, 1),
+                                             layers)
+            L.check(lib.lic_rans_decode_step(F_._ptr(d_buf), F_._ptr(d_soff), F_._ptr(d_slen), F_._ptr(d_esc),
+                                             F_._ptr(d_eoff), F_._ptr(d_state), F_._ptr(tables), F_._ptr(center),
+                                             B, n, M, self.y_W, F_._ptr(own_idx[off:off + n]), F_._ptr(yflat), npad,
+                                             F_._stream()), "lic_rans_decode_step")
+            off += n
+        st = d_state.cpu().numpy().view(np.uint32)                                        # the one read-back
+        for b in range(B):
+            if st[b, RANS_LANES + 2] != 0:
+                raise CodecError(f"image {b}: the rANS decoder ran past the end of its stream or escape list "
+                                 f"(error word {int(st[b, RANS_LANES + 2])}): the stream is damaged")
+            if (st[b, RANS_LANES] != (len(ys[b]) - head) // 2 or st[b, RANS_LANES + 1] != len(escs[b]) // 4
+                    or (st[b, :RANS_LANES] != 1 << 16).any()):
+                raise CodecError(f"image {b}: the rANS stream was not used up exactly (trailing words or escapes, "
+                                 "or final states that are not the encoder's start): the stream is damaged")
+
+    def _finish(self, strings, ypad, z_hat, shape) -> Dict:
+        """checksum of the decoded latents, then the synthesis transform"""
+        m, p = self.model, self.pad
+        B, M, h, w = shape
         if "y_crc32" in strings:
             got = ypad[:, p:p + h, p:p + w, :].reshape(B, h * w * M).round().to(torch.int32).cpu().numpy()
             for b in range(B):
@@ -394,28 +536,40 @@ class ContextCodec:
         return BITSTREAM_FAMILIES[name]
 
     @torch.no_grad()
-    def compress_image(self, x: torch.Tensor, mode: str = "replicate", align: str = "topleft") -> bytes:
+    def compress_image(self, x: torch.Tensor, mode: str = "replicate", align: str = "topleft",
+                       coder: str = None) -> bytes:
         """x [B,3,H,W] of ANY size -> one byte string that `decompress_image` decodes by itself.  The image is padded
         to multiples of 64 (`functional.pad_to_multiple`) and the payload is exactly what `compress` produces for
         the padded tensor; the header (`pack_bitstream`) carries everything the decoder needs to rebuild the
         shapes and to crop back.  bpp_coded of the result is 8 * len(data) / (B * H * W): header and checksums
-        included, per ORIGINAL pixel."""
+        included, per ORIGINAL pixel.  `coder`: None = this codec's own; "range" writes a LICBITS1 container,
+        "rans" a LICBITS2 one (`pack_bitstream_rans`)."""
         if x.dim() != 4:
             raise CodecError("expected a [B,3,H,W] tensor")
+        if coder is not None and coder != self.coder:
+            return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder).compress_image(x, mode, align)
         B, _, H, W = x.shape
         _, _, top, left = F_.pad_geometry(H, W, 64, align)
         r = self.compress(F_.pad_to_multiple(x, 64, mode, align))
         s = r["strings"]
         head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
                 "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
+        if self.coder == "rans":
+            return pack_bitstream_rans(head, s["z"], s["y"], s["y_esc"], s["y_crc32"])
         return pack_bitstream(head, s["z"], s["y"], s["y_crc32"])
 
     @torch.no_grad()
     def decompress_image(self, data: bytes) -> torch.Tensor:
         """The inverse of `compress_image`: x_hat [B,3,H,W] (channels_last).  Raises CodecError, before any GPU
         work, for a bad magic, a truncated buffer, a failing CRC or a header whose family / M / K are not this
-        model's."""
-        head, z_bytes, y_streams, y_crc = unpack_bitstream(data)
+        model's.  The magic selects the coder, whatever this codec's own is."""
+        strings = {}
+        if bytes(data[:8]) == BITSTREAM_MAGIC_RANS:
+            head, z_bytes, y_streams, y_esc, y_crc = unpack_bitstream_rans(data)
+            strings.update(coder="rans", y_esc=y_esc)
+        else:
+            head, z_bytes, y_streams, y_crc = unpack_bitstream(data)
+        strings.update(y=y_streams, z=z_bytes, y_crc32=y_crc)
         m = self.model
         if (head["family"], head["M"], head["K"]) != (self._family(), m.M, m.K):
             raise CodecError(f"bitstream was written by family {head['family']} with M={head['M']}, K={head['K']}; "
@@ -424,9 +578,8 @@ class ContextCodec:
         Hp, Wp = -(-H // 64) * 64, -(-W // 64) * 64
         dec = self
         if (head["z_lo"], head["z_S"], head["y_W"]) != (self.z_lo, self.z_S, self.y_W):
-            dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"])
-        out = dec.decompress({"y": y_streams, "z": z_bytes, "y_crc32": y_crc}, (B, m.M, Hp // 16, Wp // 16),
-                             (B, m.M, Hp // 64, Wp // 64))
+            dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"], self.coder)
+        out = dec.decompress(strings, (B, m.M, Hp // 16, Wp // 16), (B, m.M, Hp // 64, Wp // 64))
         return F_.crop_window(out["x_hat"], top, left, H, W)
 
 
@@ -473,12 +626,7 @@ def unpack_bitstream(data: bytes):
     at += 8 * B
     if len(data) != at + z_len + sum(n for n, _ in table) + 4:
         raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
-    if zlib.crc32(data[:-4]) & 0xFFFFFFFF != struct.unpack_from("<I", data, len(data) - 4)[0]:
-        raise CodecError("bitstream is damaged (CRC-32 mismatch)")
-    if not (head["H"] > 0 and head["W"] > 0 and head["top"] < 64 and head["left"] < 64
-            and head["top"] + head["H"] <= -(-head["H"] // 64) * 64 and head["left"] + head["W"] <= -(-head["W"] // 64) * 64
-            and head["M"] > 0 and head["K"] > 0 and head["z_S"] > 0 and head["y_W"] > 0):
-        raise CodecError("bitstream header is inconsistent")
+    _check_crc_and_head(data, head)
     z_bytes = data[at:at + z_len]
     at += z_len
     ys = []
@@ -486,3 +634,72 @@ def unpack_bitstream(data: bytes):
         ys.append(data[at:at + n])
         at += n
     return head, z_bytes, ys, [c for _, c in table]
+
+
+def _check_crc_and_head(data: bytes, head: Dict):
+    """the checks both containers share: the trailing CRC-32 and a header that can be right"""
+    if zlib.crc32(data[:-4]) & 0xFFFFFFFF != struct.unpack_from("<I", data, len(data) - 4)[0]:
+        raise CodecError("bitstream is damaged (CRC-32 mismatch)")
+    if not (head["H"] > 0 and head["W"] > 0 and head["top"] < 64 and head["left"] < 64
+            and head["top"] + head["H"] <= -(-head["H"] // 64) * 64 and head["left"] + head["W"] <= -(-head["W"] // 64) * 64
+            and head["M"] > 0 and head["K"] > 0 and head["z_S"] > 0 and head["y_W"] > 0):
+        raise CodecError("bitstream header is inconsistent")
+
+
+# ---------------------------------------------------------------------------------------------
+# Container of the "rans" coder.  The LICBITS1 layout with three additions:
+#   magic b"LICBITS2" | the LICBITS1 header fields | uint32 z-stream length | uint32 lanes (64)
+#   | B x (uint32 y-stream length, uint32 CRC-32 of the latent symbols, uint32 escape count)
+#   | z stream | for image 0 .. B-1: y stream, then its escape list (uint32 each) | uint32 CRC-32 of all before it
+# `lanes` is the interleaving of the y streams: a decoder that meets a value it does not implement raises
+# CodecError, so wider interleaving later needs no new magic.
+# ---------------------------------------------------------------------------------------------
+BITSTREAM_MAGIC_RANS = b"LICBITS2"
+_BITS_HEAD_RANS = struct.Struct("<8sIIIiIIIIIIIII")
+
+
+def pack_bitstream_rans(head: Dict, z_bytes: bytes, y_streams, y_esc, y_crc32, lanes: int = RANS_LANES) -> bytes:
+    """`head`: the _BITS_FIELDS; one y stream, one escape list (bytes, uint32 each) and one symbol checksum per image"""
+    if len(y_streams) != head["B"] or len(y_crc32) != head["B"] or len(y_esc) != head["B"]:
+        raise CodecError("one y stream, one escape list and one checksum per image expected")
+    if any(len(e) % 4 for e in y_esc):
+        raise CodecError("an escape list is not a whole number of uint32")
+    parts = [_BITS_HEAD_RANS.pack(BITSTREAM_MAGIC_RANS, *(int(head[k]) for k in _BITS_FIELDS), len(z_bytes), int(lanes))]
+    parts += [struct.pack("<III", len(s), int(c) & 0xFFFFFFFF, len(e) // 4)
+              for s, c, e in zip(y_streams, y_crc32, y_esc)]
+    parts += [bytes(z_bytes)]
+    for s, e in zip(y_streams, y_esc):
+        parts += [bytes(s), bytes(e)]
+    body = b"".join(parts)
+    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+
+
+def unpack_bitstream_rans(data: bytes):
+    """-> (head dict, z_bytes, [y stream per image], [escape list per image], [symbol checksum per image]);
+    CodecError as `unpack_bitstream`, and for a `lanes` value other than 64."""
+    data = bytes(data)
+    if len(data) < _BITS_HEAD_RANS.size + 4:
+        raise CodecError("bitstream is truncated (shorter than its header)")
+    vals = _BITS_HEAD_RANS.unpack_from(data, 0)
+    if vals[0] != BITSTREAM_MAGIC_RANS:
+        raise CodecError("not a LICBITS2 bitstream (bad magic)")
+    head = dict(zip(_BITS_FIELDS, vals[1:-2]))
+    z_len, lanes, B = vals[-2], vals[-1], head["B"]
+    at = _BITS_HEAD_RANS.size
+    if B == 0 or len(data) < at + 12 * B + 4:
+        raise CodecError("bitstream is truncated (per-image table)")
+    table = [struct.unpack_from("<III", data, at + 12 * b) for b in range(B)]
+    at += 12 * B
+    if len(data) != at + z_len + sum(n + 4 * e for n, _, e in table) + 4:
+        raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
+    _check_crc_and_head(data, head)
+    if lanes != RANS_LANES:
+        raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements {RANS_LANES}")
+    z_bytes = data[at:at + z_len]
+    at += z_len
+    ys, es = [], []
+    for n, _, e in table:
+        ys.append(data[at:at + n])
+        es.append(data[at + n:at + n + 4 * e])
+        at += n + 4 * e
+    return head, z_bytes, ys, es, [c for _, c, _ in table]

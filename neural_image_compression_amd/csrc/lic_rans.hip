@@ -1,0 +1,221 @@
+// lic_rans_decode_step: one wavefront step of the "rANS-64" y streams (include/lic_codec.h) decoded where the
+// tables are built, so codec.ContextCodec's step loop needs no copy to the host, no synchronisation and no host
+// arithmetic.
+//
+// One wave per image: lane l owns coder state l.  A round decodes 64 symbols: each lane searches its own table
+// row for the 16-bit slot of its state, updates the state, and the lanes that fell below 2^16 share the stream
+// with one ballot (who needs a word), one popcount (rank among them) and a wave-uniform cursor.
+//
+// Latency, not bandwidth, paces this kernel, so every global load is issued ahead of its use:
+//  * a round's 64 table rows are contiguous (64 * (S+1) * 4 bytes); they are fetched with 16-byte loads into
+//    registers one round ahead (the tables do not depend on what this step decodes) and dropped into LDS after the
+//    current round has been searched;
+//  * the next 64 stream words (a round consumes at most 64) are loaded at the start of the round, one per lane,
+//    and a needing lane takes the word of lane `rank` by shuffle: no load depends on the search;
+//  * centres and destination indices depend on the symbol number only.
+// LDS row stride is S+2 dwords: S+1 = 2W+2 is even, and with an even stride the 64 lanes' first probe (the same
+// column of 64 rows) would land on 16 of ds_read_b32's 32 banks; an odd stride spreads a 32-lane group over all 32.
+// With that stride element `rel` of the round (row rel / (S+1)) sits at LDS dword rel + row.
+//
+// Nothing outside the given buffers is ever read: a word or escape is read only after cursor + rank has been
+// compared with the image's length; otherwise the image's error word is set and every later symbol decodes as
+// its table centre.  Destination indices outside [0, pixels) are not written and set the error word too.
+#include "lic_common.h"
+
+namespace {
+
+constexpr int kLanes = 64;
+constexpr int kStateWords = LIC_RANS_STATE_WORDS;
+
+// NQ: 16-byte table pieces a lane holds for one round; S1MAX: largest S+1 that fits
+template <int NQ, int S1MAX>
+__global__ __launch_bounds__(64) void rans_step_kernel(const uint8_t* __restrict__ streams,
+                                                       const int64_t* __restrict__ stream_off,
+                                                       const int64_t* __restrict__ stream_bytes,
+                                                       const uint32_t* __restrict__ escapes,
+                                                       const int64_t* __restrict__ esc_off, uint32_t* state,
+                                                       const uint32_t* __restrict__ tables,
+                                                       const int32_t* __restrict__ center, int32_t nsym, int32_t M,
+                                                       int32_t W, const int64_t* __restrict__ dest, float* ypad,
+                                                       int64_t pixels, int64_t total_dwords) {
+  __shared__ uint32_t lds[kLanes * (S1MAX + 1)];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int S1 = 2 * W + 2, S = S1 - 1, stride = S1 + 1;
+  const uint32_t inv = ((1u << 24) + S1 - 1) / S1;  // rel / S1 == (rel * inv) >> 24 for rel < 64 * S1 <= 2^14
+
+  uint32_t* st = state + (size_t)b * kStateWords;
+  uint32_t x = st[lane];
+  uint32_t ptr = st[kLanes], eptr = st[kLanes + 1], err = st[kLanes + 2];
+  const int64_t o0 = stream_off[b], room = stream_off[b + 1] - o0;
+  int64_t len = stream_bytes[b];
+  if (len > room || len < kLanes * 4 || o0 < 0) {
+    err |= LIC_RANS_ERR_STREAM;
+    len = kLanes * 4;
+  }
+  const uint16_t* words = reinterpret_cast<const uint16_t*>(streams + (o0 < 0 ? 0 : o0) + kLanes * 4);
+  const uint64_t nwords = (uint64_t)(len - kLanes * 4) >> 1;
+  const int64_t e0 = esc_off[b], e1 = esc_off[b + 1];
+  const uint64_t nesc = (e0 >= 0 && e1 >= e0) ? (uint64_t)(e1 - e0) : 0;
+  const uint32_t* esc = escapes + (e0 < 0 ? 0 : e0);
+
+  const int rounds = (nsym + kLanes - 1) / kLanes;
+  const int64_t gbase = (int64_t)b * nsym * S1;  // this image's first table dword
+  uint4 pre[NQ];
+
+  // global -> registers: the dwords [g0, g1) of round r, fetched as the 16-byte pieces that cover them
+  auto fetch = [&](int r) {
+    const int64_t g0 = gbase + (int64_t)r * kLanes * S1;
+    const int rows = min(kLanes, nsym - r * kLanes);
+    const int64_t a0 = g0 & ~(int64_t)3;
+    const int nq = (int)((g0 + (int64_t)rows * S1 - a0 + 3) >> 2);
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      const int q = lane + kLanes * i;
+      if (q < nq) {
+        const int64_t e = a0 + 4 * (int64_t)q;
+        if (e + 4 <= total_dwords) {
+          pre[i] = *reinterpret_cast<const uint4*>(tables + e);
+        } else {  // the buffer's last, partial piece
+          pre[i].x = e < total_dwords ? tables[e] : 0u;
+          pre[i].y = e + 1 < total_dwords ? tables[e + 1] : 0u;
+          pre[i].z = e + 2 < total_dwords ? tables[e + 2] : 0u;
+          pre[i].w = 0u;
+        }
+      }
+    }
+  };
+  // registers -> LDS rows of S1 dwords at a pitch of S1 + 1
+  auto drop = [&](int r) {
+    const int64_t g0 = gbase + (int64_t)r * kLanes * S1;
+    const int rows = min(kLanes, nsym - r * kLanes);
+    const int head = (int)(g0 & 3), lim = rows * S1;
+    const int nq = (head + lim + 3) >> 2;
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+      const int q = lane + kLanes * i;
+      if (q < nq) {
+        const int rel0 = 4 * q - head;  // >= -3
+        int row = rel0 > 0 ? (int)(((uint32_t)rel0 * inv) >> 24) : 0;
+        int col = rel0 - row * S1;
+        const uint32_t v[4] = {pre[i].x, pre[i].y, pre[i].z, pre[i].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int rel = rel0 + j;
+          if (rel >= 0 && rel < lim) lds[rel + row] = v[j];
+          if (++col == S1) {
+            col = 0;
+            ++row;
+          }
+        }
+      }
+    }
+  };
+
+  fetch(0);
+  drop(0);
+  __syncthreads();
+  for (int r = 0; r < rounds; ++r) {
+    const int k = r * kLanes + lane;
+    const bool active = k < nsym;
+    // loads that do not depend on the search, oldest first so that waiting for them leaves the prefetch in flight
+    const uint64_t wi = (uint64_t)ptr + lane;
+    const uint32_t wpre = (err == 0 && wi < nwords) ? (uint32_t)words[wi] : 0u;
+    const int32_t c = active ? center[(int64_t)b * nsym + k] : 0;
+    const int64_t d = active ? dest[k / M] : 0;
+    if (r + 1 < rounds) fetch(r + 1);
+
+    int s = W;  // the table centre: what an image in error decodes
+    bool bad = false;
+    uint32_t excess = 0;
+    if (err == 0) {
+      const uint32_t slot = x & 0xFFFFu;
+      const uint32_t* row = lds + lane * stride;
+      int lo = 0, hi = S;  // largest s with cum[s] <= slot
+      if (active) {
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (row[mid] <= slot)
+            lo = mid;
+          else
+            hi = mid;
+        }
+        const uint32_t start = row[lo], freq = row[lo + 1] - start;
+        x = freq * (x >> 16) + slot - start;
+        s = lo;
+      }
+      // renormalisation: one ballot, one popcount, one shuffle of the prefetched words
+      const bool need = active && x < 65536u;
+      const unsigned long long mask = __ballot(need);
+      const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+      const uint32_t w = __shfl(wpre, rank, kLanes);
+      if (need) {
+        if ((uint64_t)ptr + rank < nwords)
+          x = (x << 16) | w;
+        else
+          bad = true;
+      }
+      ptr += (uint32_t)__popcll(mask);
+      // escapes: the same rule on a second cursor; rare, so their load may depend on the search
+      const bool edge = active && (s == 0 || s == S - 1);
+      const unsigned long long emask = __ballot(edge);
+      if (emask != 0ull) {
+        const int erank = __popcll(emask & ((1ull << lane) - 1ull));
+        if (edge) {
+          if ((uint64_t)eptr + erank < nesc)
+            excess = esc[(uint64_t)eptr + erank];
+          else
+            bad = true;
+        }
+        eptr += (uint32_t)__popcll(emask);
+      }
+    }
+    if (active) {
+      int64_t v = (int64_t)s + c - W;
+      if (s == 0) v -= excess;
+      if (s == S - 1) v += excess;
+      if (d >= 0 && d < pixels)
+        ypad[((int64_t)b * pixels + d) * M + (k % M)] = (float)v;
+      else
+        bad = true;
+    }
+    if (__any(bad)) err |= LIC_RANS_ERR_RANGE;
+    __syncthreads();  // every lane has finished searching this round's rows
+    if (r + 1 < rounds) {
+      drop(r + 1);
+      __syncthreads();
+    }
+  }
+  st[lane] = x;
+  if (lane == 0) {
+    st[kLanes] = ptr;
+    st[kLanes + 1] = eptr;
+    st[kLanes + 2] = err;
+  }
+}
+
+}  // namespace
+
+LIC_EXPORT int lic_rans_decode_step(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
+                                    const uint32_t* escapes, const int64_t* esc_off, uint32_t* state,
+                                    const uint32_t* tables, const int32_t* center, int32_t B, int32_t n, int32_t M,
+                                    int32_t W, const int64_t* dest, float* ypad, int64_t pixels,
+                                    lic_stream_t stream) {
+  if (!streams || !stream_off || !stream_bytes || !escapes || !esc_off || !state || !tables || !center || !dest || !ypad)
+    return LIC_ERR_INVALID;
+  if (B <= 0 || n <= 0 || M <= 0 || W <= 0 || pixels <= 0) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(tables) & 15) || (reinterpret_cast<uintptr_t>(streams) & 3)) return LIC_ERR_INVALID;
+  if (W > 64) return LIC_ERR_UNSUPPORTED;
+  const int64_t nsym = (int64_t)n * M;
+  if (nsym > 0x7FFFFFFFL - kLanes || (int64_t)B > 65535) return LIC_ERR_UNSUPPORTED;
+  const int64_t total = (int64_t)B * nsym * (2 * W + 2);
+  // a round spans 64 * (S+1) dwords plus up to 3 of misalignment: 17 pieces per lane for S+1 <= 66, 33 for <= 130
+  if (W <= 32)
+    hipLaunchKernelGGL((rans_step_kernel<17, 66>), dim3(B), dim3(kLanes), 0, (hipStream_t)stream, streams, stream_off,
+                       stream_bytes, escapes, esc_off, state, tables, center, (int32_t)nsym, M, W, dest, ypad, pixels,
+                       total);
+  else
+    hipLaunchKernelGGL((rans_step_kernel<33, 130>), dim3(B), dim3(kLanes), 0, (hipStream_t)stream, streams,
+                       stream_off, stream_bytes, escapes, esc_off, state, tables, center, (int32_t)nsym, M, W, dest,
+                       ypad, pixels, total);
+  return lic_check_launch();
+}

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Wall time of ContextCodec.compress / decompress on a Kodak-sized image (GPU only)."""
+"""Wall time of ContextCodec.compress / decompress on a Kodak-sized image (GPU only), per coder: warm, median of
+RUNS calls, the GPU synchronised around each call only.  Environment: M, K, H, W, CODERS (comma list), RUNS."""
 import os
+import statistics
 import sys
 import time
 
@@ -12,21 +14,34 @@ from neural_image_compression_amd.codec import ContextCodec  # noqa: E402
 
 M, K = int(os.environ.get("M", "192")), int(os.environ.get("K", "3"))
 H, W = int(os.environ.get("H", "512")), int(os.environ.get("W", "768"))
+CODERS = os.environ.get("CODERS", "range,rans").split(",")
+RUNS = int(os.environ.get("RUNS", "10"))
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, 1e3 * (time.perf_counter() - t0)
+
+
 torch.manual_seed(0)
 model = nic.JointAutoregressiveHierarchical(M, K).cuda().eval()
 x = torch.rand(1, 3, H, W, device="cuda").contiguous(memory_format=torch.channels_last)
-cc = ContextCodec(model)
-for it in range(2):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    enc = cc.compress(x)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    dec = cc.decompress(enc["strings"], enc["shape"], enc["z_shape"])
-    torch.cuda.synchronize()
-    t2 = time.perf_counter()
+for coder in CODERS:
+    cc = ContextCodec(model, coder=coder)
+    for _ in range(2):                                                       # warm: allocator, weight packs, tuning
+        enc = cc.compress(x)
+        dec = cc.decompress(enc["strings"], enc["shape"], enc["z_shape"])
     ok = torch.equal(dec["y_hat"], enc["y_in"])
+    t_enc = [timed(lambda: cc.compress(x))[1] for _ in range(RUNS)]
+    t_dec = [timed(lambda: cc.decompress(enc["strings"], enc["shape"], enc["z_shape"]))[1] for _ in range(RUNS)]
+    s = enc["strings"]
+    nbytes = len(s["z"]) + sum(map(len, s["y"])) + sum(map(len, s.get("y_esc", [])))
     npx = enc["shape"][2] * enc["shape"][3]
-    print(f"JAH({M},{K}) {H}x{W}: compress {1e3 * (t1 - t0):8.1f} ms, decompress {1e3 * (t2 - t1):8.1f} ms "
-          f"({1e6 * (t2 - t1) / npx:6.1f} us per latent pixel, {npx} pixels), round trip {'ok' if ok else 'MISMATCH'}, "
-          f"bpp coded {enc['bpp_coded']:.4f} est {enc['bpp_est']:.4f}", flush=True)
+    md = statistics.median(t_dec)
+    print(f"JAH({M},{K}) {H}x{W} coder={coder}: compress {statistics.median(t_enc):8.2f} ms, decompress {md:8.2f} ms "
+          f"(min {min(t_dec):.2f}, max {max(t_dec):.2f}, median of {RUNS}; {1e3 * md / npx:6.1f} us per latent pixel, "
+          f"{npx} pixels), round trip {'ok' if ok else 'MISMATCH'}, {nbytes} bytes, bpp coded {enc['bpp_coded']:.4f} "
+          f"est {enc['bpp_est']:.4f}", flush=True)
