@@ -434,6 +434,57 @@ int lic_rans_decode_step(const uint8_t* streams, const int64_t* stream_off, cons
                          float* ypad, int64_t pixels, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2 -- the device encoder of the same streams: byte for byte what the host encoder of lic_codec.h
+ *   writes, from the tables where lic_gmm_cdf_tables left them, so no table ever travels to the host.  Two
+ *   launches per batch on one stream, lic_rans_encode_pick then lic_rans_encode.  (This lic_rans_encode is the
+ *   entry of the device library; the host coder of the same name lives in the host library of lic_codec.h.  The
+ *   two headers describe two libraries and are not meant for one translation unit.)
+ *
+ *   lic_rans_encode_pick -- the parallel half, one thread per symbol.  Image b has P pixels of M channels, nsym =
+ *   P * M symbols; symbol k in CODING order is pixel order[k / M], channel k % M.
+ *     tables        [B][P*M][2W+2] and center [B*P][M]: lic_gmm_cdf_tables' outputs, raster pixel order, as written
+ *     y             [B][P][M] int32: the integer latents, pixel-major (the rounded symbols, not fp32)
+ *     order         [P] int64 (device): the raster pixel of every position of the coding order (the wavefront
+ *                   steps of codec.ContextCodec, concatenated), each in [0, P)
+ *     sf            [B][nsym] uint32 out, coding order: cum[s] << 16 | (cum[s+1] - cum[s]) of the coded symbol
+ *                   s = clamp(idx, 0, S-1), idx = y - center + W in 32-bit two's complement, S = 2W+1
+ *     exc           [B][nsym] uint32 out, coding order: the escape excess (-idx for idx <= 0, idx - (S-1) for
+ *                   idx >= S-1; idx == 0 and idx == S-1 escape with excess 0) or 0xFFFFFFFF for no escape; the
+ *                   largest real excess is 2^31
+ *     state         [B][LIC_RANS_STATE_WORDS] uint32: only the error word (the last) is touched here, by atomic OR.
+ *                   The caller ZEROES every image's error word before this launch.
+ *   Every symbol's table is validated as the host does: cum[0] == 0, cum[S] == 65536, 0 < freq < 65536 (and
+ *   cum[s] < 65536, which a table that passes the others can only miss by not being monotone); order entries must
+ *   lie in [0, P).  A violation sets LIC_RANS_ERR_RANGE in that image's error word and codes that symbol as
+ *   (start 0, freq 1) without an escape, so that lic_rans_encode never divides by zero; other images are not
+ *   affected.  An order entry is compared before it indexes anything: nothing outside the buffers is read.
+ *   W <= 64, B <= 65535, nsym < 2^31 - 64 (LIC_ERR_UNSUPPORTED otherwise); every buffer 4-byte aligned, order 8.
+ *
+ *   lic_rans_encode -- the serial half, one 64-lane wave per image, lane l owns coder state l.
+ *     sf, exc       lic_rans_encode_pick's outputs
+ *     step_len      [nsteps] int64 (device), in symbols; zero-length steps are allowed; non-negative, summing to nsym
+ *     words         [B][slot] bytes out; slot >= 2 * nsym, a multiple of 4 (lic_rans_bound(nsym) of lic_codec.h
+ *                   rounded up to 4 serves).  Image b's 16-bit words, in reading order, END at the end of its
+ *                   slot: bytes [slot - 2 * count, slot) of the slot; the bytes before them are not touched.
+ *     esc_out       [B][nsym] uint32 out: image b's escape list in symbol order, its first `escape count` entries;
+ *                   the rest is not touched
+ *     state         [B][LIC_RANS_STATE_WORDS] uint32, the decoder's block layout: the 64 FINAL coder states (lane 0
+ *                   first), the word count, the escape count, the error word (read at entry: pick's bits stay).
+ *   The host assembles image b's stream as  64 little-endian states + its `word count` words;  that is
+ *   lic_rans_encode's stream of lic_codec.h, and esc_out[b][:escape count] its escape list.
+ *   Step lengths that are negative or do not add up to nsym set LIC_RANS_ERR_RANGE and code nothing (states 2^16,
+ *   counts 0).  The word cursor is compared with the slot's first byte before every store; a slot as above cannot
+ *   run out (at most one word per symbol), if it did the error word would say so and the store would not happen.
+ *   One launch each, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+int lic_rans_encode_pick(const uint32_t* tables, const int32_t* center, const int32_t* y, const int64_t* order,
+                         int32_t B, int64_t P, int32_t M, int32_t W, uint32_t* sf, uint32_t* exc, uint32_t* state,
+                         lic_stream_t stream);
+int lic_rans_encode(const uint32_t* sf, const uint32_t* exc, const int64_t* step_len, int64_t nsteps, int32_t B,
+                    int64_t nsym, uint8_t* words, int64_t slot, uint32_t* esc_out, uint32_t* state,
+                    lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).1 -- evaluation metric on the device.
  * Multi-scale SSIM exactly as the reference's evaluator calls it (Evaluator.py:7,38,45:
  * `ms_ssim(recon, orig, data_range=1.0, size_average=True)` of the third-party pytorch-msssim==0.2.1,

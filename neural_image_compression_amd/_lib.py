@@ -162,6 +162,8 @@ SIGNATURES = {
     "lic_factorized_cdf_tables": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "lic_gmm_cdf_tables": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "lic_rans_decode_step": (C.c_int, [_vp] * 8 + [_i32] * 4 + [_vp, _vp, _i64, _vp]),
+    "lic_rans_encode_pick": (C.c_int, [_vp] * 4 + [_i32, _i64, _i32, _i32] + [_vp] * 4),
+    "lic_rans_encode": (C.c_int, [_vp] * 3 + [_i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
     "lic_msssim_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "lic_msssim": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _sz,
                              _vp]),

@@ -18,6 +18,8 @@ self-describing byte string (`pack_bitstream`: header, per-image lengths and che
 `ContextCodec(..., coder="rans")` codes the y streams with the 64-lane interleaved rANS coder of lic_codec.h
 instead: its decoder is a device kernel (`lic_rans_decode_step`), so the decode loop has no host in it; the
 container of that coder is `pack_bitstream_rans` (magic LICBITS2).  The range coder stays the default and codes z.
+With `encoder="device"` that coder's encoder runs on the device as well (`lic_rans_encode_pick` + `lic_rans_encode`):
+the same bytes, and no table is copied to the host.
 """
 from __future__ import annotations
 
@@ -115,6 +117,7 @@ def rc_ideal_bits(tables: np.ndarray, idx: np.ndarray, table_of: np.ndarray = No
 # ---- the interleaved rANS coder of the y streams (lic_codec.h "rANS-64") ---------------------
 RANS_LANES = 64
 CODERS = ("range", "rans")
+ENCODERS = ("host", "device")
 
 
 def rans_encode(tables: np.ndarray, idx: np.ndarray, step_len) -> tuple:
@@ -293,12 +296,23 @@ class ContextCodec:
     `coder`: "range" (the default) codes y with the host range coder as described above; "rans" codes y with
     the 64-lane interleaved rANS coder of lic_codec.h, whose decoder is a device kernel
     (`lic_rans_decode_step`): the step loop is then {gather -> per-pixel layers -> tables -> decode}, all
-    asynchronous launches, and the host reads back one small block after the last step.  z keeps the range coder."""
+    asynchronous launches, and the host reads back one small block after the last step.  z keeps the range coder.
 
-    def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range"):
+    `encoder`: where `compress` codes the y streams.  "host" (the default) gathers the tables into wavefront order,
+    copies them to the host and runs the C++ encoder, one image after the other; "device" (coder "rans" only) runs
+    `lic_rans_encode_pick` + `lic_rans_encode` on the tables where they were built and copies back state blocks,
+    streams and escape lists only.  Both write the same bytes."""
+
+    def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range",
+                 encoder: str = "host"):
         if coder not in CODERS:
             raise CodecError(f"unknown coder {coder!r}: expected one of {CODERS}")
+        if encoder not in ENCODERS:
+            raise CodecError(f"unknown encoder {encoder!r}: expected one of {ENCODERS}")
+        if encoder == "device" and coder != "rans":
+            raise CodecError(f"encoder='device' needs coder='rans': the {coder!r} coder has no device encoder")
         self.model, self.z_lo, self.z_S, self.y_W, self.coder = model, int(z_lo), int(z_S), int(y_W), coder
+        self.encoder = encoder
         mc = model.context_model.masked
         k = mc.kernel_size[0]
         self.taps = [(r, s) for r in range(k) for s in range(k) if (mc._tap_mask >> (r * k + s)) & 1]
@@ -381,17 +395,28 @@ class ContextCodec:
         y_sym = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
         # symbols leave in the decoder's wavefront order (see _wavefront), M channels per pixel
         steps = self._wavefront(h, w)
-        perm = torch.from_numpy(np.concatenate([ii * w + jj for ii, jj in steps])).to(y_in.device)
+        order = np.concatenate([ii * w + jj for ii, jj in steps])
+        step_len = [len(ii) * M for ii, _ in steps]
+        strings = {"z": z_bytes}
+        if self.encoder == "device":
+            y_streams, y_esc = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, M)
+            strings.update(coder="rans", y_esc=y_esc)
+            return self._compressed(x, out, strings, y_streams, y_esc, y_sym, y_in, z_in)
+        perm = torch.from_numpy(order).to(y_in.device)
         idx = (y_sym - center + self.y_W).view(B, h * w, M)[:, perm].cpu().numpy().reshape(B, h * w * M)
         tabs = tables.view(B, h * w, M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * M, -1)
-        strings = {"z": z_bytes}
         if self.coder == "rans":
-            step_len = [len(ii) * M for ii, _ in steps]
             pairs = [rans_encode(tabs[b], idx[b], step_len) for b in range(B)]
             y_streams, y_esc = [p[0] for p in pairs], [p[1] for p in pairs]
             strings.update(coder="rans", y_esc=y_esc)
         else:
             y_streams, y_esc = [rc_encode(tabs[b], idx[b]) for b in range(B)], []
+        return self._compressed(x, out, strings, y_streams, y_esc, y_sym, y_in, z_in)
+
+    def _compressed(self, x, out, strings, y_streams, y_esc, y_sym, y_in, z_in) -> Dict:
+        """what `compress` returns, from the coded streams: sizes, the estimate and the symbol checksums"""
+        z_bytes = strings["z"]
+        B, M, h, w = y_in.shape
         npix = x.shape[0] * x.shape[2] * x.shape[3]
         coded = 8.0 * (len(z_bytes) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
         est = float(-(out["logp_y"].double().sum() + out["logp_z"].double().sum()) / np.log(2.0) / npix)
@@ -403,6 +428,43 @@ class ContextCodec:
         return {"strings": strings, "shape": (B, M, h, w),
                 "z_shape": tuple(z_in.shape),
                 "bpp_coded": coded, "bpp_est": est, "y_in": y_in, "z_in": z_in}
+
+    def _encode_y_device(self, tables, center, y_sym, order, step_len, B: int, P: int, M: int):
+        """The y streams of the "rans" coder without the host encoder: `lic_rans_encode_pick` turns tables (raster
+        order, where `_params_at` left them), centres and symbols into one start|freq word and one escape word per
+        symbol in wavefront order, `lic_rans_encode` codes them, one wave per image.  Order and step lengths go up
+        once; the state blocks (final states, word count, escape count, error word) come back once, then exactly the
+        used bytes of every slot and escape list.  -> ([stream bytes per image], [escape-list bytes per image])"""
+        dev = tables.device
+        nsym = P * M
+        slot = (4 * RANS_LANES + 2 * nsym + 3) // 4 * 4                         # lic_rans_bound, whole dwords
+        d_order = torch.from_numpy(np.ascontiguousarray(order, np.int64)).to(dev)
+        d_steps = torch.from_numpy(np.asarray(step_len, np.int64)).to(dev)
+        sf = torch.empty((B, nsym), device=dev, dtype=torch.int32)
+        exc, esc = torch.empty_like(sf), torch.empty_like(sf)
+        words = torch.empty((B, slot), device=dev, dtype=torch.uint8)
+        state = torch.zeros((B, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
+        y_sym = y_sym.contiguous()
+        lib = L.load()
+        L.check(lib.lic_rans_encode_pick(F_._ptr(tables), F_._ptr(center), F_._ptr(y_sym), F_._ptr(d_order), B, P, M,
+                                         self.y_W, F_._ptr(sf), F_._ptr(exc), F_._ptr(state), F_._stream()),
+                "lic_rans_encode_pick")
+        L.check(lib.lic_rans_encode(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), len(step_len), B, nsym,
+                                    F_._ptr(words), slot, F_._ptr(esc), F_._ptr(state), F_._stream()),
+                "lic_rans_encode")
+        st = state.cpu().numpy().view(np.uint32)                                  # the one read-back that waits
+        for b in range(B):
+            if st[b, RANS_LANES + 2] != 0:
+                raise CodecError(f"image {b}: the rANS encoder met a malformed table, a pixel index outside the "
+                                 f"image or step lengths that do not add up (error word {int(st[b, RANS_LANES + 2])})")
+        streams, escs = [], []
+        for b in range(B):
+            nw, ne = int(st[b, RANS_LANES]), int(st[b, RANS_LANES + 1])
+            if 2 * nw > slot or ne > nsym:
+                raise CodecError(f"image {b}: the rANS encoder reports impossible counts ({nw} words, {ne} escapes)")
+            streams.append(st[b, :RANS_LANES].astype("<u4").tobytes() + words[b, slot - 2 * nw:].cpu().numpy().tobytes())
+            escs.append(esc[b, :ne].cpu().numpy().view(np.uint32).astype("<u4").tobytes())
+        return streams, escs
 
     @torch.no_grad()
     def decompress(self, strings: Dict, shape, z_shape) -> Dict:
@@ -547,7 +609,9 @@ class ContextCodec:
         if x.dim() != 4:
             raise CodecError("expected a [B,3,H,W] tensor")
         if coder is not None and coder != self.coder:
-            return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder).compress_image(x, mode, align)
+            # the encoder goes with the coder it belongs to: only "rans" has a device encoder
+            enc = self.encoder if coder == "rans" else "host"
+            return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder, enc).compress_image(x, mode, align)
         B, _, H, W = x.shape
         _, _, top, left = F_.pad_geometry(H, W, 64, align)
         r = self.compress(F_.pad_to_multiple(x, 64, mode, align))

@@ -1,0 +1,226 @@
+// lic_rans_encode_pick + lic_rans_encode: the encoder of the "rANS-64" y streams (include/lic_codec.h) run where
+// lic_gmm_cdf_tables has left the tables, so codec.ContextCodec.compress copies streams, not tables, to the host.
+// Byte for byte the host encoder of lic_rans.cpp: same streams, same escape lists.
+//
+// An rANS encoder never searches: symbol k needs cum[s] and cum[s+1] of its own table, and neither its table nor
+// its symbol depends on a coder state.  So the work splits in two launches:
+//  * pick (one thread per symbol, any grid) resolves wavefront order -> raster pixel, clamps the symbol, validates
+//    the table as the host does and leaves one uint32 (start << 16 | freq) and one escape word per symbol, in
+//    coding order;
+//  * encode (one wave per image, lane l owns state l) walks those words.  Escapes first, forward: ballot, rank,
+//    a wave-uniform cursor.  Then the states, backward: steps and rounds last to first; the lanes whose state
+//    would overflow share the stream with one ballot (who emits), one popcount below the lane (rank) and a
+//    wave-uniform cursor that moves towards lower addresses.  Ascending lane id is reading order, which is what the
+//    host's "lanes 63 down to 0, towards lower addresses" produces.
+//
+// Latency on a single wave paces the second kernel, so nothing but the compare, the ballot, the word store and the
+// divide sits on the state's dependent chain: the start|freq words of the next kRing rounds are already in
+// registers (a ring the unrolled loop indexes statically), and the step lengths are read by the producer side of
+// that ring, kRing rounds ahead of their use.  An inactive lane of a partial round carries the word 0 (a real one
+// has freq >= 1), so the consumer needs no round geometry at all.
+//
+// Nothing outside the given buffers is read or written: pick checks every order entry before it indexes with it,
+// encode checks the step lengths (non-negative, summing to nsym) before it walks them and compares the word cursor
+// with the slot's first word before every store.
+#include "lic_common.h"
+
+namespace {
+
+constexpr int kLanes = LIC_RANS_LANES;
+constexpr int kStateWords = LIC_RANS_STATE_WORDS;
+constexpr int kRing = 8;                    // rounds of start|freq words in flight
+constexpr uint32_t kNoEscape = 0xFFFFFFFFu;  // the largest real excess is 2^31
+constexpr uint32_t kHarmless = 1u;           // start 0, freq 1: what a symbol in error codes
+
+__global__ __launch_bounds__(256) void rans_pick_kernel(const uint32_t* __restrict__ tables,
+                                                        const int32_t* __restrict__ center,
+                                                        const int32_t* __restrict__ y,
+                                                        const int64_t* __restrict__ order, int32_t P, int32_t M,
+                                                        int32_t W, int32_t nsym, uint32_t* __restrict__ sf,
+                                                        uint32_t* __restrict__ exc, uint32_t* state) {
+  const int b = blockIdx.y;
+  const int S1 = 2 * W + 2, S = S1 - 1;
+  bool bad = false;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nsym; k += (int64_t)gridDim.x * blockDim.x) {
+    const int pos = (int)k / M, c = (int)k - pos * M;
+    const int64_t pix = order[pos];
+    uint32_t word = kHarmless, excess = kNoEscape;
+    if (pix >= 0 && pix < P) {
+      const int64_t i = ((int64_t)b * P + pix) * M + c;
+      // two's complement, as the host path's int32 tensor arithmetic
+      const int32_t idx = (int32_t)((uint32_t)y[i] - (uint32_t)center[i] + (uint32_t)W);
+      const int32_t s = idx <= 0 ? 0 : (idx >= S - 1 ? S - 1 : idx);
+      if (idx <= 0) excess = (uint32_t)(-(int64_t)idx);
+      if (idx >= S - 1) excess = (uint32_t)((int64_t)idx - (S - 1));
+      const uint32_t* row = tables + i * S1;
+      const uint32_t first = row[0], last = row[S], start = row[s], end = row[s + 1];
+      if (first == 0u && last == 65536u && end > start && end - start < 65536u && start < 65536u)
+        word = (start << 16) | (end - start);
+      else
+        bad = true;
+    } else {
+      bad = true;
+    }
+    sf[(int64_t)b * nsym + k] = word;
+    exc[(int64_t)b * nsym + k] = excess;
+  }
+  // one atomic per wave at the most; the loop has ended for every lane here
+  if (__any(bad) && (threadIdx.x & (kLanes - 1)) == 0)
+    atomicOr(state + (size_t)b * kStateWords + kLanes + 2, LIC_RANS_ERR_RANGE);
+}
+
+// Producer side of the ring: the rounds of an image last to first, as (first symbol, active lanes).  Wave-uniform.
+struct RoundWalk {
+  const int64_t* step_len;
+  int64_t t;     // steps [0, t) are still whole
+  int32_t base;  // first symbol of step t
+  int32_t rem;   // symbols of step t not yet handed out, counted from its start
+  __device__ __forceinline__ bool next(int32_t& k0, int32_t& n) {
+    while (rem == 0 && t > 0) {
+      --t;
+      rem = (int32_t)step_len[t];
+      base -= rem;
+    }
+    if (rem == 0) return false;
+    const int32_t head = (rem - 1) & ~(kLanes - 1);  // where the step's last remaining round starts
+    k0 = base + head;
+    n = rem - head;
+    rem = head;
+    return true;
+  }
+};
+
+__global__ __launch_bounds__(64) void rans_encode_kernel(const uint32_t* __restrict__ sf,
+                                                         const uint32_t* __restrict__ exc,
+                                                         const int64_t* __restrict__ step_len, int64_t nsteps,
+                                                         int32_t nsym, uint8_t* __restrict__ words, int64_t slot,
+                                                         uint32_t* __restrict__ esc_out, uint32_t* state) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  sf += (int64_t)b * nsym;
+  exc += (int64_t)b * nsym;
+  esc_out += (int64_t)b * nsym;
+  uint32_t* st = state + (size_t)b * kStateWords;
+  uint32_t err = st[kLanes + 2];
+
+  // the step lengths must be non-negative and add up to nsym before anything is indexed with them
+  int64_t sum = 0, rounds = 0;
+  bool okl = true;
+  for (int64_t t = lane; t < nsteps; t += kLanes) {
+    const int64_t n = step_len[t];
+    if (n < 0 || n > nsym)
+      okl = false;
+    else
+      sum += n, rounds += (n + kLanes - 1) / kLanes;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o, kLanes);
+    rounds += __shfl_xor(rounds, o, kLanes);
+  }
+  if (!__all(okl) || sum != nsym) {
+    st[lane] = 1u << 16;
+    if (lane == 0) st[kLanes] = 0u, st[kLanes + 1] = 0u, st[kLanes + 2] = err | LIC_RANS_ERR_RANGE;
+    return;
+  }
+
+  // escapes, forward, in symbol order: rounds play no part in their order
+  uint32_t nesc = 0;
+  for (uint32_t k0 = 0; k0 < (uint32_t)nsym; k0 += kRing * kLanes) {
+    uint32_t e[kRing];
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {  // all loads first: none depends on the cursor
+      const uint32_t k = k0 + j * kLanes + lane;
+      e[j] = k < (uint32_t)nsym ? exc[k] : kNoEscape;
+    }
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {
+      const bool edge = e[j] != kNoEscape;
+      const unsigned long long mask = __ballot(edge);
+      if (edge) esc_out[nesc + (uint32_t)__popcll(mask & below)] = e[j];
+      nesc += (uint32_t)__popcll(mask);
+    }
+  }
+
+  // states, backward
+  uint16_t* wbuf = reinterpret_cast<uint16_t*>(words + (int64_t)b * slot);
+  const uint32_t wend = (uint32_t)(slot >> 1);
+  uint32_t wpos = wend;  // in 16-bit words from the slot's start; the words so far are [wpos, wend)
+  uint32_t x = 1u << 16;
+  RoundWalk walk{step_len, nsteps, nsym, 0};
+  // the ring: a round's raw words and its number of active lanes.  Exactly one load per round, taken or not (an
+  // idle lane reads word 0; it is dropped where the round is consumed): a load under a branch cannot be counted,
+  // and every wait for the ring would then wait for all of it
+  uint32_t ring[kRing];
+  int32_t live[kRing];
+  auto fetch = [&](int j) {
+    int32_t k0 = 0, n = 0;
+    walk.next(k0, n);  // leaves (0, 0) once the walk is over
+    ring[j] = sf[lane < n ? k0 + lane : 0];
+    live[j] = n;
+  };
+#pragma unroll
+  for (int j = 0; j < kRing; ++j) fetch(j);
+  for (int64_t r = 0; r < rounds; r += kRing) {
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {
+      const uint32_t w = lane < live[j] ? ring[j] : 0u;
+      fetch(j);  // the round kRing ahead; no lane is live once the walk is over
+      const uint32_t freq = w & 0xFFFFu, start = w >> 16;
+      const bool active = freq != 0u;
+      const bool emit = active && (x >> 16) >= freq;
+      const unsigned long long mask = __ballot(emit);
+      const uint32_t cnt = (uint32_t)__popcll(mask);
+      if (cnt > wpos) {  // cannot happen in a slot of lic_rans_bound(nsym) bytes: at most one word per symbol
+        err |= LIC_RANS_ERR_RANGE;
+      } else {
+        wpos -= cnt;
+        if (emit) {
+          wbuf[wpos + (uint32_t)__popcll(mask & below)] = (uint16_t)x;
+          x >>= 16;
+        }
+      }
+      const uint32_t f = active ? freq : 1u;
+      const uint32_t q = x / f;
+      if (active) x = (q << 16) + (x - q * f) + start;
+    }
+  }
+  st[lane] = x;
+  if (lane == 0) st[kLanes] = wend - wpos, st[kLanes + 1] = nesc, st[kLanes + 2] = err;
+}
+
+}  // namespace
+
+LIC_EXPORT int lic_rans_encode_pick(const uint32_t* tables, const int32_t* center, const int32_t* y,
+                                    const int64_t* order, int32_t B, int64_t P, int32_t M, int32_t W, uint32_t* sf,
+                                    uint32_t* exc, uint32_t* state, lic_stream_t stream) {
+  if (!tables || !center || !y || !order || !sf || !exc || !state) return LIC_ERR_INVALID;
+  if (B <= 0 || P <= 0 || M <= 0 || W <= 0) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(tables) | reinterpret_cast<uintptr_t>(center) | reinterpret_cast<uintptr_t>(y) |
+       reinterpret_cast<uintptr_t>(sf) | reinterpret_cast<uintptr_t>(exc) | reinterpret_cast<uintptr_t>(state)) & 3)
+    return LIC_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(order) & 7) return LIC_ERR_INVALID;
+  if (W > 64 || B > 65535) return LIC_ERR_UNSUPPORTED;
+  if (P > 0x7FFFFFFFL || P * M > 0x7FFFFFFFL - kLanes) return LIC_ERR_UNSUPPORTED;
+  const int32_t nsym = (int32_t)(P * M);
+  hipLaunchKernelGGL(rans_pick_kernel, dim3(ew_grid(nsym, 256), B), dim3(256), 0, (hipStream_t)stream, tables, center,
+                     y, order, (int32_t)P, M, W, nsym, sf, exc, state);
+  return lic_check_launch();
+}
+
+LIC_EXPORT int lic_rans_encode(const uint32_t* sf, const uint32_t* exc, const int64_t* step_len, int64_t nsteps,
+                               int32_t B, int64_t nsym, uint8_t* words, int64_t slot, uint32_t* esc_out,
+                               uint32_t* state, lic_stream_t stream) {
+  if (!sf || !exc || !step_len || !words || !esc_out || !state) return LIC_ERR_INVALID;
+  if (B <= 0 || nsym <= 0 || nsteps <= 0) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(sf) | reinterpret_cast<uintptr_t>(exc) | reinterpret_cast<uintptr_t>(words) |
+       reinterpret_cast<uintptr_t>(esc_out) | reinterpret_cast<uintptr_t>(state)) & 3)
+    return LIC_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(step_len) & 7) return LIC_ERR_INVALID;
+  if (nsym > 0x7FFFFFFFL - kLanes) return LIC_ERR_UNSUPPORTED;
+  // a slot holds the words only: at most one per symbol, whole dwords so that every image's slot is aligned
+  if (slot < 2 * nsym || (slot & 3) || slot > 0xFFFFFFFFL) return LIC_ERR_INVALID;
+  hipLaunchKernelGGL(rans_encode_kernel, dim3(B), dim3(kLanes), 0, (hipStream_t)stream, sf, exc, step_len, nsteps,
+                     (int32_t)nsym, words, slot, esc_out, state);
+  return lic_check_launch();
+}

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Wall time of ContextCodec.compress / decompress on a Kodak-sized image (GPU only), per coder: warm, median of
-RUNS calls, the GPU synchronised around each call only.  Environment: M, K, H, W, CODERS (comma list), RUNS."""
+RUNS calls, the GPU synchronised around each call only.  Environment: M, K, H, W, CODERS (comma list), RUNS, and
+ENCODERS (comma list of host / device, applied to the rans coder in the order given; a name may repeat, so that
+`ENCODERS=host,device,host,device` alternates the two in one process)."""
 import os
 import statistics
 import sys
@@ -15,6 +17,7 @@ from neural_image_compression_amd.codec import ContextCodec  # noqa: E402
 M, K = int(os.environ.get("M", "192")), int(os.environ.get("K", "3"))
 H, W = int(os.environ.get("H", "512")), int(os.environ.get("W", "768"))
 CODERS = os.environ.get("CODERS", "range,rans").split(",")
+ENCODERS = os.environ.get("ENCODERS", "host").split(",")
 RUNS = int(os.environ.get("RUNS", "10"))
 
 
@@ -29,8 +32,8 @@ def timed(fn):
 torch.manual_seed(0)
 model = nic.JointAutoregressiveHierarchical(M, K).cuda().eval()
 x = torch.rand(1, 3, H, W, device="cuda").contiguous(memory_format=torch.channels_last)
-for coder in CODERS:
-    cc = ContextCodec(model, coder=coder)
+for coder, encoder in [(c, e) for c in CODERS for e in (ENCODERS if c == "rans" else ["host"])]:
+    cc = ContextCodec(model, coder=coder, encoder=encoder)
     for _ in range(2):                                                       # warm: allocator, weight packs, tuning
         enc = cc.compress(x)
         dec = cc.decompress(enc["strings"], enc["shape"], enc["z_shape"])
@@ -41,7 +44,8 @@ for coder in CODERS:
     nbytes = len(s["z"]) + sum(map(len, s["y"])) + sum(map(len, s.get("y_esc", [])))
     npx = enc["shape"][2] * enc["shape"][3]
     md = statistics.median(t_dec)
-    print(f"JAH({M},{K}) {H}x{W} coder={coder}: compress {statistics.median(t_enc):8.2f} ms, decompress {md:8.2f} ms "
+    print(f"JAH({M},{K}) {H}x{W} coder={coder} encoder={encoder}: compress {statistics.median(t_enc):8.2f} ms "
+          f"(min {min(t_enc):.2f}, max {max(t_enc):.2f}), decompress {md:8.2f} ms "
           f"(min {min(t_dec):.2f}, max {max(t_dec):.2f}, median of {RUNS}; {1e3 * md / npx:6.1f} us per latent pixel, "
           f"{npx} pixels), round trip {'ok' if ok else 'MISMATCH'}, {nbytes} bytes, bpp coded {enc['bpp_coded']:.4f} "
           f"est {enc['bpp_est']:.4f}", flush=True)
