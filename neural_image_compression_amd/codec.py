@@ -118,6 +118,7 @@ def rc_ideal_bits(tables: np.ndarray, idx: np.ndarray, table_of: np.ndarray = No
 RANS_LANES = 64
 CODERS = ("range", "rans")
 ENCODERS = ("host", "device")
+RANS_MAX_W = 64                                  # widest window lic_rans_decode_step / lic_rans_encode_pick take
 
 
 def rans_encode(tables: np.ndarray, idx: np.ndarray, step_len) -> tuple:
@@ -297,6 +298,7 @@ class ContextCodec:
     the 64-lane interleaved rANS coder of lic_codec.h, whose decoder is a device kernel
     (`lic_rans_decode_step`): the step loop is then {gather -> per-pixel layers -> tables -> decode}, all
     asynchronous launches, and the host reads back one small block after the last step.  z keeps the range coder.
+    Its kernels take `y_W` from 1 to 64 (RANS_MAX_W); the constructor refuses a wider window for this coder.
 
     `encoder`: where `compress` codes the y streams.  "host" (the default) gathers the tables into wavefront order,
     copies them to the host and runs the C++ encoder, one image after the other; "device" (coder "rans" only) runs
@@ -311,6 +313,12 @@ class ContextCodec:
             raise CodecError(f"unknown encoder {encoder!r}: expected one of {ENCODERS}")
         if encoder == "device" and coder != "rans":
             raise CodecError(f"encoder='device' needs coder='rans': the {coder!r} coder has no device encoder")
+        if int(y_W) < 1:
+            raise CodecError(f"y_W = {int(y_W)}: the window half-width must be at least 1")
+        if coder == "rans" and int(y_W) > RANS_MAX_W:
+            # the only rANS decoder is the device kernel: a wider stream could be written but never read
+            raise CodecError(f"y_W = {int(y_W)}: coder='rans' takes windows of 1 to {RANS_MAX_W} "
+                             "(the limit of its device kernels); the range coder has no such limit")
         self.model, self.z_lo, self.z_S, self.y_W, self.coder = model, int(z_lo), int(z_S), int(y_W), coder
         self.encoder = encoder
         mc = model.context_model.masked
@@ -630,6 +638,9 @@ class ContextCodec:
         strings = {}
         if bytes(data[:8]) == BITSTREAM_MAGIC_RANS:
             head, z_bytes, y_streams, y_esc, y_crc = unpack_bitstream_rans(data)
+            if head["y_W"] > RANS_MAX_W:
+                raise CodecError(f"bitstream names y_W = {head['y_W']}; the rANS decoder takes windows of 1 to "
+                                 f"{RANS_MAX_W}")
             strings.update(coder="rans", y_esc=y_esc)
         else:
             head, z_bytes, y_streams, y_crc = unpack_bitstream(data)
@@ -642,7 +653,7 @@ class ContextCodec:
         Hp, Wp = -(-H // 64) * 64, -(-W // 64) * 64
         dec = self
         if (head["z_lo"], head["z_S"], head["y_W"]) != (self.z_lo, self.z_S, self.y_W):
-            dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"], self.coder)
+            dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"], strings.get("coder", "range"))
         out = dec.decompress(strings, (B, m.M, Hp // 16, Wp // 16), (B, m.M, Hp // 64, Wp // 64))
         return F_.crop_window(out["x_hat"], top, left, H, W)
 

@@ -38,35 +38,43 @@ def _model(nic, kind, M, K, seed, dev):
     return model.to(dev).eval()
 
 
-@pytest.fixture(scope="module")
-def synthetic(env):
+def make_synthetic(codec, W=W_):
     """B = 3 images of different entropy (so different stream lengths), escapes in images 0 and 2, coded by the host
-    encoder and decoded back by the host decoder: the reference of both kernel tests, computed once"""
-    _, codec, _, _ = env
+    encoder and decoded back by the host decoder, for the window half-width W: the reference of the kernel tests"""
+    S = 2 * W + 1
     r = np.random.RandomState(21)
     B, steps = 3, [M * n for M, n in LAUNCHES]
     nsym = sum(steps)
     tabs, idx = [], []
     for b, shape in enumerate((0.3, 0.02, 2.0)):
-        f = r.gamma(shape, 1.0, size=(nsym, S_)) + 1e-9
+        f = r.gamma(shape, 1.0, size=(nsym, S)) + 1e-9
         F = np.concatenate([np.zeros((nsym, 1)), np.cumsum(f / f.sum(1, keepdims=True), 1)], 1)
         F[:, -1] = 1.0
         t = CR.quantize_cdf(F)
         u = r.randint(0, 65536, size=nsym)
         # interior symbols drawn from the tables; the edge symbols are placed by hand below
-        i = np.array([np.searchsorted(t[k], u[k], side="right") - 1 for k in range(nsym)], np.int32).clip(1, S_ - 2)
+        i = np.array([np.searchsorted(t[k], u[k], side="right") - 1 for k in range(nsym)], np.int32).clip(1, S - 2)
         tabs.append(t)
         idx.append(i)
-    idx[0][[3, 40, 130, 131, 454, 455]] = [0, -1, S_ - 1, S_ + 100000, -100000, S_]
-    idx[2][[31, 127, 128 + 64 * 5 + 6]] = [-7, S_ - 1, 0]            # last lanes of partial rounds
+    idx[0][[3, 40, 130, 131, 454, 455]] = [0, -1, S - 1, S + 100000, -100000, S]
+    idx[2][[31, 127, 128 + 64 * 5 + 6]] = [-7, S - 1, 0]              # last lanes of partial rounds
     streams, escs = zip(*[codec.rans_encode(tabs[b], idx[b], steps) for b in range(B)])
-    assert len({len(s) for s in streams}) == 3 and len(escs[0]) == 24 and escs[1] == b"" and len(escs[2]) == 12
+    # the escape lists by the format's rule (idx <= 0 or idx >= S - 1): 6, 0 and 3 entries
+    n_esc = [int(((idx[b] <= 0) | (idx[b] >= S - 1)).sum()) for b in range(B)]
+    assert n_esc == [6, 0, 3] and [len(e) for e in escs] == [4 * c for c in n_esc]
+    assert len({len(s) for s in streams}) == 3
     host = [codec.rans_decode(streams[b], escs[b], tabs[b], steps) for b in range(B)]
     assert all((host[b] == idx[b]).all() for b in range(B))
     center = r.randint(-10, 11, size=(B, nsym)).astype(np.int32)
     dest = {0: np.array([5]), 1: np.array([0, 7, 2]), 2: r.permutation(399)[:327], 3: np.array([399])}
-    return {"B": B, "steps": steps, "tabs": np.stack(tabs), "idx": np.stack(host), "streams": streams, "escs": escs,
-            "center": center, "dest": dest}
+    return {"B": B, "W": W, "steps": steps, "tabs": np.stack(tabs), "idx": np.stack(host), "streams": streams,
+            "escs": escs, "center": center, "dest": dest}
+
+
+@pytest.fixture(scope="module")
+def synthetic(env):
+    """the W = 24 reference of both kernel tests, computed once"""
+    return make_synthetic(env[1])
 
 
 def _run_launches(env, syn, shorten=None):
@@ -100,7 +108,7 @@ def _run_launches(env, syn, shorten=None):
         cen = up(np.ascontiguousarray(syn["center"][:, base:base + ns]))
         dst = up(syn["dest"][li].astype(np.int64))
         rc = lib.lic_rans_decode_step(F_._ptr(d_buf), F_._ptr(d_soff), F_._ptr(d_slen), F_._ptr(d_esc), F_._ptr(d_eoff),
-                                      F_._ptr(d_state), F_._ptr(tabs), F_._ptr(cen), B, n, M, W_, F_._ptr(dst),
+                                      F_._ptr(d_state), F_._ptr(tabs), F_._ptr(cen), B, n, M, syn["W"], F_._ptr(dst),
                                       F_._ptr(ybuf[M]), PIXELS[M], F_._stream())
         assert rc == 0
         base += ns
@@ -114,13 +122,14 @@ def _expected(syn, images):
     for li, (M, n) in enumerate(LAUNCHES):
         ns = M * n
         for b in images:
-            v = (syn["idx"][b, base:base + ns].astype(np.int64) + syn["center"][b, base:base + ns] - W_)
+            v = (syn["idx"][b, base:base + ns].astype(np.int64) + syn["center"][b, base:base + ns] - syn["W"])
             want[M][b, syn["dest"][li]] = v.astype(np.float32).reshape(n, M)
         base += ns
     return want
 
 
-def test_kernel_matches_host_decoder_over_consecutive_launches(env, synthetic):
+def check_consecutive_launches(env, synthetic):
+    """values, untouched elements, error words, both cursors and the final states against the host decoder's"""
     got, state = _run_launches(env, synthetic)
     want = _expected(synthetic, range(3))
     for M in PIXELS:
@@ -132,7 +141,11 @@ def test_kernel_matches_host_decoder_over_consecutive_launches(env, synthetic):
     assert (state[:, :64] == 1 << 16).all()                                   # the encoder's initial states
 
 
-def test_kernel_stops_at_the_given_stream_length(env, synthetic):
+def test_kernel_matches_host_decoder_over_consecutive_launches(env, synthetic):
+    check_consecutive_launches(env, synthetic)
+
+
+def check_stops_at_the_given_stream_length(env, synthetic):
     """image 1's length is given as one word less: the cursor rule refuses that word although it is allocated memory
     (the next image's stream follows it), sets image 1's error word and leaves the other images alone"""
     got, state = _run_launches(env, synthetic, shorten=1)
@@ -143,7 +156,7 @@ def test_kernel_stops_at_the_given_stream_length(env, synthetic):
     # image 1 still wrote its destinations and nothing else; each holds the right value (decoded before the missing
     # word was needed) or the table centre (idx = W, decoded after it), and some are not the right value
     full = _expected(synthetic, (1,))
-    centre = dict(synthetic, idx=np.full_like(synthetic["idx"], W_))
+    centre = dict(synthetic, idx=np.full_like(synthetic["idx"], synthetic["W"]))
     cen = _expected(centre, (1,))
     wrong = 0
     for M in PIXELS:
@@ -151,6 +164,10 @@ def test_kernel_stops_at_the_given_stream_length(env, synthetic):
         assert ((got[M][1] == full[M][1]) | (got[M][1] == cen[M][1])).all()
         wrong += int((got[M][1] != full[M][1]).sum())
     assert wrong > 0
+
+
+def test_kernel_stops_at_the_given_stream_length(env, synthetic):
+    check_stops_at_the_given_stream_length(env, synthetic)
 
 
 CASES = [(1, 2, 64, 128, "jah", 32), (3, 1, 128, 64, "jah", 32), (3, 2, 64, 192, "hmr", 32),

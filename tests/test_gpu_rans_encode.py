@@ -36,12 +36,10 @@ def _model(nic, kind, M, K, seed, dev):
     return model.to(dev).eval()
 
 
-@pytest.fixture(scope="module")
-def synthetic(env):
-    """the five images in coding order with both references, computed once: M = 1 on the whole step list, and the
-    M = 32 rerun on the first 128 symbols"""
-    _, codec, _, _ = env
-    tabs, idx = EH.make_images()
+def make_synthetic(codec, W=W_):
+    """the five images in coding order with both references for the window half-width W: M = 1 on the whole step
+    list, and the M = 32 rerun on the first 128 symbols"""
+    tabs, idx = EH.make_images(W=W)
     out = {}
     for M, steps in ((1, EH.STEPS), (32, [32, 96])):
         n = sum(steps)
@@ -50,13 +48,19 @@ def synthetic(env):
         assert host == [RR.encode(t[b], i[b], steps) for b in range(5)]
         r = np.random.RandomState(32 + M)
         P = n // M
-        out[M] = {"M": M, "P": P, "steps": steps, "tabs": t, "idx": i, "host": host,
+        out[M] = {"M": M, "P": P, "W": W, "steps": steps, "tabs": t, "idx": i, "host": host,
                   "order": r.permutation(P).astype(np.int64),          # a fixed permutation, not the identity
                   "center": r.randint(-10, 11, size=(5, n)).astype(np.int64)}
         assert (out[M]["order"] != np.arange(P)).any()
         # y = idx + center - W must be an int32: the one symbol with idx = -2^31 gets center = W
-        out[M]["center"][i == -2 ** 31] = W_
+        out[M]["center"][i == -2 ** 31] = W
     return out
+
+
+@pytest.fixture(scope="module")
+def synthetic(env):
+    """the W = 24 references, computed once"""
+    return make_synthetic(env[1])
 
 
 def _raster(syn, images, tabs=None):
@@ -64,16 +68,17 @@ def _raster(syn, images, tabs=None):
     in RASTER pixel order (coded position p is pixel order[p])"""
     M, P, order = syn["M"], syn["P"], syn["order"]
     tabs = syn["tabs"] if tabs is None else tabs
-    B = len(images)
-    t_r = np.zeros((B, P, M, S_ + 1), np.uint32)
+    B, W, S1 = len(images), syn["W"], tabs.shape[-1]
+    assert S1 == 2 * W + 2
+    t_r = np.zeros((B, P, M, S1), np.uint32)
     c_r, y_r = np.zeros((B, P, M), np.int32), np.zeros((B, P, M), np.int32)
     for j, b in enumerate(images):
-        y = syn["idx"][b] + syn["center"][b] - W_
+        y = syn["idx"][b] + syn["center"][b] - W
         assert (y >= -2 ** 31).all() and (y < 2 ** 31).all()
-        t_r[j, order] = tabs[b].reshape(P, M, S_ + 1)
+        t_r[j, order] = tabs[b].reshape(P, M, S1)
         c_r[j, order] = syn["center"][b].reshape(P, M)
         y_r[j, order] = y.reshape(P, M)
-    return t_r.reshape(B, P * M, S_ + 1), c_r.reshape(B * P, M), y_r
+    return t_r.reshape(B, P * M, S1), c_r.reshape(B * P, M), y_r
 
 
 def _launch(env, syn, t_r, c_r, y_r):
@@ -95,7 +100,7 @@ def _launch(env, syn, t_r, c_r, y_r):
     sview = state[PAD:PAD + 4 * B * 67].view(torch.int32).view(B, 67)
     sview[:, 66] = 0                                                   # the caller zeroes the error words
     off = lambda t: t.data_ptr() + PAD
-    rc = lib.lic_rans_encode_pick(F_._ptr(d_t), F_._ptr(d_c), F_._ptr(d_y), F_._ptr(d_order), B, P, M, W_, F_._ptr(sf),
+    rc = lib.lic_rans_encode_pick(F_._ptr(d_t), F_._ptr(d_c), F_._ptr(d_y), F_._ptr(d_order), B, P, M, syn["W"], F_._ptr(sf),
                                   F_._ptr(exc), off(state), F_._stream())
     assert rc == 0
     rc = lib.lic_rans_encode(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), len(syn["steps"]), B, nsym, off(words), slot,
@@ -115,10 +120,10 @@ def _stream_of(st, slot, words, esc, j, nsym):
     return st[j, :64].astype("<u4").tobytes() + words[end - 2 * nw:end].tobytes(), esc[e0:e0 + 4 * ne].tobytes()
 
 
-@pytest.mark.parametrize("M", [1, 32])
-def test_kernels_match_the_host_encoder(env, synthetic, M):
+def check_kernels_match_the_host_encoder(env, syn):
+    """streams, escape lists and counts of the five images against the host encoder's, whatever the window"""
     _, codec, _, _ = env
-    syn = synthetic[M]
+    M = syn["M"]
     nsym = syn["P"] * M
     st, slot, words, esc, _ = _launch(env, syn, *_raster(syn, range(5)))
     assert (st[:, 66] == 0).all(), st[:, 66]
@@ -133,12 +138,18 @@ def test_kernels_match_the_host_encoder(env, synthetic, M):
     # the two ends of the word cursor: one word per symbol, and none
     assert st[3, 64] == nsym and st[4, 64] == 0
     if M == 1:
-        assert len(syn["host"][0][1]) == 28 and len(syn["host"][2][1]) == 12 and syn["host"][1][1] == b""
+        # the escape lists by the format's rule (idx <= 0 or idx >= S - 1): 7, 0 and 3 entries
+        n_esc = [EH.escape_count(syn["idx"][b], 2 * syn["W"] + 1) for b in range(3)]
+        assert n_esc == [7, 0, 3] and [len(syn["host"][b][1]) for b in range(3)] == [4 * c for c in n_esc]
 
 
-def test_nothing_outside_the_slots_is_written(env, synthetic):
-    syn = synthetic[1]
-    nsym, B = syn["P"], 5
+@pytest.mark.parametrize("M", [1, 32])
+def test_kernels_match_the_host_encoder(env, synthetic, M):
+    check_kernels_match_the_host_encoder(env, synthetic[M])
+
+
+def check_nothing_outside_the_slots_is_written(env, syn):
+    nsym, B = syn["P"] * syn["M"], 5
     st, slot, words, esc, state = _launch(env, syn, *_raster(syn, range(5)))
     keep_w, keep_e = np.ones(words.size, bool), np.ones(esc.size, bool)
     for b in range(B):
@@ -149,6 +160,10 @@ def test_nothing_outside_the_slots_is_written(env, synthetic):
     assert (words[keep_w] == CANARY).all(), "bytes outside [slot_end - 2 * count, slot_end) were written"
     assert (esc[keep_e] == CANARY).all(), "escape entries beyond the count were written"
     assert (state[:PAD] == CANARY).all() and (state[PAD + 4 * B * 67:] == CANARY).all()
+
+
+def test_nothing_outside_the_slots_is_written(env, synthetic):
+    check_nothing_outside_the_slots_is_written(env, synthetic[1])
 
 
 @pytest.mark.parametrize("damage", ["last entry 65535", "frequency 0"])

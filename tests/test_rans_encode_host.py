@@ -20,40 +20,52 @@ STEPS = [64, 0, 130, 1, 128, 327]
 KINDS = ("gamma 0.3", "gamma 0.02", "gamma 2.0", "freq 1", "freq 65536-48")
 
 
-def make_images(steps=STEPS, seed=31):
-    """The five images of the encoder tests in CODING order: tables [5][n][S+1] uint32 and idx [5][n] int64.
+def make_images(steps=STEPS, seed=31, W=W_):
+    """The five images of the encoder tests in CODING order: tables [5][n][S+1] uint32 and idx [5][n] int64, for the
+    window half-width W (S = 2W + 1 symbols).
     (a) gamma(0.3) tables, (b) gamma(0.02): peaked, few words, (c) gamma(2.0), (d) every coded symbol has frequency
-    1: one word per symbol, the word cursor ends at its floor, (e) every coded symbol has frequency 65536 - 48: no
-    word at all.  Edge symbols are placed by hand in (a) and (c) where they fit into `steps`' n symbols."""
+    1: one word per symbol, the word cursor ends at its floor, (e) every coded symbol has frequency 65536 - (S - 1):
+    no word at all.  Edge symbols are placed by hand in (a) and (c) where they fit into `steps`' n symbols.  At W = 1
+    the only interior symbol is 1, so image (d) takes its frequency-1 symbol from the two edge symbols (they come
+    with an escape)."""
+    S = 2 * W + 1
     r = np.random.RandomState(seed)
     n = int(sum(steps))
     tabs, idx = [], []
     for shape in (0.3, 0.02, 2.0):
-        f = r.gamma(shape, 1.0, size=(n, S_)) + 1e-9
+        f = r.gamma(shape, 1.0, size=(n, S)) + 1e-9
         F = np.concatenate([np.zeros((n, 1)), np.cumsum(f / f.sum(1, keepdims=True), 1)], 1)
         F[:, -1] = 1.0
         t = CR.quantize_cdf(F)
         u = r.randint(0, 65536, size=n)
-        i = np.array([np.searchsorted(t[k], u[k], side="right") - 1 for k in range(n)], np.int64).clip(1, S_ - 2)
+        i = np.array([np.searchsorted(t[k], u[k], side="right") - 1 for k in range(n)], np.int64).clip(1, S - 2)
         tabs.append(t)
         idx.append(i)
-    big = r.randint(1, S_ - 1, size=n)
-    t = np.zeros((n, S_ + 1), np.uint32)
+    big = r.randint(1, S - 1, size=n)
+    t = np.zeros((n, S + 1), np.uint32)
     for k in range(n):
-        f = np.ones(S_, np.int64)
-        f[big[k]] = 65536 - (S_ - 1)
+        f = np.ones(S, np.int64)
+        f[big[k]] = 65536 - (S - 1)
         t[k, 1:] = np.cumsum(f)
-    other = np.where(big + 1 <= S_ - 2, big + 1, big - 1)                 # an interior symbol of frequency 1
+    other = np.where(big + 1 <= S - 2, big + 1, big - 1)                  # an interior symbol of frequency 1
+    if S == 3:
+        other = np.where(r.randint(0, 2, size=n) == 1, S - 1, 0)          # none is interior: symbol 0 or S - 1
     tabs += [t, t.copy()]
     idx += [other.astype(np.int64), big.astype(np.int64)]
     # lane 0 and lane 63 of a full round, the last lane of a partial round (193: step 2's third round; 649: the
     # last symbol), a one-symbol step (194), and the largest excess there is: 2^31, one below the sentinel's range
-    for b, places in ((0, {0: 0, 63: -1, 130: -2 ** 31, 193: S_ - 1, 194: S_ + 100000, 400: -100000, 649: S_}),
-                      (2, {127: -7, 193: S_ - 1, 649: 0})):
+    for b, places in ((0, {0: 0, 63: -1, 130: -2 ** 31, 193: S - 1, 194: S + 100000, 400: -100000, 649: S}),
+                      (2, {127: -7, 193: S - 1, 649: 0})):
         for k, v in places.items():
             if k < n:
                 idx[b][k] = v
     return np.stack(tabs), np.stack(idx)
+
+
+def escape_count(idx, S):
+    """escapes of a symbol sequence by the format's rule: one for every idx <= 0 and every idx >= S - 1"""
+    idx = np.asarray(idx, np.int64)
+    return int(((idx <= 0) | (idx >= S - 1)).sum())
 
 
 def pick(tables, idx):
