@@ -160,7 +160,8 @@ typedef struct lic_wgrad_desc {
   float scale;
   /* overrides of the launch plan, 0 = automatic (see lic_igemm_desc): tile in 64-channel units, one of
    * (1,1) (1,3) (2,1) (2,2) (2,3) (3,3) -- (3,3) needs both channel counts % 192 == 0 -- and the number
-   * of pixel splits */
+   * of pixel splits.  Honoured by lic_wgrad (fp32) only: lic_wgrad_bf16 plans from the shape alone (tile from
+   * the channel counts, splits from the pixel count) and ignores all three. */
   int32_t force_tm, force_tn, force_split;
 } lic_wgrad_desc;
 
