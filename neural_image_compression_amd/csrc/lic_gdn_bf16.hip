@@ -5,32 +5,25 @@
 // through HBM twice and t three times: 1.2 GB at 128^2 x 32 x 128 channels for a C x C contraction of 17 GFLOP -- the
 // launches are memory-bound, not matrix-bound.  Here a wave owns 32 pixels x all C channels, reads g, x, norm ONCE
 // (16 bytes per lane: pixel = lane & 31, 8 consecutive channels per 16-channel group and lane half), forms t in
-// registers, turns its packed pairs into the MFMA B operand with one v_permlane32_swap per dword pair (the K order
+// registers, turns its packed pairs into the MFMA B operand with swap_dword_pairs of lic_epilogue_bf16.h (the K order
 // of lic_pack_weight_bf16_kperm: the inverse of the fused conv+GDN kernels' store swap), contracts it against
 // gamma_eff (staged once per workgroup in LDS, kperm-packed) with the operands swapped -- the accumulators hold the
 // transposed tile -- swaps the pool back to the loaded layout and finishes element-wise: 0.67 GB, no LDS round trip
 // of the activations, t and dx written with 16-byte stores.  Rounding points are the two-launch route's (t to bf16,
 // fp32 pool of bf16 operands, fp32 epilogue on the bf16 inputs); the pool sums each group of 16 channels in another
 // order, so dx agrees to fp32 / one-bf16-ulp rounding, not bitwise.
-#include "lic_common.h"
-
-typedef __bf16 gb_bf16;
-typedef __bf16 gb_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float gb_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned gb_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned gb_u32x4 __attribute__((ext_vector_type(4)));
+#include "lic_epilogue_bf16.h"
 
 namespace {
 
 struct GdnBwdHParams {
-  const gb_bf16* g;
-  const gb_bf16* x;
-  const gb_bf16* norm;
-  const gb_bf16* gamma;  // gamma_eff packed by lic_pack_weight_bf16_kperm(taps 1, K = C (norm index), N = C, s_k = C, s_n = 1)
-  gb_bf16* dx;
-  gb_bf16* t;
-  const gb_bf16* gammaT;  // RN: gamma_eff^T packed by lic_pack_weight_bf16_kperm(K = C (x index), N = C, s_k = 1, s_n = C)
+  const bf16_t* g;
+  const bf16_t* x;
+  const bf16_t* norm;
+  const bf16_t* gamma;  // gamma_eff packed by lic_pack_weight_bf16_kperm(taps 1, K = C (norm index), N = C, s_k = C, s_n = 1)
+  bf16_t* dx;
+  bf16_t* t;
+  const bf16_t* gammaT;  // RN: gamma_eff^T packed by lic_pack_weight_bf16_kperm(K = C (x index), N = C, s_k = 1, s_n = C)
   const float* beta;      // RN: beta_eff [C]
   float* cs_t;   // optional: [gridDim.x][C] per-workgroup column sums of t (-> d beta) ...
   float* cs_dx;  // ... and of dx (-> the d bias of the convolution in front); both or neither
@@ -53,8 +46,8 @@ template <int NT4, bool CS = false, bool RN = false>  // C / 32
 __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(const GdnBwdHParams p) {
   constexpr int C = 32 * NT4, NG = C / 16;
   constexpr int CSLD = C / 2 + 4;   // dwords per parked row
-  __shared__ __attribute__((aligned(16))) gb_bf16 gam[C * C];  // [chunk = C/32][tile = C/32][2][64 lanes][8]
-  __shared__ __attribute__((aligned(16))) gb_bf16 gamT[RN ? C * C : 8];
+  __shared__ __attribute__((aligned(16))) bf16_t gam[C * C];  // [chunk = C/32][tile = C/32][2][64 lanes][8]
+  __shared__ __attribute__((aligned(16))) bf16_t gamT[RN ? C * C : 8];
   __shared__ __attribute__((aligned(16))) float s_beta[RN ? C : 4];
   __shared__ __attribute__((aligned(16))) unsigned park[CS ? 4 * 32 * CSLD : 4];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -80,11 +73,11 @@ __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(con
   // gamma panel: C*C*2 bytes, 16 bytes per thread per pass
 #pragma unroll
   for (int i = 0; i < C * C / 8 / 256; ++i)
-    reinterpret_cast<gb_u32x4*>(gam)[i * 256 + tid] = reinterpret_cast<const gb_u32x4*>(p.gamma)[i * 256 + tid];
+    reinterpret_cast<u32x4*>(gam)[i * 256 + tid] = reinterpret_cast<const u32x4*>(p.gamma)[i * 256 + tid];
   if (RN) {
 #pragma unroll
     for (int i = 0; i < C * C / 8 / 256; ++i)
-      reinterpret_cast<gb_u32x4*>(gamT)[i * 256 + tid] = reinterpret_cast<const gb_u32x4*>(p.gammaT)[i * 256 + tid];
+      reinterpret_cast<u32x4*>(gamT)[i * 256 + tid] = reinterpret_cast<const u32x4*>(p.gammaT)[i * 256 + tid];
     if (tid < C) s_beta[tid] = p.beta[tid];
   }
   __syncthreads();
@@ -93,14 +86,14 @@ __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(con
   // RN: the NEXT tile's g and x are in flight while the current one is computed (a second register set, copied over at
   // the top of the loop) -- with the pool recomputed the sweep has more arithmetic between its loads and its stores, and a
   // wave that computes has nothing in flight
-  gb_u32x4 gN[RN ? NG : 1], xN[RN ? NG : 1];
+  u32x4 gN[RN ? NG : 1], xN[RN ? NG : 1];
   auto prefetch = [&](long tile) {
     const long row = tile * 128 + wave * 32 + li;
     const long off = (row < p.P ? row : 0) * C + 8 * lh;
 #pragma unroll
     for (int s = 0; s < NG; ++s) {
-      gN[RN ? s : 0] = *reinterpret_cast<const gb_u32x4*>(p.g + off + 16 * s);
-      xN[RN ? s : 0] = *reinterpret_cast<const gb_u32x4*>(p.x + off + 16 * s);
+      gN[RN ? s : 0] = *reinterpret_cast<const u32x4*>(p.g + off + 16 * s);
+      xN[RN ? s : 0] = *reinterpret_cast<const u32x4*>(p.x + off + 16 * s);
     }
   };
   if (RN && (long)blockIdx.x < ntile) prefetch(blockIdx.x);
@@ -111,7 +104,7 @@ __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(con
     const bool rok = row < p.P;
     const long off = (rok ? row : 0) * C + 8 * lh;
     // ---- one sweep: 8 consecutive channels of group s for this lane's pixel, all three streams in flight at once
-    gb_u32x4 gq[NG], xq[NG], nq[NG];
+    u32x4 gq[NG], xq[NG], nq[NG];
     if (RN) {
 #pragma unroll
       for (int s = 0; s < NG; ++s) {
@@ -122,26 +115,20 @@ __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(con
     } else {
 #pragma unroll
       for (int s = 0; s < NG; ++s) {
-        gq[s] = *reinterpret_cast<const gb_u32x4*>(p.g + off + 16 * s);
-        xq[s] = *reinterpret_cast<const gb_u32x4*>(p.x + off + 16 * s);
-        nq[s] = *reinterpret_cast<const gb_u32x4*>(p.norm + off + 16 * s);
+        gq[s] = *reinterpret_cast<const u32x4*>(p.g + off + 16 * s);
+        xq[s] = *reinterpret_cast<const u32x4*>(p.x + off + 16 * s);
+        nq[s] = *reinterpret_cast<const u32x4*>(p.norm + off + 16 * s);
       }
     }
-    auto lo = [](unsigned u) { return __builtin_bit_cast(float, u << 16); };
-    auto hi = [](unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
-    auto pack2 = [](float a, float b) {
-      const gb_f32x2 v = {a, b};
-      return __builtin_bit_cast(unsigned, __builtin_convertvector(v, gb_bf16x2));
-    };
     // a transposed accumulator tile back in the loaded layout: the accumulator of channel tile bo holds, for this lane's
     // pixel, channels 8 gg + 4 lh + {0..3} (gg = 0..3); group s = 2 bo + (gg >> 1) wants channels 8 lh + {0..7}
     auto unswap = [&](const f32x16& a16, int s, float (&pl)[8]) {
       const int g0 = 2 * (s & 1);   // registers 4 g0 .. 4 g0 + 7
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        // (by value first: __builtin_bit_cast on a vector-element lvalue reads element 0 of the vector with this clang)
+        // (by value first: see bf16_lo in lic_epilogue_bf16.h)
         const float q0 = a16[4 * g0 + e], q1 = a16[4 * g0 + 4 + e];
-        const gb_u32x2 sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, q0),
+        const u32x2 sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, q0),
                                                              __builtin_bit_cast(unsigned, q1), false, false);
         // low lanes: (own first quad, partner's first quad) = channels e, 4 + e; high lanes: (partner's second quad,
         // own second quad) = channels 8 + e, 12 + e
@@ -159,18 +146,16 @@ __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(con
         for (int r = 0; r < 16; ++r) nacc[bo][r] = 0.0f;
 #pragma unroll
       for (int s = 0; s < NG; ++s) {
-        gb_u32x4 sq;
+        u32x4 sq;
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
-          const float x0 = lo(xq[s][d]), x1 = hi(xq[s][d]);
-          sq[d] = pack2(x0 * x0, x1 * x1);
+          const float x0 = bf16_lo(xq[s][d]), x1 = bf16_hi(xq[s][d]);
+          sq[d] = pack2(f32x2{x0 * x0, x1 * x1});
         }
-        const gb_u32x2 a = __builtin_amdgcn_permlane32_swap(sq[0], sq[2], false, false);
-        const gb_u32x2 b = __builtin_amdgcn_permlane32_swap(sq[1], sq[3], false, false);
-        const gb_bf16x8 b2 = __builtin_bit_cast(gb_bf16x8, gb_u32x4{a[0], b[0], a[1], b[1]});
+        const bf16x8 b2 = __builtin_bit_cast(bf16x8, swap_dword_pairs(sq[0], sq[1], sq[2], sq[3]));
 #pragma unroll
         for (int bo = 0; bo < NT4; ++bo) {
-          const gb_bf16x8 a2 = *reinterpret_cast<const gb_bf16x8*>(gamT + (((s >> 1) * NT4 + bo) * 2 + (s & 1)) * 512 + lane * 8);
+          const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(gamT + (((s >> 1) * NT4 + bo) * 2 + (s & 1)) * 512 + lane * 8);
           nacc[bo] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, nacc[bo], 0, 0, 0);
         }
       }
@@ -180,30 +165,28 @@ __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(con
         unswap(nacc[s >> 1], s, pl);
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(s_beta + 16 * s + 8 * lh);
         const f32x4 b1 = *reinterpret_cast<const f32x4*>(s_beta + 16 * s + 8 * lh + 4);
-        nq[s] = gb_u32x4{pack2(pl[0] + b0[0], pl[1] + b0[1]), pack2(pl[2] + b0[2], pl[3] + b0[3]),
-                         pack2(pl[4] + b1[0], pl[5] + b1[1]), pack2(pl[6] + b1[2], pl[7] + b1[3])};
+        nq[s] = u32x4{pack2(f32x2{pl[0] + b0[0], pl[1] + b0[1]}), pack2(f32x2{pl[2] + b0[2], pl[3] + b0[3]}),
+                      pack2(f32x2{pl[4] + b1[0], pl[5] + b1[1]}), pack2(f32x2{pl[6] + b1[2], pl[7] + b1[3]})};
       }
     }
     // ---- t = dL/dnorm, rounded to bf16 (what the d-gamma / d-beta launches read); its kperm B operand
-    gb_u32x4 tb[NG];
+    u32x4 tb[NG];
 #pragma unroll
     for (int s = 0; s < NG; ++s) {
-      gb_u32x4 tq;
+      u32x4 tq;
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
-        const float n0 = lo(nq[s][d]), n1 = hi(nq[s][d]);
+        const float n0 = bf16_lo(nq[s][d]), n1 = bf16_hi(nq[s][d]);
         const float r0 = __builtin_amdgcn_rsqf(n0), r1 = __builtin_amdgcn_rsqf(n1);
-        const float gx0 = lo(gq[s][d]) * lo(xq[s][d]), gx1 = hi(gq[s][d]) * hi(xq[s][d]);
+        const float gx0 = bf16_lo(gq[s][d]) * bf16_lo(xq[s][d]), gx1 = bf16_hi(gq[s][d]) * bf16_hi(xq[s][d]);
         const float t0 = p.inverse ? 0.5f * gx0 * r0 : -0.5f * gx0 * r0 * (r0 * r0);
         const float t1 = p.inverse ? 0.5f * gx1 * r1 : -0.5f * gx1 * r1 * (r1 * r1);
-        tq[d] = pack2(t0, t1);
+        tq[d] = pack2(f32x2{t0, t1});
       }
-      if (rok) *reinterpret_cast<gb_u32x4*>(p.t + off + 16 * s) = tq;
-      if (CS) *reinterpret_cast<gb_u32x4*>(mypark + li * CSLD + 8 * s + 4 * lh) = rok ? tq : gb_u32x4{0u, 0u, 0u, 0u};
+      if (rok) *reinterpret_cast<u32x4*>(p.t + off + 16 * s) = tq;
+      if (CS) *reinterpret_cast<u32x4*>(mypark + li * CSLD + 8 * s + 4 * lh) = rok ? tq : u32x4{0u, 0u, 0u, 0u};
       // lanes li / li + 32 hold channels 0..7 / 8..15 of the group; the kperm operand wants {0..3, 8..11} / {4..7, 12..15}
-      const gb_u32x2 a = __builtin_amdgcn_permlane32_swap(tq[0], tq[2], false, false);
-      const gb_u32x2 b = __builtin_amdgcn_permlane32_swap(tq[1], tq[3], false, false);
-      tb[s] = gb_u32x4{a[0], b[0], a[1], b[1]};
+      tb[s] = swap_dword_pairs(tq[0], tq[1], tq[2], tq[3]);
     }
     if (CS) colsum_tile(cst);
     // ---- pool^T[co][pixel] = sum_ci gamma_eff[ci][co] t[pixel][ci]   (A = gamma from LDS, B = t from registers)
@@ -214,10 +197,10 @@ __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(con
       for (int r = 0; r < 16; ++r) acc[bo][r] = 0.0f;
 #pragma unroll
     for (int s = 0; s < NG; ++s) {
-      const gb_bf16x8 b2 = __builtin_bit_cast(gb_bf16x8, tb[s]);
+      const bf16x8 b2 = __builtin_bit_cast(bf16x8, tb[s]);
 #pragma unroll
       for (int bo = 0; bo < NT4; ++bo) {
-        const gb_bf16x8 a2 = *reinterpret_cast<const gb_bf16x8*>(gam + (((s >> 1) * NT4 + bo) * 2 + (s & 1)) * 512 + lane * 8);
+        const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(gam + (((s >> 1) * NT4 + bo) * 2 + (s & 1)) * 512 + lane * 8);
         acc[bo] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, acc[bo], 0, 0, 0);
       }
     }
@@ -226,18 +209,18 @@ __global__ __launch_bounds__(256, NT4 <= 2 ? 2 : 1) void gdn_bwd_bf16_kernel(con
     for (int s = 0; s < NG; ++s) {
       float pl[8];
       unswap(acc[s >> 1], s, pl);
-      gb_u32x4 dq;
+      u32x4 dq;
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
-        const float n0 = lo(nq[s][d]), n1 = hi(nq[s][d]);
+        const float n0 = bf16_lo(nq[s][d]), n1 = bf16_hi(nq[s][d]);
         const float f0 = p.inverse ? __builtin_amdgcn_sqrtf(n0) : __builtin_amdgcn_rsqf(n0);
         const float f1 = p.inverse ? __builtin_amdgcn_sqrtf(n1) : __builtin_amdgcn_rsqf(n1);
-        const float d0 = __builtin_fmaf(2.0f * lo(xq[s][d]), pl[2 * d], lo(gq[s][d]) * f0);
-        const float d1 = __builtin_fmaf(2.0f * hi(xq[s][d]), pl[2 * d + 1], hi(gq[s][d]) * f1);
-        dq[d] = pack2(d0, d1);
+        const float d0 = __builtin_fmaf(2.0f * bf16_lo(xq[s][d]), pl[2 * d], bf16_lo(gq[s][d]) * f0);
+        const float d1 = __builtin_fmaf(2.0f * bf16_hi(xq[s][d]), pl[2 * d + 1], bf16_hi(gq[s][d]) * f1);
+        dq[d] = pack2(f32x2{d0, d1});
       }
-      if (rok) *reinterpret_cast<gb_u32x4*>(p.dx + off + 16 * s) = dq;
-      if (CS) *reinterpret_cast<gb_u32x4*>(mypark + li * CSLD + 8 * s + 4 * lh) = rok ? dq : gb_u32x4{0u, 0u, 0u, 0u};
+      if (rok) *reinterpret_cast<u32x4*>(p.dx + off + 16 * s) = dq;
+      if (CS) *reinterpret_cast<u32x4*>(mypark + li * CSLD + 8 * s + 4 * lh) = rok ? dq : u32x4{0u, 0u, 0u, 0u};
     }
     if (CS) colsum_tile(csd);
   }
@@ -306,8 +289,8 @@ LIC_EXPORT int lic_gdn_bwd_bf16(const void* g, const void* x, const void* norm, 
   if (!lic_gdn_bwd_bf16_supported(C)) return LIC_ERR_UNSUPPORTED;
   for (const void* q : {g, x, norm, gamma_packed, (const void*)dx, (const void*)t})
     if (reinterpret_cast<uintptr_t>(q) & 15) return LIC_ERR_INVALID;
-  GdnBwdHParams p{(const gb_bf16*)g, (const gb_bf16*)x, (const gb_bf16*)norm, (const gb_bf16*)gamma_packed,
-                  (gb_bf16*)dx, (gb_bf16*)t, nullptr, nullptr, colsum_t_partial, colsum_dx_partial, (long)P,
+  GdnBwdHParams p{(const bf16_t*)g, (const bf16_t*)x, (const bf16_t*)norm, (const bf16_t*)gamma_packed,
+                  (bf16_t*)dx, (bf16_t*)t, nullptr, nullptr, colsum_t_partial, colsum_dx_partial, (long)P,
                   (long)gdn_bwd_bf16_grid(P), inverse ? 1 : 0};
   return gdn_bwd_bf16_run(p, C, false, (hipStream_t)stream);
 }
@@ -324,8 +307,8 @@ LIC_EXPORT int lic_gdn_bwd_bf16_recompute(const void* g, const void* x, const vo
   if (!lic_gdn_bwd_bf16_supported(C)) return LIC_ERR_UNSUPPORTED;
   for (const void* q : {g, x, gamma_packed, gammaT_packed, (const void*)beta_eff, (const void*)dx, (const void*)t})
     if (reinterpret_cast<uintptr_t>(q) & 15) return LIC_ERR_INVALID;
-  GdnBwdHParams p{(const gb_bf16*)g, (const gb_bf16*)x, nullptr, (const gb_bf16*)gamma_packed, (gb_bf16*)dx, (gb_bf16*)t,
-                  (const gb_bf16*)gammaT_packed, beta_eff, colsum_t_partial, colsum_dx_partial, (long)P,
+  GdnBwdHParams p{(const bf16_t*)g, (const bf16_t*)x, nullptr, (const bf16_t*)gamma_packed, (bf16_t*)dx, (bf16_t*)t,
+                  (const bf16_t*)gammaT_packed, beta_eff, colsum_t_partial, colsum_dx_partial, (long)P,
                   (long)gdn_bwd_bf16_grid(P), inverse ? 1 : 0};
   return gdn_bwd_bf16_run(p, C, true, (hipStream_t)stream);
 }

@@ -5,11 +5,10 @@
 // wave -- shorter than a memory round trip -- so, as in the bf16 wgrad below, the DMA runs TWO
 // chunks ahead through a ring of three LDS buffers (counted `s_waitcnt vmcnt`, raw `s_barrier`).
 #include "lic_conv_plan.h"
+#include "lic_epilogue_bf16.h"
 #include <algorithm>
 #include <type_traits>
 
-typedef __bf16 bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int HB_BK = 32;  // bf16 elements per K chunk (64-byte rows, 2 MFMA K steps)
@@ -63,10 +62,9 @@ __device__ __forceinline__ bf16x8 sq8(bf16x8 v) {
 // (li, lh) owns pixel li and, of every 32-channel tile, channels 4*lh + 8*g + j (g, j = 0..3).  Eight of those
 // (g = 2s, 2s+1) are exactly one lane's share of a 16-deep MFMA B operand if K is counted in that order, which is
 // how lic_pack_weight_bf16_kperm lays gamma_eff^T out: x -> bf16, x^2 -> bf16 and the pool's operand never leave
-// the registers (no LDS transpose, no barrier), y = x * rsqrt(norm) is element-wise in the same layout, and one
-// v_permlane32_swap per dword pair turns a lane's 4+4 channels into 8 consecutive ones for 16-byte stores.
-// The element-wise part is written with 2-wide vectors (v_pk_add/mul_f32, v_cvt_pk_bf16_f32): at 2^26 outputs
-// per launch of the first layer every VALU instruction per element is 1.7 us.
+// the registers (no LDS transpose, no barrier), y = x * rsqrt(norm) is element-wise in the same layout, and a
+// lane-half swap turns a lane's 4+4 channels into 8 consecutive ones for 16-byte stores: the transposed-tile
+// epilogue of lic_epilogue_bf16.h, which owns the rounding points.
 template <int... Is, class F>
 __device__ __forceinline__ void lich_for_seq(std::integer_sequence<int, Is...>, F&& f) {
   (f(std::integral_constant<int, Is>{}), ...);
@@ -396,12 +394,8 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
   float* stg = reinterpret_cast<float*>(smem_all) + wave * 1024;
   const int c8 = (lane & 3) * 8, r16 = lane >> 2;
   if constexpr (FUSE) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    auto pack2 = [](f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); };
-    // this lane's pixel (TM == 1) and where it lives in the output tensors
+    // the transposed-tile epilogue of lic_epilogue_bf16.h; this lane's pixel (TM == 1) and where it lives in the
+    // output tensors
     const int prow = m0 + wm0 + li;
     const bool rok = prow < P;
     long opix = rok ? prow : 0;
@@ -411,39 +405,18 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
       const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
       opix = ((long)bb * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
     }
-    // a lane's 16 channels of tile b as 8 bf16 pairs -> two 16-byte stores of 8 consecutive channels each
-    auto store_tile = [&](bf16_t* base, long ld, const unsigned (&pk)[8], int b) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const u32x2 r0 = __builtin_amdgcn_permlane32_swap(pk[4 * s], pk[4 * s + 2], false, false);
-        const u32x2 r1 = __builtin_amdgcn_permlane32_swap(pk[4 * s + 1], pk[4 * s + 3], false, false);
-        if (rok) {
-          const u32x4 v = {r0[0], r1[0], r0[1], r1[1]};
-          *reinterpret_cast<u32x4*>(base + opix * ld + b * 32 + 16 * s + 8 * lh) = v;
-        }
-      }
-    };
-    // 1. x = conv + bias, rounded to bf16 (what the backward pass reads); x^2 rounded again: the pool's operand
+    // 1. x = conv + bias -> bf16, x^2 -> bf16: the pool's operand
     unsigned sqpk[TW][8];
 #pragma unroll
     for (int b = 0; b < TW; ++b) {
-      unsigned xpk[8];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
+      auto bias = [&](int g) {
         f32x4 bs = {0.0f, 0.0f, 0.0f, 0.0f};
         if (p.bias) bs = *reinterpret_cast<const f32x4*>(p.bias + b * 32 + 4 * lh + 8 * g);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const f32x2 v = {acc[0][b][4 * g + 2 * h] + bs[2 * h], acc[0][b][4 * g + 2 * h + 1] + bs[2 * h + 1]};
-          const unsigned pk = pack2(v);
-          xpk[2 * g + h] = pk;
-          const f32x2 xb = {__builtin_bit_cast(float, pk << 16), __builtin_bit_cast(float, pk & 0xffff0000u)};
-          acc[0][b][4 * g + 2 * h] = xb[0];
-          acc[0][b][4 * g + 2 * h + 1] = xb[1];
-          sqpk[b][2 * g + h] = pack2(xb * xb);
-        }
-      }
-      if (p.out3) store_tile(p.out3, p.out3_ld, xpk, b);
+        return bs;
+      };
+      unsigned xpk[8];
+      gdn_fwd_square_tile(acc[0][b], bias, xpk, sqpk[b]);
+      if (p.out3) store_tile_swapped(p.out3, p.out3_ld, opix, rok, b * 32, lh, xpk);
     }
     // 2. norm^T = gamma_eff . (x^2)^T: A fragments of gamma_eff^T straight from L2 (16 bytes per lane, fragment order)
     f32x16 nacc[TW];
@@ -465,27 +438,15 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
           nacc[bo] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b2, nacc[bo], 0, 0, 0);
         }
       }
-    // 3. y = x * norm^-1/2 (GDN) or x * norm^1/2 (IGDN), element-wise in the accumulator layout
+    // 3. y = x * norm^-1/2 (GDN) or x * norm^1/2 (IGDN)
     auto finish = [&](auto inv) {
-      constexpr bool INV = decltype(inv)::value;
 #pragma unroll
       for (int b = 0; b < TW; ++b) {
+        auto beta = [&](int g) { return *reinterpret_cast<const f32x4*>(p.beta + b * 32 + 4 * lh + 8 * g); };
         unsigned npk[8], ypk[8];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 be = *reinterpret_cast<const f32x4*>(p.beta + b * 32 + 4 * lh + 8 * g);
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const f32x2 nv = {nacc[b][4 * g + 2 * h] + be[2 * h], nacc[b][4 * g + 2 * h + 1] + be[2 * h + 1]};
-            npk[2 * g + h] = pack2(nv);
-            const f32x2 f = {INV ? __builtin_amdgcn_sqrtf(nv[0]) : __builtin_amdgcn_rsqf(nv[0]),
-                             INV ? __builtin_amdgcn_sqrtf(nv[1]) : __builtin_amdgcn_rsqf(nv[1])};
-            const f32x2 xv = {acc[0][b][4 * g + 2 * h], acc[0][b][4 * g + 2 * h + 1]};
-            ypk[2 * g + h] = pack2(xv * f);
-          }
-        }
-        if (p.out2) store_tile(p.out2, p.out2_ld, npk, b);
-        store_tile(reinterpret_cast<bf16_t*>(p.out), p.out_ld, ypk, b);
+        gdn_fwd_finish_tile(nacc[b], beta, acc[0][b], inv, npk, ypk);
+        if (p.out2) store_tile_swapped(p.out2, p.out2_ld, opix, rok, b * 32, lh, npk);
+        store_tile_swapped(reinterpret_cast<bf16_t*>(p.out), p.out_ld, opix, rok, b * 32, lh, ypk);
       }
     };
     if (epi == LIC_EPI_CONV_IGDN) finish(std::true_type{});

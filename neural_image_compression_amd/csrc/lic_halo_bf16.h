@@ -32,9 +32,9 @@
 //     so only a workgroup's first tile pays a cold prologue (measured with in-kernel stamps on the one-tile-per-
 //     workgroup version: prologue 8.7 us + LDS-staged epilogue 6.5 us around a 41 us main loop).
 //   * the accumulators hold the TRANSPOSED tile (MFMA operands swapped: channels down the rows, pixels across the
-//     lanes), as in the fused conv+GDN kernel above: a lane owns 4 x 4 consecutive channels of one pixel per tile, so
-//     bias / LeakyReLU / bf16 packing are element-wise and one v_permlane32_swap per dword pair gives 16-byte stores --
-//     the epilogue uses no LDS (the buffers already hold the next tile's first chunk).
+//     lanes): a lane owns 4 x 4 consecutive channels of one pixel per tile, so bias / LeakyReLU / bf16 packing are
+//     element-wise and a lane-half swap gives 16-byte stores -- the epilogue (halo_epilogue_plain / halo_epilogue_fused
+//     in lic_epilogue_bf16.h) uses no LDS of its own (the buffers already hold the next tile's first chunk).
 //
 // Same packed weights, same epilogue conventions as igemm_bf16_kernel.  The K order per output differs (chunk-major
 // instead of tap-major): results agree with the other variants to fp32 summation order, not bitwise.
@@ -61,7 +61,6 @@ constexpr int younger(int t, int NB) {
 }
 }  // namespace halo
 
-typedef unsigned hu32x4 __attribute__((ext_vector_type(4)));
 #ifdef LIC_HALO_ABLATE
 __device__ unsigned long long g_halo_dbg[1024 * 10];
 #define HALO_STAMP(i)                                                    \
@@ -195,8 +194,8 @@ __global__ __launch_bounds__(256, 1) void halo_conv_bf16_kernel(const IgemmHPara
   const long wrap_next = PANEL - (long)(NTAP - 1) * tap_inc;  // tap 24 of chunk c -> tap 0 of chunk c + 1
 
   f32x16 acc[4][TW];
-  hu32x4 af[2][4][2];   // [slot][row tile][k step]
-  hu32x4 bq[D][TW][2];  // [slot][column tile][k step]
+  u32x4 af[2][4][2];   // [slot][row tile][k step]
+  u32x4 bq[D][TW][2];  // [slot][column tile][k step]
   auto& af_ = af;
   auto& bq_ = bq;
 
@@ -308,9 +307,6 @@ __global__ __launch_bounds__(256, 1) void halo_conv_bf16_kernel(const IgemmHPara
   });
   HALO_STAMP(1);
 
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   for (int it = 0;; ++it) {
     const int tnext = tile + G;
     const bool more = tnext < ntiles;
@@ -337,211 +333,21 @@ __global__ __launch_bounds__(256, 1) void halo_conv_bf16_kernel(const IgemmHPara
     }
     if (it == 0) HALO_STAMP(2);
 
-    if constexpr (FUSE) {
-      // ---- conv -> GDN / IGDN in the same launch (LIC_EPI_CONV_GDN / CONV_IGDN; Components.py:12-15), as the fused
-      // variant of igemm_bf16_kernel does it: x = conv + bias rounded to bf16, x^2 rounded again is the B operand of
-      // norm^T = gamma_eff . (x^2)^T in the K order a lane owns its channels in (gamma_eff^T packed by
-      // lic_pack_weight_bf16_kperm), y = x * norm^-1/2 (or ^1/2) element-wise in the accumulator layout.  Here a wave
-      // holds only HALF the channels of its pixels (2 x 2 waves), so the x^2 fragments are exchanged through LDS:
-      // every wave writes its 16 fragments (4 row tiles x 2 channel tiles x 2 k steps, lane-linear 1 KiB each) into
-      // the halo buffer that is idle now (buffer 1: buffer 0 already holds the next tile's first chunk), one barrier,
-      // and reads back all 32 fragments of its pixel half -- its partner's lanes own the same pixels, so the exchange
-      // is a lane-wise copy.  A second barrier at the end keeps the next tile's DMA out of the buffer until every
-      // wave has read.
-      int lho = lh, lio = li, wno = wn, wmo = wm;
-      asm volatile("" : "+v"(lho), "+v"(lio), "+s"(wno), "+s"(wmo));
-      const bool inv = p.epilogue == LIC_EPI_CONV_IGDN;
-      unsigned char* xch = smem + BUFB;                       // [wm][a][channel tile 0..2TW-1][k step][64 lanes][16 B]
-      auto frag_at = [&](int wmi, int a, int tt, int s2) { return xch + ((((wmi * 4 + a) * (2 * TW) + tt) * 2 + s2) * 64 + lane) * 16; };
-      auto pack2 = [](f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); };
-      auto store_tile = [&](bf16_t* base, long ld, long opix, bool rok, int cb, const unsigned (&pk)[8]) {
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const u32x2 r0 = __builtin_amdgcn_permlane32_swap(pk[4 * s2], pk[4 * s2 + 2], false, false);
-          const u32x2 r1 = __builtin_amdgcn_permlane32_swap(pk[4 * s2 + 1], pk[4 * s2 + 3], false, false);
-          if (rok) {
-            const hu32x4 o = {r0[0], r1[0], r0[1], r1[1]};
-            *reinterpret_cast<hu32x4*>(base + opix * ld + cb + 16 * s2 + 8 * lho) = o;
-          }
-        }
-      };
-      f32x4 bs[TW][4];
-#pragma unroll
-      for (int t = 0; t < TW; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bs[t][g] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (p.bias) {
-#pragma unroll
-        for (int t = 0; t < TW; ++t)
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            bs[t][g] = *reinterpret_cast<const f32x4*>(p.bias + (wno * TW + t) * 32 + 4 * lho + 8 * g);
-      }
-      // (gamma_eff^T fragments and beta_eff are requested NOW, all at once: a load in front of each pool MFMA /
-      // each finish tile was one exposed L2 round trip after the other at one wave per SIMD -- the fused epilogue
-      // took 14 us per tile that way)
-      const bf16_t* gA = p.aux + lane * 8;
-      const int ntile = p.Npad >> 5;
-      bf16x8 gfr[2 * TW][2][TW];
-#pragma unroll
-      for (int tt = 0; tt < 2 * TW; ++tt)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-          for (int t = 0; t < TW; ++t)
-            gfr[tt][s2][t] = *reinterpret_cast<const bf16x8*>(gA + ((long)tt * ntile + (wno * TW + t)) * 1024 + s2 * 512);
-      f32x4 be[TW][4];
-#pragma unroll
-      for (int t = 0; t < TW; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) be[t][g] = *reinterpret_cast<const f32x4*>(p.beta + (wno * TW + t) * 32 + 4 * lho + 8 * g);
-      // 1. x -> bf16 (kept in the accumulators as the rounded value), x^2 -> bf16 -> LDS; the conv output if asked for
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int oy = cur.oy0 + 4 * wmo + a, ox = cur.ox0 + lio;
-        const bool rok = oy < p.Ho && ox < p.Wo;
-        const long opix = rok ? ((long)cur.b * p.Ho + oy) * p.Wo + ox : 0;
-#pragma unroll
-        for (int t = 0; t < TW; ++t) {
-          unsigned xpk[8], sqpk[8];
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const f32x2 v = {acc[a][t][4 * g + 2 * h] + bs[t][g][2 * h], acc[a][t][4 * g + 2 * h + 1] + bs[t][g][2 * h + 1]};
-              const unsigned pk = pack2(v);
-              xpk[2 * g + h] = pk;
-              const f32x2 xb = {__builtin_bit_cast(float, pk << 16), __builtin_bit_cast(float, pk & 0xffff0000u)};
-              acc[a][t][4 * g + 2 * h] = xb[0];
-              acc[a][t][4 * g + 2 * h + 1] = xb[1];
-              sqpk[2 * g + h] = pack2(xb * xb);
-            }
-          if (p.out3) store_tile(p.out3, p.out3_ld, opix, rok, (wno * TW + t) * 32, xpk);
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2)
-            *reinterpret_cast<hu32x4*>(frag_at(wmo, a, wno * TW + t, s2)) =
-                hu32x4{sqpk[4 * s2], sqpk[4 * s2 + 1], sqpk[4 * s2 + 2], sqpk[4 * s2 + 3]};
-        }
-      }
-      __syncthreads();
-      // 2. + 3. two row tiles at a time (register budget): pool over all 2 TW input channel tiles, then finish
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        f32x16 nacc[2][TW];
-#pragma unroll
-        for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-          for (int t = 0; t < TW; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) nacc[a2][t][r] = 0.0f;
-#pragma unroll
-        for (int tt = 0; tt < 2 * TW; ++tt)
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            bf16x8 b2[2];
-#pragma unroll
-            for (int a2 = 0; a2 < 2; ++a2) b2[a2] = *reinterpret_cast<const bf16x8*>(frag_at(wmo, 2 * hh + a2, tt, s2));
-#pragma unroll
-            for (int t = 0; t < TW; ++t) {
-              const bf16x8 a2f = gfr[tt][s2][t];
-#pragma unroll
-              for (int a2 = 0; a2 < 2; ++a2)
-                nacc[a2][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2f, b2[a2], nacc[a2][t], 0, 0, 0);
-            }
-          }
-#pragma unroll
-        for (int a2 = 0; a2 < 2; ++a2) {
-          const int a = 2 * hh + a2;
-          const int oy = cur.oy0 + 4 * wmo + a, ox = cur.ox0 + lio;
-          const bool rok = oy < p.Ho && ox < p.Wo;
-          const long opix = rok ? ((long)cur.b * p.Ho + oy) * p.Wo + ox : 0;
-#pragma unroll
-          for (int t = 0; t < TW; ++t) {
-            const int cb = (wno * TW + t) * 32;
-            unsigned npk[8], ypk[8];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              #pragma unroll
-              for (int h = 0; h < 2; ++h) {
-                const f32x2 nv = {nacc[a2][t][4 * g + 2 * h] + be[t][g][2 * h], nacc[a2][t][4 * g + 2 * h + 1] + be[t][g][2 * h + 1]};
-                npk[2 * g + h] = pack2(nv);
-                const f32x2 f = {inv ? __builtin_amdgcn_sqrtf(nv[0]) : __builtin_amdgcn_rsqf(nv[0]),
-                                 inv ? __builtin_amdgcn_sqrtf(nv[1]) : __builtin_amdgcn_rsqf(nv[1])};
-                const f32x2 xv = {acc[a][t][4 * g + 2 * h], acc[a][t][4 * g + 2 * h + 1]};
-                ypk[2 * g + h] = pack2(xv * f);
-              }
-            }
-            if (p.out2) store_tile(p.out2, p.out2_ld, opix, rok, cb, npk);
-            store_tile(reinterpret_cast<bf16_t*>(p.out), p.out_ld, opix, rok, cb, ypk);
-          }
-        }
-      }
-      __syncthreads();   // (the next tile's second chunk is DMA'd into the exchange buffer)
-    } else
-    // ---- epilogue, straight from the registers: lane (li, lh) holds, of tile (a, t), pixel li of output row
-    // 4 wm + a and channels 32 (wn TW + t) + 8 g + 4 lh + {0..3}, g = 0..3.  LeakyReLU as max(v, slope v) (slope 1 =
-    // none); the bias is fetched in one batch (a load per tile would drain the stores in flight every time).
+    // ---- epilogue, straight from the registers (lic_epilogue_bf16.h).  The fused pool exchanges its x^2 fragments
+    // through the halo buffer that is idle now (buffer 1: buffer 0 already holds the next tile's first chunk); the
+    // barrier that ends it keeps the next tile's second chunk, which is DMA'd there, out until every wave has read.
     {
-      // (opaque copies: hipcc otherwise hoists every address below out of the tile loop and spills it across the
-      // main loop)
+      // (opaque copies: hipcc otherwise hoists every address of the epilogue out of the tile loop and spills it
+      // across the main loop)
       int lho = lh, lio = li, wno = wn, wmo = wm;
       asm volatile("" : "+v"(lho), "+v"(lio), "+s"(wno), "+s"(wmo));
-      f32x4 bs[TW][4];
-#pragma unroll
-      for (int t = 0; t < TW; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bs[t][g] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (p.bias) {
-#pragma unroll
-        for (int t = 0; t < TW; ++t)
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            bs[t][g] = *reinterpret_cast<const f32x4*>(p.bias + (wno * TW + t) * 32 + 4 * lho + 8 * g);
-      }
-      const float sl = p.epilogue == LIC_EPI_LEAKY ? p.slope : 1.0f;
-      const bool of32 = p.out_f32 != 0;
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
+      auto out_pixel = [&](int a, bool& rok) {
         const int oy = cur.oy0 + 4 * wmo + a, ox = cur.ox0 + lio;
-        const bool rok = oy < p.Ho && ox < p.Wo;
-        const long opix = rok ? ((long)cur.b * p.Ho + oy) * p.Wo + ox : 0;
-#pragma unroll
-        for (int t = 0; t < TW; ++t) {
-          const int cb = (wno * TW + t) * 32;
-          f32x4 v[4];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            v[g] = f32x4{acc[a][t][4 * g], acc[a][t][4 * g + 1], acc[a][t][4 * g + 2], acc[a][t][4 * g + 3]} + bs[t][g];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[g][e] = __builtin_fmaxf(v[g][e], v[g][e] * sl);
-          }
-          if (of32) {
-            if (rok) {
-#pragma unroll
-              for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + opix * p.out_ld + cb + 8 * g + 4 * lho) = v[g];
-            }
-          } else {
-            unsigned pk[8];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const f32x2 v0 = {v[g][0], v[g][1]}, v1 = {v[g][2], v[g][3]};
-              pk[2 * g] = __builtin_bit_cast(unsigned, __builtin_convertvector(v0, bf16x2));
-              pk[2 * g + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(v1, bf16x2));
-            }
-            // lanes li and li + 32 exchange halves: each ends up with 8 consecutive channels -> 16-byte stores
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-              const u32x2 r0 = __builtin_amdgcn_permlane32_swap(pk[4 * s2], pk[4 * s2 + 2], false, false);
-              const u32x2 r1 = __builtin_amdgcn_permlane32_swap(pk[4 * s2 + 1], pk[4 * s2 + 3], false, false);
-              if (rok) {
-                const hu32x4 o = {r0[0], r1[0], r0[1], r1[1]};
-                *reinterpret_cast<hu32x4*>(reinterpret_cast<bf16_t*>(p.out) + opix * p.out_ld + cb + 16 * s2 + 8 * lho) = o;
-              }
-            }
-          }
-        }
-      }
+        rok = oy < p.Ho && ox < p.Wo;
+        return rok ? ((long)cur.b * p.Ho + oy) * p.Wo + ox : 0L;
+      };
+      if constexpr (FUSE) halo_epilogue_fused<TW>(acc, p, smem + BUFB, lane, lho, wno, wmo, out_pixel);
+      else halo_epilogue_plain<TW>(acc, p, lho, wno, out_pixel);
     }
     if (it == 0) HALO_STAMP(3);
     if (!more) break;

@@ -160,8 +160,8 @@ __global__ __launch_bounds__(256, 1) void halo_convt_bf16_kernel(const IgemmHPar
   const long tap_inc = (long)nch * PANEL;
 
   f32x16 acc[4][TW];
-  hu32x4 af[2][4][2];
-  hu32x4 bq[6][TW][2];
+  u32x4 af[2][4][2];
+  u32x4 bq[6][TW][2];
   auto& af_ = af;
   auto& bq_ = bq;
 
@@ -264,9 +264,6 @@ __global__ __launch_bounds__(256, 1) void halo_convt_bf16_kernel(const IgemmHPar
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(DIST * NB) : "memory");
   read_first(std::integral_constant<int, 0>{});
 
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   for (;;) {
     const int tnext = tile + G;
     const bool more = tnext < ntiles;
@@ -302,174 +299,19 @@ __global__ __launch_bounds__(256, 1) void halo_convt_bf16_kernel(const IgemmHPar
                      "+a"(af[0][2][1]), "+a"(af[0][3][0]), "+a"(af[0][3][1]));
       read_first(std::integral_constant<int, (PH + 1) & 3>{});
 
-      // ---- epilogue of the phase, straight from the registers (see halo_conv_bf16_kernel)
+      // ---- epilogue of the phase, straight from the registers (lic_epilogue_bf16.h); the fused pool exchanges its
+      // x^2 fragments through a dedicated area behind the chunk buffers (which hold the next phase's first chunk)
+      // (opaque copies: hipcc otherwise hoists every address of the epilogue out of the tile loop and spills it
+      // across the main loop)
       int lho = lh, lio = li, wno = wn, wmo = wm;
       asm volatile("" : "+v"(lho), "+v"(lio), "+s"(wno), "+s"(wmo));
-      f32x4 bs[TW][4];
-#pragma unroll
-      for (int t = 0; t < TW; ++t)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bs[t][g] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      if (p.bias) {
-#pragma unroll
-        for (int t = 0; t < TW; ++t)
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            bs[t][g] = *reinterpret_cast<const f32x4*>(p.bias + (wno * TW + t) * 32 + 4 * lho + 8 * g);
-      }
       auto out_pixel = [&](int a, bool& rok) {
         const int oy = 2 * (cur.qy0 + 4 * wmo + a) + py(PH), ox = 2 * (cur.qx0 + lio) + px(PH);
         rok = oy < p.Ho && ox < p.Wo;
         return rok ? ((long)cur.b * p.Ho + oy) * p.Wo + ox : 0L;
       };
-      auto pack2 = [](f32x2 v) { return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)); };
-      auto store_tile = [&](bf16_t* base, long ld, long opix, bool rok, int cb, const unsigned (&pk)[8]) {
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const u32x2 r0 = __builtin_amdgcn_permlane32_swap(pk[4 * s2], pk[4 * s2 + 2], false, false);
-          const u32x2 r1 = __builtin_amdgcn_permlane32_swap(pk[4 * s2 + 1], pk[4 * s2 + 3], false, false);
-          if (rok) {
-            const hu32x4 o = {r0[0], r1[0], r0[1], r1[1]};
-            *reinterpret_cast<hu32x4*>(base + opix * ld + cb + 16 * s2 + 8 * lho) = o;
-          }
-        }
-      };
-      if constexpr (FUSE) {
-        // conv -> IGDN / GDN in the same launch: see the fused epilogue of halo_conv_bf16_kernel (x^2 fragments of the
-        // two channel halves exchanged through LDS, here a dedicated area behind the chunk buffers)
-        const bool inv = p.epilogue == LIC_EPI_CONV_IGDN;
-        unsigned char* xch = smem + 2 * BUFB;
-        // (gamma_eff^T fragments and beta_eff requested up front, all at once: see halo_conv_bf16_kernel)
-        const bf16_t* gA = p.aux + lane * 8;
-        const int ntile = p.Npad >> 5;
-        bf16x8 gfr[2 * TW][2][TW];
-#pragma unroll
-        for (int tt = 0; tt < 2 * TW; ++tt)
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-            for (int t = 0; t < TW; ++t)
-              gfr[tt][s2][t] = *reinterpret_cast<const bf16x8*>(gA + ((long)tt * ntile + (wno * TW + t)) * 1024 + s2 * 512);
-        f32x4 be[TW][4];
-#pragma unroll
-        for (int t = 0; t < TW; ++t)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) be[t][g] = *reinterpret_cast<const f32x4*>(p.beta + (wno * TW + t) * 32 + 4 * lho + 8 * g);
-        auto frag_at = [&](int wmi, int a, int tt, int s2) { return xch + ((((wmi * 4 + a) * (2 * TW) + tt) * 2 + s2) * 64 + lane) * 16; };
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          bool rok;
-          const long opix = out_pixel(a, rok);
-#pragma unroll
-          for (int t = 0; t < TW; ++t) {
-            unsigned xpk[8], sqpk[8];
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-              for (int h = 0; h < 2; ++h) {
-                const f32x2 v = {acc[a][t][4 * g + 2 * h] + bs[t][g][2 * h], acc[a][t][4 * g + 2 * h + 1] + bs[t][g][2 * h + 1]};
-                const unsigned pk = pack2(v);
-                xpk[2 * g + h] = pk;
-                const f32x2 xb = {__builtin_bit_cast(float, pk << 16), __builtin_bit_cast(float, pk & 0xffff0000u)};
-                acc[a][t][4 * g + 2 * h] = xb[0];
-                acc[a][t][4 * g + 2 * h + 1] = xb[1];
-                sqpk[2 * g + h] = pack2(xb * xb);
-              }
-            if (p.out3) store_tile(p.out3, p.out3_ld, opix, rok, (wno * TW + t) * 32, xpk);
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-              *reinterpret_cast<hu32x4*>(frag_at(wmo, a, wno * TW + t, s2)) =
-                  hu32x4{sqpk[4 * s2], sqpk[4 * s2 + 1], sqpk[4 * s2 + 2], sqpk[4 * s2 + 3]};
-          }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh) {
-          f32x16 nacc[2][TW];
-#pragma unroll
-          for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-            for (int t = 0; t < TW; ++t)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) nacc[a2][t][r] = 0.0f;
-#pragma unroll
-          for (int tt = 0; tt < 2 * TW; ++tt)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-              bf16x8 b2[2];
-#pragma unroll
-              for (int a2 = 0; a2 < 2; ++a2) b2[a2] = *reinterpret_cast<const bf16x8*>(frag_at(wmo, 2 * hh + a2, tt, s2));
-#pragma unroll
-              for (int t = 0; t < TW; ++t) {
-                const bf16x8 a2f = gfr[tt][s2][t];
-#pragma unroll
-                for (int a2 = 0; a2 < 2; ++a2)
-                  nacc[a2][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2f, b2[a2], nacc[a2][t], 0, 0, 0);
-              }
-            }
-#pragma unroll
-          for (int a2 = 0; a2 < 2; ++a2) {
-            const int a = 2 * hh + a2;
-            bool rok;
-            const long opix = out_pixel(a, rok);
-#pragma unroll
-            for (int t = 0; t < TW; ++t) {
-              const int cb = (wno * TW + t) * 32;
-              unsigned npk[8], ypk[8];
-#pragma unroll
-              for (int g = 0; g < 4; ++g) {
-                #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                  const f32x2 nv = {nacc[a2][t][4 * g + 2 * h] + be[t][g][2 * h], nacc[a2][t][4 * g + 2 * h + 1] + be[t][g][2 * h + 1]};
-                  npk[2 * g + h] = pack2(nv);
-                  const f32x2 f = {inv ? __builtin_amdgcn_sqrtf(nv[0]) : __builtin_amdgcn_rsqf(nv[0]),
-                                   inv ? __builtin_amdgcn_sqrtf(nv[1]) : __builtin_amdgcn_rsqf(nv[1])};
-                  const f32x2 xv = {acc[a][t][4 * g + 2 * h], acc[a][t][4 * g + 2 * h + 1]};
-                  ypk[2 * g + h] = pack2(xv * f);
-                }
-              }
-              if (p.out2) store_tile(p.out2, p.out2_ld, opix, rok, cb, npk);
-              store_tile(reinterpret_cast<bf16_t*>(p.out), p.out_ld, opix, rok, cb, ypk);
-            }
-          }
-        }
-        __syncthreads();   // (the next phase's pool writes the exchange area again)
-      } else {
-        const float sl = p.epilogue == LIC_EPI_LEAKY ? p.slope : 1.0f;
-        const bool of32 = p.out_f32 != 0;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-          bool rok;
-          const long opix = out_pixel(a, rok);
-#pragma unroll
-          for (int t = 0; t < TW; ++t) {
-            const int cb = (wno * TW + t) * 32;
-            f32x4 v[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              v[g] = f32x4{acc[a][t][4 * g], acc[a][t][4 * g + 1], acc[a][t][4 * g + 2], acc[a][t][4 * g + 3]} + bs[t][g];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[g][e] = __builtin_fmaxf(v[g][e], v[g][e] * sl);
-            }
-            if (of32) {
-              if (rok) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                  *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.out) + opix * p.out_ld + cb + 8 * g + 4 * lho) = v[g];
-              }
-            } else {
-              unsigned pk[8];
-#pragma unroll
-              for (int g = 0; g < 4; ++g) {
-                const f32x2 v0 = {v[g][0], v[g][1]}, v1 = {v[g][2], v[g][3]};
-                pk[2 * g] = pack2(v0);
-                pk[2 * g + 1] = pack2(v1);
-              }
-              store_tile(reinterpret_cast<bf16_t*>(p.out), p.out_ld, opix, rok, cb, pk);
-            }
-          }
-        }
-      }
+      if constexpr (FUSE) halo_epilogue_fused<TW>(acc, p, smem + 2 * BUFB, lane, lho, wno, wmo, out_pixel);
+      else halo_epilogue_plain<TW>(acc, p, lho, wno, out_pixel);
     });
     if (!more) break;
     cur = nxt;

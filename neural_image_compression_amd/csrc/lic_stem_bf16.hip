@@ -13,21 +13,15 @@
 //     straight from the image (the 6x overlap between neighbouring windows is L1/L2 traffic), converted to bf16
 //     in registers; slot 15 of a row multiplies a zero weight;
 //   * the accumulators hold the transposed tile (lane = pixel; channels 4*lh + 8*g + j of every 32-channel
-//     tile), as in igemm_bf16_kernel's FUSE variant: x -> bf16, x^2 -> bf16 and the pool's operand stay in
-//     registers, gamma_eff^T comes from LDS in lic_pack_weight_bf16_kperm's order, y = x * rsqrt(norm) is
-//     element-wise, and v_permlane32_swap turns a lane's 4+4 channels into 8 consecutive ones for 16-byte stores.
-// Rounding points are those of conv2d_bf16 -> gdn_bf16 (x and x^2 to bf16, fp32 norm).
-#include "lic_common.h"
+//     tile) and are finished by the transposed-tile epilogue of lic_epilogue_bf16.h: x -> bf16, x^2 -> bf16 and the
+//     pool's operand stay in registers, gamma_eff^T comes from LDS in lic_pack_weight_bf16_kperm's order, y = x *
+//     rsqrt(norm) is element-wise, and a lane-half swap gives 16-byte stores of 8 consecutive channels.
+// Rounding points are those of conv2d_bf16 -> gdn_bf16 (x and x^2 to bf16, fp32 norm), defined in that header.
+#include "lic_epilogue_bf16.h"
 #include <type_traits>
 
 namespace {
 
-typedef __bf16 bf16_t;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));  // image rows are only 4-byte aligned
 
 struct StemParams {
@@ -43,10 +37,6 @@ struct StemParams {
   long P;
   int ntiles;
 };
-
-__device__ __forceinline__ unsigned pack2(f32x2 v) {
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 
 // TW: 32-channel tiles (C = 32*TW); NW: waves per workgroup (tile = 32*NW pixels).
 // (C = 128 compiles to 184 VGPR + 64 AGPR: two waves per SIMD.  Forced to three -- 168 registers, 60 bytes of
@@ -136,44 +126,20 @@ __global__ __launch_bounds__(64 * NW) void stem_gdn_bf16_kernel(const StemParams
       }
     }
 
-    auto store_tile = [&](bf16_t* base, const unsigned (&pk)[8], int t) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const u32x2 r0 = __builtin_amdgcn_permlane32_swap(pk[4 * s], pk[4 * s + 2], false, false);
-        const u32x2 r1 = __builtin_amdgcn_permlane32_swap(pk[4 * s + 1], pk[4 * s + 3], false, false);
-        if (rok) {
-          const u32x4 v = {r0[0], r1[0], r0[1], r1[1]};
-          *reinterpret_cast<u32x4*>(base + prow * C + t * 32 + 16 * s + 8 * lh) = v;
-        }
-      }
-    };
-    // x = conv + bias -> bf16; x^2 -> bf16 (the pool's B operand)
+    // the transposed-tile epilogue of lic_epilogue_bf16.h: x = conv + bias -> bf16; x^2 -> bf16 (the pool's B operand)
     unsigned sqpk[TW][8];
 #pragma unroll
     for (int t = 0; t < TW; ++t) {
+      auto bias = [&](int g) { return *reinterpret_cast<const f32x4*>(s_bias + t * 32 + 4 * lh + 8 * g); };
       unsigned xpk[8];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 bs = *reinterpret_cast<const f32x4*>(s_bias + t * 32 + 4 * lh + 8 * g);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const f32x2 v = {acc[t][4 * g + 2 * h] + bs[2 * h], acc[t][4 * g + 2 * h + 1] + bs[2 * h + 1]};
-          const unsigned pk = pack2(v);
-          xpk[2 * g + h] = pk;
-          const f32x2 xb = {__builtin_bit_cast(float, pk << 16), __builtin_bit_cast(float, pk & 0xffff0000u)};
-          acc[t][4 * g + 2 * h] = xb[0];
-          acc[t][4 * g + 2 * h + 1] = xb[1];
-          sqpk[t][2 * g + h] = pack2(xb * xb);
-        }
-      }
-      if (PLAIN) store_tile(p.y, xpk, t);
-      else if (p.conv_out) store_tile(p.conv_out, xpk, t);
+      gdn_fwd_square_tile(acc[t], bias, xpk, sqpk[t]);
+      if (PLAIN) store_tile_swapped(p.y, C, prow, rok, t * 32, lh, xpk);
+      else if (p.conv_out) store_tile_swapped(p.conv_out, C, prow, rok, t * 32, lh, xpk);
     }
     if (PLAIN) continue;
     asm volatile("" ::: "memory");
     // per output-channel tile: norm^T = gamma_eff . (x^2)^T + beta, y = x * norm^-1/2 (or ^1/2)
     auto finish = [&](auto inv) {
-      constexpr bool INV = decltype(inv)::value;
 #pragma unroll
       for (int bo = 0; bo < TW; ++bo) {
         f32x16 nacc;
@@ -187,22 +153,11 @@ __global__ __launch_bounds__(64 * NW) void stem_gdn_bf16_kernel(const StemParams
             const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(s_g + ((t * TW + bo) * 2 + s) * 512 + lane * 8);
             nacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, __builtin_bit_cast(bf16x8, bq), nacc, 0, 0, 0);
           }
+        auto beta = [&](int g) { return *reinterpret_cast<const f32x4*>(s_beta + bo * 32 + 4 * lh + 8 * g); };
         unsigned npk[8], ypk[8];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const f32x4 be = *reinterpret_cast<const f32x4*>(s_beta + bo * 32 + 4 * lh + 8 * g);
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const f32x2 nv = {nacc[4 * g + 2 * h] + be[2 * h], nacc[4 * g + 2 * h + 1] + be[2 * h + 1]};
-            npk[2 * g + h] = pack2(nv);
-            const f32x2 f = {INV ? __builtin_amdgcn_sqrtf(nv[0]) : __builtin_amdgcn_rsqf(nv[0]),
-                             INV ? __builtin_amdgcn_sqrtf(nv[1]) : __builtin_amdgcn_rsqf(nv[1])};
-            const f32x2 xv = {acc[bo][4 * g + 2 * h], acc[bo][4 * g + 2 * h + 1]};
-            ypk[2 * g + h] = pack2(xv * f);
-          }
-        }
-        if (p.norm) store_tile(p.norm, npk, bo);
-        store_tile(p.y, ypk, bo);
+        gdn_fwd_finish_tile(nacc, beta, acc[bo], inv, npk, ypk);
+        if (p.norm) store_tile_swapped(p.norm, C, prow, rok, bo * 32, lh, npk);
+        store_tile_swapped(p.y, C, prow, rok, bo * 32, lh, ypk);
       }
     };
     if (p.inverse) finish(std::true_type{});
