@@ -4,7 +4,7 @@
 // the kernels' job is to keep that pipe issuing: K is consumed in 16-deep chunks staged
 // through LDS, the next chunk's global loads are issued before the current chunk's MFMAs, and
 // 3-4 workgroups per CU cover each other's load/store phases.
-#include "lic_conv_plan.h"
+#include "lic_tile_map.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -63,8 +63,58 @@ constexpr int IG_LDA = IG_BK + 4;
 
 // 16 zero bytes: the source of LDS-DMA lanes that fall on padding / past the last pixel
 __device__ __attribute__((aligned(16))) float g_lic_zero16[4];
-typedef const __attribute__((address_space(1))) void* lic_gptr_t;
-typedef __attribute__((address_space(3))) void* lic_lptr_t;
+
+// ---- the elementwise epilogue of igemm_kernel, on one value (scalar path) or four channels (staged 16-byte path)
+// The two paths round differently, and stay so: a scalar goes through sqrtf and a division, a vector through
+// v_rsq_f32 / v_sqrt_f32 (1 ulp, far inside the 1e-4 bar).
+__device__ __forceinline__ float ew_rsqrt(float v) { return 1.0f / sqrtf(v); }
+__device__ __forceinline__ float ew_sqrt(float v) { return sqrtf(v); }
+__device__ __forceinline__ float ew_where_pos(float m, float a, float b) { return m > 0.0f ? a : b; }
+// the GDN backward combination: the scalar path is left to contract into fmas, the 16-byte path rounds both products
+// and the sum (what its packed multiplies and adds have always computed), now said rather than left to the vectoriser
+__device__ __forceinline__ float ew_gdn_bwd(float g, float f, float x, float v) { return g * f + 2.0f * x * v; }
+__device__ __forceinline__ f32x4 ew_gdn_bwd(f32x4 g, f32x4 f, f32x4 x, f32x4 v) {
+#pragma clang fp contract(off)
+  return g * f + 2.0f * x * v;
+}
+__device__ __forceinline__ f32x4 ew_rsqrt(f32x4 v) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_rsqf(v[e]);
+  return v;
+}
+__device__ __forceinline__ f32x4 ew_sqrt(f32x4 v) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_sqrtf(v[e]);
+  return v;
+}
+__device__ __forceinline__ f32x4 ew_where_pos(f32x4 m, f32x4 a, f32x4 b) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a[e] = m[e] > 0.0f ? a[e] : b[e];
+  return a;
+}
+// v = accumulator + bias at output pixel `opix`, channel(s) `col`..; applies p's epilogue and stores
+template <class V>
+__device__ __forceinline__ void igemm_elementwise(const IgemmParams& p, int epi, long opix, int col, V v) {
+  auto ld = [&](const float* t, long pitch) { return *reinterpret_cast<const V*>(t + opix * pitch + col); };
+  auto st = [&](float* t, long pitch, V x) { *reinterpret_cast<V*>(t + opix * pitch + col) = x; };
+  if (epi == LIC_EPI_LEAKY) {
+    v = ew_where_pos(v, v, v * p.slope);
+    if (p.res) st(p.out2, p.out2_ld, v + ld(p.res, p.res_ld));
+  } else {
+    if (epi == LIC_EPI_MUL_LEAKY_MASK) {
+      v = ew_where_pos(ld(p.aux, p.aux_ld), v, v * p.slope);
+    } else if (epi == LIC_EPI_GDN || epi == LIC_EPI_IGDN) {
+      if (p.out2) st(p.out2, p.out2_ld, v);
+      v = ld(p.aux, p.aux_ld) * ((epi == LIC_EPI_GDN) ? ew_rsqrt(v) : ew_sqrt(v));
+    } else if (epi == LIC_EPI_GDN_BWD || epi == LIC_EPI_IGDN_BWD) {
+      const V n = ld(p.aux3, p.aux3_ld);
+      const V f = (epi == LIC_EPI_GDN_BWD) ? ew_rsqrt(n) : ew_sqrt(n);
+      v = ew_gdn_bwd(ld(p.aux, p.aux_ld), f, ld(p.aux2, p.aux2_ld), v);
+    }
+    if (p.res) v += ld(p.res, p.res_ld);
+  }
+  st(p.out, p.out_ld, v);
+}
 
 // FULLN: every wave of every workgroup has all its TN column tiles live (Npad % (64*TN) == 0), so
 // the MFMA block is branch-free.  (With the scalar branches of the ragged variant hipcc shuffles
@@ -99,46 +149,13 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
   const int li = lane & 31, lh = lane >> 5;
 
-  // XCD-aware block remap (bijective): consecutive ids on one XCD share A rows / the weight panel
-  const int nwg = gridDim.x;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  // phases interleave under one M tile index so that every XCD's contiguous id range holds all
-  // phases (their K lengths differ up to 2.25x: 9/6/6/4 taps for 5x5 stride 2)
-  const int ks = wg % p.ksplit;  // K split fastest: the splits of a tile share its A rows in L2
-  wg /= p.ksplit;
-  const int nt = wg % p.NT;
-  const int kq = wg / p.NT;
-  // Rotate the phase order from one M tile to the next.  Phase durations differ (9/6/6/4 taps)
-  // and the hardware deals consecutive workgroups round-robin over its shader engines / CUs:
-  // with a fixed period-4 order one engine would receive only 9-tap workgroups and pace all the
-  // others (measured: 1.2 instead of 1.9 resident waves per SIMD).
-  int phase = 0, mt = kq;
-  if (p.nphase == 4) {
-    if (p.pgroup > 0) {
-      // phases sorted by tap count inside groups of `pgroup` M tiles: an XCD's 64 slots run a round of
-      // 9-tap workgroups, then the 6-tap ones, then the 4-tap ones -- homogeneous rounds, short tail
-      // (all-equal neighbours also avoid the period-4 pattern described above)
-      const int span = 4 * p.pgroup;
-      const int grp = kq / span, loc = kq - grp * span;
-      const int rank = loc / p.pgroup;
-      phase = (p.porder >> (2 * rank)) & 3;
-      mt = grp * p.pgroup + (loc - rank * p.pgroup);
-    } else {
-      phase = (kq + (kq >> 2) + (kq >> 4) + (kq >> 6) + (kq >> 8)) & 3;
-      mt = kq / p.nphase;
-    }
-  }
-  const int Hq = p.Hq[phase], Wq = p.Wq[phase];
-  const int P = p.B * Hq * Wq;
-  const int m0 = mt * BM, n0 = nt * BN;
-  if (m0 >= P) return;
-  const int sph = (p.nphase > 1) ? p.stride : 1;  // output step between rows of this phase
-  const int py = (p.nphase > 1) ? phase / p.stride : 0;
-  const int px = (p.nphase > 1) ? phase % p.stride : 0;
+  // consecutive ids on one XCD share A rows / the weight panel
+  const ConvTile tile = conv_tile(p, xcd_contiguous(blockIdx.x, gridDim.x));
+  const int ks = tile.ks, nt = tile.nt, phase = tile.phase;
+  const PhaseView pv(p, phase);
+  const int P = pv.P;
+  const int m0 = tile.mt * BM, n0 = nt * BN;
+  if (m0 >= P) return;  // past a phase's last tile, padding tiles of a phase-sorted group included
 
   // ---- per-thread A row slots -------------------------------------------------------------
   const int a_c4 = (tid & 3) * 4;
@@ -148,19 +165,10 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
   for (int j = 0; j < APASS; ++j) {
     const int prow = m0 + (tid >> 2) + 64 * j;
     a_ok[j] = prow < P;
-    const int pr = a_ok[j] ? prow : 0;
-    const int b = fdiv(pr, p.dHW[phase]);
-    const int rem = pr - b * Hq * Wq;
-    const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
-    const int oy = i * sph + py, ox = jj * sph + px;
-    a_base[j] = b * p.Hi * p.Wi;
-    if (p.transposed) {
-      a_hy[j] = oy + p.pad;
-      a_wx[j] = ox + p.pad;
-    } else {
-      a_hy[j] = oy * p.stride - p.pad;
-      a_wx[j] = ox * p.stride - p.pad;
-    }
+    const GatherOrigin g = gather_origin(p, pv, a_ok[j] ? prow : 0);
+    a_base[j] = g.base;
+    a_hy[j] = g.hy;
+    a_wx[j] = g.wx;
   }
 
   f32x16 acc[TM][TN];
@@ -589,15 +597,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
       for (int it = 0; it < 4; ++it) {
         const int prow = m0 + wm0 + a * 32 + it * 8 + r8;
         rok[it] = prow < P;
-        const int pr = rok[it] ? prow : 0;
-        if (p.nphase > 1) {
-          const int bb = fdiv(pr, p.dHW[phase]);
-          const int rem = pr - bb * Hq * Wq;
-          const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
-          opix[it] = ((long)bb * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
-        } else {
-          opix[it] = pr;
-        }
+        opix[it] = pv.out_pixel(rok[it] ? prow : 0);
       }
       float* stg = smem + 64 * LDX + wave * 1024;
 #pragma unroll
@@ -636,13 +636,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
       for (int r = 0; r < 16; ++r) {
         const int prow = m0 + wm0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         if (prow >= P) continue;
-        long opix = prow;
-        if (p.nphase > 1) {
-          const int b = fdiv(prow, p.dHW[phase]);
-          const int rem = prow - b * Hq * Wq;
-          const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
-          opix = ((long)b * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
-        }
+        const long opix = pv.out_pixel(prow);
 #pragma unroll
         for (int b = 0; b < TN; ++b) {
           const int col = n0 + wn0 + b * 32 + li;
@@ -676,46 +670,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
           const int rr = it * 8 + r8;
           const int prow = m0 + wm0 + a * 32 + rr;
           if (prow >= P) continue;
-          long opix;
-          if (p.nphase > 1) {
-            const int bb = fdiv(prow, p.dHW[phase]);
-            const int rem = prow - bb * Hq * Wq;
-            const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
-            opix = ((long)bb * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
-          } else {
-            opix = prow;
-          }
-          f32x4 v = *reinterpret_cast<const f32x4*>(&stg[rr * 32 + c4]) + bias4;
-          if (epi == LIC_EPI_LEAKY) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.0f ? v[e] : v[e] * p.slope;
-            if (p.res)
-              *reinterpret_cast<f32x4*>(p.out2 + opix * p.out2_ld + col) =
-                  v + *reinterpret_cast<const f32x4*>(p.res + opix * p.res_ld + col);
-          } else {
-            if (epi == LIC_EPI_MUL_LEAKY_MASK) {
-              const f32x4 m = *reinterpret_cast<const f32x4*>(p.aux + opix * p.aux_ld + col);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) v[e] = m[e] > 0.0f ? v[e] : v[e] * p.slope;
-            } else if (epi == LIC_EPI_GDN || epi == LIC_EPI_IGDN) {
-              if (p.out2) *reinterpret_cast<f32x4*>(p.out2 + opix * p.out2_ld + col) = v;
-              const f32x4 x = *reinterpret_cast<const f32x4*>(p.aux + opix * p.aux_ld + col);
-#pragma unroll
-              for (int e = 0; e < 4; ++e)  // v_rsq_f32 / v_sqrt_f32: 1 ulp, far inside the 1e-4 bar
-                v[e] = x[e] * ((epi == LIC_EPI_GDN) ? __builtin_amdgcn_rsqf(v[e]) : __builtin_amdgcn_sqrtf(v[e]));
-            } else if (epi == LIC_EPI_GDN_BWD || epi == LIC_EPI_IGDN_BWD) {
-              const f32x4 n = *reinterpret_cast<const f32x4*>(p.aux3 + opix * p.aux3_ld + col);
-              const f32x4 g = *reinterpret_cast<const f32x4*>(p.aux + opix * p.aux_ld + col);
-              const f32x4 x = *reinterpret_cast<const f32x4*>(p.aux2 + opix * p.aux2_ld + col);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const float f = (epi == LIC_EPI_GDN_BWD) ? __builtin_amdgcn_rsqf(n[e]) : __builtin_amdgcn_sqrtf(n[e]);
-                v[e] = g[e] * f + 2.0f * x[e] * v[e];
-              }
-            }
-            if (p.res) v += *reinterpret_cast<const f32x4*>(p.res + opix * p.res_ld + col);
-          }
-          *reinterpret_cast<f32x4*>(p.out + opix * p.out_ld + col) = v;
+          igemm_elementwise(p, epi, pv.out_pixel(prow), col,
+                            *reinterpret_cast<const f32x4*>(&stg[rr * 32 + c4]) + bias4);
         }
       }
   } else {
@@ -726,39 +682,14 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
         const int row = wm0 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
         const int prow = m0 + row;
         if (prow >= P) continue;
-        long opix;
-        if (p.nphase > 1) {
-          const int b = fdiv(prow, p.dHW[phase]);
-          const int rem = prow - b * Hq * Wq;
-          const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
-          opix = ((long)b * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
-        } else {
-          opix = prow;
-        }
+        const long opix = pv.out_pixel(prow);
 #pragma unroll
         for (int b = 0; b < TN; ++b) {
           const int col = n0 + wn0 + b * 32 + li;
           if (col >= p.Cout) continue;
           float v = acc[a][b][r];
           if (p.bias) v += p.bias[col];
-          if (epi == LIC_EPI_LEAKY) {
-            v = v > 0.0f ? v : v * p.slope;
-            if (p.res) p.out2[opix * p.out2_ld + col] = v + p.res[opix * p.res_ld + col];
-          } else {
-            if (epi == LIC_EPI_MUL_LEAKY_MASK) {
-              v = p.aux[opix * p.aux_ld + col] > 0.0f ? v : v * p.slope;
-            } else if (epi == LIC_EPI_GDN || epi == LIC_EPI_IGDN) {
-              if (p.out2) p.out2[opix * p.out2_ld + col] = v;
-              const float f = (epi == LIC_EPI_GDN) ? 1.0f / sqrtf(v) : sqrtf(v);
-              v = p.aux[opix * p.aux_ld + col] * f;
-            } else if (epi == LIC_EPI_GDN_BWD || epi == LIC_EPI_IGDN_BWD) {
-              const float n = p.aux3[opix * p.aux3_ld + col];
-              const float f = (epi == LIC_EPI_GDN_BWD) ? 1.0f / sqrtf(n) : sqrtf(n);
-              v = p.aux[opix * p.aux_ld + col] * f + 2.0f * p.aux2[opix * p.aux2_ld + col] * v;
-            }
-            if (p.res) v += p.res[opix * p.res_ld + col];
-          }
-          p.out[opix * p.out_ld + col] = v;
+          igemm_elementwise(p, epi, opix, col, v);
         }
       }
   }
@@ -1293,24 +1224,11 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
   const int li = lane & 31, lh = lane >> 5;
-  // XCD-aware bijective remap: the hardware deals workgroup ids round-robin over the 8 XCDs; give
-  // each XCD a contiguous range of K splits, so the (tile, tap) workgroups that stream the same
-  // pixel range share one L2 instead of pulling it through the fabric into all eight.
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, rr = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-  }
-  const int tiles = p.MTt * p.NTt;
-  const int tile = wg % tiles;
-  wg /= tiles;
-  const int tap = wg % p.ntaps, split = wg / p.ntaps;
-  const int mt = tile / p.NTt, nt = tile - mt * p.NTt;
-  const int m0 = mt * BMt, n0 = nt * BNt;
-  const int r = tap / p.kw, s = tap - r * p.kw;
-  const int c_begin = split * p.chunks_per_split;
-  const int c_end = min(p.nchunks, c_begin + p.chunks_per_split);
-  const int nloc = c_end - c_begin;
+  // each XCD gets a contiguous range of K splits, so the (tile, tap) workgroups that stream the same pixel
+  // range share one L2 instead of pulling it through the fabric into all eight
+  const WgradTile wt = wgrad_tile(p, xcd_contiguous(blockIdx.x, gridDim.x), BMt, BNt);
+  const int m0 = wt.m0, n0 = wt.n0, tap = wt.tap, split = wt.split;
+  const int c_begin = wt.c_begin, c_end = wt.c_end, nloc = c_end - c_begin;
 
   // live 32-wide sub-tiles of this wave (wave-uniform)
   int m_live = 0, n_live = 0;
@@ -1337,19 +1255,10 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   // chunk indices past the end are clamped to the last one (harmless duplicate loads)
   auto load_chunk = [&](int c) {
-    const long pk = (long)(c < c_end ? c : c_end - 1) * WG_BK + kr;
-    const bool inb = pk < p.Ps;
-    const long pix = inb ? pk : 0;
-    // gathered position of this pixel on the large grid (used by whichever operand is gathered)
-    const int b = fdiv((int)pix, p.dHW);
-    const int rem = (int)pix - b * p.Hs * p.Ws;
-    const int hs = fdiv(rem, p.dW), ws = rem - hs * p.Ws;
-    const int hl = hs * p.stride - p.pad + r, wl = ws * p.stride - p.pad + s;
-    const bool gok = inb && hl >= 0 && wl >= 0 && hl < p.Hl && wl < p.Wl;
-    const long gpix = ((long)b * p.Hl + hl) * p.Wl + wl;
+    const WgradPixel w = wgrad_pixel(p, (long)(c < c_end ? c : c_end - 1) * WG_BK + kr, wt.r, wt.s);
     auto load_op = [&](const WgOperand& op, int ch, f32x4& v, bool& okr) {
-      bool ok = op.gathered ? gok : inb;
-      const long px = op.gathered ? gpix : pix;
+      bool ok = op.gathered ? w.gok : w.inb;
+      const long px = op.gathered ? w.gpix : (long)w.pix;
       if (VEC) {
         ok = ok && ch < op.C;
         v = *reinterpret_cast<const f32x4*>(op.ptr + (ok ? px * op.ld + ch : 0L));
@@ -1474,21 +1383,10 @@ __global__ __launch_bounds__(256, (TM * TN >= 6 ? 2 : 1)) void wgrad_glds_kernel
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
   const int li = lane & 31, lh = lane >> 5;
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, rr = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-  }
-  const int tiles = p.MTt * p.NTt;
-  const int tile = wg % tiles;
-  wg /= tiles;
-  const int tap = wg % p.ntaps, split = wg / p.ntaps;
-  const int mt = tile / p.NTt, nt = tile - mt * p.NTt;
-  const int m0 = mt * BMt, n0 = nt * BNt;
-  const int r = tap / p.kw, s = tap - r * p.kw;
-  const int c_begin = split * p.chunks_per_split;
-  const int c_end = min(p.nchunks, c_begin + p.chunks_per_split);
-  const int nloc = c_end - c_begin;
+  // whole K splits per XCD (see wgrad_kernel)
+  const WgradTile wt = wgrad_tile(p, xcd_contiguous(blockIdx.x, gridDim.x), BMt, BNt);
+  const int m0 = wt.m0, n0 = wt.n0, tap = wt.tap, split = wt.split;
+  const int c_begin = wt.c_begin, c_end = wt.c_end, nloc = c_end - c_begin;
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -1498,37 +1396,27 @@ __global__ __launch_bounds__(256, (TM * TN >= 6 ? 2 : 1)) void wgrad_glds_kernel
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.0f;
 
-  typedef lic_gptr_t gptr_t;
-  typedef lic_lptr_t lptr_t;
   const int kr = tid >> 4, c16 = (tid & 15) * 4;
   // chunk indices past the end are clamped to the last one (harmless duplicate DMA into the idle buffer)
   auto issue = [&](int c, int buf) {
-    const long pk = (long)(c < c_end ? c : c_end - 1) * WG_BK + kr;
-    const bool inb = pk < p.Ps;
-    const long pix = inb ? pk : 0;
-    const int b = fdiv((int)pix, p.dHW);
-    const int rem = (int)pix - b * p.Hs * p.Ws;
-    const int hs = fdiv(rem, p.dW), ws = rem - hs * p.Ws;
-    const int hl = hs * p.stride - p.pad + r, wl = ws * p.stride - p.pad + s;
-    const bool gok = inb && hl >= 0 && wl >= 0 && hl < p.Hl && wl < p.Wl;
-    const long gpix = ((long)b * p.Hl + hl) * p.Wl + wl;
-    const float* rowp = (p.row.gathered ? gok : inb)
-                            ? p.row.ptr + (p.row.gathered ? gpix : pix) * p.row.ld + m0 + c16
+    const WgradPixel w = wgrad_pixel(p, (long)(c < c_end ? c : c_end - 1) * WG_BK + kr, wt.r, wt.s);
+    const float* rowp = (p.row.gathered ? w.gok : w.inb)
+                            ? p.row.ptr + (p.row.gathered ? w.gpix : (long)w.pix) * p.row.ld + m0 + c16
                             : nullptr;
-    const float* colp = (p.col.gathered ? gok : inb)
-                            ? p.col.ptr + (p.col.gathered ? gpix : pix) * p.col.ld + n0 + c16
+    const float* colp = (p.col.gathered ? w.gok : w.inb)
+                            ? p.col.ptr + (p.col.gathered ? w.gpix : (long)w.pix) * p.col.ld + n0 + c16
                             : nullptr;
 #pragma unroll
     for (int j = 0; j < TM; ++j) {
       const bool ok = rowp && (FULL || m0 + c16 + 64 * j < p.row.C);
-      __builtin_amdgcn_global_load_lds((gptr_t)(ok ? rowp + 64 * j : g_lic_zero16),
-                                       (lptr_t)&smem[buf][j][wave * 256], 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((lic_gptr_t)(ok ? rowp + 64 * j : g_lic_zero16),
+                                       (lic_lptr_t)&smem[buf][j][wave * 256], 16, 0, 0);
     }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const bool ok = colp && (FULL || n0 + c16 + 64 * j < p.col.C);
-      __builtin_amdgcn_global_load_lds((gptr_t)(ok ? colp + 64 * j : g_lic_zero16),
-                                       (lptr_t)&smem[buf][TM + j][wave * 256], 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((lic_gptr_t)(ok ? colp + 64 * j : g_lic_zero16),
+                                       (lic_lptr_t)&smem[buf][TM + j][wave * 256], 16, 0, 0);
     }
   };
   auto compute = [&](int buf) {

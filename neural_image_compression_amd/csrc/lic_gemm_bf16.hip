@@ -4,7 +4,7 @@
 // LDS-staged 16-byte epilogue) with 32-deep chunks.  A chunk is only TM*TN*2 MFMAs of 32 cycles per
 // wave -- shorter than a memory round trip -- so, as in the bf16 wgrad below, the DMA runs TWO
 // chunks ahead through a ring of three LDS buffers (counted `s_waitcnt vmcnt`, raw `s_barrier`).
-#include "lic_conv_plan.h"
+#include "lic_tile_map.h"
 #include "lic_epilogue_bf16.h"
 #include <algorithm>
 #include <type_traits>
@@ -14,8 +14,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int HB_BK = 32;  // bf16 elements per K chunk (64-byte rows, 2 MFMA K steps)
 
 __device__ __attribute__((aligned(16))) float g_lic_zero16h[4];  // DMA source of padding / tail lanes
-typedef const __attribute__((address_space(1))) void* lich_gptr_t;
-typedef __attribute__((address_space(3))) void* lich_lptr_t;
 
 struct IgemmHParams {
   const bf16_t* in;
@@ -110,39 +108,13 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
   const int wm0 = (wave / WGN) * WM, wn0 = (wave % WGN) * WN;
   const int li = lane & 31, lh = lane >> 5;
 
-  const int nwg = gridDim.x;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg >> 3, r = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int ksp = 0;
-  if (p.ksplit > 1) {  // the splits of a tile are neighbours in launch order (they share its activations in L2)
-    ksp = wg % p.ksplit;
-    wg /= p.ksplit;
-  }
-  const int nt = wg % p.NT;
-  const int kq = wg / p.NT;
-  int phase = 0, mt = kq;
-  if (p.nphase == 4) {
-    if (p.pgroup > 0) {  // phases sorted by tap count inside groups of M tiles (see lic_gemm.hip)
-      const int span = 4 * p.pgroup;
-      const int grp = kq / span, loc = kq - grp * span;
-      const int rank = loc / p.pgroup;
-      phase = (p.porder >> (2 * rank)) & 3;
-      mt = grp * p.pgroup + (loc - rank * p.pgroup);
-    } else {
-      phase = (kq + (kq >> 2) + (kq >> 4) + (kq >> 6) + (kq >> 8)) & 3;
-      mt = kq / p.nphase;
-    }
-  }
-  const int Hq = p.Hq[phase], Wq = p.Wq[phase];
-  const int P = p.B * Hq * Wq;
-  const int m0 = mt * BM, n0 = nt * BN;
-  if (m0 >= P) return;
-  const int sph = (p.nphase > 1) ? p.stride : 1;
-  const int py = (p.nphase > 1) ? phase / p.stride : 0;
-  const int px = (p.nphase > 1) ? phase % p.stride : 0;
+  // consecutive ids on one XCD share A rows / the weight panel
+  const ConvTile tile = conv_tile(p, xcd_contiguous(blockIdx.x, gridDim.x));
+  const int ksp = tile.ks, nt = tile.nt, phase = tile.phase;
+  const PhaseView pv(p, phase);
+  const int P = pv.P;
+  const int m0 = tile.mt * BM, n0 = nt * BN;
+  if (m0 >= P) return;  // past a phase's last tile, padding tiles of a phase-sorted group included
 
   // A tile image [BM][32] bf16, packed 64-byte rows: thread t of pass j owns row t/4 + 64j, 16-byte
   // slot t%4 = byte 16t + 4096j, the wave-linear order the DMA writes.  Rows r, r+4, r+8, r+12 of a
@@ -158,19 +130,10 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
   for (int j = 0; j < APASS; ++j) {
     const int prow = m0 + arow0 + 64 * j;
     a_ok[j] = prow < P;
-    const int pr = a_ok[j] ? prow : 0;
-    const int b = fdiv(pr, p.dHW[phase]);
-    const int rem = pr - b * Hq * Wq;
-    const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
-    const int oy = i * sph + py, ox = jj * sph + px;
-    a_base[j] = b * p.Hi * p.Wi;
-    if (p.transposed) {
-      a_hy[j] = oy + p.pad;
-      a_wx[j] = ox + p.pad;
-    } else {
-      a_hy[j] = oy * p.stride - p.pad;
-      a_wx[j] = ox * p.stride - p.pad;
-    }
+    const GatherOrigin g = gather_origin(p, pv, a_ok[j] ? prow : 0);
+    a_base[j] = g.base;
+    a_hy[j] = g.hy;
+    a_wx[j] = g.wx;
   }
 
   f32x16 acc[TM][TW];
@@ -249,7 +212,7 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
       if (cin_tail && ci_cur >= p.Cin) src = zsrc;  // (wave-uniform flag: Cin % 32 == 0 layers skip the compare)
       // (A image: 64-byte rows in row order; a wave's 64 lanes cover 16 consecutive rows = 1 KiB)
       bf16_t* da = (NWV == 8) ? dstA + 4096 * grp + 2048 * j + 512 * (wave & 3) : dstA + j * 2048 + wave * 512;
-      __builtin_amdgcn_global_load_lds((lich_gptr_t)src, (lich_lptr_t)da, 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((lic_gptr_t)src, (lic_lptr_t)da, 16, 0, 0);
     }
     bf16_t* dstB = dstA + BM * HB_BK;
 #pragma unroll
@@ -258,7 +221,7 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
       // the wrap is a multiple of 64 pieces) onto pieces that are loaded twice with the same bytes
       int wv = j * NWV + wave;
       if (wv * 64 >= 256 * TN) wv -= 4 * TN;
-      __builtin_amdgcn_global_load_lds((lich_gptr_t)(w_ptr + wv * 512 + lane * 8), (lich_lptr_t)(dstB + wv * 512), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((lic_gptr_t)(w_ptr + wv * 512 + lane * 8), (lic_lptr_t)(dstB + wv * 512), 16, 0, 0);
     }
   };
   // A step reads ALL its fragments first (TM*2 + TW*2 ds_read_b128), then issues the next chunk's DMAs -- ~40
@@ -398,13 +361,7 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
     // output tensors
     const int prow = m0 + wm0 + li;
     const bool rok = prow < P;
-    long opix = rok ? prow : 0;
-    if (p.nphase > 1) {
-      const int bb = fdiv((int)opix, p.dHW[phase]);
-      const int rem = (int)opix - bb * Hq * Wq;
-      const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
-      opix = ((long)bb * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
-    }
+    const long opix = pv.out_pixel(rok ? prow : 0);
     // 1. x = conv + bias -> bf16, x^2 -> bf16: the pool's operand
     unsigned sqpk[TW][8];
 #pragma unroll
@@ -471,13 +428,7 @@ __global__ __launch_bounds__(64 * NWV) void igemm_bf16_kernel(const IgemmHParams
         const int rr = it * 16 + r16;
         const int prow = m0 + wm0 + a * 32 + rr;
         if (prow >= P) continue;
-        long opix = prow;
-        if (p.nphase > 1) {
-          const int bb = fdiv(prow, p.dHW[phase]);
-          const int rem = prow - bb * Hq * Wq;
-          const int i = fdiv(rem, p.dW[phase]), jj = rem - i * Wq;
-          opix = ((long)bb * p.Ho + i * sph + py) * p.Wo + jj * sph + px;
-        }
+        const long opix = pv.out_pixel(prow);
         float v[8];
         {
           const f32x4 v0 = *reinterpret_cast<const f32x4*>(&stg[rr * 32 + c8]);
@@ -986,22 +937,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradHParams p
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
   const int li = lane & 31, lh = lane >> 5;
-  // XCD-aware bijective remap: whole K splits per XCD (see wgrad_kernel in lic_gemm.hip)
-  int wg = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, rr = nwg & 7, xcd = wg & 7, idx = wg >> 3;
-    wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
-  }
-  const int tiles = p.MTt * p.NTt;
-  const int tile = wg % tiles;
-  wg /= tiles;
-  const int tap = wg % p.ntaps, split = wg / p.ntaps;
-  const int mt = tile / p.NTt, nt = tile - mt * p.NTt;
-  const int m0 = mt * BMt, n0 = nt * BNt;
-  const int r = tap / p.kw, s = tap - r * p.kw;
-  const int c_begin = split * p.chunks_per_split;
-  const int c_end = min(p.nchunks, c_begin + p.chunks_per_split);
-  const int nloc = c_end - c_begin;
+  // whole K splits per XCD (see wgrad_kernel in lic_gemm.hip)
+  const WgradTile wt = wgrad_tile(p, xcd_contiguous(blockIdx.x, gridDim.x), BMt, BNt);
+  const int m0 = wt.m0, n0 = wt.n0, tap = wt.tap, split = wt.split;
+  const int c_begin = wt.c_begin, c_end = wt.c_end, nloc = c_end - c_begin;
 
   f32x16 acc[TM][TN];
 #pragma unroll
@@ -1020,23 +959,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradHParams p
     const int cc = c < c_end ? c : c_end - 1;  // past the end: harmless duplicate DMA into the idle buffer
 #pragma unroll
     for (int j = 0; j < NPASS; ++j) {
-      const long pk = (long)cc * BK + kr + 32 * j;
-      const bool inb = pk < p.Ps;
-      const int pix = inb ? (int)pk : 0;
-      const int b = fdiv(pix, p.dHW);
-      const int rem = pix - b * p.Hs * p.Ws;
-      const int hs = fdiv(rem, p.dW), ws = rem - hs * p.Ws;
-      const int hl = hs * p.stride - p.pad + r, wl = ws * p.stride - p.pad + s;
-      const bool gok = inb && hl >= 0 && wl >= 0 && hl < p.Hl && wl < p.Wl;
-      const long gpix = ((long)b * p.Hl + hl) * p.Wl + wl;
-      const bool rok = p.row.gathered ? gok : inb, cok = p.col.gathered ? gok : inb;
-      const long rpx = (p.row.gathered ? gpix : (long)pix), cpx = (p.col.gathered ? gpix : (long)pix);
+      const WgradPixel w = wgrad_pixel(p, (long)cc * BK + kr + 32 * j, wt.r, wt.s);
+      const bool rok = p.row.gathered ? w.gok : w.inb, cok = p.col.gathered ? w.gok : w.inb;
+      const long rpx = p.row.gathered ? w.gpix : (long)w.pix, cpx = p.col.gathered ? w.gpix : (long)w.pix;
 #pragma unroll
       for (int t = 0; t < TM; ++t) {
         const int ch = m0 + 64 * t + c8;
         const bool ok = rok && ch < p.row.C;
         const bf16_t* src = ok ? p.row.ptr + rpx * p.row.ld + ch : zsrc;
-        __builtin_amdgcn_global_load_lds((lich_gptr_t)src, (lich_lptr_t)&smem[buf][t][j * 2048 + wave * 512], 16, 0,
+        __builtin_amdgcn_global_load_lds((lic_gptr_t)src, (lic_lptr_t)&smem[buf][t][j * 2048 + wave * 512], 16, 0,
                                          0);
       }
 #pragma unroll
@@ -1044,7 +975,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradHParams p
         const int ch = n0 + 64 * t + c8;
         const bool ok = cok && ch < p.col.C;
         const bf16_t* src = ok ? p.col.ptr + cpx * p.col.ld + ch : zsrc;
-        __builtin_amdgcn_global_load_lds((lich_gptr_t)src, (lich_lptr_t)&smem[buf][TM + t][j * 2048 + wave * 512],
+        __builtin_amdgcn_global_load_lds((lic_gptr_t)src, (lic_lptr_t)&smem[buf][TM + t][j * 2048 + wave * 512],
                                          16, 0, 0);
       }
     }

@@ -93,11 +93,8 @@ __global__ __launch_bounds__(256, 1) void halo_conv_bf16_kernel(const IgemmHPara
   HALO_STAMP(0);
 
   const int G = gridDim.x, ntiles = p.MT;
-  int tile = blockIdx.x;
-  {  // XCD-aware bijective remap: an XCD's workgroups walk neighbouring tiles (shared halo rows / columns in its L2)
-    const int q = G >> 3, r = G & 7, xcd = tile & 7, idx = tile >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  // an XCD's workgroups walk neighbouring tiles (shared halo rows / columns in its L2)
+  int tile = xcd_contiguous(blockIdx.x, G);
 
   // ---- halo DMA: piece (4 j + wave) of a buffer = LDS bytes [1024 (4 j + wave), +1024); lane -> 16-byte slot
   // n = 64 (4 j + wave) + lane = (plane-linear pixel n >> 2, physical octet n & 3).  Tile-independent per lane:
@@ -162,7 +159,7 @@ __global__ __launch_bounds__(256, 1) void halo_conv_bf16_kernel(const IgemmHPara
   // idle buffer, which keeps the vmcnt arithmetic exact
   auto dma_piece = [&](int j, __amdgpu_buffer_rsrc_t rs, int soff, unsigned vm, int buf) {
     const unsigned off = ((vm >> j) & 1u) ? rel[j] : OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lich_lptr_t)(smem + buf * BUFB + (j * 4 + wave) * 1024), 16, (int)off, soff,
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lic_lptr_t)(smem + buf * BUFB + (j * 4 + wave) * 1024), 16, (int)off, soff,
                                              0, 0);
   };
 
@@ -171,7 +168,7 @@ __global__ __launch_bounds__(256, 1) void halo_conv_bf16_kernel(const IgemmHPara
   // immediate offset (2 a + r) * row bytes.
   unsigned abase[2][5][2];
   {
-    const unsigned s0 = (unsigned)(size_t)(lich_lptr_t)smem;
+    const unsigned s0 = (unsigned)(size_t)(lic_lptr_t)smem;
 #pragma unroll
     for (int ps = 0; ps < 5; ++ps) {
       const int pl = ps >= 3 ? 1 : 0, sh = pl ? ps - 3 : ps;

@@ -79,11 +79,7 @@ __global__ __launch_bounds__(256, 1) void halo_convt_bf16_kernel(const IgemmHPar
   const int li = lane & 31, lh = lane >> 5;
 
   const int G = gridDim.x, ntiles = p.MT;
-  int tile = blockIdx.x;
-  {
-    const int q = G >> 3, r = G & 7, xcd = tile & 7, idx = tile >> 3;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int tile = xcd_contiguous(blockIdx.x, G);  // neighbouring tiles per XCD, as in halo_conv_bf16_kernel
 
   // ---- halo DMA (buffer_load ... lds on a per-tile descriptor, out-of-image lanes zero-filled by the range check)
   unsigned rel[NPIECE];
@@ -134,7 +130,7 @@ __global__ __launch_bounds__(256, 1) void halo_convt_bf16_kernel(const IgemmHPar
   };
   auto dma_piece = [&](int j, __amdgpu_buffer_rsrc_t rs, int soff, unsigned vm, int buf) {
     const unsigned off = ((vm >> j) & 1u) ? rel[j] : OOB;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lich_lptr_t)(smem + buf * BUFB + (j * 4 + wave) * 1024), 16, (int)off, soff,
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lic_lptr_t)(smem + buf * BUFB + (j * 4 + wave) * 1024), 16, (int)off, soff,
                                              0, 0);
   };
 
@@ -142,7 +138,7 @@ __global__ __launch_bounds__(256, 1) void halo_convt_bf16_kernel(const IgemmHPar
   // (2 ks + lh) ^ ((column >> 2) & 3).  abase[buf][shoff][ks]; (a + dyoff) * ROWB is the immediate offset.
   unsigned abase[2][3][2];
   {
-    const unsigned s0 = (unsigned)(size_t)(lich_lptr_t)smem;
+    const unsigned s0 = (unsigned)(size_t)(lic_lptr_t)smem;
 #pragma unroll
     for (int sh = 0; sh < 3; ++sh) {
       const int hc = li + sh;
