@@ -435,6 +435,25 @@ int lic_rans_decode_step(const uint8_t* streams, const int64_t* stream_off, cons
                          float* ypad, int64_t pixels, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2d -- the same step for "rANS-64 x G" streams (lic_codec.h: round r of every step belongs to
+ *   sub-stream r % G of its image): B * G workgroups of one wave, wave (b, g) decodes rounds g, g + G, ... of the
+ *   step from block b * G + g.  The arguments of lic_rans_decode_step, with
+ *     stream_off    B*G + 1 entries, stream_bytes B*G, esc_off B*G + 1: block b * G + g is sub-stream g of image b
+ *     state         [B*G][LIC_RANS_STATE_WORDS], one block per sub-stream, seeded and checked as above
+ *     tables, center, dest, ypad: per IMAGE, unchanged; round r's rows start at dword (b * n*M + 64 r) * (2W+2)
+ *   A wave whose group has no round in this step (fewer rounds than G) leaves its state block bit for bit as it
+ *   found it.  Error words are per block: a block in error decodes its later symbols as the table centre, the other
+ *   blocks of the image carry on.  G = 1 is lic_rans_decode_step.  G outside 1..LIC_RANS_MAX_GROUPS:
+ *   LIC_ERR_INVALID; B * G <= 65535 (LIC_ERR_UNSUPPORTED above); the other limits as above.
+ * ------------------------------------------------------------------------------------------ */
+#define LIC_RANS_MAX_GROUPS 8
+int lic_rans_decode_step_groups(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
+                                const uint32_t* escapes, const int64_t* esc_off, uint32_t* state,
+                                const uint32_t* tables, const int32_t* center, int32_t B, int32_t G, int32_t n,
+                                int32_t M, int32_t W, const int64_t* dest, float* ypad, int64_t pixels,
+                                lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).2 -- the device encoder of the same streams: byte for byte what the host encoder of lic_codec.h
  *   writes, from the tables where lic_gmm_cdf_tables left them, so no table ever travels to the host.  Two
  *   launches per batch on one stream, lic_rans_encode_pick then lic_rans_encode.  (This lic_rans_encode is the
@@ -484,6 +503,31 @@ int lic_rans_encode_pick(const uint32_t* tables, const int32_t* center, const in
 int lic_rans_encode(const uint32_t* sf, const uint32_t* exc, const int64_t* step_len, int64_t nsteps, int32_t B,
                     int64_t nsym, uint8_t* words, int64_t slot, uint32_t* esc_out, uint32_t* state,
                     lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2d -- lic_rans_encode for "rANS-64 x G" streams: B * G workgroups of one wave, wave (b, g) codes the
+ *   rounds of image b whose index inside their step is g, g + G, ... into block b * G + g.  lic_rans_encode_pick is
+ *   the same launch as before: sf and exc are per image, in coding order, and every group reads them there.
+ *     step_len      [nsteps] the IMAGE's step lengths, as for lic_rans_encode; the kernel derives each group's rounds
+ *     words         [B*G][slot] bytes out, slot a multiple of 4; block's words END at the end of its slot
+ *     esc_out       [B*G][esc_cap] uint32 out: the block's escape list in the order of its own symbols
+ *     state         [B*G][LIC_RANS_STATE_WORDS]: final states, word count, escape count, error word per block (read
+ *                   at entry, so the caller zeroes it).  lic_rans_encode_pick strides its `state` by one block per
+ *                   IMAGE, so for G > 1 it is given a [B] block buffer of its own; an image is in error if its
+ *                   pick block or any of its G blocks here is.
+ *   Sizes.  Sub-stream g of an image holds  n_g = sum over steps t of |{k < step_len[t] : (k / 64) % G == g}|
+ *   symbols.  A symbol costs at most one 16-bit word (lic_codec.h) and at most one escape, so
+ *     slot >= 2 * max_g n_g (rounded up to 4)  and  esc_cap >= max_g n_g
+ *   can never run out; n_g <= nsym, so slot = 2 * nsym (rounded up to 4) and esc_cap = nsym always serve.  The
+ *   entry cannot see the step lengths, so it does not check these two sizes beyond slot >= 4, slot % 4 == 0 and
+ *   esc_cap >= 1; the kernel compares the word cursor with the slot's first word and the escape cursor with esc_cap
+ *   before EVERY store: a block whose slot or list is too small stores nothing outside it and reports
+ *   LIC_RANS_ERR_RANGE.  Bad step lengths: all G blocks of the image report, as lic_rans_encode's one does.
+ *   G = 1 with esc_cap = nsym is lic_rans_encode.  G outside 1..LIC_RANS_MAX_GROUPS: LIC_ERR_INVALID; B * G <= 65535.
+ * ------------------------------------------------------------------------------------------ */
+int lic_rans_encode_groups(const uint32_t* sf, const uint32_t* exc, const int64_t* step_len, int64_t nsteps,
+                           int32_t B, int32_t G, int64_t nsym, uint8_t* words, int64_t slot, uint32_t* esc_out,
+                           int64_t esc_cap, uint32_t* state, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).1 -- evaluation metric on the device.

@@ -68,6 +68,14 @@ double lic_rc_ideal_bits(const uint32_t* tables, const int32_t* table_of, int32_
  *   a separate list of uint32, in symbol order, 32 bits each (an in-stream escape would break the lock step).
  * lic_rans_decode returns LIC_CODEC_ERR_CORRUPT for a truncated stream, a word or escape cursor past the end,
  * trailing unused words or escapes, and final states other than 2^16.
+ *
+ * "rANS-64 x G" (G = 1..8; codec.rans_deal is the definition): one image's symbols dealt to G independent rANS-64
+ *   streams so that G waves can code them.  The symbols keep their coding order and their rounds; round r of EVERY
+ *   step belongs to sub-stream r % G.  Sub-stream g is an ordinary rANS-64 stream over the symbols dealt to it, in
+ *   their original order, with step lengths step_len_g[t] = the symbols of step t in rounds = g (mod G): its own 64
+ *   states, words and escape list.  A step with fewer rounds than G gives some sub-streams a zero-length step; an
+ *   image with fewer rounds than G gives some no symbol at all (256 bytes of states).  G = 1 is rANS-64.  The
+ *   functions below code one sub-stream at a time: the composition needs no symbol of its own.
  * ------------------------------------------------------------------------------------------ */
 /* upper bound of the stream of n symbols in bytes (256 + 2 n); the escape list has at most n entries */
 size_t lic_rans_bound(int64_t n);

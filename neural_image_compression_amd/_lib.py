@@ -74,7 +74,7 @@ class AdamJob(C.Structure):
     _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", _i64), ("block0", _i32), ("nblocks", _i32)]
 
 
-RANS_LANES, RANS_STATE_WORDS = 64, 67
+RANS_LANES, RANS_STATE_WORDS, RANS_MAX_GROUPS = 64, 67, 8
 
 WINDOW_ZERO, WINDOW_REPLICATE, WINDOW_REFLECT = range(3)
 WINDOW_FLIP = 1
@@ -164,6 +164,8 @@ SIGNATURES = {
     "lic_rans_decode_step": (C.c_int, [_vp] * 8 + [_i32] * 4 + [_vp, _vp, _i64, _vp]),
     "lic_rans_encode_pick": (C.c_int, [_vp] * 4 + [_i32, _i64, _i32, _i32] + [_vp] * 4),
     "lic_rans_encode": (C.c_int, [_vp] * 3 + [_i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "lic_rans_decode_step_groups": (C.c_int, [_vp] * 8 + [_i32] * 5 + [_vp, _vp, _i64, _vp]),
+    "lic_rans_encode_groups": (C.c_int, [_vp] * 3 + [_i64, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "lic_msssim_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "lic_msssim": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _sz,
                              _vp]),

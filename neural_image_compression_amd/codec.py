@@ -20,6 +20,11 @@ instead: its decoder is a device kernel (`lic_rans_decode_step`), so the decode 
 container of that coder is `pack_bitstream_rans` (magic LICBITS2).  The range coder stays the default and codes z.
 With `encoder="device"` that coder's encoder runs on the device as well (`lic_rans_encode_pick` + `lic_rans_encode`):
 the same bytes, and no table is copied to the host.
+
+`ContextCodec(..., coder="rans", groups=G)` deals every image's rounds to G independent rANS-64 sub-streams
+(`rans_deal`: round r of a step goes to sub-stream r % G), so G waves per image decode and encode them
+(`lic_rans_decode_step_groups`, `lic_rans_encode_groups`); each sub-stream costs its 256 bytes of states.  G = 1,
+the default, is the format above; the container of G > 1 is `pack_bitstream_grouped` (magic LICBITS3).
 """
 from __future__ import annotations
 
@@ -119,6 +124,7 @@ RANS_LANES = 64
 CODERS = ("range", "rans")
 ENCODERS = ("host", "device")
 RANS_MAX_W = 64                                  # widest window lic_rans_decode_step / lic_rans_encode_pick take
+RANS_MAX_GROUPS = 8                              # sub-streams per image of the "rANS-64 x G" format
 
 
 def rans_encode(tables: np.ndarray, idx: np.ndarray, step_len) -> tuple:
@@ -154,6 +160,60 @@ def rans_decode(data: bytes, esc: bytes, tables: np.ndarray, step_len) -> np.nda
                                   S, n, _p(steps, C.c_int64), steps.size, _p(out, C.c_int32))
     if rc != 0:
         raise CodecError(f"lic_rans_decode failed with status {rc}")
+    return out
+
+
+def _groups(G) -> int:
+    """G as an int in 1..RANS_MAX_GROUPS, or CodecError"""
+    if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or not 1 <= int(G) <= RANS_MAX_GROUPS:
+        raise CodecError(f"groups = {G!r}: expected an integer from 1 to {RANS_MAX_GROUPS}")
+    return int(G)
+
+
+def rans_deal(step_len, G: int):
+    """The "rANS-64 x G" format (lic_codec.h): symbol k of a step lies in round k // 64 of that step, and round r of
+    every step belongs to sub-stream r % G.  step_len: symbols per step of one image, in coding order.
+    -> [(positions, step_len_g) for g in range(G)]: the positions (int64, ascending) of sub-stream g's symbols in the
+    image's coding order, and how many of them every step contributes (int64, one entry per step, zeros included)."""
+    G = _groups(G)
+    steps = np.ascontiguousarray(step_len, np.int64).ravel()
+    if (steps < 0).any():
+        raise CodecError("negative step length")
+    pos = np.arange(int(steps.sum()), dtype=np.int64)
+    step_of = np.repeat(np.arange(steps.size, dtype=np.int64), steps)
+    in_step = pos - np.repeat(np.cumsum(steps) - steps, steps)
+    group_of = (in_step // RANS_LANES) % G
+    counts = np.bincount(step_of * G + group_of, minlength=steps.size * G).reshape(steps.size, G).astype(np.int64)
+    return [(pos[group_of == g], np.ascontiguousarray(counts[:, g])) for g in range(G)]
+
+
+def rans_group_sizes(step_len, G: int) -> np.ndarray:
+    """[G] int64: the symbols of every sub-stream of `rans_deal(step_len, G)`, from the step lengths alone.  Of a
+    step's R rounds, (R + G - 1 - g) // G are group g's; all are full but the step's last, round R - 1."""
+    G = _groups(G)
+    n = np.ascontiguousarray(step_len, np.int64).ravel()[:, None]
+    R = (n + RANS_LANES - 1) // RANS_LANES
+    g = np.arange(G, dtype=np.int64)[None, :]
+    short = np.where((n % RANS_LANES != 0) & ((R - 1) % G == g), RANS_LANES - n % RANS_LANES, 0)
+    return (RANS_LANES * ((R + G - 1 - g) // G) - short).sum(0)
+
+
+def rans_encode_grouped(tables: np.ndarray, idx: np.ndarray, step_len, G: int) -> tuple:
+    """`rans_encode` per sub-stream of `rans_deal` -> ([G stream bytes], [G escape-list bytes])"""
+    tables = np.ascontiguousarray(tables, np.uint32)
+    idx = np.ascontiguousarray(idx, np.int32).ravel()
+    pairs = [rans_encode(tables[pos], idx[pos], steps_g) for pos, steps_g in rans_deal(step_len, G)]
+    return [p[0] for p in pairs], [p[1] for p in pairs]
+
+
+def rans_decode_grouped(streams, escs, tables: np.ndarray, step_len) -> np.ndarray:
+    """the inverse of `rans_encode_grouped` for known tables; G = len(streams)"""
+    if len(streams) != len(escs):
+        raise CodecError("one escape list per sub-stream expected")
+    tables = np.ascontiguousarray(tables, np.uint32)
+    out = np.empty(int(np.asarray(step_len, np.int64).sum()), np.int32)
+    for (pos, steps_g), data, esc in zip(rans_deal(step_len, len(streams)), streams, escs):
+        out[pos] = rans_decode(data, esc, tables[pos], steps_g)
     return out
 
 
@@ -303,10 +363,14 @@ class ContextCodec:
     `encoder`: where `compress` codes the y streams.  "host" (the default) gathers the tables into wavefront order,
     copies them to the host and runs the C++ encoder, one image after the other; "device" (coder "rans" only) runs
     `lic_rans_encode_pick` + `lic_rans_encode` on the tables where they were built and copies back state blocks,
-    streams and escape lists only.  Both write the same bytes."""
+    streams and escape lists only.  Both write the same bytes.
+
+    `groups`: sub-streams per image of the "rans" coder (1 to 8, `rans_deal`).  1 (the default) is the rANS-64
+    format; with G > 1 `strings["groups"]` is G and `strings["y"]`, `strings["y_esc"]` hold B * G entries,
+    image-major (entry b * G + g), coded and decoded by G waves per image.  `decompress` reads G from the strings."""
 
     def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range",
-                 encoder: str = "host"):
+                 encoder: str = "host", groups: int = 1):
         if coder not in CODERS:
             raise CodecError(f"unknown coder {coder!r}: expected one of {CODERS}")
         if encoder not in ENCODERS:
@@ -321,6 +385,9 @@ class ContextCodec:
                              "(the limit of its device kernels); the range coder has no such limit")
         self.model, self.z_lo, self.z_S, self.y_W, self.coder = model, int(z_lo), int(z_S), int(y_W), coder
         self.encoder = encoder
+        self.groups = _groups(groups)
+        if self.groups > 1 and coder != "rans":
+            raise CodecError(f"groups={self.groups} needs coder='rans': the {coder!r} coder has one stream per image")
         mc = model.context_model.masked
         k = mc.kernel_size[0]
         self.taps = [(r, s) for r in range(k) for s in range(k) if (mc._tap_mask >> (r * k + s)) & 1]
@@ -406,6 +473,8 @@ class ContextCodec:
         order = np.concatenate([ii * w + jj for ii, jj in steps])
         step_len = [len(ii) * M for ii, _ in steps]
         strings = {"z": z_bytes}
+        if self.groups > 1:
+            strings["groups"] = self.groups
         if self.encoder == "device":
             y_streams, y_esc = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, M)
             strings.update(coder="rans", y_esc=y_esc)
@@ -414,8 +483,8 @@ class ContextCodec:
         idx = (y_sym - center + self.y_W).view(B, h * w, M)[:, perm].cpu().numpy().reshape(B, h * w * M)
         tabs = tables.view(B, h * w, M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * M, -1)
         if self.coder == "rans":
-            pairs = [rans_encode(tabs[b], idx[b], step_len) for b in range(B)]
-            y_streams, y_esc = [p[0] for p in pairs], [p[1] for p in pairs]
+            pairs = [rans_encode_grouped(tabs[b], idx[b], step_len, self.groups) for b in range(B)]
+            y_streams, y_esc = [s for p in pairs for s in p[0]], [e for p in pairs for e in p[1]]
             strings.update(coder="rans", y_esc=y_esc)
         else:
             y_streams, y_esc = [rc_encode(tabs[b], idx[b]) for b in range(B)], []
@@ -440,38 +509,51 @@ class ContextCodec:
     def _encode_y_device(self, tables, center, y_sym, order, step_len, B: int, P: int, M: int):
         """The y streams of the "rans" coder without the host encoder: `lic_rans_encode_pick` turns tables (raster
         order, where `_params_at` left them), centres and symbols into one start|freq word and one escape word per
-        symbol in wavefront order, `lic_rans_encode` codes them, one wave per image.  Order and step lengths go up
-        once; the state blocks (final states, word count, escape count, error word) come back once, then exactly the
-        used bytes of every slot and escape list.  -> ([stream bytes per image], [escape-list bytes per image])"""
+        symbol in wavefront order, `lic_rans_encode` (`lic_rans_encode_groups` for G > 1) codes them, one wave per image
+        and group.  Order and step
+        lengths go up once; the state blocks (final states, word count, escape count, error word) come back once,
+        then exactly the used bytes of every slot and escape list.
+        -> ([stream bytes per image and group, image-major], [escape-list bytes likewise])"""
         dev = tables.device
-        nsym = P * M
-        slot = (4 * RANS_LANES + 2 * nsym + 3) // 4 * 4                         # lic_rans_bound, whole dwords
+        nsym, G = P * M, self.groups
+        # one word and one escape per symbol at the most (lic.h): the fullest sub-stream sets both sizes
+        cap = nsym if G == 1 else max(int(rans_group_sizes(step_len, G).max()), 1)
+        slot = (4 * RANS_LANES + 2 * cap + 3) // 4 * 4                          # lic_rans_bound, whole dwords
         d_order = torch.from_numpy(np.ascontiguousarray(order, np.int64)).to(dev)
         d_steps = torch.from_numpy(np.asarray(step_len, np.int64)).to(dev)
         sf = torch.empty((B, nsym), device=dev, dtype=torch.int32)
-        exc, esc = torch.empty_like(sf), torch.empty_like(sf)
-        words = torch.empty((B, slot), device=dev, dtype=torch.uint8)
-        state = torch.zeros((B, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
+        exc = torch.empty_like(sf)
+        esc = torch.empty((B * G, cap), device=dev, dtype=torch.int32)
+        words = torch.empty((B * G, slot), device=dev, dtype=torch.uint8)
+        state = torch.zeros((B * G, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
+        # pick strides its blocks by image: with one block per image it shares the encoder's
+        picked = state if G == 1 else torch.zeros((B, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
         y_sym = y_sym.contiguous()
         lib = L.load()
         L.check(lib.lic_rans_encode_pick(F_._ptr(tables), F_._ptr(center), F_._ptr(y_sym), F_._ptr(d_order), B, P, M,
-                                         self.y_W, F_._ptr(sf), F_._ptr(exc), F_._ptr(state), F_._stream()),
+                                         self.y_W, F_._ptr(sf), F_._ptr(exc), F_._ptr(picked), F_._stream()),
                 "lic_rans_encode_pick")
-        L.check(lib.lic_rans_encode(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), len(step_len), B, nsym,
-                                    F_._ptr(words), slot, F_._ptr(esc), F_._ptr(state), F_._stream()),
-                "lic_rans_encode")
+        if G == 1:
+            L.check(lib.lic_rans_encode(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), len(step_len), B, nsym,
+                                        F_._ptr(words), slot, F_._ptr(esc), F_._ptr(state), F_._stream()),
+                    "lic_rans_encode")
+        else:
+            L.check(lib.lic_rans_encode_groups(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), len(step_len), B, G, nsym,
+                                               F_._ptr(words), slot, F_._ptr(esc), cap, F_._ptr(state), F_._stream()),
+                    "lic_rans_encode_groups")
+            state[::G, RANS_LANES + 2] |= picked[:, RANS_LANES + 2]
         st = state.cpu().numpy().view(np.uint32)                                  # the one read-back that waits
-        for b in range(B):
-            if st[b, RANS_LANES + 2] != 0:
-                raise CodecError(f"image {b}: the rANS encoder met a malformed table, a pixel index outside the "
-                                 f"image or step lengths that do not add up (error word {int(st[b, RANS_LANES + 2])})")
+        for i in range(B * G):
+            if st[i, RANS_LANES + 2] != 0:
+                raise CodecError(f"image {i // G}: the rANS encoder met a malformed table, a pixel index outside the "
+                                 f"image or step lengths that do not add up (error word {int(st[i, RANS_LANES + 2])})")
         streams, escs = [], []
-        for b in range(B):
-            nw, ne = int(st[b, RANS_LANES]), int(st[b, RANS_LANES + 1])
-            if 2 * nw > slot or ne > nsym:
-                raise CodecError(f"image {b}: the rANS encoder reports impossible counts ({nw} words, {ne} escapes)")
-            streams.append(st[b, :RANS_LANES].astype("<u4").tobytes() + words[b, slot - 2 * nw:].cpu().numpy().tobytes())
-            escs.append(esc[b, :ne].cpu().numpy().view(np.uint32).astype("<u4").tobytes())
+        for i in range(B * G):
+            nw, ne = int(st[i, RANS_LANES]), int(st[i, RANS_LANES + 1])
+            if 2 * nw > slot or ne > cap:
+                raise CodecError(f"image {i // G}: the rANS encoder reports impossible counts ({nw} words, {ne} escapes)")
+            streams.append(st[i, :RANS_LANES].astype("<u4").tobytes() + words[i, slot - 2 * nw:].cpu().numpy().tobytes())
+            escs.append(esc[i, :ne].cpu().numpy().view(np.uint32).astype("<u4").tobytes())
         return streams, escs
 
     @torch.no_grad()
@@ -534,18 +616,21 @@ class ContextCodec:
 
     def _decode_y_rans(self, strings, steps, layers, yflat, psi_flat, win_idx, own_idx, psi_idx):
         """The step loop of the "rans" coder: streams, escape lists, state blocks and index arrays go up once, then
-        every step is gather -> per-pixel layers + tables -> lic_rans_decode_step, which writes the decoded values
-        into `yflat` where the next gather reads them.  Nothing in the loop waits for the device; the state blocks
-        (error words, cursors, final states) come back once, after the last step."""
-        B, npad, M = yflat.shape
+        every step is gather -> per-pixel layers + tables -> lic_rans_decode_step_groups, which writes the decoded
+        values into `yflat` where the next gather reads them.  Nothing in the loop waits for the device; the state
+        blocks (error words, cursors, final states) come back once, after the last step.  One block per image and
+        group (`strings["groups"]`, 1 if absent), image-major; below B counts blocks."""
+        nimg, npad, M = yflat.shape
         dev = yflat.device
+        G = _groups(strings.get("groups", 1))
+        B = nimg * G
         ys, escs = strings["y"], strings.get("y_esc")
         if escs is None or len(ys) != B or len(escs) != B:
-            raise CodecError("one y stream and one escape list per image expected")
+            raise CodecError("one y stream and one escape list per image and group expected")
         head = 4 * RANS_LANES
         for b in range(B):
             if len(ys[b]) < head or len(ys[b]) % 2 or len(escs[b]) % 4:
-                raise CodecError(f"image {b}: y stream or escape list has an impossible length")
+                raise CodecError(f"image {b // G}: y stream or escape list has an impossible length")
         # staging: every stream starts on a 4-byte boundary; offsets, lengths and seeds in one upload each
         s_off = np.zeros(B + 1, np.int64)
         for b in range(B):
@@ -566,22 +651,23 @@ class ContextCodec:
         for ii, _ in steps:
             n = len(ii)
             win = yflat.index_select(1, win_idx[off * nt:(off + n) * nt])                 # [B, n*12, M]
-            center, tables = self._params_at(win.view(B * n, nt * M, 1, 1),
-                                             psi_flat.index_select(1, psi_idx[off:off + n]).view(B * n, -1, 1, 1),
+            center, tables = self._params_at(win.view(nimg * n, nt * M, 1, 1),
+                                             psi_flat.index_select(1, psi_idx[off:off + n]).view(nimg * n, -1, 1, 1),
                                              layers)
-            L.check(lib.lic_rans_decode_step(F_._ptr(d_buf), F_._ptr(d_soff), F_._ptr(d_slen), F_._ptr(d_esc),
-                                             F_._ptr(d_eoff), F_._ptr(d_state), F_._ptr(tables), F_._ptr(center),
-                                             B, n, M, self.y_W, F_._ptr(own_idx[off:off + n]), F_._ptr(yflat), npad,
-                                             F_._stream()), "lic_rans_decode_step")
+            L.check(lib.lic_rans_decode_step_groups(F_._ptr(d_buf), F_._ptr(d_soff), F_._ptr(d_slen), F_._ptr(d_esc),
+                                                    F_._ptr(d_eoff), F_._ptr(d_state), F_._ptr(tables),
+                                                    F_._ptr(center), nimg, G, n, M, self.y_W,
+                                                    F_._ptr(own_idx[off:off + n]), F_._ptr(yflat), npad,
+                                                    F_._stream()), "lic_rans_decode_step_groups")
             off += n
         st = d_state.cpu().numpy().view(np.uint32)                                        # the one read-back
         for b in range(B):
             if st[b, RANS_LANES + 2] != 0:
-                raise CodecError(f"image {b}: the rANS decoder ran past the end of its stream or escape list "
+                raise CodecError(f"image {b // G}: the rANS decoder ran past the end of its stream or escape list "
                                  f"(error word {int(st[b, RANS_LANES + 2])}): the stream is damaged")
             if (st[b, RANS_LANES] != (len(ys[b]) - head) // 2 or st[b, RANS_LANES + 1] != len(escs[b]) // 4
                     or (st[b, :RANS_LANES] != 1 << 16).any()):
-                raise CodecError(f"image {b}: the rANS stream was not used up exactly (trailing words or escapes, "
+                raise CodecError(f"image {b // G}: the rANS stream was not used up exactly (trailing words or escapes, "
                                  "or final states that are not the encoder's start): the stream is damaged")
 
     def _finish(self, strings, ypad, z_hat, shape) -> Dict:
@@ -613,19 +699,22 @@ class ContextCodec:
         the padded tensor; the header (`pack_bitstream`) carries everything the decoder needs to rebuild the
         shapes and to crop back.  bpp_coded of the result is 8 * len(data) / (B * H * W): header and checksums
         included, per ORIGINAL pixel.  `coder`: None = this codec's own; "range" writes a LICBITS1 container,
-        "rans" a LICBITS2 one (`pack_bitstream_rans`)."""
+        "rans" a LICBITS2 one (`pack_bitstream_rans`), or with `groups` > 1 a LICBITS3 one
+        (`pack_bitstream_grouped`)."""
         if x.dim() != 4:
             raise CodecError("expected a [B,3,H,W] tensor")
         if coder is not None and coder != self.coder:
             # the encoder goes with the coder it belongs to: only "rans" has a device encoder
-            enc = self.encoder if coder == "rans" else "host"
-            return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder, enc).compress_image(x, mode, align)
+            enc, G = (self.encoder, self.groups) if coder == "rans" else ("host", 1)
+            return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder, enc, G).compress_image(x, mode, align)
         B, _, H, W = x.shape
         _, _, top, left = F_.pad_geometry(H, W, 64, align)
         r = self.compress(F_.pad_to_multiple(x, 64, mode, align))
         s = r["strings"]
         head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
                 "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
+        if self.groups > 1:
+            return pack_bitstream_grouped(head, s["z"], s["y"], s["y_esc"], s["y_crc32"], self.groups)
         if self.coder == "rans":
             return pack_bitstream_rans(head, s["z"], s["y"], s["y_esc"], s["y_crc32"])
         return pack_bitstream(head, s["z"], s["y"], s["y_crc32"])
@@ -636,8 +725,14 @@ class ContextCodec:
         work, for a bad magic, a truncated buffer, a failing CRC or a header whose family / M / K are not this
         model's.  The magic selects the coder, whatever this codec's own is."""
         strings = {}
-        if bytes(data[:8]) == BITSTREAM_MAGIC_RANS:
-            head, z_bytes, y_streams, y_esc, y_crc = unpack_bitstream_rans(data)
+        magic = bytes(data[:8])
+        if magic in (BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_GROUPED):
+            if magic == BITSTREAM_MAGIC_GROUPED:
+                head, z_bytes, y_streams, y_esc, y_crc, G = unpack_bitstream_grouped(data)
+                if G > 1:
+                    strings["groups"] = G
+            else:
+                head, z_bytes, y_streams, y_esc, y_crc = unpack_bitstream_rans(data)
             if head["y_W"] > RANS_MAX_W:
                 raise CodecError(f"bitstream names y_W = {head['y_W']}; the rANS decoder takes windows of 1 to "
                                  f"{RANS_MAX_W}")
@@ -726,8 +821,8 @@ def _check_crc_and_head(data: bytes, head: Dict):
 #   magic b"LICBITS2" | the LICBITS1 header fields | uint32 z-stream length | uint32 lanes (64)
 #   | B x (uint32 y-stream length, uint32 CRC-32 of the latent symbols, uint32 escape count)
 #   | z stream | for image 0 .. B-1: y stream, then its escape list (uint32 each) | uint32 CRC-32 of all before it
-# `lanes` is the interleaving of the y streams: a decoder that meets a value it does not implement raises
-# CodecError, so wider interleaving later needs no new magic.
+# `lanes` is the interleaving of the y streams: 64.  A decoder that meets another value raises CodecError; wider
+# interleaving has a container of its own (LICBITS3 below), because its per-image table has another shape.
 # ---------------------------------------------------------------------------------------------
 BITSTREAM_MAGIC_RANS = b"LICBITS2"
 _BITS_HEAD_RANS = struct.Struct("<8sIIIiIIIIIIIII")
@@ -778,3 +873,71 @@ def unpack_bitstream_rans(data: bytes):
         es.append(data[at + n:at + n + 4 * e])
         at += n + 4 * e
     return head, z_bytes, ys, es, [c for _, c, _ in table]
+
+
+# ---------------------------------------------------------------------------------------------
+# Container of the "rans" coder with groups ("rANS-64 x G", `rans_deal`).  Little endian:
+#   magic b"LICBITS3" | the LICBITS1 header fields | uint32 z-stream length | uint32 lanes (= 64 G, G in 1..8)
+#   | B x uint32 CRC-32 of the image's latent symbols
+#   | B*G x (uint32 sub-stream length, uint32 escape count), image-major (entry b * G + g)
+#   | z stream | for image 0 .. B-1, for group 0 .. G-1: sub-stream, then its escape list
+#   | uint32 CRC-32 of all before it
+# ---------------------------------------------------------------------------------------------
+BITSTREAM_MAGIC_GROUPED = b"LICBITS3"
+
+
+def pack_bitstream_grouped(head: Dict, z_bytes: bytes, y_streams, y_esc, y_crc32, groups: int) -> bytes:
+    """`head`: the _BITS_FIELDS; B * `groups` sub-streams and escape lists (bytes, uint32 each), image-major, and one
+    symbol checksum per image"""
+    G, B = _groups(groups), int(head["B"])
+    if len(y_streams) != B * G or len(y_esc) != B * G or len(y_crc32) != B:
+        raise CodecError("one sub-stream and one escape list per image and group, one checksum per image expected")
+    if any(len(e) % 4 for e in y_esc):
+        raise CodecError("an escape list is not a whole number of uint32")
+    parts = [_BITS_HEAD_RANS.pack(BITSTREAM_MAGIC_GROUPED, *(int(head[k]) for k in _BITS_FIELDS), len(z_bytes),
+                                  RANS_LANES * G)]
+    parts += [struct.pack("<I", int(c) & 0xFFFFFFFF) for c in y_crc32]
+    parts += [struct.pack("<II", len(s), len(e) // 4) for s, e in zip(y_streams, y_esc)]
+    parts += [bytes(z_bytes)]
+    for s, e in zip(y_streams, y_esc):
+        parts += [bytes(s), bytes(e)]
+    body = b"".join(parts)
+    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+
+
+def unpack_bitstream_grouped(data: bytes):
+    """-> (head dict, z_bytes, [sub-stream per image and group], [escape list likewise], [symbol checksum per image],
+    groups); CodecError as `unpack_bitstream`, for a `lanes` value that is no multiple of 64 from 64 to 512, and for
+    a sub-stream shorter than its 64 states or of odd length."""
+    data = bytes(data)
+    if len(data) < _BITS_HEAD_RANS.size + 4:
+        raise CodecError("bitstream is truncated (shorter than its header)")
+    vals = _BITS_HEAD_RANS.unpack_from(data, 0)
+    if vals[0] != BITSTREAM_MAGIC_GROUPED:
+        raise CodecError("not a LICBITS3 bitstream (bad magic)")
+    head = dict(zip(_BITS_FIELDS, vals[1:-2]))
+    z_len, lanes, B = vals[-2], vals[-1], head["B"]
+    if lanes % RANS_LANES or not RANS_LANES <= lanes <= RANS_LANES * RANS_MAX_GROUPS:
+        raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements multiples of "
+                         f"{RANS_LANES} up to {RANS_LANES * RANS_MAX_GROUPS}")
+    G = lanes // RANS_LANES
+    at = _BITS_HEAD_RANS.size
+    if B == 0 or len(data) < at + 4 * B + 8 * B * G + 4:
+        raise CodecError("bitstream is truncated (per-image tables)")
+    crcs = list(struct.unpack_from("<%dI" % B, data, at))
+    at += 4 * B
+    table = [struct.unpack_from("<II", data, at + 8 * i) for i in range(B * G)]
+    at += 8 * B * G
+    if len(data) != at + z_len + sum(n + 4 * e for n, e in table) + 4:
+        raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
+    _check_crc_and_head(data, head)
+    if any(n < 4 * RANS_LANES or n % 2 for n, _ in table):
+        raise CodecError("bitstream names a sub-stream shorter than its 64 states or of odd length")
+    z_bytes = data[at:at + z_len]
+    at += z_len
+    ys, es = [], []
+    for n, e in table:
+        ys.append(data[at:at + n])
+        es.append(data[at + n:at + n + 4 * e])
+        at += n + 4 * e
+    return head, z_bytes, ys, es, crcs, G

@@ -1,8 +1,9 @@
-// lic_rans_decode_step: one wavefront step of the "rANS-64" y streams (include/lic_codec.h) decoded where the
-// tables are built, so codec.ContextCodec's step loop needs no copy to the host, no synchronisation and no host
-// arithmetic.
+// lic_rans_decode_step / lic_rans_decode_step_groups: one wavefront step of the "rANS-64" and "rANS-64 x G" y
+// streams (include/lic_codec.h) decoded where the tables are built, so codec.ContextCodec's step loop needs no copy
+// to the host, no synchronisation and no host arithmetic.
 //
-// One wave per image: lane l owns coder state l.  A round decodes 64 symbols: each lane searches its own table
+// One wave per (image, group), each a workgroup of its own with its own LDS rows: lane l owns coder state l of the
+// block, and the wave of group g decodes rounds g, g + G, ... of the step (G = 1: one wave per image, every round).  A round decodes 64 symbols: each lane searches its own table
 // row for the 16-bit slot of its state, updates the state, and the lanes that fell below 2^16 share the stream
 // with one ballot (who needs a word), one popcount (rank among them) and a wave-uniform cursor.
 //
@@ -18,8 +19,8 @@
 // With that stride element `rel` of the round (row rel / (S+1)) sits at LDS dword rel + row.
 //
 // Nothing outside the given buffers is ever read: a word or escape is read only after cursor + rank has been
-// compared with the image's length; otherwise the image's error word is set and every later symbol decodes as
-// its table centre.  Destination indices outside [0, pixels) are not written and set the error word too.
+// compared with the block's length; otherwise the block's error word is set and every later symbol of the block
+// decodes as its table centre.  Destination indices outside [0, pixels) are not written and set the error word too.
 #include "lic_common.h"
 
 namespace {
@@ -27,38 +28,42 @@ namespace {
 constexpr int kLanes = 64;
 constexpr int kStateWords = LIC_RANS_STATE_WORDS;
 
-// NQ: 16-byte table pieces a lane holds for one round; S1MAX: largest S+1 that fits
-template <int NQ, int S1MAX>
+// NQ: 16-byte table pieces a lane holds for one round; S1MAX: largest S+1 that fits; kGrouped == false: one group,
+// G is the constant 1 and the code is the one-wave-per-image kernel it always was
+template <int NQ, int S1MAX, bool kGrouped>
 __global__ __launch_bounds__(64) void rans_step_kernel(const uint8_t* __restrict__ streams,
                                                        const int64_t* __restrict__ stream_off,
                                                        const int64_t* __restrict__ stream_bytes,
                                                        const uint32_t* __restrict__ escapes,
                                                        const int64_t* __restrict__ esc_off, uint32_t* state,
                                                        const uint32_t* __restrict__ tables,
-                                                       const int32_t* __restrict__ center, int32_t nsym, int32_t M,
-                                                       int32_t W, const int64_t* __restrict__ dest, float* ypad,
-                                                       int64_t pixels, int64_t total_dwords) {
+                                                       const int32_t* __restrict__ center, int32_t groups, int32_t nsym,
+                                                       int32_t M, int32_t W, const int64_t* __restrict__ dest,
+                                                       float* ypad, int64_t pixels, int64_t total_dwords) {
   __shared__ uint32_t lds[kLanes * (S1MAX + 1)];
-  const int b = blockIdx.x, lane = threadIdx.x;
+  // blk: the state block, stream and escape list of (image b, group g); tables, centres and ypad go by image
+  const int G = kGrouped ? groups : 1;
+  const int blk = blockIdx.x, b = blk / G, g = blk - b * G, lane = threadIdx.x;
+  const int rounds = (nsym + kLanes - 1) / kLanes;
+  if (g >= rounds) return;  // no round of this step is this group's: the state block stays as it is
   const int S1 = 2 * W + 2, S = S1 - 1, stride = S1 + 1;
   const uint32_t inv = ((1u << 24) + S1 - 1) / S1;  // rel / S1 == (rel * inv) >> 24 for rel < 64 * S1 <= 2^14
 
-  uint32_t* st = state + (size_t)b * kStateWords;
+  uint32_t* st = state + (size_t)blk * kStateWords;
   uint32_t x = st[lane];
   uint32_t ptr = st[kLanes], eptr = st[kLanes + 1], err = st[kLanes + 2];
-  const int64_t o0 = stream_off[b], room = stream_off[b + 1] - o0;
-  int64_t len = stream_bytes[b];
+  const int64_t o0 = stream_off[blk], room = stream_off[blk + 1] - o0;
+  int64_t len = stream_bytes[blk];
   if (len > room || len < kLanes * 4 || o0 < 0) {
     err |= LIC_RANS_ERR_STREAM;
     len = kLanes * 4;
   }
   const uint16_t* words = reinterpret_cast<const uint16_t*>(streams + (o0 < 0 ? 0 : o0) + kLanes * 4);
   const uint64_t nwords = (uint64_t)(len - kLanes * 4) >> 1;
-  const int64_t e0 = esc_off[b], e1 = esc_off[b + 1];
+  const int64_t e0 = esc_off[blk], e1 = esc_off[blk + 1];
   const uint64_t nesc = (e0 >= 0 && e1 >= e0) ? (uint64_t)(e1 - e0) : 0;
   const uint32_t* esc = escapes + (e0 < 0 ? 0 : e0);
 
-  const int rounds = (nsym + kLanes - 1) / kLanes;
   const int64_t gbase = (int64_t)b * nsym * S1;  // this image's first table dword
   uint4 pre[NQ];
 
@@ -111,10 +116,10 @@ __global__ __launch_bounds__(64) void rans_step_kernel(const uint8_t* __restrict
     }
   };
 
-  fetch(0);
-  drop(0);
+  fetch(g);
+  drop(g);
   __syncthreads();
-  for (int r = 0; r < rounds; ++r) {
+  for (int r = g; r < rounds; r += G) {
     const int k = r * kLanes + lane;
     const bool active = k < nsym;
     // loads that do not depend on the search, oldest first so that waiting for them leaves the prefetch in flight
@@ -122,7 +127,7 @@ __global__ __launch_bounds__(64) void rans_step_kernel(const uint8_t* __restrict
     const uint32_t wpre = (err == 0 && wi < nwords) ? (uint32_t)words[wi] : 0u;
     const int32_t c = active ? center[(int64_t)b * nsym + k] : 0;
     const int64_t d = active ? dest[k / M] : 0;
-    if (r + 1 < rounds) fetch(r + 1);
+    if (r + G < rounds) fetch(r + G);
 
     int s = W;  // the table centre: what an image in error decodes
     bool bad = false;
@@ -180,8 +185,8 @@ __global__ __launch_bounds__(64) void rans_step_kernel(const uint8_t* __restrict
     }
     if (__any(bad)) err |= LIC_RANS_ERR_RANGE;
     __syncthreads();  // every lane has finished searching this round's rows
-    if (r + 1 < rounds) {
-      drop(r + 1);
+    if (r + G < rounds) {
+      drop(r + G);
       __syncthreads();
     }
   }
@@ -195,27 +200,46 @@ __global__ __launch_bounds__(64) void rans_step_kernel(const uint8_t* __restrict
 
 }  // namespace
 
+static int decode_step(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
+                       const uint32_t* escapes, const int64_t* esc_off, uint32_t* state, const uint32_t* tables,
+                       const int32_t* center, int32_t B, int32_t G, int32_t n, int32_t M, int32_t W,
+                       const int64_t* dest, float* ypad, int64_t pixels, lic_stream_t stream) {
+  if (!streams || !stream_off || !stream_bytes || !escapes || !esc_off || !state || !tables || !center || !dest || !ypad)
+    return LIC_ERR_INVALID;
+  if (B <= 0 || n <= 0 || M <= 0 || W <= 0 || pixels <= 0) return LIC_ERR_INVALID;
+  if (G < 1 || G > LIC_RANS_MAX_GROUPS) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(tables) & 15) || (reinterpret_cast<uintptr_t>(streams) & 3)) return LIC_ERR_INVALID;
+  if (W > 64) return LIC_ERR_UNSUPPORTED;
+  const int64_t nsym = (int64_t)n * M;
+  if (nsym > 0x7FFFFFFFL - kLanes || (int64_t)B * G > 65535) return LIC_ERR_UNSUPPORTED;
+  const int64_t total = (int64_t)B * nsym * (2 * W + 2);
+  // a round spans 64 * (S+1) dwords plus up to 3 of misalignment: 17 pieces per lane for S+1 <= 66, 33 for <= 130
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(B * G), dim3(kLanes), 0, (hipStream_t)stream, streams, stream_off, stream_bytes,
+                       escapes, esc_off, state, tables, center, G, (int32_t)nsym, M, W, dest, ypad, pixels, total);
+  };
+  if (W <= 32)
+    G == 1 ? launch(rans_step_kernel<17, 66, false>) : launch(rans_step_kernel<17, 66, true>);
+  else
+    G == 1 ? launch(rans_step_kernel<33, 130, false>) : launch(rans_step_kernel<33, 130, true>);
+  return lic_check_launch();
+}
+
 LIC_EXPORT int lic_rans_decode_step(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
                                     const uint32_t* escapes, const int64_t* esc_off, uint32_t* state,
                                     const uint32_t* tables, const int32_t* center, int32_t B, int32_t n, int32_t M,
                                     int32_t W, const int64_t* dest, float* ypad, int64_t pixels,
                                     lic_stream_t stream) {
-  if (!streams || !stream_off || !stream_bytes || !escapes || !esc_off || !state || !tables || !center || !dest || !ypad)
-    return LIC_ERR_INVALID;
-  if (B <= 0 || n <= 0 || M <= 0 || W <= 0 || pixels <= 0) return LIC_ERR_INVALID;
-  if ((reinterpret_cast<uintptr_t>(tables) & 15) || (reinterpret_cast<uintptr_t>(streams) & 3)) return LIC_ERR_INVALID;
-  if (W > 64) return LIC_ERR_UNSUPPORTED;
-  const int64_t nsym = (int64_t)n * M;
-  if (nsym > 0x7FFFFFFFL - kLanes || (int64_t)B > 65535) return LIC_ERR_UNSUPPORTED;
-  const int64_t total = (int64_t)B * nsym * (2 * W + 2);
-  // a round spans 64 * (S+1) dwords plus up to 3 of misalignment: 17 pieces per lane for S+1 <= 66, 33 for <= 130
-  if (W <= 32)
-    hipLaunchKernelGGL((rans_step_kernel<17, 66>), dim3(B), dim3(kLanes), 0, (hipStream_t)stream, streams, stream_off,
-                       stream_bytes, escapes, esc_off, state, tables, center, (int32_t)nsym, M, W, dest, ypad, pixels,
-                       total);
-  else
-    hipLaunchKernelGGL((rans_step_kernel<33, 130>), dim3(B), dim3(kLanes), 0, (hipStream_t)stream, streams,
-                       stream_off, stream_bytes, escapes, esc_off, state, tables, center, (int32_t)nsym, M, W, dest,
-                       ypad, pixels, total);
-  return lic_check_launch();
+  return decode_step(streams, stream_off, stream_bytes, escapes, esc_off, state, tables, center, B, 1, n, M, W, dest,
+                     ypad, pixels, stream);
+}
+
+LIC_EXPORT int lic_rans_decode_step_groups(const uint8_t* streams, const int64_t* stream_off,
+                                           const int64_t* stream_bytes, const uint32_t* escapes,
+                                           const int64_t* esc_off, uint32_t* state, const uint32_t* tables,
+                                           const int32_t* center, int32_t B, int32_t G, int32_t n, int32_t M,
+                                           int32_t W, const int64_t* dest, float* ypad, int64_t pixels,
+                                           lic_stream_t stream) {
+  return decode_step(streams, stream_off, stream_bytes, escapes, esc_off, state, tables, center, B, G, n, M, W, dest,
+                     ypad, pixels, stream);
 }

@@ -1,14 +1,17 @@
-// lic_rans_encode_pick + lic_rans_encode: the encoder of the "rANS-64" y streams (include/lic_codec.h) run where
-// lic_gmm_cdf_tables has left the tables, so codec.ContextCodec.compress copies streams, not tables, to the host.
-// Byte for byte the host encoder of lic_rans.cpp: same streams, same escape lists.
+// lic_rans_encode_pick + lic_rans_encode / lic_rans_encode_groups: the encoder of the "rANS-64" and "rANS-64 x G" y
+// streams (include/lic_codec.h) run where lic_gmm_cdf_tables has left the tables, so codec.ContextCodec.compress
+// copies streams, not tables, to the host.  Byte for byte the host encoder of lic_rans.cpp: same streams, same
+// escape lists.
 //
 // An rANS encoder never searches: symbol k needs cum[s] and cum[s+1] of its own table, and neither its table nor
 // its symbol depends on a coder state.  So the work splits in two launches:
 //  * pick (one thread per symbol, any grid) resolves wavefront order -> raster pixel, clamps the symbol, validates
 //    the table as the host does and leaves one uint32 (start << 16 | freq) and one escape word per symbol, in
 //    coding order;
-//  * encode (one wave per image, lane l owns state l) walks those words.  Escapes first, forward: ballot, rank,
-//    a wave-uniform cursor.  Then the states, backward: steps and rounds last to first; the lanes whose state
+//  * encode (one wave per image, lane l owns state l; in rans_encode_groups_kernel one wave per image and group, the
+//    wave of group g visiting the rounds whose index inside their step is g, g + G, ...) walks those words.
+//    Escapes first, forward: ballot, rank, a wave-uniform cursor.  Then the states, backward: steps and rounds
+//    last to first; the lanes whose state
 //    would overflow share the stream with one ballot (who emits), one popcount below the lane (rank) and a
 //    wave-uniform cursor that moves towards lower addresses.  Ascending lane id is reading order, which is what the
 //    host's "lanes 63 down to 0, towards lower addresses" produces.
@@ -21,7 +24,7 @@
 //
 // Nothing outside the given buffers is read or written: pick checks every order entry before it indexes with it,
 // encode checks the step lengths (non-negative, summing to nsym) before it walks them and compares the word cursor
-// with the slot's first word before every store.
+// with the slot's first word, and the escape cursor with the list's capacity, before every store.
 #include "lic_common.h"
 
 namespace {
@@ -189,6 +192,175 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint32_t* __restr
   if (lane == 0) st[kLanes] = wend - wpos, st[kLanes + 1] = nesc, st[kLanes + 2] = err;
 }
 
+// The rounds of one group, as (first symbol, active lanes): round r of a step is the group's if r % G == g.
+// Wave-uniform.
+struct GroupRounds {
+  const int64_t* step_len;
+  int32_t g, G;
+  __device__ __forceinline__ int32_t count(int32_t n) const {  // the group's rounds in a step of n symbols
+    const int32_t R = (n + kLanes - 1) / kLanes;
+    return R > g ? (int32_t)((uint32_t)(R - 1 - g) / (uint32_t)G) + 1 : 0;
+  }
+};
+
+// RoundWalk for one group: its rounds last to first.
+struct GroupWalk {
+  GroupRounds of;
+  int64_t t;     // steps [0, t) are still whole
+  int32_t base;  // first symbol of step t
+  int32_t len;   // symbols of step t
+  int32_t r;     // the group's last round of step t not yet handed out; below 0: none
+  __device__ __forceinline__ bool next(int32_t& k0, int32_t& n) {
+    while (r < 0 && t > 0) {
+      --t;
+      len = (int32_t)of.step_len[t];
+      base -= len;
+      r = of.g + (of.count(len) - 1) * of.G;  // g - G < 0 for a step without a round of this group
+    }
+    if (r < 0) return false;
+    k0 = base + r * kLanes;
+    n = min(kLanes, len - r * kLanes);
+    r -= of.G;
+    return true;
+  }
+};
+
+// The same rounds first to last: the order of the escape list.
+struct GroupWalkForward {
+  GroupRounds of;
+  int64_t nsteps;
+  int64_t t;     // the next step to open
+  int32_t base;  // first symbol of the open step
+  int32_t len;   // symbols of the open step
+  int32_t R;     // its rounds
+  int32_t r;     // the group's first round of the open step not yet handed out; R or above: none
+  __device__ __forceinline__ bool next(int32_t& k0, int32_t& n) {
+    while (r >= R && t < nsteps) {
+      base += len;
+      len = (int32_t)of.step_len[t++];
+      R = (len + kLanes - 1) / kLanes;
+      r = of.g;
+    }
+    if (r >= R) return false;
+    k0 = base + r * kLanes;
+    n = min(kLanes, len - r * kLanes);
+    r += of.G;
+    return true;
+  }
+};
+
+// rans_encode_kernel with one wave per (image, group).  The same escape pass, ring and divide; the two walks hand out
+// the group's rounds only, and the escape list has a capacity of its own to compare with
+__global__ __launch_bounds__(64) void rans_encode_groups_kernel(const uint32_t* __restrict__ sf,
+                                                         const uint32_t* __restrict__ exc,
+                                                         const int64_t* __restrict__ step_len, int64_t nsteps,
+                                                         int32_t G, int32_t nsym, uint8_t* __restrict__ words,
+                                                         int64_t slot, uint32_t* __restrict__ esc_out,
+                                                         uint32_t esc_cap, uint32_t* state) {
+  // blk: the slot, escape list and state block of (image b, group g); sf and exc go by image
+  const int blk = blockIdx.x, b = blk / G, g = blk - b * G, lane = threadIdx.x;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const GroupRounds of{step_len, g, G};
+  sf += (int64_t)b * nsym;
+  exc += (int64_t)b * nsym;
+  esc_out += (int64_t)blk * esc_cap;
+  uint32_t* st = state + (size_t)blk * kStateWords;
+  uint32_t err = st[kLanes + 2];
+
+  // the step lengths must be non-negative and add up to nsym before anything is indexed with them
+  int64_t sum = 0, rounds = 0;
+  bool okl = true;
+  for (int64_t t = lane; t < nsteps; t += kLanes) {
+    const int64_t n = step_len[t];
+    if (n < 0 || n > nsym)
+      okl = false;
+    else
+      sum += n, rounds += of.count((int32_t)n);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sum += __shfl_xor(sum, o, kLanes);
+    rounds += __shfl_xor(rounds, o, kLanes);
+  }
+  if (!__all(okl) || sum != nsym) {
+    st[lane] = 1u << 16;
+    if (lane == 0) st[kLanes] = 0u, st[kLanes + 1] = 0u, st[kLanes + 2] = err | LIC_RANS_ERR_RANGE;
+    return;
+  }
+
+  // escapes, forward, in the symbol order of the group's rounds
+  uint32_t nesc = 0;
+  GroupWalkForward fwd{of, nsteps, 0, 0, 0, 0, 0};
+  for (int64_t r = 0; r < rounds; r += kRing) {
+    uint32_t e[kRing];
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {  // all loads first: none depends on the cursor, none sits under a branch
+      int32_t k0 = 0, n = 0;
+      fwd.next(k0, n);  // leaves (0, 0) once the walk is over
+      const uint32_t v = exc[lane < n ? k0 + lane : 0];
+      e[j] = lane < n ? v : kNoEscape;
+    }
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {
+      const bool edge = e[j] != kNoEscape;
+      const unsigned long long mask = __ballot(edge);
+      const uint32_t cnt = (uint32_t)__popcll(mask);
+      // the list has room for the round's escapes or takes none of them; it cannot run out with one entry per symbol
+      // of the group.  No branch around the store: the waits for e[] stay counted
+      const bool room = cnt <= esc_cap - nesc;
+      if (edge && room) esc_out[nesc + (uint32_t)__popcll(mask & below)] = e[j];
+      nesc += room ? cnt : 0u;
+      err |= room ? 0u : LIC_RANS_ERR_RANGE;
+    }
+  }
+
+  // states, backward
+  uint16_t* wbuf = reinterpret_cast<uint16_t*>(words + (int64_t)blk * slot);
+  const uint32_t wend = (uint32_t)(slot >> 1);
+  uint32_t wpos = wend;  // in 16-bit words from the slot's start; the words so far are [wpos, wend)
+  uint32_t x = 1u << 16;
+  GroupWalk walk{of, nsteps, nsym, 0, -1};
+  // the ring: a round's raw words and its number of active lanes.  Exactly one load per round, taken or not (an
+  // idle lane reads word 0; it is dropped where the round is consumed): a load under a branch cannot be counted,
+  // and every wait for the ring would then wait for all of it
+  uint32_t ring[kRing];
+  int32_t live[kRing];
+  auto fetch = [&](int j) {
+    int32_t k0 = 0, n = 0;
+    walk.next(k0, n);  // leaves (0, 0) once the walk is over
+    ring[j] = sf[lane < n ? k0 + lane : 0];
+    live[j] = n;
+  };
+#pragma unroll
+  for (int j = 0; j < kRing; ++j) fetch(j);
+  for (int64_t r = 0; r < rounds; r += kRing) {
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {
+      const uint32_t w = lane < live[j] ? ring[j] : 0u;
+      fetch(j);  // the round kRing ahead; no lane is live once the walk is over
+      const uint32_t freq = w & 0xFFFFu, start = w >> 16;
+      const bool active = freq != 0u;
+      const bool emit = active && (x >> 16) >= freq;
+      const unsigned long long mask = __ballot(emit);
+      const uint32_t cnt = (uint32_t)__popcll(mask);
+      if (cnt > wpos) {  // cannot happen in a slot of one word per symbol of the group
+        err |= LIC_RANS_ERR_RANGE;
+      } else {
+        wpos -= cnt;
+        if (emit) {
+          wbuf[wpos + (uint32_t)__popcll(mask & below)] = (uint16_t)x;
+          x >>= 16;
+        }
+      }
+      const uint32_t f = active ? freq : 1u;
+      const uint32_t q = x / f;
+      if (active) x = (q << 16) + (x - q * f) + start;
+    }
+  }
+  st[lane] = x;
+  if (lane == 0) st[kLanes] = wend - wpos, st[kLanes + 1] = nesc, st[kLanes + 2] = err;
+}
+
 }  // namespace
 
 LIC_EXPORT int lic_rans_encode_pick(const uint32_t* tables, const int32_t* center, const int32_t* y,
@@ -222,5 +394,25 @@ LIC_EXPORT int lic_rans_encode(const uint32_t* sf, const uint32_t* exc, const in
   if (slot < 2 * nsym || (slot & 3) || slot > 0xFFFFFFFFL) return LIC_ERR_INVALID;
   hipLaunchKernelGGL(rans_encode_kernel, dim3(B), dim3(kLanes), 0, (hipStream_t)stream, sf, exc, step_len, nsteps,
                      (int32_t)nsym, words, slot, esc_out, state);
+  return lic_check_launch();
+}
+
+LIC_EXPORT int lic_rans_encode_groups(const uint32_t* sf, const uint32_t* exc, const int64_t* step_len,
+                                      int64_t nsteps, int32_t B, int32_t G, int64_t nsym, uint8_t* words,
+                                      int64_t slot, uint32_t* esc_out, int64_t esc_cap, uint32_t* state,
+                                      lic_stream_t stream) {
+  if (!sf || !exc || !step_len || !words || !esc_out || !state) return LIC_ERR_INVALID;
+  if (B <= 0 || nsym <= 0 || nsteps <= 0) return LIC_ERR_INVALID;
+  if (G < 1 || G > LIC_RANS_MAX_GROUPS) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(sf) | reinterpret_cast<uintptr_t>(exc) | reinterpret_cast<uintptr_t>(words) |
+       reinterpret_cast<uintptr_t>(esc_out) | reinterpret_cast<uintptr_t>(state)) & 3)
+    return LIC_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(step_len) & 7) return LIC_ERR_INVALID;
+  if (nsym > 0x7FFFFFFFL - kLanes || (int64_t)B * G > 65535) return LIC_ERR_UNSUPPORTED;
+  // whole dwords, so that every block's slot is aligned; what the two sizes must be at least is the caller's to know
+  // (lic.h): the kernel compares before every store
+  if (slot < 4 || (slot & 3) || slot > 0xFFFFFFFFL || esc_cap < 1 || esc_cap > 0x7FFFFFFFL) return LIC_ERR_INVALID;
+  hipLaunchKernelGGL(rans_encode_groups_kernel, dim3(B * G), dim3(kLanes), 0, (hipStream_t)stream, sf, exc, step_len,
+                     nsteps, G, (int32_t)nsym, words, slot, esc_out, (uint32_t)esc_cap, state);
   return lic_check_launch();
 }
