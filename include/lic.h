@@ -672,6 +672,35 @@ int lic_adam_run(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_b
                  double bias_correction2, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * lic_grad_norm / lic_adam_run_scaled -- torch.nn.utils.clip_grad_norm_(parameters, max_norm) in front of
+ *   optimizer.step() (the usual recipe for these models: the CompressAI example trainer clips at 1.0), and a guard
+ *   against a non-finite step, on the job table and `grads_host` of lic_adam_run.  Three launches, no read-back:
+ *   lic_grad_norm_partial  (once per job table / parameter group) block b of the lic_adam_plan partition writes the
+ *       sum of squares of its <= 4096 gradient elements, taken in double, to partials[b] (DEVICE, total_blocks
+ *       doubles).  Several groups write consecutive ranges of one buffer.
+ *   lic_grad_norm_finish   (once) one workgroup sums the nparts partials in a fixed order, in double, and writes
+ *       clip_state (DEVICE, 4 dwords, zeroed by the owner before the first call):
+ *         [0] float    total norm: the double square root, rounded once
+ *         [1] float    coefficient min(max_norm / (norm + 1e-6), 1) in fp32 arithmetic (a NaN norm gives NaN, as
+ *                      torch.clamp does); exactly 1 when max_norm is +inf (norm only, no clipping)
+ *         [2] uint32   1 if [0] is not finite, else 0
+ *         [3] uint32   running count: incremented by [2] when count_skip is set
+ *   lic_adam_run_scaled    (once per group) lic_adam_run with every gradient multiplied by [1] and rounded to fp32
+ *       once before the update uses it (bit for bit what `g *= coefficient` followed by lic_adam_run gives);
+ *       skip_nonfinite: when [2] is set, p / m / v are left untouched.
+ *   Fixed per-thread strides and fixed-shape trees, no atomics: the norm depends on the gradients, the job order and
+ *   the block size only, and is bitwise the same from run to run.
+ * ------------------------------------------------------------------------------------------ */
+int lic_grad_norm_partial(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
+                          const float* const* grads_host, double* partials, lic_stream_t stream);
+int lic_grad_norm_finish(const double* partials, int64_t nparts, double max_norm, int32_t count_skip, float* clip_state,
+                         lic_stream_t stream);
+int lic_adam_run_scaled(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
+                        const float* const* grads_host, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, double bias_correction1, double bias_correction2, const float* clip_state,
+                        int32_t skip_nonfinite, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * lic_reduce_batch -- every pending reduction of a backward pass (Trainer.py:84 `loss.backward()`) in ONE launch.
  *   The weight-gradient launches end in a slab reduction and the column sums (bias / GDN beta gradients) in a second
  *   stage: 41 launches of 5-15 us per config-3 step.  lic_wgrad_bf16_partial / lic_colsum_bf16_partial /

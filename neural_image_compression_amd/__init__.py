@@ -11,9 +11,9 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from .models import JointAutoregressiveHierarchical, HierarchicalMixtureResidual, ScalableImageCoding  # noqa: F401
 from .loss import rd_loss, rd_loss_msssim, vision_rd_loss  # noqa: F401
-from .optim import FusedAdam  # noqa: F401
+from .optim import FusedAdam, grad_norm  # noqa: F401
 from .anysize import padded_forward  # noqa: F401
 from . import _lib  # noqa: F401
 
 __all__ = ["JointAutoregressiveHierarchical", "HierarchicalMixtureResidual", "ScalableImageCoding", "rd_loss",
-           "rd_loss_msssim", "vision_rd_loss", "FusedAdam", "padded_forward"]
+           "rd_loss_msssim", "vision_rd_loss", "FusedAdam", "grad_norm", "padded_forward"]

@@ -80,6 +80,158 @@ __global__ __launch_bounds__(256) void adam_kernel(const lic_adam_job* jobs, int
     for (long i = begin + threadIdx.x; i < end; i += 256) upd(p[i], g[i], m[i], v[i]);
   }
 }
+// lic_grad_norm_partial / lic_grad_norm_finish / lic_adam_run_scaled: the global-norm clipping of the usual recipe
+// for these models (torch.nn.utils.clip_grad_norm_ before optimizer.step(): a handful of foreach launches that
+// read every gradient twice and write it once, and ~240 small host-side calls) as one more read of the gradients
+// over the block partition lic_adam_run already has, a one-workgroup sum, and a scale applied inside the update.
+// Every sum is a double sum of fixed shape: thread t of a block takes elements at a fixed stride, the 64 lanes of
+// a wave combine in a butterfly, thread 0 adds the 4 wave sums in wave order; no atomics.  The norm is therefore
+// a function of the gradients, the job order and AD_ITEMS only, bitwise the same from run to run.
+__device__ __forceinline__ double block_sum_d(double acc, double* s_wave) {
+  acc = wave_sum_d(acc);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];  // (wave order; every thread forms the same sum)
+}
+
+template <int NG>
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const lic_adam_job* jobs, int njobs,
+                                                                const AdamGrads<NG> grads, double* partials) {
+  __shared__ long s_n;
+  __shared__ int s_blk;
+  __shared__ const float* s_g;
+  __shared__ double s_wave[4];
+  if (threadIdx.x == 0) {
+    int lo = 0, hi = njobs - 1;
+    const int b = blockIdx.x;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (jobs[mid].block0 <= b) lo = mid;
+      else hi = mid - 1;
+    }
+    s_n = jobs[lo].n;
+    s_blk = b - jobs[lo].block0;
+    s_g = grads.g[lo];
+  }
+  __syncthreads();
+  const float* __restrict__ g = s_g;
+  const long n = s_n;
+  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
+  double acc = 0.0;
+  auto add = [&](float gw) { acc += (double)gw * (double)gw; };  // (the product of two floats is exact in double)
+  if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+    const long e4 = begin + ((end - begin) & ~3L);
+    for (long i = begin + threadIdx.x * 4L; i < e4; i += 256 * 4) {
+      const f32x4 gw = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) add(gw[e]);
+    }
+    for (long i = e4 + threadIdx.x; i < end; i += 256) add(g[i]);
+  } else {
+    for (long i = begin + threadIdx.x; i < end; i += 256) add(g[i]);
+  }
+  const double total = block_sum_d(acc, s_wave);
+  if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+// clip_state: [0] fp32 norm, [1] fp32 coefficient, [2] u32 norm-is-not-finite, [3] u32 skipped steps so far
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partials, long nparts,
+                                                               float max_norm, int unbounded, int count_skip,
+                                                               float* clip_state) {
+  __shared__ double s_wave[4];
+  double acc = 0.0;
+  for (long i = threadIdx.x; i < nparts; i += 256) acc += partials[i];
+  const double total = block_sum_d(acc, s_wave);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(total);  // (correctly rounded double sqrt, then ONE rounding to fp32)
+    // torch: clamp(max_norm / (total_norm + 1e-6), max=1.0) on an fp32 tensor; like torch.clamp, a NaN stays a NaN
+    const float c = max_norm / (norm + 1e-6f);
+    const float coef = unbounded ? 1.0f : (c > 1.0f ? 1.0f : c);
+    const unsigned bad = isfinite(norm) ? 0u : 1u;
+    unsigned* flags = reinterpret_cast<unsigned*>(clip_state);
+    const unsigned skipped = flags[3] + (count_skip ? bad : 0u);
+    clip_state[0] = norm;
+    clip_state[1] = coef;
+    flags[2] = bad;
+    flags[3] = skipped;
+  }
+}
+
+// the one rounding of g * coefficient that an unfused `grad.mul_(coefficient)` performs.  The empty asm makes the
+// product a value the optimiser cannot look into: hipcc would otherwise contract it into the multiply-adds of the
+// update, or pair it with `weight_decay * p` in one packed multiply and so undo the contraction adam_kernel gets
+// there -- either way other bits than the unfused order gives
+__device__ __forceinline__ float scale_once(float g, float coef) {
+  float r = g * coef;
+  asm volatile("" : "+v"(r));
+  return r;
+}
+
+// adam_kernel with the gradient scaled by clip_state[1] on the way in, and nothing done at all when the caller
+// asked for non-finite steps to be skipped and clip_state[2] says this one is
+template <int NG>
+__global__ __launch_bounds__(256) void adam_scaled_kernel(const lic_adam_job* jobs, int njobs, const AdamGrads<NG> grads,
+                                                          float lerp_w, float beta2, float one_minus_beta2, float eps,
+                                                          float weight_decay, float step_size, float bc2_sqrt,
+                                                          const float* __restrict__ clip_state, int skip_nonfinite) {
+  if (skip_nonfinite && reinterpret_cast<const unsigned*>(clip_state)[2] != 0u) return;  // (uniform over the grid)
+  const float coef = clip_state[1];
+  __shared__ lic_adam_job job;
+  __shared__ int s_blk;
+  __shared__ const float* s_g;
+  if (threadIdx.x == 0) {
+    int lo = 0, hi = njobs - 1;
+    const int b = blockIdx.x;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (jobs[mid].block0 <= b) lo = mid;
+      else hi = mid - 1;
+    }
+    job = jobs[lo];
+    s_blk = b - jobs[lo].block0;
+    s_g = grads.g[lo];
+  }
+  __syncthreads();
+  float* __restrict__ p = job.p;
+  const float* __restrict__ g = s_g;
+  float* __restrict__ m = job.m;
+  float* __restrict__ v = job.v;
+  const long n = job.n;
+  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
+  auto upd = [&](float& pw, float graw, float& mw, float& vw) {
+    float gw = scale_once(graw, coef);
+    if (weight_decay != 0.0f) gw += weight_decay * pw;
+    mw = lerp_w < 0.5f ? mw + lerp_w * (gw - mw) : gw - (gw - mw) * (1.0f - lerp_w);  // torch.lerp
+    vw = vw * beta2;
+    vw = vw + (one_minus_beta2 * gw) * gw;
+    const float denom = sqrtf(vw) / bc2_sqrt + eps;
+    pw = pw - step_size * (mw / denom);
+  };
+  const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                     reinterpret_cast<uintptr_t>(v)) & 15) == 0;
+  if (vec) {
+    const long e4 = begin + ((end - begin) & ~3L);
+    for (long i = begin + threadIdx.x * 4L; i < e4; i += 256 * 4) {
+      f32x4 pw = *reinterpret_cast<const f32x4*>(p + i), mw = *reinterpret_cast<const f32x4*>(m + i);
+      f32x4 vw = *reinterpret_cast<const f32x4*>(v + i);
+      const f32x4 gw = *reinterpret_cast<const f32x4*>(g + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pw[e], me = mw[e], ve = vw[e];
+        upd(pe, gw[e], me, ve);
+        pw[e] = pe;
+        mw[e] = me;
+        vw[e] = ve;
+      }
+      *reinterpret_cast<f32x4*>(p + i) = pw;
+      *reinterpret_cast<f32x4*>(m + i) = mw;
+      *reinterpret_cast<f32x4*>(v + i) = vw;
+    }
+    for (long i = e4 + threadIdx.x; i < end; i += 256) upd(p[i], g[i], m[i], v[i]);
+  } else {
+    for (long i = begin + threadIdx.x; i < end; i += 256) upd(p[i], g[i], m[i], v[i]);
+  }
+}
 }  // namespace
 
 // fills block0 / nblocks of a host-side job array; returns the grid size of lic_adam_run (or a negative status)
@@ -123,5 +275,79 @@ LIC_EXPORT int lic_adam_run(const lic_adam_job* jobs_device, int32_t njobs, int6
   if (njobs <= 96) adam_launch<96>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, s);
   else if (njobs <= 224) adam_launch<224>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, s);
   else adam_launch<448>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, s);
+  return lic_check_launch();
+}
+
+template <int NG>
+static void grad_norm_partial_launch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads,
+                                     double* partials, hipStream_t s) {
+  AdamGrads<NG> a;
+  for (int i = 0; i < NG; ++i) a.g[i] = i < njobs ? grads[i] : nullptr;
+  hipLaunchKernelGGL((grad_norm_partial_kernel<NG>), dim3((unsigned)blocks), dim3(256), 0, s, jobs_device, njobs, a,
+                     partials);
+}
+
+// the first half of torch.nn.utils.clip_grad_norm_ (torch._foreach_norm over every gradient): block b of the
+// lic_adam_plan partition writes the double sum of squares of its <= 4096 gradient elements to partials[b].
+// Same job table, same grads_host as lic_adam_run; partials: total_blocks doubles (DEVICE)
+LIC_EXPORT int lic_grad_norm_partial(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
+                                     const float* const* grads_host, double* partials, lic_stream_t stream) {
+  if (!jobs_device || !grads_host || !partials || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL)
+    return LIC_ERR_INVALID;
+  if (njobs > 448) return LIC_ERR_UNSUPPORTED;
+  for (int i = 0; i < njobs; ++i)
+    if (!grads_host[i]) return LIC_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  if (njobs <= 96) grad_norm_partial_launch<96>(jobs_device, njobs, total_blocks, grads_host, partials, s);
+  else if (njobs <= 224) grad_norm_partial_launch<224>(jobs_device, njobs, total_blocks, grads_host, partials, s);
+  else grad_norm_partial_launch<448>(jobs_device, njobs, total_blocks, grads_host, partials, s);
+  return lic_check_launch();
+}
+
+// the second half (vector_norm of the per-tensor norms, max_norm / (total_norm + 1e-6), clamp): one workgroup sums
+// the nparts partials of ALL groups in a fixed order and writes the 4 dwords of clip_state (DEVICE; see lic.h).
+// max_norm +inf: the norm is computed and the coefficient is exactly 1
+LIC_EXPORT int lic_grad_norm_finish(const double* partials, int64_t nparts, double max_norm, int32_t count_skip,
+                                    float* clip_state, lic_stream_t stream) {
+  if (!partials || !clip_state || nparts <= 0) return LIC_ERR_INVALID;
+  if (!(max_norm >= 0.0)) return LIC_ERR_INVALID;  // (negative or NaN)
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (long)nparts,
+                     (float)max_norm, isinf(max_norm) ? 1 : 0, count_skip ? 1 : 0, clip_state);
+  return lic_check_launch();
+}
+
+template <int NG>
+static void adam_scaled_launch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads,
+                               float lerp_w, float beta2, float one_minus_beta2, float eps, float wd, float step_size,
+                               float bc2_sqrt, const float* clip_state, int skip, hipStream_t s) {
+  AdamGrads<NG> a;
+  for (int i = 0; i < NG; ++i) a.g[i] = i < njobs ? grads[i] : nullptr;
+  hipLaunchKernelGGL((adam_scaled_kernel<NG>), dim3((unsigned)blocks), dim3(256), 0, s, jobs_device, njobs, a, lerp_w,
+                     beta2, one_minus_beta2, eps, wd, step_size, bc2_sqrt, clip_state, skip);
+}
+
+// lic_adam_run on gradients scaled by clip_state[1] (the `g.mul_(clip_coef_clamped)` of clip_grad_norm_, rounded to
+// fp32 once as there, without the pass over memory); skip_nonfinite: leave p / m / v alone when clip_state[2] is set.
+// clip_state is read on the device: the host does not wait for the norm
+LIC_EXPORT int lic_adam_run_scaled(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
+                                   const float* const* grads_host, double lr, double beta1, double beta2, double eps,
+                                   double weight_decay, double bias_correction1, double bias_correction2,
+                                   const float* clip_state, int32_t skip_nonfinite, lic_stream_t stream) {
+  if (!jobs_device || !grads_host || !clip_state || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL)
+    return LIC_ERR_INVALID;
+  if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) return LIC_ERR_INVALID;
+  if (njobs > 448) return LIC_ERR_UNSUPPORTED;
+  for (int i = 0; i < njobs; ++i)
+    if (!grads_host[i]) return LIC_ERR_INVALID;
+  const float lw = (float)(1.0 - beta1), ss = (float)(lr / bias_correction1), bs = (float)sqrt(bias_correction2);
+  const float b2 = (float)beta2, omb2 = (float)(1.0 - beta2), ep = (float)eps, wd = (float)weight_decay;
+  const int sk = skip_nonfinite ? 1 : 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (njobs <= 96)
+    adam_scaled_launch<96>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, clip_state, sk, s);
+  else if (njobs <= 224)
+    adam_scaled_launch<224>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, clip_state, sk, s);
+  else
+    adam_scaled_launch<448>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, clip_state, sk, s);
   return lic_check_launch();
 }

@@ -8,6 +8,16 @@ parameter, created by torch's own `_init_group`), so checkpoints move freely bet
 the host from the step count (torch's default, non-capturable path); anything else -- amsgrad, maximize,
 capturable / differentiable, non-fp32 or CPU parameters, parameters without gradients, step counts that differ
 between parameters -- falls through to torch's implementation for that call.
+
+`FusedAdam(..., max_grad_norm=m, skip_nonfinite=True)` adds what `torch.nn.utils.clip_grad_norm_(params, m)` in
+front of `step()` does, and a guard against a non-finite step, without the foreach launches and the ~240 host-side
+calls of that recipe: `lic_grad_norm_partial` per group and one `lic_grad_norm_finish` leave the global L2 norm, the
+clipping coefficient and a not-finite flag in 4 dwords of device memory, and `lic_adam_run_scaled` reads them there
+-- the host never waits for the norm.  `grad_norm()` is the last step's norm (a device scalar), `skipped_steps()`
+the number of steps the guard dropped.  ONE deviation from GradScaler-style skipping: a skipped fused step leaves
+parameters and moments untouched but still advances the step count, because the bias corrections are computed on
+the host from that count and the host does not know the flag.  (The fallback path reads the norm back anyway and
+skips before torch's step, so there the count stays.)  `grad_norm(parameters)` is the norm alone, for any optimizer.
 """
 from __future__ import annotations
 
@@ -22,8 +32,18 @@ from . import functional as F_
 class FusedAdam(torch.optim.Adam):
     MAX_TENSORS = 448   # per parameter group (include/lic.h: lic_adam_run)
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, **kw):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
+                 max_grad_norm=None, skip_nonfinite=False, **kw):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
+        # global-norm clipping over ALL groups (torch.nn.utils.clip_grad_norm_'s max_norm) / leave the step out when
+        # the norm is not finite.  Attributes of the optimizer, not of param_groups: the state dict stays torch's
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self._clip_state = None   # 4 dwords on the device: norm, coefficient, not-finite flag, skipped steps (lic.h)
+        self._partials = None     # one double per block of every group (lic_grad_norm_partial), allocated per plan
+        self._last_norm = None    # what grad_norm() returns
+        self._skipped_host = 0    # steps skipped on the fallback path
         self._tables = {}   # group index -> (key, device job table, njobs, blocks, ctypes array of gradient pointers)
         self._fast = None   # the last planned step, re-used while nothing it depends on changed
         self._t0, self._lazy = 0.0, 0   # step count the plan started from / fast steps not yet written to the state
@@ -40,6 +60,61 @@ class FusedAdam(torch.optim.Adam):
                     g.is_sparse or not p.is_contiguous() or not g.is_contiguous():
                 return False
         return dev.index == torch.cuda.current_device()
+
+    def _clipping(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _clip_prologue(self, lib, tabs):
+        """the norm of the gradients `tabs` (one job table per group) point at -> self._clip_state, no read-back"""
+        dev = tabs[0][1].device
+        total = sum(t[3] for t in tabs)
+        if self._clip_state is None or self._clip_state.device != dev:
+            self._skipped_host = self.skipped_steps()
+            self._clip_state = torch.zeros(4, dtype=torch.float32, device=dev)
+        if self._partials is None or self._partials.numel() != total or self._partials.device != dev:
+            self._partials = torch.empty(total, dtype=torch.float64, device=dev)
+        stream, at = F_._stream(), 0
+        for _, dev_tab, njobs, blocks, gptrs in tabs:
+            L.check(lib.lic_grad_norm_partial(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs,
+                                              C.c_void_p(self._partials.data_ptr() + 8 * at), stream),
+                    "lic_grad_norm_partial")
+            at += blocks
+        max_norm = float("inf") if self.max_grad_norm is None else float(self.max_grad_norm)
+        L.check(lib.lic_grad_norm_finish(C.c_void_p(self._partials.data_ptr()), total, max_norm,
+                                         int(self.skip_nonfinite), C.c_void_p(self._clip_state.data_ptr()), stream),
+                "lic_grad_norm_finish")
+        self._last_norm = self._clip_state[0]
+
+    def _launch(self, lib, group, tab, t, clip):
+        _, dev_tab, njobs, blocks, gptrs = tab
+        beta1, beta2 = group["betas"]
+        if not clip:
+            L.check(lib.lic_adam_run(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]),
+                                     float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
+                                     1.0 - beta1 ** t, 1.0 - beta2 ** t, F_._stream()), "lic_adam_run")
+        else:
+            L.check(lib.lic_adam_run_scaled(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]),
+                                            float(beta1), float(beta2), float(group["eps"]),
+                                            float(group["weight_decay"]), 1.0 - beta1 ** t, 1.0 - beta2 ** t,
+                                            C.c_void_p(self._clip_state.data_ptr()), int(self.skip_nonfinite),
+                                            F_._stream()), "lic_adam_run_scaled")
+
+    def grad_norm(self):
+        """global L2 norm of the gradients of the last step(): a 0-dim tensor on the parameters' device (a view of the
+        kernels' state after a fused step: reading it is the caller's synchronisation, this call makes none)"""
+        if not self._clipping():
+            raise RuntimeError("gradient clipping is off: construct FusedAdam with max_grad_norm= and / or "
+                               "skip_nonfinite=True to have the norm computed")
+        if self._last_norm is None:
+            raise RuntimeError("grad_norm() is the norm of the last step(): no step has been taken yet")
+        return self._last_norm
+
+    def skipped_steps(self):
+        """number of steps skip_nonfinite dropped so far (one read-back of 4 bytes)"""
+        n = self._skipped_host
+        if self._clip_state is not None:
+            n += int(self._clip_state.view(torch.int32)[3])
+        return n
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -69,15 +144,16 @@ class FusedAdam(torch.optim.Adam):
                     break
             if ok:
                 lib = L.load()
+                clip = self._clipping()
                 for group, plist, params, hyper, (tab, moments, steps) in fast:
-                    _, dev_tab, njobs, blocks, gptrs = tab
+                    gptrs = tab[4]
                     for i, p in enumerate(params):
                         gptrs[i] = p.grad.data_ptr()
-                    t = self._t0 + self._lazy + 1.0
-                    beta1, beta2 = group["betas"]
-                    L.check(lib.lic_adam_run(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]),
-                                             float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                                             1.0 - beta1 ** t, 1.0 - beta2 ** t, F_._stream()), "lic_adam_run")
+                if clip:    # (the norm is global: every group's partial sums before the first update)
+                    self._clip_prologue(lib, [f[4][0] for f in fast])
+                t = self._t0 + self._lazy + 1.0
+                for group, plist, params, hyper, (tab, moments, steps) in fast:
+                    self._launch(lib, group, tab, t, clip)
                     torch.autograd.graph.increment_version(moments)
                 # the per-parameter `step` tensors of the state (CPU scalars, one per parameter: bumping them is ~240
                 # small ATen calls per step) are brought up to date lazily: _flush_steps() before anything reads them
@@ -96,7 +172,8 @@ class FusedAdam(torch.optim.Adam):
                 return self._fallback(loss)
             plans.append((gi, group, params, grads, exp_avgs, exp_avg_sqs, steps))
         lib = L.load()
-        fast = []
+        clip = self._clipping()
+        tabs = []
         for gi, group, params, grads, exp_avgs, exp_avg_sqs, steps in plans:
             key = tuple((p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) for p, m, v in zip(params, exp_avgs, exp_avg_sqs))
             tab = self._tables.get(gi)
@@ -109,14 +186,15 @@ class FusedAdam(torch.optim.Adam):
                     raise L.LicError(f"lic_adam_plan failed: {blocks}")
                 dev_tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(params[0].device)
                 tab = self._tables[gi] = (key, dev_tab, len(params), int(blocks), (C.c_void_p * len(params))())
-            _, dev_tab, njobs, blocks, gptrs = tab
+            gptrs = tab[4]
             for i, g in enumerate(grads):       # gradients are fresh tensors every step: their addresses go along
                 gptrs[i] = g.data_ptr()         # as kernel arguments (copied at launch)
-            t = float(steps[0]) + 1.0
-            beta1, beta2 = group["betas"]
-            L.check(lib.lic_adam_run(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]), float(beta1),
-                                     float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                                     1.0 - beta1 ** t, 1.0 - beta2 ** t, F_._stream()), "lic_adam_run")
+            tabs.append(tab)
+        if clip:
+            self._clip_prologue(lib, tabs)
+        fast = []
+        for (gi, group, params, grads, exp_avgs, exp_avg_sqs, steps), tab in zip(plans, tabs):
+            self._launch(lib, group, tab, float(steps[0]) + 1.0, clip)
             for s in steps:     # (only once the launch went out: a refused launch leaves the state untouched)
                 s += 1
             # the kernel wrote through raw pointers: tell autograd (and prep.StepPrep, which re-derives the packed
@@ -173,5 +251,66 @@ class FusedAdam(torch.optim.Adam):
         """torch's own update for this call (state was initialised by the same `_init_group`)"""
         self._flush_steps()
         self._fast = None
+        if self._clipping():
+            params = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+            if self.max_grad_norm is not None:
+                norm = torch.nn.utils.clip_grad_norm_(params, float(self.max_grad_norm))
+            else:
+                norm = torch.nn.utils.get_total_norm([p.grad for p in params])
+            self._last_norm = norm
+            if self.skip_nonfinite and not bool(torch.isfinite(norm)):   # (the one synchronisation of this path)
+                self._skipped_host += 1
+                return loss
         super().step()
         return loss
+
+
+_norm_tables = {}   # (device, tensor lengths) -> [(device job table, njobs, blocks)] of grad_norm()
+
+
+def grad_norm(parameters):
+    """Global L2 norm of the gradients of `parameters` (fp32 CUDA tensors on the current device, contiguous gradients;
+    parameters without a gradient are left out, as torch.nn.utils.clip_grad_norm_ does): the two launches FusedAdam's
+    clipping takes, for logging the norm under any optimizer.  Returns a 0-dim device tensor, no synchronisation."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        raise ValueError("grad_norm: no parameter has a gradient")
+    dev = grads[0].device
+    for g in grads:
+        if not g.is_cuda or g.device != dev or g.dtype != torch.float32 or g.is_sparse or not g.is_contiguous() or \
+                g.numel() == 0:
+            raise ValueError("grad_norm: gradients must be non-empty contiguous fp32 CUDA tensors on one device")
+    if dev.index != torch.cuda.current_device():
+        raise ValueError("grad_norm: the gradients are not on the current device")
+    lib = L.load()
+    key = (dev.index, tuple(g.numel() for g in grads))
+    tabs = _norm_tables.get(key)
+    if tabs is None:
+        tabs = []
+        for at in range(0, len(grads), FusedAdam.MAX_TENSORS):    # (one kernel-argument block per launch)
+            chunk = grads[at:at + FusedAdam.MAX_TENSORS]
+            arr = (L.AdamJob * len(chunk))()
+            for j, g in zip(arr, chunk):     # only the lengths are read: lic_adam_plan wants the pointers non-null
+                j.p = j.m = j.v = g.data_ptr()
+                j.n = g.numel()
+            blocks = lib.lic_adam_plan(arr, len(chunk))
+            if blocks <= 0:
+                raise L.LicError(f"lic_adam_plan failed: {blocks}")
+            tabs.append((torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), len(chunk), int(blocks)))
+        if len(_norm_tables) >= 8:
+            _norm_tables.clear()
+        _norm_tables[key] = tabs
+    total = sum(t[2] for t in tabs)
+    partials = torch.empty(total, dtype=torch.float64, device=dev)
+    state = torch.zeros(4, dtype=torch.float32, device=dev)
+    stream, at, g0 = F_._stream(), 0, 0
+    for dev_tab, njobs, blocks in tabs:
+        gptrs = (C.c_void_p * njobs)(*[g.data_ptr() for g in grads[g0:g0 + njobs]])
+        L.check(lib.lic_grad_norm_partial(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs,
+                                          C.c_void_p(partials.data_ptr() + 8 * at), stream), "lic_grad_norm_partial")
+        at, g0 = at + blocks, g0 + njobs
+    L.check(lib.lic_grad_norm_finish(C.c_void_p(partials.data_ptr()), total, float("inf"), 0,
+                                     C.c_void_p(state.data_ptr()), stream), "lic_grad_norm_finish")
+    return state[0]

@@ -13,6 +13,10 @@ same tags from device-side summaries (`data.tensor_stats` -> `lic_tensor_stats`:
 min, max and a 64-bin histogram; 6 doubles + 64 counters cross PCIe per tag).  Image / figure logging
 (:219-345) is not reproduced.  Scalars go to a TensorBoard SummaryWriter when tensorboard is
 installed, otherwise to <log_dir>/scalars.jsonl (summaries as JSON objects).
+Added to the reference's contract as trailing keyword arguments: `clip_max_norm` (global-norm gradient clipping, the
+`torch.nn.utils.clip_grad_norm_(model.parameters(), clip_max_norm)` of the usual recipe for these models) and
+`skip_nonfinite` (a step whose gradient norm is not finite is left out); `train/grad_norm` and
+`train/skipped_steps` are logged every `log_interval`.
 """
 from __future__ import annotations
 
@@ -69,7 +73,8 @@ class Trainer:
     def __init__(self, model, optimizer, train_loader, val_loader=None, rd_loss=None, lambda_val=0.005,
                  scheduler=None, max_steps=10000, resume=False, log_interval=None, img_interval=None,
                  val_interval=None, log_dir="runs/experiment", checkpoint_path="./checkpoints/checkpoint.pth",
-                 device="cuda", distributed: Optional[bool] = None, writer=None, step_plan: bool = False):
+                 device="cuda", distributed: Optional[bool] = None, writer=None, step_plan: bool = False,
+                 clip_max_norm: Optional[float] = None, skip_nonfinite: bool = False):
         if rd_loss is None:
             raise ValueError("You must provide a rate-distortion loss function (`rd_loss`)")
         self.device = device
@@ -109,6 +114,17 @@ class Trainer:
         self._plan = None
         if self.step_plan and self.reducer is not None:
             raise ValueError("step_plan replays one GPU's step; data-parallel training uses the eager step")
+        # gradient clipping / non-finite guard: a FusedAdam does both inside its own launches (optim.py: no read-back,
+        # no extra pass over the gradients); any other optimizer gets torch's clip_grad_norm_ in front of its step.
+        # Either way after the reducer, so every rank clips the same averaged gradient; the optimizer step is outside
+        # the step plan, so step_plan=True needs nothing of its own.
+        from .optim import FusedAdam
+        self.clip_max_norm, self.skip_nonfinite = clip_max_norm, bool(skip_nonfinite)
+        self._clip = clip_max_norm is not None or self.skip_nonfinite
+        self._fused_clip = self._clip and isinstance(optimizer, FusedAdam)
+        if self._fused_clip:
+            optimizer.max_grad_norm, optimizer.skip_nonfinite = clip_max_norm, self.skip_nonfinite
+        self._grad_norm, self._skipped = None, 0   # (of the torch path)
 
     # -- checkpointing: the reference's file format (Trainer.py:52-71) ---------------------------
     def _checkpoint_state(self):
@@ -136,6 +152,28 @@ class Trainer:
         print(f"[trainer] resumed from {self.checkpoint_path} at step {self.step}")
 
     # -- the step (Trainer.py:78-86) -------------------------------------------------------------
+    def _optimizer_step(self):
+        if self._clip and not self._fused_clip:
+            params = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
+            if self.clip_max_norm is not None:
+                self._grad_norm = torch.nn.utils.clip_grad_norm_(params, float(self.clip_max_norm))
+            else:
+                self._grad_norm = torch.nn.utils.get_total_norm([p.grad for p in params])
+            if self.skip_nonfinite and not bool(torch.isfinite(self._grad_norm)):   # (one synchronisation)
+                self._skipped += 1
+                return
+        self.optimizer.step()
+
+    def _log_clipping(self):
+        """train/grad_norm (and train/skipped_steps) of the step just taken: the only steps that read them back"""
+        if not self._clip or self.writer is None or not self.log_interval or self.step % self.log_interval != 0:
+            return
+        norm = self.optimizer.grad_norm() if self._fused_clip else self._grad_norm
+        self.writer.add_scalar("train/grad_norm", float(norm), self.step)
+        if self.skip_nonfinite:
+            skipped = self.optimizer.skipped_steps() if self._fused_clip else self._skipped
+            self.writer.add_scalar("train/skipped_steps", skipped, self.step)
+
     def _planned_step(self, imgs):
         from .loss import _KEYS
         from .plan import StepPlan
@@ -144,7 +182,7 @@ class Trainer:
         if imgs.shape != self._plan.x.shape:
             return None
         model_out, res = self._plan.step(imgs)
-        self.optimizer.step()
+        self._optimizer_step()
         results = dict(res)
         buf = results.pop('_buffer', None)
         if buf is not None:   # the plain numbers the eager rd_loss returns, from one device-to-host copy
@@ -165,7 +203,7 @@ class Trainer:
         results['loss'].backward()
         if self.reducer is not None:
             self.reducer.finish()
-        self.optimizer.step()
+        self._optimizer_step()
         return model_out, results
 
     def train(self):
@@ -173,6 +211,7 @@ class Trainer:
             imgs = self._next_batch()
             model_out, results = self.train_step(imgs)
             self._log_scalars(results)
+            self._log_clipping()
             if self.writer is not None and self.log_interval and self.step % self.log_interval == 0 and \
                     self.log_statistics and self._has_device_outputs(model_out):
                 self._log_histograms(model_out)
