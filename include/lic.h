@@ -368,7 +368,10 @@ int lic_quantize_bf16(const float* v, const float* u, float* out, void* v_bf16, 
  *   lic_gdn_bwd: t = dL/dnorm (written: the d-gamma / d-beta launches read it),
  *                dx = g * rsqrt(norm) + 2 x (t . gamma_eff)  (inverse: g * sqrt(norm) + ...)
  *                gamma_packed = lic_pack_weight(gamma_eff, taps=1, K=C, N=C, s_k=C, s_n=1)
- * Same chunk / k order as lic_igemm's prologue-1 / prologue-2 route, which serves other channel counts.
+ * Same chunk / k order as lic_igemm's prologue-1 / prologue-2 route, which serves other channel counts: norm, y, t and
+ * the pooled sums of the backward are bitwise that route's.  dx is not: lic_gdn_bwd forms g f + 2 x (t . gamma_eff) with
+ * one fused multiply-add, the generic 16-byte epilogue rounds the product first (a last-bit difference in about one
+ * element in seven).
  * ------------------------------------------------------------------------------------------ */
 int lic_gdn_supported(int32_t C);
 int lic_gdn_fwd(const float* x, const float* gammaT_packed, const float* beta_eff, const float* res, float* y,
