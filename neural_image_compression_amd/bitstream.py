@@ -1,0 +1,160 @@
+"""The self-describing container of `ContextCodec.compress_image` (host only, no torch): one byte string per batch
+of images of any size.  Three formats, one per (coder, grouped) pair of the y streams; `_FORMATS` below describes
+them, `_pack` writes and `_unpack` reads all three, and the six public functions are their wrappers.
+
+Every format, little endian:
+  magic (8 bytes) | uint32 family (1 = JointAutoregressiveHierarchical, 2 = HierarchicalMixtureResidual)
+  | uint32 M, K | int32 z_lo | uint32 z_S, y_W, B, H, W, top, left | uint32 z-stream length | [uint32 lanes]
+  | image table: B rows | block table: B*G rows, image-major (row b * G + g)
+  | z stream | for every block: its y stream, then its escape list (uint32 each) | uint32 CRC-32 of all before it
+The padded size is the next multiple of 64 of (H, W); the latent is [B, M, Hp/16, Wp/16], z [B, M, Hp/64, Wp/64].
+
+  magic     coder  lanes word        image table row   block table row                    blocks per image
+  LICBITS1  range  absent            none              y length, symbol CRC-32            1
+  LICBITS2  rans   64                none              y length, symbol CRC-32, escapes   1
+  LICBITS3  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G ("rANS-64 x G", `rans_deal`)
+
+"symbol CRC-32" is `compress`'s y_crc32 of that image's latent symbols, "escapes" the number of uint32 in the block's
+escape list.  `lanes` is the interleaving of an image's y streams.  A LICBITS2 reader refuses any value but 64: wider
+interleaving has LICBITS3, whose tables have another shape.  A LICBITS3 reader takes the multiples of 64 up to 512
+(64 is legal there, though `compress_image` writes LICBITS2 for one group) and refuses a sub-stream shorter than its 64
+states or of odd length.
+"""
+from __future__ import annotations
+
+import struct
+import zlib
+from itertools import accumulate
+from typing import Dict
+
+import numpy as np
+
+RANS_LANES = 64
+RANS_MAX_GROUPS = 8                              # sub-streams per image of the "rANS-64 x G" format
+
+
+class CodecError(RuntimeError):
+    pass
+
+
+def _groups(G) -> int:
+    """G as an int in 1..RANS_MAX_GROUPS, or CodecError"""
+    if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or not 1 <= int(G) <= RANS_MAX_GROUPS:
+        raise CodecError(f"groups = {G!r}: expected an integer from 1 to {RANS_MAX_GROUPS}")
+    return int(G)
+
+
+BITSTREAM_FAMILIES = {"JointAutoregressiveHierarchical": 1, "HierarchicalMixtureResidual": 2}
+BITSTREAM_MAGIC, BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_GROUPED = b"LICBITS1", b"LICBITS2", b"LICBITS3"
+_BITS_FIELDS = ("family", "M", "K", "z_lo", "z_S", "y_W", "B", "H", "W", "top", "left")
+_BITS_HEAD, _BITS_HEAD_RANS = struct.Struct("<8s3Ii8I"), struct.Struct("<8s3Ii9I")          # without / with `lanes`
+# (coder, more than one group) -> (magic, header, image table columns, block table columns, what `_pack` expects)
+_FORMATS = {
+    ("range", False): (BITSTREAM_MAGIC, _BITS_HEAD, (), ("len", "crc"), "one y stream and one checksum per image"),
+    ("rans", False): (BITSTREAM_MAGIC_RANS, _BITS_HEAD_RANS, (), ("len", "crc", "esc"),
+                      "one y stream, one escape list and one checksum per image"),
+    ("rans", True): (BITSTREAM_MAGIC_GROUPED, _BITS_HEAD_RANS, ("crc",), ("len", "esc"),
+                     "one sub-stream and one escape list per image and group, one checksum per image"),
+}
+_FORMAT_OF_MAGIC = {f[0]: key for key, f in _FORMATS.items()}
+
+
+def _pack(fmt, head: Dict, z_bytes: bytes, ys, escs, crcs, G: int = 1, lanes: int = None) -> bytes:
+    """`head`: the _BITS_FIELDS; B * G y streams and escape lists (bytes; None where the format has none), image-major,
+    and one symbol checksum per image"""
+    magic, st, img_cols, blk_cols, expects = _FORMATS[fmt]
+    B = int(head["B"])
+    escs = [b""] * len(ys) if escs is None else escs
+    if len(ys) != B * G or len(escs) != B * G or len(crcs) != B:
+        raise CodecError(expects + " expected")
+    if any(len(e) % 4 for e in escs):
+        raise CodecError("an escape list is not a whole number of uint32")
+    words = (len(z_bytes), RANS_LANES * G if lanes is None else int(lanes))
+    parts = [st.pack(magic, *(int(head[k]) for k in _BITS_FIELDS), *words[:1 + (st is _BITS_HEAD_RANS)])]
+    rows = [{"crc": int(c) & 0xFFFFFFFF} for c in crcs]
+    blocks = [dict(rows[i // G], len=len(s), esc=len(e) // 4) for i, (s, e) in enumerate(zip(ys, escs))]
+    parts += [struct.pack("<%dI" % len(cols), *(r[k] for k in cols)) for cols, t in ((img_cols, rows), (blk_cols, blocks))
+              for r in t]
+    parts += [bytes(z_bytes)] + [bytes(p) for s, e in zip(ys, escs) for p in (s, e)]
+    body = b"".join(parts)
+    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+
+
+def _unpack(fmt, data: bytes):
+    """-> (head dict, z_bytes, [y stream per block], [escape list per block], [symbol checksum per image], G).
+    CodecError, in this order, for a buffer shorter than its header or tables, another magic, a total length that is
+    not the one the header and tables name, a failing CRC-32, a header that cannot be right, and what the format itself
+    refuses (module docstring) -- except that LICBITS3 must know G to find its tables, so its `lanes` rule comes first."""
+    magic, st, img_cols, blk_cols, _ = _FORMATS[fmt]
+    data = bytes(data)
+    if len(data) < st.size + 4:
+        raise CodecError("bitstream is truncated (shorter than its header)")
+    vals = st.unpack_from(data, 0)
+    if vals[0] != magic:
+        raise CodecError(f"not a {magic.decode()} bitstream (bad magic)")
+    head = dict(zip(_BITS_FIELDS, vals[1:12]))
+    z_len, lanes, B, G = vals[12], vals[-1] if st is _BITS_HEAD_RANS else RANS_LANES, head["B"], 1
+    if fmt[1]:
+        if lanes % RANS_LANES or not RANS_LANES <= lanes <= RANS_LANES * RANS_MAX_GROUPS:
+            raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements multiples of "
+                             f"{RANS_LANES} up to {RANS_LANES * RANS_MAX_GROUPS}")
+        G = lanes // RANS_LANES
+    at = st.size
+    if B == 0 or len(data) < at + 4 * (len(img_cols) + len(blk_cols) * G) * B + 4:
+        raise CodecError("bitstream is truncated (per-image table%s)" % ("s" if img_cols else ""))
+    tables = []
+    for cols, n in ((img_cols, B), (blk_cols, B * G)):
+        row = struct.Struct("<%dI" % len(cols))
+        tables.append([dict(zip(cols, row.unpack_from(data, at + row.size * i))) for i in range(n)])
+        at += row.size * n
+    rows, blocks = tables
+    # where the z stream, then every block's y stream and escape list, begin and end
+    cuts = list(accumulate([z_len] + [n for r in blocks for n in (r["len"], 4 * r.get("esc", 0))], initial=at))
+    if len(data) != cuts[-1] + 4:
+        raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
+    _check_crc_and_head(data, head)
+    if not fmt[1] and lanes != RANS_LANES:
+        raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements {RANS_LANES}")
+    if fmt[1] and any(r["len"] < 4 * RANS_LANES or r["len"] % 2 for r in blocks):
+        raise CodecError("bitstream names a sub-stream shorter than its 64 states or of odd length")
+    payload = [data[a:b] for a, b in zip(cuts, cuts[1:])]
+    return head, payload[0], payload[1::2], payload[2::2], [r["crc"] for r in (rows if img_cols else blocks)], G
+
+
+def _check_crc_and_head(data: bytes, head: Dict):
+    """the checks all containers share: the trailing CRC-32 and a header that can be right"""
+    if zlib.crc32(data[:-4]) & 0xFFFFFFFF != struct.unpack_from("<I", data, len(data) - 4)[0]:
+        raise CodecError("bitstream is damaged (CRC-32 mismatch)")
+    if not (head["H"] > 0 and head["W"] > 0 and head["top"] < 64 and head["left"] < 64
+            and head["top"] + head["H"] <= -(-head["H"] // 64) * 64 and head["left"] + head["W"] <= -(-head["W"] // 64) * 64
+            and head["M"] > 0 and head["K"] > 0 and head["z_S"] > 0 and head["y_W"] > 0):
+        raise CodecError("bitstream header is inconsistent")
+
+
+def pack_bitstream(head: Dict, z_bytes: bytes, y_streams, y_crc32) -> bytes:
+    return _pack(("range", False), head, z_bytes, y_streams, None, y_crc32)
+
+
+def unpack_bitstream(data: bytes):
+    """-> (head dict, z_bytes, [y stream per image], [symbol checksum per image])"""
+    head, z_bytes, ys, _, crcs, _ = _unpack(("range", False), data)
+    return head, z_bytes, ys, crcs
+
+
+def pack_bitstream_rans(head: Dict, z_bytes: bytes, y_streams, y_esc, y_crc32, lanes: int = RANS_LANES) -> bytes:
+    return _pack(("rans", False), head, z_bytes, y_streams, y_esc, y_crc32, lanes=lanes)
+
+
+def unpack_bitstream_rans(data: bytes):
+    """-> (head dict, z_bytes, [y stream per image], [escape list per image], [symbol checksum per image])"""
+    return _unpack(("rans", False), data)[:5]
+
+
+def pack_bitstream_grouped(head: Dict, z_bytes: bytes, y_streams, y_esc, y_crc32, groups: int) -> bytes:
+    return _pack(("rans", True), head, z_bytes, y_streams, y_esc, y_crc32, _groups(groups))
+
+
+def unpack_bitstream_grouped(data: bytes):
+    """-> (head dict, z_bytes, [sub-stream per image and group], [escape list likewise], [symbol checksum per image],
+    groups)"""
+    return _unpack(("rans", True), data)

@@ -13,23 +13,23 @@ prior, so it decodes without context) and `decode_y_with_tables` (decodes y from
 used -- the coder's inverse).  `ContextCodec`: the full round trip; its decoder rebuilds the tables from
 already-decoded pixels through the masked 5x5 context model, wavefront by wavefront.
 `ContextCodec.compress_image` / `decompress_image` wrap that round trip, for images of any size, in one
-self-describing byte string (`pack_bitstream`: header, per-image lengths and checksums, streams, CRC-32).
+self-describing byte string: header, per-image lengths and checksums, streams, CRC-32.  bitstream.py holds the three
+containers (LICBITS1/2/3, one per coder and grouping), their one writer and one reader; its names are this module's too.
 
 `ContextCodec(..., coder="rans")` codes the y streams with the 64-lane interleaved rANS coder of lic_codec.h
-instead: its decoder is a device kernel (`lic_rans_decode_step`), so the decode loop has no host in it; the
-container of that coder is `pack_bitstream_rans` (magic LICBITS2).  The range coder stays the default and codes z.
+instead: its decoder is a device kernel (`lic_rans_decode_step`), so the decode loop has no host in it.  The range
+coder stays the default and codes z.
 With `encoder="device"` that coder's encoder runs on the device as well (`lic_rans_encode_pick` + `lic_rans_encode`):
 the same bytes, and no table is copied to the host.
 
 `ContextCodec(..., coder="rans", groups=G)` deals every image's rounds to G independent rANS-64 sub-streams
 (`rans_deal`: round r of a step goes to sub-stream r % G), so G waves per image decode and encode them
 (`lic_rans_decode_step_groups`, `lic_rans_encode_groups`); each sub-stream costs its 256 bytes of states.  G = 1,
-the default, is the format above; the container of G > 1 is `pack_bitstream_grouped` (magic LICBITS3).
+the default, is the format above.
 """
 from __future__ import annotations
 
 import ctypes as C
-import struct
 import zlib
 import os
 from typing import Dict
@@ -39,12 +39,13 @@ import torch
 
 from . import _lib as L
 from . import functional as F_
+from .bitstream import (BITSTREAM_FAMILIES, BITSTREAM_MAGIC, BITSTREAM_MAGIC_GROUPED,  # noqa: F401
+                        BITSTREAM_MAGIC_RANS, RANS_LANES, RANS_MAX_GROUPS, CodecError, _BITS_FIELDS, _BITS_HEAD,
+                        _BITS_HEAD_RANS, _FORMAT_OF_MAGIC, _FORMATS, _check_crc_and_head, _groups, _pack, _unpack,
+                        pack_bitstream, pack_bitstream_grouped, pack_bitstream_rans, unpack_bitstream,
+                        unpack_bitstream_grouped, unpack_bitstream_rans)
 
 _CODEC = None
-
-
-class CodecError(RuntimeError):
-    pass
 
 
 def _codec():
@@ -63,6 +64,10 @@ def _codec():
         lib.lic_rc_ideal_bits.restype = C.c_double
         lib.lic_rc_ideal_bits.argtypes = [u32p, i32p, C.c_int32, i32p, C.c_int64]
         lib.lic_codec_version.restype = C.c_int
+        lib.lic_rc_decoder_new.restype, lib.lic_rc_decoder_new.argtypes = C.c_void_p, [u8p, C.c_size_t]
+        lib.lic_rc_decoder_next.restype = C.c_int
+        lib.lic_rc_decoder_next.argtypes = [C.c_void_p, u32p, i32p, C.c_int32, C.c_int64, i32p]
+        lib.lic_rc_decoder_free.argtypes = [C.c_void_p]
         i64p, szp = C.POINTER(C.c_int64), C.POINTER(C.c_size_t)
         lib.lic_rans_bound.restype, lib.lic_rans_bound.argtypes = C.c_size_t, [C.c_int64]
         lib.lic_rans_encode.restype = C.c_int
@@ -120,11 +125,9 @@ def rc_ideal_bits(tables: np.ndarray, idx: np.ndarray, table_of: np.ndarray = No
 
 
 # ---- the interleaved rANS coder of the y streams (lic_codec.h "rANS-64") ---------------------
-RANS_LANES = 64
 CODERS = ("range", "rans")
 ENCODERS = ("host", "device")
 RANS_MAX_W = 64                                  # widest window lic_rans_decode_step / lic_rans_encode_pick take
-RANS_MAX_GROUPS = 8                              # sub-streams per image of the "rANS-64 x G" format
 
 
 def rans_encode(tables: np.ndarray, idx: np.ndarray, step_len) -> tuple:
@@ -161,13 +164,6 @@ def rans_decode(data: bytes, esc: bytes, tables: np.ndarray, step_len) -> np.nda
     if rc != 0:
         raise CodecError(f"lic_rans_decode failed with status {rc}")
     return out
-
-
-def _groups(G) -> int:
-    """G as an int in 1..RANS_MAX_GROUPS, or CodecError"""
-    if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or not 1 <= int(G) <= RANS_MAX_GROUPS:
-        raise CodecError(f"groups = {G!r}: expected an integer from 1 to {RANS_MAX_GROUPS}")
-    return int(G)
 
 
 def rans_deal(step_len, G: int):
@@ -247,6 +243,20 @@ def gmm_tables(act: torch.Tensor, M: int, K: int, W: int):
     return center, tables
 
 
+def _state_blocks(d_state: torch.Tensor, G: int, problem):
+    """The one read-back of a rANS kernel's state blocks [blocks][RANS_STATE_WORDS] (lic.h: 64 coder states, word
+    count, escape count, error word), image-major with G blocks per image -> [(states uint32 [64], words, escapes)].
+    `problem(i, states, words, escapes, error word)` says what is wrong with block i, if anything: the first such
+    block raises CodecError, named by its image."""
+    blocks = []
+    for i, row in enumerate(d_state.cpu().numpy().view(np.uint32)):
+        blocks.append((row[:RANS_LANES], int(row[RANS_LANES]), int(row[RANS_LANES + 1])))
+        what = problem(i, *blocks[-1], int(row[RANS_LANES + 2]))
+        if what:
+            raise CodecError(f"image {i // G}: {what}")
+    return blocks
+
+
 class LatentCodec:
     """compress / decompress the (y, z) latents of a JointAutoregressiveHierarchical /
     HierarchicalMixtureResidual model.  `z_lo`, `z_S`: symbol window of the hyper-latent tables;
@@ -261,10 +271,7 @@ class LatentCodec:
         out = m.analysis_hyperprior(x, training=False, with_packed_params=True)
         y_in, z_in = out["y_in"], out["z_in"]                      # NCHW-logical, NHWC-physical, integer valued
         B, M, h, w = y_in.shape
-        zt = factorized_tables(m.factorized_entropy_model, self.z_lo, self.z_S).cpu().numpy().view(np.uint32)
-        z_nhwc = z_in.permute(0, 2, 3, 1).contiguous()
-        z_idx = (z_nhwc.round().to(torch.int32) - self.z_lo).cpu().numpy().ravel()
-        z_tab = np.tile(np.arange(M, dtype=np.int32), z_idx.size // M)
+        zt, z_idx, z_tab = self._z_symbols(z_in)
         z_bytes = rc_encode(zt, z_idx, z_tab)
         act = out["_act"]
         center, yt = gmm_tables(act, M, m.K, self.y_W)
@@ -281,15 +288,27 @@ class LatentCodec:
                 "bpp_est_z": float(-out["logp_z"].double().sum() / np.log(2.0) / npix),
                 "y_in": y_in, "z_in": z_in, "_y_tables": yt_h, "_y_center": center}
 
+    def _z_tables(self, n: int):
+        """(factorised tables [M][z_S+1] uint32, table of each of the n z symbols: pixel by pixel, channel by channel)"""
+        zt = factorized_tables(self.model.factorized_entropy_model, self.z_lo, self.z_S).cpu().numpy().view(np.uint32)
+        return zt, np.tile(np.arange(len(zt), dtype=np.int32), n // len(zt))
+
+    def _z_symbols(self, z_in: torch.Tensor):
+        """z_in [B,M,h4,w4] -> `rc_encode`'s arguments: (tables, symbol - z_lo in coding order, table of each symbol)"""
+        zt, z_tab = self._z_tables(z_in.numel())
+        return zt, (z_in.permute(0, 2, 3, 1).contiguous().round().to(torch.int32) - self.z_lo).cpu().numpy().ravel(), z_tab
+
+    def encode_z(self, z_in: torch.Tensor) -> bytes:
+        return rc_encode(*self._z_symbols(z_in))
+
     @torch.no_grad()
     def decompress_z(self, z_bytes: bytes, z_shape) -> torch.Tensor:
         """The hyper-latent: parameter-free prior, decodes in one pass.  Returns z_in [B,M,h4,w4]."""
-        m = self.model
         B, M, h4, w4 = z_shape
-        dev = next(m.parameters()).device
-        zt = factorized_tables(m.factorized_entropy_model, self.z_lo, self.z_S).cpu().numpy().view(np.uint32)
+        dev = next(self.model.parameters()).device
         n = B * M * h4 * w4
-        idx = rc_decode(z_bytes, zt, n, np.tile(np.arange(M, dtype=np.int32), n // M))
+        zt, z_tab = self._z_tables(n)
+        idx = rc_decode(z_bytes, zt, n, z_tab)
         z = torch.from_numpy((idx + self.z_lo).astype(np.float32)).view(B, h4, w4, M).to(dev)
         return z.permute(0, 3, 1, 2)
 
@@ -309,15 +328,8 @@ class _StreamDecoder:
     """lic_rc_decoder_* wrapper (one per image stream)."""
 
     def __init__(self, data: bytes):
-        lib = _codec()
-        lib.lic_rc_decoder_new.restype = C.c_void_p
-        lib.lic_rc_decoder_new.argtypes = [C.POINTER(C.c_uint8), C.c_size_t]
-        lib.lic_rc_decoder_next.restype = C.c_int
-        lib.lic_rc_decoder_next.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_int32,
-                                            C.c_int64, C.POINTER(C.c_int32)]
-        lib.lic_rc_decoder_free.argtypes = [C.c_void_p]
         self._buf = np.frombuffer(data, np.uint8).copy()
-        self._h = lib.lic_rc_decoder_new(_p(self._buf, C.c_uint8), self._buf.size)
+        self._h = _codec().lic_rc_decoder_new(_p(self._buf, C.c_uint8), self._buf.size)
         if not self._h:
             raise CodecError("lic_rc_decoder_new failed")
 
@@ -461,9 +473,7 @@ class ContextCodec:
         out = m.analysis_hyperprior(x, training=False)
         y_in, z_in = out["y_in"].contiguous(), out["z_in"]
         B, M, h, w = y_in.shape
-        zt = factorized_tables(m.factorized_entropy_model, self.z_lo, self.z_S).cpu().numpy().view(np.uint32)
-        z_idx = (z_in.permute(0, 2, 3, 1).contiguous().round().to(torch.int32) - self.z_lo).cpu().numpy().ravel()
-        z_bytes = rc_encode(zt, z_idx, np.tile(np.arange(M, dtype=np.int32), z_idx.size // M))
+        z_bytes = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in)
         psi = m.hyper_decoder(z_in).float()
         psi_px = psi.permute(0, 2, 3, 1).reshape(B * h * w, -1, 1, 1).contiguous()
         center, tables = self._params_at(self._windows_all(y_in), psi_px, self._prepack())
@@ -542,17 +552,14 @@ class ContextCodec:
                                                F_._ptr(words), slot, F_._ptr(esc), cap, F_._ptr(state), F_._stream()),
                     "lic_rans_encode_groups")
             state[::G, RANS_LANES + 2] |= picked[:, RANS_LANES + 2]
-        st = state.cpu().numpy().view(np.uint32)                                  # the one read-back that waits
-        for i in range(B * G):
-            if st[i, RANS_LANES + 2] != 0:
-                raise CodecError(f"image {i // G}: the rANS encoder met a malformed table, a pixel index outside the "
-                                 f"image or step lengths that do not add up (error word {int(st[i, RANS_LANES + 2])})")
+        blocks = _state_blocks(state, G, lambda i, states, nw, ne, err: err and (
+            "the rANS encoder met a malformed table, a pixel index outside the image or step lengths that do not add up "
+            f"(error word {err})"))                                               # the one read-back that waits
         streams, escs = [], []
-        for i in range(B * G):
-            nw, ne = int(st[i, RANS_LANES]), int(st[i, RANS_LANES + 1])
+        for i, (states, nw, ne) in enumerate(blocks):
             if 2 * nw > slot or ne > cap:
                 raise CodecError(f"image {i // G}: the rANS encoder reports impossible counts ({nw} words, {ne} escapes)")
-            streams.append(st[i, :RANS_LANES].astype("<u4").tobytes() + words[i, slot - 2 * nw:].cpu().numpy().tobytes())
+            streams.append(states.astype("<u4").tobytes() + words[i, slot - 2 * nw:].cpu().numpy().tobytes())
             escs.append(esc[i, :ne].cpu().numpy().view(np.uint32).astype("<u4").tobytes())
         return streams, escs
 
@@ -564,62 +571,72 @@ class ContextCodec:
         z_hat = LatentCodec(m, self.z_lo, self.z_S, self.y_W).decompress_z(strings["z"], z_shape)
         z_hat = z_hat.contiguous(memory_format=torch.channels_last)
         psi = m.hyper_decoder(z_hat).float()
-        layers = self._prepack()
         p = self.pad
-        S1 = 2 * self.y_W + 2
         # decoded latents, pixel-major, inside a zero frame
         ypad = torch.zeros((B, h + 2 * p, w + 2 * p, M), device=dev, dtype=torch.float32)
-        psi_h = psi.permute(0, 2, 3, 1).contiguous()                              # [B, h, w, 2M]
-        steps = self._wavefront(h, w)
-        nmax = max(len(ii) for ii, _ in steps)
-        # flat indices of every step's context windows / own pixels, uploaded once: one gather per step
-        Wp = w + 2 * p
-        tr = np.array([r for (r, _) in self.taps]), np.array([c for (_, c) in self.taps])
-        win_idx = torch.from_numpy(np.concatenate(
-            [((ii[:, None] + tr[0][None, :]) * Wp + jj[:, None] + tr[1][None, :]).ravel() for ii, jj in steps])).to(dev)
-        own_idx = torch.from_numpy(np.concatenate([(ii + p) * Wp + jj + p for ii, jj in steps])).to(dev)
-        psi_idx = torch.from_numpy(np.concatenate([ii * w + jj for ii, jj in steps])).to(dev)
         yflat = ypad.view(B, -1, M)
-        psi_flat = psi_h.view(B, h * w, -1)
-        nt = len(self.taps)
+        steps = self._wavefront(h, w)
+        front = self._step_front_end(steps, yflat, psi)
         coder = strings.get("coder", "range")
         if coder not in CODERS:
             raise CodecError(f"unknown coder {coder!r} in the strings")
         if coder == "rans":
-            self._decode_y_rans(strings, steps, layers, yflat, psi_flat, win_idx, own_idx, psi_idx)
+            self._decode_y_rans(strings, front, yflat)
             return self._finish(strings, ypad, z_hat, shape)
         pin = dev.type == "cuda"
+        nmax, S1 = max(len(ii) for ii, _ in steps), 2 * self.y_W + 2
         tabs_host = torch.empty((B, nmax * M, S1), dtype=torch.int32, pin_memory=pin)
         c_host = torch.empty((B, nmax * M), dtype=torch.int32, pin_memory=pin)
         vals_host = torch.empty((B, nmax * M), dtype=torch.float32, pin_memory=pin)
         tabs_np, c_np, vals_np = tabs_host.numpy().view(np.uint32), c_host.numpy(), vals_host.numpy()
         decs = [_StreamDecoder(s) for s in strings["y"]]
         try:
-            off = 0
-            for ii, _ in steps:
-                n = len(ii)
-                win = yflat.index_select(1, win_idx[off * nt:(off + n) * nt])             # [B, n*12, M]
-                center, tables = self._params_at(win.view(B * n, nt * M, 1, 1),
-                                                 psi_flat.index_select(1, psi_idx[off:off + n]).view(B * n, -1, 1, 1),
-                                                 layers)
+            for n, own, center, tables in front:
                 tabs_host[:, :n * M].copy_(tables.view(B, n * M, S1), non_blocking=True)
                 c_host[:, :n * M].copy_(center.view(B, n * M), non_blocking=True)
                 torch.cuda.current_stream().synchronize()
                 for b in range(B):
                     vals_np[b, :n * M] = decs[b].next(tabs_np[b, :n * M], n * M) + c_np[b, :n * M] - self.y_W
-                yflat.index_copy_(1, own_idx[off:off + n], vals_host[:, :n * M].to(dev, non_blocking=True).view(B, n, M))
-                off += n
+                yflat.index_copy_(1, own, vals_host[:, :n * M].to(dev, non_blocking=True).view(B, n, M))
         finally:
             for d in decs:
                 d.close()
         return self._finish(strings, ypad, z_hat, shape)
 
-    def _decode_y_rans(self, strings, steps, layers, yflat, psi_flat, win_idx, own_idx, psi_idx):
-        """The step loop of the "rans" coder: streams, escape lists, state blocks and index arrays go up once, then
-        every step is gather -> per-pixel layers + tables -> lic_rans_decode_step_groups, which writes the decoded
-        values into `yflat` where the next gather reads them.  Nothing in the loop waits for the device; the state
-        blocks (error words, cursors, final states) come back once, after the last step.  One block per image and
-        group (`strings["groups"]`, 1 if absent), image-major; below B counts blocks."""
+    def _step_front_end(self, steps, yflat, psi):
+        """What both decoders do per wavefront step before their coder runs.  Here, once: the layers are packed and the
+        flat indices of every step's context windows / own pixels / psi rows uploaded.  Then, per step of `steps`
+        (`_wavefront`) as the returned generator is advanced: one gather of the windows from `yflat` (the zero-framed
+        latents [B, (h+2p)(w+2p), M], which the coder fills in between), one of `psi` [B, 2M, h, w], the per-pixel
+        layers and the table kernel -> (n pixels, their n indices into yflat, center [B*n, M], tables [B*n*M, S+1])"""
+        B, M, p, nt, dev = yflat.shape[0], yflat.shape[2], self.pad, len(self.taps), yflat.device
+        w = psi.shape[3]
+        layers = self._prepack()
+        psi_flat = psi.permute(0, 2, 3, 1).contiguous().view(B, psi.shape[2] * w, -1)     # [B, h*w, 2M]
+        Wp = w + 2 * p
+        tr = np.array([r for (r, _) in self.taps]), np.array([c for (_, c) in self.taps])
+        win_idx = torch.from_numpy(np.concatenate(
+            [((ii[:, None] + tr[0][None, :]) * Wp + jj[:, None] + tr[1][None, :]).ravel() for ii, jj in steps])).to(dev)
+        own_idx = torch.from_numpy(np.concatenate([(ii + p) * Wp + jj + p for ii, jj in steps])).to(dev)
+        psi_idx = torch.from_numpy(np.concatenate([ii * w + jj for ii, jj in steps])).to(dev)
+
+        def run():
+            off = 0
+            for ii, _ in steps:
+                n = len(ii)
+                win = yflat.index_select(1, win_idx[off * nt:(off + n) * nt])             # [B, n*12, M]
+                yield (n, own_idx[off:off + n]) + self._params_at(
+                    win.view(B * n, nt * M, 1, 1), psi_flat.index_select(1, psi_idx[off:off + n]).view(B * n, -1, 1, 1),
+                    layers)
+                off += n
+        return run()
+
+    def _decode_y_rans(self, strings, front, yflat):
+        """The step loop of the "rans" coder: streams, escape lists and state blocks go up once, then every step of
+        `front` (`_step_front_end`: gather -> per-pixel layers + tables) ends in lic_rans_decode_step_groups, which
+        writes the decoded values into `yflat` where the next gather reads them.  Nothing in the loop waits for the
+        device; the state blocks (error words, cursors, final states) come back once, after the last step.  One block
+        per image and group (`strings["groups"]`, 1 if absent), image-major; below B counts blocks."""
         nimg, npad, M = yflat.shape
         dev = yflat.device
         G = _groups(strings.get("groups", 1))
@@ -646,29 +663,21 @@ class ContextCodec:
         d_buf, d_esc = torch.from_numpy(buf).to(dev), torch.from_numpy(e_all.view(np.int32)).to(dev)
         d_soff, d_slen, d_eoff = (torch.from_numpy(a).to(dev) for a in (s_off, s_len, e_off))
         d_state = torch.from_numpy(state.view(np.int32)).to(dev)
-        lib, nt = L.load(), len(self.taps)
-        off = 0
-        for ii, _ in steps:
-            n = len(ii)
-            win = yflat.index_select(1, win_idx[off * nt:(off + n) * nt])                 # [B, n*12, M]
-            center, tables = self._params_at(win.view(nimg * n, nt * M, 1, 1),
-                                             psi_flat.index_select(1, psi_idx[off:off + n]).view(nimg * n, -1, 1, 1),
-                                             layers)
+        lib = L.load()
+        for n, own, center, tables in front:
             L.check(lib.lic_rans_decode_step_groups(F_._ptr(d_buf), F_._ptr(d_soff), F_._ptr(d_slen), F_._ptr(d_esc),
                                                     F_._ptr(d_eoff), F_._ptr(d_state), F_._ptr(tables),
-                                                    F_._ptr(center), nimg, G, n, M, self.y_W,
-                                                    F_._ptr(own_idx[off:off + n]), F_._ptr(yflat), npad,
-                                                    F_._stream()), "lic_rans_decode_step_groups")
-            off += n
-        st = d_state.cpu().numpy().view(np.uint32)                                        # the one read-back
-        for b in range(B):
-            if st[b, RANS_LANES + 2] != 0:
-                raise CodecError(f"image {b // G}: the rANS decoder ran past the end of its stream or escape list "
-                                 f"(error word {int(st[b, RANS_LANES + 2])}): the stream is damaged")
-            if (st[b, RANS_LANES] != (len(ys[b]) - head) // 2 or st[b, RANS_LANES + 1] != len(escs[b]) // 4
-                    or (st[b, :RANS_LANES] != 1 << 16).any()):
-                raise CodecError(f"image {b // G}: the rANS stream was not used up exactly (trailing words or escapes, "
-                                 "or final states that are not the encoder's start): the stream is damaged")
+                                                    F_._ptr(center), nimg, G, n, M, self.y_W, F_._ptr(own),
+                                                    F_._ptr(yflat), npad, F_._stream()), "lic_rans_decode_step_groups")
+
+        def problem(b, states, nw, ne, err):
+            if err:
+                return (f"the rANS decoder ran past the end of its stream or escape list (error word {err}): "
+                        "the stream is damaged")
+            if nw != (len(ys[b]) - head) // 2 or ne != len(escs[b]) // 4 or (states != 1 << 16).any():
+                return ("the rANS stream was not used up exactly (trailing words or escapes, or final states that are "
+                        "not the encoder's start): the stream is damaged")
+        _state_blocks(d_state, G, problem)                                                # the one read-back
 
     def _finish(self, strings, ypad, z_hat, shape) -> Dict:
         """checksum of the decoded latents, then the synthesis transform"""
@@ -696,16 +705,16 @@ class ContextCodec:
                        coder: str = None) -> bytes:
         """x [B,3,H,W] of ANY size -> one byte string that `decompress_image` decodes by itself.  The image is padded
         to multiples of 64 (`functional.pad_to_multiple`) and the payload is exactly what `compress` produces for
-        the padded tensor; the header (`pack_bitstream`) carries everything the decoder needs to rebuild the
+        the padded tensor; the header (bitstream.py) carries everything the decoder needs to rebuild the
         shapes and to crop back.  bpp_coded of the result is 8 * len(data) / (B * H * W): header and checksums
-        included, per ORIGINAL pixel.  `coder`: None = this codec's own; "range" writes a LICBITS1 container,
-        "rans" a LICBITS2 one (`pack_bitstream_rans`), or with `groups` > 1 a LICBITS3 one
-        (`pack_bitstream_grouped`)."""
+        included, per ORIGINAL pixel.  `coder`: None = this codec's own; the container is the one `_FORMATS` has for
+        (coder, groups > 1): LICBITS1 for "range", LICBITS2 for "rans", LICBITS3 for "rans" with groups."""
         if x.dim() != 4:
             raise CodecError("expected a [B,3,H,W] tensor")
         if coder is not None and coder != self.coder:
-            # the encoder goes with the coder it belongs to: only "rans" has a device encoder
-            enc, G = (self.encoder, self.groups) if coder == "rans" else ("host", 1)
+            # encoder and groups go with the coder they belong to: only a coder that has a grouped format ("rans")
+            # has a device encoder
+            enc, G = (self.encoder, self.groups) if (coder, True) in _FORMATS else ("host", 1)
             return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder, enc, G).compress_image(x, mode, align)
         B, _, H, W = x.shape
         _, _, top, left = F_.pad_geometry(H, W, 64, align)
@@ -713,33 +722,21 @@ class ContextCodec:
         s = r["strings"]
         head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
                 "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
-        if self.groups > 1:
-            return pack_bitstream_grouped(head, s["z"], s["y"], s["y_esc"], s["y_crc32"], self.groups)
-        if self.coder == "rans":
-            return pack_bitstream_rans(head, s["z"], s["y"], s["y_esc"], s["y_crc32"])
-        return pack_bitstream(head, s["z"], s["y"], s["y_crc32"])
+        return _pack((self.coder, self.groups > 1), head, s["z"], s["y"], s.get("y_esc"), s["y_crc32"], self.groups)
 
     @torch.no_grad()
     def decompress_image(self, data: bytes) -> torch.Tensor:
         """The inverse of `compress_image`: x_hat [B,3,H,W] (channels_last).  Raises CodecError, before any GPU
         work, for a bad magic, a truncated buffer, a failing CRC or a header whose family / M / K are not this
         model's.  The magic selects the coder, whatever this codec's own is."""
-        strings = {}
-        magic = bytes(data[:8])
-        if magic in (BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_GROUPED):
-            if magic == BITSTREAM_MAGIC_GROUPED:
-                head, z_bytes, y_streams, y_esc, y_crc, G = unpack_bitstream_grouped(data)
-                if G > 1:
-                    strings["groups"] = G
-            else:
-                head, z_bytes, y_streams, y_esc, y_crc = unpack_bitstream_rans(data)
+        fmt = _FORMAT_OF_MAGIC.get(bytes(data[:8]), ("range", False))         # an unknown magic: LICBITS1's reader says so
+        head, z_bytes, y_streams, y_esc, y_crc, G = _unpack(fmt, data)
+        strings = {"y": y_streams, "z": z_bytes, "y_crc32": y_crc}
+        if fmt[0] == "rans":
             if head["y_W"] > RANS_MAX_W:
                 raise CodecError(f"bitstream names y_W = {head['y_W']}; the rANS decoder takes windows of 1 to "
                                  f"{RANS_MAX_W}")
-            strings.update(coder="rans", y_esc=y_esc)
-        else:
-            head, z_bytes, y_streams, y_crc = unpack_bitstream(data)
-        strings.update(y=y_streams, z=z_bytes, y_crc32=y_crc)
+            strings.update(coder="rans", y_esc=y_esc, **({"groups": G} if G > 1 else {}))
         m = self.model
         if (head["family"], head["M"], head["K"]) != (self._family(), m.M, m.K):
             raise CodecError(f"bitstream was written by family {head['family']} with M={head['M']}, K={head['K']}; "
@@ -751,193 +748,3 @@ class ContextCodec:
             dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"], strings.get("coder", "range"))
         out = dec.decompress(strings, (B, m.M, Hp // 16, Wp // 16), (B, m.M, Hp // 64, Wp // 64))
         return F_.crop_window(out["x_hat"], top, left, H, W)
-
-
-# ---------------------------------------------------------------------------------------------
-# Container of ContextCodec.compress_image (host only).  Little endian:
-#   magic b"LICBITS1" | uint32 family (1 = JointAutoregressiveHierarchical, 2 = HierarchicalMixtureResidual)
-#   | uint32 M, K | int32 z_lo | uint32 z_S, y_W, B, H, W, top, left | uint32 z-stream length
-#   | B x (uint32 y-stream length, uint32 CRC-32 of that image's latent symbols, `compress`'s y_crc32)
-#   | z stream | y stream of image 0 .. B-1 | uint32 CRC-32 of every byte before it
-# The padded size is the next multiple of 64 of (H, W); the latent is [B, M, Hp/16, Wp/16], z [B, M, Hp/64, Wp/64].
-# ---------------------------------------------------------------------------------------------
-BITSTREAM_MAGIC = b"LICBITS1"
-BITSTREAM_FAMILIES = {"JointAutoregressiveHierarchical": 1, "HierarchicalMixtureResidual": 2}
-_BITS_HEAD = struct.Struct("<8sIIIiIIIIIIII")
-_BITS_FIELDS = ("family", "M", "K", "z_lo", "z_S", "y_W", "B", "H", "W", "top", "left")
-
-
-def pack_bitstream(head: Dict, z_bytes: bytes, y_streams, y_crc32) -> bytes:
-    """`head`: the _BITS_FIELDS; one y stream and one symbol checksum per image"""
-    if len(y_streams) != head["B"] or len(y_crc32) != head["B"]:
-        raise CodecError("one y stream and one checksum per image expected")
-    parts = [_BITS_HEAD.pack(BITSTREAM_MAGIC, *(int(head[k]) for k in _BITS_FIELDS), len(z_bytes))]
-    parts += [struct.pack("<II", len(s), int(c) & 0xFFFFFFFF) for s, c in zip(y_streams, y_crc32)]
-    parts += [bytes(z_bytes)] + [bytes(s) for s in y_streams]
-    body = b"".join(parts)
-    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
-
-
-def unpack_bitstream(data: bytes):
-    """-> (head dict, z_bytes, [y stream per image], [symbol checksum per image]); CodecError for a bad magic, a
-    truncated or over-long buffer, a failing CRC or a header that cannot be right."""
-    data = bytes(data)
-    if len(data) < _BITS_HEAD.size + 4:
-        raise CodecError("bitstream is truncated (shorter than its header)")
-    vals = _BITS_HEAD.unpack_from(data, 0)
-    if vals[0] != BITSTREAM_MAGIC:
-        raise CodecError("not a LICBITS1 bitstream (bad magic)")
-    head = dict(zip(_BITS_FIELDS, vals[1:-1]))
-    z_len, B = vals[-1], head["B"]
-    at = _BITS_HEAD.size
-    if B == 0 or len(data) < at + 8 * B + 4:
-        raise CodecError("bitstream is truncated (per-image table)")
-    table = [struct.unpack_from("<II", data, at + 8 * b) for b in range(B)]
-    at += 8 * B
-    if len(data) != at + z_len + sum(n for n, _ in table) + 4:
-        raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
-    _check_crc_and_head(data, head)
-    z_bytes = data[at:at + z_len]
-    at += z_len
-    ys = []
-    for n, _ in table:
-        ys.append(data[at:at + n])
-        at += n
-    return head, z_bytes, ys, [c for _, c in table]
-
-
-def _check_crc_and_head(data: bytes, head: Dict):
-    """the checks both containers share: the trailing CRC-32 and a header that can be right"""
-    if zlib.crc32(data[:-4]) & 0xFFFFFFFF != struct.unpack_from("<I", data, len(data) - 4)[0]:
-        raise CodecError("bitstream is damaged (CRC-32 mismatch)")
-    if not (head["H"] > 0 and head["W"] > 0 and head["top"] < 64 and head["left"] < 64
-            and head["top"] + head["H"] <= -(-head["H"] // 64) * 64 and head["left"] + head["W"] <= -(-head["W"] // 64) * 64
-            and head["M"] > 0 and head["K"] > 0 and head["z_S"] > 0 and head["y_W"] > 0):
-        raise CodecError("bitstream header is inconsistent")
-
-
-# ---------------------------------------------------------------------------------------------
-# Container of the "rans" coder.  The LICBITS1 layout with three additions:
-#   magic b"LICBITS2" | the LICBITS1 header fields | uint32 z-stream length | uint32 lanes (64)
-#   | B x (uint32 y-stream length, uint32 CRC-32 of the latent symbols, uint32 escape count)
-#   | z stream | for image 0 .. B-1: y stream, then its escape list (uint32 each) | uint32 CRC-32 of all before it
-# `lanes` is the interleaving of the y streams: 64.  A decoder that meets another value raises CodecError; wider
-# interleaving has a container of its own (LICBITS3 below), because its per-image table has another shape.
-# ---------------------------------------------------------------------------------------------
-BITSTREAM_MAGIC_RANS = b"LICBITS2"
-_BITS_HEAD_RANS = struct.Struct("<8sIIIiIIIIIIIII")
-
-
-def pack_bitstream_rans(head: Dict, z_bytes: bytes, y_streams, y_esc, y_crc32, lanes: int = RANS_LANES) -> bytes:
-    """`head`: the _BITS_FIELDS; one y stream, one escape list (bytes, uint32 each) and one symbol checksum per image"""
-    if len(y_streams) != head["B"] or len(y_crc32) != head["B"] or len(y_esc) != head["B"]:
-        raise CodecError("one y stream, one escape list and one checksum per image expected")
-    if any(len(e) % 4 for e in y_esc):
-        raise CodecError("an escape list is not a whole number of uint32")
-    parts = [_BITS_HEAD_RANS.pack(BITSTREAM_MAGIC_RANS, *(int(head[k]) for k in _BITS_FIELDS), len(z_bytes), int(lanes))]
-    parts += [struct.pack("<III", len(s), int(c) & 0xFFFFFFFF, len(e) // 4)
-              for s, c, e in zip(y_streams, y_crc32, y_esc)]
-    parts += [bytes(z_bytes)]
-    for s, e in zip(y_streams, y_esc):
-        parts += [bytes(s), bytes(e)]
-    body = b"".join(parts)
-    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
-
-
-def unpack_bitstream_rans(data: bytes):
-    """-> (head dict, z_bytes, [y stream per image], [escape list per image], [symbol checksum per image]);
-    CodecError as `unpack_bitstream`, and for a `lanes` value other than 64."""
-    data = bytes(data)
-    if len(data) < _BITS_HEAD_RANS.size + 4:
-        raise CodecError("bitstream is truncated (shorter than its header)")
-    vals = _BITS_HEAD_RANS.unpack_from(data, 0)
-    if vals[0] != BITSTREAM_MAGIC_RANS:
-        raise CodecError("not a LICBITS2 bitstream (bad magic)")
-    head = dict(zip(_BITS_FIELDS, vals[1:-2]))
-    z_len, lanes, B = vals[-2], vals[-1], head["B"]
-    at = _BITS_HEAD_RANS.size
-    if B == 0 or len(data) < at + 12 * B + 4:
-        raise CodecError("bitstream is truncated (per-image table)")
-    table = [struct.unpack_from("<III", data, at + 12 * b) for b in range(B)]
-    at += 12 * B
-    if len(data) != at + z_len + sum(n + 4 * e for n, _, e in table) + 4:
-        raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
-    _check_crc_and_head(data, head)
-    if lanes != RANS_LANES:
-        raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements {RANS_LANES}")
-    z_bytes = data[at:at + z_len]
-    at += z_len
-    ys, es = [], []
-    for n, _, e in table:
-        ys.append(data[at:at + n])
-        es.append(data[at + n:at + n + 4 * e])
-        at += n + 4 * e
-    return head, z_bytes, ys, es, [c for _, c, _ in table]
-
-
-# ---------------------------------------------------------------------------------------------
-# Container of the "rans" coder with groups ("rANS-64 x G", `rans_deal`).  Little endian:
-#   magic b"LICBITS3" | the LICBITS1 header fields | uint32 z-stream length | uint32 lanes (= 64 G, G in 1..8)
-#   | B x uint32 CRC-32 of the image's latent symbols
-#   | B*G x (uint32 sub-stream length, uint32 escape count), image-major (entry b * G + g)
-#   | z stream | for image 0 .. B-1, for group 0 .. G-1: sub-stream, then its escape list
-#   | uint32 CRC-32 of all before it
-# ---------------------------------------------------------------------------------------------
-BITSTREAM_MAGIC_GROUPED = b"LICBITS3"
-
-
-def pack_bitstream_grouped(head: Dict, z_bytes: bytes, y_streams, y_esc, y_crc32, groups: int) -> bytes:
-    """`head`: the _BITS_FIELDS; B * `groups` sub-streams and escape lists (bytes, uint32 each), image-major, and one
-    symbol checksum per image"""
-    G, B = _groups(groups), int(head["B"])
-    if len(y_streams) != B * G or len(y_esc) != B * G or len(y_crc32) != B:
-        raise CodecError("one sub-stream and one escape list per image and group, one checksum per image expected")
-    if any(len(e) % 4 for e in y_esc):
-        raise CodecError("an escape list is not a whole number of uint32")
-    parts = [_BITS_HEAD_RANS.pack(BITSTREAM_MAGIC_GROUPED, *(int(head[k]) for k in _BITS_FIELDS), len(z_bytes),
-                                  RANS_LANES * G)]
-    parts += [struct.pack("<I", int(c) & 0xFFFFFFFF) for c in y_crc32]
-    parts += [struct.pack("<II", len(s), len(e) // 4) for s, e in zip(y_streams, y_esc)]
-    parts += [bytes(z_bytes)]
-    for s, e in zip(y_streams, y_esc):
-        parts += [bytes(s), bytes(e)]
-    body = b"".join(parts)
-    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
-
-
-def unpack_bitstream_grouped(data: bytes):
-    """-> (head dict, z_bytes, [sub-stream per image and group], [escape list likewise], [symbol checksum per image],
-    groups); CodecError as `unpack_bitstream`, for a `lanes` value that is no multiple of 64 from 64 to 512, and for
-    a sub-stream shorter than its 64 states or of odd length."""
-    data = bytes(data)
-    if len(data) < _BITS_HEAD_RANS.size + 4:
-        raise CodecError("bitstream is truncated (shorter than its header)")
-    vals = _BITS_HEAD_RANS.unpack_from(data, 0)
-    if vals[0] != BITSTREAM_MAGIC_GROUPED:
-        raise CodecError("not a LICBITS3 bitstream (bad magic)")
-    head = dict(zip(_BITS_FIELDS, vals[1:-2]))
-    z_len, lanes, B = vals[-2], vals[-1], head["B"]
-    if lanes % RANS_LANES or not RANS_LANES <= lanes <= RANS_LANES * RANS_MAX_GROUPS:
-        raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements multiples of "
-                         f"{RANS_LANES} up to {RANS_LANES * RANS_MAX_GROUPS}")
-    G = lanes // RANS_LANES
-    at = _BITS_HEAD_RANS.size
-    if B == 0 or len(data) < at + 4 * B + 8 * B * G + 4:
-        raise CodecError("bitstream is truncated (per-image tables)")
-    crcs = list(struct.unpack_from("<%dI" % B, data, at))
-    at += 4 * B
-    table = [struct.unpack_from("<II", data, at + 8 * i) for i in range(B * G)]
-    at += 8 * B * G
-    if len(data) != at + z_len + sum(n + 4 * e for n, e in table) + 4:
-        raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
-    _check_crc_and_head(data, head)
-    if any(n < 4 * RANS_LANES or n % 2 for n, _ in table):
-        raise CodecError("bitstream names a sub-stream shorter than its 64 states or of odd length")
-    z_bytes = data[at:at + z_len]
-    at += z_len
-    ys, es = [], []
-    for n, e in table:
-        ys.append(data[at:at + n])
-        es.append(data[at + n:at + n + 4 * e])
-        at += n + 4 * e
-    return head, z_bytes, ys, es, crcs, G
