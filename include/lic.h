@@ -402,6 +402,42 @@ int lic_gmm_cdf_tables(const float* params, int64_t P, int32_t M, int32_t K, int
                        uint32_t* out, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2e -- the rows the coder's per-pixel layers read, in one launch: the live taps of the masked context
+ *   convolution evaluated as a gather (ContextModels.py:18-20: the mask kills taps, the zero padding of the
+ *   convolution kills what leaves the image) and the hyper-decoder's half of torch.cat([phi, psi], dim=1)
+ *   (Models.py:73).  codec.ContextCodec calls it once per image for the encoder and once per decode step.
+ *     y             the latents, an fp32 NHWC plane: element (b, i, j, c) at
+ *                   y[b * y_batch + y_origin + i * y_row + j * y_pix + c], 0 <= i < h, 0 <= j < w, c < M <= y_pix
+ *                   (all in floats).  A zero-framed [B][h+2p][w+2p][M] buffer has y_row = (w+2p) M, y_pix = M,
+ *                   y_origin = (p (w+2p) + p) M; a plain [B][h][w][M] one y_row = w M, y_pix = M, y_origin = 0.
+ *                   Nothing but those h * w pixels is ever read: the frame is not relied on.
+ *     taps          [nt][2] int32 (device): the live taps as (dr, ds) offsets from the pixel, in the order of the
+ *                   packed context weight's K dimension
+ *     slice_rows    R >= 1: the plane is cut into bands of R rows (the last one shorter when R does not divide h).
+ *                   A tap with dr < 0 of pixel (i, j) is read only if (i mod R) + dr >= 0, else it is zero, as a
+ *                   tap above the image is.  R >= h: no slices.
+ *     pix           [n] int64 (device): raster indices i * w + j of the pixels wanted, the same for every image
+ *     win           out, [B*n][nt*M] contiguous: row b * n + k, column t * M + c = tap t, channel c of pixel pix[k]
+ *     psi, comb     optional (psi NULL: neither is touched).  psi [B][h*w][Cpsi] contiguous; row b * n + k of
+ *                   comb, comb_ld floats per row, gets the Cpsi floats of pixel pix[k].  `comb` points at the first
+ *                   column to write, so a column range of a wider buffer is comb = buffer + first column.
+ *     path          LIC_CTX_AUTO: 16-byte pieces when M % 4 == 0 (and Cpsi % 4 == 0, comb_ld % 4 == 0 with psi),
+ *                   y_batch, y_row, y_pix, y_origin are multiples of 4 and y, win (psi, comb) are 16-byte
+ *                   aligned; single floats otherwise.  LIC_CTX_ELEMENT forces single floats, LIC_CTX_VECTOR the
+ *                   pieces (LIC_ERR_INVALID where the conditions above do not hold).  Both write the same bytes.
+ *   A pix[k] outside [0, h*w) reads nothing and writes zeros to its rows.  NULL y / taps / pix / win, psi without
+ *   comb, B, h, w, M, n <= 0, nt < 1, slice_rows < 1, a pointer that is not float aligned: LIC_ERR_INVALID, nothing
+ *   launched.  One launch on `stream`, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define LIC_CTX_AUTO 0
+#define LIC_CTX_VECTOR 1
+#define LIC_CTX_ELEMENT 2
+int lic_ctx_gather(const float* y, int64_t y_batch, int64_t y_row, int64_t y_pix, int64_t y_origin, int32_t B,
+                   int32_t h, int32_t w, int32_t M, const int32_t* taps, int32_t nt, int32_t slice_rows,
+                   const int64_t* pix, int64_t n, float* win, const float* psi, int32_t Cpsi, float* comb,
+                   int64_t comb_ld, int32_t path, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).2 -- the device decoder of the "rANS-64" y streams (format and host coder: lic_codec.h).
  *   lic_rans_decode_step decodes ONE wavefront step of all B images in one launch, one wave per image, from the
  *   tables lic_gmm_cdf_tables has just built, and writes the values where the next step's gather reads them:

@@ -76,6 +76,8 @@ class AdamJob(C.Structure):
 
 RANS_LANES, RANS_STATE_WORDS, RANS_MAX_GROUPS = 64, 67, 8
 
+CTX_AUTO, CTX_VECTOR, CTX_ELEMENT = range(3)
+
 WINDOW_ZERO, WINDOW_REPLICATE, WINDOW_REFLECT = range(3)
 WINDOW_FLIP = 1
 
@@ -166,6 +168,8 @@ SIGNATURES = {
     "lic_rans_encode": (C.c_int, [_vp] * 3 + [_i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
     "lic_rans_decode_step_groups": (C.c_int, [_vp] * 8 + [_i32] * 5 + [_vp, _vp, _i64, _vp]),
     "lic_rans_encode_groups": (C.c_int, [_vp] * 3 + [_i64, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "lic_ctx_gather": (C.c_int, [_vp] + [_i64] * 4 + [_i32] * 4 + [_vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _i64,
+                                 _i32, _vp]),
     "lic_msssim_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "lic_msssim": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _sz,
                              _vp]),

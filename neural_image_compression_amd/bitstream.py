@@ -1,10 +1,11 @@
 """The self-describing container of `ContextCodec.compress_image` (host only, no torch): one byte string per batch
-of images of any size.  Three formats, one per (coder, grouped) pair of the y streams; `_FORMATS` below describes
-them, `_pack` writes and `_unpack` reads all three, and the six public functions are their wrappers.
+of images of any size.  Four formats, one per (coder, grouping) pair of the y streams; `_FORMATS` below describes
+them, `_pack` writes and `_unpack` reads all four, and the eight public functions are their wrappers.
 
 Every format, little endian:
   magic (8 bytes) | uint32 family (1 = JointAutoregressiveHierarchical, 2 = HierarchicalMixtureResidual)
   | uint32 M, K | int32 z_lo | uint32 z_S, y_W, B, H, W, top, left | uint32 z-stream length | [uint32 lanes]
+  | [uint32 slice_rows]
   | image table: B rows | block table: B*G rows, image-major (row b * G + g)
   | z stream | for every block: its y stream, then its escape list (uint32 each) | uint32 CRC-32 of all before it
 The padded size is the next multiple of 64 of (H, W); the latent is [B, M, Hp/16, Wp/16], z [B, M, Hp/64, Wp/64].
@@ -13,12 +14,16 @@ The padded size is the next multiple of 64 of (H, W); the latent is [B, M, Hp/16
   LICBITS1  range  absent            none              y length, symbol CRC-32            1
   LICBITS2  rans   64                none              y length, symbol CRC-32, escapes   1
   LICBITS3  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G ("rANS-64 x G", `rans_deal`)
+  LICBITS4  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G, and the slice_rows word
 
 "symbol CRC-32" is `compress`'s y_crc32 of that image's latent symbols, "escapes" the number of uint32 in the block's
 escape list.  `lanes` is the interleaving of an image's y streams.  A LICBITS2 reader refuses any value but 64: wider
 interleaving has LICBITS3, whose tables have another shape.  A LICBITS3 reader takes the multiples of 64 up to 512
 (64 is legal there, though `compress_image` writes LICBITS2 for one group) and refuses a sub-stream shorter than its 64
-states or of odd length.
+states or of odd length.  LICBITS4 is LICBITS3 with one more header word: `slice_rows` = R >= 1, the latent rows per slice
+of the context model (codec.ContextCodec: no context tap crosses a boundary between bands of R rows, and the bands
+decode side by side); `compress_image` writes it only for a codec with slices, for any G.  Its reader refuses what
+LICBITS3's does, and R = 0 as a damaged header; R comes back as head["slice_rows"].
 """
 from __future__ import annotations
 
@@ -46,31 +51,40 @@ def _groups(G) -> int:
 
 BITSTREAM_FAMILIES = {"JointAutoregressiveHierarchical": 1, "HierarchicalMixtureResidual": 2}
 BITSTREAM_MAGIC, BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_GROUPED = b"LICBITS1", b"LICBITS2", b"LICBITS3"
+BITSTREAM_MAGIC_SLICED = b"LICBITS4"
 _BITS_FIELDS = ("family", "M", "K", "z_lo", "z_S", "y_W", "B", "H", "W", "top", "left")
 _BITS_HEAD, _BITS_HEAD_RANS = struct.Struct("<8s3Ii8I"), struct.Struct("<8s3Ii9I")          # without / with `lanes`
-# (coder, more than one group) -> (magic, header, image table columns, block table columns, what `_pack` expects)
+_BITS_HEAD_SLICED = struct.Struct("<8s3Ii10I")                                                # `lanes`, `slice_rows`
+# (coder, grouping: False = one stream per image, True = G sub-streams, "sliced" = those and slices)
+# -> (magic, header, image table columns, block table columns, what `_pack` expects)
 _FORMATS = {
     ("range", False): (BITSTREAM_MAGIC, _BITS_HEAD, (), ("len", "crc"), "one y stream and one checksum per image"),
     ("rans", False): (BITSTREAM_MAGIC_RANS, _BITS_HEAD_RANS, (), ("len", "crc", "esc"),
                       "one y stream, one escape list and one checksum per image"),
     ("rans", True): (BITSTREAM_MAGIC_GROUPED, _BITS_HEAD_RANS, ("crc",), ("len", "esc"),
                      "one sub-stream and one escape list per image and group, one checksum per image"),
+    ("rans", "sliced"): (BITSTREAM_MAGIC_SLICED, _BITS_HEAD_SLICED, ("crc",), ("len", "esc"),
+                         "one sub-stream and one escape list per image and group, one checksum per image"),
 }
 _FORMAT_OF_MAGIC = {f[0]: key for key, f in _FORMATS.items()}
 
 
 def _pack(fmt, head: Dict, z_bytes: bytes, ys, escs, crcs, G: int = 1, lanes: int = None) -> bytes:
     """`head`: the _BITS_FIELDS; B * G y streams and escape lists (bytes; None where the format has none), image-major,
-    and one symbol checksum per image"""
+    and one symbol checksum per image.  The sliced format takes head["slice_rows"] as well."""
     magic, st, img_cols, blk_cols, expects = _FORMATS[fmt]
+    R = head.get("slice_rows", 0) if st is _BITS_HEAD_SLICED else 0
+    if st is _BITS_HEAD_SLICED and (isinstance(R, bool) or not isinstance(R, (int, np.integer))
+                                    or not 1 <= int(R) <= 0xFFFFFFFF):
+        raise CodecError(f"slice_rows = {R!r}: a sliced bitstream needs a whole number of rows per slice, at least 1")
     B = int(head["B"])
     escs = [b""] * len(ys) if escs is None else escs
     if len(ys) != B * G or len(escs) != B * G or len(crcs) != B:
         raise CodecError(expects + " expected")
     if any(len(e) % 4 for e in escs):
         raise CodecError("an escape list is not a whole number of uint32")
-    words = (len(z_bytes), RANS_LANES * G if lanes is None else int(lanes))
-    parts = [st.pack(magic, *(int(head[k]) for k in _BITS_FIELDS), *words[:1 + (st is _BITS_HEAD_RANS)])]
+    words = (len(z_bytes), RANS_LANES * G if lanes is None else int(lanes), int(R))
+    parts = [st.pack(magic, *(int(head[k]) for k in _BITS_FIELDS), *words[:1 + (st.size - _BITS_HEAD.size) // 4])]
     rows = [{"crc": int(c) & 0xFFFFFFFF} for c in crcs]
     blocks = [dict(rows[i // G], len=len(s), esc=len(e) // 4) for i, (s, e) in enumerate(zip(ys, escs))]
     parts += [struct.pack("<%dI" % len(cols), *(r[k] for k in cols)) for cols, t in ((img_cols, rows), (blk_cols, blocks))
@@ -93,7 +107,7 @@ def _unpack(fmt, data: bytes):
     if vals[0] != magic:
         raise CodecError(f"not a {magic.decode()} bitstream (bad magic)")
     head = dict(zip(_BITS_FIELDS, vals[1:12]))
-    z_len, lanes, B, G = vals[12], vals[-1] if st is _BITS_HEAD_RANS else RANS_LANES, head["B"], 1
+    z_len, lanes, B, G = vals[12], RANS_LANES if st is _BITS_HEAD else vals[13], head["B"], 1
     if fmt[1]:
         if lanes % RANS_LANES or not RANS_LANES <= lanes <= RANS_LANES * RANS_MAX_GROUPS:
             raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements multiples of "
@@ -117,6 +131,10 @@ def _unpack(fmt, data: bytes):
         raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements {RANS_LANES}")
     if fmt[1] and any(r["len"] < 4 * RANS_LANES or r["len"] % 2 for r in blocks):
         raise CodecError("bitstream names a sub-stream shorter than its 64 states or of odd length")
+    if st is _BITS_HEAD_SLICED:
+        if vals[14] < 1:
+            raise CodecError("bitstream header is damaged (slice_rows = 0)")
+        head["slice_rows"] = vals[14]
     payload = [data[a:b] for a, b in zip(cuts, cuts[1:])]
     return head, payload[0], payload[1::2], payload[2::2], [r["crc"] for r in (rows if img_cols else blocks)], G
 
@@ -158,3 +176,14 @@ def unpack_bitstream_grouped(data: bytes):
     """-> (head dict, z_bytes, [sub-stream per image and group], [escape list likewise], [symbol checksum per image],
     groups)"""
     return _unpack(("rans", True), data)
+
+
+def pack_bitstream_sliced(head: Dict, z_bytes: bytes, y_streams, y_esc, y_crc32, groups: int, slice_rows: int) -> bytes:
+    return _pack(("rans", "sliced"), dict(head, slice_rows=slice_rows), z_bytes, y_streams, y_esc, y_crc32,
+                 _groups(groups))
+
+
+def unpack_bitstream_sliced(data: bytes):
+    """-> `unpack_bitstream_grouped`'s six, then slice_rows (head["slice_rows"] too)"""
+    out = _unpack(("rans", "sliced"), data)
+    return out + (out[0]["slice_rows"],)

@@ -13,8 +13,8 @@ prior, so it decodes without context) and `decode_y_with_tables` (decodes y from
 used -- the coder's inverse).  `ContextCodec`: the full round trip; its decoder rebuilds the tables from
 already-decoded pixels through the masked 5x5 context model, wavefront by wavefront.
 `ContextCodec.compress_image` / `decompress_image` wrap that round trip, for images of any size, in one
-self-describing byte string: header, per-image lengths and checksums, streams, CRC-32.  bitstream.py holds the three
-containers (LICBITS1/2/3, one per coder and grouping), their one writer and one reader; its names are this module's too.
+self-describing byte string: header, per-image lengths and checksums, streams, CRC-32.  bitstream.py holds the four
+containers (LICBITS1/2/3/4, one per coder and grouping), their one writer and one reader; its names are this module's too.
 
 `ContextCodec(..., coder="rans")` codes the y streams with the 64-lane interleaved rANS coder of lic_codec.h
 instead: its decoder is a device kernel (`lic_rans_decode_step`), so the decode loop has no host in it.  The range
@@ -26,6 +26,11 @@ the same bytes, and no table is copied to the host.
 (`rans_deal`: round r of a step goes to sub-stream r % G), so G waves per image decode and encode them
 (`lic_rans_decode_step_groups`, `lic_rans_encode_groups`); each sub-stream costs its 256 bytes of states.  G = 1,
 the default, is the format above.
+
+`ContextCodec(..., coder="rans", slice_rows=R)` cuts the latent plane into slices of R rows whose contexts do not see
+each other, so all slices decode side by side: w + 3 (min(R, h) - 1) dependent steps instead of w + 3 (h - 1), paid
+for in rate by the first rows of every slice (DESIGN 1.1 f.2e has the rule).  Both sides build the rows their
+per-pixel layers read with one gather, `lic_ctx_gather`, which applies that rule.
 """
 from __future__ import annotations
 
@@ -40,10 +45,11 @@ import torch
 from . import _lib as L
 from . import functional as F_
 from .bitstream import (BITSTREAM_FAMILIES, BITSTREAM_MAGIC, BITSTREAM_MAGIC_GROUPED,  # noqa: F401
-                        BITSTREAM_MAGIC_RANS, RANS_LANES, RANS_MAX_GROUPS, CodecError, _BITS_FIELDS, _BITS_HEAD,
-                        _BITS_HEAD_RANS, _FORMAT_OF_MAGIC, _FORMATS, _check_crc_and_head, _groups, _pack, _unpack,
-                        pack_bitstream, pack_bitstream_grouped, pack_bitstream_rans, unpack_bitstream,
-                        unpack_bitstream_grouped, unpack_bitstream_rans)
+                        BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_SLICED, RANS_LANES, RANS_MAX_GROUPS, CodecError,
+                        _BITS_FIELDS, _BITS_HEAD, _BITS_HEAD_RANS, _FORMAT_OF_MAGIC, _FORMATS, _check_crc_and_head,
+                        _groups, _pack, _unpack, pack_bitstream, pack_bitstream_grouped, pack_bitstream_rans,
+                        pack_bitstream_sliced, unpack_bitstream, unpack_bitstream_grouped, unpack_bitstream_rans,
+                        unpack_bitstream_sliced)
 
 _CODEC = None
 
@@ -243,6 +249,30 @@ def gmm_tables(act: torch.Tensor, M: int, K: int, W: int):
     return center, tables
 
 
+def _slice_rows(R) -> int:
+    """R as an int >= 1 (latent rows per slice), or CodecError"""
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or int(R) < 1:
+        raise CodecError(f"slice_rows = {R!r}: expected None (no slices) or an integer of at least 1")
+    return int(R)
+
+
+def wavefront(h: int, w: int, pad: int, slice_rows: int = None):
+    """The decode schedule of an h x w latent plane under a causal mask of half-width `pad`, cut into slices of
+    `slice_rows` rows (None: one slice).  Pixel (i, j) belongs to step t = j + (pad + 1) * (i mod R): its own row's
+    taps lie in earlier steps, and so do the rows above it INSIDE its slice up to column j + pad; rows above the slice
+    are not context (ContextCodec).  -> [(rows, cols)] per step, rows ascending: w + (pad + 1)(min(R, h) - 1) steps."""
+    k = pad + 1
+    R = h if slice_rows is None else min(_slice_rows(slice_rows), h)
+    rows = np.arange(h, dtype=np.int64)
+    steps = []
+    for t in range(w + k * (R - 1)):
+        jj = t - k * (rows % R)
+        keep = (jj >= 0) & (jj < w)
+        if keep.any():
+            steps.append((rows[keep], jj[keep]))
+    return steps
+
+
 def _state_blocks(d_state: torch.Tensor, G: int, problem):
     """The one read-back of a rANS kernel's state blocks [blocks][RANS_STATE_WORDS] (lic.h: 64 coder states, word
     count, escape count, error word), image-major with G blocks per image -> [(states uint32 [64], words, escapes)].
@@ -379,10 +409,18 @@ class ContextCodec:
 
     `groups`: sub-streams per image of the "rans" coder (1 to 8, `rans_deal`).  1 (the default) is the rANS-64
     format; with G > 1 `strings["groups"]` is G and `strings["y"]`, `strings["y_esc"]` hold B * G entries,
-    image-major (entry b * G + g), coded and decoded by G waves per image.  `decompress` reads G from the strings."""
+    image-major (entry b * G + g), coded and decoded by G waves per image.  `decompress` reads G from the strings.
+
+    `slice_rows`: None (the default) or R >= 1, coder "rans" only: latent rows per slice.  A context tap (dr, ds) with
+    dr < 0 of pixel (i, j) contributes y_hat[i + dr, j + ds] only if (i mod R) + dr >= 0 and zero otherwise, exactly
+    as a tap above the image does; taps of the pixel's own row are untouched.  The slices then advance together
+    (`wavefront`): fewer, wider steps, for the rate the first rows of every slice lose with their context.  The model
+    is not told: encoder and decoder evaluate the same layers on the same masked windows, so their tables agree and
+    y_hat, x_hat are what the codec without slices reconstructs; only the bytes differ.  R >= h is that codec, byte
+    for byte.  `strings["slice_rows"]` is R when slicing is on; `decompress` reads it from the strings."""
 
     def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range",
-                 encoder: str = "host", groups: int = 1):
+                 encoder: str = "host", groups: int = 1, slice_rows: int = None):
         if coder not in CODERS:
             raise CodecError(f"unknown coder {coder!r}: expected one of {CODERS}")
         if encoder not in ENCODERS:
@@ -400,6 +438,9 @@ class ContextCodec:
         self.groups = _groups(groups)
         if self.groups > 1 and coder != "rans":
             raise CodecError(f"groups={self.groups} needs coder='rans': the {coder!r} coder has one stream per image")
+        self.slice_rows = None if slice_rows is None else _slice_rows(slice_rows)
+        if self.slice_rows is not None and coder != "rans":
+            raise CodecError(f"slice_rows={self.slice_rows} needs coder='rans': the {coder!r} coder has no sliced format")
         mc = model.context_model.masked
         k = mc.kernel_size[0]
         self.taps = [(r, s) for r in range(k) for s in range(k) if (mc._tap_mask >> (r * k + s)) & 1]
@@ -408,19 +449,14 @@ class ContextCodec:
         if any((s - self.pad) + (self.pad + 1) * (r - self.pad) >= 0 for (r, s) in self.taps):
             raise CodecError("context mask is not causal in raster order")
 
-    def _wavefront(self, h: int, w: int):
+    def _wavefront(self, h: int, w: int, slice_rows: int = None):
         """Decode schedule.  With mask type A a pixel (i, j) sees rows above it up to column j + pad and its own
         row up to j - 1, so for t = j + (pad + 1) * i every pixel's context lies in steps < t: the pixels of one
         step are independent and go through the GPU as one batch -- w + (pad + 1)(h - 1) dependent steps
-        instead of h * w (141 instead of 1536 for a 512x768 image).  Returns [(rows, cols)] per step, rows
+        instead of h * w (141 instead of 1536 for a 512x768 image).  With slices of `slice_rows` rows i counts
+        inside the pixel's slice (`wavefront`).  Returns [(rows, cols)] per step, rows
         ascending; encoder and decoder order the symbols step by step, pixel by pixel, channel by channel."""
-        k = self.pad + 1
-        steps = []
-        for t in range(w + k * (h - 1)):
-            ii = np.array([i for i in range(h) if 0 <= t - k * i < w], dtype=np.int64)
-            if ii.size:
-                steps.append((ii, t - k * ii))
-        return steps
+        return wavefront(h, w, self.pad, slice_rows)
 
     def _ctx_weight(self):
         mc = self.model.context_model.masked
@@ -444,28 +480,61 @@ class ContextCodec:
                            i < 2, slopes[i] if i < 2 else 0.01))
         return layers
 
-    def _act_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers) -> torch.Tensor:
-        """windows [N, 12M, 1, 1], psi_px [N, 2M, 1, 1] -> the activated entropy parameters [N, G*K*M, 1, 1]"""
+    def _act_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None) -> torch.Tensor:
+        """windows [N, 12M, 1, 1], psi_px [N, 2M, 1, 1] -> the activated entropy parameters [N, G*K*M, 1, 1].
+        `comb` [N, 4M]: the input of the first 1x1 layer with psi already in its last 2M columns (`_gather`), instead
+        of psi_px; the context GEMM writes its 2M columns beside them, so no `cat` (Models.py:73) runs."""
         m = self.model
         wp, b, co, _, _ = layers[0]
-        x = torch.cat([F_.conv2d_prepacked(windows, wp, b, co, 1, pin_tile=True), psi_px], dim=1)
+        N = windows.shape[0]
+        if comb is None:
+            comb = torch.empty((N, co + psi_px.shape[1]), device=windows.device, dtype=torch.float32)
+            comb[:, co:] = psi_px.reshape(N, -1)
+        comb = comb.view(N, 1, 1, -1)
+        F_.conv2d_prepacked(windows, wp, b, co, 1, pin_tile=True, out=comb[..., :co])
+        x = comb.permute(0, 3, 1, 2)
         for wp, b, co, leaky, slope in layers[1:]:
             x = F_.conv2d_prepacked(x, wp, b, co, 1, leaky=leaky, slope=slope, pin_tile=True)
         return F_.entropy_params_activation(x, m.M, m.K)
 
-    def _params_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers):
-        """windows [N, 12M, 1, 1], psi_px [N, 2M, 1, 1] -> (center [N, M], tables [N*M, S+1]) on the device"""
+    def _params_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None):
+        """`_act_at`'s arguments -> (center [N, M], tables [N*M, S+1]) on the device"""
         m = self.model
-        return gmm_tables(self._act_at(windows, psi_px, layers), m.M, m.K, self.y_W)
+        return gmm_tables(self._act_at(windows, psi_px, layers, comb), m.M, m.K, self.y_W)
 
-    def _windows_all(self, y_hat: torch.Tensor) -> torch.Tensor:
-        """[B, M, h, w] -> [B*h*w, 12M, 1, 1]: the live taps of every pixel (zeros outside the image)"""
+    def _gather(self, y: torch.Tensor, geometry, h: int, w: int, pix: torch.Tensor, slice_rows, psi_flat=None):
+        """One `lic_ctx_gather` launch.  y: fp32 latents of B images, pixel (i, j) of image b at float
+        b * batch + origin + i * row + j * M for geometry = (batch, row, origin); pix: int64 raster indices (device)
+        of the n pixels wanted; psi_flat [B, h*w, 2M] or None.
+        -> (windows [B*n, 12M, 1, 1] with zeros for taps outside the image or the pixel's slice,
+            comb [B*n, 4M] whose last 2M columns hold the pixels' psi, the first 2M still unwritten; None without psi)"""
+        B, M, n, nt, dev = y.shape[0], self.model.M, pix.numel(), len(self.taps), y.device
+        if getattr(self, "_taps_dev", None) is None or self._taps_dev.device != dev:
+            self._taps_dev = torch.tensor([(r - self.pad, s - self.pad) for (r, s) in self.taps], dtype=torch.int32,
+                                          device=dev)
+        win = torch.empty((B * n, nt * M, 1, 1), device=dev, dtype=torch.float32)
+        comb = cpsi = None
+        if psi_flat is not None:
+            cpsi, cctx = psi_flat.shape[2], self.model.context_model.masked.out_channels
+            comb = torch.empty((B * n, cctx + cpsi), device=dev, dtype=torch.float32)
+        batch, row, origin = geometry
+        L.check(L.load().lic_ctx_gather(
+            F_._ptr(y), batch, row, M, origin, B, h, w, M, F_._ptr(self._taps_dev), nt,
+            h if slice_rows is None else min(slice_rows, h), F_._ptr(pix), n, F_._ptr(win), F_._ptr(psi_flat), cpsi or 0,
+            None if comb is None else C.c_void_p(comb.data_ptr() + 4 * cctx), 0 if comb is None else comb.shape[1],
+            L.CTX_AUTO, F_._stream()), "lic_ctx_gather")
+        return win, comb
+
+    def _windows_all(self, y_hat: torch.Tensor, slice_rows: int = None, psi: torch.Tensor = None):
+        """[B, M, h, w] -> [B*h*w, 12M, 1, 1]: the live taps of every pixel (zeros outside the image and, with
+        `slice_rows`, outside the pixel's slice).  With psi [B, 2M, h, w]: -> (those windows, `_gather`'s comb)"""
+        F_._require_cuda(y_hat, psi)
         B, M, h, w = y_hat.shape
-        p = self.pad
-        yp = torch.nn.functional.pad(y_hat, (p, p, p, p))
-        cols = [yp[:, :, r:r + h, s:s + w] for (r, s) in self.taps]              # each [B, M, h, w]
-        win = torch.cat(cols, dim=1)                                              # [B, 12M, h, w]
-        return win.permute(0, 2, 3, 1).reshape(B * h * w, -1, 1, 1).contiguous()
+        y = F_._nhwc(y_hat)
+        pix = torch.arange(h * w, device=y.device, dtype=torch.int64)
+        win, comb = self._gather(y, (h * w * M, w * M, 0), h, w, pix, slice_rows,
+                                 None if psi is None else F_._nhwc(psi).view(B, h * w, -1))
+        return win if psi is None else (win, comb)
 
     @torch.no_grad()
     def compress(self, x: torch.Tensor) -> Dict:
@@ -475,16 +544,18 @@ class ContextCodec:
         B, M, h, w = y_in.shape
         z_bytes = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in)
         psi = m.hyper_decoder(z_in).float()
-        psi_px = psi.permute(0, 2, 3, 1).reshape(B * h * w, -1, 1, 1).contiguous()
-        center, tables = self._params_at(self._windows_all(y_in), psi_px, self._prepack())
+        win, comb = self._windows_all(out["y_in"], self.slice_rows, psi)
+        center, tables = self._params_at(win, None, self._prepack(), comb)
         y_sym = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
         # symbols leave in the decoder's wavefront order (see _wavefront), M channels per pixel
-        steps = self._wavefront(h, w)
+        steps = self._wavefront(h, w, self.slice_rows)
         order = np.concatenate([ii * w + jj for ii, jj in steps])
         step_len = [len(ii) * M for ii, _ in steps]
         strings = {"z": z_bytes}
         if self.groups > 1:
             strings["groups"] = self.groups
+        if self.slice_rows is not None:
+            strings["slice_rows"] = self.slice_rows
         if self.encoder == "device":
             y_streams, y_esc = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, M)
             strings.update(coder="rans", y_esc=y_esc)
@@ -575,11 +646,14 @@ class ContextCodec:
         # decoded latents, pixel-major, inside a zero frame
         ypad = torch.zeros((B, h + 2 * p, w + 2 * p, M), device=dev, dtype=torch.float32)
         yflat = ypad.view(B, -1, M)
-        steps = self._wavefront(h, w)
-        front = self._step_front_end(steps, yflat, psi)
         coder = strings.get("coder", "range")
         if coder not in CODERS:
             raise CodecError(f"unknown coder {coder!r} in the strings")
+        R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
+        if R is not None and coder != "rans":
+            raise CodecError(f"the strings name slice_rows with coder {coder!r}: only 'rans' streams have slices")
+        steps = self._wavefront(h, w, R)
+        front = self._step_front_end(steps, yflat, psi, R)
         if coder == "rans":
             self._decode_y_rans(strings, front, yflat)
             return self._finish(strings, ypad, z_hat, shape)
@@ -603,31 +677,28 @@ class ContextCodec:
                 d.close()
         return self._finish(strings, ypad, z_hat, shape)
 
-    def _step_front_end(self, steps, yflat, psi):
-        """What both decoders do per wavefront step before their coder runs.  Here, once: the layers are packed and the
-        flat indices of every step's context windows / own pixels / psi rows uploaded.  Then, per step of `steps`
-        (`_wavefront`) as the returned generator is advanced: one gather of the windows from `yflat` (the zero-framed
-        latents [B, (h+2p)(w+2p), M], which the coder fills in between), one of `psi` [B, 2M, h, w], the per-pixel
-        layers and the table kernel -> (n pixels, their n indices into yflat, center [B*n, M], tables [B*n*M, S+1])"""
-        B, M, p, nt, dev = yflat.shape[0], yflat.shape[2], self.pad, len(self.taps), yflat.device
-        w = psi.shape[3]
+    def _step_front_end(self, steps, yflat, psi, slice_rows=None):
+        """What both decoders do per wavefront step before their coder runs.  Here, once: the layers are packed and
+        one array uploaded, the raster index and the index into yflat of every step's pixels.  Then, per step of
+        `steps` (`_wavefront`) as the returned generator is advanced: one `lic_ctx_gather` of the windows from `yflat`
+        (the zero-framed latents [B, (h+2p)(w+2p), M], which the coder fills in between) and of the pixels' columns
+        of `psi` [B, 2M, h, w], the per-pixel layers and the table kernel
+        -> (n pixels, their n indices into yflat, center [B*n, M], tables [B*n*M, S+1])"""
+        B, M, p = yflat.shape[0], yflat.shape[2], self.pad
+        h, w = psi.shape[2], psi.shape[3]
         layers = self._prepack()
-        psi_flat = psi.permute(0, 2, 3, 1).contiguous().view(B, psi.shape[2] * w, -1)     # [B, h*w, 2M]
+        psi_flat = F_._nhwc(psi).view(B, h * w, -1)                                       # [B, h*w, 2M]
         Wp = w + 2 * p
-        tr = np.array([r for (r, _) in self.taps]), np.array([c for (_, c) in self.taps])
-        win_idx = torch.from_numpy(np.concatenate(
-            [((ii[:, None] + tr[0][None, :]) * Wp + jj[:, None] + tr[1][None, :]).ravel() for ii, jj in steps])).to(dev)
-        own_idx = torch.from_numpy(np.concatenate([(ii + p) * Wp + jj + p for ii, jj in steps])).to(dev)
-        psi_idx = torch.from_numpy(np.concatenate([ii * w + jj for ii, jj in steps])).to(dev)
+        idx = torch.from_numpy(np.stack([np.concatenate([ii * w + jj for ii, jj in steps]),
+                                         np.concatenate([(ii + p) * Wp + jj + p for ii, jj in steps])])).to(yflat.device)
+        geometry = (yflat.shape[1] * M, Wp * M, (p * Wp + p) * M)
 
         def run():
             off = 0
             for ii, _ in steps:
                 n = len(ii)
-                win = yflat.index_select(1, win_idx[off * nt:(off + n) * nt])             # [B, n*12, M]
-                yield (n, own_idx[off:off + n]) + self._params_at(
-                    win.view(B * n, nt * M, 1, 1), psi_flat.index_select(1, psi_idx[off:off + n]).view(B * n, -1, 1, 1),
-                    layers)
+                win, comb = self._gather(yflat, geometry, h, w, idx[0, off:off + n], slice_rows, psi_flat)
+                yield (n, idx[1, off:off + n]) + self._params_at(win, None, layers, comb)
                 off += n
         return run()
 
@@ -708,7 +779,8 @@ class ContextCodec:
         the padded tensor; the header (bitstream.py) carries everything the decoder needs to rebuild the
         shapes and to crop back.  bpp_coded of the result is 8 * len(data) / (B * H * W): header and checksums
         included, per ORIGINAL pixel.  `coder`: None = this codec's own; the container is the one `_FORMATS` has for
-        (coder, groups > 1): LICBITS1 for "range", LICBITS2 for "rans", LICBITS3 for "rans" with groups."""
+        (coder, groups > 1): LICBITS1 for "range", LICBITS2 for "rans", LICBITS3 for "rans" with groups -- and LICBITS4
+        for a codec with slices, whatever its groups.  Slices, like groups, do not follow to another coder."""
         if x.dim() != 4:
             raise CodecError("expected a [B,3,H,W] tensor")
         if coder is not None and coder != self.coder:
@@ -722,6 +794,9 @@ class ContextCodec:
         s = r["strings"]
         head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
                 "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
+        if self.slice_rows is not None:
+            return _pack((self.coder, "sliced"), dict(head, slice_rows=self.slice_rows), s["z"], s["y"], s["y_esc"],
+                         s["y_crc32"], self.groups)
         return _pack((self.coder, self.groups > 1), head, s["z"], s["y"], s.get("y_esc"), s["y_crc32"], self.groups)
 
     @torch.no_grad()
@@ -737,6 +812,8 @@ class ContextCodec:
                 raise CodecError(f"bitstream names y_W = {head['y_W']}; the rANS decoder takes windows of 1 to "
                                  f"{RANS_MAX_W}")
             strings.update(coder="rans", y_esc=y_esc, **({"groups": G} if G > 1 else {}))
+            if "slice_rows" in head:
+                strings["slice_rows"] = head["slice_rows"]
         m = self.model
         if (head["family"], head["M"], head["K"]) != (self._family(), m.M, m.K):
             raise CodecError(f"bitstream was written by family {head['family']} with M={head['M']}, K={head['K']}; "

@@ -439,15 +439,23 @@ def pack_conv_weight(weight: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def conv2d_prepacked(x, w_packed, bias, cout, kernel, stride=1, padding=0, leaky=False, slope=0.01, tap_mask=0,
-                     pin_tile=False):
+                     pin_tile=False, out=None):
     """Inference-only conv2d whose weight was packed once with `pack_conv_weight` (no autograd, no per-call
     packing): same kernel, same operands, hence the same bits as `conv2d`.  The serial context decoder calls
-    four layers h*w times with unchanged weights (codec.ContextCodec)."""
-    _require_cuda(x, w_packed, bias)
+    four layers h*w times with unchanged weights (codec.ContextCodec).  `out`: as `conv2d`'s, a [B,Ho,Wo,cout]
+    channel slice of a wider contiguous NHWC buffer to write into instead of a fresh tensor."""
+    _require_cuda(x, w_packed, bias, out)
     xh = _nhwc(x)
     B, Hi, Wi, Cin = xh.shape
     Ho, Wo = conv_out_size(Hi, Wi, kernel, stride, padding, False)
-    out = torch.empty((B, Ho, Wo, cout), device=x.device, dtype=torch.float32)
+    out_ld = None
+    if out is None:
+        out = torch.empty((B, Ho, Wo, cout), device=x.device, dtype=torch.float32)
+    else:
+        if tuple(out.shape) != (B, Ho, Wo, cout) or out.stride(3) != 1 or out.stride(1) != Wo * out.stride(2) or \
+                out.stride(0) != Ho * out.stride(1):
+            raise ValueError("out must be a [B,Ho,Wo,cout] channel slice of a contiguous NHWC buffer")
+        out_ld = out.stride(2)
     global FORCE_IGEMM
     saved = FORCE_IGEMM
     if pin_tile and Cin % 4 == 0 and cout % 64 == 0:
@@ -458,7 +466,7 @@ def conv2d_prepacked(x, w_packed, bias, cout, kernel, stride=1, padding=0, leaky
     try:
         _igemm(xh, w_packed, out, B=B, Hi=Hi, Wi=Wi, Cin=Cin, Ho=Ho, Wo=Wo, Cout=cout, kh=kernel, kw=kernel,
                stride=stride, pad=padding, transposed=False, bias=bias,
-               epilogue=L.EPI_LEAKY if leaky else L.EPI_NONE, slope=slope, tap_mask=tap_mask)
+               epilogue=L.EPI_LEAKY if leaky else L.EPI_NONE, slope=slope, tap_mask=tap_mask, out_ld=out_ld)
     finally:
         FORCE_IGEMM = saved
     return _nchw_view(out)
