@@ -438,6 +438,47 @@ int lic_ctx_gather(const float* y, int64_t y_batch, int64_t y_row, int64_t y_pix
                    int64_t comb_ld, int32_t path, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2f -- lic_ctx_gather for rows that belong to DIFFERENT images: codec.ContextCodec.decompress_images
+ *   advances many bitstreams of different sizes together, and step t's rows of all of them are built by one launch.
+ *   All planes lie in one flat buffer, all psi planes in another; row, tap and column rules are lic_ctx_gather's.
+ *     y, y_len      the flat latent buffer and its length in floats; y_pix (>= M) is call-wide
+ *     images        [nimg][LIC_CTX_IMAGE_WORDS] int64 (device), per image: Y_BASE the plane's first float in y,
+ *                   Y_ROW its row pitch, Y_ORIGIN pixel (0, 0) behind the base (element (i, j, c) at
+ *                   y[Y_BASE + Y_ORIGIN + i * Y_ROW + j * y_pix + c]), PSI_BASE the first float of its [h*w][Cpsi]
+ *                   rows in psi, H, W, and R = its slice_rows (>= 1; >= H: no slices).  Word 7 is not read.
+ *     row_image, row_pix   [rows] int64 each (device): output row k is pixel row_pix[k] (raster, i * W + j) of image
+ *                   row_image[k]
+ *     win           out, [rows][nt*M] contiguous
+ *     psi, psi_len, comb   optional as in lic_ctx_gather; psi_len is the flat psi buffer's length in floats; row k of
+ *                   comb gets psi[PSI_BASE + row_pix[k] * Cpsi ...], Cpsi floats
+ *     path          as in lic_ctx_gather for what the entry can see: M, Cpsi, comb_ld, y_pix multiples of 4 and y, win
+ *                   (psi, comb) 16-byte aligned.  An image's Y_BASE, Y_ROW, Y_ORIGIN, PSI_BASE live on the device: in
+ *                   the 16-byte kernel a row whose image has one that is no multiple of 4 is moved float by float
+ *                   instead -- the kernel falls back per row, the entry does not refuse -- and gets the same bytes.
+ *   The kernel checks a descriptor before it addresses anything with it: bases, pitch and origin in [0, y_len]
+ *   ([0, psi_len]), 1 <= H, W <= 32768, R >= 1, the plane's last float Y_BASE + Y_ORIGIN + (H-1) Y_ROW + (W-1) y_pix
+ *   + M <= y_len and PSI_BASE + H W Cpsi <= psi_len.  A row whose image fails, whose row_image is outside [0, nimg) or
+ *   whose row_pix is outside [0, H*W) reads nothing and is written as zeros (win and comb).  Taps are applied only
+ *   where they stay inside the H x W pixels, so no address leaves y[0, y_len), psi[0, psi_len) whatever the tables say.
+ *   NULL y / images / taps / row_image / row_pix / win, psi without comb, nimg, M, rows, y_len <= 0, nt < 1, y_pix < M,
+ *   a float pointer that is not 4-byte or an int64 pointer that is not 8-byte aligned, LIC_CTX_VECTOR where the entry
+ *   sees it cannot hold: LIC_ERR_INVALID; y_len, psi_len, y_pix above 2^40: LIC_ERR_UNSUPPORTED; nothing launched.
+ *   One launch on `stream`, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define LIC_CTX_IMAGE_WORDS 8
+#define LIC_CTX_IMAGE_Y_BASE 0
+#define LIC_CTX_IMAGE_Y_ROW 1
+#define LIC_CTX_IMAGE_Y_ORIGIN 2
+#define LIC_CTX_IMAGE_PSI_BASE 3
+#define LIC_CTX_IMAGE_H 4
+#define LIC_CTX_IMAGE_W 5
+#define LIC_CTX_IMAGE_R 6
+int lic_ctx_gather_ragged(const float* y, int64_t y_len, int64_t y_pix, const int64_t* images, int32_t nimg, int32_t M,
+                          const int32_t* taps, int32_t nt, const int64_t* row_image, const int64_t* row_pix,
+                          int64_t rows, float* win, const float* psi, int64_t psi_len, int32_t Cpsi, float* comb,
+                          int64_t comb_ld, int32_t path, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).2 -- the device decoder of the "rANS-64" y streams (format and host coder: lic_codec.h).
  *   lic_rans_decode_step decodes ONE wavefront step of all B images in one launch, one wave per image, from the
  *   tables lic_gmm_cdf_tables has just built, and writes the values where the next step's gather reads them:
@@ -491,6 +532,35 @@ int lic_rans_decode_step_groups(const uint8_t* streams, const int64_t* stream_of
                                 const uint32_t* tables, const int32_t* center, int32_t B, int32_t G, int32_t n,
                                 int32_t M, int32_t W, const int64_t* dest, float* ypad, int64_t pixels,
                                 lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2f -- the same step for images that bring DIFFERENT numbers of rows to it, or none
+ *   (codec.ContextCodec.decompress_images): nimg * G workgroups of one wave; tables, centres and dest of the step are
+ *   the images' rows one after the other, total_rows in all.  The arguments of lic_rans_decode_step_groups, with
+ *     tables        [total_rows * M][2W+2] (16-byte aligned), center [total_rows * M], dest [total_rows]
+ *     seg           [nimg][2] int32 (device): image b's rows of this step are seg[b][0] .. seg[b][0] + seg[b][1] of
+ *                   those; its symbols number seg[b][1] * M, its tables start at dword seg[b][0] * M * (2W+2) -- any
+ *                   offset mod 4 -- and dest[seg[b][0] + k / M] is symbol k's pixel INSIDE the image's plane
+ *     ypad, ypad_len  one flat fp32 buffer and its length in floats; image b's plane is
+ *                   ypad[y_base[b] .. y_base[b] + pixels[b] * M), element (d, c) at y_base[b] + d * M + c;
+ *                   y_base, pixels: [nimg] int64 (device)
+ *   A wave whose image has seg[b][1] == 0 (finished, or idle in this step), or whose group has no round in the step,
+ *   returns before it reads its state block: the block stays bit for bit as it was.  Checked on the device before
+ *   anything is addressed: a segment with a negative entry or an end beyond total_rows sets LIC_RANS_ERR_RANGE in the
+ *   blocks of that image and decodes nothing; a plane that does not lie inside [0, ypad_len) counts as empty, so
+ *   every destination of the image is refused (LIC_RANS_ERR_RANGE, nothing written); a dest outside [0, pixels[b]) is
+ *   refused alike.  No table read goes beyond dword total_rows * M * (2W+2).  Cursor rules, error words and their
+ *   effect are lic_rans_decode_step's, per block.  With every image at seg[b] = (b * n, n), y_base[b] = b * pixels * M
+ *   this is lic_rans_decode_step_groups.
+ *   NULL pointers, nimg, total_rows, M, W, ypad_len <= 0, G outside 1..LIC_RANS_MAX_GROUPS, misaligned pointers
+ *   (tables 16 bytes, int64 arrays 8, the others 4): LIC_ERR_INVALID.  W > 64, total_rows * M >= 2^31 - 64,
+ *   nimg * G > 65535, ypad_len > 2^40: LIC_ERR_UNSUPPORTED.  One launch, no allocation, no synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+int lic_rans_decode_step_ragged(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
+                                const uint32_t* escapes, const int64_t* esc_off, uint32_t* state,
+                                const uint32_t* tables, const int32_t* center, const int32_t* seg, int32_t nimg,
+                                int32_t G, int64_t total_rows, int32_t M, int32_t W, const int64_t* dest, float* ypad,
+                                const int64_t* y_base, const int64_t* pixels, int64_t ypad_len, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).2 -- the device encoder of the same streams: byte for byte what the host encoder of lic_codec.h

@@ -77,6 +77,8 @@ class AdamJob(C.Structure):
 RANS_LANES, RANS_STATE_WORDS, RANS_MAX_GROUPS = 64, 67, 8
 
 CTX_AUTO, CTX_VECTOR, CTX_ELEMENT = range(3)
+# lic_ctx_gather_ragged's per-image descriptor: int64 words Y_BASE, Y_ROW, Y_ORIGIN, PSI_BASE, H, W, R, one unused
+CTX_IMAGE_WORDS = 8
 
 WINDOW_ZERO, WINDOW_REPLICATE, WINDOW_REFLECT = range(3)
 WINDOW_FLIP = 1
@@ -170,6 +172,9 @@ SIGNATURES = {
     "lic_rans_encode_groups": (C.c_int, [_vp] * 3 + [_i64, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "lic_ctx_gather": (C.c_int, [_vp] + [_i64] * 4 + [_i32] * 4 + [_vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _i64,
                                  _i32, _vp]),
+    "lic_ctx_gather_ragged": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
+                                        _vp, _i64, _i32, _vp]),
+    "lic_rans_decode_step_ragged": (C.c_int, [_vp] * 9 + [_i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "lic_msssim_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "lic_msssim": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _sz,
                              _vp]),

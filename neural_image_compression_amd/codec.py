@@ -31,13 +31,17 @@ the default, is the format above.
 each other, so all slices decode side by side: w + 3 (min(R, h) - 1) dependent steps instead of w + 3 (h - 1), paid
 for in rate by the first rows of every slice (DESIGN 1.1 f.2e has the rule).  Both sides build the rows their
 per-pixel layers read with one gather, `lic_ctx_gather`, which applies that rule.
+
+`ContextCodec.decompress_images(blobs)` decodes many `compress_image` blobs of different sizes together: step t of
+every image shares one gather (`lic_ctx_gather_ragged`), one pass through the per-pixel layers and one decode launch
+(`lic_rans_decode_step_ragged`), by the schedule of `merged_wavefront`; entry i is bit for bit `decompress_image(blobs[i])`.
 """
 from __future__ import annotations
 
 import ctypes as C
 import zlib
 import os
-from typing import Dict
+from typing import Dict, List, NamedTuple, Sequence
 
 import numpy as np
 import torch
@@ -273,18 +277,122 @@ def wavefront(h: int, w: int, pad: int, slice_rows: int = None):
     return steps
 
 
-def _state_blocks(d_state: torch.Tensor, G: int, problem):
+def _image_name(img: int) -> str:
+    return f"image {img}"
+
+
+def _state_blocks(d_state: torch.Tensor, G: int, problem, name=_image_name):
     """The one read-back of a rANS kernel's state blocks [blocks][RANS_STATE_WORDS] (lic.h: 64 coder states, word
     count, escape count, error word), image-major with G blocks per image -> [(states uint32 [64], words, escapes)].
     `problem(i, states, words, escapes, error word)` says what is wrong with block i, if anything: the first such
-    block raises CodecError, named by its image."""
+    block raises CodecError, named by its image (`name(image)`, `_image_name` by default)."""
     blocks = []
     for i, row in enumerate(d_state.cpu().numpy().view(np.uint32)):
         blocks.append((row[:RANS_LANES], int(row[RANS_LANES]), int(row[RANS_LANES + 1])))
         what = problem(i, *blocks[-1], int(row[RANS_LANES + 2]))
         if what:
-            raise CodecError(f"image {i // G}: {what}")
+            raise CodecError(f"{name(i // G)}: {what}")
     return blocks
+
+
+class MergedSchedule(NamedTuple):
+    """what `merged_wavefront` returns, uploaded once per call.  Image b's step lengths, as `compress` orders its
+    symbols and `rans_deal` reads them, are seg[:, b, 1] * M up to the image's last step."""
+    T: int                    # steps of the call: the largest step count of any image
+    seg: np.ndarray           # [T][nimg][2] int32: (first row, rows) of image b inside step t's row batch
+    rows: np.ndarray          # [3][sum of h*w] int64, steps concatenated: image index, raster pixel index inside the
+    #                           image, destination pixel index inside its zero-framed (h + 2 pad) x (w + 2 pad) plane
+    step_off: np.ndarray      # [T + 1] int64: step t's rows are rows[:, step_off[t]:step_off[t + 1]]
+
+
+def merged_wavefront(shapes, pad: int, slice_rows_list) -> MergedSchedule:
+    """The decode schedule of several latent planes advanced together.  shapes: [(h, w)] per image; slice_rows_list:
+    each image's slice_rows (None: no slices).  Step t of the call is step t of every image that still has one, images
+    in list order; inside an image the order is exactly `wavefront(h, w, pad, R)`'s.  An image that has finished keeps
+    a segment of 0 rows whose first row is the running sum, so every segment is well defined.
+    No loop over steps: every pixel gets its step number, and one stable sort by (step, image) of the pixels in
+    raster order, image after image, leaves them step by step, image by image, rows ascending."""
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    slice_rows_list = list(slice_rows_list)
+    if len(slice_rows_list) != len(shapes):
+        raise CodecError("one slice_rows entry per image expected")
+    nimg, k = len(shapes), pad + 1
+    kinds, per = {}, []                                          # images of one shape and slice height share their arrays
+    for (h, w), R in zip(shapes, slice_rows_list):
+        if (h, w, R) not in kinds:
+            Reff = h if R is None else min(_slice_rows(R), h)
+            i, j = np.repeat(np.arange(h, dtype=np.int64), w), np.tile(np.arange(w, dtype=np.int64), h)
+            # `wavefront` leaves out the steps that hold no pixel (w < pad + 1 only): number the ones that remain
+            _, t = np.unique(j + k * (i % Reff), return_inverse=True)
+            kinds[h, w, R] = (t.astype(np.int64).ravel(), i * w + j, (i + pad) * (w + 2 * pad) + j + pad)
+        per.append(kinds[h, w, R])
+    if not per:
+        return MergedSchedule(0, np.zeros((0, 0, 2), np.int32), np.zeros((3, 0), np.int64), np.zeros(1, np.int64))
+    step = np.concatenate([a[0] for a in per])
+    image = np.repeat(np.arange(nimg, dtype=np.int64), [a[0].size for a in per])
+    T = int(step.max()) + 1
+    key = step * nimg + image
+    order = np.argsort(key, kind="stable")
+    rows = np.stack([image, np.concatenate([a[1] for a in per]), np.concatenate([a[2] for a in per])])[:, order]
+    count = np.bincount(key, minlength=T * nimg).reshape(T, nimg)
+    seg = np.stack([np.cumsum(count, 1) - count, count], 2).astype(np.int32)
+    step_off = np.concatenate([[0], np.cumsum(count.sum(1))]).astype(np.int64)
+    return MergedSchedule(T, seg, np.ascontiguousarray(rows), step_off)
+
+
+def _step_indices(steps, w: int, pad: int) -> np.ndarray:
+    """[2][pixels] int64 for the steps of one plane (`wavefront`), concatenated: the raster index i * w + j of every
+    pixel and its index inside the zero-framed (h + 2 pad) x (w + 2 pad) plane"""
+    Wp = w + 2 * pad
+    return np.stack([np.concatenate([ii * w + jj for ii, jj in steps]),
+                     np.concatenate([(ii + pad) * Wp + jj + pad for ii, jj in steps])])
+
+
+class _RansStaging:
+    """The streams, escape lists and state blocks of `nimg * G` rANS blocks (image-major) as the decode kernels take
+    them: every stream on a 4-byte boundary of one buffer, offsets, lengths and seeds in one array each.  The
+    constructor is host only and refuses what cannot be staged; `upload` sends the six arrays once; `check` is the one
+    read-back after the last step.  `name(image)` labels an image in the messages."""
+
+    def __init__(self, ys, escs, nimg: int, G: int, name=_image_name):
+        B = nimg * G
+        if escs is None or len(ys) != B or len(escs) != B:
+            raise CodecError("one y stream and one escape list per image and group expected")
+        head = 4 * RANS_LANES
+        for b in range(B):
+            if len(ys[b]) < head or len(ys[b]) % 2 or len(escs[b]) % 4:
+                raise CodecError(f"{name(b // G)}: y stream or escape list has an impossible length")
+        # staging: every stream starts on a 4-byte boundary; offsets, lengths and seeds in one upload each
+        s_off = np.zeros(B + 1, np.int64)
+        for b in range(B):
+            s_off[b + 1] = s_off[b] + (len(ys[b]) + 3) // 4 * 4
+        s_len = np.array([len(s) for s in ys], np.int64)
+        buf = np.zeros(int(s_off[B]), np.uint8)
+        state = np.zeros((B, L.RANS_STATE_WORDS), np.uint32)
+        for b in range(B):
+            buf[s_off[b]:s_off[b] + len(ys[b])] = np.frombuffer(ys[b], np.uint8)
+            state[b, :RANS_LANES] = np.frombuffer(ys[b][:head], np.dtype("<u4"))
+        e_off = np.concatenate([[0], np.cumsum([len(e) // 4 for e in escs])]).astype(np.int64)
+        e_all = np.frombuffer(b"".join(escs) + b"\0\0\0\0", np.dtype("<u4")).astype(np.uint32)
+        self.ys, self.escs, self.G, self.name = ys, escs, G, name
+        self.host = (buf, s_off, s_len, e_all.view(np.int32), e_off, state.view(np.int32))
+
+    def upload(self, dev):
+        """-> the kernels' first six arguments: streams, stream_off, stream_bytes, escapes, esc_off, state"""
+        self.dev = tuple(torch.from_numpy(a).to(dev) for a in self.host)
+        return tuple(F_._ptr(t) for t in self.dev)
+
+    def check(self):
+        ys, escs, head = self.ys, self.escs, 4 * RANS_LANES
+
+        def problem(b, states, nw, ne, err):
+            if err:
+                return (f"the rANS decoder ran past the end of its stream or escape list (error word {err}): "
+                        "the stream is damaged")
+            if nw != (len(ys[b]) - head) // 2 or ne != len(escs[b]) // 4 or (states != 1 << 16).any():
+                return ("the rANS stream was not used up exactly (trailing words or escapes, or final states that are "
+                        "not the encoder's start): the stream is damaged")
+        _state_blocks(self.dev[5], self.G, problem, self.name)                            # the one read-back
 
 
 class LatentCodec:
@@ -502,6 +610,28 @@ class ContextCodec:
         m = self.model
         return gmm_tables(self._act_at(windows, psi_px, layers, comb), m.M, m.K, self.y_W)
 
+    def _taps_on(self, dev) -> torch.Tensor:
+        """the live taps as (dr, ds) int32 pairs on `dev`, uploaded once"""
+        if getattr(self, "_taps_dev", None) is None or self._taps_dev.device != dev:
+            self._taps_dev = torch.tensor([(r - self.pad, s - self.pad) for (r, s) in self.taps], dtype=torch.int32,
+                                          device=dev)
+        return self._taps_dev
+
+    def _gather_ragged(self, yflat: torch.Tensor, images: torch.Tensor, row_image: torch.Tensor, row_pix: torch.Tensor,
+                       psiflat: torch.Tensor, cpsi: int):
+        """One `lic_ctx_gather_ragged` launch: `_gather` for rows of different images.  yflat, psiflat: the flat
+        buffers all planes lie in; images [nimg, CTX_IMAGE_WORDS] int64 (device): where, and h, w, R of each;
+        row_image, row_pix [n] int64 (device): the image and raster index of every row -> (windows, comb) as `_gather`"""
+        M, n, nt, dev = self.model.M, row_pix.numel(), len(self.taps), yflat.device
+        cctx = self.model.context_model.masked.out_channels
+        win = torch.empty((n, nt * M, 1, 1), device=dev, dtype=torch.float32)
+        comb = torch.empty((n, cctx + cpsi), device=dev, dtype=torch.float32)
+        L.check(L.load().lic_ctx_gather_ragged(
+            F_._ptr(yflat), yflat.numel(), M, F_._ptr(images), images.shape[0], M, F_._ptr(self._taps_on(dev)), nt,
+            F_._ptr(row_image), F_._ptr(row_pix), n, F_._ptr(win), F_._ptr(psiflat), psiflat.numel(), cpsi,
+            C.c_void_p(comb.data_ptr() + 4 * cctx), comb.shape[1], L.CTX_AUTO, F_._stream()), "lic_ctx_gather_ragged")
+        return win, comb
+
     def _gather(self, y: torch.Tensor, geometry, h: int, w: int, pix: torch.Tensor, slice_rows, psi_flat=None):
         """One `lic_ctx_gather` launch.  y: fp32 latents of B images, pixel (i, j) of image b at float
         b * batch + origin + i * row + j * M for geometry = (batch, row, origin); pix: int64 raster indices (device)
@@ -509,9 +639,7 @@ class ContextCodec:
         -> (windows [B*n, 12M, 1, 1] with zeros for taps outside the image or the pixel's slice,
             comb [B*n, 4M] whose last 2M columns hold the pixels' psi, the first 2M still unwritten; None without psi)"""
         B, M, n, nt, dev = y.shape[0], self.model.M, pix.numel(), len(self.taps), y.device
-        if getattr(self, "_taps_dev", None) is None or self._taps_dev.device != dev:
-            self._taps_dev = torch.tensor([(r - self.pad, s - self.pad) for (r, s) in self.taps], dtype=torch.int32,
-                                          device=dev)
+        self._taps_on(dev)
         win = torch.empty((B * n, nt * M, 1, 1), device=dev, dtype=torch.float32)
         comb = cpsi = None
         if psi_flat is not None:
@@ -689,8 +817,7 @@ class ContextCodec:
         layers = self._prepack()
         psi_flat = F_._nhwc(psi).view(B, h * w, -1)                                       # [B, h*w, 2M]
         Wp = w + 2 * p
-        idx = torch.from_numpy(np.stack([np.concatenate([ii * w + jj for ii, jj in steps]),
-                                         np.concatenate([(ii + p) * Wp + jj + p for ii, jj in steps])])).to(yflat.device)
+        idx = torch.from_numpy(_step_indices(steps, w, p)).to(yflat.device)
         geometry = (yflat.shape[1] * M, Wp * M, (p * Wp + p) * M)
 
         def run():
@@ -709,46 +836,15 @@ class ContextCodec:
         device; the state blocks (error words, cursors, final states) come back once, after the last step.  One block
         per image and group (`strings["groups"]`, 1 if absent), image-major; below B counts blocks."""
         nimg, npad, M = yflat.shape
-        dev = yflat.device
         G = _groups(strings.get("groups", 1))
-        B = nimg * G
-        ys, escs = strings["y"], strings.get("y_esc")
-        if escs is None or len(ys) != B or len(escs) != B:
-            raise CodecError("one y stream and one escape list per image and group expected")
-        head = 4 * RANS_LANES
-        for b in range(B):
-            if len(ys[b]) < head or len(ys[b]) % 2 or len(escs[b]) % 4:
-                raise CodecError(f"image {b // G}: y stream or escape list has an impossible length")
-        # staging: every stream starts on a 4-byte boundary; offsets, lengths and seeds in one upload each
-        s_off = np.zeros(B + 1, np.int64)
-        for b in range(B):
-            s_off[b + 1] = s_off[b] + (len(ys[b]) + 3) // 4 * 4
-        s_len = np.array([len(s) for s in ys], np.int64)
-        buf = np.zeros(int(s_off[B]), np.uint8)
-        state = np.zeros((B, L.RANS_STATE_WORDS), np.uint32)
-        for b in range(B):
-            buf[s_off[b]:s_off[b] + len(ys[b])] = np.frombuffer(ys[b], np.uint8)
-            state[b, :RANS_LANES] = np.frombuffer(ys[b][:head], np.dtype("<u4"))
-        e_off = np.concatenate([[0], np.cumsum([len(e) // 4 for e in escs])]).astype(np.int64)
-        e_all = np.frombuffer(b"".join(escs) + b"\0\0\0\0", np.dtype("<u4")).astype(np.uint32)
-        d_buf, d_esc = torch.from_numpy(buf).to(dev), torch.from_numpy(e_all.view(np.int32)).to(dev)
-        d_soff, d_slen, d_eoff = (torch.from_numpy(a).to(dev) for a in (s_off, s_len, e_off))
-        d_state = torch.from_numpy(state.view(np.int32)).to(dev)
+        staged = _RansStaging(strings["y"], strings.get("y_esc"), nimg, G)
+        blocks = staged.upload(yflat.device)
         lib = L.load()
         for n, own, center, tables in front:
-            L.check(lib.lic_rans_decode_step_groups(F_._ptr(d_buf), F_._ptr(d_soff), F_._ptr(d_slen), F_._ptr(d_esc),
-                                                    F_._ptr(d_eoff), F_._ptr(d_state), F_._ptr(tables),
-                                                    F_._ptr(center), nimg, G, n, M, self.y_W, F_._ptr(own),
-                                                    F_._ptr(yflat), npad, F_._stream()), "lic_rans_decode_step_groups")
-
-        def problem(b, states, nw, ne, err):
-            if err:
-                return (f"the rANS decoder ran past the end of its stream or escape list (error word {err}): "
-                        "the stream is damaged")
-            if nw != (len(ys[b]) - head) // 2 or ne != len(escs[b]) // 4 or (states != 1 << 16).any():
-                return ("the rANS stream was not used up exactly (trailing words or escapes, or final states that are "
-                        "not the encoder's start): the stream is damaged")
-        _state_blocks(d_state, G, problem)                                                # the one read-back
+            L.check(lib.lic_rans_decode_step_groups(*blocks, F_._ptr(tables), F_._ptr(center), nimg, G, n, M, self.y_W,
+                                                    F_._ptr(own), F_._ptr(yflat), npad, F_._stream()),
+                    "lic_rans_decode_step_groups")
+        staged.check()
 
     def _finish(self, strings, ypad, z_hat, shape) -> Dict:
         """checksum of the decoded latents, then the synthesis transform"""
@@ -763,6 +859,106 @@ class ContextCodec:
         y_hat = ypad[:, p:p + h, p:p + w, :].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
         x_hat = m.decoder(y_hat)
         return {"x_hat": x_hat, "y_hat": y_hat, "z_hat": z_hat}
+
+    # ---- many bitstreams in one step loop -------------------------------------------------------
+    @torch.no_grad()
+    def decompress_many(self, items, z_windows=None, names=None) -> List[Dict]:
+        """`decompress` for several bitstreams at once.  items: [(strings, shape, z_shape)] as `decompress` takes
+        them, all of the "rans" coder, this codec's y_W and one G; they may differ in B, h, w and slice_rows.
+        z_windows: [(z_lo, z_S)] per item (default: this codec's); names: what to call an item in a message (default
+        "item i").  -> one `decompress` result per item, bit for bit what `decompress` gives for it alone.
+
+        Per item the hyper-latent is decoded and the hyper-decoder run exactly as `decompress` does.  All psi planes
+        and all zero-framed latent planes lie in two flat buffers, every item's on a multiple of 4 floats; streams,
+        escape lists and state blocks of all images are staged once.  Then ONE loop of T steps (`merged_wavefront`),
+        each {lic_ctx_gather_ragged -> per-pixel layers and tables over the step's rows of every image ->
+        lic_rans_decode_step_ragged}: no copy, no synchronisation, no host arithmetic.  Then one read-back of the state
+        blocks, and `_finish` per item on a view of its planes.  Everything the host can refuse is refused before
+        the device is touched."""
+        m, p = self.model, self.pad
+        M = m.M
+        items = list(items)
+        if not items:
+            return []
+        names = [f"item {i}" for i in range(len(items))] if names is None else list(names)
+        z_windows = [(self.z_lo, self.z_S)] * len(items) if z_windows is None else list(z_windows)
+        G, shapes, Rs, owner, ys, escs = None, [], [], [], [], []
+        for i, (strings, shape, _) in enumerate(items):
+            if strings.get("coder", "range") != "rans":
+                raise CodecError(f"{names[i]}: only streams of the 'rans' coder decode together (the range coder's "
+                                 "loop waits for the host at every step)")
+            g = _groups(strings.get("groups", 1))
+            if G is not None and g != G:
+                raise CodecError(f"{names[i]}: {g} sub-streams per image, {names[0]} has {G}: one call decodes one G")
+            G = g
+            B, Mi, h, w = shape
+            if Mi != M:
+                raise CodecError(f"{names[i]}: {Mi} latent channels, this model has {M}")
+            try:
+                R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
+            except CodecError as err:
+                raise CodecError(f"{names[i]}: {err}") from None
+            if strings.get("y_esc") is None or len(strings["y"]) != B * G or len(strings["y_esc"]) != B * G:
+                raise CodecError(f"{names[i]}: one y stream and one escape list per image and group expected")
+            shapes += [(h, w)] * B
+            Rs += [R] * B
+            owner += [(i, b) for b in range(B)]
+            ys += list(strings["y"])
+            escs += list(strings["y_esc"])
+        nimg = len(shapes)
+        staged = _RansStaging(ys, escs, nimg, G, lambda img: f"{names[owner[img][0]]}: image {owner[img][1]}")
+        sched = merged_wavefront(shapes, p, Rs)
+        # ---- the device from here on
+        dev = next(m.parameters()).device
+        z_hats, psis = [], []
+        for i, ((strings, _, z_shape), (z_lo, z_S)) in enumerate(zip(items, z_windows)):
+            try:
+                z_hat = LatentCodec(m, z_lo, z_S, self.y_W).decompress_z(strings["z"], z_shape)
+            except CodecError as err:
+                raise CodecError(f"{names[i]}: {err}") from None
+            z_hats.append(z_hat.contiguous(memory_format=torch.channels_last))
+            psis.append(m.hyper_decoder(z_hats[-1]).float())
+        cpsi = psis[0].shape[1]
+        # the layout: item after item, each on a multiple of 4 floats, its B planes one behind the other
+        y_at, psi_at, y_len, psi_len, img = [], [], 0, 0, 0
+        desc = np.zeros((nimg, L.CTX_IMAGE_WORDS), np.int64)
+        for _, (B, _, h, w), _ in items:
+            y_at.append((y_len + 3) // 4 * 4)
+            psi_at.append((psi_len + 3) // 4 * 4)
+            Wp, plane = w + 2 * p, (h + 2 * p) * (w + 2 * p) * M
+            for b in range(B):
+                desc[img, :7] = (y_at[-1] + b * plane, Wp * M, (p * Wp + p) * M, psi_at[-1] + b * h * w * cpsi, h, w,
+                                 h if Rs[img] is None else min(Rs[img], h))
+                img += 1
+            y_len, psi_len = y_at[-1] + B * plane, psi_at[-1] + B * h * w * cpsi
+        yflat = torch.zeros(y_len, device=dev, dtype=torch.float32)                # decoded latents inside zero frames
+        psiflat = torch.empty(psi_len, device=dev, dtype=torch.float32)
+        for i, (_, (B, _, h, w), _) in enumerate(items):
+            psiflat[psi_at[i]:psi_at[i] + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psis[i]).view(B, h * w, -1))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        d_desc, d_rows, d_seg = up(desc), up(sched.rows), up(sched.seg)
+        d_ybase = up(desc[:, 0])
+        d_pixels = up(np.array([(h + 2 * p) * (w + 2 * p) for h, w in shapes], np.int64))
+        blocks = staged.upload(dev)
+        layers, lib, off = self._prepack(), L.load(), sched.step_off
+        for t in range(sched.T):
+            a, e = int(off[t]), int(off[t + 1])
+            win, comb = self._gather_ragged(yflat, d_desc, d_rows[0, a:e], d_rows[1, a:e], psiflat, cpsi)
+            center, tables = self._params_at(win, None, layers, comb)
+            L.check(lib.lic_rans_decode_step_ragged(*blocks, F_._ptr(tables), F_._ptr(center), F_._ptr(d_seg[t]), nimg,
+                                                    G, e - a, M, self.y_W, F_._ptr(d_rows[2, a:e]), F_._ptr(yflat),
+                                                    F_._ptr(d_ybase), F_._ptr(d_pixels), y_len, F_._stream()),
+                    "lic_rans_decode_step_ragged")
+        staged.check()
+        out = []
+        for i, (strings, shape, _) in enumerate(items):
+            B, _, h, w = shape
+            ypad = yflat[y_at[i]:y_at[i] + B * (h + 2 * p) * (w + 2 * p) * M].view(B, h + 2 * p, w + 2 * p, M)
+            try:
+                out.append(self._finish(strings, ypad, z_hats[i], shape))
+            except CodecError as err:
+                raise CodecError(f"{names[i]}: {err}") from None
+        return out
 
     # ---- self-describing container: one byte string per batch, any image size ---------------------
     def _family(self) -> int:
@@ -804,6 +1000,19 @@ class ContextCodec:
         """The inverse of `compress_image`: x_hat [B,3,H,W] (channels_last).  Raises CodecError, before any GPU
         work, for a bad magic, a truncated buffer, a failing CRC or a header whose family / M / K are not this
         model's.  The magic selects the coder, whatever this codec's own is."""
+        head, strings = self._open_blob(data)
+        m = self.model
+        B, H, W, top, left = (head[k] for k in ("B", "H", "W", "top", "left"))
+        Hp, Wp = -(-H // 64) * 64, -(-W // 64) * 64
+        dec = self
+        if (head["z_lo"], head["z_S"], head["y_W"]) != (self.z_lo, self.z_S, self.y_W):
+            dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"], strings.get("coder", "range"))
+        out = dec.decompress(strings, (B, m.M, Hp // 16, Wp // 16), (B, m.M, Hp // 64, Wp // 64))
+        return F_.crop_window(out["x_hat"], top, left, H, W)
+
+    def _open_blob(self, data: bytes):
+        """`decompress_image`'s host half -> (header, the strings `decompress` takes).  Its refusals, in order: the
+        container reader's (`_unpack`), a window the rANS decoder does not take, a model that is not this one."""
         fmt = _FORMAT_OF_MAGIC.get(bytes(data[:8]), ("range", False))         # an unknown magic: LICBITS1's reader says so
         head, z_bytes, y_streams, y_esc, y_crc, G = _unpack(fmt, data)
         strings = {"y": y_streams, "z": z_bytes, "y_crc32": y_crc}
@@ -818,10 +1027,45 @@ class ContextCodec:
         if (head["family"], head["M"], head["K"]) != (self._family(), m.M, m.K):
             raise CodecError(f"bitstream was written by family {head['family']} with M={head['M']}, K={head['K']}; "
                              f"this model is family {self._family()} with M={m.M}, K={m.K}")
-        B, H, W, top, left = (head[k] for k in ("B", "H", "W", "top", "left"))
-        Hp, Wp = -(-H // 64) * 64, -(-W // 64) * 64
-        dec = self
-        if (head["z_lo"], head["z_S"], head["y_W"]) != (self.z_lo, self.z_S, self.y_W):
-            dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"], strings.get("coder", "range"))
-        out = dec.decompress(strings, (B, m.M, Hp // 16, Wp // 16), (B, m.M, Hp // 64, Wp // 64))
-        return F_.crop_window(out["x_hat"], top, left, H, W)
+        return head, strings
+
+    @torch.no_grad()
+    def decompress_images(self, blobs: Sequence[bytes]) -> List[torch.Tensor]:
+        """Many `compress_image` blobs in one decode loop: entry i is bit for bit `decompress_image(blobs[i])`,
+        [B_i, 3, H_i, W_i], channels_last, cropped.  The blobs may differ in size, batch, crop, slice_rows, z window and
+        between LICBITS2 / 3 / 4; step t of all their images shares its launches (`decompress_many`), so a folder of
+        blobs costs about one blob's step loop plus every blob's transforms.  Raises CodecError before any GPU work,
+        every message naming its blob ("blob i: ..."): whatever `decompress_image` refuses for blob i; a LICBITS1 blob
+        (the range coder's loop waits for the host at every step: nothing to merge); a y_W or a G (sub-streams per
+        image; 1 for LICBITS2) that is not blob 0's.  An empty list gives an empty list."""
+        blobs = list(blobs)
+        opened = []
+        for i, data in enumerate(blobs):
+            try:
+                opened.append(self._open_blob(data))
+            except CodecError as err:
+                raise CodecError(f"blob {i}: {err}") from None
+        if not opened:
+            return []
+        for i, (head, strings) in enumerate(opened):
+            if strings.get("coder", "range") != "rans":
+                raise CodecError(f"blob {i}: a LICBITS1 blob (range coder) cannot join a batched decode: its loop waits "
+                                 "for the host at every step; decode it with decompress_image")
+        y_W, G = opened[0][0]["y_W"], opened[0][1].get("groups", 1)
+        for i, (head, strings) in enumerate(opened):
+            if head["y_W"] != y_W:
+                raise CodecError(f"blob {i}: y_W = {head['y_W']}, blob 0 has y_W = {y_W}: one call decodes one window")
+        for i, (head, strings) in enumerate(opened):
+            if strings.get("groups", 1) != G:
+                raise CodecError(f"blob {i}: G = {strings.get('groups', 1)} sub-streams per image, blob 0 has G = {G}: "
+                                 "one call decodes one G")
+        m = self.model
+        items = []
+        for head, strings in opened:
+            Hp, Wp = -(-head["H"] // 64) * 64, -(-head["W"] // 64) * 64
+            items.append((strings, (head["B"], m.M, Hp // 16, Wp // 16), (head["B"], m.M, Hp // 64, Wp // 64)))
+        dec = self if y_W == self.y_W else ContextCodec(m, self.z_lo, self.z_S, y_W, "rans")
+        outs = dec.decompress_many(items, [(head["z_lo"], head["z_S"]) for head, _ in opened],
+                                   [f"blob {i}" for i in range(len(opened))])
+        return [F_.crop_window(out["x_hat"], head["top"], head["left"], head["H"], head["W"])
+                for out, (head, _) in zip(outs, opened)]

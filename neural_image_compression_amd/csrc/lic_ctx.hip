@@ -12,6 +12,13 @@
 // Both paths write the same bytes.  Every address is decided from (i, j, dr, ds, R, h, w) before the load: nothing
 // outside the h x w pixels of the plane is read, whatever surrounds them, and a pixel index outside [0, h*w) reads
 // nothing and writes a row of zeros.
+//
+// lic_ctx_gather_ragged: the same rows for pixels of DIFFERENT images in one launch (codec.ContextCodec.decompress_images:
+// step t of many bitstreams at once).  Every row names its image and its pixel; an image's geometry (plane base, row
+// pitch, origin, psi base, h, w, R) comes from a device table of LIC_CTX_IMAGE_WORDS int64 per image, which the kernel
+// checks against the buffers' lengths before it addresses anything: a descriptor that fails, like a bad image or pixel
+// index, gives a row of zeros and no read.  The 16-byte kernel moves a row float by float when its image's bases are
+// not multiples of 4 floats: the same bytes either way.
 #include "lic_common.h"
 
 namespace {
@@ -63,6 +70,92 @@ __global__ __launch_bounds__(256) void ctx_gather_kernel(const CtxGatherParams p
 
 inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
+// ---- rows of different images ------------------------------------------------------------------------------------
+constexpr int64_t kMaxSide = 1 << 15;            // h, w of one latent plane: keeps every product below in 64 bits
+constexpr int64_t kMaxFloats = (int64_t)1 << 40;  // y_len, psi_len
+
+struct CtxRaggedParams {
+  const float* y;
+  const int64_t* images;
+  const int32_t* taps;
+  const int64_t* row_image;
+  const int64_t* row_pix;
+  const float* psi;
+  float* win;
+  float* comb;
+  int64_t y_len, y_pix, psi_len, comb_ld, rows;
+  int32_t nimg, M, nt, Cpsi;
+};
+
+struct CtxImage {
+  int64_t y_base, y_row, y_origin, psi_base, h, w, R;
+};
+
+// the descriptor of image b if every address it can produce lies inside y[0, y_len) and psi[0, psi_len)
+__device__ __forceinline__ bool ctx_image(const CtxRaggedParams& p, int64_t b, CtxImage& g) {
+  if (b < 0 || b >= p.nimg) return false;
+  const int64_t* d = p.images + b * LIC_CTX_IMAGE_WORDS;
+  g.y_base = d[LIC_CTX_IMAGE_Y_BASE];
+  g.y_row = d[LIC_CTX_IMAGE_Y_ROW];
+  g.y_origin = d[LIC_CTX_IMAGE_Y_ORIGIN];
+  g.psi_base = d[LIC_CTX_IMAGE_PSI_BASE];
+  g.h = d[LIC_CTX_IMAGE_H];
+  g.w = d[LIC_CTX_IMAGE_W];
+  g.R = d[LIC_CTX_IMAGE_R];
+  if (g.h < 1 || g.h > kMaxSide || g.w < 1 || g.w > kMaxSide || g.R < 1) return false;
+  if (g.y_base < 0 || g.y_base > p.y_len || g.y_row < 0 || g.y_row > p.y_len || g.y_origin < 0 || g.y_origin > p.y_len)
+    return false;
+  // the last float of the last pixel: every term is below 2^55
+  if (g.y_base + g.y_origin + (g.h - 1) * g.y_row + (g.w - 1) * p.y_pix + p.M > p.y_len) return false;
+  if (p.psi && (g.psi_base < 0 || g.psi_base > p.psi_len || g.psi_base + g.h * g.w * p.Cpsi > p.psi_len)) return false;
+  return true;
+}
+
+// one row in pieces of V floats; `ok` false: zeros, nothing read
+template <int V>
+__device__ __forceinline__ void ctx_ragged_row(const CtxRaggedParams& p, int64_t row, bool ok, const CtxImage& g,
+                                               int64_t px) {
+  typedef float piece __attribute__((ext_vector_type(V)));
+  const int Mq = p.M / V, Cq = p.psi ? p.Cpsi / V : 0;
+  const int nwin = p.nt * Mq, per_row = nwin + Cq;
+  const int h = ok ? (int)g.h : 1, w = ok ? (int)g.w : 1;
+  const int i = ok ? (int)(px / w) : 0, j = ok ? (int)(px - (int64_t)i * w) : 0;
+  const int64_t ri = ok ? i % g.R : 0;  // row inside the pixel's slice
+  const float* yb = p.y + (ok ? g.y_base + g.y_origin : 0);
+  float* wrow = p.win + row * ((int64_t)p.nt * p.M);
+  for (int e = threadIdx.x; e < per_row; e += 256) {
+    if (e < nwin) {
+      const int t = e / Mq, c = (e - t * Mq) * V;
+      const int dr = p.taps[2 * t], ds = p.taps[2 * t + 1];
+      // 64 bits: a tap table with absurd offsets must not wrap back into the plane
+      const int64_t si = (int64_t)i + dr, sj = (int64_t)j + ds;
+      const bool live = ok && si >= 0 && si < h && sj >= 0 && sj < w && (dr >= 0 || ri + dr >= 0);
+      piece v = {};
+      if (live) v = *reinterpret_cast<const piece*>(yb + si * g.y_row + sj * p.y_pix + c);
+      *reinterpret_cast<piece*>(wrow + (int64_t)e * V) = v;
+    } else {
+      const int c = (e - nwin) * V;
+      piece v = {};
+      if (ok) v = *reinterpret_cast<const piece*>(p.psi + g.psi_base + px * p.Cpsi + c);
+      *reinterpret_cast<piece*>(p.comb + row * p.comb_ld + c) = v;
+    }
+  }
+}
+
+// V as in ctx_gather_kernel; with V = 4 a row whose image is not laid out in multiples of 4 floats goes by floats
+template <int V>
+__global__ __launch_bounds__(256) void ctx_gather_ragged_kernel(const CtxRaggedParams p) {
+  for (int64_t row = blockIdx.x; row < p.rows; row += gridDim.x) {
+    const int64_t b = p.row_image[row], px = p.row_pix[row];
+    CtxImage g = {};
+    const bool ok = ctx_image(p, b, g) && px >= 0 && px < g.h * g.w;
+    if (V == 1 || (ok && ((g.y_base | g.y_row | g.y_origin | g.psi_base) & 3)))
+      ctx_ragged_row<1>(p, row, ok, g, px);
+    else
+      ctx_ragged_row<V>(p, row, ok, g, px);
+  }
+}
+
 }  // namespace
 
 LIC_EXPORT int lic_ctx_gather(const float* y, int64_t y_batch, int64_t y_row, int64_t y_pix, int64_t y_origin,
@@ -110,5 +203,52 @@ LIC_EXPORT int lic_ctx_gather(const float* y, int64_t y_batch, int64_t y_row, in
     hipLaunchKernelGGL(ctx_gather_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(ctx_gather_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  return lic_check_launch();
+}
+
+LIC_EXPORT int lic_ctx_gather_ragged(const float* y, int64_t y_len, int64_t y_pix, const int64_t* images, int32_t nimg,
+                                     int32_t M, const int32_t* taps, int32_t nt, const int64_t* row_image,
+                                     const int64_t* row_pix, int64_t rows, float* win, const float* psi,
+                                     int64_t psi_len, int32_t Cpsi, float* comb, int64_t comb_ld, int32_t path,
+                                     lic_stream_t stream) {
+  if (!y || !images || !taps || !row_image || !row_pix || !win) return LIC_ERR_INVALID;
+  if (nimg <= 0 || M <= 0 || rows <= 0 || nt < 1 || y_len <= 0 || y_pix < M) return LIC_ERR_INVALID;
+  if (psi && (!comb || Cpsi <= 0 || comb_ld < Cpsi || psi_len <= 0)) return LIC_ERR_INVALID;
+  if (path != LIC_CTX_AUTO && path != LIC_CTX_VECTOR && path != LIC_CTX_ELEMENT) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(win) | reinterpret_cast<uintptr_t>(psi) |
+       reinterpret_cast<uintptr_t>(comb) | reinterpret_cast<uintptr_t>(taps)) & 3)
+    return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(row_image) |
+       reinterpret_cast<uintptr_t>(row_pix)) & 7)
+    return LIC_ERR_INVALID;
+  if ((int64_t)nt * M + (psi ? Cpsi : 0) > 0x7FFFFFFFL - 256 || rows > (1LL << 40) || y_len > kMaxFloats ||
+      y_pix > kMaxFloats || (psi && psi_len > kMaxFloats))
+    return LIC_ERR_UNSUPPORTED;
+  const bool can_vec = M % 4 == 0 && aligned16(y) && aligned16(win) && y_pix % 4 == 0 &&
+                       (!psi || (Cpsi % 4 == 0 && comb_ld % 4 == 0 && aligned16(psi) && aligned16(comb)));
+  if (path == LIC_CTX_VECTOR && !can_vec) return LIC_ERR_INVALID;
+  CtxRaggedParams p;
+  p.y = y;
+  p.images = images;
+  p.taps = taps;
+  p.row_image = row_image;
+  p.row_pix = row_pix;
+  p.psi = psi;
+  p.win = win;
+  p.comb = psi ? comb : nullptr;
+  p.y_len = y_len;
+  p.y_pix = y_pix;
+  p.psi_len = psi ? psi_len : 0;
+  p.comb_ld = comb_ld;
+  p.rows = rows;
+  p.nimg = nimg;
+  p.M = M;
+  p.nt = nt;
+  p.Cpsi = psi ? Cpsi : 0;
+  const dim3 grid(ew_grid(rows, 1));
+  if (can_vec && path != LIC_CTX_ELEMENT)
+    hipLaunchKernelGGL(ctx_gather_ragged_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(ctx_gather_ragged_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
   return lic_check_launch();
 }

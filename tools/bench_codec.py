@@ -6,7 +6,12 @@ ENCODERS (comma list of host / device, applied to the rans coder in the order gi
 1..8, applied to the rans coder like ENCODERS, inside every encoder; `GROUPS=1,2,4,8,1,2,4,8` alternates them.
 bash keeps a variable GROUPS of its own and ignores an assignment to it: from bash, `env GROUPS=1,2,4,8 python ...`),
 and SLICE_ROWS (comma list of latent rows per slice, 0 = no slices, applied to the rans coder outside GROUPS:
-`SLICE_ROWS=0,16,8,4`).  A line names the decode steps per image as well."""
+`SLICE_ROWS=0,16,8,4`).  A line names the decode steps per image as well.
+
+BLOBS (comma list of blob counts, `BLOBS=1,4,16`) selects the batched-decode mode instead: for every SLICE_ROWS and GROUPS
+entry, N `compress_image` blobs of 512x768, 768x512 and 384x512 in turn are decoded once with `decompress_images` and
+once as a loop of `decompress_image`, alternating, warm, median of RUNS.  PROFILE=many:3 (or seq:3) skips the timing and
+makes just that many calls of one path on the first BLOBS entry, for a kernel trace whose counts can be subtracted."""
 import os
 import statistics
 import sys
@@ -25,6 +30,9 @@ ENCODERS = os.environ.get("ENCODERS", "host").split(",")
 GROUPS = [int(g) for g in os.environ.get("GROUPS", "1").split(",")]
 SLICE_ROWS = [int(r) for r in os.environ.get("SLICE_ROWS", "0").split(",")]
 RUNS = int(os.environ.get("RUNS", "10"))
+BLOBS = [int(n) for n in os.environ.get("BLOBS", "").split(",") if n]
+PROFILE = os.environ.get("PROFILE", "")
+BLOB_SIZES = [(512, 768), (768, 512), (384, 512)]
 
 
 def timed(fn):
@@ -35,8 +43,40 @@ def timed(fn):
     return out, 1e3 * (time.perf_counter() - t0)
 
 
+def blob_mode(model):
+    """decompress_images against a loop of decompress_image on the same N blobs, in one process"""
+    for rows, groups in [(r, g) for r in SLICE_ROWS for g in GROUPS]:
+        cc = ContextCodec(model, coder="rans", encoder="device", groups=groups, slice_rows=rows or None)
+        pool = [cc.compress_image(torch.rand(1, 3, h, w, device="cuda")) for h, w in BLOB_SIZES]
+        for n in BLOBS:
+            blobs = [pool[i % len(pool)] for i in range(n)]
+            many = lambda: cc.decompress_images(blobs)
+            seq = lambda: [cc.decompress_image(b) for b in blobs]
+            if PROFILE:
+                path, calls = PROFILE.split(":")
+                for _ in range(int(calls)):
+                    timed({"many": many, "seq": seq}[path])
+                print(f"profile: {calls} calls of {path}, {n} blobs, groups={groups} slice_rows={rows}", flush=True)
+                return
+            for _ in range(2):                                                   # warm: allocator, weight packs, tuning
+                a, b = many(), seq()
+            ok = all(torch.equal(u, v) for u, v in zip(a, b))
+            t_many, t_seq = [], []
+            for _ in range(RUNS):                                                # alternating: same clocks for both
+                t_many.append(timed(many)[1])
+                t_seq.append(timed(seq)[1])
+            mm, ms = statistics.median(t_many), statistics.median(t_seq)
+            print(f"JAH({M},{K}) groups={groups} slice_rows={rows} blobs={n}: decompress_images {mm:8.2f} ms "
+                  f"(min {min(t_many):.2f}, max {max(t_many):.2f}; {mm / n:6.2f} ms per blob), loop of decompress_image "
+                  f"{ms:8.2f} ms (min {min(t_seq):.2f}, max {max(t_seq):.2f}; {ms / n:6.2f} ms per blob), median of {RUNS}, "
+                  f"{'bit-equal' if ok else 'MISMATCH'}, {sum(map(len, blobs))} bytes", flush=True)
+
+
 torch.manual_seed(0)
 model = nic.JointAutoregressiveHierarchical(M, K).cuda().eval()
+if BLOBS:
+    blob_mode(model)
+    sys.exit(0)
 x = torch.rand(1, 3, H, W, device="cuda").contiguous(memory_format=torch.channels_last)
 for coder, encoder, rows, groups in [(c, e, r, g) for c in CODERS for e in (ENCODERS if c == "rans" else ["host"])
                                      for r in (SLICE_ROWS if c == "rans" else [0])
