@@ -23,98 +23,26 @@
 
 namespace {
 
-struct CtxGatherParams {
+// What the walk of one row reads and writes, whichever launch names the row; comb is null and Cpsi 0 without psi
+struct CtxRowParams {
   const float* y;
   const int32_t* taps;
-  const int64_t* pix;
   const float* psi;
   float* win;
   float* comb;
-  int64_t y_batch, y_row, y_pix, y_origin, comb_ld, n, rows;
-  int32_t h, w, M, nt, R, Cpsi;
+  int64_t y_pix, comb_ld;
+  int32_t M, nt, Cpsi;
 };
 
-// V: floats per piece (4: 16-byte moves, 1: element by element)
-template <int V>
-__global__ __launch_bounds__(256) void ctx_gather_kernel(const CtxGatherParams p) {
-  typedef float piece __attribute__((ext_vector_type(V)));
-  const int Mq = p.M / V, Cq = p.psi ? p.Cpsi / V : 0;
-  const int nwin = p.nt * Mq, per_row = nwin + Cq;
-  const int64_t hw = (int64_t)p.h * p.w;
-  for (int64_t row = blockIdx.x; row < p.rows; row += gridDim.x) {
-    const int64_t b = row / p.n, k = row - b * p.n;
-    const int64_t px = p.pix[k];
-    const bool ok = px >= 0 && px < hw;  // a bad index: zeros out, nothing in
-    const int i = ok ? (int)(px / p.w) : 0, j = ok ? (int)(px - (int64_t)i * p.w) : 0;
-    const int ri = i % p.R;  // row inside the pixel's slice
-    const float* yb = p.y + b * p.y_batch + p.y_origin;
-    float* wrow = p.win + row * ((int64_t)p.nt * p.M);
-    for (int e = threadIdx.x; e < per_row; e += 256) {
-      if (e < nwin) {
-        const int t = e / Mq, c = (e - t * Mq) * V;
-        const int dr = p.taps[2 * t], ds = p.taps[2 * t + 1];
-        const int si = i + dr, sj = j + ds;
-        const bool live = ok && si >= 0 && si < p.h && sj >= 0 && sj < p.w && (dr >= 0 || ri + dr >= 0);
-        piece v = {};
-        if (live) v = *reinterpret_cast<const piece*>(yb + si * p.y_row + sj * p.y_pix + c);
-        *reinterpret_cast<piece*>(wrow + (int64_t)e * V) = v;
-      } else {
-        const int c = (e - nwin) * V;
-        piece v = {};
-        if (ok) v = *reinterpret_cast<const piece*>(p.psi + (b * hw + px) * p.Cpsi + c);
-        *reinterpret_cast<piece*>(p.comb + row * p.comb_ld + c) = v;
-      }
-    }
-  }
-}
-
-inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
-// ---- rows of different images ------------------------------------------------------------------------------------
-constexpr int64_t kMaxSide = 1 << 15;            // h, w of one latent plane: keeps every product below in 64 bits
-constexpr int64_t kMaxFloats = (int64_t)1 << 40;  // y_len, psi_len
-
-struct CtxRaggedParams {
-  const float* y;
-  const int64_t* images;
-  const int32_t* taps;
-  const int64_t* row_image;
-  const int64_t* row_pix;
-  const float* psi;
-  float* win;
-  float* comb;
-  int64_t y_len, y_pix, psi_len, comb_ld, rows;
-  int32_t nimg, M, nt, Cpsi;
-};
-
+// The plane a row's pixel lies in: built from the launch's uniform geometry in ctx_gather_kernel, read from the image's
+// descriptor in ctx_gather_ragged_kernel
 struct CtxImage {
   int64_t y_base, y_row, y_origin, psi_base, h, w, R;
 };
 
-// the descriptor of image b if every address it can produce lies inside y[0, y_len) and psi[0, psi_len)
-__device__ __forceinline__ bool ctx_image(const CtxRaggedParams& p, int64_t b, CtxImage& g) {
-  if (b < 0 || b >= p.nimg) return false;
-  const int64_t* d = p.images + b * LIC_CTX_IMAGE_WORDS;
-  g.y_base = d[LIC_CTX_IMAGE_Y_BASE];
-  g.y_row = d[LIC_CTX_IMAGE_Y_ROW];
-  g.y_origin = d[LIC_CTX_IMAGE_Y_ORIGIN];
-  g.psi_base = d[LIC_CTX_IMAGE_PSI_BASE];
-  g.h = d[LIC_CTX_IMAGE_H];
-  g.w = d[LIC_CTX_IMAGE_W];
-  g.R = d[LIC_CTX_IMAGE_R];
-  if (g.h < 1 || g.h > kMaxSide || g.w < 1 || g.w > kMaxSide || g.R < 1) return false;
-  if (g.y_base < 0 || g.y_base > p.y_len || g.y_row < 0 || g.y_row > p.y_len || g.y_origin < 0 || g.y_origin > p.y_len)
-    return false;
-  // the last float of the last pixel: every term is below 2^55
-  if (g.y_base + g.y_origin + (g.h - 1) * g.y_row + (g.w - 1) * p.y_pix + p.M > p.y_len) return false;
-  if (p.psi && (g.psi_base < 0 || g.psi_base > p.psi_len || g.psi_base + g.h * g.w * p.Cpsi > p.psi_len)) return false;
-  return true;
-}
-
-// one row in pieces of V floats; `ok` false: zeros, nothing read
+// one row in pieces of V floats (4: 16-byte moves, 1: element by element); `ok` false: zeros, nothing read
 template <int V>
-__device__ __forceinline__ void ctx_ragged_row(const CtxRaggedParams& p, int64_t row, bool ok, const CtxImage& g,
-                                               int64_t px) {
+__device__ __forceinline__ void ctx_row(const CtxRowParams& p, int64_t row, bool ok, const CtxImage& g, int64_t px) {
   typedef float piece __attribute__((ext_vector_type(V)));
   const int Mq = p.M / V, Cq = p.psi ? p.Cpsi / V : 0;
   const int nwin = p.nt * Mq, per_row = nwin + Cq;
@@ -142,7 +70,62 @@ __device__ __forceinline__ void ctx_ragged_row(const CtxRaggedParams& p, int64_t
   }
 }
 
-// V as in ctx_gather_kernel; with V = 4 a row whose image is not laid out in multiples of 4 floats goes by floats
+struct CtxGatherParams {
+  CtxRowParams row;
+  const int64_t* pix;
+  int64_t y_batch, y_row, y_origin, n, rows;
+  int32_t h, w, R;
+};
+
+// V as in ctx_row
+template <int V>
+__global__ __launch_bounds__(256) void ctx_gather_kernel(const CtxGatherParams p) {
+  const int64_t hw = (int64_t)p.h * p.w;
+  for (int64_t row = blockIdx.x; row < p.rows; row += gridDim.x) {
+    const int64_t b = row / p.n, k = row - b * p.n;
+    const int64_t px = p.pix[k];
+    const CtxImage g{b * p.y_batch, p.y_row, p.y_origin, b * hw * p.row.Cpsi, p.h, p.w, p.R};
+    ctx_row<V>(p.row, row, px >= 0 && px < hw, g, px);  // a bad index: zeros out, nothing in
+  }
+}
+
+inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// ---- rows of different images ------------------------------------------------------------------------------------
+constexpr int64_t kMaxSide = 1 << 15;            // h, w of one latent plane: keeps every product below in 64 bits
+constexpr int64_t kMaxFloats = (int64_t)1 << 40;  // y_len, psi_len
+
+struct CtxRaggedParams {
+  CtxRowParams row;
+  const int64_t* images;
+  const int64_t* row_image;
+  const int64_t* row_pix;
+  int64_t y_len, psi_len, rows;
+  int32_t nimg;
+};
+
+// the descriptor of image b if every address it can produce lies inside y[0, y_len) and psi[0, psi_len)
+__device__ __forceinline__ bool ctx_image(const CtxRaggedParams& p, int64_t b, CtxImage& g) {
+  if (b < 0 || b >= p.nimg) return false;
+  const int64_t* d = p.images + b * LIC_CTX_IMAGE_WORDS;
+  g.y_base = d[LIC_CTX_IMAGE_Y_BASE];
+  g.y_row = d[LIC_CTX_IMAGE_Y_ROW];
+  g.y_origin = d[LIC_CTX_IMAGE_Y_ORIGIN];
+  g.psi_base = d[LIC_CTX_IMAGE_PSI_BASE];
+  g.h = d[LIC_CTX_IMAGE_H];
+  g.w = d[LIC_CTX_IMAGE_W];
+  g.R = d[LIC_CTX_IMAGE_R];
+  if (g.h < 1 || g.h > kMaxSide || g.w < 1 || g.w > kMaxSide || g.R < 1) return false;
+  if (g.y_base < 0 || g.y_base > p.y_len || g.y_row < 0 || g.y_row > p.y_len || g.y_origin < 0 || g.y_origin > p.y_len)
+    return false;
+  // the last float of the last pixel: every term is below 2^55
+  if (g.y_base + g.y_origin + (g.h - 1) * g.y_row + (g.w - 1) * p.row.y_pix + p.row.M > p.y_len) return false;
+  if (p.row.psi && (g.psi_base < 0 || g.psi_base > p.psi_len || g.psi_base + g.h * g.w * p.row.Cpsi > p.psi_len))
+    return false;
+  return true;
+}
+
+// V as in ctx_row; with V = 4 a row whose image is not laid out in multiples of 4 floats goes by floats
 template <int V>
 __global__ __launch_bounds__(256) void ctx_gather_ragged_kernel(const CtxRaggedParams p) {
   for (int64_t row = blockIdx.x; row < p.rows; row += gridDim.x) {
@@ -150,10 +133,16 @@ __global__ __launch_bounds__(256) void ctx_gather_ragged_kernel(const CtxRaggedP
     CtxImage g = {};
     const bool ok = ctx_image(p, b, g) && px >= 0 && px < g.h * g.w;
     if (V == 1 || (ok && ((g.y_base | g.y_row | g.y_origin | g.psi_base) & 3)))
-      ctx_ragged_row<1>(p, row, ok, g, px);
+      ctx_row<1>(p.row, row, ok, g, px);
     else
-      ctx_ragged_row<V>(p, row, ok, g, px);
+      ctx_row<V>(p.row, row, ok, g, px);
   }
+}
+
+// the fields both launches fill the same way
+CtxRowParams ctx_row_params(const float* y, const int32_t* taps, const float* psi, float* win, float* comb,
+                            int64_t y_pix, int64_t comb_ld, int32_t M, int32_t nt, int32_t Cpsi) {
+  return CtxRowParams{y, taps, psi, win, psi ? comb : nullptr, y_pix, comb_ld, M, nt, psi ? Cpsi : 0};
 }
 
 }  // namespace
@@ -179,25 +168,16 @@ LIC_EXPORT int lic_ctx_gather(const float* y, int64_t y_batch, int64_t y_row, in
                        (!psi || (Cpsi % 4 == 0 && comb_ld % 4 == 0 && aligned16(psi) && aligned16(comb)));
   if (path == LIC_CTX_VECTOR && !can_vec) return LIC_ERR_INVALID;
   CtxGatherParams p;
-  p.y = y;
-  p.taps = taps;
+  p.row = ctx_row_params(y, taps, psi, win, comb, y_pix, comb_ld, M, nt, Cpsi);
   p.pix = pix;
-  p.psi = psi;
-  p.win = win;
-  p.comb = psi ? comb : nullptr;
   p.y_batch = y_batch;
   p.y_row = y_row;
-  p.y_pix = y_pix;
   p.y_origin = y_origin;
-  p.comb_ld = comb_ld;
   p.n = n;
   p.rows = (int64_t)B * n;
   p.h = h;
   p.w = w;
-  p.M = M;
-  p.nt = nt;
   p.R = slice_rows;
-  p.Cpsi = psi ? Cpsi : 0;
   const dim3 grid(ew_grid(p.rows, 1));
   if (can_vec && path != LIC_CTX_ELEMENT)
     hipLaunchKernelGGL(ctx_gather_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
@@ -228,23 +208,14 @@ LIC_EXPORT int lic_ctx_gather_ragged(const float* y, int64_t y_len, int64_t y_pi
                        (!psi || (Cpsi % 4 == 0 && comb_ld % 4 == 0 && aligned16(psi) && aligned16(comb)));
   if (path == LIC_CTX_VECTOR && !can_vec) return LIC_ERR_INVALID;
   CtxRaggedParams p;
-  p.y = y;
+  p.row = ctx_row_params(y, taps, psi, win, comb, y_pix, comb_ld, M, nt, Cpsi);
   p.images = images;
-  p.taps = taps;
   p.row_image = row_image;
   p.row_pix = row_pix;
-  p.psi = psi;
-  p.win = win;
-  p.comb = psi ? comb : nullptr;
   p.y_len = y_len;
-  p.y_pix = y_pix;
   p.psi_len = psi ? psi_len : 0;
-  p.comb_ld = comb_ld;
   p.rows = rows;
   p.nimg = nimg;
-  p.M = M;
-  p.nt = nt;
-  p.Cpsi = psi ? Cpsi : 0;
   const dim3 grid(ew_grid(rows, 1));
   if (can_vec && path != LIC_CTX_ELEMENT)
     hipLaunchKernelGGL(ctx_gather_ragged_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);

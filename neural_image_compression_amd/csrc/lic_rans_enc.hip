@@ -93,64 +93,44 @@ struct RoundWalk {
   }
 };
 
-__global__ __launch_bounds__(64) void rans_encode_kernel(const uint32_t* __restrict__ sf,
-                                                         const uint32_t* __restrict__ exc,
-                                                         const int64_t* __restrict__ step_len, int64_t nsteps,
-                                                         int32_t nsym, uint8_t* __restrict__ words, int64_t slot,
-                                                         uint32_t* __restrict__ esc_out, uint32_t* state) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  sf += (int64_t)b * nsym;
-  exc += (int64_t)b * nsym;
-  esc_out += (int64_t)b * nsym;
-  uint32_t* st = state + (size_t)b * kStateWords;
-  uint32_t err = st[kLanes + 2];
-
-  // the step lengths must be non-negative and add up to nsym before anything is indexed with them
-  int64_t sum = 0, rounds = 0;
+// The step lengths must be non-negative and add up to nsym before anything is indexed with them.  True if they do;
+// rounds is then the wave's number of rounds, count(n) of them in a step of n symbols.  Wave-uniform.
+template <class Count>
+__device__ __forceinline__ bool step_lengths_ok(const int64_t* __restrict__ step_len, int64_t nsteps, int32_t nsym,
+                                                int lane, Count count, int64_t& rounds) {
+  int64_t sum = 0;
   bool okl = true;
+  rounds = 0;
   for (int64_t t = lane; t < nsteps; t += kLanes) {
     const int64_t n = step_len[t];
     if (n < 0 || n > nsym)
       okl = false;
     else
-      sum += n, rounds += (n + kLanes - 1) / kLanes;
+      sum += n, rounds += count(n);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     sum += __shfl_xor(sum, o, kLanes);
     rounds += __shfl_xor(rounds, o, kLanes);
   }
-  if (!__all(okl) || sum != nsym) {
-    st[lane] = 1u << 16;
-    if (lane == 0) st[kLanes] = 0u, st[kLanes + 1] = 0u, st[kLanes + 2] = err | LIC_RANS_ERR_RANGE;
-    return;
-  }
+  return __all(okl) && sum == nsym;
+}
 
-  // escapes, forward, in symbol order: rounds play no part in their order
-  uint32_t nesc = 0;
-  for (uint32_t k0 = 0; k0 < (uint32_t)nsym; k0 += kRing * kLanes) {
-    uint32_t e[kRing];
-#pragma unroll
-    for (int j = 0; j < kRing; ++j) {  // all loads first: none depends on the cursor
-      const uint32_t k = k0 + j * kLanes + lane;
-      e[j] = k < (uint32_t)nsym ? exc[k] : kNoEscape;
-    }
-#pragma unroll
-    for (int j = 0; j < kRing; ++j) {
-      const bool edge = e[j] != kNoEscape;
-      const unsigned long long mask = __ballot(edge);
-      if (edge) esc_out[nesc + (uint32_t)__popcll(mask & below)] = e[j];
-      nesc += (uint32_t)__popcll(mask);
-    }
-  }
+// What a wave leaves of lengths it refuses: the initial state, no word, no escape and the error word
+__device__ __forceinline__ void refuse_steps(uint32_t* st, int lane, uint32_t err) {
+  st[lane] = 1u << 16;
+  if (lane == 0) st[kLanes] = 0u, st[kLanes + 1] = 0u, st[kLanes + 2] = err | LIC_RANS_ERR_RANGE;
+}
 
-  // states, backward
-  uint16_t* wbuf = reinterpret_cast<uint16_t*>(words + (int64_t)b * slot);
-  const uint32_t wend = (uint32_t)(slot >> 1);
+// States, backward: the wave codes the `rounds` rounds that walk hands out, last to first, into the slot's words
+// [.., wend) and stores its state, word count, escape count (nesc, counted by the caller) and error word.
+template <class Walk>
+__device__ __forceinline__ void encode_states(const uint32_t* __restrict__ sf, Walk walk, int64_t rounds,
+                                              uint16_t* __restrict__ wbuf, uint32_t wend, uint32_t nesc, uint32_t err,
+                                              uint32_t* st, int lane) {
+  const unsigned long long below = (1ull << lane) - 1ull;
   uint32_t wpos = wend;  // in 16-bit words from the slot's start; the words so far are [wpos, wend)
   uint32_t x = 1u << 16;
-  RoundWalk walk{step_len, nsteps, nsym, 0};
   // the ring: a round's raw words and its number of active lanes.  Exactly one load per round, taken or not (an
   // idle lane reads word 0; it is dropped where the round is consumed): a load under a branch cannot be counted,
   // and every wait for the ring would then wait for all of it
@@ -174,7 +154,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint32_t* __restr
       const bool emit = active && (x >> 16) >= freq;
       const unsigned long long mask = __ballot(emit);
       const uint32_t cnt = (uint32_t)__popcll(mask);
-      if (cnt > wpos) {  // cannot happen in a slot of lic_rans_bound(nsym) bytes: at most one word per symbol
+      if (cnt > wpos) {  // cannot happen in a slot of one word per symbol of the wave's rounds (lic_rans_bound)
         err |= LIC_RANS_ERR_RANGE;
       } else {
         wpos -= cnt;
@@ -190,6 +170,45 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(const uint32_t* __restr
   }
   st[lane] = x;
   if (lane == 0) st[kLanes] = wend - wpos, st[kLanes + 1] = nesc, st[kLanes + 2] = err;
+}
+
+__global__ __launch_bounds__(64) void rans_encode_kernel(const uint32_t* __restrict__ sf,
+                                                         const uint32_t* __restrict__ exc,
+                                                         const int64_t* __restrict__ step_len, int64_t nsteps,
+                                                         int32_t nsym, uint8_t* __restrict__ words, int64_t slot,
+                                                         uint32_t* __restrict__ esc_out, uint32_t* state) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  sf += (int64_t)b * nsym;
+  exc += (int64_t)b * nsym;
+  esc_out += (int64_t)b * nsym;
+  uint32_t* st = state + (size_t)b * kStateWords;
+  uint32_t err = st[kLanes + 2];
+
+  int64_t rounds;
+  if (!step_lengths_ok(step_len, nsteps, nsym, lane, [](int64_t n) { return (n + kLanes - 1) / kLanes; }, rounds))
+    return refuse_steps(st, lane, err);
+
+  // escapes, forward, in symbol order: rounds play no part in their order
+  uint32_t nesc = 0;
+  for (uint32_t k0 = 0; k0 < (uint32_t)nsym; k0 += kRing * kLanes) {
+    uint32_t e[kRing];
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {  // all loads first: none depends on the cursor
+      const uint32_t k = k0 + j * kLanes + lane;
+      e[j] = k < (uint32_t)nsym ? exc[k] : kNoEscape;
+    }
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {
+      const bool edge = e[j] != kNoEscape;
+      const unsigned long long mask = __ballot(edge);
+      if (edge) esc_out[nesc + (uint32_t)__popcll(mask & below)] = e[j];
+      nesc += (uint32_t)__popcll(mask);
+    }
+  }
+
+  encode_states(sf, RoundWalk{step_len, nsteps, nsym, 0}, rounds,
+                reinterpret_cast<uint16_t*>(words + (int64_t)b * slot), (uint32_t)(slot >> 1), nesc, err, st, lane);
 }
 
 // The rounds of one group, as (first symbol, active lanes): round r of a step is the group's if r % G == g.
@@ -249,7 +268,7 @@ struct GroupWalkForward {
   }
 };
 
-// rans_encode_kernel with one wave per (image, group).  The same escape pass, ring and divide; the two walks hand out
+// rans_encode_kernel with one wave per (image, group).  The same length check, ring and divide; the two walks hand out
 // the group's rounds only, and the escape list has a capacity of its own to compare with
 __global__ __launch_bounds__(64) void rans_encode_groups_kernel(const uint32_t* __restrict__ sf,
                                                          const uint32_t* __restrict__ exc,
@@ -267,26 +286,9 @@ __global__ __launch_bounds__(64) void rans_encode_groups_kernel(const uint32_t* 
   uint32_t* st = state + (size_t)blk * kStateWords;
   uint32_t err = st[kLanes + 2];
 
-  // the step lengths must be non-negative and add up to nsym before anything is indexed with them
-  int64_t sum = 0, rounds = 0;
-  bool okl = true;
-  for (int64_t t = lane; t < nsteps; t += kLanes) {
-    const int64_t n = step_len[t];
-    if (n < 0 || n > nsym)
-      okl = false;
-    else
-      sum += n, rounds += of.count((int32_t)n);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o, kLanes);
-    rounds += __shfl_xor(rounds, o, kLanes);
-  }
-  if (!__all(okl) || sum != nsym) {
-    st[lane] = 1u << 16;
-    if (lane == 0) st[kLanes] = 0u, st[kLanes + 1] = 0u, st[kLanes + 2] = err | LIC_RANS_ERR_RANGE;
-    return;
-  }
+  int64_t rounds;
+  if (!step_lengths_ok(step_len, nsteps, nsym, lane, [&](int64_t n) { return (int64_t)of.count((int32_t)n); }, rounds))
+    return refuse_steps(st, lane, err);
 
   // escapes, forward, in the symbol order of the group's rounds
   uint32_t nesc = 0;
@@ -314,51 +316,8 @@ __global__ __launch_bounds__(64) void rans_encode_groups_kernel(const uint32_t* 
     }
   }
 
-  // states, backward
-  uint16_t* wbuf = reinterpret_cast<uint16_t*>(words + (int64_t)blk * slot);
-  const uint32_t wend = (uint32_t)(slot >> 1);
-  uint32_t wpos = wend;  // in 16-bit words from the slot's start; the words so far are [wpos, wend)
-  uint32_t x = 1u << 16;
-  GroupWalk walk{of, nsteps, nsym, 0, -1};
-  // the ring: a round's raw words and its number of active lanes.  Exactly one load per round, taken or not (an
-  // idle lane reads word 0; it is dropped where the round is consumed): a load under a branch cannot be counted,
-  // and every wait for the ring would then wait for all of it
-  uint32_t ring[kRing];
-  int32_t live[kRing];
-  auto fetch = [&](int j) {
-    int32_t k0 = 0, n = 0;
-    walk.next(k0, n);  // leaves (0, 0) once the walk is over
-    ring[j] = sf[lane < n ? k0 + lane : 0];
-    live[j] = n;
-  };
-#pragma unroll
-  for (int j = 0; j < kRing; ++j) fetch(j);
-  for (int64_t r = 0; r < rounds; r += kRing) {
-#pragma unroll
-    for (int j = 0; j < kRing; ++j) {
-      const uint32_t w = lane < live[j] ? ring[j] : 0u;
-      fetch(j);  // the round kRing ahead; no lane is live once the walk is over
-      const uint32_t freq = w & 0xFFFFu, start = w >> 16;
-      const bool active = freq != 0u;
-      const bool emit = active && (x >> 16) >= freq;
-      const unsigned long long mask = __ballot(emit);
-      const uint32_t cnt = (uint32_t)__popcll(mask);
-      if (cnt > wpos) {  // cannot happen in a slot of one word per symbol of the group
-        err |= LIC_RANS_ERR_RANGE;
-      } else {
-        wpos -= cnt;
-        if (emit) {
-          wbuf[wpos + (uint32_t)__popcll(mask & below)] = (uint16_t)x;
-          x >>= 16;
-        }
-      }
-      const uint32_t f = active ? freq : 1u;
-      const uint32_t q = x / f;
-      if (active) x = (q << 16) + (x - q * f) + start;
-    }
-  }
-  st[lane] = x;
-  if (lane == 0) st[kLanes] = wend - wpos, st[kLanes + 1] = nesc, st[kLanes + 2] = err;
+  encode_states(sf, GroupWalk{of, nsteps, nsym, 0, -1}, rounds,
+                reinterpret_cast<uint16_t*>(words + (int64_t)blk * slot), (uint32_t)(slot >> 1), nesc, err, st, lane);
 }
 
 }  // namespace
