@@ -639,6 +639,67 @@ int lic_rans_encode_groups(const uint32_t* sf, const uint32_t* exc, const int64_
                            int64_t esc_cap, uint32_t* state, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2g -- the same encoder for images of DIFFERENT sizes in one launch each
+ *   (codec.ContextCodec.compress_images): the tables, centres and symbols of all images are rows one after the
+ *   other, total_rows rows of M values, as one lic_gmm_cdf_tables launch leaves them.  Where an image's rows, steps,
+ *   slots and lists lie is said by two descriptor tables of int64 words on the device:
+ *     images        [nimg][LIC_RANS_IMAGE_WORDS]: ROW0 the image's first row in tables / center / y, which is also
+ *                   its first coding position (its symbols are sf / exc [ROW0 * M, (ROW0 + P) * M)); P its pixels
+ *                   (>= 1); STEP0 its first entry in the flat step_len array; NSTEPS its steps
+ *     blocks        [nimg*G][LIC_RANS_BLOCK_WORDS], image-major: WORD_OFF the byte offset of the block's slot in
+ *                   `words` (a multiple of 4); SLOT its bytes (a multiple of 4, >= 4); ESC_OFF the first uint32 entry
+ *                   of its escape list in esc_out; ESC_CAP its entries (>= 1).  Sizes as for lic_rans_encode_groups,
+ *                   per image: SLOT >= 2 * max_g n_g rounded up to 4 and ESC_CAP >= max_g n_g never run out.
+ *
+ *   lic_rans_encode_pick_ragged -- one thread per symbol of the whole call.  Coding position q (symbol k = q * M + c)
+ *   belongs to image row_image[q] and stands for raster pixel order[q] of that image: its table row is ROW0 + order[q].
+ *     row_image, order   [total_rows] int64 each (device)
+ *     sf, exc       [total_rows * M] uint32 out, as lic_rans_encode_pick writes them, image after image
+ *     state         [nimg][LIC_RANS_STATE_WORDS]: one block per IMAGE, only the error word is touched, by atomic OR;
+ *                   the caller zeroes it
+ *   Checked before anything is indexed: row_image[q] in [0, nimg), ROW0 >= 0, P >= 1, ROW0 + P <= total_rows, q in
+ *   [ROW0, ROW0 + P), order[q] in [0, P).  A violation, or a malformed table (lic_rans_encode_pick's rules), codes the
+ *   symbol as (start 0, freq 1) and sets LIC_RANS_ERR_RANGE in the image's error word; a row whose row_image names no
+ *   image is coded likewise and can report nowhere.  Other images are not affected.
+ *
+ *   lic_rans_encode_ragged -- nimg * G workgroups of one wave; wave (b, g) is lic_rans_encode_groups' wave on the
+ *   image's own sf / exc / step_len ranges and on block b * G + g's own slot and list.  G = 1 is the same kernel.
+ *     step_len, steps_len   all images' step lengths in one int64 array (device) and its length in entries
+ *     words, words_len      one byte buffer for all slots and its length; a block's words END at the end of its slot
+ *     esc_out, esc_len      one uint32 buffer for all escape lists and its length in entries
+ *     state         [nimg*G][LIC_RANS_STATE_WORDS]: final states, word count, escape count, error word (read at
+ *                   entry, so the caller zeroes it); an image is in error if its pick block or one of its G blocks is
+ *   A wave compares its descriptors with the given lengths before it addresses anything: no negative entry, P >= 1,
+ *   ROW0 + P <= total_rows, P * M < 2^31 - 64, STEP0 + NSTEPS <= steps_len, WORD_OFF and SLOT multiples of 4,
+ *   SLOT >= 4, WORD_OFF + SLOT <= words_len, ESC_CAP >= 1, ESC_OFF + ESC_CAP <= esc_len.  A block that fails, or whose
+ *   image's step lengths are negative or do not add up to P * M, reports LIC_RANS_ERR_RANGE with states 2^16 and
+ *   counts 0 and reads and writes nothing else; the blocks of other images are not affected.  Word and escape cursor
+ *   are compared with the slot's first word and ESC_CAP before every store, as in lic_rans_encode_groups.
+ *   Both entries: NULL pointers, nimg, total_rows, M (W; steps_len, words_len, esc_len) <= 0, G outside
+ *   1..LIC_RANS_MAX_GROUPS, misaligned pointers (int64 arrays 8 bytes, the others 4): LIC_ERR_INVALID.  W > 64,
+ *   nimg * G > 65535 (pick: nimg > 65535), total_rows * M >= 2^31 - 64: LIC_ERR_UNSUPPORTED.  One launch each, no
+ *   allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define LIC_RANS_IMAGE_WORDS 4
+#define LIC_RANS_IMAGE_ROW0 0
+#define LIC_RANS_IMAGE_P 1
+#define LIC_RANS_IMAGE_STEP0 2
+#define LIC_RANS_IMAGE_NSTEPS 3
+#define LIC_RANS_BLOCK_WORDS 4
+#define LIC_RANS_BLOCK_WORD_OFF 0
+#define LIC_RANS_BLOCK_SLOT 1
+#define LIC_RANS_BLOCK_ESC_OFF 2
+#define LIC_RANS_BLOCK_ESC_CAP 3
+int lic_rans_encode_pick_ragged(const uint32_t* tables, const int32_t* center, const int32_t* y, int64_t total_rows,
+                                const int64_t* images, int32_t nimg, const int64_t* row_image, const int64_t* order,
+                                int32_t M, int32_t W, uint32_t* sf, uint32_t* exc, uint32_t* state,
+                                lic_stream_t stream);
+int lic_rans_encode_ragged(const uint32_t* sf, const uint32_t* exc, const int64_t* step_len, int64_t steps_len,
+                           const int64_t* images, const int64_t* blocks, int32_t nimg, int32_t G, int64_t total_rows,
+                           int32_t M, uint8_t* words, int64_t words_len, uint32_t* esc_out, int64_t esc_len,
+                           uint32_t* state, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).1 -- evaluation metric on the device.
  * Multi-scale SSIM exactly as the reference's evaluator calls it (Evaluator.py:7,38,45:
  * `ms_ssim(recon, orig, data_range=1.0, size_average=True)` of the third-party pytorch-msssim==0.2.1,

@@ -79,6 +79,9 @@ RANS_LANES, RANS_STATE_WORDS, RANS_MAX_GROUPS = 64, 67, 8
 CTX_AUTO, CTX_VECTOR, CTX_ELEMENT = range(3)
 # lic_ctx_gather_ragged's per-image descriptor: int64 words Y_BASE, Y_ROW, Y_ORIGIN, PSI_BASE, H, W, R, one unused
 CTX_IMAGE_WORDS = 8
+# lic_rans_encode_ragged's descriptors, int64 words: per image ROW0, P, STEP0, NSTEPS; per block WORD_OFF, SLOT,
+# ESC_OFF, ESC_CAP
+RANS_IMAGE_WORDS = RANS_BLOCK_WORDS = 4
 
 WINDOW_ZERO, WINDOW_REPLICATE, WINDOW_REFLECT = range(3)
 WINDOW_FLIP = 1
@@ -170,6 +173,9 @@ SIGNATURES = {
     "lic_rans_encode": (C.c_int, [_vp] * 3 + [_i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp]),
     "lic_rans_decode_step_groups": (C.c_int, [_vp] * 8 + [_i32] * 5 + [_vp, _vp, _i64, _vp]),
     "lic_rans_encode_groups": (C.c_int, [_vp] * 3 + [_i64, _i32, _i32, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "lic_rans_encode_pick_ragged": (C.c_int, [_vp] * 3 + [_i64, _vp, _i32, _vp, _vp, _i32, _i32] + [_vp] * 4),
+    "lic_rans_encode_ragged": (C.c_int, [_vp] * 3 + [_i64, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _i64, _vp, _i64,
+                                         _vp, _vp]),
     "lic_ctx_gather": (C.c_int, [_vp] + [_i64] * 4 + [_i32] * 4 + [_vp, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _i64,
                                  _i32, _vp]),
     "lic_ctx_gather_ragged": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32,

@@ -35,10 +35,15 @@ per-pixel layers read with one gather, `lic_ctx_gather`, which applies that rule
 `ContextCodec.decompress_images(blobs)` decodes many `compress_image` blobs of different sizes together: step t of
 every image shares one gather (`lic_ctx_gather_ragged`), one pass through the per-pixel layers and one decode launch
 (`lic_rans_decode_step_ragged`), by the schedule of `merged_wavefront`; entry i is bit for bit `decompress_image(blobs[i])`.
+
+`ContextCodec.compress_images(images)` is its counterpart: images of different sizes share one gather, one pass through
+the per-pixel layers, one table launch and one launch of each encoder kernel (`lic_rans_encode_pick_ragged`,
+`lic_rans_encode_ragged`); entry i is byte for byte `compress_image(images[i])`.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import zlib
 import os
 from typing import Dict, List, NamedTuple, Sequence
@@ -346,6 +351,71 @@ def _step_indices(steps, w: int, pad: int) -> np.ndarray:
     Wp = w + 2 * pad
     return np.stack([np.concatenate([ii * w + jj for ii, jj in steps]),
                      np.concatenate([(ii + pad) * Wp + jj + pad for ii, jj in steps])])
+
+
+class RaggedEncodePlan(NamedTuple):
+    """what `ragged_encode_plan` returns: the arguments of `lic_rans_encode_pick_ragged` / `lic_rans_encode_ragged`
+    that the host knows before the device has run (lic.h has the descriptor words)"""
+    images: np.ndarray        # [nimg][4] int64: ROW0, P, STEP0, NSTEPS
+    blocks: np.ndarray        # [nimg * G][4] int64, image-major: WORD_OFF (bytes), SLOT (bytes), ESC_OFF, ESC_CAP (entries)
+    row_image: np.ndarray     # [total_rows] int64: the image of every row, which is the image of every coding position
+    order: np.ndarray         # [total_rows] int64: the raster pixel, inside its image, of every coding position
+    step_len: np.ndarray      # int64, the images' step lengths one after the other
+    total_rows: int
+    words_len: int            # bytes of all slots
+    esc_len: int              # entries of all escape lists
+
+
+@functools.lru_cache(maxsize=64)
+def _encode_layout_of(h: int, w: int, M: int, pad: int, slice_rows, G: int):
+    """what `ragged_encode_plan` needs of one image shape, kept between calls (a folder has few shapes; the arrays
+    are read only): (raster pixel of every coding position, step lengths, slot bytes, escape entries)"""
+    steps = wavefront(h, w, pad, slice_rows)
+    step_len = np.array([len(ii) * M for ii, _ in steps], np.int64)
+    fullest = max(int(rans_group_sizes(step_len, G).max()), 1)
+    order = np.concatenate([ii * w + jj for ii, jj in steps]).astype(np.int64)
+    order.setflags(write=False)
+    step_len.setflags(write=False)
+    return order, step_len, (2 * fullest + 3) // 4 * 4, fullest
+
+
+def ragged_encode_plan(shapes, M: int, pad: int, slice_rows, G: int) -> RaggedEncodePlan:
+    """The layout of one ragged encode.  shapes: [(h, w)] per image, all coded with this `slice_rows` and G.  Image b
+    owns rows [ROW0, ROW0 + h w) of the tables, centres and symbols, in raster order, and the same range of coding
+    positions: position ROW0 + q is pixel `wavefront(h, w, pad, slice_rows)`[concatenated][q], its step lengths are
+    len(rows_t) * M, exactly `compress`'s.  Every block gets the smallest slot and escape list that cannot run out
+    (`rans_group_sizes`): 2 * max_g n_g bytes rounded up to 4, and max_g n_g entries; slots and lists lie one behind
+    the other, so every slot starts on a multiple of 4 bytes."""
+    G = _groups(G)
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    kinds = {(h, w): _encode_layout_of(h, w, int(M), int(pad), slice_rows, G) for h, w in set(shapes)}
+    nimg = len(shapes)
+    images, blocks = np.zeros((nimg, L.RANS_IMAGE_WORDS), np.int64), np.zeros((nimg * G, L.RANS_BLOCK_WORDS), np.int64)
+    row0 = step0 = word_off = esc_off = 0
+    for b, (h, w) in enumerate(shapes):
+        order, step_len, slot, cap = kinds[h, w]
+        images[b] = (row0, order.size, step0, step_len.size)
+        for g in range(G):
+            blocks[b * G + g] = (word_off, slot, esc_off, cap)
+            word_off, esc_off = word_off + slot, esc_off + cap
+        row0, step0 = row0 + order.size, step0 + step_len.size
+    cat = lambda k: (np.concatenate([kinds[s][k] for s in shapes]) if nimg else np.zeros(0, np.int64))
+    return RaggedEncodePlan(images, blocks, np.repeat(np.arange(nimg, dtype=np.int64), images[:, 1]), cat(0), cat(1),
+                            row0, word_off, esc_off)
+
+
+def table_chunks(costs, budget: int):
+    """Consecutive runs [(first, end)] of whole items whose costs (table bytes) add up to `budget` at the most; an
+    item that is larger than the budget runs alone."""
+    chunks, first, used = [], 0, 0
+    for i, c in enumerate(costs):
+        if i > first and used + c > budget:
+            chunks.append((first, i))
+            first, used = i, 0
+        used += c
+    if len(costs) > first:
+        chunks.append((first, len(costs)))
+    return chunks
 
 
 class _RansStaging:
@@ -762,6 +832,155 @@ class ContextCodec:
             escs.append(esc[i, :ne].cpu().numpy().view(np.uint32).astype("<u4").tobytes())
         return streams, escs
 
+    # ---- many images in one encode pass -----------------------------------------------------------
+    @torch.no_grad()
+    def compress_many(self, xs: Sequence[torch.Tensor], table_budget_bytes: int = 2 << 30, names=None) -> List[Dict]:
+        """`compress` for several inputs at once (coder "rans", encoder "device").  xs: [B_i, 3, H_i, W_i] tensors as
+        `compress` takes them (sides already multiples of 64), of any sizes; names: what to call an item in a message
+        (default "item i").  -> one `compress` result per item: the same strings byte for byte, shape, z_shape,
+        bpp_coded, bpp_est, y_in, z_in.
+
+        Per item the transforms run exactly as in `compress`; the factorised z tables are built and copied once per
+        call.  `table_budget_bytes` cuts the list into chunks, consecutive runs of whole items whose y tables
+        (rows * M * (2 y_W + 2) * 4 bytes) fit the budget together, an item above it alone (`table_chunks`); a chunk
+        is one pass of `_compress_chunk`, and chunking changes no byte.  Everything the host can refuse is refused
+        before the device is touched."""
+        xs = list(xs)
+        names = [f"item {i}" for i in range(len(xs))] if names is None else list(names)
+        for i, x in enumerate(xs):
+            try:
+                self._refuse_unless_batched_encoder()
+                if not isinstance(x, torch.Tensor) or x.dim() != 4:
+                    raise CodecError("expected a [B,3,H,W] tensor")
+                if not x.is_cuda:
+                    raise CodecError("expected a tensor on the GPU: the device encoder runs where the tables are built")
+            except CodecError as err:
+                raise CodecError(f"{names[i]}: {err}") from None
+        if not xs:
+            return []
+        M = self.model.M
+        costs = [x.shape[0] * (x.shape[2] // 16) * (x.shape[3] // 16) * M * (2 * self.y_W + 2) * 4 for x in xs]
+        zt = factorized_tables(self.model.factorized_entropy_model, self.z_lo, self.z_S).cpu().numpy().view(np.uint32)
+        out = []
+        for first, end in table_chunks(costs, int(table_budget_bytes)):
+            out += self._compress_chunk(xs[first:end], zt, names[first:end])
+        return out
+
+    def _compress_chunk(self, xs, zt: np.ndarray, names) -> List[Dict]:
+        """One pass of `compress_many`.  After every item's transforms: all y_in and psi planes in two flat buffers
+        (every item on a multiple of 4 floats, plain NHWC planes), ONE `lic_ctx_gather_ragged` over every pixel of
+        every image (rows image-major, raster order inside an image), ONE `_params_at` over all rows, ONE
+        `lic_rans_encode_pick_ragged` and ONE `lic_rans_encode_ragged` (`ragged_encode_plan` lays their buffers out).
+        The device -> host copies that wait do not grow with the images: the z symbols of all items, the state
+        blocks, the word buffer, the used escape entries (one gather by an index built from the counts; none if there
+        is no escape), the symbols for the checksums and the rate estimates."""
+        m, G, R = self.model, self.groups, self.slice_rows
+        M, dev = m.M, xs[0].device
+        outs, psis, sums = [], [], []
+        for x in xs:
+            out = m.analysis_hyperprior(x, training=False)
+            outs.append((out["y_in"].contiguous(), out["z_in"], out["y_in"]))
+            psis.append(m.hyper_decoder(out["z_in"]).float())
+            sums.append(out["logp_y"].double().sum() + out["logp_z"].double().sum())
+        # z: the symbols of all items in one read-back, one host range coder run per item as `compress` has it
+        z_sym = [(z.permute(0, 2, 3, 1).contiguous().round().to(torch.int32) - self.z_lo).reshape(-1) for _, z, _ in outs]
+        z_all = torch.cat(z_sym).cpu().numpy()
+        z_bytes, at = [], 0
+        for z in z_sym:
+            n = z.numel()
+            z_bytes.append(rc_encode(zt, z_all[at:at + n], np.tile(np.arange(len(zt), dtype=np.int32), n // len(zt))))
+            at += n
+        # the layout: item after item, each on a multiple of 4 floats, its B planes one behind the other
+        cpsi = psis[0].shape[1]
+        shapes, y_at, psi_at, y_len, psi_len = [], [], [], 0, 0
+        for y_in, _, _ in outs:
+            B, _, h, w = y_in.shape
+            y_at.append((y_len + 3) // 4 * 4)
+            psi_at.append((psi_len + 3) // 4 * 4)
+            shapes += [(h, w)] * B
+            y_len, psi_len = y_at[-1] + B * h * w * M, psi_at[-1] + B * h * w * cpsi
+        nimg = len(shapes)
+        plan = ragged_encode_plan(shapes, M, self.pad, R, G)
+        desc, img = np.zeros((nimg, L.CTX_IMAGE_WORDS), np.int64), 0
+        for i, (y_in, _, _) in enumerate(outs):
+            B, _, h, w = y_in.shape
+            for b in range(B):
+                desc[img, :7] = (y_at[i] + b * h * w * M, w * M, 0, psi_at[i] + b * h * w * cpsi, h, w,
+                                 h if R is None else min(R, h))
+                img += 1
+        yflat = torch.empty(y_len, device=dev, dtype=torch.float32)       # no frame: the gather never leaves a plane
+        psiflat = torch.empty(psi_len, device=dev, dtype=torch.float32)
+        y_syms = []
+        for i, (y_in, _, y_raw) in enumerate(outs):
+            B, _, h, w = y_in.shape
+            yflat[y_at[i]:y_at[i] + B * h * w * M].view(B, h, w, M).copy_(F_._nhwc(y_raw))
+            psiflat[psi_at[i]:psi_at[i] + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psis[i]).view(B, h * w, -1))
+            y_syms.append(y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32))
+        y_sym = torch.cat(y_syms) if len(y_syms) > 1 else y_syms[0].contiguous()
+        # one upload of everything the kernels index with; every part is int64, so every part is 8-byte aligned
+        row_pix = np.concatenate([np.arange(h * w, dtype=np.int64) for h, w in shapes])
+        parts = [desc.ravel(), plan.images.ravel(), plan.blocks.ravel(), plan.row_image, row_pix, plan.order, plan.step_len]
+        d_all = torch.from_numpy(np.concatenate(parts)).to(dev)
+        d_desc, d_images, d_blocks, d_row_image, d_row_pix, d_order, d_steps = torch.split(d_all, [a.size for a in parts])
+        rows, nsym = plan.total_rows, plan.total_rows * M
+        win, comb = self._gather_ragged(yflat, d_desc.view(nimg, -1), d_row_image, d_row_pix, psiflat, cpsi)
+        center, tables = self._params_at(win, None, self._prepack(), comb)
+        sf = torch.empty(nsym, device=dev, dtype=torch.int32)
+        exc = torch.empty_like(sf)
+        words = torch.empty(plan.words_len, device=dev, dtype=torch.uint8)
+        esc = torch.empty(plan.esc_len, device=dev, dtype=torch.int32)
+        # the encoder's nimg * G blocks, then pick's one block per image: one buffer, one read-back
+        state = torch.zeros((nimg * G + nimg, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
+        lib = L.load()
+        L.check(lib.lic_rans_encode_pick_ragged(F_._ptr(tables), F_._ptr(center), F_._ptr(y_sym), rows, F_._ptr(d_images),
+                                                nimg, F_._ptr(d_row_image), F_._ptr(d_order), M, self.y_W, F_._ptr(sf),
+                                                F_._ptr(exc), F_._ptr(state[nimg * G:]), F_._stream()),
+                "lic_rans_encode_pick_ragged")
+        L.check(lib.lic_rans_encode_ragged(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), plan.step_len.size,
+                                           F_._ptr(d_images), F_._ptr(d_blocks), nimg, G, rows, M, F_._ptr(words),
+                                           plan.words_len, F_._ptr(esc), plan.esc_len, F_._ptr(state), F_._stream()),
+                "lic_rans_encode_ragged")
+        owner = [(i, b) for i, (y_in, _, _) in enumerate(outs) for b in range(y_in.shape[0])]
+        h_state = state.cpu()                                                     # the first read-back that waits
+        picked = h_state[nimg * G:, RANS_LANES + 2].numpy()
+        blocks = _state_blocks(h_state[:nimg * G], G, lambda i, states, nw, ne, err: (err or picked[i // G]) and (
+            "the rANS encoder met a malformed table, a pixel index outside the image or step lengths that do not add up "
+            f"(error word {err | int(picked[i // G])})"), lambda im: f"{names[owner[im][0]]}: image {owner[im][1]}")
+        for i, (_, nw, ne) in enumerate(blocks):
+            if 2 * nw > plan.blocks[i, 1] or ne > plan.blocks[i, 3]:
+                raise CodecError(f"{names[owner[i // G][0]]}: image {owner[i // G][1]}: the rANS encoder reports "
+                                 f"impossible counts ({nw} words, {ne} escapes)")
+        h_words = words.cpu().numpy()
+        used = np.concatenate([plan.blocks[i, 2] + np.arange(ne, dtype=np.int64) for i, (_, _, ne) in enumerate(blocks)])
+        h_esc = (esc[torch.from_numpy(used).to(dev)].cpu().numpy() if used.size else np.zeros(0, np.int32)).view(np.uint32)
+        h_sym = y_sym.cpu().numpy()
+        h_sums = torch.stack(sums).cpu().numpy()
+        streams, escs, e_at = [], [], 0
+        for i, (states, nw, ne) in enumerate(blocks):
+            end = int(plan.blocks[i, 0] + plan.blocks[i, 1])
+            streams.append(states.astype("<u4").tobytes() + h_words[end - 2 * nw:end].tobytes())
+            escs.append(h_esc[e_at:e_at + ne].astype("<u4").tobytes())
+            e_at += ne
+        res, img = [], 0
+        for i, ((y_in, z_in, _), x) in enumerate(zip(outs, xs)):
+            B, _, h, w = y_in.shape
+            strings = {"z": z_bytes[i]}
+            if G > 1:
+                strings["groups"] = G
+            if R is not None:
+                strings["slice_rows"] = R
+            y_streams, y_esc = streams[img * G:(img + B) * G], escs[img * G:(img + B) * G]
+            row0 = int(plan.images[img, 0])
+            y_crc = [zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
+                     for a in h_sym[row0:row0 + B * h * w].reshape(B, h * w * M)]
+            strings.update(coder="rans", y_esc=y_esc, y=y_streams, y_crc32=y_crc)
+            npix = x.shape[0] * x.shape[2] * x.shape[3]
+            coded = 8.0 * (len(z_bytes[i]) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
+            res.append({"strings": strings, "shape": (B, M, h, w), "z_shape": tuple(z_in.shape), "bpp_coded": coded,
+                        "bpp_est": float(-h_sums[i] / np.log(2.0) / npix), "y_in": y_in, "z_in": z_in})
+            img += B
+        return res
+
     @torch.no_grad()
     def decompress(self, strings: Dict, shape, z_shape) -> Dict:
         m = self.model
@@ -987,13 +1206,53 @@ class ContextCodec:
         B, _, H, W = x.shape
         _, _, top, left = F_.pad_geometry(H, W, 64, align)
         r = self.compress(F_.pad_to_multiple(x, 64, mode, align))
-        s = r["strings"]
+        return self._pack_image(r["strings"], B, H, W, top, left)
+
+    def _pack_image(self, s: Dict, B: int, H: int, W: int, top: int, left: int) -> bytes:
+        """the container of `compress_image` around the strings `compress` gave for the padded image"""
         head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
                 "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
         if self.slice_rows is not None:
             return _pack((self.coder, "sliced"), dict(head, slice_rows=self.slice_rows), s["z"], s["y"], s["y_esc"],
                          s["y_crc32"], self.groups)
         return _pack((self.coder, self.groups > 1), head, s["z"], s["y"], s.get("y_esc"), s["y_crc32"], self.groups)
+
+    def _refuse_unless_batched_encoder(self):
+        if self.coder != "rans" or self.encoder != "device":
+            raise CodecError(f"this codec has coder={self.coder!r}, encoder={self.encoder!r}: images are encoded "
+                             "together by the device encoder of the 'rans' coder only (coder='rans', encoder='device'); "
+                             "encode them one by one with compress_image")
+
+    @torch.no_grad()
+    def compress_images(self, images: Sequence[torch.Tensor], mode: str = "replicate", align: str = "topleft",
+                        table_budget_bytes: int = 2 << 30) -> List[bytes]:
+        """Many images of any sizes in one encode pass: entry i is byte for byte `compress_image(images[i], mode,
+        align)`, the container of this codec's groups and slice_rows (LICBITS2 / 3 / 4).  All images of a chunk share
+        one gather, one pass through the per-pixel layers, one table launch and one launch of each encoder kernel
+        (`compress_many`, which also says what `table_budget_bytes` does).  Needs coder="rans", encoder="device".
+        Raises CodecError before any GPU work, every message naming its entry ("image i: ..."): a codec with another
+        coder or encoder, an entry that is not a [B,3,H,W] tensor, a tensor that is not on the GPU.  An empty list
+        gives an empty list."""
+        images = list(images)
+        for i, x in enumerate(images):
+            try:
+                self._refuse_unless_batched_encoder()
+                if not isinstance(x, torch.Tensor) or x.dim() != 4:
+                    raise CodecError("expected a [B,3,H,W] tensor")
+                if not x.is_cuda:
+                    raise CodecError("expected a tensor on the GPU: the device encoder runs where the tables are built")
+            except CodecError as err:
+                raise CodecError(f"image {i}: {err}") from None
+        if not images:
+            return []
+        names = [f"image {i}" for i in range(len(images))]
+        rs = self.compress_many([F_.pad_to_multiple(x, 64, mode, align) for x in images], table_budget_bytes, names)
+        blobs = []
+        for x, r in zip(images, rs):
+            B, _, H, W = x.shape
+            _, _, top, left = F_.pad_geometry(H, W, 64, align)
+            blobs.append(self._pack_image(r["strings"], B, H, W, top, left))
+        return blobs
 
     @torch.no_grad()
     def decompress_image(self, data: bytes) -> torch.Tensor:

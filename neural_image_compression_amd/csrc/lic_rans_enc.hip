@@ -2,6 +2,8 @@
 // streams (include/lic_codec.h) run where lic_gmm_cdf_tables has left the tables, so codec.ContextCodec.compress
 // copies streams, not tables, to the host.  Byte for byte the host encoder of lic_rans.cpp: same streams, same
 // escape lists.
+// lic_rans_encode_pick_ragged + lic_rans_encode_ragged, at the end of the file, are the same pair for images of different
+// sizes in one launch each (codec.ContextCodec.compress_images).
 //
 // An rANS encoder never searches: symbol k needs cum[s] and cum[s+1] of its own table, and neither its table nor
 // its symbol depends on a coder state.  So the work splits in two launches:
@@ -320,6 +322,118 @@ __global__ __launch_bounds__(64) void rans_encode_groups_kernel(const uint32_t* 
                 reinterpret_cast<uint16_t*>(words + (int64_t)blk * slot), (uint32_t)(slot >> 1), nesc, err, st, lane);
 }
 
+// ---- many images of different sizes in one launch each (codec.ContextCodec.compress_images) ----------------------
+// Every image brings its own rows, steps, slots and lists; where they lie is read from descriptors on the device, so
+// both kernels compare a descriptor with the lengths the entry was given before they address anything with it.
+
+// rans_pick_kernel for the rows of a whole chunk: position q of the coding order belongs to image row_image[q], whose
+// rows of tables, centres and symbols are [ROW0, ROW0 + P), and stands for raster pixel order[q] of that image.  The
+// lanes of a wave may belong to different images, so every symbol in error reports for itself
+__global__ __launch_bounds__(256) void rans_pick_ragged_kernel(
+    const uint32_t* __restrict__ tables, const int32_t* __restrict__ center, const int32_t* __restrict__ y,
+    int64_t total_rows, const int64_t* __restrict__ images, int32_t nimg, const int64_t* __restrict__ row_image,
+    const int64_t* __restrict__ order, int32_t M, int32_t W, int32_t nsym, uint32_t* __restrict__ sf,
+    uint32_t* __restrict__ exc, uint32_t* state) {
+  const int S1 = 2 * W + 2, S = S1 - 1;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nsym; k += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t q = (int32_t)k / M, c = (int32_t)k - q * M;
+    const int64_t b = row_image[q];
+    uint32_t word = kHarmless, excess = kNoEscape;
+    if (b >= 0 && b < nimg) {  // a row of no image has no error block to name
+      const int64_t row0 = images[b * LIC_RANS_IMAGE_WORDS + LIC_RANS_IMAGE_ROW0];
+      const int64_t P = images[b * LIC_RANS_IMAGE_WORDS + LIC_RANS_IMAGE_P];
+      const int64_t pix = order[q];
+      bool bad = true;
+      if (row0 >= 0 && P >= 1 && row0 <= total_rows && P <= total_rows - row0 && q >= row0 && q - row0 < P &&
+          pix >= 0 && pix < P) {
+        const int64_t i = (row0 + pix) * M + c;
+        // two's complement, as the host path's int32 tensor arithmetic
+        const int32_t idx = (int32_t)((uint32_t)y[i] - (uint32_t)center[i] + (uint32_t)W);
+        const int32_t s = idx <= 0 ? 0 : (idx >= S - 1 ? S - 1 : idx);
+        if (idx <= 0) excess = (uint32_t)(-(int64_t)idx);
+        if (idx >= S - 1) excess = (uint32_t)((int64_t)idx - (S - 1));
+        const uint32_t* row = tables + i * S1;
+        const uint32_t first = row[0], last = row[S], start = row[s], end = row[s + 1];
+        if (first == 0u && last == 65536u && end > start && end - start < 65536u && start < 65536u) {
+          word = (start << 16) | (end - start);
+          bad = false;
+        }
+      }
+      if (bad) atomicOr(state + (size_t)b * kStateWords + kLanes + 2, LIC_RANS_ERR_RANGE);
+    }
+    sf[k] = word;
+    exc[k] = excess;
+  }
+}
+
+// rans_encode_groups_kernel with one wave per (image, group) of images that differ in size: the image's range of sf /
+// exc / step_len and the block's slot and escape list come from the two descriptor tables.  A wave whose descriptors
+// do not fit the given lengths leaves what a wave leaves of step lengths it refuses; otherwise the same length check,
+// walks, ring and divide
+__global__ __launch_bounds__(64) void rans_encode_ragged_kernel(
+    const uint32_t* __restrict__ sf, const uint32_t* __restrict__ exc, const int64_t* __restrict__ step_len,
+    int64_t steps_len, const int64_t* __restrict__ images, const int64_t* __restrict__ blocks, int32_t G,
+    int64_t total_rows, int32_t M, uint8_t* __restrict__ words, int64_t words_len, uint32_t* __restrict__ esc_out,
+    int64_t esc_len, uint32_t* state) {
+  const int blk = blockIdx.x, b = blk / G, g = blk - b * G, lane = threadIdx.x;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  uint32_t* st = state + (size_t)blk * kStateWords;
+  uint32_t err = st[kLanes + 2];
+
+  const int64_t* im = images + (int64_t)b * LIC_RANS_IMAGE_WORDS;
+  const int64_t* bl = blocks + (int64_t)blk * LIC_RANS_BLOCK_WORDS;
+  const int64_t row0 = im[LIC_RANS_IMAGE_ROW0], P = im[LIC_RANS_IMAGE_P], step0 = im[LIC_RANS_IMAGE_STEP0],
+                nsteps = im[LIC_RANS_IMAGE_NSTEPS];
+  const int64_t word_off = bl[LIC_RANS_BLOCK_WORD_OFF], slot = bl[LIC_RANS_BLOCK_SLOT],
+                esc_off = bl[LIC_RANS_BLOCK_ESC_OFF], cap = bl[LIC_RANS_BLOCK_ESC_CAP];
+  // wave-uniform; every sum is written as a difference of checked terms, so none can overflow
+  const bool fits = row0 >= 0 && P >= 1 && step0 >= 0 && nsteps >= 0 && word_off >= 0 && slot >= 4 && esc_off >= 0 &&
+                    cap >= 1 && row0 <= total_rows && P <= total_rows - row0 && P <= (0x7FFFFFFFL - kLanes) / M &&
+                    step0 <= steps_len && nsteps <= steps_len - step0 && (word_off & 3) == 0 && (slot & 3) == 0 &&
+                    slot <= 0xFFFFFFFFL && word_off <= words_len && slot <= words_len - word_off &&
+                    cap <= 0x7FFFFFFFL && esc_off <= esc_len && cap <= esc_len - esc_off;
+  if (!fits) return refuse_steps(st, lane, err);
+
+  const int32_t nsym = (int32_t)(P * M);
+  const uint32_t esc_cap = (uint32_t)cap;
+  step_len += step0;
+  sf += row0 * M;
+  exc += row0 * M;
+  esc_out += esc_off;
+  const GroupRounds of{step_len, g, G};
+
+  int64_t rounds;
+  if (!step_lengths_ok(step_len, nsteps, nsym, lane, [&](int64_t n) { return (int64_t)of.count((int32_t)n); }, rounds))
+    return refuse_steps(st, lane, err);
+
+  // escapes, forward, in the symbol order of the group's rounds: rans_encode_groups_kernel's loop
+  uint32_t nesc = 0;
+  GroupWalkForward fwd{of, nsteps, 0, 0, 0, 0, 0};
+  for (int64_t r = 0; r < rounds; r += kRing) {
+    uint32_t e[kRing];
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {  // all loads first: none depends on the cursor, none sits under a branch
+      int32_t k0 = 0, n = 0;
+      fwd.next(k0, n);  // leaves (0, 0) once the walk is over
+      const uint32_t v = exc[lane < n ? k0 + lane : 0];
+      e[j] = lane < n ? v : kNoEscape;
+    }
+#pragma unroll
+    for (int j = 0; j < kRing; ++j) {
+      const bool edge = e[j] != kNoEscape;
+      const unsigned long long mask = __ballot(edge);
+      const uint32_t cnt = (uint32_t)__popcll(mask);
+      const bool room = cnt <= esc_cap - nesc;  // the round's escapes all fit or none is stored
+      if (edge && room) esc_out[nesc + (uint32_t)__popcll(mask & below)] = e[j];
+      nesc += room ? cnt : 0u;
+      err |= room ? 0u : LIC_RANS_ERR_RANGE;
+    }
+  }
+
+  encode_states(sf, GroupWalk{of, nsteps, nsym, 0, -1}, rounds, reinterpret_cast<uint16_t*>(words + word_off),
+                (uint32_t)(slot >> 1), nesc, err, st, lane);
+}
+
 }  // namespace
 
 LIC_EXPORT int lic_rans_encode_pick(const uint32_t* tables, const int32_t* center, const int32_t* y,
@@ -373,5 +487,47 @@ LIC_EXPORT int lic_rans_encode_groups(const uint32_t* sf, const uint32_t* exc, c
   if (slot < 4 || (slot & 3) || slot > 0xFFFFFFFFL || esc_cap < 1 || esc_cap > 0x7FFFFFFFL) return LIC_ERR_INVALID;
   hipLaunchKernelGGL(rans_encode_groups_kernel, dim3(B * G), dim3(kLanes), 0, (hipStream_t)stream, sf, exc, step_len,
                      nsteps, G, (int32_t)nsym, words, slot, esc_out, (uint32_t)esc_cap, state);
+  return lic_check_launch();
+}
+
+LIC_EXPORT int lic_rans_encode_pick_ragged(const uint32_t* tables, const int32_t* center, const int32_t* y,
+                                           int64_t total_rows, const int64_t* images, int32_t nimg,
+                                           const int64_t* row_image, const int64_t* order, int32_t M, int32_t W,
+                                           uint32_t* sf, uint32_t* exc, uint32_t* state, lic_stream_t stream) {
+  if (!tables || !center || !y || !images || !row_image || !order || !sf || !exc || !state) return LIC_ERR_INVALID;
+  if (total_rows <= 0 || nimg <= 0 || M <= 0 || W <= 0) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(tables) | reinterpret_cast<uintptr_t>(center) | reinterpret_cast<uintptr_t>(y) |
+       reinterpret_cast<uintptr_t>(sf) | reinterpret_cast<uintptr_t>(exc) | reinterpret_cast<uintptr_t>(state)) & 3)
+    return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(row_image) |
+       reinterpret_cast<uintptr_t>(order)) & 7)
+    return LIC_ERR_INVALID;
+  if (W > 64 || nimg > 65535) return LIC_ERR_UNSUPPORTED;
+  if (total_rows > 0x7FFFFFFFL || total_rows * M > 0x7FFFFFFFL - kLanes) return LIC_ERR_UNSUPPORTED;
+  const int32_t nsym = (int32_t)(total_rows * M);
+  hipLaunchKernelGGL(rans_pick_ragged_kernel, dim3(ew_grid(nsym, 256)), dim3(256), 0, (hipStream_t)stream, tables,
+                     center, y, total_rows, images, nimg, row_image, order, M, W, nsym, sf, exc, state);
+  return lic_check_launch();
+}
+
+LIC_EXPORT int lic_rans_encode_ragged(const uint32_t* sf, const uint32_t* exc, const int64_t* step_len,
+                                      int64_t steps_len, const int64_t* images, const int64_t* blocks, int32_t nimg,
+                                      int32_t G, int64_t total_rows, int32_t M, uint8_t* words, int64_t words_len,
+                                      uint32_t* esc_out, int64_t esc_len, uint32_t* state, lic_stream_t stream) {
+  if (!sf || !exc || !step_len || !images || !blocks || !words || !esc_out || !state) return LIC_ERR_INVALID;
+  if (nimg <= 0 || total_rows <= 0 || M <= 0 || steps_len <= 0 || words_len <= 0 || esc_len <= 0)
+    return LIC_ERR_INVALID;
+  if (G < 1 || G > LIC_RANS_MAX_GROUPS) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(sf) | reinterpret_cast<uintptr_t>(exc) | reinterpret_cast<uintptr_t>(words) |
+       reinterpret_cast<uintptr_t>(esc_out) | reinterpret_cast<uintptr_t>(state)) & 3)
+    return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(step_len) | reinterpret_cast<uintptr_t>(images) |
+       reinterpret_cast<uintptr_t>(blocks)) & 7)
+    return LIC_ERR_INVALID;
+  if ((int64_t)nimg * G > 65535) return LIC_ERR_UNSUPPORTED;
+  if (total_rows > 0x7FFFFFFFL || total_rows * M > 0x7FFFFFFFL - kLanes) return LIC_ERR_UNSUPPORTED;
+  // what every image's and block's descriptor must satisfy is the kernel's to check: they live on the device
+  hipLaunchKernelGGL(rans_encode_ragged_kernel, dim3(nimg * G), dim3(kLanes), 0, (hipStream_t)stream, sf, exc,
+                     step_len, steps_len, images, blocks, G, total_rows, M, words, words_len, esc_out, esc_len, state);
   return lic_check_launch();
 }

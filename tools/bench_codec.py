@@ -11,7 +11,11 @@ and SLICE_ROWS (comma list of latent rows per slice, 0 = no slices, applied to t
 BLOBS (comma list of blob counts, `BLOBS=1,4,16`) selects the batched-decode mode instead: for every SLICE_ROWS and GROUPS
 entry, N `compress_image` blobs of 512x768, 768x512 and 384x512 in turn are decoded once with `decompress_images` and
 once as a loop of `decompress_image`, alternating, warm, median of RUNS.  PROFILE=many:3 (or seq:3) skips the timing and
-makes just that many calls of one path on the first BLOBS entry, for a kernel trace whose counts can be subtracted."""
+makes just that many calls of one path on the first BLOBS entry, for a kernel trace whose counts can be subtracted.
+
+ENCODE_BLOBS (`ENCODE_BLOBS=1,4,16`) is the same mode for the encoder: N images of those sizes through `compress_images`
+and through a loop of `compress_image`, every blob compared with ==; a line also gives the host time of the layout
+(`ragged_encode_plan`) per call.  PROFILE works as above."""
 import os
 import statistics
 import sys
@@ -31,6 +35,7 @@ GROUPS = [int(g) for g in os.environ.get("GROUPS", "1").split(",")]
 SLICE_ROWS = [int(r) for r in os.environ.get("SLICE_ROWS", "0").split(",")]
 RUNS = int(os.environ.get("RUNS", "10"))
 BLOBS = [int(n) for n in os.environ.get("BLOBS", "").split(",") if n]
+ENCODE_BLOBS = [int(n) for n in os.environ.get("ENCODE_BLOBS", "").split(",") if n]
 PROFILE = os.environ.get("PROFILE", "")
 BLOB_SIZES = [(512, 768), (768, 512), (384, 512)]
 
@@ -72,10 +77,48 @@ def blob_mode(model):
                   f"{'bit-equal' if ok else 'MISMATCH'}, {sum(map(len, blobs))} bytes", flush=True)
 
 
+def encode_blob_mode(model):
+    """compress_images against a loop of compress_image on the same N images, in one process"""
+    from neural_image_compression_amd.codec import ragged_encode_plan
+    for rows, groups in [(r, g) for r in SLICE_ROWS for g in GROUPS]:
+        cc = ContextCodec(model, coder="rans", encoder="device", groups=groups, slice_rows=rows or None)
+        pool = [torch.rand(1, 3, h, w, device="cuda") for h, w in BLOB_SIZES]
+        for n in ENCODE_BLOBS:
+            xs = [pool[i % len(pool)] for i in range(n)]
+            many = lambda: cc.compress_images(xs)
+            seq = lambda: [cc.compress_image(x) for x in xs]
+            if PROFILE:
+                path, calls = PROFILE.split(":")
+                for _ in range(int(calls)):
+                    timed({"many": many, "seq": seq}[path])
+                print(f"profile: {calls} calls of {path}, {n} images, groups={groups} slice_rows={rows}", flush=True)
+                return
+            for _ in range(2):                                                   # warm: allocator, weight packs, tuning
+                a, b = many(), seq()
+            ok = len(a) == len(b) and all(u == v for u, v in zip(a, b))
+            t_many, t_seq, t_plan = [], [], []
+            for _ in range(RUNS):                                                # alternating: same clocks for both
+                t_many.append(timed(many)[1])
+                t_seq.append(timed(seq)[1])
+                t0 = time.perf_counter()
+                ragged_encode_plan([(-(-x.shape[2] // 64) * 4, -(-x.shape[3] // 64) * 4) for x in xs], M, cc.pad,
+                                   rows or None, groups)
+                t_plan.append(1e3 * (time.perf_counter() - t0))
+            mm, ms = statistics.median(t_many), statistics.median(t_seq)
+            print(f"JAH({M},{K}) groups={groups} slice_rows={rows} images={n}: compress_images {mm:8.2f} ms "
+                  f"(min {min(t_many):.2f}, max {max(t_many):.2f}; {mm / n:6.2f} ms per image), loop of compress_image "
+                  f"{ms:8.2f} ms (min {min(t_seq):.2f}, max {max(t_seq):.2f}; {ms / n:6.2f} ms per image), median of {RUNS}, "
+                  f"layout on the host {statistics.median(t_plan):.2f} ms per call, "
+                  f"{'byte-equal' if ok else 'MISMATCH'}, {sum(map(len, a))} bytes", flush=True)
+
+
 torch.manual_seed(0)
 model = nic.JointAutoregressiveHierarchical(M, K).cuda().eval()
 if BLOBS:
     blob_mode(model)
+    sys.exit(0)
+if ENCODE_BLOBS:
+    encode_blob_mode(model)
     sys.exit(0)
 x = torch.rand(1, 3, H, W, device="cuda").contiguous(memory_format=torch.channels_last)
 for coder, encoder, rows, groups in [(c, e, r, g) for c in CODERS for e in (ENCODERS if c == "rans" else ["host"])
