@@ -781,6 +781,50 @@ int lic_window_f32(const float* src, int64_t sb, int64_t sc, int64_t sh, int64_t
                    lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * lic_resample -- a window of an image resized with Pillow's 8-bit bicubic filter: resize, crop, flip and
+ *   ToTensor() as one launch.
+ *   The reference draws a downscale factor per image, resizes with Image.BICUBIC and cuts one crop, once,
+ *   offline, on the host (preprocess.py:23-33).  Pillow's 8-bit resize is integer arithmetic on integer
+ *   coefficients, so the result here equals Pillow's byte for byte.  The resize is defined per axis.
+ *   One axis, n_in samples to n_out.  n_out == n_in: the axis is copied (Pillow skips the pass).  Otherwise,
+ *   in IEEE double with every operation rounded on its own (no fused multiply-add):
+ *     scale = n_in / n_out;  fs = max(scale, 1.0);  support = 2.0 * fs;  ss = 1.0 / fs
+ *     for output index xx:
+ *       center = (xx + 0.5) * scale
+ *       xmin = max(0, (int)(center - support + 0.5));  xmax = min(n_in, (int)(center + support + 0.5)) - xmin
+ *       w[x] = bicubic((x + xmin - center + 0.5) * ss), x in [0, xmax), with a = -0.5:
+ *              |t| < 1: ((a + 2) t - (a + 3)) t t + 1;   |t| < 2: (((t - 5) t + 8) t - 4) a;   else 0
+ *       ww = w[0] + w[1] + ... (left to right);  w[x] = w[x] / ww
+ *       k[x] = (int)(w[x] * 2^22 + (w[x] < 0 ? -0.5 : 0.5))               (truncation toward zero)
+ *       out = clamp((2^21 + sum_x pixel[xmin + x] * k[x]) >> 22, 0, 255)    (32-bit integers, arithmetic shift)
+ *   Two axes: the horizontal pass first, to uint8; the vertical pass on those uint8 values, to uint8; the float
+ *   is float(v) / 255, the single division of lic_u8_to_f32.  A window of the resized image is computed from
+ *   its own rows and columns only (the horizontal pass runs over the source rows the window's rows read) and
+ *   equals resize-then-crop exactly.
+ *   `out` is [B][h][w][C] contiguous fp32 (16-byte aligned, at most 2^31 - 1 elements), C <= 4
+ *   (LIC_ERR_UNSUPPORTED above):
+ *     out[b, oy, ox, c] = resized_b(y0 + oy, x0 + ox', c) / 255,   ox' = (flags & 1) ? w - 1 - ox : ox
+ *   with resized_b image b resized to Hn x Wn.  Supported per axis: n_in / 2 <= n_out <= n_in (downscale by at
+ *   most 2, so at most 9 taps), the window inside the resized image.  The job table lives on the device (8-byte
+ *   aligned), so the library cannot inspect it: sizes, the range of Hn / Wn, the window and the offsets are the
+ *   caller's to check before the upload (data.resample_jobs does).  Every source index is still resolved to an
+ *   in-range index before any load -- first taps clamped into [0, n_in), tap counts into [0, 9], an Hn or Wn
+ *   outside the supported range treated as "copy" -- so a table nobody validated produces garbage but no
+ *   address leaves an image's [src_offset, src_offset + Hs*Ws*C).
+ *   One launch, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct lic_resample_job { /* 40 bytes, one per output image */
+  int64_t src_offset;             /* bytes from `pool` to this image's [Hs][Ws][C] uint8 pixels */
+  int32_t Hs, Ws;                 /* source image size */
+  int32_t Hn, Wn;                 /* size the image is resized to */
+  int32_t y0, x0;                 /* window origin in the resized image */
+  int32_t flags;                  /* bit 0: horizontal flip of the WINDOW */
+  int32_t reserved;
+} lic_resample_job;
+int lic_resample_u8_to_f32(const uint8_t* pool, const lic_resample_job* jobs_device, int32_t B, int32_t h, int32_t w,
+                           int32_t C, float* out, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * lic_prep -- every parameter-derived buffer of a model refreshed by ONE launch per optimizer step.
  *   The reference keeps derived values implicit in ATen (cuDNN/oneDNN repack weights internally; compressai's
  *   GDN recomputes beta/gamma re-parametrisations in every forward, Components.py:11-44; ContextModels.py:19

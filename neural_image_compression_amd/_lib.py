@@ -92,6 +92,11 @@ class WindowJob(C.Structure):
                 ("reserved", _i32)]
 
 
+class ResampleJob(C.Structure):
+    _fields_ = [("src_offset", _i64), ("Hs", _i32), ("Ws", _i32), ("Hn", _i32), ("Wn", _i32), ("y0", _i32),
+                ("x0", _i32), ("flags", _i32), ("reserved", _i32)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/lic.h
 SIGNATURES = {
     "lic_igemm": (C.c_int, [C.POINTER(IgemmDesc), _vp]),
@@ -190,6 +195,7 @@ SIGNATURES = {
     "lic_u8_to_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
     "lic_window_u8_to_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lic_window_f32": (C.c_int, [_vp, _i64, _i64, _i64, _i64] + [_i32] * 9 + [_vp, _vp]),
+    "lic_resample_u8_to_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lic_tensor_stats_workspace_bytes": (_sz, []),
     "lic_tensor_stats": (C.c_int, [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _sz, _vp]),
     "lic_prep_plan": (_i64, [C.POINTER(PrepJob), _i32]),

@@ -20,6 +20,12 @@ byte_offset bytes after the end of the entry table.  `RaggedShardDataset` maps s
 preprocess.py:30-32 fixes one window per image for ever -- with the pixels resident in HBM: a batch is
 one 32*B-byte job table and one `lic_window_u8_to_f32` launch.  `load_image_u8` is the evaluation-side
 use of the same kernel: one image padded to the multiple of 64 the models need.
+
+Random scale: preprocess.py:23-33 also draws a downscale factor per image and resizes with Pillow's
+`Image.BICUBIC` before it crops.  `RandomCropLoader(min_factor=...)` draws the factor per image and epoch and
+`lic_resample_u8_to_f32` resizes, crops, flips and converts in one launch, byte for byte what Pillow gives
+(`resample_jobs`, `resample_u8_to_f32`).  `shard_from_image_files` applies the reference's two discard rules
+(smallest side, saturation) when asked to.
 """
 from __future__ import annotations
 
@@ -47,12 +53,27 @@ def write_shard(path: str, images: np.ndarray) -> None:
         f.write(a.tobytes())
 
 
-def shard_from_image_files(files: Sequence[str], path: str, ragged: bool = False) -> int:
+def is_saturated(image: np.ndarray, threshold: float = 0.95) -> bool:
+    """The reference's saturation verdict (preprocess.py:18-21) on a uint8 [H,W,C] image: in float32, more than
+    5 % of the pixels have a spread of v/255 over the channels above `threshold`."""
+    v = np.asarray(image, np.uint8).astype(np.float32) / np.float32(255.0)
+    spread = v.max(axis=2) - v.min(axis=2)
+    return bool(np.mean(spread > np.float32(threshold)) > 0.05)
+
+
+def shard_from_image_files(files: Sequence[str], path: str, ragged: bool = False, min_side: Optional[int] = None,
+                           saturation_thresh: Optional[float] = None) -> int:
     """Decode image files (the sorted jpg/jpeg/png list of Dataloader.py:13-18, `.convert("RGB")`)
     once, offline, into a shard.  All images must share one size (preprocess.py crops to 256x256)
-    unless `ragged=True`, which writes shard format 2 (`write_ragged_shard`)."""
+    unless `ragged=True`, which writes shard format 2 (`write_ragged_shard`).  `min_side` skips images with
+    min(H, W) < min_side and `saturation_thresh` those `is_saturated` at that threshold (preprocess.py:56-62
+    discards both kinds); returns the number of images written."""
     from PIL import Image  # offline tool only
     arrs = [np.asarray(Image.open(f).convert("RGB"), np.uint8) for f in files]
+    if min_side is not None:
+        arrs = [a for a in arrs if min(a.shape[:2]) >= min_side]
+    if saturation_thresh is not None:
+        arrs = [a for a in arrs if not is_saturated(a, saturation_thresh)]
     if not arrs:
         raise ValueError("no images")
     if ragged:
@@ -160,6 +181,9 @@ _ENTRY2 = np.dtype([("H", "<u4"), ("W", "<u4"), ("offset", "<u8")])
 # host mirror of lic_window_job (include/lic.h), as a numpy record so that a table is built without a Python loop
 WINDOW_JOB = np.dtype([("src_offset", "<i8"), ("Hs", "<i4"), ("Ws", "<i4"), ("y0", "<i4"), ("x0", "<i4"),
                        ("flags", "<i4"), ("reserved", "<i4")])
+# host mirror of lic_resample_job
+RESAMPLE_JOB = np.dtype([("src_offset", "<i8"), ("Hs", "<i4"), ("Ws", "<i4"), ("Hn", "<i4"), ("Wn", "<i4"),
+                         ("y0", "<i4"), ("x0", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 BORDERS = {"zeros": L.WINDOW_ZERO, "constant": L.WINDOW_ZERO, "replicate": L.WINDOW_REPLICATE,
            "edge": L.WINDOW_REPLICATE, "reflect": L.WINDOW_REFLECT}
 
@@ -307,6 +331,61 @@ def window_u8_to_f32(pool: torch.Tensor, jobs: np.ndarray, h: int, w: int, C: in
     return out.permute(0, 3, 1, 2)
 
 
+def resample_jobs(offsets, sizes, new_sizes, y0, x0, flip, h: int, w: int, C: int = 3,
+                  pool_bytes: Optional[int] = None):
+    """The host copy of a lic_resample_job table (a RESAMPLE_JOB record array), checked: the library cannot
+    inspect a table that lives on the device, so everything the kernel assumes is verified here -- sizes >= 1,
+    per axis ceil(n_in / 2) <= n_out <= n_in, the h x w window inside the resized image, offsets inside the
+    pool."""
+    sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
+    n = sizes.shape[0]
+    new_sizes = np.broadcast_to(np.asarray(new_sizes, np.int64).reshape(-1, 2), (n, 2))
+    offsets = np.broadcast_to(np.asarray(offsets, np.int64), (n,))
+    y0 = np.broadcast_to(np.asarray(y0, np.int64), (n,))
+    x0 = np.broadcast_to(np.asarray(x0, np.int64), (n,))
+    flip = np.broadcast_to(np.asarray(flip, np.int64), (n,))
+    if n == 0 or h <= 0 or w <= 0:
+        raise ValueError("empty resample table")
+    if not 1 <= C <= 4:
+        raise ValueError("lic_resample_u8_to_f32 takes 1 to 4 channels")
+    if np.any(sizes < 1) or np.any(sizes >= 2 ** 30):
+        raise ValueError("source sizes must be in [1, 2^30)")
+    if np.any(offsets < 0) or (pool_bytes is not None and np.any(offsets + sizes[:, 0] * sizes[:, 1] * C > pool_bytes)):
+        raise ValueError("an image lies outside the pool")
+    if np.any(new_sizes > sizes) or np.any(new_sizes < (sizes + 1) // 2):
+        raise L.LicError("lic_resample_u8_to_f32 failed: LIC_ERR_INVALID (a new size outside [ceil(n / 2), n]: "
+                         "downscaling by at most 2 is supported, upscaling is not)")
+    if np.any(y0 < 0) or np.any(x0 < 0) or np.any(y0 + h > new_sizes[:, 0]) or np.any(x0 + w > new_sizes[:, 1]):
+        raise L.LicError("lic_resample_u8_to_f32 failed: LIC_ERR_INVALID (a window leaves the resized image)")
+    jobs = np.zeros(n, RESAMPLE_JOB)
+    jobs["src_offset"], jobs["Hs"], jobs["Ws"] = offsets, sizes[:, 0], sizes[:, 1]
+    jobs["Hn"], jobs["Wn"] = new_sizes[:, 0], new_sizes[:, 1]
+    jobs["y0"], jobs["x0"], jobs["flags"] = y0, x0, (flip != 0) * L.WINDOW_FLIP
+    return jobs
+
+
+def resample_u8_to_f32(pool: torch.Tensor, jobs: np.ndarray, h: int, w: int, C: int = 3) -> torch.Tensor:
+    """`pool`: uint8 device tensor (any shape; offsets are bytes from its first element); `jobs`: a table from
+    `resample_jobs`.  One pinned 40*B-byte upload and one lic_resample_u8_to_f32 launch -> fp32 [B,C,h,w]
+    (channels_last memory): the h x w window of every image resized with Pillow's 8-bit bicubic filter."""
+    if not isinstance(pool, torch.Tensor) or pool.dtype != torch.uint8:
+        raise ValueError("expected a uint8 tensor")
+    if not pool.is_cuda:
+        raise L.LicError("lic_resample_u8_to_f32 needs a CUDA tensor (there is no CPU fallback)")
+    if jobs.dtype != RESAMPLE_JOB or not pool.is_contiguous():
+        raise ValueError("jobs must be a resample_jobs() table and the pool contiguous")
+    if int((jobs["src_offset"] + jobs["Hs"].astype(np.int64) * jobs["Ws"] * C).max()) > pool.numel():
+        raise ValueError("an image lies outside the pool")
+    B = jobs.shape[0]
+    host = torch.empty(B * RESAMPLE_JOB.itemsize, dtype=torch.uint8, pin_memory=True)
+    host.numpy()[:] = jobs.view(np.uint8)
+    dev = host.to(pool.device, non_blocking=True)
+    out = torch.empty((B, h, w, C), device=pool.device, dtype=torch.float32)
+    L.check(L.load().lic_resample_u8_to_f32(F_._ptr(pool), F_._ptr(dev), B, h, w, C, F_._ptr(out), F_._stream()),
+            "lic_resample_u8_to_f32")
+    return out.permute(0, 3, 1, 2)
+
+
 def load_image_u8(t_u8_hwc: torch.Tensor, multiple: int = 64, mode="replicate", align: str = "topleft"):
     """One uint8 [H,W,C] image on the device -> (x_padded fp32 [1,C,Hp,Wp] channels_last, (H, W, top, left)):
     v/255 and the padding to a multiple of `multiple` in one lic_window_u8_to_f32 launch."""
@@ -335,12 +414,27 @@ class RandomCropLoader:
     Rank r of `world_size` takes slots [r * per, (r + 1) * per), per = N // world_size (as `ShardLoader.order`),
     so ranks see disjoint images; `schedule(epoch)` returns this rank's rows (image, y0, x0, flip).
 
+    `min_factor` (0.5 <= min_factor <= 1; None, the default, leaves everything above as it is) adds the random
+    downscale of preprocess.py:23-33: every image is resized with Pillow's 8-bit bicubic filter before the crop,
+    byte for byte what `Image.resize(..., Image.BICUBIC)` gives.  One more draw follows the ones above:
+      4. `us = rs.random_sample(N)`             -- slot k: factor = min_factor + us[k] * (1 - min_factor),
+                                                   Hn = int(H * factor), Wn = int(W * factor), and at least
+                                                   ceil(H / 2), ceil(W / 2): the kernel downscales by at most 2,
+                                                   which an odd side at a factor just above 0.5 would exceed;
+    y0 and x0 come from the same uy / ux with (Hn, Wn) in the place of (H, W), and `schedule(epoch)` returns
+    rows (image, y0, x0, flip, Hn, Wn).  A batch is then one 40*B-byte table and one lic_resample_u8_to_f32
+    launch.  Images with min(H, W) * min_factor < crop are refused (the reference discards them,
+    preprocess.py:61).
+
     `resident=True` uploads all pixel bytes once; a batch is one pinned 32*B-byte job table and one
     lic_window_u8_to_f32 launch.  `resident=False` concatenates the B source images of a batch into a pinned
     staging buffer, copies it once and runs the same kernel with offsets into that buffer."""
 
+    min_factor: Optional[float] = None
+
     def __init__(self, dataset: RaggedShardDataset, batch_size: int, crop: int = 256, device="cuda", seed: int = 0,
-                 hflip: bool = False, resident: bool = True, drop_last: bool = True, rank: int = 0, world_size: int = 1):
+                 hflip: bool = False, resident: bool = True, drop_last: bool = True, rank: int = 0, world_size: int = 1,
+                 min_factor: Optional[float] = None):
         self.ds, self.bs, self.crop, self.device = dataset, int(batch_size), int(crop), torch.device(device)
         self.seed, self.hflip, self.resident, self.drop_last = int(seed), bool(hflip), bool(resident), bool(drop_last)
         self.rank, self.world = int(rank), int(world_size)
@@ -350,6 +444,14 @@ class RandomCropLoader:
         small = int(np.sum((dataset.sizes < self.crop).any(axis=1)))
         if small:
             raise ValueError(f"{small} of {len(dataset)} images are smaller than the {self.crop}x{self.crop} crop on a side")
+        self.min_factor = None if min_factor is None else float(min_factor)
+        if self.min_factor is not None:
+            if not 0.5 <= self.min_factor <= 1.0:
+                raise ValueError(f"min_factor must lie in [0.5, 1], got {min_factor}")
+            small = int(np.sum(dataset.sizes.min(axis=1) * self.min_factor < self.crop))
+            if small:
+                raise ValueError(f"{small} of {len(dataset)} images are too small for a {self.crop}x{self.crop} crop "
+                                 f"after a downscale by min_factor={self.min_factor}")
         self._per = len(dataset) // self.world
         self._n_batches = self._per // self.bs if drop_last else (self._per + self.bs - 1) // self.bs
         self._pool = None
@@ -371,16 +473,22 @@ class RandomCropLoader:
 
     def schedule(self, epoch: int) -> np.ndarray:
         """int64 [n, 4] rows (image, y0, x0, flip) of this rank's slots in `epoch`, n = per-rank image count
-        (whole batches only when drop_last)"""
+        (whole batches only when drop_last); with `min_factor`, [n, 6] rows (image, y0, x0, flip, Hn, Wn)"""
         n_all = len(self.ds)
         rs = np.random.RandomState(self.seed + int(epoch))
         order = rs.permutation(n_all)
         uy, ux = rs.random_sample(n_all), rs.random_sample(n_all)
         flip = rs.randint(0, 2, n_all) if self.hflip else np.zeros(n_all, np.int64)
-        room = self.ds.sizes[order] - self.crop + 1                     # [N, 2] positions available, >= 1
+        sizes = self.ds.sizes[order]
+        if self.min_factor is not None:
+            factor = self.min_factor + rs.random_sample(n_all) * (1.0 - self.min_factor)
+            # int(H * factor), int(W * factor); an odd side at a factor just above 0.5 would land on (n - 1) / 2
+            sizes = np.maximum((sizes * factor[:, None]).astype(np.int64), (sizes + 1) // 2)
+        room = sizes - self.crop + 1                                    # [N, 2] positions available, >= 1
         y0 = np.minimum((uy * room[:, 0]).astype(np.int64), room[:, 0] - 1)
         x0 = np.minimum((ux * room[:, 1]).astype(np.int64), room[:, 1] - 1)
-        rows = np.stack([order, y0, x0, flip], axis=1).astype(np.int64)
+        cols = [order, y0, x0, flip] + ([sizes[:, 0], sizes[:, 1]] if self.min_factor is not None else [])
+        rows = np.stack(cols, axis=1).astype(np.int64)
         rows = rows[self.rank * self._per:(self.rank + 1) * self._per]
         return rows[:self._n_batches * self.bs] if self.drop_last else rows
 
@@ -396,6 +504,10 @@ class RandomCropLoader:
             for i, o, n in zip(img, offsets, nbytes):
                 flat[o:o + n] = ds[int(i)].reshape(-1)
             pool = host.to(self.device, non_blocking=True)
+        if self.min_factor is not None:
+            jobs = resample_jobs(offsets, ds.sizes[img], rows[:, 4:6], rows[:, 1], rows[:, 2], rows[:, 3], self.crop,
+                                 self.crop, ds.C)
+            return resample_u8_to_f32(pool, jobs, self.crop, self.crop, ds.C)
         jobs = window_jobs(offsets, ds.sizes[img], rows[:, 1], rows[:, 2], rows[:, 3], self.crop, self.crop,
                            L.WINDOW_ZERO, ds.C)
         return window_u8_to_f32(pool, jobs, self.crop, self.crop, ds.C, L.WINDOW_ZERO)
