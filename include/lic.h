@@ -700,6 +700,69 @@ int lic_rans_encode_ragged(const uint32_t* sf, const uint32_t* exc, const int64_
                            uint32_t* state, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SURVEY 8(f).2h -- the hyper-latent z as "rANS-64 x G" streams, coded by kernels (codec.ContextCodec(z_coder="rans")).
+ *   The z prior has no parameters: a stream has M tables [M][S+1] (lic_factorized_cdf_tables' output, any S >= 2) and
+ *   symbol k of an image -- pixel by pixel, channel by channel over its [h4][w4][M] plane -- uses table k % M and
+ *   codes idx = z - lo.  An image is ONE step of all its symbols: round r (symbols 64 r .. 64 r + 63) belongs to
+ *   sub-stream r % G, and the edge symbols 0 and S-1 escape into the sub-stream's uint32 list, exactly as for y.
+ *
+ *   lic_rans_z_pick -- the parallel half of the encoder, one thread per z symbol of the whole call; all images lie
+ *   flat, one after the other, each a multiple of M symbols long, so k % M is the channel everywhere.
+ *     tables        [M][S+1] uint32
+ *     z             [n] int32: the rounded hyper-latents of all images (the symbols, not fp32)
+ *     sf, exc       [n] uint32 out, exactly lic_rans_encode_pick's words: cum[s] << 16 | freq of s = clamp(idx, 0, S-1),
+ *                   idx = z - lo in 32-bit two's complement; the excess (-idx for idx <= 0, idx - (S-1) for idx >= S-1,
+ *                   0 at idx == 0 and idx == S-1) or 0xFFFFFFFF for no escape
+ *     err           one uint32 for the whole call, touched by atomic OR only; the caller zeroes it and folds it into
+ *                   every block's error word
+ *   The table of every symbol is validated as lic_rans_encode_pick does (cum[0] == 0, cum[S] == 65536, 0 < freq <
+ *   65536); a violation codes (start 0, freq 1) without an escape and ORs LIC_RANS_ERR_RANGE into *err.
+ *   The serial half is lic_rans_encode_ragged, unchanged: image b is the descriptor (ROW0 = its first pixel, P = its
+ *   h4 * w4 pixels, NSTEPS = 1) with the step length P * M, sf and exc as written here.
+ *   NULL pointers, M <= 0, S < 2, n <= 0, n % M != 0, a pointer that is not 4-byte aligned: LIC_ERR_INVALID.
+ *   S > LIC_RANS_Z_MAX_S, M > LIC_RANS_Z_MAX_M, n >= 2^31 - 64: LIC_ERR_UNSUPPORTED.
+ *
+ *   lic_rans_z_decode -- nimg * G workgroups of one wave; wave (b, g) decodes rounds g, g + G, ... of image b's single
+ *   step from block b * G + g.  streams .. state are lic_rans_decode_step_ragged's staging arguments and state blocks
+ *   (seeded with the streams' 64 states, 0, 0, 0; checked by the caller afterwards: word cursor at the end, escape
+ *   cursor at its count, every state 2^16, error word 0).
+ *     nsym          [nimg] int64 (device): image b's symbols, >= 0.  0: the image has no z in this call, its blocks
+ *                   stay bit for bit as they were.  So do the blocks of groups g >= ceil(nsym / 64).
+ *     z, z_len      one flat fp32 buffer and its length in floats; z_base [nimg] int64 (device): symbol k of image b is
+ *                   written to z[z_base[b] + k] as float(idx + lo), the escape excess applied at the edge symbols.
+ *                   Nothing else is written.
+ *     path          LIC_RANS_Z_AUTO: the M tables are staged once per wave into LDS as M rows of S 16-bit entries
+ *                   (cum[0..S-1] < 65536, cum[S] implied) at a pitch of the smallest P >= S with P % 4 == 2, and stay
+ *                   there for the whole stream, if M * P * 2 <= LIC_RANS_Z_LDS_BYTES (192 x 129: 49 920 bytes);
+ *                   otherwise the rows are searched in global memory.  LIC_RANS_Z_RESIDENT forces the first
+ *                   (LIC_ERR_INVALID above the budget), LIC_RANS_Z_GLOBAL the second.  Both write the same bytes.
+ *                   lic_rans_z_decode_path(M, S) says which of the two AUTO takes (a host function, no launch).
+ *   Checked on the device before anything is addressed with it: a negative nsym or one of 2^31 - 64 or more, or a plane
+ *   that does not lie inside [0, z_len), sets LIC_RANS_ERR_RANGE in the image's blocks, reads and writes nothing else.
+ *   Every wave validates the tables while it stages them, by pick's rules: a malformed table sets LIC_RANS_ERR_RANGE in
+ *   the block and decodes nothing, no z element is written.  A stream_bytes below 256 or beyond its slot, or a
+ *   stream_off that is negative or no multiple of 4: LIC_RANS_ERR_STREAM.  Word and escape cursors are compared with
+ *   their lengths before every read: out of range reads nothing and sets LIC_RANS_ERR_RANGE.  A block in error decodes
+ *   its later symbols as lo + S / 2; the other blocks carry on.
+ *   NULL pointers, M, nimg, z_len <= 0, S < 2, G outside 1..LIC_RANS_MAX_GROUPS, an unknown path, misaligned pointers
+ *   (int64 arrays 8 bytes, the others 4): LIC_ERR_INVALID.  S > LIC_RANS_Z_MAX_S, M > LIC_RANS_Z_MAX_M, nimg * G > 65535,
+ *   z_len > 2^40: LIC_ERR_UNSUPPORTED.  One launch each, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+#define LIC_RANS_Z_AUTO 0
+#define LIC_RANS_Z_RESIDENT 1
+#define LIC_RANS_Z_GLOBAL 2
+#define LIC_RANS_Z_LDS_BYTES 65536 /* the LDS budget of the resident path */
+#define LIC_RANS_Z_MAX_S 4096
+#define LIC_RANS_Z_MAX_M 65535
+int lic_rans_z_pick(const uint32_t* tables, int32_t M, int32_t lo, int32_t S, const int32_t* z, int64_t n, uint32_t* sf,
+                    uint32_t* exc, uint32_t* err, lic_stream_t stream);
+int lic_rans_z_decode_path(int32_t M, int32_t S);
+int lic_rans_z_decode(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
+                      const uint32_t* escapes, const int64_t* esc_off, uint32_t* state, const uint32_t* tables,
+                      int32_t M, int32_t lo, int32_t S, int32_t nimg, int32_t G, const int64_t* nsym,
+                      const int64_t* z_base, float* z, int64_t z_len, int32_t path, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).1 -- evaluation metric on the device.
  * Multi-scale SSIM exactly as the reference's evaluator calls it (Evaluator.py:7,38,45:
  * `ms_ssim(recon, orig, data_range=1.0, size_average=True)` of the third-party pytorch-msssim==0.2.1,

@@ -84,6 +84,17 @@ int lic_rans_encode(const uint32_t* tables, int32_t S, const int32_t* idx, int64
                     size_t* nesc);
 int lic_rans_decode(const uint8_t* in, size_t nbytes, const uint32_t* esc, size_t nesc, const uint32_t* tables,
                     int32_t S, int64_t n, const int64_t* step_len, int64_t nsteps, int32_t* idx_out);
+/* The same coder for symbols that SHARE tables, lic_rc_encode's convention: tables is [T][S+1] and table_of[i] in
+ * [0, T) selects the table of symbol i (NULL: table i, T is not read -- lic_rans_encode / lic_rans_decode).  The
+ * hyper-latent z of codec.ContextCodec(z_coder="rans") is such a stream: T = M tables, table_of[k] = k % M, one step
+ * of all the image's symbols dealt to G sub-streams.  Everything lic_rans_encode / lic_rans_decode refuse, and a
+ * table_of entry outside [0, T): LIC_CODEC_ERR_INVALID, before anything is indexed with it.  Any S >= 2. */
+int lic_rans_encode_shared(const uint32_t* tables, const int32_t* table_of, int32_t T, int32_t S, const int32_t* idx,
+                           int64_t n, const int64_t* step_len, int64_t nsteps, uint8_t* out, size_t cap,
+                           size_t* nbytes, uint32_t* esc_out, size_t esc_cap, size_t* nesc);
+int lic_rans_decode_shared(const uint8_t* in, size_t nbytes, const uint32_t* esc, size_t nesc, const uint32_t* tables,
+                           const int32_t* table_of, int32_t T, int32_t S, int64_t n, const int64_t* step_len,
+                           int64_t nsteps, int32_t* idx_out);
 /* lic_rc_ideal_bits' definition with 32 bits per escape instead of the Elias-gamma length */
 double lic_rans_ideal_bits(const uint32_t* tables, const int32_t* table_of, int32_t S, const int32_t* idx,
                            int64_t n);

@@ -83,6 +83,10 @@ CTX_IMAGE_WORDS = 8
 # ESC_OFF, ESC_CAP
 RANS_IMAGE_WORDS = RANS_BLOCK_WORDS = 4
 
+# lic_rans_z_decode's `path`: tables resident in LDS where they fit its budget, or searched in global memory
+RANS_Z_AUTO, RANS_Z_RESIDENT, RANS_Z_GLOBAL = range(3)
+RANS_Z_MAX_S, RANS_Z_MAX_M, RANS_Z_LDS_BYTES = 4096, 65535, 65536
+
 WINDOW_ZERO, WINDOW_REPLICATE, WINDOW_REFLECT = range(3)
 WINDOW_FLIP = 1
 
@@ -186,6 +190,9 @@ SIGNATURES = {
     "lic_ctx_gather_ragged": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
                                         _vp, _i64, _i32, _vp]),
     "lic_rans_decode_step_ragged": (C.c_int, [_vp] * 9 + [_i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "lic_rans_z_pick": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "lic_rans_z_decode_path": (C.c_int, [_i32, _i32]),
+    "lic_rans_z_decode": (C.c_int, [_vp] * 7 + [_i32] * 5 + [_vp, _vp, _vp, _i64, _i32, _vp]),
     "lic_msssim_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "lic_msssim": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _sz,
                              _vp]),

@@ -1,6 +1,7 @@
 """The self-describing container of `ContextCodec.compress_image` (host only, no torch): one byte string per batch
-of images of any size.  Four formats, one per (coder, grouping) pair of the y streams; `_FORMATS` below describes
-them, `_pack` writes and `_unpack` reads all four, and the eight public functions are their wrappers.
+of images of any size.  Five formats, one per (coder, grouping) pair of the y streams and one for rANS-coded z;
+`_FORMATS` and `_FORMAT_ZRANS_ROW` below describe them, `_pack` writes and `_unpack` reads all five, and the ten public
+functions are their wrappers.
 
 Every format, little endian:
   magic (8 bytes) | uint32 family (1 = JointAutoregressiveHierarchical, 2 = HierarchicalMixtureResidual)
@@ -15,6 +16,7 @@ The padded size is the next multiple of 64 of (H, W); the latent is [B, M, Hp/16
   LICBITS2  rans   64                none              y length, symbol CRC-32, escapes   1
   LICBITS3  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G ("rANS-64 x G", `rans_deal`)
   LICBITS4  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G, and the slice_rows word
+  LICBITS5  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G, slice_rows word, z section
 
 "symbol CRC-32" is `compress`'s y_crc32 of that image's latent symbols, "escapes" the number of uint32 in the block's
 escape list.  `lanes` is the interleaving of an image's y streams.  A LICBITS2 reader refuses any value but 64: wider
@@ -24,6 +26,13 @@ states or of odd length.  LICBITS4 is LICBITS3 with one more header word: `slice
 of the context model (codec.ContextCodec: no context tap crosses a boundary between bands of R rows, and the bands
 decode side by side); `compress_image` writes it only for a codec with slices, for any G.  Its reader refuses what
 LICBITS3's does, and R = 0 as a damaged header; R comes back as head["slice_rows"].
+LICBITS5 is the container of a codec with z_coder="rans" (codec.ContextCodec), for any G, with or without slices: the
+header is LICBITS4's, and its slice_rows word may be 0 = no slices (head then has no "slice_rows").  The hyper-latent
+is not one range-coder stream for the batch but "rANS-64 x G" sub-streams per image, so where the other formats have
+the z stream LICBITS5 has a z SECTION, and the header's "z-stream length" is the section's length:
+  z block table: B*G rows (sub-stream length, escapes), image-major | for every z block: its stream, then its escape list
+Its reader refuses what LICBITS3's does, for the z blocks too -- a z sub-stream shorter than its 64 states or of odd
+length -- and a z section whose table and blocks do not add up to its length.
 """
 from __future__ import annotations
 
@@ -52,6 +61,7 @@ def _groups(G) -> int:
 BITSTREAM_FAMILIES = {"JointAutoregressiveHierarchical": 1, "HierarchicalMixtureResidual": 2}
 BITSTREAM_MAGIC, BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_GROUPED = b"LICBITS1", b"LICBITS2", b"LICBITS3"
 BITSTREAM_MAGIC_SLICED = b"LICBITS4"
+BITSTREAM_MAGIC_ZRANS = b"LICBITS5"
 _BITS_FIELDS = ("family", "M", "K", "z_lo", "z_S", "y_W", "B", "H", "W", "top", "left")
 _BITS_HEAD, _BITS_HEAD_RANS = struct.Struct("<8s3Ii8I"), struct.Struct("<8s3Ii9I")          # without / with `lanes`
 _BITS_HEAD_SLICED = struct.Struct("<8s3Ii10I")                                                # `lanes`, `slice_rows`
@@ -67,17 +77,34 @@ _FORMATS = {
                          "one sub-stream and one escape list per image and group, one checksum per image"),
 }
 _FORMAT_OF_MAGIC = {f[0]: key for key, f in _FORMATS.items()}
+# the four above carry z as ONE range-coder stream; LICBITS5 carries a z section and is kept beside them
+_FORMAT_ZRANS = ("rans", "zrans")
+_FORMAT_ZRANS_ROW = (BITSTREAM_MAGIC_ZRANS, _BITS_HEAD_SLICED, ("crc",), ("len", "esc"),
+                     "one y and one z sub-stream and escape list per image and group, one checksum per image")
+
+
+def _format_of_magic(magic: bytes):
+    """the key `_pack` / `_unpack` take for a blob that starts with `magic`; an unknown magic: LICBITS1's reader says so"""
+    return _FORMAT_ZRANS if bytes(magic) == BITSTREAM_MAGIC_ZRANS else _FORMAT_OF_MAGIC.get(bytes(magic), ("range", False))
+
+
+def _format(fmt):
+    return _FORMAT_ZRANS_ROW if fmt == _FORMAT_ZRANS else _FORMATS[fmt]
 
 
 def _pack(fmt, head: Dict, z_bytes: bytes, ys, escs, crcs, G: int = 1, lanes: int = None) -> bytes:
     """`head`: the _BITS_FIELDS; B * G y streams and escape lists (bytes; None where the format has none), image-major,
     and one symbol checksum per image.  The sliced format takes head["slice_rows"] as well."""
-    magic, st, img_cols, blk_cols, expects = _FORMATS[fmt]
+    magic, st, img_cols, blk_cols, expects = _format(fmt)
+    zrans = fmt == _FORMAT_ZRANS
     R = head.get("slice_rows", 0) if st is _BITS_HEAD_SLICED else 0
+    R = 0 if zrans and R is None else R
     if st is _BITS_HEAD_SLICED and (isinstance(R, bool) or not isinstance(R, (int, np.integer))
-                                    or not 1 <= int(R) <= 0xFFFFFFFF):
+                                    or not (0 if zrans else 1) <= int(R) <= 0xFFFFFFFF):
         raise CodecError(f"slice_rows = {R!r}: a sliced bitstream needs a whole number of rows per slice, at least 1")
     B = int(head["B"])
+    if zrans:
+        z_bytes = _pack_z_section(z_bytes, B * G, expects)
     escs = [b""] * len(ys) if escs is None else escs
     if len(ys) != B * G or len(escs) != B * G or len(crcs) != B:
         raise CodecError(expects + " expected")
@@ -94,12 +121,43 @@ def _pack(fmt, head: Dict, z_bytes: bytes, ys, escs, crcs, G: int = 1, lanes: in
     return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
 
 
+def _pack_z_section(z, nblocks: int, expects: str) -> bytes:
+    """z = ([sub-stream per image and group], [escape list likewise]) -> LICBITS5's z section"""
+    try:
+        zs, zes = z
+        zs, zes = [bytes(s) for s in zs], [bytes(e) for e in zes]
+    except (TypeError, ValueError):
+        raise CodecError(expects + " expected") from None
+    if len(zs) != nblocks or len(zes) != nblocks:
+        raise CodecError(expects + " expected")
+    if any(len(e) % 4 for e in zes):
+        raise CodecError("an escape list is not a whole number of uint32")
+    return b"".join([struct.pack("<2I", len(s), len(e) // 4) for s, e in zip(zs, zes)]
+                    + [p for s, e in zip(zs, zes) for p in (s, e)])
+
+
+def _unpack_z_section(sec: bytes, nblocks: int):
+    """the inverse -> ([sub-stream], [escape list]); CodecError for a section that does not add up or a sub-stream
+    shorter than its 64 states or of odd length"""
+    if len(sec) < 8 * nblocks:
+        raise CodecError("bitstream is truncated (z block table)")
+    rows = [struct.unpack_from("<2I", sec, 8 * i) for i in range(nblocks)]
+    cuts = list(accumulate([n for ln, ne in rows for n in (ln, 4 * ne)], initial=8 * nblocks))
+    if cuts[-1] != len(sec):
+        raise CodecError("bitstream z section does not add up (its block table and its length disagree)")
+    if any(ln < 4 * RANS_LANES or ln % 2 for ln, _ in rows):
+        raise CodecError("bitstream names a z sub-stream shorter than its 64 states or of odd length")
+    payload = [sec[a:b] for a, b in zip(cuts, cuts[1:])]
+    return payload[0::2], payload[1::2]
+
+
 def _unpack(fmt, data: bytes):
-    """-> (head dict, z_bytes, [y stream per block], [escape list per block], [symbol checksum per image], G).
+    """-> (head dict, z_bytes, [y stream per block], [escape list per block], [symbol checksum per image], G); for
+    LICBITS5 z_bytes is the pair ([z sub-stream per block], [z escape list per block]).
     CodecError, in this order, for a buffer shorter than its header or tables, another magic, a total length that is
     not the one the header and tables name, a failing CRC-32, a header that cannot be right, and what the format itself
     refuses (module docstring) -- except that LICBITS3 must know G to find its tables, so its `lanes` rule comes first."""
-    magic, st, img_cols, blk_cols, _ = _FORMATS[fmt]
+    magic, st, img_cols, blk_cols, _ = _format(fmt)
     data = bytes(data)
     if len(data) < st.size + 4:
         raise CodecError("bitstream is truncated (shorter than its header)")
@@ -131,12 +189,15 @@ def _unpack(fmt, data: bytes):
         raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements {RANS_LANES}")
     if fmt[1] and any(r["len"] < 4 * RANS_LANES or r["len"] % 2 for r in blocks):
         raise CodecError("bitstream names a sub-stream shorter than its 64 states or of odd length")
+    zrans = fmt == _FORMAT_ZRANS
     if st is _BITS_HEAD_SLICED:
-        if vals[14] < 1:
+        if vals[14] < 1 and not zrans:
             raise CodecError("bitstream header is damaged (slice_rows = 0)")
-        head["slice_rows"] = vals[14]
+        if vals[14] >= 1:
+            head["slice_rows"] = vals[14]
     payload = [data[a:b] for a, b in zip(cuts, cuts[1:])]
-    return head, payload[0], payload[1::2], payload[2::2], [r["crc"] for r in (rows if img_cols else blocks)], G
+    z = _unpack_z_section(payload[0], B * G) if zrans else payload[0]
+    return head, z, payload[1::2], payload[2::2], [r["crc"] for r in (rows if img_cols else blocks)], G
 
 
 def _check_crc_and_head(data: bytes, head: Dict):
@@ -187,3 +248,17 @@ def unpack_bitstream_sliced(data: bytes):
     """-> `unpack_bitstream_grouped`'s six, then slice_rows (head["slice_rows"] too)"""
     out = _unpack(("rans", "sliced"), data)
     return out + (out[0]["slice_rows"],)
+
+
+def pack_bitstream_zrans(head: Dict, z_streams, z_esc, y_streams, y_esc, y_crc32, groups: int,
+                         slice_rows: int = None) -> bytes:
+    """LICBITS5: z as B * groups rANS sub-streams and escape lists, image-major; slice_rows None or 0: no slices"""
+    return _pack(_FORMAT_ZRANS, dict(head, slice_rows=slice_rows or 0), (z_streams, z_esc), y_streams, y_esc,
+                 y_crc32, _groups(groups))
+
+
+def unpack_bitstream_zrans(data: bytes):
+    """-> (head dict, [z sub-stream per image and group], [z escape list likewise], [y sub-stream likewise],
+    [y escape list likewise], [symbol checksum per image], groups, slice_rows or None)"""
+    head, (zs, zes), ys, escs, crcs, G = _unpack(_FORMAT_ZRANS, data)
+    return head, zs, zes, ys, escs, crcs, G, head.get("slice_rows")

@@ -13,12 +13,13 @@ prior, so it decodes without context) and `decode_y_with_tables` (decodes y from
 used -- the coder's inverse).  `ContextCodec`: the full round trip; its decoder rebuilds the tables from
 already-decoded pixels through the masked 5x5 context model, wavefront by wavefront.
 `ContextCodec.compress_image` / `decompress_image` wrap that round trip, for images of any size, in one
-self-describing byte string: header, per-image lengths and checksums, streams, CRC-32.  bitstream.py holds the four
-containers (LICBITS1/2/3/4, one per coder and grouping), their one writer and one reader; its names are this module's too.
+self-describing byte string: header, per-image lengths and checksums, streams, CRC-32.  bitstream.py holds the five
+containers (LICBITS1/2/3/4, one per coder and grouping, and LICBITS5 for rANS-coded z), their one writer and one reader;
+its names are this module's too.
 
 `ContextCodec(..., coder="rans")` codes the y streams with the 64-lane interleaved rANS coder of lic_codec.h
 instead: its decoder is a device kernel (`lic_rans_decode_step`), so the decode loop has no host in it.  The range
-coder stays the default and codes z.
+coder stays the default and codes z, unless `z_coder="rans"` (below).
 With `encoder="device"` that coder's encoder runs on the device as well (`lic_rans_encode_pick` + `lic_rans_encode`):
 the same bytes, and no table is copied to the host.
 
@@ -35,6 +36,13 @@ per-pixel layers read with one gather, `lic_ctx_gather`, which applies that rule
 `ContextCodec.decompress_images(blobs)` decodes many `compress_image` blobs of different sizes together: step t of
 every image shares one gather (`lic_ctx_gather_ragged`), one pass through the per-pixel layers and one decode launch
 (`lic_rans_decode_step_ragged`), by the schedule of `merged_wavefront`; entry i is bit for bit `decompress_image(blobs[i])`.
+
+`ContextCodec(..., coder="rans", z_coder="rans")` codes the hyper-latent z on the device as well: every image's z is one
+step of all its symbols dealt to the same G sub-streams ("rANS-64 x G"), symbol k using row k % M of the factorised
+tables, which `lic_rans_z_decode` keeps in LDS for the whole stream.  `lic_rans_z_pick` + `lic_rans_encode_ragged` encode
+(`encoder="host"`: `rans_encode_shared`, the same bytes); `decompress_many` decodes every item's z in one launch ahead
+of its step loop and checks the z state blocks in the read-back it already has.  The container is LICBITS5; y streams,
+checksums, z_hat, y_hat and x_hat are those of `z_coder="range"`, only the z bytes differ.
 
 `ContextCodec.compress_images(images)` is its counterpart: images of different sizes share one gather, one pass through
 the per-pixel layers, one table launch and one launch of each encoder kernel (`lic_rans_encode_pick_ragged`,
@@ -54,11 +62,13 @@ import torch
 from . import _lib as L
 from . import functional as F_
 from .bitstream import (BITSTREAM_FAMILIES, BITSTREAM_MAGIC, BITSTREAM_MAGIC_GROUPED,  # noqa: F401
-                        BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_SLICED, RANS_LANES, RANS_MAX_GROUPS, CodecError,
-                        _BITS_FIELDS, _BITS_HEAD, _BITS_HEAD_RANS, _FORMAT_OF_MAGIC, _FORMATS, _check_crc_and_head,
+                        BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_SLICED, BITSTREAM_MAGIC_ZRANS, RANS_LANES, RANS_MAX_GROUPS,
+                        CodecError,
+                        _BITS_FIELDS, _BITS_HEAD, _BITS_HEAD_RANS, _FORMAT_OF_MAGIC, _FORMAT_ZRANS, _FORMATS,
+                        _check_crc_and_head, _format_of_magic,
                         _groups, _pack, _unpack, pack_bitstream, pack_bitstream_grouped, pack_bitstream_rans,
-                        pack_bitstream_sliced, unpack_bitstream, unpack_bitstream_grouped, unpack_bitstream_rans,
-                        unpack_bitstream_sliced)
+                        pack_bitstream_sliced, pack_bitstream_zrans, unpack_bitstream, unpack_bitstream_grouped,
+                        unpack_bitstream_rans, unpack_bitstream_sliced, unpack_bitstream_zrans)
 
 _CODEC = None
 
@@ -93,6 +103,12 @@ def _codec():
                                         i32p]
         lib.lic_rans_ideal_bits.restype = C.c_double
         lib.lic_rans_ideal_bits.argtypes = [u32p, i32p, C.c_int32, i32p, C.c_int64]
+        lib.lic_rans_encode_shared.restype = C.c_int
+        lib.lic_rans_encode_shared.argtypes = [u32p, i32p, C.c_int32, C.c_int32, i32p, C.c_int64, i64p, C.c_int64, u8p,
+                                               C.c_size_t, szp, u32p, C.c_size_t, szp]
+        lib.lic_rans_decode_shared.restype = C.c_int
+        lib.lic_rans_decode_shared.argtypes = [u8p, C.c_size_t, u32p, C.c_size_t, u32p, i32p, C.c_int32, C.c_int32,
+                                               C.c_int64, i64p, C.c_int64, i32p]
         _CODEC = lib
     return _CODEC
 
@@ -142,6 +158,7 @@ def rc_ideal_bits(tables: np.ndarray, idx: np.ndarray, table_of: np.ndarray = No
 # ---- the interleaved rANS coder of the y streams (lic_codec.h "rANS-64") ---------------------
 CODERS = ("range", "rans")
 ENCODERS = ("host", "device")
+Z_CODERS = ("range", "rans")                     # who codes the hyper-latent z: the host range coder, or rANS-64 x G kernels
 RANS_MAX_W = 64                                  # widest window lic_rans_decode_step / lic_rans_encode_pick take
 
 
@@ -178,6 +195,50 @@ def rans_decode(data: bytes, esc: bytes, tables: np.ndarray, step_len) -> np.nda
                                   S, n, _p(steps, C.c_int64), steps.size, _p(out, C.c_int32))
     if rc != 0:
         raise CodecError(f"lic_rans_decode failed with status {rc}")
+    return out
+
+
+def rans_encode_shared(tables: np.ndarray, idx: np.ndarray, step_len, table_of: np.ndarray = None) -> tuple:
+    """`rans_encode` for symbols that share tables, `rc_encode`'s convention: tables [T][S+1] uint32, table_of [n] int32
+    (None: table n, which is `rans_encode`) -> (stream bytes, escape list bytes)"""
+    tables = np.ascontiguousarray(tables, np.uint32)
+    idx = np.ascontiguousarray(idx, np.int32).ravel()
+    steps = np.ascontiguousarray(step_len, np.int64).ravel()
+    tof = None if table_of is None else np.ascontiguousarray(table_of, np.int32).ravel()
+    if tof is not None and tof.size != idx.size:
+        raise CodecError("one table_of entry per symbol expected")
+    T, S = tables.shape[0], tables.shape[-1] - 1
+    lib = _codec()
+    cap = lib.lic_rans_bound(idx.size)
+    out, esc = np.empty(cap, np.uint8), np.empty(max(idx.size, 1), np.dtype("<u4"))
+    nb, ne = C.c_size_t(0), C.c_size_t(0)
+    rc = lib.lic_rans_encode_shared(_p(tables, C.c_uint32), _p(tof, C.c_int32), T, S, _p(idx, C.c_int32), idx.size,
+                                    _p(steps, C.c_int64), steps.size, _p(out, C.c_uint8), cap, C.byref(nb),
+                                    _p(esc, C.c_uint32), idx.size, C.byref(ne))
+    if rc != 0:
+        raise CodecError(f"lic_rans_encode_shared failed with status {rc}")
+    return out[:nb.value].tobytes(), esc[:ne.value].tobytes()
+
+
+def rans_decode_shared(data: bytes, esc: bytes, tables: np.ndarray, step_len, table_of: np.ndarray = None) -> np.ndarray:
+    """the inverse of `rans_encode_shared` for known tables"""
+    tables = np.ascontiguousarray(tables, np.uint32)
+    steps = np.ascontiguousarray(step_len, np.int64).ravel()
+    n = int(steps.sum())
+    tof = None if table_of is None else np.ascontiguousarray(table_of, np.int32).ravel()
+    if tof is not None and tof.size != n:
+        raise CodecError("one table_of entry per symbol expected")
+    T, S = tables.shape[0], tables.shape[-1] - 1
+    if len(esc) % 4:
+        raise CodecError("escape list is not a whole number of uint32")
+    buf = np.frombuffer(data, np.uint8)
+    ebuf = np.frombuffer(esc, np.dtype("<u4")).astype(np.uint32)
+    out = np.empty(n, np.int32)
+    rc = _codec().lic_rans_decode_shared(_p(buf, C.c_uint8), buf.size, _p(ebuf, C.c_uint32), ebuf.size,
+                                         _p(tables, C.c_uint32), _p(tof, C.c_int32), T, S, n, _p(steps, C.c_int64),
+                                         steps.size, _p(out, C.c_int32))
+    if rc != 0:
+        raise CodecError(f"lic_rans_decode_shared failed with status {rc}")
     return out
 
 
@@ -280,6 +341,13 @@ def wavefront(h: int, w: int, pad: int, slice_rows: int = None):
         if keep.any():
             steps.append((rows[keep], jj[keep]))
     return steps
+
+
+def _z_size(strings) -> int:
+    """bytes of the coded hyper-latent in `compress`'s strings: one stream, or sub-streams and escape lists"""
+    if strings.get("z_coder", "range") == "rans":
+        return sum(len(s) for s in strings["z"]) + sum(len(e) for e in strings["z_esc"])
+    return len(strings["z"])
 
 
 def _image_name(img: int) -> str:
@@ -404,6 +472,25 @@ def ragged_encode_plan(shapes, M: int, pad: int, slice_rows, G: int) -> RaggedEn
                             row0, word_off, esc_off)
 
 
+def z_encode_plan(pixels, M: int, G: int):
+    """`lic_rans_encode_ragged`'s layout for the hyper-latents of several images (z_coder="rans"): image b is pixels[b]
+    rows of M symbols in raster order and ONE step of pixels[b] * M symbols; slots and escape lists are the smallest
+    that cannot run out (`rans_group_sizes`), one behind the other.
+    -> (images [nimg][4], blocks [nimg * G][4], step_len [nimg], total_rows, words_len, esc_len), as RaggedEncodePlan"""
+    G = _groups(G)
+    nimg = len(pixels)
+    images, blocks = np.zeros((nimg, L.RANS_IMAGE_WORDS), np.int64), np.zeros((nimg * G, L.RANS_BLOCK_WORDS), np.int64)
+    row0 = word_off = esc_off = 0
+    for b, P in enumerate(pixels):
+        fullest = max(int(rans_group_sizes([int(P) * M], G).max()), 1)
+        images[b] = (row0, int(P), b, 1)
+        for g in range(G):
+            blocks[b * G + g] = (word_off, (2 * fullest + 3) // 4 * 4, esc_off, fullest)
+            word_off, esc_off = word_off + (2 * fullest + 3) // 4 * 4, esc_off + fullest
+        row0 += int(P)
+    return images, blocks, np.array([int(P) * M for P in pixels], np.int64), row0, word_off, esc_off
+
+
 def table_chunks(costs, budget: int):
     """Consecutive runs [(first, end)] of whole items whose costs (table bytes) add up to `budget` at the most; an
     item that is larger than the budget runs alone."""
@@ -452,6 +539,12 @@ class _RansStaging:
         self.dev = tuple(torch.from_numpy(a).to(dev) for a in self.host)
         return tuple(F_._ptr(t) for t in self.dev)
 
+    def blocks_from(self, first: int):
+        """the same six arguments for the blocks from `first` on (after `upload`): the offsets stay absolute, so only
+        the per-block arrays move"""
+        s, s_off, s_len, e, e_off, state = self.dev
+        return tuple(F_._ptr(t) for t in (s, s_off[first:], s_len[first:], e, e_off[first:], state[first:]))
+
     def check(self):
         ys, escs, head = self.ys, self.escs, 4 * RANS_LANES
 
@@ -463,6 +556,28 @@ class _RansStaging:
                 return ("the rANS stream was not used up exactly (trailing words or escapes, or final states that are "
                         "not the encoder's start): the stream is damaged")
         _state_blocks(self.dev[5], self.G, problem, self.name)                            # the one read-back
+
+
+def _z_coder_of(strings) -> str:
+    """who coded the hyper-latent of these strings: "range" if they do not say; CodecError for what cannot be"""
+    z_coder = strings.get("z_coder", "range")
+    if z_coder not in Z_CODERS:
+        raise CodecError(f"unknown z_coder {z_coder!r} in the strings")
+    if z_coder == "rans" and strings.get("coder", "range") != "rans":
+        raise CodecError("the strings name z_coder 'rans' without coder 'rans': only 'rans' streams carry rANS z streams")
+    return z_coder
+
+
+def _stage_y_and_z(ys, escs, nimg: int, zs, zescs, nz: int, G: int, name=_image_name, zname=None) -> _RansStaging:
+    """One staging for the nimg * G y blocks and, behind them, the nz * G z blocks of the images whose hyper-latent is
+    rANS-coded: one upload, one read-back.  `name(image)` / `zname(z image)` label them in the messages."""
+    if escs is None or len(ys) != nimg * G or len(escs) != nimg * G:
+        raise CodecError("one y stream and one escape list per image and group expected")
+    if zescs is None or isinstance(zs, (bytes, bytearray)) or len(zs) != nz * G or len(zescs) != nz * G:
+        raise CodecError("one z stream and one escape list per image and group expected")
+    zname = name if zname is None else zname
+    return _RansStaging(list(ys) + list(zs), list(escs) + list(zescs), nimg + nz, G,
+                        lambda img: name(img) if img < nimg else zname(img - nimg) + " (hyper-latent)")
 
 
 class LatentCodec:
@@ -577,7 +692,8 @@ class ContextCodec:
     `coder`: "range" (the default) codes y with the host range coder as described above; "rans" codes y with
     the 64-lane interleaved rANS coder of lic_codec.h, whose decoder is a device kernel
     (`lic_rans_decode_step`): the step loop is then {gather -> per-pixel layers -> tables -> decode}, all
-    asynchronous launches, and the host reads back one small block after the last step.  z keeps the range coder.
+    asynchronous launches, and the host reads back one small block after the last step.  z keeps the range coder
+    unless `z_coder` says otherwise.
     Its kernels take `y_W` from 1 to 64 (RANS_MAX_W); the constructor refuses a wider window for this coder.
 
     `encoder`: where `compress` codes the y streams.  "host" (the default) gathers the tables into wavefront order,
@@ -595,10 +711,23 @@ class ContextCodec:
     (`wavefront`): fewer, wider steps, for the rate the first rows of every slice lose with their context.  The model
     is not told: encoder and decoder evaluate the same layers on the same masked windows, so their tables agree and
     y_hat, x_hat are what the codec without slices reconstructs; only the bytes differ.  R >= h is that codec, byte
-    for byte.  `strings["slice_rows"]` is R when slicing is on; `decompress` reads it from the strings."""
+    for byte.  `strings["slice_rows"]` is R when slicing is on; `decompress` reads it from the strings.
+
+    `z_coder`: "range" (the default: one host range-coder stream for the batch's z) or "rans" (coder "rans" only): every
+    image's z as `groups` rANS-64 sub-streams of its own, coded by kernels (`_encode_z`, `_decode_z`) for any window
+    z_S >= 2.  Then `strings["z_coder"]` is "rans" and `strings["z"]`, `strings["z_esc"]` are lists of B * G byte
+    strings, image-major; the decoders read `z_coder` from the strings.  Nothing else changes: y streams, `y_crc32`
+    and the decoded z_hat, y_hat, x_hat are bit for bit those of "range"."""
 
     def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range",
-                 encoder: str = "host", groups: int = 1, slice_rows: int = None):
+                 encoder: str = "host", groups: int = 1, slice_rows: int = None, z_coder: str = "range"):
+        if z_coder not in Z_CODERS:
+            raise CodecError(f"unknown z_coder {z_coder!r}: expected one of {Z_CODERS}")
+        if z_coder == "rans" and coder != "rans":
+            raise CodecError(f"z_coder='rans' needs coder='rans': the {coder!r} coder has no container for rANS z streams")
+        if z_coder == "rans" and int(z_S) < 2:
+            raise CodecError(f"z_S = {int(z_S)}: z_coder='rans' needs a window of at least 2 symbols")
+        self.z_coder = z_coder
         if coder not in CODERS:
             raise CodecError(f"unknown coder {coder!r}: expected one of {CODERS}")
         if encoder not in ENCODERS:
@@ -740,7 +869,10 @@ class ContextCodec:
         out = m.analysis_hyperprior(x, training=False)
         y_in, z_in = out["y_in"].contiguous(), out["z_in"]
         B, M, h, w = y_in.shape
-        z_bytes = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in)
+        if self.z_coder == "rans":
+            z_bytes, z_esc = self._encode_z(list(self._z_symbols(z_in)))
+        else:
+            z_bytes = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in)
         psi = m.hyper_decoder(z_in).float()
         win, comb = self._windows_all(out["y_in"], self.slice_rows, psi)
         center, tables = self._params_at(win, None, self._prepack(), comb)
@@ -750,6 +882,8 @@ class ContextCodec:
         order = np.concatenate([ii * w + jj for ii, jj in steps])
         step_len = [len(ii) * M for ii, _ in steps]
         strings = {"z": z_bytes}
+        if self.z_coder == "rans":
+            strings.update(z_coder="rans", z_esc=z_esc)
         if self.groups > 1:
             strings["groups"] = self.groups
         if self.slice_rows is not None:
@@ -771,10 +905,9 @@ class ContextCodec:
 
     def _compressed(self, x, out, strings, y_streams, y_esc, y_sym, y_in, z_in) -> Dict:
         """what `compress` returns, from the coded streams: sizes, the estimate and the symbol checksums"""
-        z_bytes = strings["z"]
         B, M, h, w = y_in.shape
         npix = x.shape[0] * x.shape[2] * x.shape[3]
-        coded = 8.0 * (len(z_bytes) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
+        coded = 8.0 * (_z_size(strings) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
         est = float(-(out["logp_y"].double().sum() + out["logp_z"].double().sum()) / np.log(2.0) / npix)
         # CRC-32 of every image's latent symbols: a decoder whose tables differ from the encoder's by one count
         # decodes garbage silently; with the checksum it fails loudly instead
@@ -784,6 +917,85 @@ class ContextCodec:
         return {"strings": strings, "shape": (B, M, h, w),
                 "z_shape": tuple(z_in.shape),
                 "bpp_coded": coded, "bpp_est": est, "y_in": y_in, "z_in": z_in}
+
+    @staticmethod
+    def _z_symbols(z_in: torch.Tensor):
+        """z_in [B,M,h4,w4] -> [B][h4*w4*M] int32 on its device: every image's rounded hyper-latents, pixel by pixel,
+        channel by channel (`LatentCodec._z_symbols`' order)"""
+        return z_in.permute(0, 2, 3, 1).contiguous().round().to(torch.int32).reshape(z_in.shape[0], -1)
+
+    def _encode_z(self, z_syms, name=_image_name):
+        """The hyper-latents as "rANS-64 x G" streams (z_coder="rans").  z_syms: one flat int32 tensor per image
+        (`_z_symbols`), of any sizes.  An image is ONE step of all its symbols dealt to G sub-streams
+        (`rans_deal([n], G)`); symbol k uses row k % M of the factorised tables.
+        -> ([stream bytes per image and group, image-major], [escape-list bytes likewise]), the same bytes from
+        `encoder="host"` (`rans_encode_shared`) and from "device" (`lic_rans_z_pick` + `lic_rans_encode_ragged`)."""
+        M, G = self.model.M, self.groups
+        tables = factorized_tables(self.model.factorized_entropy_model, self.z_lo, self.z_S)
+        if self.encoder != "device":
+            zt = tables.cpu().numpy().view(np.uint32)
+            streams, escs = [], []
+            for z in z_syms:
+                idx = (z.reshape(-1) - self.z_lo).cpu().numpy()
+                for pos, steps_g in rans_deal([idx.size], G):
+                    s, e = rans_encode_shared(zt, idx[pos], steps_g, (pos % M).astype(np.int32))
+                    streams.append(s)
+                    escs.append(e)
+            return streams, escs
+        dev = tables.device
+        nimg = len(z_syms)
+        images, blocks, step_len, rows, words_len, esc_len = z_encode_plan([z.numel() // M for z in z_syms], M, G)
+        z_all = torch.cat([z.reshape(-1) for z in z_syms]) if nimg > 1 else z_syms[0].reshape(-1).contiguous()
+        n = z_all.numel()
+        parts = [images.ravel(), blocks.ravel(), step_len]
+        d_images, d_blocks, d_steps = torch.split(torch.from_numpy(np.concatenate(parts)).to(dev), [a.size for a in parts])
+        sf = torch.empty(n, device=dev, dtype=torch.int32)
+        exc = torch.empty_like(sf)
+        words = torch.empty(words_len, device=dev, dtype=torch.uint8)
+        esc = torch.empty(esc_len, device=dev, dtype=torch.int32)
+        # the encoder's nimg * G blocks, then one row whose first word is pick's call-level error word
+        state = torch.zeros((nimg * G + 1, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
+        lib = L.load()
+        L.check(lib.lic_rans_z_pick(F_._ptr(tables), M, self.z_lo, self.z_S, F_._ptr(z_all), n, F_._ptr(sf), F_._ptr(exc),
+                                    F_._ptr(state[nimg * G:]), F_._stream()), "lic_rans_z_pick")
+        L.check(lib.lic_rans_encode_ragged(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), nimg, F_._ptr(d_images),
+                                           F_._ptr(d_blocks), nimg, G, rows, M, F_._ptr(words), words_len, F_._ptr(esc),
+                                           esc_len, F_._ptr(state), F_._stream()), "lic_rans_encode_ragged")
+        h_state = state.cpu()                                                     # the read-back that waits
+        picked = int(h_state[nimg * G, 0])
+        found = _state_blocks(h_state[:nimg * G], G, lambda i, states, nw, ne, err: (err or picked) and (
+            f"the rANS encoder of z met a malformed table or step lengths that do not add up (error word {err | picked})"),
+            name)
+        h_words, h_esc = words.cpu().numpy(), esc.cpu().numpy().view(np.uint32)
+        streams, escs = [], []
+        for i, (states, nw, ne) in enumerate(found):
+            if 2 * nw > blocks[i, 1] or ne > blocks[i, 3]:
+                raise CodecError(f"{name(i // G)}: the rANS encoder of z reports impossible counts ({nw} words, "
+                                 f"{ne} escapes)")
+            end = int(blocks[i, 0] + blocks[i, 1])
+            streams.append(states.astype("<u4").tobytes() + h_words[end - 2 * nw:end].tobytes())
+            escs.append(h_esc[blocks[i, 2]:blocks[i, 2] + ne].astype("<u4").tobytes())
+        return streams, escs
+
+    def _decode_z(self, staged, first: int, windows, nsyms, bases, z_len: int, dev) -> torch.Tensor:
+        """The hyper-latents of `len(nsyms)` images from their staged "rANS-64 x G" blocks (blocks `first` on of
+        `staged`, after `upload`), every image in ONE `lic_rans_z_decode` launch per z window (one launch when all share
+        it: an image of another window has 0 symbols in that launch and its blocks stay as they are).  windows:
+        (z_lo, z_S) per image; nsyms: its symbols; bases: where its plane starts in the flat fp32 buffer of z_len
+        floats that is returned.  Nothing waits: the blocks are checked with the y blocks, by `staged.check()`."""
+        M, G, nz, lib = self.model.M, staged.G, len(nsyms), L.load()
+        zflat = torch.zeros(z_len, device=dev, dtype=torch.float32)
+        kinds = list(dict.fromkeys(windows))
+        desc = np.array([[n if win == kind else 0 for n, win in zip(nsyms, windows)] for kind in kinds] + [list(bases)],
+                        np.int64)
+        d_desc = torch.from_numpy(desc).to(dev)
+        blocks = staged.blocks_from(first)
+        for i, (z_lo, z_S) in enumerate(kinds):
+            tables = factorized_tables(self.model.factorized_entropy_model, z_lo, z_S)
+            L.check(lib.lic_rans_z_decode(*blocks, F_._ptr(tables), M, int(z_lo), int(z_S), nz, G, F_._ptr(d_desc[i]),
+                                          F_._ptr(d_desc[len(kinds)]), F_._ptr(zflat), z_len, L.RANS_Z_AUTO, F_._stream()),
+                    "lic_rans_z_decode")
+        return zflat
 
     def _encode_y_device(self, tables, center, y_sym, order, step_len, B: int, P: int, M: int):
         """The y streams of the "rans" coder without the host encoder: `lic_rans_encode_pick` turns tables (raster
@@ -882,14 +1094,26 @@ class ContextCodec:
             outs.append((out["y_in"].contiguous(), out["z_in"], out["y_in"]))
             psis.append(m.hyper_decoder(out["z_in"]).float())
             sums.append(out["logp_y"].double().sum() + out["logp_z"].double().sum())
-        # z: the symbols of all items in one read-back, one host range coder run per item as `compress` has it
-        z_sym = [(z.permute(0, 2, 3, 1).contiguous().round().to(torch.int32) - self.z_lo).reshape(-1) for _, z, _ in outs]
-        z_all = torch.cat(z_sym).cpu().numpy()
-        z_bytes, at = [], 0
-        for z in z_sym:
-            n = z.numel()
-            z_bytes.append(rc_encode(zt, z_all[at:at + n], np.tile(np.arange(len(zt), dtype=np.int32), n // len(zt))))
-            at += n
+        # z: the symbols of all items in one read-back, one host range coder run per item as `compress` has it -- or,
+        # with z_coder="rans", the kernels on all of them at once
+        z_bytes, z_escs, at = [], [], 0
+        if self.z_coder == "rans":
+            # every image of every item in one pick and one encode launch; the strings are cut per item below
+            owner_z = [(i, b) for i, (_, z, _) in enumerate(outs) for b in range(z.shape[0])]
+            zs, zes = self._encode_z([row for _, z, _ in outs for row in self._z_symbols(z)],
+                                     lambda im: f"{names[owner_z[im][0]]}: image {owner_z[im][1]}")
+            for _, z, _ in outs:
+                z_bytes.append(zs[at:at + z.shape[0] * G])
+                z_escs.append(zes[at:at + z.shape[0] * G])
+                at += z.shape[0] * G
+        else:
+            z_sym = [(z.permute(0, 2, 3, 1).contiguous().round().to(torch.int32) - self.z_lo).reshape(-1)
+                     for _, z, _ in outs]
+            z_all = torch.cat(z_sym).cpu().numpy()
+            for z in z_sym:
+                n = z.numel()
+                z_bytes.append(rc_encode(zt, z_all[at:at + n], np.tile(np.arange(len(zt), dtype=np.int32), n // len(zt))))
+                at += n
         # the layout: item after item, each on a multiple of 4 floats, its B planes one behind the other
         cpsi = psis[0].shape[1]
         shapes, y_at, psi_at, y_len, psi_len = [], [], [], 0, 0
@@ -965,6 +1189,8 @@ class ContextCodec:
         for i, ((y_in, z_in, _), x) in enumerate(zip(outs, xs)):
             B, _, h, w = y_in.shape
             strings = {"z": z_bytes[i]}
+            if self.z_coder == "rans":
+                strings.update(z_coder="rans", z_esc=z_escs[i])
             if G > 1:
                 strings["groups"] = G
             if R is not None:
@@ -975,7 +1201,7 @@ class ContextCodec:
                      for a in h_sym[row0:row0 + B * h * w].reshape(B, h * w * M)]
             strings.update(coder="rans", y_esc=y_esc, y=y_streams, y_crc32=y_crc)
             npix = x.shape[0] * x.shape[2] * x.shape[3]
-            coded = 8.0 * (len(z_bytes[i]) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
+            coded = 8.0 * (_z_size(strings) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
             res.append({"strings": strings, "shape": (B, M, h, w), "z_shape": tuple(z_in.shape), "bpp_coded": coded,
                         "bpp_est": float(-h_sums[i] / np.log(2.0) / npix), "y_in": y_in, "z_in": z_in})
             img += B
@@ -986,7 +1212,20 @@ class ContextCodec:
         m = self.model
         B, M, h, w = shape
         dev = next(m.parameters()).device
-        z_hat = LatentCodec(m, self.z_lo, self.z_S, self.y_W).decompress_z(strings["z"], z_shape)
+        z_coder, staged = _z_coder_of(strings), None
+        if z_coder == "rans":
+            # y and z blocks are staged together: z decodes in one launch ahead of the step loop and its state blocks
+            # come back with the y blocks', in the one read-back after the last step
+            G = _groups(strings.get("groups", 1))
+            _, _, h4, w4 = z_shape
+            staged = _stage_y_and_z(strings["y"], strings.get("y_esc"), B, strings["z"], strings.get("z_esc"), B, G)
+            staged.upload(dev)
+            n = h4 * w4 * M
+            zflat = self._decode_z(staged, B * G, [(self.z_lo, self.z_S)] * B, [n] * B, [b * n for b in range(B)], B * n,
+                                   dev)
+            z_hat = zflat.view(B, h4, w4, M).permute(0, 3, 1, 2)
+        else:
+            z_hat = LatentCodec(m, self.z_lo, self.z_S, self.y_W).decompress_z(strings["z"], z_shape)
         z_hat = z_hat.contiguous(memory_format=torch.channels_last)
         psi = m.hyper_decoder(z_hat).float()
         p = self.pad
@@ -1002,7 +1241,7 @@ class ContextCodec:
         steps = self._wavefront(h, w, R)
         front = self._step_front_end(steps, yflat, psi, R)
         if coder == "rans":
-            self._decode_y_rans(strings, front, yflat)
+            self._decode_y_rans(strings, front, yflat, staged)
             return self._finish(strings, ypad, z_hat, shape)
         pin = dev.type == "cuda"
         nmax, S1 = max(len(ii) for ii, _ in steps), 2 * self.y_W + 2
@@ -1048,16 +1287,20 @@ class ContextCodec:
                 off += n
         return run()
 
-    def _decode_y_rans(self, strings, front, yflat):
+    def _decode_y_rans(self, strings, front, yflat, staged=None):
         """The step loop of the "rans" coder: streams, escape lists and state blocks go up once, then every step of
         `front` (`_step_front_end`: gather -> per-pixel layers + tables) ends in lic_rans_decode_step_groups, which
         writes the decoded values into `yflat` where the next gather reads them.  Nothing in the loop waits for the
         device; the state blocks (error words, cursors, final states) come back once, after the last step.  One block
-        per image and group (`strings["groups"]`, 1 if absent), image-major; below B counts blocks."""
+        per image and group (`strings["groups"]`, 1 if absent), image-major; below B counts blocks.  `staged`: the
+        staging `decompress` has already uploaded, with the z blocks behind the y blocks (z_coder="rans")."""
         nimg, npad, M = yflat.shape
         G = _groups(strings.get("groups", 1))
-        staged = _RansStaging(strings["y"], strings.get("y_esc"), nimg, G)
-        blocks = staged.upload(yflat.device)
+        if staged is None:
+            staged = _RansStaging(strings["y"], strings.get("y_esc"), nimg, G)
+            blocks = staged.upload(yflat.device)
+        else:
+            blocks = staged.blocks_from(0)
         lib = L.load()
         for n, own, center, tables in front:
             L.check(lib.lic_rans_decode_step_groups(*blocks, F_._ptr(tables), F_._ptr(center), nimg, G, n, M, self.y_W,
@@ -1087,7 +1330,9 @@ class ContextCodec:
         z_windows: [(z_lo, z_S)] per item (default: this codec's); names: what to call an item in a message (default
         "item i").  -> one `decompress` result per item, bit for bit what `decompress` gives for it alone.
 
-        Per item the hyper-latent is decoded and the hyper-decoder run exactly as `decompress` does.  All psi planes
+        Per item the hyper-latent is decoded and the hyper-decoder run exactly as `decompress` does; the items whose z
+        is rANS-coded (`strings["z_coder"]`) have it decoded together, in one `lic_rans_z_decode` launch into one flat
+        buffer the hyper-decoders read views of (`_decode_z`), their z blocks staged behind the y blocks.  All psi planes
         and all zero-framed latent planes lie in two flat buffers, every item's on a multiple of 4 floats; streams,
         escape lists and state blocks of all images are staged once.  Then ONE loop of T steps (`merged_wavefront`),
         each {lic_ctx_gather_ragged -> per-pixel layers and tables over the step's rows of every image ->
@@ -1125,14 +1370,49 @@ class ContextCodec:
             ys += list(strings["y"])
             escs += list(strings["y_esc"])
         nimg = len(shapes)
-        staged = _RansStaging(ys, escs, nimg, G, lambda img: f"{names[owner[img][0]]}: image {owner[img][1]}")
+        # the items whose hyper-latent is rANS-coded: their z blocks ride behind the y blocks in the one staging
+        zs, zescs, zowner, zwin, znsym, zbase, zitem, z_len = [], [], [], [], [], [], {}, 0
+        for i, ((strings, shape, z_shape), win) in enumerate(zip(items, z_windows)):
+            try:
+                if _z_coder_of(strings) != "rans":
+                    continue
+                B, _, h4, w4 = z_shape
+                if B != shape[0]:
+                    raise CodecError("z_shape and shape name different batch sizes")
+                if strings.get("z_esc") is None or isinstance(strings["z"], (bytes, bytearray)) or \
+                        len(strings["z"]) != B * G or len(strings["z_esc"]) != B * G:
+                    raise CodecError("one z stream and one escape list per image and group expected")
+            except CodecError as err:
+                raise CodecError(f"{names[i]}: {err}") from None
+            z_len = (z_len + 3) // 4 * 4                                          # every item on a multiple of 4 floats
+            zitem[i] = z_len
+            for b in range(B):
+                zowner.append((i, b))
+                zwin.append((int(win[0]), int(win[1])))
+                znsym.append(h4 * w4 * M)
+                zbase.append(z_len)
+                z_len += h4 * w4 * M
+            zs += list(strings["z"])
+            zescs += list(strings["z_esc"])
+        label = lambda own: (lambda img: f"{names[own[img][0]]}: image {own[img][1]}")
+        if zowner:
+            staged = _stage_y_and_z(ys, escs, nimg, zs, zescs, len(zowner), G, label(owner), label(zowner))
+        else:
+            staged = _RansStaging(ys, escs, nimg, G, label(owner))
         sched = merged_wavefront(shapes, p, Rs)
         # ---- the device from here on
         dev = next(m.parameters()).device
+        blocks = staged.upload(dev)
+        if zowner:
+            zflat = self._decode_z(staged, nimg * G, zwin, znsym, zbase, z_len, dev)      # every such item's z, one launch
         z_hats, psis = [], []
         for i, ((strings, _, z_shape), (z_lo, z_S)) in enumerate(zip(items, z_windows)):
             try:
-                z_hat = LatentCodec(m, z_lo, z_S, self.y_W).decompress_z(strings["z"], z_shape)
+                if i in zitem:
+                    B, _, h4, w4 = z_shape
+                    z_hat = zflat[zitem[i]:zitem[i] + B * h4 * w4 * M].view(B, h4, w4, M).permute(0, 3, 1, 2)
+                else:
+                    z_hat = LatentCodec(m, z_lo, z_S, self.y_W).decompress_z(strings["z"], z_shape)
             except CodecError as err:
                 raise CodecError(f"{names[i]}: {err}") from None
             z_hats.append(z_hat.contiguous(memory_format=torch.channels_last))
@@ -1158,7 +1438,6 @@ class ContextCodec:
         d_desc, d_rows, d_seg = up(desc), up(sched.rows), up(sched.seg)
         d_ybase = up(desc[:, 0])
         d_pixels = up(np.array([(h + 2 * p) * (w + 2 * p) for h, w in shapes], np.int64))
-        blocks = staged.upload(dev)
         layers, lib, off = self._prepack(), L.load(), sched.step_off
         for t in range(sched.T):
             a, e = int(off[t]), int(off[t + 1])
@@ -1195,7 +1474,8 @@ class ContextCodec:
         shapes and to crop back.  bpp_coded of the result is 8 * len(data) / (B * H * W): header and checksums
         included, per ORIGINAL pixel.  `coder`: None = this codec's own; the container is the one `_FORMATS` has for
         (coder, groups > 1): LICBITS1 for "range", LICBITS2 for "rans", LICBITS3 for "rans" with groups -- and LICBITS4
-        for a codec with slices, whatever its groups.  Slices, like groups, do not follow to another coder."""
+        for a codec with slices, whatever its groups, LICBITS5 for one with z_coder="rans", whatever its groups and
+        slices.  Slices, groups and z_coder do not follow to another coder."""
         if x.dim() != 4:
             raise CodecError("expected a [B,3,H,W] tensor")
         if coder is not None and coder != self.coder:
@@ -1212,6 +1492,9 @@ class ContextCodec:
         """the container of `compress_image` around the strings `compress` gave for the padded image"""
         head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
                 "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
+        if self.z_coder == "rans":
+            return _pack(_FORMAT_ZRANS, dict(head, slice_rows=self.slice_rows or 0), (s["z"], s["z_esc"]), s["y"],
+                         s["y_esc"], s["y_crc32"], self.groups)
         if self.slice_rows is not None:
             return _pack((self.coder, "sliced"), dict(head, slice_rows=self.slice_rows), s["z"], s["y"], s["y_esc"],
                          s["y_crc32"], self.groups)
@@ -1227,7 +1510,8 @@ class ContextCodec:
     def compress_images(self, images: Sequence[torch.Tensor], mode: str = "replicate", align: str = "topleft",
                         table_budget_bytes: int = 2 << 30) -> List[bytes]:
         """Many images of any sizes in one encode pass: entry i is byte for byte `compress_image(images[i], mode,
-        align)`, the container of this codec's groups and slice_rows (LICBITS2 / 3 / 4).  All images of a chunk share
+        align)`, the container of this codec's groups, slice_rows and z_coder (LICBITS2 / 3 / 4 / 5).  All images of a
+        chunk share
         one gather, one pass through the per-pixel layers, one table launch and one launch of each encoder kernel
         (`compress_many`, which also says what `table_budget_bytes` does).  Needs coder="rans", encoder="device".
         Raises CodecError before any GPU work, every message naming its entry ("image i: ..."): a codec with another
@@ -1272,9 +1556,14 @@ class ContextCodec:
     def _open_blob(self, data: bytes):
         """`decompress_image`'s host half -> (header, the strings `decompress` takes).  Its refusals, in order: the
         container reader's (`_unpack`), a window the rANS decoder does not take, a model that is not this one."""
-        fmt = _FORMAT_OF_MAGIC.get(bytes(data[:8]), ("range", False))         # an unknown magic: LICBITS1's reader says so
+        fmt = _format_of_magic(data[:8])                                      # an unknown magic: LICBITS1's reader says so
         head, z_bytes, y_streams, y_esc, y_crc, G = _unpack(fmt, data)
         strings = {"y": y_streams, "z": z_bytes, "y_crc32": y_crc}
+        if fmt == _FORMAT_ZRANS:
+            if not 2 <= head["z_S"] <= L.RANS_Z_MAX_S:
+                raise CodecError(f"bitstream names z_S = {head['z_S']}; the rANS decoder of z takes windows of 2 to "
+                                 f"{L.RANS_Z_MAX_S} symbols")
+            strings.update(z_coder="rans", z=z_bytes[0], z_esc=z_bytes[1])
         if fmt[0] == "rans":
             if head["y_W"] > RANS_MAX_W:
                 raise CodecError(f"bitstream names y_W = {head['y_W']}; the rANS decoder takes windows of 1 to "
@@ -1292,7 +1581,7 @@ class ContextCodec:
     def decompress_images(self, blobs: Sequence[bytes]) -> List[torch.Tensor]:
         """Many `compress_image` blobs in one decode loop: entry i is bit for bit `decompress_image(blobs[i])`,
         [B_i, 3, H_i, W_i], channels_last, cropped.  The blobs may differ in size, batch, crop, slice_rows, z window and
-        between LICBITS2 / 3 / 4; step t of all their images shares its launches (`decompress_many`), so a folder of
+        between LICBITS2 / 3 / 4 / 5; step t of all their images shares its launches (`decompress_many`), so a folder of
         blobs costs about one blob's step loop plus every blob's transforms.  Raises CodecError before any GPU work,
         every message naming its blob ("blob i: ..."): whatever `decompress_image` refuses for blob i; a LICBITS1 blob
         (the range coder's loop waits for the host at every step: nothing to merge); a y_W or a G (sub-streams per

@@ -38,18 +38,22 @@ bool steps_ok(const int64_t* step_len, int64_t nsteps, int64_t n) {
   return sum == n;
 }
 
-}  // namespace
-
-LIC_CODEC_EXPORT size_t lic_rans_bound(int64_t n) {
-  // the 64 final states + at most one 16-bit word per symbol
-  return n < 0 ? 0 : (size_t)kLanes * 4 + (size_t)n * 2;
+// every table_of entry must name one of the T tables before anything is indexed with it (NULL: table i, no T)
+bool table_of_ok(const int32_t* table_of, int32_t T, int64_t n) {
+  if (!table_of) return true;
+  if (T < 1) return n == 0;
+  for (int64_t i = 0; i < n; ++i)
+    if (table_of[i] < 0 || table_of[i] >= T) return false;
+  return true;
 }
 
-LIC_CODEC_EXPORT int lic_rans_encode(const uint32_t* tables, int32_t S, const int32_t* idx, int64_t n,
-                                     const int64_t* step_len, int64_t nsteps, uint8_t* out, size_t cap,
-                                     size_t* nbytes, uint32_t* esc_out, size_t esc_cap, size_t* nesc) {
+// The one encoder: symbol i codes with table table_of[i] of `tables` (table_of == NULL: table i).
+int encode(const uint32_t* tables, const int32_t* table_of, int32_t T, int32_t S, const int32_t* idx, int64_t n,
+           const int64_t* step_len, int64_t nsteps, uint8_t* out, size_t cap, size_t* nbytes, uint32_t* esc_out,
+           size_t esc_cap, size_t* nesc) {
   if (!out || !nbytes || !nesc || S < 2 || n < 0 || (n > 0 && (!tables || !idx))) return LIC_CODEC_ERR_INVALID;
   if (!steps_ok(step_len, nsteps, n)) return LIC_CODEC_ERR_INVALID;
+  if (!table_of_ok(table_of, T, n)) return LIC_CODEC_ERR_INVALID;
   if (cap < (size_t)kLanes * 4) return LIC_CODEC_ERR_OVERFLOW;
   // escapes leave in symbol order: a forward pass of their own
   size_t ne = 0;
@@ -69,7 +73,7 @@ LIC_CODEC_EXPORT int lic_rans_encode(const uint32_t* tables, int32_t S, const in
     base -= step_len[t];
     for (int64_t k = step_len[t] - 1; k >= 0; --k) {  // rounds last to first, lanes 63 down to 0
       const int64_t i = base + k;
-      const uint32_t* tb = tables + (size_t)i * (size_t)(S + 1);
+      const uint32_t* tb = tables + (size_t)(table_of ? table_of[i] : i) * (size_t)(S + 1);
       if (!table_ok(tb, S)) return LIC_CODEC_ERR_INVALID;
       const int32_t v = idx[i];
       const int32_t s = v <= 0 ? 0 : (v >= S - 1 ? S - 1 : v);
@@ -93,11 +97,13 @@ LIC_CODEC_EXPORT int lic_rans_encode(const uint32_t* tables, int32_t S, const in
   return LIC_CODEC_OK;
 }
 
-LIC_CODEC_EXPORT int lic_rans_decode(const uint8_t* in, size_t nbytes, const uint32_t* esc, size_t nesc,
-                                     const uint32_t* tables, int32_t S, int64_t n, const int64_t* step_len,
-                                     int64_t nsteps, int32_t* idx_out) {
+// The one decoder, with encode's table rule.
+int decode(const uint8_t* in, size_t nbytes, const uint32_t* esc, size_t nesc, const uint32_t* tables,
+           const int32_t* table_of, int32_t T, int32_t S, int64_t n, const int64_t* step_len, int64_t nsteps,
+           int32_t* idx_out) {
   if (!in || S < 2 || n < 0 || (n > 0 && (!tables || !idx_out)) || (nesc > 0 && !esc)) return LIC_CODEC_ERR_INVALID;
   if (!steps_ok(step_len, nsteps, n)) return LIC_CODEC_ERR_INVALID;
+  if (!table_of_ok(table_of, T, n)) return LIC_CODEC_ERR_INVALID;
   if (nbytes < (size_t)kLanes * 4 || (nbytes & 1)) return LIC_CODEC_ERR_CORRUPT;
   uint32_t x[kLanes];
   for (int l = 0; l < kLanes; ++l) {
@@ -112,7 +118,7 @@ LIC_CODEC_EXPORT int lic_rans_decode(const uint8_t* in, size_t nbytes, const uin
     // lanes in ascending order within a round is ascending k: the rank rule of the format, serialised
     for (int64_t k = 0; k < step_len[t]; ++k) {
       const int64_t i = base + k;
-      const uint32_t* tb = tables + (size_t)i * (size_t)(S + 1);
+      const uint32_t* tb = tables + (size_t)(table_of ? table_of[i] : i) * (size_t)(S + 1);
       if (!table_ok(tb, S)) return LIC_CODEC_ERR_INVALID;
       uint32_t xl = x[k % kLanes];
       const uint32_t slot = xl & 0xFFFFu;
@@ -148,6 +154,38 @@ LIC_CODEC_EXPORT int lic_rans_decode(const uint8_t* in, size_t nbytes, const uin
   for (int l = 0; l < kLanes; ++l)
     if (x[l] != kLow) return LIC_CODEC_ERR_CORRUPT;
   return LIC_CODEC_OK;
+}
+
+}  // namespace
+
+LIC_CODEC_EXPORT size_t lic_rans_bound(int64_t n) {
+  // the 64 final states + at most one 16-bit word per symbol
+  return n < 0 ? 0 : (size_t)kLanes * 4 + (size_t)n * 2;
+}
+
+LIC_CODEC_EXPORT int lic_rans_encode(const uint32_t* tables, int32_t S, const int32_t* idx, int64_t n,
+                                     const int64_t* step_len, int64_t nsteps, uint8_t* out, size_t cap,
+                                     size_t* nbytes, uint32_t* esc_out, size_t esc_cap, size_t* nesc) {
+  return encode(tables, nullptr, 0, S, idx, n, step_len, nsteps, out, cap, nbytes, esc_out, esc_cap, nesc);
+}
+
+LIC_CODEC_EXPORT int lic_rans_decode(const uint8_t* in, size_t nbytes, const uint32_t* esc, size_t nesc,
+                                     const uint32_t* tables, int32_t S, int64_t n, const int64_t* step_len,
+                                     int64_t nsteps, int32_t* idx_out) {
+  return decode(in, nbytes, esc, nesc, tables, nullptr, 0, S, n, step_len, nsteps, idx_out);
+}
+
+LIC_CODEC_EXPORT int lic_rans_encode_shared(const uint32_t* tables, const int32_t* table_of, int32_t T, int32_t S,
+                                            const int32_t* idx, int64_t n, const int64_t* step_len, int64_t nsteps,
+                                            uint8_t* out, size_t cap, size_t* nbytes, uint32_t* esc_out,
+                                            size_t esc_cap, size_t* nesc) {
+  return encode(tables, table_of, T, S, idx, n, step_len, nsteps, out, cap, nbytes, esc_out, esc_cap, nesc);
+}
+
+LIC_CODEC_EXPORT int lic_rans_decode_shared(const uint8_t* in, size_t nbytes, const uint32_t* esc, size_t nesc,
+                                            const uint32_t* tables, const int32_t* table_of, int32_t T, int32_t S,
+                                            int64_t n, const int64_t* step_len, int64_t nsteps, int32_t* idx_out) {
+  return decode(in, nbytes, esc, nesc, tables, table_of, T, S, n, step_len, nsteps, idx_out);
 }
 
 LIC_CODEC_EXPORT double lic_rans_ideal_bits(const uint32_t* tables, const int32_t* table_of, int32_t S,
