@@ -97,7 +97,8 @@ typedef struct lic_igemm_desc {
                      * aux3 = norm (-0.5 g x norm^-3/2, or 0.5 g x norm^-1/2 for IGDN) and also
                      * written to out2 for the d-gamma / d-beta launches (replaces lic_gdn_dnorm) */
   int32_t epilogue; /* enum lic_epilogue */
-  uint32_t tap_mask; /* bit (r*kw+s) set = tap is live; 0 = all taps (kh*kw <= 32) */
+  uint32_t tap_mask; /* bit (r*kw+s) set = tap is live; 0 = all taps.  kh*kw <= 28 (LIC_ERR_UNSUPPORTED above): the
+                      * kernels take each phase's taps from a 28-slot list in their parameter block (IgemmParams::taps) */
   float slope;       /* LeakyReLU negative slope */
   void* workspace;   /* optional (may be NULL): lets small layers split K across workgroups */
   size_t workspace_bytes;

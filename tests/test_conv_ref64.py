@@ -1,0 +1,364 @@
+"""CPU checks of tests/conv_ref64.py, the float64 statements tests/test_gpu_conv_fp32.py holds lic_igemm, lic_wgrad,
+lic_im2col and lic_col2im to: they agree with oracle/oracle.py within the oracle's own fp32 rounding; the exact cases are
+exact (S < 2^24 on integer data); every mutant of a statement changes an exact case and misses the element-wise band of a
+banded one by more than 8 x; and the case tables reach, through the library's planners, every igemm_kernel<.., FUSE = false>,
+wgrad_kernel<> and wgrad_glds_kernel<> instantiation of liblic_hip.so, the K splits that begin inside a tap and the
+phase-sorted launch.  No GPU."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import conv_ref64 as R
+from test_variant_tables import library_kernels
+
+U = 2.0 ** -24
+_STANDIN = C.create_string_buffer(4096)
+ALIGNED = (C.addressof(_STANDIN) + 15) & ~15       # planners never dereference operands: a host buffer stands in
+# instantiations no few-second case reaches (at most three): none
+UNREACHED = {}
+
+ids = repr
+
+
+def nchw(a):
+    return np.ascontiguousarray(a.permute(0, 3, 1, 2).numpy()).astype(np.float32)
+
+
+def nhwc(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).permute(0, 2, 3, 1)
+
+
+def within(got, ref, bound, what):
+    err = (R.f64(got) - R.f64(ref)).abs()
+    worst = float((err / bound.clamp_min(1e-300)).max())
+    print(f"{what}: {worst:.3f} of the oracle's rounding bound")
+    assert got.shape == ref.shape and bool((err <= bound).all()), (what, worst)
+
+
+# ---------------------------------------------------------------------------------------------
+# the statements against the oracle
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", R.IGEMM_CASES, ids=ids)
+def test_igemm_statement_agrees_with_the_oracle(c):
+    """The oracle adds one fp32 product at a time: a sum of n terms is within (n + 8) u of the sum of their magnitudes, to
+    first order -- the bound used for y (before the epilogue) and for dx."""
+    from oracle import oracle as O
+    inp = R.igemm_inputs(c, exact=False)
+    x = inp["x"] * inp["x"] if c.sq else inp["x"]
+    w = inp["w"].numpy()
+    if c.tap_mask:
+        w = w * R.live_taps(c.k, c.k, c.tap_mask).reshape(1, 1, c.k, c.k).float().numpy()
+    b = None if inp["b"] is None else inp["b"].numpy()
+    ref = R.igemm_reference(c, inp)
+    n = c.k * c.k * c.cin + 1
+    if c.kind == "conv":
+        y = O.conv2d_fwd(nchw(x), w, b, c.s, c.p)
+    else:
+        y = O.convT2d_fwd(nchw(x), w, b, c.s, c.p, c.op)
+    within(nhwc(y), ref["pre"], (n + 8 + (2 if c.sq else 0)) * U * ref["S"], f"{c} y")
+    if c.dgrad:
+        dref = R.igemm_reference(c, inp, "dgrad")
+        if c.kind == "conv":
+            dx, _, _ = O.conv2d_bwd(nchw(inp["x"]), w, nchw(inp["dy"]), c.s, c.p)
+        else:
+            dx, _, _ = O.convT2d_bwd(nchw(inp["x"]), w, nchw(inp["dy"]), c.s, c.p, c.op)
+        within(nhwc(dx), dref["out"], (c.k * c.k * c.cout + 8) * U * dref["S"], f"{c} dx")
+
+
+def _oracle_wgrad(c, inp):
+    """lic_wgrad's R[tap][m][n] / scale from the oracle's weight gradients (operands squared beforehand in fp32)"""
+    from oracle import oracle as O
+    g = c.g
+    P = inp["P"] * inp["P"] if g["sq_p"] else inp["P"]
+    G = inp["G"] * inp["G"] if g["sq_g"] else inp["G"]
+    k = g["kh"]
+    w0 = np.zeros((g["Cp"], g["Cg"], k, k), np.float32)
+    if g["g_is_row"]:    # the small grid is a convolution's output gradient: dw[Cp][Cg][kh][kw]
+        _, dw, db = O.conv2d_bwd(nchw(G), w0, nchw(P), g["stride"], g["pad"], need_dx=False)
+        return torch.from_numpy(dw).permute(2, 3, 1, 0).reshape(k * k, g["Cg"], g["Cp"]), torch.from_numpy(db)
+    op = g["Hl"] - ((g["Hs"] - 1) * g["stride"] - 2 * g["pad"] + k)
+    assert op == g["Wl"] - ((g["Ws"] - 1) * g["stride"] - 2 * g["pad"] + k)
+    _, dw, db = O.convT2d_bwd(nchw(P), w0, nchw(G), g["stride"], g["pad"], op, need_dx=False)
+    return torch.from_numpy(dw).permute(2, 3, 0, 1).reshape(k * k, g["Cp"], g["Cg"]), torch.from_numpy(db)
+
+
+@pytest.mark.parametrize("c", R.WGRAD_CASES, ids=ids)
+def test_wgrad_statement_agrees_with_the_oracle(c):
+    """the oracle sums a row of pixels in fp32 and the rows in double: within (pixels + 8) u of S; db the same way"""
+    inp = R.wgrad_inputs(c, exact=False)
+    ref = R.wgrad_reference(c, inp)
+    dw, db = _oracle_wgrad(c, inp)
+    within(c.g["scale"] * dw.double(), ref["R"], (c.pixels + 8) * U * ref["S"], f"{c} dw")
+    small = inp["G"] if not c.g["g_is_row"] else inp["P"]     # the oracle's db: column sums of its dy operand
+    small = small * small if (c.g["sq_g"] if not c.g["g_is_row"] else c.g["sq_p"]) else small
+    s, S = R.colsum(small)
+    within(db, s, (small.numel() // small.shape[-1] + 8) * U * S, f"{c} db")
+    # the destination layouts: conv / convT are the weight layouts of the layers, every layout maps one to one
+    flat, idx = R.scatter_dst(c, ref["R"], float("nan"))
+    sm, sn, st, span = c.dst_strides()
+    assert flat.numel() == span and int(idx.max()) == span - 1 and int(torch.isnan(flat).sum()) == span - idx.numel()
+    if c.layout == "conv":
+        assert torch.equal(flat.reshape(c.Cn, c.Cm, c.taps), ref["R"].permute(2, 1, 0))
+    if c.layout == "convT":
+        assert torch.equal(flat.reshape(c.Cm, c.Cn, c.taps), ref["R"].permute(1, 2, 0))
+
+
+@pytest.mark.parametrize("c", R.COL_CASES, ids=lambda c: c[0])
+def test_column_statements_agree_with_the_oracle(c):
+    """im2col followed by the dense product is the oracle's convolution; the dense product followed by col2im is its
+    transposed convolution (both products in double here, so only the oracle's rounding is in the bound)"""
+    from oracle import oracle as O
+    q, inp = R.col_geom(c), R.col_inputs(c, exact=False)
+    B, H, W, Cc, k, s, p, Ho, Wo, Kpad = (q[n] for n in ("B", "H", "W", "C", "k", "s", "p", "Ho", "Wo", "Kpad"))
+    g_ = torch.Generator().manual_seed(11)
+    N = 8
+    w = torch.randn((N, Cc, k, k), generator=g_) / (Cc * k * k) ** 0.5          # conv [Cout,Cin,kh,kw] = convT [Cin,Cout,kh,kw]
+    col = R.im2col(inp["x"], Ho, Wo, k, k, s, p, Kpad)
+    assert col.shape == (B * Ho * Wo, Kpad) and not bool(col[:, k * k * Cc:].any())
+    Wm = torch.zeros((Kpad, N), dtype=torch.float64)
+    Wm[:k * k * Cc] = w.double().permute(2, 3, 1, 0).reshape(k * k * Cc, N)           # [(tap, c)][n]
+    y = O.conv2d_fwd(nchw(inp["x"]), w.numpy(), None, s, p)
+    S = col.abs() @ Wm.abs()
+    within(nhwc(y).reshape(-1, N), col @ Wm, (k * k * Cc + 8) * U * S, f"{c[0]} im2col -> product")
+    # transposed: z [B,Ho,Wo,N] -> columns [., Kpad] -> col2im -> [B,H,W,C]
+    z = torch.randn((B, Ho, Wo, N), generator=g_)
+    cols = torch.full((B * Ho * Wo, Kpad), 7.0, dtype=torch.float64)                  # (the padding columns must not be read)
+    cols[:, :k * k * Cc] = z.double().reshape(-1, N) @ w.double().permute(0, 2, 3, 1).reshape(N, k * k * Cc)
+    out, _ = R.col2im(cols, inp["b"], B, Ho, Wo, Cc, H, W, k, k, s, p)
+    acols = torch.zeros_like(cols)
+    acols[:, :k * k * Cc] = z.double().abs().reshape(-1, N) @ w.double().abs().permute(0, 2, 3, 1).reshape(N, k * k * Cc)
+    _, S2 = R.col2im(acols, inp["b"], B, Ho, Wo, Cc, H, W, k, k, s, p)
+    yt = O.convT2d_fwd(nchw(z), w.numpy(), inp["b"].numpy(), s, p, q["op"])
+    within(nhwc(yt), out, (k * k * N + 8) * U * S2, f"{c[0]} product -> col2im")
+
+
+def test_logical_weights_are_what_the_pack_strides_read():
+    for kind in ("conv", "convT"):
+        for dgrad in (False, True):
+            cin, cout, k = 5, 7, 3
+            w = torch.arange((cout * cin * k * k), dtype=torch.float32).reshape((cout, cin, k, k) if kind == "conv" else (cin, cout, k, k))
+            taps, K, N, s_tap, s_k, s_n = R.pack_strides(kind, dgrad, cin, cout, k * k)
+            t, kk, n = torch.meshgrid(torch.arange(taps), torch.arange(K), torch.arange(N), indexing="ij")
+            assert torch.equal(w.reshape(-1)[t * s_tap + kk * s_k + n * s_n], R.logical_weight(w, kind, dgrad))
+
+
+# ---------------------------------------------------------------------------------------------
+# the exact cases
+# ---------------------------------------------------------------------------------------------
+def _is_int(t, lo, hi):
+    return bool((t == t.round()).all()) and float(t.min()) >= lo and float(t.max()) <= hi
+
+
+@pytest.mark.parametrize("c", R.IGEMM_CASES, ids=ids)
+def test_exact_igemm_cases_are_exact(c):
+    inp = R.igemm_inputs(c, exact=True)
+    assert _is_int(inp["x"], -3, 3) and _is_int(inp["w"], -2, 2) and (inp["b"] is None or _is_int(inp["b"], -4, 4))
+    ref = R.igemm_reference(c, inp)
+    assert R.exact_ok(ref["S"] + (3 if c.epi == "leaky_res" else 0))
+    assert float((ref["out"] != 0).double().mean()) > 0.5, "a degenerate case"
+    R.canon_bits(ref["out"])                       # representable in fp32 (the slope is a power of two)
+    if ref["out2"] is not None:
+        R.canon_bits(ref["out2"])
+    if c.dgrad:
+        assert R.exact_ok(R.igemm_reference(c, inp, "dgrad")["S"])
+    # no two (tap, channel) pairs of the weight agree everywhere: a transposition cannot cancel
+    if c.cin * c.k * c.k > 1 and c.cout >= 24:
+        Wl = R.logical_weight(inp["w"], c.kind, False).reshape(-1, c.cout)
+        assert len(torch.unique(Wl, dim=0)) == Wl.shape[0]
+
+
+@pytest.mark.parametrize("c", R.WGRAD_CASES, ids=ids)
+def test_exact_wgrad_cases_are_exact(c):
+    inp = R.wgrad_inputs(c, exact=True)
+    assert _is_int(inp["P"], -3, 3) and _is_int(inp["G"], -3, 3)
+    ref = R.wgrad_reference(c, inp)
+    assert R.exact_ok(ref["S"] / c.g["scale"]) and c.g["scale"] in (1.0, 0.5)
+    R.canon_bits(ref["R"])
+
+
+@pytest.mark.parametrize("c", R.COL_CASES, ids=lambda c: c[0])
+def test_exact_column_cases_are_exact(c):
+    q, inp = R.col_geom(c), R.col_inputs(c, exact=True)
+    _, S = R.col2im(inp["col"], inp["b"], q["B"], q["Ho"], q["Wo"], q["C"], q["H"], q["W"], q["k"], q["k"], q["s"], q["p"])
+    assert R.exact_ok(S)
+
+
+# ---------------------------------------------------------------------------------------------
+# the mutants
+# ---------------------------------------------------------------------------------------------
+def test_every_mutant_changes_an_exact_case_and_misses_the_band_of_a_banded_one():
+    only_new = []
+    for name, make in R.MUTANTS.items():
+        kind, ref, mut, S, A = make(True)
+        changed = int((ref != mut).sum())
+        assert changed > 0, f"{name}: the exact case does not notice"
+        kind, ref, mut, S, A = make(False)
+        assert A <= R.A_CEILING
+        miss = R.err_over_S(mut, ref, S) / A
+        old = (R.old_output_band_passes if kind == "output" else R.old_gradient_band_passes)(mut, ref)
+        print(f"MUTANT {name}: {changed} elements of the exact case differ; banded: {miss:.3g} x the band"
+              f" ({kind}); the old whole-tensor band {'PASSES it' if old else 'catches it'}")
+        assert miss > 8.0, (name, miss)
+        if old:
+            only_new.append(name)
+    print("mutants only the element-wise bands catch:", only_new or "none at these shapes")
+
+
+def test_err_over_S_and_same_bits():
+    one = torch.ones(3)
+    assert R.err_over_S(one, one, torch.zeros(3)) == 0.0
+    assert R.err_over_S(torch.tensor([1.0, float("nan"), 1.0]), one, one) == float("inf")
+    assert R.err_over_S(torch.tensor([1.0, 1.5, 1.0]), one, torch.tensor([1.0, 4.0, 1.0])) == 0.125
+    assert R.err_over_S(torch.tensor([1.0, 1.5, 1.0]), one, torch.tensor([1.0, 0.0, 1.0])) == float("inf")
+    assert R.same_bits(torch.tensor([0.0, -0.0]), torch.tensor([-0.0, 0.0], dtype=torch.float64))
+    assert not R.same_bits(torch.tensor([1.0]), torch.tensor([1.0000001]))
+
+
+# ---------------------------------------------------------------------------------------------
+# what the tables reach, through the library's planners
+# ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def lib():
+    from neural_image_compression_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return _lib
+
+
+def igemm_desc(L, c, which, tile, split):
+    addr = {"in": ALIGNED + 4 * (c.in_off if which == "fwd" else 0), "w": ALIGNED,
+            "out": ALIGNED + 4 * (c.out_col0 if which == "fwd" else 0), "bias": ALIGNED, "out2": ALIGNED, "res": ALIGNED,
+            "aux": ALIGNED, "workspace": ALIGNED, "workspace_bytes": 1 << 40}
+    return R.fill_igemm_desc(L.IgemmDesc(), c, which, tile, split, addr)
+
+
+def wgrad_desc(L, c, split):
+    return R.fill_wgrad_desc(L.WgradDesc(), c, split, {"p": ALIGNED + 4 * c.p_off, "g": ALIGNED, "dst": ALIGNED})
+
+
+def _name(fn, d):
+    buf = C.create_string_buffer(96)
+    rc = fn(C.byref(d), buf, 96)
+    assert rc == 0, rc
+    return buf.value.decode()
+
+
+def test_the_tables_reach_every_fp32_gemm_instantiation(lib, tmp_path):
+    L, so = lib, lib.load()
+    kernels = library_kernels(L.LIB_PATH, str(tmp_path))
+    want = {k for k in kernels if k.startswith(("wgrad_kernel<", "wgrad_glds_kernel<"))}
+    igemm_all = {k for k in kernels if k.startswith("igemm_kernel<")}
+    fused = {k for k in igemm_all if k.split(", ")[4] == "true"}       # igemm_kernel<BM, TN, VEC, FULLN, FUSE, GLDS>
+    assert len(fused) == 3 and len(igemm_all) == 18 and len(want) == 33, (sorted(igemm_all), len(want))
+    want |= igemm_all - fused
+    reached = set()
+    for c in R.IGEMM_CASES:
+        for which, tile, split in c.launches():
+            reached.add(_name(so.lic_igemm_kernel_name, igemm_desc(L, c, which, tile, split)))
+    for c in R.WGRAD_CASES:
+        for split in c.splits:
+            reached.add(_name(so.lic_wgrad_kernel_name, wgrad_desc(L, c, split)))
+    assert reached <= kernels
+    assert len(UNREACHED) <= 3 and set(UNREACHED) <= want
+    missing = sorted(want - reached - set(UNREACHED))
+    assert not missing, "instantiated, but no case of conv_ref64 launches them:\n  " + "\n  ".join(missing)
+    assert not (set(UNREACHED) & reached), "listed as unreached, but a case reaches it"
+
+
+def _ksplit(so, d, c):
+    nbytes = so.lic_igemm_workspace_bytes(C.byref(d))
+    per = c.B * c.Ho * c.Wo * c.cout * 4
+    assert nbytes % per == 0
+    return nbytes // per
+
+
+def test_the_planner_accepts_every_launch_and_forced_tiles_are_taken(lib):
+    L, so = lib, lib.load()
+    for c in R.IGEMM_CASES:
+        for which, tile, split in c.launches():
+            d = igemm_desc(L, c, which, tile, split)
+            bm, bn = C.c_int32(0), C.c_int32(0)
+            assert so.lic_igemm_plan(C.byref(d), C.byref(bm), C.byref(bn), None) == 0, (c, which, tile, split)
+            if tile != (0, 0):
+                assert (bm.value, bn.value) == (tile[0], 64 * tile[1])
+            if isinstance(split, int) and split > 1:
+                assert _ksplit(so, d, c) == c.chunks_per_split(split)[1] > 1, (c, split)
+    for c in R.WGRAD_CASES:
+        for split in c.splits:
+            d = wgrad_desc(L, c, split)
+            tm, tn, sk = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+            assert so.lic_wgrad_plan(C.byref(d), C.byref(tm), C.byref(tn), C.byref(sk)) == 0, (c, split)
+            if c.tile != (0, 0):
+                assert (tm.value, tn.value) == c.tile
+            if split:
+                assert sk.value == c.split_plan(split)[1]
+    # "more splits than there are chunks" and ragged last chunks occur
+    assert any(s > c.nchunks for c in R.WGRAD_CASES for s in c.splits)
+    assert any(c.pixels % R.IG_BK for c in R.WGRAD_CASES) and any(c.pixels % R.IG_BK == 0 for c in R.WGRAD_CASES)
+
+
+def test_mid_tap_splits_begin_inside_a_tap(lib):
+    """the second slice of each listed launch starts at chunk `cps` of the (tap, channel block) list: inside a tap when
+    cps is no multiple of the chunks per tap.  The library's own split count is read back from its workspace query."""
+    L, so = lib, lib.load()
+    assert len(R.MID_TAP) >= 6
+    for name, split in R.MID_TAP:
+        c = R.ICASE[name]
+        assert split in c.splits
+        (mc, cpt), (cps, slices) = c.max_chunks(), c.chunks_per_split(split)
+        assert cpt > 1 and cps % cpt != 0 and slices > 1, (name, split, cps, cpt)
+        assert _ksplit(so, igemm_desc(L, c, "fwd", (0, 0), split), c) == slices
+    # both finish kernels: four channels per lane (Cout % 4 == 0, aligned rows) and the scalar one
+    mids = [R.ICASE[n] for n, _ in R.MID_TAP]
+    assert any(c.cout % 4 == 0 and c.out_ld % 4 == 0 and c.out_col0 % 4 == 0 for c in mids)
+    assert any(c.cout % 4 for c in mids) and any(c.out_ld % 4 for c in mids)
+    # the automatic plan splits only with a workspace
+    c = R.ICASE["auto-ws"]
+    assert _ksplit(so, igemm_desc(L, c, "fwd", (0, 0), "ws"), c) == 3
+
+
+def test_the_phase_sorted_case_is_phase_sorted(lib):
+    """phase_order's documented rule: four phases and at least 128 M tiles in the largest phase"""
+    L, so = lib, lib.load()
+    c = R.ICASE[R.PGROUP_CASE]
+    assert c.kind == "convT" and c.s == 2
+    for which, tile, split in c.launches():
+        d = igemm_desc(L, c, which, tile, split)
+        bm = C.c_int32(0)
+        assert so.lic_igemm_plan(C.byref(d), C.byref(bm), None, None) == 0
+        per_phase = c.B * ((c.Ho + 1) // 2) * ((c.Wo + 1) // 2)
+        assert -(-per_phase // bm.value) >= R.PGROUP_TILES, (per_phase, bm.value)
+    # and no other transposed case is: they rotate phases tile by tile
+    for o in R.IGEMM_CASES:
+        if o is not c and o.kind == "convT" and o.s == 2:
+            assert -(-(o.B * ((o.Ho + 1) // 2) * ((o.Wo + 1) // 2)) // 64) < R.PGROUP_TILES
+
+
+def test_case_tables():
+    for table in (R.IGEMM_CASES, R.WGRAD_CASES):
+        assert len({c.name for c in table}) == len(table)
+    ic = R.IGEMM_CASES
+    residues = set()
+    for c in ic:
+        if c.tiles == "all" and c.vec():
+            residues.add(c.max_chunks()[0] % 3)
+    assert residues == {0, 1, 2}, residues                    # the three-slot ring's tails
+    assert any(c.cin % 16 and c.cin % 4 == 0 for c in ic) and any(c.cin % 4 for c in ic) and any(c.in_off for c in ic)
+    assert any(c.cout <= 32 for c in ic) and any(c.cout % 4 for c in ic)
+    assert any(c.in_extra for c in ic) and any(c.out_ld > c.cout and c.out_col0 for c in ic)
+    assert {(c.Ho % 2, c.Wo % 2) for c in ic if c.kind == "convT" and c.s == 2} >= {(0, 0), (1, 1)}
+    assert any(c.tap_mask == R.mask_a_bits(5) for c in ic)
+    assert {c.epi for c in ic} == {"none", "leaky", "leaky_res", "mulmask"}
+    wc = R.WGRAD_CASES
+    assert {c.tile for c in wc} >= {(1, 1), (1, 3), (2, 1), (2, 2), (2, 3), (3, 3)}
+    assert {c.g["g_is_row"] for c in wc} == {0, 1} and any(c.g["sq_g"] for c in wc) and any(c.g["scale"] != 1 for c in wc)
+    assert {c.layout for c in wc} >= {"conv", "convT", "conv-gap", "convT-gap", "dense"}
+    assert {s for c in wc for s in c.splits} >= {1, 2, 3, 99}
+    cc = [R.col_geom(c) for c in R.COL_CASES]
+    assert {(q["k"], q["s"], q["p"]) for q in cc if q["C"] == 3} == {(5, 2, 2), (3, 2, 1)}
+    assert {q["op"] for q in cc} == {0, 1} and {q["H"] % 2 for q in cc} == {0, 1}
+    assert any(q["Kpad"] == q["k"] ** 2 * q["C"] for q in cc) and any(q["Kpad"] > q["k"] ** 2 * q["C"] for q in cc)

@@ -22,10 +22,10 @@ import pytest
 import torch
 
 import gdn_ref64 as G
+from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0x7FC0BEEF          # a quiet NaN with a payload no arithmetic produces
 ERR_INVALID, ERR_UNSUPPORTED = -1, -2
 SMALL = [c for c in G.CASES if c[2] in (65, 357)]                 # two tiles with one pixel in the second; ragged, six tiles
 SOME = SMALL + [c for c in G.CASES if c[2] == G.BIG and c[0] == 192]
@@ -40,27 +40,6 @@ def env():
     from neural_image_compression_amd import functional as F_
     L.load()  # must be the in-tree HIP extension; raises if missing
     return nic, F_, L, torch.device("cuda:0")
-
-
-class Guarded:
-    """a [rows][C] fp32 output pre-filled with the NaN pattern, with one canary row in front of it and one behind"""
-
-    def __init__(self, rows, C, dev):
-        self.buf = torch.full(((rows + 2) * C,), CANARY, dtype=torch.int32, device=dev)
-        self.rows, self.C = rows, C
-        self.t = self.buf.view(torch.float32)[C:(rows + 1) * C].view(rows, C)
-        assert self.t.data_ptr() % 16 == 0
-
-    def check(self, what=""):
-        b = self.buf.cpu()
-        assert bool((b[:self.C] == CANARY).all()), f"{what}: the row in front of the output was written"
-        assert bool((b[-self.C:] == CANARY).all()), f"{what}: the row behind the output was written"
-
-    def untouched(self):
-        return bool((self.buf.cpu() == CANARY).all())
-
-    def cpu(self):
-        return self.t.detach().cpu().contiguous()
 
 
 def bits(t):
