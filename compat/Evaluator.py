@@ -1,1 +1,1 @@
-from neural_image_compression_amd.evaluator import CompressionEvaluator  # noqa: F401
+from neural_image_compression_amd.evaluator import CompressionEvaluator, VisionCompressionEvaluator  # noqa: F401

@@ -480,6 +480,36 @@ int lic_ctx_gather_ragged(const float* y, int64_t y_len, int64_t y_pix, const in
                           int64_t comb_ld, int32_t path, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Layered codec (codec.ScalableCodec) -- lic_ctx_gather for a latent whose channels are split into L layers, each
+ *   with a context model of its own: one launch builds every layer's rows from the ONE y buffer and the one psi.
+ *   y .. n and psi, Cpsi, path are lic_ctx_gather's (the plane has y_pix channels per pixel; there is no call-wide M).
+ *     layers        [L] rows, 1 <= L <= LIC_MAX_LAYERS, a HOST array that is copied into the launch: layer l covers
+ *                   channels [c0, c0 + M) of every pixel, writes row b * n + k of win [B*n][nt*M] (column t * M + c =
+ *                   tap t, channel c0 + c) and, with psi, row b * n + k of comb (comb_ld floats per row, `comb` the
+ *                   first column to write) with the pixel's Cpsi psi columns.
+ *   The bytes written for layer l are exactly those of lic_ctx_gather(y + c0, ..., M, ..., win, psi, Cpsi, comb,
+ *   comb_ld): zeros for taps outside the image or the slice, rows of zeros for a pix[k] outside [0, h*w).
+ *   The 16-byte path is decided per layer: lic_ctx_gather's conditions with c0 and M multiples of 4 and the layer's
+ *   win / comb 16-byte aligned; a layer that misses them goes float by float, the others keep their pieces, and both
+ *   write the same bytes.  LIC_CTX_VECTOR: LIC_ERR_INVALID unless every layer qualifies.
+ *   NULL y / taps / pix / layers / a layer's win, psi with a layer without comb (or comb_ld < Cpsi), L outside
+ *   1..LIC_MAX_LAYERS, M <= 0, c0 < 0, c0 + M > y_pix, two layers whose channel ranges overlap, B, h, w, n <= 0,
+ *   nt < 1, slice_rows < 1, a misaligned pointer: LIC_ERR_INVALID; lic_ctx_gather's size limits per layer:
+ *   LIC_ERR_UNSUPPORTED; nothing launched.  One launch on `stream`, no allocation, no synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+#define LIC_MAX_LAYERS 4
+typedef struct lic_ctx_layer {
+  float* win;
+  float* comb;
+  int64_t comb_ld;
+  int32_t c0, M;
+} lic_ctx_layer;
+int lic_ctx_gather_layers(const float* y, int64_t y_batch, int64_t y_row, int64_t y_pix, int64_t y_origin, int32_t B,
+                          int32_t h, int32_t w, const int32_t* taps, int32_t nt, int32_t slice_rows, const int64_t* pix,
+                          int64_t n, const float* psi, int32_t Cpsi, const lic_ctx_layer* layers, int32_t L,
+                          int32_t path, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).2 -- the device decoder of the "rANS-64" y streams (format and host coder: lic_codec.h).
  *   lic_rans_decode_step decodes ONE wavefront step of all B images in one launch, one wave per image, from the
  *   tables lic_gmm_cdf_tables has just built, and writes the values where the next step's gather reads them:
@@ -562,6 +592,36 @@ int lic_rans_decode_step_ragged(const uint8_t* streams, const int64_t* stream_of
                                 const uint32_t* tables, const int32_t* center, const int32_t* seg, int32_t nimg,
                                 int32_t G, int64_t total_rows, int32_t M, int32_t W, const int64_t* dest, float* ypad,
                                 const int64_t* y_base, const int64_t* pixels, int64_t ypad_len, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Layered codec (codec.ScalableCodec) -- lic_rans_decode_step_groups for L layers of one latent in ONE launch:
+ *   L * B * G workgroups of one wave.  Every layer is a "rANS-64 x G" stream set of its own over its own channels,
+ *   with its own tables; the waves of different layers are independent and share the launch, dest and the plane.
+ *     stream_off, stream_bytes, esc_off, state   LAYER-MAJOR: block (l * B + b) * G + g is sub-stream g of image b of
+ *                   layer l (L*B*G + 1 offsets, L*B*G lengths and state blocks), so a call with the first layer
+ *                   alone stages and launches L = 1 with no gaps
+ *     layers        [L] rows, 1 <= L <= LIC_MAX_LAYERS, a HOST array that is copied into the launch: layer l has
+ *                   channels [c0, c0 + M), tables [B][n*M][2W+2] (16-byte aligned) and center [B][n*M]
+ *     n, W, dest, ypad, pixels   call-wide, as in lic_rans_decode_step; ypad is [B][pixels][y_pix] with
+ *                   y_pix >= c0 + M for every layer.  Symbol k of a layer's step is pixel k / M, channel c0 + k % M:
+ *                   element (b, dest[k / M], c0 + k % M) is written, no other
+ *   Per block every rule of lic_rans_decode_step_groups holds: cursors are compared before each read, error words are
+ *   per block, a group without a round in its layer's step (n * M symbols) leaves its state block bit for bit.  With
+ *   L = 1, c0 = 0, y_pix = M this is lic_rans_decode_step_groups.
+ *   NULL pointers, L outside 1..LIC_MAX_LAYERS, M <= 0, c0 < 0, c0 + M > y_pix, overlapping channel ranges, B, n, W,
+ *   pixels <= 0, G outside 1..LIC_RANS_MAX_GROUPS, misaligned pointers (tables 16 bytes, int64 arrays 8, the others 4):
+ *   LIC_ERR_INVALID.  W > 64, n * M >= 2^31 - 64, L * B * G > 65535: LIC_ERR_UNSUPPORTED.  Nothing is launched then.
+ *   One launch, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct lic_rans_layer {
+  const uint32_t* tables;
+  const int32_t* center;
+  int32_t c0, M;
+} lic_rans_layer;
+int lic_rans_decode_step_layers(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
+                                const uint32_t* escapes, const int64_t* esc_off, uint32_t* state,
+                                const lic_rans_layer* layers, int32_t L, int32_t B, int32_t G, int32_t n, int32_t W,
+                                const int64_t* dest, float* ypad, int64_t pixels, int64_t y_pix, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).2 -- the device encoder of the same streams: byte for byte what the host encoder of lic_codec.h

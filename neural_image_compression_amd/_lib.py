@@ -87,6 +87,20 @@ RANS_IMAGE_WORDS = RANS_BLOCK_WORDS = 4
 RANS_Z_AUTO, RANS_Z_RESIDENT, RANS_Z_GLOBAL = range(3)
 RANS_Z_MAX_S, RANS_Z_MAX_M, RANS_Z_LDS_BYTES = 4096, 65535, 65536
 
+# the layered codec's entries take a host array of at most MAX_LAYERS rows, which they copy into the launch
+MAX_LAYERS = 4
+
+
+class CtxLayer(C.Structure):
+    """lic_ctx_layer: one layer of lic_ctx_gather_layers"""
+    _fields_ = [("win", _vp), ("comb", _vp), ("comb_ld", _i64), ("c0", _i32), ("M", _i32)]
+
+
+class RansLayer(C.Structure):
+    """lic_rans_layer: one layer of lic_rans_decode_step_layers"""
+    _fields_ = [("tables", _vp), ("center", _vp), ("c0", _i32), ("M", _i32)]
+
+
 WINDOW_ZERO, WINDOW_REPLICATE, WINDOW_REFLECT = range(3)
 WINDOW_FLIP = 1
 
@@ -190,6 +204,10 @@ SIGNATURES = {
     "lic_ctx_gather_ragged": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
                                         _vp, _i64, _i32, _vp]),
     "lic_rans_decode_step_ragged": (C.c_int, [_vp] * 9 + [_i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "lic_ctx_gather_layers": (C.c_int, [_vp] + [_i64] * 4 + [_i32] * 3 + [_vp, _i32, _i32, _vp, _i64, _vp, _i32,
+                                        C.POINTER(CtxLayer), _i32, _i32, _vp]),
+    "lic_rans_decode_step_layers": (C.c_int, [_vp] * 6 + [C.POINTER(RansLayer)] + [_i32] * 5 + [_vp, _vp, _i64, _i64,
+                                                                                                 _vp]),
     "lic_rans_z_pick": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "lic_rans_z_decode_path": (C.c_int, [_i32, _i32]),
     "lic_rans_z_decode": (C.c_int, [_vp] * 7 + [_i32] * 5 + [_vp, _vp, _vp, _i64, _i32, _vp]),

@@ -33,6 +33,17 @@ the z stream LICBITS5 has a z SECTION, and the header's "z-stream length" is the
   z block table: B*G rows (sub-stream length, escapes), image-major | for every z block: its stream, then its escape list
 Its reader refuses what LICBITS3's does, for the z blocks too -- a z sub-stream shorter than its 64 states or of odd
 length -- and a z section whose table and blocks do not add up to its length.
+
+LICBITS6 is the layered container of codec.ScalableCodec (family 3 = ScalableImageCoding): the latent's M channels are
+two layers, the base one of M1 channels, each coded as "rANS-64 x G" sub-streams of its own.  Its header is LICBITS5's
+plus `uint32 M1, base_bytes`, and the blob is
+  header | image table: B rows (symbol CRC-32 of layer 0, of layer 1) | z section (LICBITS5's)
+  | base section: block table, B*G rows (sub-stream length, escapes), then the blocks | uint32 CRC-32 of all before it
+  | enhancement section: the same for layer 1 | uint32 CRC-32 of all before it
+`base_bytes` is the offset just behind the first CRC-32, so blob[:base_bytes] is a valid input of the base reader
+(`unpack_bitstream_layered_base`), which looks at nothing behind it; the full reader (`unpack_bitstream_layered`)
+refuses that prefix as truncated.  Both refuse what LICBITS5's reader does, M1 outside 0 < M1 < M, and a `base_bytes`
+that is not where the tables put the end of the base section.
 """
 from __future__ import annotations
 
@@ -58,7 +69,7 @@ def _groups(G) -> int:
     return int(G)
 
 
-BITSTREAM_FAMILIES = {"JointAutoregressiveHierarchical": 1, "HierarchicalMixtureResidual": 2}
+BITSTREAM_FAMILIES = {"JointAutoregressiveHierarchical": 1, "HierarchicalMixtureResidual": 2, "ScalableImageCoding": 3}
 BITSTREAM_MAGIC, BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_GROUPED = b"LICBITS1", b"LICBITS2", b"LICBITS3"
 BITSTREAM_MAGIC_SLICED = b"LICBITS4"
 BITSTREAM_MAGIC_ZRANS = b"LICBITS5"
@@ -208,6 +219,135 @@ def _check_crc_and_head(data: bytes, head: Dict):
             and head["top"] + head["H"] <= -(-head["H"] // 64) * 64 and head["left"] + head["W"] <= -(-head["W"] // 64) * 64
             and head["M"] > 0 and head["K"] > 0 and head["z_S"] > 0 and head["y_W"] > 0):
         raise CodecError("bitstream header is inconsistent")
+
+
+# ---- LICBITS6: the layered container of codec.ScalableCodec --------------------------------------------------------
+# It sits beside the five above as LICBITS5 sits beside the first four: `_FORMAT_OF_MAGIC` stays what it is.
+BITSTREAM_MAGIC_LAYERED = b"LICBITS6"
+_BITS_HEAD_LAYERED = struct.Struct("<8s3Ii12I")                        # LICBITS5's header, then `M1`, `base_bytes`
+_LAYERED_EXPECTS = ("two layers of one sub-stream and one escape list per image and group and one checksum per image, "
+                    "and one z sub-stream and escape list per image and group")
+
+
+def _pack_block_section(ys, escs) -> bytes:
+    """block table (sub-stream length, escapes per block), then every block's stream and escape list"""
+    return b"".join([struct.pack("<2I", len(s), len(e) // 4) for s, e in zip(ys, escs)]
+                    + [bytes(p) for s, e in zip(ys, escs) for p in (s, e)])
+
+
+def pack_bitstream_layered(head: Dict, z_streams, z_esc, layers, groups: int, slice_rows: int = None) -> bytes:
+    """LICBITS6.  `head`: the _BITS_FIELDS and "M1"; `layers`: two dicts {"y": [B*G sub-streams], "y_esc": [B*G escape
+    lists], "y_crc32": [B]}, base layer first; z as for LICBITS5; slice_rows None or 0: no slices.  Layout (module
+    docstring): header | image table | z section | base section | CRC-32 | enhancement section | CRC-32, and
+    header word `base_bytes` = the offset just behind the first CRC-32, so blob[:base_bytes] decodes the base alone."""
+    G, B = _groups(groups), int(head["B"])
+    R = 0 if slice_rows is None else slice_rows
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 0 <= int(R) <= 0xFFFFFFFF:
+        raise CodecError(f"slice_rows = {R!r}: expected None or a whole number of rows per slice")
+    try:
+        if len(layers) != 2:
+            raise CodecError(_LAYERED_EXPECTS + " expected")
+        secs = [([bytes(s) for s in ly["y"]], [bytes(e) for e in ly["y_esc"]], list(ly["y_crc32"])) for ly in layers]
+    except (TypeError, KeyError):
+        raise CodecError(_LAYERED_EXPECTS + " expected") from None
+    if any(len(ys) != B * G or len(es) != B * G or len(crc) != B for ys, es, crc in secs):
+        raise CodecError(_LAYERED_EXPECTS + " expected")
+    if any(len(e) % 4 for _, es, _ in secs for e in es):
+        raise CodecError("an escape list is not a whole number of uint32")
+    z_sec = _pack_z_section((z_streams, z_esc), B * G, _LAYERED_EXPECTS)
+    images = b"".join(struct.pack("<2I", int(a) & 0xFFFFFFFF, int(b) & 0xFFFFFFFF) for a, b in zip(secs[0][2], secs[1][2]))
+    base_sec, enh_sec = _pack_block_section(*secs[0][:2]), _pack_block_section(*secs[1][:2])
+    base_bytes = _BITS_HEAD_LAYERED.size + len(images) + len(z_sec) + len(base_sec) + 4
+    if base_bytes + len(enh_sec) + 4 > 0xFFFFFFFF:
+        raise CodecError("the bitstream is too long for its 32-bit lengths")
+    front = _BITS_HEAD_LAYERED.pack(BITSTREAM_MAGIC_LAYERED, *(int(head[k]) for k in _BITS_FIELDS), len(z_sec),
+                                    RANS_LANES * G, int(R), int(head["M1"]), base_bytes) + images + z_sec + base_sec
+    front += struct.pack("<I", zlib.crc32(front) & 0xFFFFFFFF)
+    body = front + enh_sec
+    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+
+
+def _block_table(data: bytes, at: int, nblocks: int):
+    """the block table at `at` -> ([(length, escapes)], the cuts of its blocks' streams and escape lists behind it)"""
+    rows = [struct.unpack_from("<2I", data, at + 8 * i) for i in range(nblocks)]
+    return rows, list(accumulate([n for ln, ne in rows for n in (ln, 4 * ne)], initial=at + 8 * nblocks))
+
+
+def _unpack_layered(data: bytes, base_only: bool):
+    """Both LICBITS6 readers.  -> (head with "M1", "base_bytes" and, if slicing, "slice_rows"; [z sub-stream per block];
+    [z escape list per block]; the layers read: [{"y", "y_esc", "y_crc32"}] -- one for the base reader, two for the
+    full one; G).  The base reader takes the whole blob, its prefix blob[:base_bytes] or either with anything behind
+    base_bytes, and looks at nothing there.  CodecError in `_unpack`'s order: a buffer shorter than its header, another
+    magic, a `lanes` word that names no G, a buffer shorter than its tables, lengths that do not add up (`base_bytes`
+    against the tables; for the full reader the total, so it refuses a prefix as truncated), a failing CRC-32 (the
+    base reader: the one at base_bytes - 4 only), a header that cannot be right (0 < M1 < M included), a sub-stream
+    shorter than its 64 states or of odd length, and what the z section refuses."""
+    st = _BITS_HEAD_LAYERED
+    data = bytes(data)
+    if len(data) < st.size + 4:
+        raise CodecError("bitstream is truncated (shorter than its header)")
+    vals = st.unpack_from(data, 0)
+    if vals[0] != BITSTREAM_MAGIC_LAYERED:
+        raise CodecError(f"not a {BITSTREAM_MAGIC_LAYERED.decode()} bitstream (bad magic)")
+    head = dict(zip(_BITS_FIELDS, vals[1:12]))
+    z_len, lanes, R, M1, base_bytes = vals[12:17]
+    B = head["B"]
+    if lanes % RANS_LANES or not RANS_LANES <= lanes <= RANS_LANES * RANS_MAX_GROUPS:
+        raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements multiples of "
+                         f"{RANS_LANES} up to {RANS_LANES * RANS_MAX_GROUPS}")
+    G = lanes // RANS_LANES
+    z_at = st.size + 8 * B
+    base_at = z_at + z_len
+    if B == 0 or len(data) < base_at + 8 * B * G + 4:
+        raise CodecError("bitstream is truncated (per-image tables)")
+    rows = [struct.unpack_from("<2I", data, st.size + 8 * i) for i in range(B)]
+    base_rows, base_cuts = _block_table(data, base_at, B * G)
+    if base_bytes != base_cuts[-1] + 4:
+        raise CodecError("bitstream header is damaged (base_bytes does not match the base layer's tables)")
+    if len(data) < base_bytes:
+        raise CodecError("bitstream is truncated (shorter than its base layer)")
+    sections = [(base_rows, base_cuts)]
+    if not base_only:
+        if len(data) < base_bytes + 8 * B * G + 4:
+            raise CodecError("bitstream is truncated (it ends with its base layer: only the base decodes)"
+                             if len(data) == base_bytes else "bitstream is truncated (enhancement layer table)")
+        enh_rows, enh_cuts = _block_table(data, base_bytes, B * G)
+        if len(data) != enh_cuts[-1] + 4:
+            raise CodecError("bitstream is truncated or has trailing bytes (its length does not match its header)")
+        sections.append((enh_rows, enh_cuts))
+    if zlib.crc32(data[:base_bytes - 4]) & 0xFFFFFFFF != struct.unpack_from("<I", data, base_bytes - 4)[0]:
+        raise CodecError("bitstream is damaged (CRC-32 mismatch in the base layer)")
+    if not base_only:
+        _check_crc_and_head(data, head)
+    else:
+        _check_crc_and_head(data[:base_bytes], head)
+    if not 0 < M1 < head["M"]:
+        raise CodecError("bitstream header is inconsistent (M1 outside 0 < M1 < M)")
+    if any(ln < 4 * RANS_LANES or ln % 2 for sec_rows, _ in sections for ln, _ in sec_rows):
+        raise CodecError("bitstream names a sub-stream shorter than its 64 states or of odd length")
+    head.update(M1=M1, base_bytes=base_bytes)
+    if R >= 1:
+        head["slice_rows"] = R
+    zs, zes = _unpack_z_section(data[z_at:base_at], B * G)
+    layers = []
+    for l, (_, cuts) in enumerate(sections):
+        payload = [data[a:b] for a, b in zip(cuts, cuts[1:])]
+        layers.append({"y": payload[0::2], "y_esc": payload[1::2], "y_crc32": [r[l] for r in rows]})
+    return head, zs, zes, layers, G
+
+
+def unpack_bitstream_layered(data: bytes):
+    """-> (head dict with "M1" and "base_bytes", [z sub-stream per image and group], [z escape list likewise],
+    [base layer, enhancement layer] as {"y", "y_esc", "y_crc32"}, groups, slice_rows or None).  Refuses a prefix."""
+    head, zs, zes, layers, G = _unpack_layered(data, False)
+    return head, zs, zes, layers, G, head.get("slice_rows")
+
+
+def unpack_bitstream_layered_base(data: bytes):
+    """The same from a whole LICBITS6 blob or from its prefix blob[:base_bytes], with the base layer alone in the
+    list; bytes behind base_bytes are not looked at."""
+    head, zs, zes, layers, G = _unpack_layered(data, True)
+    return head, zs, zes, layers, G, head.get("slice_rows")
 
 
 def pack_bitstream(head: Dict, z_bytes: bytes, y_streams, y_crc32) -> bytes:

@@ -47,11 +47,18 @@ checksums, z_hat, y_hat and x_hat are those of `z_coder="range"`, only the z byt
 `ContextCodec.compress_images(images)` is its counterpart: images of different sizes share one gather, one pass through
 the per-pixel layers, one table launch and one launch of each encoder kernel (`lic_rans_encode_pick_ragged`,
 `lic_rans_encode_ragged`); entry i is byte for byte `compress_image(images[i])`.
+
+`ScalableCodec` is the codec of `models.ScalableImageCoding`: base and enhancement latent are two layers (`CodecLayer`)
+with their own rANS sub-streams, the container (LICBITS6) puts the base layer first, and `decompress_base` /
+`decompress_base_image` decode z and the base layer alone.  `_LayeredCodec` holds what it shares with `ContextCodec`,
+the one-layer case: gather, front end and step loop over a list of layers (`lic_ctx_gather_layers`,
+`lic_rans_decode_step_layers`: all layers of a step in one launch each).
 """
 from __future__ import annotations
 
 import ctypes as C
 import functools
+import struct
 import zlib
 import os
 from typing import Dict, List, NamedTuple, Sequence
@@ -64,10 +71,13 @@ from . import functional as F_
 from .bitstream import (BITSTREAM_FAMILIES, BITSTREAM_MAGIC, BITSTREAM_MAGIC_GROUPED,  # noqa: F401
                         BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_SLICED, BITSTREAM_MAGIC_ZRANS, RANS_LANES, RANS_MAX_GROUPS,
                         CodecError,
+                        BITSTREAM_MAGIC_LAYERED, _BITS_HEAD_LAYERED,
                         _BITS_FIELDS, _BITS_HEAD, _BITS_HEAD_RANS, _FORMAT_OF_MAGIC, _FORMAT_ZRANS, _FORMATS,
                         _check_crc_and_head, _format_of_magic,
-                        _groups, _pack, _unpack, pack_bitstream, pack_bitstream_grouped, pack_bitstream_rans,
+                        _groups, _pack, _unpack, pack_bitstream, pack_bitstream_grouped, pack_bitstream_layered,
+                        pack_bitstream_rans,
                         pack_bitstream_sliced, pack_bitstream_zrans, unpack_bitstream, unpack_bitstream_grouped,
+                        unpack_bitstream_layered, unpack_bitstream_layered_base,
                         unpack_bitstream_rans, unpack_bitstream_sliced, unpack_bitstream_zrans)
 
 _CODEC = None
@@ -674,7 +684,226 @@ class _StreamDecoder:
         self.close()
 
 
-class ContextCodec:
+class CodecLayer:
+    """A layer as the codec sees it: a masked context convolution and an entropy-parameter MLP (three 1x1
+    convolutions) over the channels [c0, c0 + M) of the latent, with K mixture components.  `ContextCodec` has one,
+    over all channels; `ScalableCodec` has the base and the enhancement layer.  Everything per-pixel a codec evaluates
+    goes through here, so encoder and decoder of every codec build their tables with the same calls."""
+
+    def __init__(self, model, context: str, mlp: str, c0: int = 0, channels: str = "M"):
+        """`context`, `mlp`, `channels`: the names of the model's attributes that hold the layer's context model, its
+        entropy-parameter MLP and its channel count; only the context model's mask is read here, the rest when used"""
+        self.model, self._context, self._mlp, self.c0, self._channels = model, context, mlp, int(c0), channels
+        mc = self.context_model.masked
+        k = mc.kernel_size[0]
+        self.taps = [(r, s) for r in range(k) for s in range(k) if (mc._tap_mask >> (r * k + s)) & 1]
+        self.k, self.pad = k, mc.padding[0]
+        # the wavefront schedule (`wavefront`) needs every live tap strictly earlier: ds + (pad + 1) * dr < 0
+        if any((s - self.pad) + (self.pad + 1) * (r - self.pad) >= 0 for (r, s) in self.taps):
+            raise CodecError("context mask is not causal in raster order")
+
+    context_model = property(lambda self: getattr(self.model, self._context))
+    entropy_parameters = property(lambda self: getattr(self.model, self._mlp))
+    M = property(lambda self: int(getattr(self.model, self._channels)))
+    K = property(lambda self: int(self.model.K))
+
+    @property
+    def cctx(self) -> int:
+        """columns the context GEMM writes in front of psi in the first 1x1 layer's input"""
+        return self.context_model.masked.out_channels
+
+    def ctx_weight(self):
+        mc = self.context_model.masked
+        w = (mc.weight * mc.mask).detach()                                     # [2M, M, k, k]
+        cols = [w[:, :, r, s] for (r, s) in self.taps]                         # each [2M, M]
+        return torch.cat(cols, dim=1).reshape(w.shape[0], -1, 1, 1).contiguous(), mc.bias.detach()
+
+    def prepack(self):
+        """The four per-pixel layers (context GEMM + the 1x1 MLP) with their weights packed ONCE: the decoder
+        runs them h*w times; packing per call moved ~10 MB per latent pixel."""
+        wg, bg = self.ctx_weight()
+        net = self.entropy_parameters.net
+        convs = [net[0], net[2], net[4]]
+        slopes = [net[1].negative_slope, net[3].negative_slope]
+        layers = [(F_.pack_conv_weight(wg), bg, wg.shape[0], False, 0.01)]
+        for i, c in enumerate(convs):
+            if c.kernel_size != (1, 1):
+                raise CodecError("entropy-parameter layers are expected to be 1x1 convolutions")
+            layers.append((F_.pack_conv_weight(c.weight), None if c.bias is None else c.bias.detach(), c.out_channels,
+                           i < 2, slopes[i] if i < 2 else 0.01))
+        return layers
+
+    def act_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None) -> torch.Tensor:
+        """windows [N, 12M, 1, 1], psi_px [N, 2M, 1, 1] -> the activated entropy parameters [N, G*K*M, 1, 1].
+        `comb` [N, 4M]: the input of the first 1x1 layer with psi already in its last 2M columns (`_gather`), instead
+        of psi_px; the context GEMM writes its 2M columns beside them, so no `cat` (Models.py:73) runs."""
+        wp, b, co, _, _ = layers[0]
+        N = windows.shape[0]
+        if comb is None:
+            comb = torch.empty((N, co + psi_px.shape[1]), device=windows.device, dtype=torch.float32)
+            comb[:, co:] = psi_px.reshape(N, -1)
+        comb = comb.view(N, 1, 1, -1)
+        F_.conv2d_prepacked(windows, wp, b, co, 1, pin_tile=True, out=comb[..., :co])
+        x = comb.permute(0, 3, 1, 2)
+        for wp, b, co, leaky, slope in layers[1:]:
+            x = F_.conv2d_prepacked(x, wp, b, co, 1, leaky=leaky, slope=slope, pin_tile=True)
+        return F_.entropy_params_activation(x, self.M, self.K)
+
+    def params_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor, y_W: int):
+        """`act_at`'s arguments -> (center [N, M], tables [N*M, S+1]) on the device"""
+        return gmm_tables(self.act_at(windows, psi_px, layers, comb), self.M, self.K, y_W)
+
+
+class _LayeredCodec:
+    """What `ContextCodec` (one layer over all channels) and `ScalableCodec` (two layers) share: the gather of every
+    layer's rows from the one latent plane, the per-step front end and the rANS step loop, written once over
+    `self.layers`.  A single layer that covers the whole plane goes through `lic_ctx_gather` and
+    `lic_rans_decode_step_groups`; anything else through `lic_ctx_gather_layers` and `lic_rans_decode_step_layers`,
+    one launch each for all layers of a step."""
+
+    # False: the layered entries are launched once per layer instead of once per step (tools/bench_codec.py measures
+    # what the merged launches save); bytes and results are the same
+    merge_layers = True
+
+    def _set_layers(self, layers):
+        """the codec's layers; they share one wavefront schedule and one tap table, so their masks must agree"""
+        self.layers = list(layers)
+        first = self.layers[0]
+        for ly in self.layers[1:]:
+            if (ly.taps, ly.k, ly.pad) != (first.taps, first.k, first.pad):
+                raise CodecError("the layers' context masks differ in their live taps: one gather and one wavefront "
+                                 "schedule serve all layers, so they must agree")
+        self.taps, self.k, self.pad = first.taps, first.k, first.pad
+
+    @staticmethod
+    def _whole_plane(layers, y_pix: int) -> bool:
+        return len(layers) == 1 and layers[0].c0 == 0 and layers[0].M == y_pix
+
+    def _wavefront(self, h: int, w: int, slice_rows: int = None):
+        """Decode schedule.  With mask type A a pixel (i, j) sees rows above it up to column j + pad and its own
+        row up to j - 1, so for t = j + (pad + 1) * i every pixel's context lies in steps < t: the pixels of one
+        step are independent and go through the GPU as one batch -- w + (pad + 1)(h - 1) dependent steps
+        instead of h * w (141 instead of 1536 for a 512x768 image).  With slices of `slice_rows` rows i counts
+        inside the pixel's slice (`wavefront`).  Returns [(rows, cols)] per step, rows
+        ascending; encoder and decoder order the symbols step by step, pixel by pixel, channel by channel."""
+        return wavefront(h, w, self.pad, slice_rows)
+
+    def _taps_on(self, dev) -> torch.Tensor:
+        """the live taps as (dr, ds) int32 pairs on `dev`, uploaded once"""
+        if getattr(self, "_taps_dev", None) is None or self._taps_dev.device != dev:
+            self._taps_dev = torch.tensor([(r - self.pad, s - self.pad) for (r, s) in self.taps], dtype=torch.int32,
+                                          device=dev)
+        return self._taps_dev
+
+    def _gather_layers(self, y: torch.Tensor, y_pix: int, geometry, h: int, w: int, pix: torch.Tensor, slice_rows,
+                       psi_flat=None, layers=None):
+        """One gather launch for all `layers` (default: the codec's).  y: fp32 latents of B images with y_pix channels
+        per pixel, pixel (i, j) of image b at float b * batch + origin + i * row + j * y_pix for geometry = (batch,
+        row, origin); pix: int64 raster indices (device) of the n pixels wanted; psi_flat [B, h*w, 2M] or None.
+        -> per layer (windows [B*n, 12 M_l, 1, 1] with zeros for taps outside the image or the pixel's slice,
+                      comb [B*n, cctx_l + 2M] whose last 2M columns hold the pixels' psi, the first cctx_l still
+                      unwritten; None without psi)"""
+        layers = self.layers if layers is None else layers
+        B, n, nt, dev = y.shape[0], pix.numel(), len(self.taps), y.device
+        taps = self._taps_on(dev)
+        cpsi = 0 if psi_flat is None else psi_flat.shape[2]
+        outs = []
+        for ly in layers:
+            win = torch.empty((B * n, nt * ly.M, 1, 1), device=dev, dtype=torch.float32)
+            comb = None if psi_flat is None else torch.empty((B * n, ly.cctx + cpsi), device=dev, dtype=torch.float32)
+            outs.append((win, comb))
+        batch, row, origin = geometry
+        R = h if slice_rows is None else min(slice_rows, h)
+        first_col = lambda ly, comb: None if comb is None else C.c_void_p(comb.data_ptr() + 4 * ly.cctx)
+        if self._whole_plane(layers, y_pix):
+            (win, comb), ly = outs[0], layers[0]
+            L.check(L.load().lic_ctx_gather(
+                F_._ptr(y), batch, row, y_pix, origin, B, h, w, ly.M, F_._ptr(taps), nt, R, F_._ptr(pix), n, F_._ptr(win),
+                F_._ptr(psi_flat), cpsi, first_col(ly, comb), 0 if comb is None else comb.shape[1], L.CTX_AUTO,
+                F_._stream()), "lic_ctx_gather")
+            return outs
+        if len(layers) > L.MAX_LAYERS:
+            raise CodecError(f"{len(layers)} layers: the layered kernels take {L.MAX_LAYERS} at the most")
+        table = (L.CtxLayer * len(layers))()
+        for t, ly, (win, comb) in zip(table, layers, outs):
+            t.win, t.comb, t.comb_ld = win.data_ptr(), first_col(ly, comb), 0 if comb is None else comb.shape[1]
+            t.c0, t.M = ly.c0, ly.M
+        # merge_layers False: one launch per layer, for tools/bench_codec.py's comparison; the same bytes
+        for rows in ([table] if self.merge_layers else [(L.CtxLayer * 1)(t) for t in table]):
+            L.check(L.load().lic_ctx_gather_layers(
+                F_._ptr(y), batch, row, y_pix, origin, B, h, w, F_._ptr(taps), nt, R, F_._ptr(pix), n, F_._ptr(psi_flat),
+                cpsi, rows, len(rows), L.CTX_AUTO, F_._stream()), "lic_ctx_gather_layers")
+        return outs
+
+    def _windows_layers(self, y_hat: torch.Tensor, slice_rows: int = None, psi: torch.Tensor = None, layers=None):
+        """[B, M, h, w] -> `_gather_layers`' result for every pixel of every image, in raster order"""
+        F_._require_cuda(y_hat, psi)
+        B, M, h, w = y_hat.shape
+        y = F_._nhwc(y_hat)
+        pix = torch.arange(h * w, device=y.device, dtype=torch.int64)
+        return self._gather_layers(y, M, (h * w * M, w * M, 0), h, w, pix, slice_rows,
+                                   None if psi is None else F_._nhwc(psi).view(B, h * w, -1), layers)
+
+    def _step_front_end(self, steps, yflat, psi, slice_rows=None, layers=None):
+        """What the decoders do per wavefront step before their coder runs.  Here, once: the layers are packed and
+        one array uploaded, the raster index and the index into yflat of every step's pixels.  Then, per step of
+        `steps` (`_wavefront`) as the returned generator is advanced: one gather of every layer's windows from `yflat`
+        (the zero-framed latents [B, (h+2p)(w+2p), y_pix], which the coder fills in between) and of the pixels'
+        columns of `psi` [B, 2M, h, w], then per layer the per-pixel layers and the table kernel
+        -> (n pixels, their n indices into yflat, [(center [B*n, M_l], tables [B*n*M_l, S+1]) per layer])"""
+        layers = self.layers if layers is None else layers
+        B, y_pix, p = yflat.shape[0], yflat.shape[2], self.pad
+        h, w = psi.shape[2], psi.shape[3]
+        packed = [ly.prepack() for ly in layers]
+        psi_flat = F_._nhwc(psi).view(B, h * w, -1)                                       # [B, h*w, 2M]
+        Wp = w + 2 * p
+        idx = torch.from_numpy(_step_indices(steps, w, p)).to(yflat.device)
+        geometry = (yflat.shape[1] * y_pix, Wp * y_pix, (p * Wp + p) * y_pix)
+
+        def run():
+            off = 0
+            for ii, _ in steps:
+                n = len(ii)
+                rows = self._gather_layers(yflat, y_pix, geometry, h, w, idx[0, off:off + n], slice_rows, psi_flat, layers)
+                yield n, idx[1, off:off + n], [ly.params_at(win, None, pk, comb, self.y_W)
+                                               for ly, pk, (win, comb) in zip(layers, packed, rows)]
+                off += n
+        return run()
+
+    def _run_steps(self, front, yflat, blocks, G: int, layers=None):
+        """The step loop of the rANS coder: every step of `front` (`_step_front_end`: gather -> per-pixel layers +
+        tables) ends in ONE decode launch for all layers, which writes the decoded values into `yflat` where the next
+        gather reads them.  Nothing in the loop waits for the device.  blocks: the six staging arguments
+        (`_RansStaging.upload`), one block per layer, image and group, layer-major."""
+        layers = self.layers if layers is None else layers
+        nimg, npad, y_pix = yflat.shape
+        lib = L.load()
+        if self._whole_plane(layers, y_pix):
+            for n, own, ((center, tables),) in front:
+                L.check(lib.lic_rans_decode_step_groups(*blocks, F_._ptr(tables), F_._ptr(center), nimg, G, n, y_pix,
+                                                        self.y_W, F_._ptr(own), F_._ptr(yflat), npad, F_._stream()),
+                        "lic_rans_decode_step_groups")
+            return
+        table = (L.RansLayer * len(layers))()
+        s, s_off, s_len, e, e_off, state = blocks
+        per = nimg * G                                                      # blocks of one layer
+        shift = lambda p, l, size: C.c_void_p(p.value + l * per * size)
+        for n, own, params in front:
+            for t, ly, (center, tables) in zip(table, layers, params):
+                t.tables, t.center, t.c0, t.M = tables.data_ptr(), center.data_ptr(), ly.c0, ly.M
+            if self.merge_layers:
+                L.check(lib.lic_rans_decode_step_layers(*blocks, table, len(layers), nimg, G, n, self.y_W, F_._ptr(own),
+                                                        F_._ptr(yflat), npad, y_pix, F_._stream()),
+                        "lic_rans_decode_step_layers")
+                continue
+            for l, t in enumerate(table):                                   # one launch per layer (bench_codec.py)
+                L.check(lib.lic_rans_decode_step_layers(
+                    s, shift(s_off, l, 8), shift(s_len, l, 8), e, shift(e_off, l, 8),
+                    shift(state, l, 4 * L.RANS_STATE_WORDS), (L.RansLayer * 1)(t), 1, nimg, G, n, self.y_W, F_._ptr(own),
+                    F_._ptr(yflat), npad, y_pix, F_._stream()), "lic_rans_decode_step_layers")
+
+
+class ContextCodec(_LayeredCodec):
     """compress(x) -> byte strings, decompress(strings) -> x_hat, through the model's masked-conv
     context (ContextModels.py:3-36): the parameters of pixel (i, j) of y depend on the already decoded
     pixels above / left of it, so decoding is serial -- but only along a wavefront: pixels with equal
@@ -748,73 +977,23 @@ class ContextCodec:
         self.slice_rows = None if slice_rows is None else _slice_rows(slice_rows)
         if self.slice_rows is not None and coder != "rans":
             raise CodecError(f"slice_rows={self.slice_rows} needs coder='rans': the {coder!r} coder has no sliced format")
-        mc = model.context_model.masked
-        k = mc.kernel_size[0]
-        self.taps = [(r, s) for r in range(k) for s in range(k) if (mc._tap_mask >> (r * k + s)) & 1]
-        self.k, self.pad = k, mc.padding[0]
-        # the wavefront schedule (_wavefront) needs every live tap strictly earlier: ds + (pad + 1) * dr < 0
-        if any((s - self.pad) + (self.pad + 1) * (r - self.pad) >= 0 for (r, s) in self.taps):
-            raise CodecError("context mask is not causal in raster order")
-
-    def _wavefront(self, h: int, w: int, slice_rows: int = None):
-        """Decode schedule.  With mask type A a pixel (i, j) sees rows above it up to column j + pad and its own
-        row up to j - 1, so for t = j + (pad + 1) * i every pixel's context lies in steps < t: the pixels of one
-        step are independent and go through the GPU as one batch -- w + (pad + 1)(h - 1) dependent steps
-        instead of h * w (141 instead of 1536 for a 512x768 image).  With slices of `slice_rows` rows i counts
-        inside the pixel's slice (`wavefront`).  Returns [(rows, cols)] per step, rows
-        ascending; encoder and decoder order the symbols step by step, pixel by pixel, channel by channel."""
-        return wavefront(h, w, self.pad, slice_rows)
+        # the one-layer case of `_LayeredCodec`: all M channels, the model's one context model and MLP
+        self._set_layers([CodecLayer(model, "context_model", "entropy_parameters")])
 
     def _ctx_weight(self):
-        mc = self.model.context_model.masked
-        w = (mc.weight * mc.mask).detach()                                     # [2M, M, k, k]
-        cols = [w[:, :, r, s] for (r, s) in self.taps]                         # each [2M, M]
-        return torch.cat(cols, dim=1).reshape(w.shape[0], -1, 1, 1).contiguous(), mc.bias.detach()
+        return self.layers[0].ctx_weight()
 
     def _prepack(self):
-        """The four per-pixel layers (context GEMM + the 1x1 MLP) with their weights packed ONCE: the decoder
-        runs them h*w times; packing per call moved ~10 MB per latent pixel."""
-        m = self.model
-        wg, bg = self._ctx_weight()
-        net = m.entropy_parameters.net
-        convs = [net[0], net[2], net[4]]
-        slopes = [net[1].negative_slope, net[3].negative_slope]
-        layers = [(F_.pack_conv_weight(wg), bg, wg.shape[0], False, 0.01)]
-        for i, c in enumerate(convs):
-            if c.kernel_size != (1, 1):
-                raise CodecError("entropy-parameter layers are expected to be 1x1 convolutions")
-            layers.append((F_.pack_conv_weight(c.weight), None if c.bias is None else c.bias.detach(), c.out_channels,
-                           i < 2, slopes[i] if i < 2 else 0.01))
-        return layers
+        """the per-pixel layers of the codec's one layer, packed once (`CodecLayer.prepack`)"""
+        return self.layers[0].prepack()
 
     def _act_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None) -> torch.Tensor:
-        """windows [N, 12M, 1, 1], psi_px [N, 2M, 1, 1] -> the activated entropy parameters [N, G*K*M, 1, 1].
-        `comb` [N, 4M]: the input of the first 1x1 layer with psi already in its last 2M columns (`_gather`), instead
-        of psi_px; the context GEMM writes its 2M columns beside them, so no `cat` (Models.py:73) runs."""
-        m = self.model
-        wp, b, co, _, _ = layers[0]
-        N = windows.shape[0]
-        if comb is None:
-            comb = torch.empty((N, co + psi_px.shape[1]), device=windows.device, dtype=torch.float32)
-            comb[:, co:] = psi_px.reshape(N, -1)
-        comb = comb.view(N, 1, 1, -1)
-        F_.conv2d_prepacked(windows, wp, b, co, 1, pin_tile=True, out=comb[..., :co])
-        x = comb.permute(0, 3, 1, 2)
-        for wp, b, co, leaky, slope in layers[1:]:
-            x = F_.conv2d_prepacked(x, wp, b, co, 1, leaky=leaky, slope=slope, pin_tile=True)
-        return F_.entropy_params_activation(x, m.M, m.K)
+        """`CodecLayer.act_at` of the codec's one layer; `layers` is what `_prepack` gave"""
+        return self.layers[0].act_at(windows, psi_px, layers, comb)
 
     def _params_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None):
         """`_act_at`'s arguments -> (center [N, M], tables [N*M, S+1]) on the device"""
-        m = self.model
-        return gmm_tables(self._act_at(windows, psi_px, layers, comb), m.M, m.K, self.y_W)
-
-    def _taps_on(self, dev) -> torch.Tensor:
-        """the live taps as (dr, ds) int32 pairs on `dev`, uploaded once"""
-        if getattr(self, "_taps_dev", None) is None or self._taps_dev.device != dev:
-            self._taps_dev = torch.tensor([(r - self.pad, s - self.pad) for (r, s) in self.taps], dtype=torch.int32,
-                                          device=dev)
-        return self._taps_dev
+        return self.layers[0].params_at(windows, psi_px, layers, comb, self.y_W)
 
     def _gather_ragged(self, yflat: torch.Tensor, images: torch.Tensor, row_image: torch.Tensor, row_pix: torch.Tensor,
                        psiflat: torch.Tensor, cpsi: int):
@@ -837,20 +1016,7 @@ class ContextCodec:
         of the n pixels wanted; psi_flat [B, h*w, 2M] or None.
         -> (windows [B*n, 12M, 1, 1] with zeros for taps outside the image or the pixel's slice,
             comb [B*n, 4M] whose last 2M columns hold the pixels' psi, the first 2M still unwritten; None without psi)"""
-        B, M, n, nt, dev = y.shape[0], self.model.M, pix.numel(), len(self.taps), y.device
-        self._taps_on(dev)
-        win = torch.empty((B * n, nt * M, 1, 1), device=dev, dtype=torch.float32)
-        comb = cpsi = None
-        if psi_flat is not None:
-            cpsi, cctx = psi_flat.shape[2], self.model.context_model.masked.out_channels
-            comb = torch.empty((B * n, cctx + cpsi), device=dev, dtype=torch.float32)
-        batch, row, origin = geometry
-        L.check(L.load().lic_ctx_gather(
-            F_._ptr(y), batch, row, M, origin, B, h, w, M, F_._ptr(self._taps_dev), nt,
-            h if slice_rows is None else min(slice_rows, h), F_._ptr(pix), n, F_._ptr(win), F_._ptr(psi_flat), cpsi or 0,
-            None if comb is None else C.c_void_p(comb.data_ptr() + 4 * cctx), 0 if comb is None else comb.shape[1],
-            L.CTX_AUTO, F_._stream()), "lic_ctx_gather")
-        return win, comb
+        return self._gather_layers(y, self.model.M, geometry, h, w, pix, slice_rows, psi_flat)[0]
 
     def _windows_all(self, y_hat: torch.Tensor, slice_rows: int = None, psi: torch.Tensor = None):
         """[B, M, h, w] -> [B*h*w, 12M, 1, 1]: the live taps of every pixel (zeros outside the image and, with
@@ -1251,7 +1417,7 @@ class ContextCodec:
         tabs_np, c_np, vals_np = tabs_host.numpy().view(np.uint32), c_host.numpy(), vals_host.numpy()
         decs = [_StreamDecoder(s) for s in strings["y"]]
         try:
-            for n, own, center, tables in front:
+            for n, own, ((center, tables),) in front:
                 tabs_host[:, :n * M].copy_(tables.view(B, n * M, S1), non_blocking=True)
                 c_host[:, :n * M].copy_(center.view(B, n * M), non_blocking=True)
                 torch.cuda.current_stream().synchronize()
@@ -1263,49 +1429,19 @@ class ContextCodec:
                 d.close()
         return self._finish(strings, ypad, z_hat, shape)
 
-    def _step_front_end(self, steps, yflat, psi, slice_rows=None):
-        """What both decoders do per wavefront step before their coder runs.  Here, once: the layers are packed and
-        one array uploaded, the raster index and the index into yflat of every step's pixels.  Then, per step of
-        `steps` (`_wavefront`) as the returned generator is advanced: one `lic_ctx_gather` of the windows from `yflat`
-        (the zero-framed latents [B, (h+2p)(w+2p), M], which the coder fills in between) and of the pixels' columns
-        of `psi` [B, 2M, h, w], the per-pixel layers and the table kernel
-        -> (n pixels, their n indices into yflat, center [B*n, M], tables [B*n*M, S+1])"""
-        B, M, p = yflat.shape[0], yflat.shape[2], self.pad
-        h, w = psi.shape[2], psi.shape[3]
-        layers = self._prepack()
-        psi_flat = F_._nhwc(psi).view(B, h * w, -1)                                       # [B, h*w, 2M]
-        Wp = w + 2 * p
-        idx = torch.from_numpy(_step_indices(steps, w, p)).to(yflat.device)
-        geometry = (yflat.shape[1] * M, Wp * M, (p * Wp + p) * M)
-
-        def run():
-            off = 0
-            for ii, _ in steps:
-                n = len(ii)
-                win, comb = self._gather(yflat, geometry, h, w, idx[0, off:off + n], slice_rows, psi_flat)
-                yield (n, idx[1, off:off + n]) + self._params_at(win, None, layers, comb)
-                off += n
-        return run()
-
     def _decode_y_rans(self, strings, front, yflat, staged=None):
-        """The step loop of the "rans" coder: streams, escape lists and state blocks go up once, then every step of
-        `front` (`_step_front_end`: gather -> per-pixel layers + tables) ends in lic_rans_decode_step_groups, which
-        writes the decoded values into `yflat` where the next gather reads them.  Nothing in the loop waits for the
+        """The step loop of the "rans" coder (`_run_steps`): streams, escape lists and state blocks go up once, then
+        every step of `front` ends in lic_rans_decode_step_groups.  Nothing in the loop waits for the
         device; the state blocks (error words, cursors, final states) come back once, after the last step.  One block
-        per image and group (`strings["groups"]`, 1 if absent), image-major; below B counts blocks.  `staged`: the
+        per image and group (`strings["groups"]`, 1 if absent), image-major.  `staged`: the
         staging `decompress` has already uploaded, with the z blocks behind the y blocks (z_coder="rans")."""
-        nimg, npad, M = yflat.shape
         G = _groups(strings.get("groups", 1))
         if staged is None:
-            staged = _RansStaging(strings["y"], strings.get("y_esc"), nimg, G)
+            staged = _RansStaging(strings["y"], strings.get("y_esc"), yflat.shape[0], G)
             blocks = staged.upload(yflat.device)
         else:
             blocks = staged.blocks_from(0)
-        lib = L.load()
-        for n, own, center, tables in front:
-            L.check(lib.lic_rans_decode_step_groups(*blocks, F_._ptr(tables), F_._ptr(center), nimg, G, n, M, self.y_W,
-                                                    F_._ptr(own), F_._ptr(yflat), npad, F_._stream()),
-                    "lic_rans_decode_step_groups")
+        self._run_steps(front, yflat, blocks, G)
         staged.check()
 
     def _finish(self, strings, ypad, z_hat, shape) -> Dict:
@@ -1617,3 +1753,242 @@ class ContextCodec:
                                    [f"blob {i}" for i in range(len(opened))])
         return [F_.crop_window(out["x_hat"], head["top"], head["left"], head["H"], head["W"])
                 for out, (head, _) in zip(outs, opened)]
+
+
+class ScalableCodec(_LayeredCodec):
+    """The bitstream of `models.ScalableImageCoding`: the base latent y1 (the model's first `base_channels` channels)
+    and the enhancement latent y2 travel as separate, separately decodable bytes, so a vision client downloads and
+    decodes z and y1 and stops there (`decompress_base`, `decompress_base_image`).
+
+    Two layers (`CodecLayer`): layer l's tables come from `context_model_l` on y_l ALONE plus the shared psi, so layer 0
+    never reads y2, and layer l codes its symbols in wavefront step order, pixel by pixel, over its own M_l channels --
+    exactly what a one-layer codec over those channels does.  rANS only: every layer's y as "rANS-64 x G" sub-streams
+    of its own, z as rANS sub-streams (`ContextCodec(z_coder="rans")`'s), groups and slice_rows as there.  The decode
+    loop runs both layers' steps together: per step ONE gather (`lic_ctx_gather_layers`) from the one M-channel plane
+    and the one psi, the per-pixel layers and tables per layer, and ONE decode launch (`lic_rans_decode_step_layers`)
+    whose waves of both layers run side by side.  A base-only decode is the one-layer loop over an M1-channel plane.
+    `encoder`: "device" (the default) or "host" (`rans_encode_grouped` from tables copied back); the same bytes.
+
+    `compress` returns strings with `layers` = [{"y": [B*G], "y_esc": [B*G], "y_crc32": [B]}, the same for layer 1],
+    `z`, `z_esc`, `z_coder`, `coder`, and `groups` / `slice_rows` when set; `bpp_coded` and `bpp_coded_base` count the
+    LICBITS6 container (bitstream.py) that `compress_image` writes, header and checksums included: all of it, and its
+    first `base_bytes` (header, z and layer 0).  Several images are coded one after the other (`compress_images`,
+    `decompress_images`); a merged step loop for layered blobs does not exist."""
+
+    def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, encoder: str = "device", groups: int = 1,
+                 slice_rows: int = None):
+        from .models import ScalableImageCoding
+        if not isinstance(model, ScalableImageCoding):
+            raise CodecError(f"ScalableCodec codes a ScalableImageCoding model, not a {type(model).__name__}: "
+                             "the one-layer models have ContextCodec")
+        if encoder not in ENCODERS:
+            raise CodecError(f"unknown encoder {encoder!r}: expected one of {ENCODERS}")
+        if int(z_S) < 2:
+            raise CodecError(f"z_S = {int(z_S)}: the rANS coder of z needs a window of at least 2 symbols")
+        if int(y_W) < 1:
+            raise CodecError(f"y_W = {int(y_W)}: the window half-width must be at least 1")
+        if int(y_W) > RANS_MAX_W:
+            raise CodecError(f"y_W = {int(y_W)}: the rANS coder takes windows of 1 to {RANS_MAX_W} (the limit of its "
+                             "device kernels)")
+        self.model, self.z_lo, self.z_S, self.y_W, self.encoder = model, int(z_lo), int(z_S), int(y_W), encoder
+        self.coder = self.z_coder = "rans"
+        self.groups = _groups(groups)
+        self.slice_rows = None if slice_rows is None else _slice_rows(slice_rows)
+        self._set_layers([CodecLayer(model, "context_model_1", "entropy_parameters_1", 0, "M1"),
+                          CodecLayer(model, "context_model_2", "entropy_parameters_2", model.M1, "M2")])
+
+    # the z coder, the device y encoder and the family id do not know how many layers y has: ContextCodec's serve
+    _z_symbols = staticmethod(ContextCodec._z_symbols)
+    _encode_z, _decode_z = ContextCodec._encode_z, ContextCodec._decode_z
+    _encode_y_device, _family = ContextCodec._encode_y_device, ContextCodec._family
+
+    @torch.no_grad()
+    def compress(self, x: torch.Tensor) -> Dict:
+        m, G = self.model, self.groups
+        if x.dim() != 4 or x.shape[2] % 64 or x.shape[3] % 64:
+            raise CodecError("expected a [B,3,H,W] tensor with H and W multiples of 64 (compress_image pads any size)")
+        if m.use_step_prep and x.is_cuda:
+            m.step_prep().run()
+        y = m.encoder(x)
+        z_in, y_in = F_.quantize(m.hyper_encoder(y), None, False), F_.quantize(y, None, False).contiguous()
+        B, M, h, w = y_in.shape
+        z_bytes, z_esc = self._encode_z(list(self._z_symbols(z_in)))
+        psi = m.hyper_decoder(z_in).float()
+        steps = self._wavefront(h, w, self.slice_rows)
+        order = np.concatenate([ii * w + jj for ii, jj in steps])
+        y_sym_all = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
+        logp = m.factorized_entropy_model.likelihood_and_log(z_in)[1].double().sum()
+        coded = []
+        for ly, (win, comb) in zip(self.layers, self._windows_layers(y_in, self.slice_rows, psi)):
+            act = ly.act_at(win, None, ly.prepack(), comb)
+            center, tables = gmm_tables(act, ly.M, ly.K, self.y_W)
+            y_sym = y_sym_all[:, ly.c0:ly.c0 + ly.M].contiguous()
+            step_len = [len(ii) * ly.M for ii, _ in steps]
+            if self.encoder == "device":
+                streams, escs = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, ly.M)
+            else:
+                perm = torch.from_numpy(order).to(y_in.device)
+                idx = (y_sym - center + self.y_W).view(B, h * w, ly.M)[:, perm].cpu().numpy().reshape(B, h * w * ly.M)
+                tabs = tables.view(B, h * w, ly.M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * ly.M, -1)
+                pairs = [rans_encode_grouped(tabs[b], idx[b], step_len, G) for b in range(B)]
+                streams, escs = [s for p in pairs for s in p[0]], [e for p in pairs for e in p[1]]
+            crc = [zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
+                   for a in y_sym.reshape(B, h * w * ly.M).cpu().numpy().astype(np.int32)]
+            coded.append({"y": streams, "y_esc": escs, "y_crc32": crc})
+            y_l = y_in[:, ly.c0:ly.c0 + ly.M]
+            logp = logp + m.conditional.packed_likelihood_and_log(
+                y_l, act.reshape(B, h, w, -1).permute(0, 3, 1, 2), ly.K)[1].double().sum()
+        strings = {"layers": coded, "z": z_bytes, "z_esc": z_esc, "z_coder": "rans", "coder": "rans"}
+        if G > 1:
+            strings["groups"] = G
+        if self.slice_rows is not None:
+            strings["slice_rows"] = self.slice_rows
+        npix = B * x.shape[2] * x.shape[3]
+        blob = self._pack_image(strings, B, x.shape[2], x.shape[3], 0, 0)      # the ledger counts the container
+        base_bytes = self.base_bytes_of(blob)
+        return {"strings": strings, "shape": (B, M, h, w), "z_shape": tuple(z_in.shape),
+                "bpp_coded": 8.0 * len(blob) / npix, "bpp_coded_base": 8.0 * base_bytes / npix,
+                "bpp_est": float(-logp / np.log(2.0) / npix), "y_in": y_in, "z_in": z_in}
+
+    def _decode(self, strings: Dict, shape, z_shape, nlayers: int):
+        """z, then the first `nlayers` layers in one step loop -> (ypad [B, h+2p, w+2p, channels of those layers]
+        zero-framed, z_hat).  Strings of later layers are not touched."""
+        m, p = self.model, self.pad
+        B, M, h, w = shape
+        _, _, h4, w4 = z_shape
+        if M != m.M or z_shape[0] != B:
+            raise CodecError(f"shape names {M} latent channels and z_shape {z_shape[0]} images; this model has {m.M} "
+                             f"channels and shape {B} images")
+        dev = next(m.parameters()).device
+        use = self.layers[:nlayers]
+        G = _groups(strings.get("groups", 1))
+        R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
+        coded = strings.get("layers")
+        if not isinstance(coded, (list, tuple)) or len(coded) < nlayers:
+            raise CodecError(f"the strings hold {0 if not isinstance(coded, (list, tuple)) else len(coded)} layers; "
+                             f"{nlayers} are to be decoded")
+        ys, escs = [], []
+        for l, c in enumerate(coded[:nlayers]):
+            if c.get("y_esc") is None or len(c["y"]) != B * G or len(c["y_esc"]) != B * G or len(c["y_crc32"]) != B:
+                raise CodecError(f"layer {l}: one y stream and one escape list per image and group and one checksum "
+                                 "per image expected")
+            ys += list(c["y"])
+            escs += list(c["y_esc"])
+        # layer-major blocks, the z blocks behind them: one upload, one read-back
+        staged = _stage_y_and_z(ys, escs, nlayers * B, strings["z"], strings.get("z_esc"), B, G,
+                                lambda i: f"image {i % B}, layer {i // B}", _image_name)
+        blocks = staged.upload(dev)
+        n = h4 * w4 * M
+        zflat = self._decode_z(staged, nlayers * B * G, [(self.z_lo, self.z_S)] * B, [n] * B, [b * n for b in range(B)],
+                               B * n, dev)
+        z_hat = zflat.view(B, h4, w4, M).permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
+        psi = m.hyper_decoder(z_hat).float()
+        y_pix = sum(ly.M for ly in use)                    # the layers are consecutive from channel 0
+        ypad = torch.zeros((B, h + 2 * p, w + 2 * p, y_pix), device=dev, dtype=torch.float32)
+        yflat = ypad.view(B, -1, y_pix)
+        front = self._step_front_end(self._wavefront(h, w, R), yflat, psi, R, use)
+        self._run_steps(front, yflat, blocks, G, use)
+        staged.check()
+        got = ypad[:, p:p + h, p:p + w, :].round().to(torch.int32).cpu().numpy()
+        for l, (ly, c) in enumerate(zip(use, coded)):
+            for b in range(B):
+                sym = np.ascontiguousarray(got[b, :, :, ly.c0:ly.c0 + ly.M])
+                if (zlib.crc32(sym.tobytes()) & 0xFFFFFFFF) != int(c["y_crc32"][b]):
+                    raise CodecError(f"image {b}, layer {l}: decoded latents do not match the encoder's checksum "
+                                     "(encoder and decoder built different probability tables, or the stream is damaged)")
+        return ypad, z_hat
+
+    @torch.no_grad()
+    def decompress(self, strings: Dict, shape, z_shape) -> Dict:
+        """-> {"x_hat", "y_hat", "z_hat", "F_tilde"}: both layers, the picture and the base layer's vision features"""
+        m, p = self.model, self.pad
+        B, M, h, w = shape
+        ypad, z_hat = self._decode(strings, shape, z_shape, 2)
+        y_hat = ypad[:, p:p + h, p:p + w, :].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
+        return {"x_hat": m.decoder(y_hat), "y_hat": y_hat, "z_hat": z_hat, "F_tilde": m.LST(y_hat[:, :m.M1])}
+
+    @torch.no_grad()
+    def decompress_base(self, strings: Dict, shape, z_shape) -> Dict:
+        """-> {"y1_hat", "z_hat", "F_tilde"} from z and layer 0 alone; layer 1's strings may be absent"""
+        m, p = self.model, self.pad
+        B, M, h, w = shape
+        ypad, z_hat = self._decode(strings, shape, z_shape, 1)
+        y1_hat = ypad[:, p:p + h, p:p + w, :].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
+        return {"y1_hat": y1_hat, "z_hat": z_hat, "F_tilde": m.LST(y1_hat)}
+
+    # ---- the LICBITS6 container ---------------------------------------------------------------------
+    def _pack_image(self, s: Dict, B: int, H: int, W: int, top: int, left: int) -> bytes:
+        m = self.model
+        head = {"family": self._family(), "M": m.M, "K": m.K, "z_lo": self.z_lo, "z_S": self.z_S, "y_W": self.y_W,
+                "B": B, "H": H, "W": W, "top": top, "left": left, "M1": m.M1}
+        return pack_bitstream_layered(head, s["z"], s["z_esc"], s["layers"], self.groups, self.slice_rows)
+
+    @torch.no_grad()
+    def compress_image(self, x: torch.Tensor, mode: str = "replicate", align: str = "topleft") -> bytes:
+        """x [B,3,H,W] of ANY size -> one LICBITS6 byte string that `decompress_image` decodes by itself, and whose
+        first `base_bytes` (header word; `base_bytes_of(blob)`) `decompress_base_image` decodes by themselves"""
+        if x.dim() != 4:
+            raise CodecError("expected a [B,3,H,W] tensor")
+        B, _, H, W = x.shape
+        _, _, top, left = F_.pad_geometry(H, W, 64, align)
+        r = self.compress(F_.pad_to_multiple(x, 64, mode, align))
+        return self._pack_image(r["strings"], B, H, W, top, left)
+
+    @staticmethod
+    def base_bytes_of(blob: bytes) -> int:
+        """how many leading bytes of a LICBITS6 blob the base decode needs (from the header alone)"""
+        if len(blob) < _BITS_HEAD_LAYERED.size or bytes(blob[:8]) != BITSTREAM_MAGIC_LAYERED:
+            raise CodecError("not a LICBITS6 bitstream (bad magic or shorter than its header)")
+        return struct.unpack_from("<I", blob, _BITS_HEAD_LAYERED.size - 4)[0]
+
+    def _open_blob(self, data: bytes, base_only: bool):
+        """the host half of the container decoders -> (header, strings, the codec that decodes them).  Refusals, in
+        order: the reader's (bitstream.py), a window the rANS decoders do not take, a model that is not this one."""
+        head, zs, zes, layers, G, R = (unpack_bitstream_layered_base if base_only else unpack_bitstream_layered)(data)
+        if not 2 <= head["z_S"] <= L.RANS_Z_MAX_S:
+            raise CodecError(f"bitstream names z_S = {head['z_S']}; the rANS decoder of z takes windows of 2 to "
+                             f"{L.RANS_Z_MAX_S} symbols")
+        if head["y_W"] > RANS_MAX_W:
+            raise CodecError(f"bitstream names y_W = {head['y_W']}; the rANS decoder takes windows of 1 to {RANS_MAX_W}")
+        m = self.model
+        if (head["family"], head["M"], head["K"], head["M1"]) != (self._family(), m.M, m.K, m.M1):
+            raise CodecError(f"bitstream was written by family {head['family']} with M={head['M']}, M1={head['M1']}, "
+                             f"K={head['K']}; this model is family {self._family()} with M={m.M}, M1={m.M1}, K={m.K}")
+        strings = {"layers": layers, "z": zs, "z_esc": zes, "z_coder": "rans", "coder": "rans"}
+        if G > 1:
+            strings["groups"] = G
+        if R is not None:
+            strings["slice_rows"] = R
+        dec = self
+        if (head["z_lo"], head["z_S"], head["y_W"]) != (self.z_lo, self.z_S, self.y_W):
+            dec = ScalableCodec(m, head["z_lo"], head["z_S"], head["y_W"])
+        return head, strings, dec
+
+    @staticmethod
+    def _shapes(head, M: int):
+        Hp, Wp = -(-head["H"] // 64) * 64, -(-head["W"] // 64) * 64
+        return (head["B"], M, Hp // 16, Wp // 16), (head["B"], M, Hp // 64, Wp // 64)
+
+    @torch.no_grad()
+    def decompress_image(self, data: bytes) -> torch.Tensor:
+        """The inverse of `compress_image`: x_hat [B,3,H,W], cropped back.  CodecError before any GPU work for a bad
+        magic, a truncated buffer -- the base prefix included --, a failing CRC or a header that is not this model's."""
+        head, strings, dec = self._open_blob(data, False)
+        out = dec.decompress(strings, *self._shapes(head, self.model.M))
+        return F_.crop_window(out["x_hat"], head["top"], head["left"], head["H"], head["W"])
+
+    @torch.no_grad()
+    def decompress_base_image(self, data: bytes):
+        """A whole `compress_image` blob or its prefix blob[:base_bytes] -> (y1_hat [B, M1, Hp/16, Wp/16], F_tilde).
+        Nothing behind base_bytes is looked at; damage before it is refused."""
+        head, strings, dec = self._open_blob(data, True)
+        out = dec.decompress_base(strings, *self._shapes(head, self.model.M))
+        return out["y1_hat"], out["F_tilde"]
+
+    def compress_images(self, images: Sequence[torch.Tensor], mode: str = "replicate", align: str = "topleft") -> List[bytes]:
+        """`compress_image` per entry, one after the other (no merged pass for layered blobs)"""
+        return [self.compress_image(x, mode, align) for x in images]
+
+    def decompress_images(self, blobs: Sequence[bytes]) -> List[torch.Tensor]:
+        """`decompress_image` per entry, one after the other (no merged step loop for layered blobs)"""
+        return [self.decompress_image(b) for b in blobs]

@@ -145,6 +145,38 @@ CtxRowParams ctx_row_params(const float* y, const int32_t* taps, const float* ps
   return CtxRowParams{y, taps, psi, win, psi ? comb : nullptr, y_pix, comb_ld, M, nt, psi ? Cpsi : 0};
 }
 
+// ---- the layers of one latent ------------------------------------------------------------------------------------
+// Layer l is lic_ctx_gather on the channel range [c0, c0 + M): row[l].y points at channel c0 of the plane, row[l].M
+// is the layer's width, y_pix stays the plane's.  vec bit l: the layer moves in 16-byte pieces.
+struct CtxLayersParams {
+  CtxRowParams row[LIC_MAX_LAYERS];
+  const int64_t* pix;
+  int64_t y_batch, y_row, y_origin, n, rows;
+  int32_t h, w, R, L;
+  uint32_t vec;
+};
+
+// one workgroup per row walks the row of every layer; the layer loop is unrolled so that the by-value table is read
+// with constant indices
+__global__ __launch_bounds__(256) void ctx_gather_layers_kernel(const CtxLayersParams p) {
+  const int64_t hw = (int64_t)p.h * p.w;
+  for (int64_t row = blockIdx.x; row < p.rows; row += gridDim.x) {
+    const int64_t b = row / p.n, k = row - b * p.n;
+    const int64_t px = p.pix[k];
+    const bool ok = px >= 0 && px < hw;  // a bad index: zeros out, nothing in
+#pragma unroll
+    for (int l = 0; l < LIC_MAX_LAYERS; ++l) {
+      if (l < p.L) {
+        const CtxImage g{b * p.y_batch, p.y_row, p.y_origin, b * hw * p.row[l].Cpsi, p.h, p.w, p.R};
+        if ((p.vec >> l) & 1u)
+          ctx_row<4>(p.row[l], row, ok, g, px);
+        else
+          ctx_row<1>(p.row[l], row, ok, g, px);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 LIC_EXPORT int lic_ctx_gather(const float* y, int64_t y_batch, int64_t y_row, int64_t y_pix, int64_t y_origin,
@@ -221,5 +253,55 @@ LIC_EXPORT int lic_ctx_gather_ragged(const float* y, int64_t y_len, int64_t y_pi
     hipLaunchKernelGGL(ctx_gather_ragged_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(ctx_gather_ragged_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  return lic_check_launch();
+}
+
+LIC_EXPORT int lic_ctx_gather_layers(const float* y, int64_t y_batch, int64_t y_row, int64_t y_pix, int64_t y_origin,
+                                     int32_t B, int32_t h, int32_t w, const int32_t* taps, int32_t nt,
+                                     int32_t slice_rows, const int64_t* pix, int64_t n, const float* psi, int32_t Cpsi,
+                                     const lic_ctx_layer* layers, int32_t L, int32_t path, lic_stream_t stream) {
+  if (!y || !taps || !pix || !layers) return LIC_ERR_INVALID;
+  if (L < 1 || L > LIC_MAX_LAYERS) return LIC_ERR_INVALID;
+  if (B <= 0 || h <= 0 || w <= 0 || n <= 0 || nt < 1 || slice_rows < 1) return LIC_ERR_INVALID;
+  if (y_batch < 0 || y_row < 0 || y_pix < 1 || y_origin < 0) return LIC_ERR_INVALID;
+  if (psi && Cpsi <= 0) return LIC_ERR_INVALID;
+  if (path != LIC_CTX_AUTO && path != LIC_CTX_VECTOR && path != LIC_CTX_ELEMENT) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(psi) | reinterpret_cast<uintptr_t>(taps)) & 3)
+    return LIC_ERR_INVALID;
+  if (reinterpret_cast<uintptr_t>(pix) & 7) return LIC_ERR_INVALID;
+  for (int l = 0; l < L; ++l) {
+    const lic_ctx_layer& a = layers[l];
+    if (!a.win || a.M <= 0 || a.c0 < 0 || (int64_t)a.c0 + a.M > y_pix) return LIC_ERR_INVALID;
+    if (psi && (!a.comb || a.comb_ld < Cpsi)) return LIC_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(a.win) | reinterpret_cast<uintptr_t>(a.comb)) & 3) return LIC_ERR_INVALID;
+    for (int m = 0; m < l; ++m)  // channel ranges must not overlap
+      if (a.c0 < layers[m].c0 + layers[m].M && layers[m].c0 < a.c0 + a.M) return LIC_ERR_INVALID;
+  }
+  // rows and row lengths the kernel's 32-bit piece counters and 64-bit offsets hold
+  if (n > 0x7FFFFFFFL || (int64_t)B * n > (1LL << 40)) return LIC_ERR_UNSUPPORTED;
+  for (int l = 0; l < L; ++l)
+    if ((int64_t)nt * layers[l].M + (psi ? Cpsi : 0) > 0x7FFFFFFFL - 256) return LIC_ERR_UNSUPPORTED;
+  const bool plane_vec = aligned16(y) && y_batch % 4 == 0 && y_row % 4 == 0 && y_pix % 4 == 0 && y_origin % 4 == 0 &&
+                         (!psi || (Cpsi % 4 == 0 && aligned16(psi)));
+  CtxLayersParams p = {};
+  for (int l = 0; l < L; ++l) {
+    const lic_ctx_layer& a = layers[l];
+    const bool can_vec = plane_vec && a.c0 % 4 == 0 && a.M % 4 == 0 && aligned16(a.win) &&
+                         (!psi || (a.comb_ld % 4 == 0 && aligned16(a.comb)));
+    if (path == LIC_CTX_VECTOR && !can_vec) return LIC_ERR_INVALID;
+    if (can_vec && path != LIC_CTX_ELEMENT) p.vec |= 1u << l;
+    p.row[l] = ctx_row_params(y + a.c0, taps, psi, a.win, a.comb, y_pix, a.comb_ld, a.M, nt, Cpsi);
+  }
+  p.pix = pix;
+  p.y_batch = y_batch;
+  p.y_row = y_row;
+  p.y_origin = y_origin;
+  p.n = n;
+  p.rows = (int64_t)B * n;
+  p.h = h;
+  p.w = w;
+  p.R = slice_rows;
+  p.L = L;
+  hipLaunchKernelGGL(ctx_gather_layers_kernel, dim3(ew_grid(p.rows, 1)), dim3(256), 0, (hipStream_t)stream, p);
   return lic_check_launch();
 }

@@ -38,10 +38,10 @@ class _RunningMeans:
         return {name: self._sum[name] / self._n[name] for name in self._sum}
 
 
-class CompressionEvaluator:
-    """Constructor and method signatures are the reference's (Evaluator.py:18, 32, 55, 235)."""
+class _Evaluator:
+    """what the two evaluators share: the distortion metrics of a batch and the result file"""
 
-    def __init__(self, model, dataloader, device, lambda_val, save_dir="./eval_results"):
+    def __init__(self, model, dataloader, device, lambda_val, save_dir):
         self.model, self.dataloader, self.device, self.lambda_val = model, dataloader, device, lambda_val
         self.save_dir = save_dir
         os.makedirs(self.save_dir, exist_ok=True)
@@ -66,6 +66,23 @@ class CompressionEvaluator:
             "PSNR(Y)": _psnr_unit_range(mse_y),
             "MS-SSIM(Y)": float(self._ms_ssim(y_r, y_o, data_range=1.0, size_average=True)),
         }
+
+    def save_results(self, metrics, nb_steps, caption=""):
+        """the reference's result-file name and line format (Evaluator.py:235-242, 486-493)"""
+        lines = [f"Lambda: {self.lambda_val}", f"Trained for: {nb_steps} steps"]
+        lines += [f"{name}: {value:.6f}" for name, value in metrics.items()]
+        path = os.path.join(self.save_dir, f"eval_results_{self.lambda_val}_lambda_{caption}.txt")
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        print(f"Results saved to {path}")
+        return path
+
+
+class CompressionEvaluator(_Evaluator):
+    """Constructor and method signatures are the reference's (Evaluator.py:18, 32, 55, 235)."""
+
+    def __init__(self, model, dataloader, device, lambda_val, save_dir="./eval_results"):
+        super().__init__(model, dataloader, device, lambda_val, save_dir)
 
     def evaluate(self, rd_loss_fn, coded: bool = False, pad_mode=None):
         """`coded=True` (not in the reference, which has no entropy coder) also writes every batch through
@@ -137,12 +154,46 @@ class CompressionEvaluator:
         print("\n".join(f"{name}: {value:.6f}" for name, value in report.items()))
         return report
 
-    def save_results(self, metrics, nb_steps, caption=""):
-        """the reference's result-file name and line format (Evaluator.py:235-242)"""
-        lines = [f"Lambda: {self.lambda_val}", f"Trained for: {nb_steps} steps"]
-        lines += [f"{name}: {value:.6f}" for name, value in metrics.items()]
-        path = os.path.join(self.save_dir, f"eval_results_{self.lambda_val}_lambda_{caption}.txt")
-        with open(path, "w") as f:
-            f.write("\n".join(lines) + "\n")
-        print(f"Results saved to {path}")
-        return path
+
+class VisionCompressionEvaluator(_Evaluator):
+    """The reference's evaluator of `ScalableImageCoding` (Evaluator.py:245-328, 486-493): constructor, `evaluate`,
+    `save_results` and the report keys are its own.  Its aggregation reports 'BPP' = mean(bpp_y) (Evaluator.py:313 takes
+    bpp_y_values), reproduced here under that name as `CompressionEvaluator` reproduces line 81; the intended value is
+    added as 'BPP(total)'.  `coded=True` (not in the reference, which has no coder) writes every batch through
+    `codec.ScalableCodec` and reports the size of the LICBITS6 container as 'BPP(coded)' and of its base prefix -- what
+    a vision client downloads -- as 'BPP(coded base)'."""
+
+    def __init__(self, model, dataloader, device, lambda_val, gamma, save_dir="./eval_results"):
+        super().__init__(model, dataloader, device, lambda_val, save_dir)
+        self.gamma = gamma
+
+    def evaluate(self, vision_rd_loss, coded: bool = False):
+        codec = None
+        if coded:
+            from .codec import ScalableCodec
+            codec = ScalableCodec(self.model)
+        distortion, rate = _RunningMeans(), _RunningMeans()
+        first_inputs, first_recons = [], []
+        self.model.eval()
+        with torch.no_grad():
+            for batch in self.dataloader:
+                batch = batch.to(self.device)
+                out = self.model(batch, training=False)
+                rd = vision_rd_loss(out, batch, self.lambda_val, self.gamma)
+                x_hat = out["x_hat"].clamp(0, 1)
+                distortion.add(**self.compute_metrics(batch, x_hat))
+                rate.add(y=rd["bpp_y"], y1=rd["bpp_y1"], y2=rd["bpp_y2"], z=rd["bpp_z"], total=rd["bpp_total"])
+                if codec is not None:
+                    r = codec.compress(batch)
+                    rate.add(coded=r["bpp_coded"], coded_base=r["bpp_coded_base"])
+                first_inputs.append(batch[0].cpu())
+                first_recons.append(x_hat[0].cpu())
+        report, r = distortion.means(), rate.means()
+        report["BPP"] = r["y"]                      # the reference's quirk (class docstring)
+        for key, name in (("y", "BPP(y)"), ("y1", "BPP(y1)"), ("y2", "BPP(y2)"), ("z", "BPP(z)"), ("total", "BPP(total)"),
+                          ("coded", "BPP(coded)"), ("coded_base", "BPP(coded base)")):
+            if key in r:
+                report[name] = r[key]
+        print("\n--- Evaluation Results ---")
+        print("\n".join(f"{name}: {value:.6f}" for name, value in report.items()))
+        return report, first_inputs, first_recons

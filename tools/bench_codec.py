@@ -15,7 +15,11 @@ makes just that many calls of one path on the first BLOBS entry, for a kernel tr
 
 ENCODE_BLOBS (`ENCODE_BLOBS=1,4,16`) is the same mode for the encoder: N images of those sizes through `compress_images`
 and through a loop of `compress_image`, every blob compared with ==; a line also gives the host time of the layout
-(`ragged_encode_plan`) per call.  PROFILE works as above."""
+(`ragged_encode_plan`) per call.  PROFILE works as above.
+
+SCALABLE=<base channels> (`SCALABLE=128`) is the layered codec's mode: ScalableCodec on ScalableImageCoding(M, base, K)
+for every SLICE_ROWS and GROUPS entry -- compress, full decode, base-only decode, the full decode with one launch of
+the layered entries per layer -- beside ContextCodec(coder="rans", z_coder="rans") on the one-layer model."""
 import os
 import statistics
 import sys
@@ -112,6 +116,45 @@ def encode_blob_mode(model):
                   f"{'byte-equal' if ok else 'MISMATCH'}, {sum(map(len, a))} bytes", flush=True)
 
 
+def scalable_mode(base_channels):
+    """ScalableCodec on ScalableImageCoding(M, base_channels, K): compress, full decode, base-only decode, the full
+    decode with the layered entries launched once per layer (`merge_layers = False`), and -- the yardstick for one
+    layer's cost -- ContextCodec(coder="rans", z_coder="rans") on JointAutoregressiveHierarchical(M, K), all in one
+    process, the decodes alternating inside every run so that they see the same clocks"""
+    from neural_image_compression_amd.codec import ScalableCodec
+    torch.manual_seed(0)
+    scal = nic.ScalableImageCoding(M, base_channels, K).cuda().eval()
+    jah = nic.JointAutoregressiveHierarchical(M, K).cuda().eval()
+    x = torch.rand(1, 3, H, W, device="cuda").contiguous(memory_format=torch.channels_last)
+    for rows, groups in [(r, g) for r in SLICE_ROWS for g in GROUPS]:
+        sc = ScalableCodec(scal, groups=groups, slice_rows=rows or None)
+        per = ScalableCodec(scal, groups=groups, slice_rows=rows or None)
+        per.merge_layers = False
+        cc = ContextCodec(jah, coder="rans", encoder="device", groups=groups, slice_rows=rows or None, z_coder="rans")
+        enc, one = sc.compress(x), cc.compress(x)
+        args, one_args = (enc["strings"], enc["shape"], enc["z_shape"]), (one["strings"], one["shape"], one["z_shape"])
+        paths = {"full": lambda: sc.decompress(*args), "base": lambda: sc.decompress_base(*args),
+                 "per-layer": lambda: per.decompress(*args), "one-layer": lambda: cc.decompress(*one_args),
+                 "compress": lambda: sc.compress(x), "one-layer compress": lambda: cc.compress(x)}
+        for _ in range(2):                                                   # warm: allocator, weight packs, tuning
+            outs = {k: f() for k, f in paths.items()}
+        ok = (torch.equal(outs["full"]["y_hat"], enc["y_in"]) and torch.equal(outs["per-layer"]["y_hat"], enc["y_in"])
+              and torch.equal(outs["base"]["y1_hat"], enc["y_in"][:, :base_channels]))
+        t = {k: [] for k in paths}
+        for _ in range(RUNS):
+            for k, f in paths.items():
+                t[k].append(timed(f)[1])
+        steps = len(sc._wavefront(enc["shape"][2], enc["shape"][3], rows or None))
+        line = ", ".join(f"{k} {statistics.median(v):.2f} ms (min {min(v):.2f}, max {max(v):.2f})" for k, v in t.items())
+        print(f"Scalable({M},{base_channels},{K}) vs JAH({M},{K}) {H}x{W} groups={groups} slice_rows={rows} steps={steps}: "
+              f"{line}; median of {RUNS}, round trip {'ok' if ok else 'MISMATCH'}, bpp coded {enc['bpp_coded']:.4f} "
+              f"base {enc['bpp_coded_base']:.4f} est {enc['bpp_est']:.4f}; one-layer bpp coded {one['bpp_coded']:.4f}",
+              flush=True)
+
+
+if os.environ.get("SCALABLE"):
+    scalable_mode(int(os.environ["SCALABLE"]))
+    sys.exit(0)
 torch.manual_seed(0)
 model = nic.JointAutoregressiveHierarchical(M, K).cuda().eval()
 if BLOBS:
