@@ -510,6 +510,32 @@ int lic_ctx_gather_layers(const float* y, int64_t y_batch, int64_t y_row, int64_
                           int32_t path, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Layered codec, rows of DIFFERENT images (codec.ScalableCodec.decompress_images / decompress_base_images): one
+ *   launch builds every layer's rows of a step of many layered bitstreams.  The arguments of lic_ctx_gather_ragged
+ *   without M, win, comb, comb_ld, and lic_ctx_gather_layers' layer table (a HOST array that is copied into the
+ *   launch): layer l covers channels [c0, c0 + M) of every pixel of every plane, writes row k of its own
+ *   win [rows][nt*M] and, with psi, row k of its own comb.
+ *   The bytes written for layer l are exactly those of lic_ctx_gather_ragged called with M = the layer's M, every
+ *   descriptor's Y_ORIGIN raised by c0, and that layer's win / comb / comb_ld: tap, slice, column and psi rules, rows
+ *   of zeros for a bad row_image / row_pix / descriptor, and the per-row fallback from the 16-byte path when an
+ *   image's bases are no multiple of 4 floats.  The 16-byte path is decided per layer, as in lic_ctx_gather_layers
+ *   (y, psi 16-byte aligned, y_pix, Cpsi, c0, M, comb_ld multiples of 4, the layer's win / comb 16-byte aligned).
+ *   The kernel checks a descriptor once per row, before it addresses anything: lic_ctx_gather_ragged's check, with the
+ *   plane's last float Y_BASE + Y_ORIGIN + (H-1) Y_ROW + (W-1) y_pix + max(c0 + M) <= y_len, so no address leaves
+ *   y[0, y_len) or psi[0, psi_len), whatever the tables say.
+ *   NULL y / images / taps / row_image / row_pix / layers / a layer's win, psi with a layer without comb (or comb_ld <
+ *   Cpsi), L outside 1..LIC_MAX_LAYERS, M <= 0, c0 < 0, c0 + M > y_pix, overlapping channel ranges, nimg, rows,
+ *   y_len <= 0, nt < 1, psi with Cpsi or psi_len <= 0, a float pointer that is not 4-byte or an int64 pointer that is
+ *   not 8-byte aligned, LIC_CTX_VECTOR where a layer cannot hold it: LIC_ERR_INVALID; y_len, psi_len, y_pix above 2^40,
+ *   rows above 2^40, nt * M + Cpsi of a layer above 2^31 - 257: LIC_ERR_UNSUPPORTED; nothing launched.
+ *   One launch on `stream`, no allocation, no synchronisation, graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+int lic_ctx_gather_layers_ragged(const float* y, int64_t y_len, int64_t y_pix, const int64_t* images, int32_t nimg,
+                                 const int32_t* taps, int32_t nt, const int64_t* row_image, const int64_t* row_pix,
+                                 int64_t rows, const float* psi, int64_t psi_len, int32_t Cpsi,
+                                 const lic_ctx_layer* layers, int32_t L, int32_t path, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).2 -- the device decoder of the "rANS-64" y streams (format and host coder: lic_codec.h).
  *   lic_rans_decode_step decodes ONE wavefront step of all B images in one launch, one wave per image, from the
  *   tables lic_gmm_cdf_tables has just built, and writes the values where the next step's gather reads them:
@@ -622,6 +648,42 @@ int lic_rans_decode_step_layers(const uint8_t* streams, const int64_t* stream_of
                                 const uint32_t* escapes, const int64_t* esc_off, uint32_t* state,
                                 const lic_rans_layer* layers, int32_t L, int32_t B, int32_t G, int32_t n, int32_t W,
                                 const int64_t* dest, float* ypad, int64_t pixels, int64_t y_pix, lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Layered codec, many latents of different sizes (codec.ScalableCodec.decompress_images / decompress_base_images) --
+ *   lic_rans_decode_step_ragged for L layers in ONE launch: L * nimg * G workgroups of one wave.
+ *     stream_off, stream_bytes, esc_off, state   LAYER-MAJOR: block (l * nimg + b) * G + g is sub-stream g of image b
+ *                   of layer l (L*nimg*G + 1 offsets, L*nimg*G lengths and state blocks); a base-only call is L = 1
+ *                   with no gaps
+ *     layers        [L] rows, 1 <= L <= LIC_MAX_LAYERS, a HOST array that is copied into the launch: layer l has
+ *                   channels [c0, c0 + M), tables [total_rows * M][2W+2] (16-byte aligned) and center [total_rows * M]
+ *     seg           [nimg][2] int32 (device), shared by the layers, which share the schedule: image b's rows of this
+ *                   step are seg[b][0] .. seg[b][0] + seg[b][1]; in layer l its symbols number seg[b][1] * M and its
+ *                   tables start at dword seg[b][0] * M * (2W+2) of the layer's tables -- any offset mod 4
+ *     dest, ypad, ypad_len, y_base, pixels   as in lic_rans_decode_step_ragged; y_pix is call-wide, >= c0 + M for
+ *                   every layer: image b's plane is ypad[y_base[b] .. y_base[b] + pixels[b] * y_pix), and symbol k of
+ *                   layer l writes element (dest[seg[b][0] + k / M], c0 + k % M) at y_base[b] + d * y_pix + c0 + k % M.
+ *                   No other element is touched.
+ *   Per block every rule of lic_rans_decode_step_ragged holds: cursors are compared before every read; error words are
+ *   per block; a wave whose image has seg[b][1] == 0, or whose group has no round in its layer's step, returns before
+ *   it reads its state block; a segment with a negative entry or an end beyond total_rows sets LIC_RANS_ERR_RANGE in
+ *   that image's blocks of every layer and decodes nothing; a plane that does not lie inside [0, ypad_len), measured
+ *   with pixels[b] * y_pix, counts as empty, so every destination of the image is refused (LIC_RANS_ERR_RANGE, nothing
+ *   written); no table read goes beyond dword total_rows * M * (2W+2) of its layer.
+ *   With L = 1, c0 = 0, y_pix = M this is lic_rans_decode_step_ragged.  With every image at seg[b] = (b * n, n) and
+ *   y_base[b] = b * pixels * y_pix it is lic_rans_decode_step_layers.
+ *   NULL pointers, L outside 1..LIC_MAX_LAYERS, M <= 0, c0 < 0, c0 + M > y_pix, overlapping channel ranges, nimg,
+ *   total_rows, W, ypad_len, y_pix <= 0, G outside 1..LIC_RANS_MAX_GROUPS, misaligned pointers (tables 16 bytes, int64
+ *   arrays 8, the others 4): LIC_ERR_INVALID.  W > 64, total_rows * M >= 2^31 - 64, L * nimg * G > 65535,
+ *   ypad_len > 2^40: LIC_ERR_UNSUPPORTED.  Nothing is launched then.  One launch, no allocation, no synchronisation,
+ *   graph-capturable.
+ * ------------------------------------------------------------------------------------------ */
+int lic_rans_decode_step_layers_ragged(const uint8_t* streams, const int64_t* stream_off, const int64_t* stream_bytes,
+                                       const uint32_t* escapes, const int64_t* esc_off, uint32_t* state,
+                                       const lic_rans_layer* layers, int32_t L, const int32_t* seg, int32_t nimg,
+                                       int32_t G, int64_t total_rows, int32_t W, const int64_t* dest, float* ypad,
+                                       const int64_t* y_base, const int64_t* pixels, int64_t ypad_len, int64_t y_pix,
+                                       lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * SURVEY 8(f).2 -- the device encoder of the same streams: byte for byte what the host encoder of lic_codec.h

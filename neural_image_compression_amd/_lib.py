@@ -208,6 +208,10 @@ SIGNATURES = {
                                         C.POINTER(CtxLayer), _i32, _i32, _vp]),
     "lic_rans_decode_step_layers": (C.c_int, [_vp] * 6 + [C.POINTER(RansLayer)] + [_i32] * 5 + [_vp, _vp, _i64, _i64,
                                                                                                  _vp]),
+    "lic_ctx_gather_layers_ragged": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _i64, _i32,
+                                               C.POINTER(CtxLayer), _i32, _i32, _vp]),
+    "lic_rans_decode_step_layers_ragged": (C.c_int, [_vp] * 6 + [C.POINTER(RansLayer), _i32, _vp, _i32, _i32, _i64,
+                                                                 _i32, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "lic_rans_z_pick": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
     "lic_rans_z_decode_path": (C.c_int, [_i32, _i32]),
     "lic_rans_z_decode": (C.c_int, [_vp] * 7 + [_i32] * 5 + [_vp, _vp, _vp, _i64, _i32, _vp]),

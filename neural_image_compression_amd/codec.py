@@ -759,7 +759,9 @@ class _LayeredCodec:
     layer's rows from the one latent plane, the per-step front end and the rANS step loop, written once over
     `self.layers`.  A single layer that covers the whole plane goes through `lic_ctx_gather` and
     `lic_rans_decode_step_groups`; anything else through `lic_ctx_gather_layers` and `lic_rans_decode_step_layers`,
-    one launch each for all layers of a step."""
+    one launch each for all layers of a step.  `_run_merged_steps` is that loop for many latents of different sizes
+    (`lic_ctx_gather_layers_ragged`, `lic_rans_decode_step_layers_ragged`); `ContextCodec.decompress_many` keeps its
+    own one-layer entries."""
 
     # False: the layered entries are launched once per layer instead of once per step (tools/bench_codec.py measures
     # what the merged launches save); bytes and results are the same
@@ -901,6 +903,43 @@ class _LayeredCodec:
                     s, shift(s_off, l, 8), shift(s_len, l, 8), e, shift(e_off, l, 8),
                     shift(state, l, 4 * L.RANS_STATE_WORDS), (L.RansLayer * 1)(t), 1, nimg, G, n, self.y_W, F_._ptr(own),
                     F_._ptr(yflat), npad, y_pix, F_._stream()), "lic_rans_decode_step_layers")
+
+    def _run_merged_steps(self, sched: MergedSchedule, layers, blocks, G: int, yflat: torch.Tensor, y_pix: int,
+                          d_desc: torch.Tensor, d_pixels: torch.Tensor, psiflat: torch.Tensor, cpsi: int):
+        """The step loop of many latents of different sizes (`merged_wavefront`), every layer of `layers` in it: per
+        step ONE `lic_ctx_gather_layers_ragged` from the flat buffers `yflat` (zero-framed planes of y_pix channels per
+        pixel) and `psiflat`, per layer the per-pixel layers and the table kernel over the step's rows of every image,
+        and ONE `lic_rans_decode_step_layers_ragged`, which writes the values where the next gather reads them.
+        d_desc [nimg, CTX_IMAGE_WORDS] (device): the planes; d_pixels [nimg]: their framed pixel counts; blocks: the six
+        staging arguments, one block per layer, image and group, layer-major.  The schedule goes up once; nothing in
+        the loop copies, waits for the device or computes on the host."""
+        if len(layers) > L.MAX_LAYERS:
+            raise CodecError(f"{len(layers)} layers: the layered kernels take {L.MAX_LAYERS} at the most")
+        dev, nt, nimg, lib = yflat.device, len(self.taps), d_desc.shape[0], L.load()
+        taps = self._taps_on(dev)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        d_rows, d_seg, d_ybase = up(sched.rows), up(sched.seg), d_desc[:, 0].contiguous()
+        packed = [ly.prepack() for ly in layers]
+        ctx, rans, off = (L.CtxLayer * len(layers))(), (L.RansLayer * len(layers))(), sched.step_off
+        for t in range(sched.T):
+            a, e = int(off[t]), int(off[t + 1])
+            rows = []
+            for c, ly in zip(ctx, layers):
+                win = torch.empty((e - a, nt * ly.M, 1, 1), device=dev, dtype=torch.float32)
+                comb = torch.empty((e - a, ly.cctx + cpsi), device=dev, dtype=torch.float32)
+                c.win, c.comb, c.comb_ld, c.c0, c.M = win.data_ptr(), comb.data_ptr() + 4 * ly.cctx, comb.shape[1], ly.c0, ly.M
+                rows.append((win, comb))
+            L.check(lib.lic_ctx_gather_layers_ragged(
+                F_._ptr(yflat), yflat.numel(), y_pix, F_._ptr(d_desc), nimg, F_._ptr(taps), nt, F_._ptr(d_rows[0, a:e]),
+                F_._ptr(d_rows[1, a:e]), e - a, F_._ptr(psiflat), psiflat.numel(), cpsi, ctx, len(layers), L.CTX_AUTO,
+                F_._stream()), "lic_ctx_gather_layers_ragged")
+            params = [ly.params_at(win, None, pk, comb, self.y_W) for ly, pk, (win, comb) in zip(layers, packed, rows)]
+            for r, ly, (center, tables) in zip(rans, layers, params):
+                r.tables, r.center, r.c0, r.M = tables.data_ptr(), center.data_ptr(), ly.c0, ly.M
+            L.check(lib.lic_rans_decode_step_layers_ragged(
+                *blocks, rans, len(layers), F_._ptr(d_seg[t]), nimg, G, e - a, self.y_W, F_._ptr(d_rows[2, a:e]),
+                F_._ptr(yflat), F_._ptr(d_ybase), F_._ptr(d_pixels), yflat.numel(), y_pix, F_._stream()),
+                "lic_rans_decode_step_layers_ragged")
 
 
 class ContextCodec(_LayeredCodec):
@@ -1772,8 +1811,14 @@ class ScalableCodec(_LayeredCodec):
     `compress` returns strings with `layers` = [{"y": [B*G], "y_esc": [B*G], "y_crc32": [B]}, the same for layer 1],
     `z`, `z_esc`, `z_coder`, `coder`, and `groups` / `slice_rows` when set; `bpp_coded` and `bpp_coded_base` count the
     LICBITS6 container (bitstream.py) that `compress_image` writes, header and checksums included: all of it, and its
-    first `base_bytes` (header, z and layer 0).  Several images are coded one after the other (`compress_images`,
-    `decompress_images`); a merged step loop for layered blobs does not exist."""
+    first `base_bytes` (header, z and layer 0).
+
+    Many blobs decode in ONE step loop: `decompress_images` (the pictures) and `decompress_base_images` (whole blobs or
+    base prefixes, the base layer alone) advance step t of every image of every blob together (`decompress_many`,
+    `merged_wavefront`): per step one `lic_ctx_gather_layers_ragged` and one `lic_rans_decode_step_layers_ragged` for
+    all images and layers, so N blobs cost about one blob's step loop plus every blob's transforms; every entry is bit
+    for bit the single-blob call's.  One call decodes one depth.  Several images are still encoded one after the
+    other (`compress_images`)."""
 
     def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, encoder: str = "device", groups: int = 1,
                  slice_rows: int = None):
@@ -1989,6 +2034,175 @@ class ScalableCodec(_LayeredCodec):
         """`compress_image` per entry, one after the other (no merged pass for layered blobs)"""
         return [self.compress_image(x, mode, align) for x in images]
 
+    # ---- many layered bitstreams in one step loop -----------------------------------------------------
+    @torch.no_grad()
+    def decompress_many(self, items, nlayers: int = 2, z_windows=None, names=None) -> List[Dict]:
+        """`decompress` (nlayers = 2) or `decompress_base` (nlayers = 1) for several bitstreams at once.  items:
+        [(strings, shape, z_shape)] as those take them, of this codec's y_W and one G; they may differ in B, h, w and
+        slice_rows.  z_windows: [(z_lo, z_S)] per item (default: this codec's); names: what to call an item in a message
+        (default "item i").  -> one result per item, bit for bit what the single call gives for it alone.
+
+        All layers' y blocks are staged layer-major (block (l * nimg + image) * G + g) with the z blocks behind them;
+        z decodes in one `lic_rans_z_decode` launch per window and the hyper-decoder runs per item.  All psi planes and
+        all zero-framed latent planes -- the channels of the first `nlayers` layers -- lie in two flat buffers, every
+        item's on a multiple of 4 floats.  Then ONE loop of T steps (`merged_wavefront`, `_run_merged_steps`), then one
+        read-back of the state blocks, the checksums per layer and image, and the synthesis transforms per item.
+        Everything the host can refuse is refused before the device is touched."""
+        m, p = self.model, self.pad
+        M = m.M
+        items = list(items)
+        if not items:
+            return []
+        if nlayers not in (1, 2):
+            raise CodecError(f"nlayers = {nlayers!r}: 1 decodes the base layer, 2 both layers")
+        use = self.layers[:nlayers]
+        y_pix = sum(ly.M for ly in use)                    # the layers are consecutive from channel 0
+        names = [f"item {i}" for i in range(len(items))] if names is None else list(names)
+        z_windows = [(self.z_lo, self.z_S)] * len(items) if z_windows is None else list(z_windows)
+        G, shapes, Rs, owner = None, [], [], []
+        per_layer = [([], []) for _ in use]                # (streams, escape lists) of every image, per layer
+        zs, zescs, zwin, znsym, zbase, zitem, z_len = [], [], [], [], [], [], 0
+        for i, ((strings, shape, z_shape), win) in enumerate(zip(items, z_windows)):
+            try:
+                g = _groups(strings.get("groups", 1))
+                if G is not None and g != G:
+                    raise CodecError(f"{g} sub-streams per image, {names[0]} has {G}: one call decodes one G")
+                G = g
+                B, Mi, h, w = shape
+                _, _, h4, w4 = z_shape
+                if Mi != M or z_shape[0] != B:
+                    raise CodecError(f"shape names {Mi} latent channels and z_shape {z_shape[0]} images; this model has "
+                                     f"{M} channels and shape {B} images")
+                R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
+                coded = strings.get("layers")
+                if not isinstance(coded, (list, tuple)) or len(coded) < nlayers:
+                    raise CodecError(f"the strings hold {0 if not isinstance(coded, (list, tuple)) else len(coded)} "
+                                     f"layers; {nlayers} are to be decoded")
+                for l, c in enumerate(coded[:nlayers]):
+                    if c.get("y_esc") is None or len(c["y"]) != B * G or len(c["y_esc"]) != B * G or len(c["y_crc32"]) != B:
+                        raise CodecError(f"layer {l}: one y stream and one escape list per image and group and one "
+                                         "checksum per image expected")
+                    per_layer[l][0].extend(c["y"])
+                    per_layer[l][1].extend(c["y_esc"])
+                if strings.get("z_esc") is None or isinstance(strings["z"], (bytes, bytearray)) or \
+                        len(strings["z"]) != B * G or len(strings["z_esc"]) != B * G:
+                    raise CodecError("one z stream and one escape list per image and group expected")
+            except CodecError as err:
+                raise CodecError(f"{names[i]}: {err}") from None
+            shapes += [(h, w)] * B
+            Rs += [R] * B
+            owner += [(i, b) for b in range(B)]
+            z_len = (z_len + 3) // 4 * 4                                          # every item on a multiple of 4 floats
+            zitem.append(z_len)
+            for b in range(B):
+                zwin.append((int(win[0]), int(win[1])))
+                znsym.append(h4 * w4 * M)
+                zbase.append(z_len)
+                z_len += h4 * w4 * M
+            zs += list(strings["z"])
+            zescs += list(strings["z_esc"])
+        nimg = len(shapes)
+        of = lambda img: f"{names[owner[img][0]]}: image {owner[img][1]}"
+        staged = _stage_y_and_z([s for ys, _ in per_layer for s in ys], [e for _, es in per_layer for e in es],
+                                nlayers * nimg, zs, zescs, nimg, G,
+                                lambda i: f"{of(i % nimg)}, layer {i // nimg}", of)
+        sched = merged_wavefront(shapes, p, Rs)
+        # ---- the device from here on
+        dev = next(m.parameters()).device
+        blocks = staged.upload(dev)
+        zflat = self._decode_z(staged, nlayers * nimg * G, zwin, znsym, zbase, z_len, dev)
+        z_hats, psis = [], []
+        for i, (_, _, (B, _, h4, w4)) in enumerate(items):
+            z_hat = zflat[zitem[i]:zitem[i] + B * h4 * w4 * M].view(B, h4, w4, M).permute(0, 3, 1, 2)
+            z_hats.append(z_hat.contiguous(memory_format=torch.channels_last))
+            psis.append(m.hyper_decoder(z_hats[-1]).float())
+        cpsi = psis[0].shape[1]
+        # the layout: item after item, each on a multiple of 4 floats, its B planes one behind the other
+        y_at, psi_at, y_len, psi_len, img = [], [], 0, 0, 0
+        desc = np.zeros((nimg, L.CTX_IMAGE_WORDS), np.int64)
+        for _, (B, _, h, w), _ in items:
+            y_at.append((y_len + 3) // 4 * 4)
+            psi_at.append((psi_len + 3) // 4 * 4)
+            Wp, plane = w + 2 * p, (h + 2 * p) * (w + 2 * p) * y_pix
+            for b in range(B):
+                desc[img, :7] = (y_at[-1] + b * plane, Wp * y_pix, (p * Wp + p) * y_pix, psi_at[-1] + b * h * w * cpsi,
+                                 h, w, h if Rs[img] is None else min(Rs[img], h))
+                img += 1
+            y_len, psi_len = y_at[-1] + B * plane, psi_at[-1] + B * h * w * cpsi
+        yflat = torch.zeros(y_len, device=dev, dtype=torch.float32)                # decoded latents inside zero frames
+        psiflat = torch.empty(psi_len, device=dev, dtype=torch.float32)
+        for i, (_, (B, _, h, w), _) in enumerate(items):
+            psiflat[psi_at[i]:psi_at[i] + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psis[i]).view(B, h * w, -1))
+        d_desc = torch.from_numpy(desc).to(dev)
+        d_pixels = torch.from_numpy(np.array([(h + 2 * p) * (w + 2 * p) for h, w in shapes], np.int64)).to(dev)
+        self._run_merged_steps(sched, use, blocks, G, yflat, y_pix, d_desc, d_pixels, psiflat, cpsi)
+        staged.check()
+        out = []
+        for i, (strings, (B, _, h, w), _) in enumerate(items):
+            ypad = yflat[y_at[i]:y_at[i] + B * (h + 2 * p) * (w + 2 * p) * y_pix].view(B, h + 2 * p, w + 2 * p, y_pix)
+            inner = ypad[:, p:p + h, p:p + w, :]
+            got = inner.round().to(torch.int32).cpu().numpy()
+            for l, (ly, c) in enumerate(zip(use, strings["layers"])):
+                for b in range(B):
+                    sym = np.ascontiguousarray(got[b, :, :, ly.c0:ly.c0 + ly.M])
+                    if (zlib.crc32(sym.tobytes()) & 0xFFFFFFFF) != int(c["y_crc32"][b]):
+                        raise CodecError(f"{names[i]}: image {b}, layer {l}: decoded latents do not match the encoder's "
+                                         "checksum (encoder and decoder built different probability tables, or the "
+                                         "stream is damaged)")
+            y_hat = inner.permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
+            if nlayers == 1:
+                out.append({"y1_hat": y_hat, "z_hat": z_hats[i], "F_tilde": m.LST(y_hat)})
+            else:
+                out.append({"x_hat": m.decoder(y_hat), "y_hat": y_hat, "z_hat": z_hats[i],
+                            "F_tilde": m.LST(y_hat[:, :m.M1])})
+        return out
+
+    def _open_blobs(self, blobs, base_only: bool):
+        """The host half of `decompress_images` / `decompress_base_images` -> ([(header, strings)], the codec that
+        decodes them all).  CodecError, naming the blob: what `_open_blob` refuses for it, a y_W or a G that is not
+        blob 0's.  An empty list gives ([], self)."""
+        opened = []
+        for i, data in enumerate(blobs):
+            try:
+                opened.append(self._open_blob(data, base_only)[:2])
+            except CodecError as err:
+                raise CodecError(f"blob {i}: {err}") from None
+        if not opened:
+            return [], self
+        y_W, G = opened[0][0]["y_W"], opened[0][1].get("groups", 1)
+        for i, (head, strings) in enumerate(opened):
+            if head["y_W"] != y_W:
+                raise CodecError(f"blob {i}: y_W = {head['y_W']}, blob 0 has y_W = {y_W}: one call decodes one window")
+        for i, (head, strings) in enumerate(opened):
+            if strings.get("groups", 1) != G:
+                raise CodecError(f"blob {i}: G = {strings.get('groups', 1)} sub-streams per image, blob 0 has G = {G}: "
+                                 "one call decodes one G")
+        return opened, (self if y_W == self.y_W else ScalableCodec(self.model, self.z_lo, self.z_S, y_W))
+
+    def _decompress_blobs(self, blobs, nlayers: int):
+        opened, dec = self._open_blobs(list(blobs), nlayers == 1)
+        if not opened:
+            return [], []
+        items = [(strings, *self._shapes(head, self.model.M)) for head, strings in opened]
+        return opened, dec.decompress_many(items, nlayers, [(head["z_lo"], head["z_S"]) for head, _ in opened],
+                                           [f"blob {i}" for i in range(len(opened))])
+
+    @torch.no_grad()
     def decompress_images(self, blobs: Sequence[bytes]) -> List[torch.Tensor]:
-        """`decompress_image` per entry, one after the other (no merged step loop for layered blobs)"""
-        return [self.decompress_image(b) for b in blobs]
+        """Many `compress_image` blobs in one decode loop: entry i is bit for bit `decompress_image(blobs[i])`,
+        [B_i, 3, H_i, W_i], channels_last, cropped.  The blobs may differ in size, batch, crop, slice_rows and z window;
+        step t of all their images and both layers shares its launches (`decompress_many`), so N blobs cost about one
+        blob's step loop plus every blob's transforms.  Raises CodecError before any GPU work, every message naming its
+        blob ("blob i: ..."): whatever `decompress_image` refuses for blob i -- a base prefix included --, a y_W or a
+        G that is not blob 0's.  An empty list gives an empty list."""
+        opened, outs = self._decompress_blobs(blobs, 2)
+        return [F_.crop_window(out["x_hat"], head["top"], head["left"], head["H"], head["W"])
+                for out, (head, _) in zip(outs, opened)]
+
+    @torch.no_grad()
+    def decompress_base_images(self, blobs: Sequence[bytes]):
+        """Whole `compress_image` blobs or their prefixes blob[:base_bytes], mixed freely, in one decode loop of the
+        base layer alone: entry i is bit for bit `decompress_base_image(blobs[i])`, (y1_hat, F_tilde).  Nothing behind
+        base_bytes is looked at.  Differences between blobs and refusals as for `decompress_images`."""
+        _, outs = self._decompress_blobs(blobs, 1)
+        return [(out["y1_hat"], out["F_tilde"]) for out in outs]

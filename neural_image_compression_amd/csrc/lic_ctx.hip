@@ -19,6 +19,9 @@
 // checks against the buffers' lengths before it addresses anything: a descriptor that fails, like a bad image or pixel
 // index, gives a row of zeros and no read.  The 16-byte kernel moves a row float by float when its image's bases are
 // not multiples of 4 floats: the same bytes either way.
+//
+// lic_ctx_gather_layers / lic_ctx_gather_layers_ragged: the two launches above for a latent whose channels are split
+// into layers (codec.ScalableCodec), every layer's rows in one launch; both at the end of this file.
 #include "lic_common.h"
 
 namespace {
@@ -303,5 +306,95 @@ LIC_EXPORT int lic_ctx_gather_layers(const float* y, int64_t y_batch, int64_t y_
   p.R = slice_rows;
   p.L = L;
   hipLaunchKernelGGL(ctx_gather_layers_kernel, dim3(ew_grid(p.rows, 1)), dim3(256), 0, (hipStream_t)stream, p);
+  return lic_check_launch();
+}
+
+// ---- the layers of one latent, rows of different images (lic_ctx_gather_layers_ragged, codec.ScalableCodec) ---------
+// ctx_gather_ragged_kernel's row walk once per layer: `chk` is the launch lic_ctx_gather_ragged would be given for the
+// whole plane -- its row.M is the widest c0 + M of the layers, so ctx_image passes a descriptor only if every layer's
+// last float lies inside y -- and row[l] is the layer's own walk, row[l].y at channel c0 of the buffer's first float.
+namespace {
+
+struct CtxLayersRaggedParams {
+  CtxRaggedParams chk;
+  CtxRowParams row[LIC_MAX_LAYERS];
+  int32_t L;
+  uint32_t vec;
+};
+
+// one workgroup per row checks the row's image once and walks the row of every layer; unrolled as in
+// ctx_gather_layers_kernel.  A layer in 16-byte pieces moves a row float by float when its image's bases are not
+// multiples of 4 floats.
+__global__ __launch_bounds__(256) void ctx_gather_layers_ragged_kernel(const CtxLayersRaggedParams p) {
+  for (int64_t row = blockIdx.x; row < p.chk.rows; row += gridDim.x) {
+    const int64_t b = p.chk.row_image[row], px = p.chk.row_pix[row];
+    CtxImage g = {};
+    const bool ok = ctx_image(p.chk, b, g) && px >= 0 && px < g.h * g.w;
+    const bool by_float = ok && ((g.y_base | g.y_row | g.y_origin | g.psi_base) & 3);
+#pragma unroll
+    for (int l = 0; l < LIC_MAX_LAYERS; ++l) {
+      if (l < p.L) {
+        if (((p.vec >> l) & 1u) && !by_float)
+          ctx_row<4>(p.row[l], row, ok, g, px);
+        else
+          ctx_row<1>(p.row[l], row, ok, g, px);
+      }
+    }
+  }
+}
+
+}  // namespace
+
+LIC_EXPORT int lic_ctx_gather_layers_ragged(const float* y, int64_t y_len, int64_t y_pix, const int64_t* images,
+                                            int32_t nimg, const int32_t* taps, int32_t nt, const int64_t* row_image,
+                                            const int64_t* row_pix, int64_t rows, const float* psi, int64_t psi_len,
+                                            int32_t Cpsi, const lic_ctx_layer* layers, int32_t L, int32_t path,
+                                            lic_stream_t stream) {
+  if (!y || !images || !taps || !row_image || !row_pix || !layers) return LIC_ERR_INVALID;
+  if (L < 1 || L > LIC_MAX_LAYERS) return LIC_ERR_INVALID;
+  if (nimg <= 0 || rows <= 0 || nt < 1 || y_len <= 0 || y_pix < 1) return LIC_ERR_INVALID;
+  if (psi && (Cpsi <= 0 || psi_len <= 0)) return LIC_ERR_INVALID;
+  if (path != LIC_CTX_AUTO && path != LIC_CTX_VECTOR && path != LIC_CTX_ELEMENT) return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(psi) | reinterpret_cast<uintptr_t>(taps)) & 3)
+    return LIC_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(row_image) |
+       reinterpret_cast<uintptr_t>(row_pix)) & 7)
+    return LIC_ERR_INVALID;
+  int32_t widest = 0;
+  for (int l = 0; l < L; ++l) {
+    const lic_ctx_layer& a = layers[l];
+    if (!a.win || a.M <= 0 || a.c0 < 0 || (int64_t)a.c0 + a.M > y_pix) return LIC_ERR_INVALID;
+    if (psi && (!a.comb || a.comb_ld < Cpsi)) return LIC_ERR_INVALID;
+    if ((reinterpret_cast<uintptr_t>(a.win) | reinterpret_cast<uintptr_t>(a.comb)) & 3) return LIC_ERR_INVALID;
+    for (int m = 0; m < l; ++m)  // channel ranges must not overlap
+      if (a.c0 < layers[m].c0 + layers[m].M && layers[m].c0 < a.c0 + a.M) return LIC_ERR_INVALID;
+    widest = a.c0 + a.M > widest ? a.c0 + a.M : widest;
+  }
+  // rows and row lengths the kernel's 32-bit piece counters and 64-bit offsets hold
+  if (rows > (1LL << 40) || y_len > kMaxFloats || y_pix > kMaxFloats || (psi && psi_len > kMaxFloats))
+    return LIC_ERR_UNSUPPORTED;
+  for (int l = 0; l < L; ++l)
+    if ((int64_t)nt * layers[l].M + (psi ? Cpsi : 0) > 0x7FFFFFFFL - 256) return LIC_ERR_UNSUPPORTED;
+  const bool plane_vec = aligned16(y) && y_pix % 4 == 0 && (!psi || (Cpsi % 4 == 0 && aligned16(psi)));
+  CtxLayersRaggedParams p = {};
+  for (int l = 0; l < L; ++l) {
+    const lic_ctx_layer& a = layers[l];
+    const bool can_vec = plane_vec && a.c0 % 4 == 0 && a.M % 4 == 0 && aligned16(a.win) &&
+                         (!psi || (a.comb_ld % 4 == 0 && aligned16(a.comb)));
+    if (path == LIC_CTX_VECTOR && !can_vec) return LIC_ERR_INVALID;
+    if (can_vec && path != LIC_CTX_ELEMENT) p.vec |= 1u << l;
+    p.row[l] = ctx_row_params(y + a.c0, taps, psi, a.win, a.comb, y_pix, a.comb_ld, a.M, nt, Cpsi);
+  }
+  // what ctx_image reads: y_pix, the widest channel end as M, psi and Cpsi; it writes nothing
+  p.chk.row = ctx_row_params(y, taps, psi, nullptr, nullptr, y_pix, 0, widest, nt, Cpsi);
+  p.chk.images = images;
+  p.chk.row_image = row_image;
+  p.chk.row_pix = row_pix;
+  p.chk.y_len = y_len;
+  p.chk.psi_len = psi ? psi_len : 0;
+  p.chk.rows = rows;
+  p.chk.nimg = nimg;
+  p.L = L;
+  hipLaunchKernelGGL(ctx_gather_layers_ragged_kernel, dim3(ew_grid(rows, 1)), dim3(256), 0, (hipStream_t)stream, p);
   return lic_check_launch();
 }

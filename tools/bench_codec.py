@@ -19,7 +19,9 @@ and through a loop of `compress_image`, every blob compared with ==; a line also
 
 SCALABLE=<base channels> (`SCALABLE=128`) is the layered codec's mode: ScalableCodec on ScalableImageCoding(M, base, K)
 for every SLICE_ROWS and GROUPS entry -- compress, full decode, base-only decode, the full decode with one launch of
-the layered entries per layer -- beside ContextCodec(coder="rans", z_coder="rans") on the one-layer model."""
+the layered entries per layer -- beside ContextCodec(coder="rans", z_coder="rans") on the one-layer model.  A second
+line per BLOBS entry (8 if BLOBS is not set) decodes N blobs of that image: `decompress_images` and
+`decompress_base_images` (one merged step loop) against loops of `decompress_image` / `decompress_base_image`."""
 import os
 import statistics
 import sys
@@ -150,6 +152,28 @@ def scalable_mode(base_channels):
               f"{line}; median of {RUNS}, round trip {'ok' if ok else 'MISMATCH'}, bpp coded {enc['bpp_coded']:.4f} "
               f"base {enc['bpp_coded_base']:.4f} est {enc['bpp_est']:.4f}; one-layer bpp coded {one['bpp_coded']:.4f}",
               flush=True)
+        # N blobs of this image: the merged step loop against a loop of the single-blob calls (what decompress_images
+        # was before the merged loop existed), alternating inside every run
+        blob = sc.compress_image(x)
+        prefix = blob[:sc.base_bytes_of(blob)]
+        for n in BLOBS or [8]:
+            many = {"decompress_images": lambda: sc.decompress_images([blob] * n),
+                    "loop of decompress_image": lambda: [sc.decompress_image(blob) for _ in range(n)],
+                    "decompress_base_images": lambda: sc.decompress_base_images([prefix] * n),
+                    "loop of decompress_base_image": lambda: [sc.decompress_base_image(prefix) for _ in range(n)]}
+            for _ in range(2):
+                outs = {k: f() for k, f in many.items()}
+            ok = (all(torch.equal(u, v) for u, v in zip(outs["decompress_images"], outs["loop of decompress_image"]))
+                  and all(torch.equal(u[0], v[0]) and torch.equal(u[1], v[1]) for u, v in
+                          zip(outs["decompress_base_images"], outs["loop of decompress_base_image"])))
+            t = {k: [] for k in many}
+            for _ in range(RUNS):
+                for k, f in many.items():
+                    t[k].append(timed(f)[1])
+            line = ", ".join(f"{k} {statistics.median(v):.2f} ms (min {min(v):.2f}, max {max(v):.2f})" for k, v in t.items())
+            print(f"Scalable({M},{base_channels},{K}) {H}x{W} groups={groups} slice_rows={rows} steps={steps} blobs={n}: "
+                  f"{line}; median of {RUNS}, {'bit-equal' if ok else 'MISMATCH'}, {n * len(blob)} bytes, "
+                  f"{n * len(prefix)} of them base", flush=True)
 
 
 if os.environ.get("SCALABLE"):
