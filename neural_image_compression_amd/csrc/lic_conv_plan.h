@@ -180,6 +180,7 @@ static inline size_t conv_workspace_bytes(const lic_igemm_desc* d, KsplitOf kspl
 struct WgPlan {
   int TM, TN, vec, MTt, NTt, ntaps, nchunks, splitk, cps;
   int Cm, Cn;
+  int dma;  // fp32: both operands within reach of the LDS-DMA kernel's 32-bit lane offsets (wgrad_dma_addressable)
 };
 static inline int wgrad_desc_check(const lic_wgrad_desc* d) {
   if (!d || d->B <= 0 || d->Hs <= 0 || d->Ws <= 0 || d->Cp <= 0 || d->Cg <= 0 || d->kh <= 0 || d->kw <= 0 ||

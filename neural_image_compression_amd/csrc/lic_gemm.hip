@@ -7,6 +7,7 @@
 #include "lic_tile_map.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <type_traits>
 
 thread_local int g_lic_last_hip_error = 0;
@@ -60,9 +61,6 @@ struct IgemmParams {
 
 constexpr int IG_BK = 16;
 constexpr int IG_LDA = IG_BK + 4;
-
-// 16 zero bytes: the source of LDS-DMA lanes that fall on padding / past the last pixel
-__device__ __attribute__((aligned(16))) float g_lic_zero16[4];
 
 // ---- the elementwise epilogue of igemm_kernel, on one value (scalar path) or four channels (staged 16-byte path)
 // The two paths round differently, and stay so: a scalar goes through sqrtf and a division, a vector through
@@ -121,7 +119,7 @@ __device__ __forceinline__ void igemm_elementwise(const IgemmParams& p, int epi,
 // accumulators through v_accvgpr_read/mov at the joins: ~2 extra AGPR moves per MFMA.)
 // FUSE (BM = 64, one N tile covering all channels): the GDN / IGDN that follows the convolution
 // runs in this kernel's epilogue -- see the block after the K loop.
-// GLDS (VEC, FULLN, no prologue): both operands reach LDS by LDS-DMA (`global_load_lds_dwordx4`):
+// GLDS (VEC, FULLN, no prologue): both operands reach LDS by LDS-DMA (`buffer_load_dwordx4 ... lds`):
 // no staging registers, no ds_write pass and no B registers held across a chunk; see the loop.
 template <int BM, int TN, bool VEC, bool FULLN, bool FUSE = false, bool GLDS = false>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
@@ -343,9 +341,24 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
     // Per-tap gather state: the pixel a row reads changes only with the tap (every cpt chunks); within a
     // tap a chunk moves 16 channels on, so the ~60 VALU of the full address computation run once per
     // tap instead of once per chunk (wave-uniform branch; `ks` splits may start mid-tap: t_tapi).
-    long t_off[APASS];
-    bool t_ok[APASS];
+    // The DMAs are `buffer_load_dwordx4 ... lds` on descriptors held in SGPRs; the vector ALU contributes one 32-bit
+    // byte offset per piece and nothing per chunk (lic_halo_bf16.h has the measurement that moved its DMA there):
+    //  * A: the descriptor base (scalar, 64-bit, once per tap) is the input pixel that the tile's first row reads
+    //    under this tap, less IG_GBIAS bytes; a row's offset is its pixel's distance from that one times the pitch,
+    //    plus the bias (rows of a tile lie within igemm_dma_addressable()'s 2^30 bytes of each other, either way
+    //    round), or IG_OOB where the tap falls on padding / the row is past P: the hardware then writes zeros
+    //    without touching memory.  The channel block of a chunk is the scalar offset.
+    //  * B: the panel of (tap, chunk) is one contiguous run: base (scalar, 64-bit, per chunk) + tid * 16, the
+    //    4 KiB step of DMA j in the scalar offset.
+    constexpr unsigned IG_OOB = 0x80000000u, IG_GBIAS = 0x40000000u;
+    const unsigned in_ld4 = (unsigned)p.in_ld * 4u;
+    const GatherOrigin go0 = gather_origin(p, pv, m0);  // (m0 < P; wave-uniform)
+    // channels past Cin exist in the last chunk of a tap only (Cin % 16 != 0): those lanes read zeros there
+    const bool gq_dead = last_cb * IG_BK + gq >= p.Cin;
+    unsigned t_voff[APASS];
+    __amdgpu_buffer_rsrc_t t_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, 0, 0x00020000);
     int t_tap = 0, t_tapi = -1;
+    const unsigned w_voff = (unsigned)tid * 16u;
     auto issue = [&](int tapi, int cb, int buf) {
       const bool past = tapi > last_tap;
       const int cbb = past ? last_cb : cb;
@@ -355,30 +368,34 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
         const int code = __builtin_amdgcn_readfirstlane(s_taps[tcur]);
         const int r = (code >> 8) & 0xFF, s = code >> 16;
         t_tap = code & 0xFF;
+        const long ref = (long)go0.base + (long)((go0.hy + sgn * r) >> sh) * p.Wi + ((go0.wx + sgn * s) >> sh);
+        t_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in + (ref * p.in_ld - (long)(IG_GBIAS / 4))), 0,
+                                                 (int)IG_OOB, 0x00020000);
 #pragma unroll
         for (int j = 0; j < APASS; ++j) {
           const int nh = a_hy[j] + sgn * r, nw = a_wx[j] + sgn * s;
           const int ih = nh >> sh, iw = nw >> sh;
-          t_ok[j] = a_ok[j] && nh >= 0 && nw >= 0 && ih < p.Hi && iw < p.Wi;
-          t_off[j] = t_ok[j] ? (long)(a_base[j] + ih * p.Wi + iw) * p.in_ld : 0L;
+          const bool ok = a_ok[j] && nh >= 0 && nw >= 0 && ih < p.Hi && iw < p.Wi;
+          const unsigned dpix = (unsigned)(a_base[j] + ih * p.Wi + iw) - (unsigned)ref;  // (modulo 2^32: small)
+          const unsigned okm = (unsigned)(-(int)ok);  // all-ones / zero mask: arithmetic keeps hipcc from branching
+          t_voff[j] = ((dpix * in_ld4 + (IG_GBIAS + (unsigned)gq * 4u)) & okm) | (~okm & IG_OOB);
         }
       }
       const int tap = t_tap;
-      const int ci = cbb * IG_BK + gq;
-      const bool cok = ci < p.Cin;
+      const bool kill = gq_dead && cbb == last_cb;
       float* dstA = smem + buf * GL_BUF;
 #pragma unroll
-      for (int j = 0; j < APASS; ++j) {
-        const bool ok = t_ok[j] && cok;
-        const float* src = ok ? p.in + t_off[j] + ci : g_lic_zero16;
-        __builtin_amdgcn_global_load_lds((lic_gptr_t)src, (lic_lptr_t)(dstA + j * 1024 + wave * 256), 16, 0, 0);
-      }
-      const float* wsrc = p.w + ((long)tap * p.cpt + cbb) * p.Npad * IG_BK + (long)n0 * IG_BK + tid * 4;
+      for (int j = 0; j < APASS; ++j)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(t_rs, (lic_lptr_t)(dstA + j * 1024 + wave * 256), 16,
+                                                 (int)(kill ? IG_OOB : t_voff[j]), cbb * (IG_BK * 4), 0, 0);
+      const float* wbase = p.w + ((long)tap * p.cpt + cbb) * p.Npad * IG_BK + (long)n0 * IG_BK;
+      const __amdgpu_buffer_rsrc_t w_rs =
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), 0, (int)IG_OOB, 0x00020000);
       float* dstB = dstA + BM * IG_BK;
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        __builtin_amdgcn_global_load_lds((lic_gptr_t)(wsrc + j * 1024), (lic_lptr_t)(dstB + j * 1024 + wave * 256),
-                                         16, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (lic_lptr_t)(dstB + j * 1024 + wave * 256), 16, (int)w_voff,
+                                                 j * 4096, 0, 0);
     };
     // Fragments of half a chunk (k-steps 4h .. 4h+3): TM + TN ds_read_b128 per lane.  The reads are inline
     // asm: left to hipcc, every fragment read is followed by `s_waitcnt lgkmcnt(0)` in front of the next MFMA
@@ -916,6 +933,38 @@ struct IgemmPlan {
               // in the DMA loop's fragment reads cost every launch ~30 VALU per chunk.)
 };
 
+// The LDS-DMA loop of igemm_kernel addresses a row of A as descriptor base (the pixel the tile's first row reads under
+// the same tap) + a 32-bit lane offset; true when every row of a BM-row tile lies within 2^30 bytes of the first.
+// Rows of a phase are the pixels (b, i, jj) of its Hq x Wq grid in raster order, and under one tap the input pixel a
+// row reads moves, from one row to the next, by e (e = stride forward, 1 transposed: one phase's rows), by
+// e + e (Wi - Wq) where the grid wraps to its next line, and by Wi (Hi - e Hq) more where it wraps to the next image.
+// Two rows of a tile are n = min(BM, P) - 1 steps apart at most.  A tile begins at a multiple of BM, i.e. at most
+// Wq - gcd(BM, Wq) rows into a grid line, so at most (n + Wq - gcd(BM, Wq)) / Wq of those steps wrap a line
+// (dma_wraps), and likewise for images with Hq Wq; they read at most
+//   D = n e + lines * e |Wi - Wq| + images * Wi |Hi - e Hq|
+// pixels apart: the tile's own rows and the input lines they straddle (254 pixels for a stride-2 layer on 2048 x 2048,
+// whose 128-row tiles never leave a grid line; 254 + 2048 where they do), whatever the batch and the image size.
+// What fails is a PIXEL pitch above 2^28 / D floats -- over 100 000 floats from one pixel to the next in that example.
+static long dma_gcd(long a, long b) { return b == 0 ? a : dma_gcd(b, a % b); }
+// most multiples of `period` among n consecutive steps that begin at a multiple of `tile`
+static long dma_wraps(long n, long tile, long period) { return (n + period - dma_gcd(tile, period)) / period; }
+static bool igemm_dma_addressable(const lic_igemm_desc* d, const PhaseGeometry& g, int BM) {
+  const long lim = 1L << 30;
+  if (d->in_ld < 0 || d->in_ld > lim) return false;
+  const long HWi = (long)d->Hi * d->Wi, e = d->transposed ? 1 : d->stride;
+  if ((long)d->B * HWi > 0x7FFFFFFFL) return false;  // (the kernels index input pixels in 32 bits)
+  for (int ph = 0; ph < g.nphase; ++ph) {
+    const long Hq = g.Hq[ph], Wq = g.Wq[ph];
+    if (Hq <= 0 || Wq <= 0) continue;
+    const long n = std::min<long>(BM, d->B * Hq * Wq) - 1;
+    const long lines = std::min<long>((long)d->B * Hq - 1, dma_wraps(n, BM, Wq));
+    const long images = std::min<long>(d->B - 1, dma_wraps(n, BM, Hq * Wq));
+    const long D = n * e + lines * e * labs((long)d->Wi - Wq) + images * d->Wi * labs((long)d->Hi - e * Hq);
+    if (D > lim || D * d->in_ld * 4 + (long)d->Cin * 4 > lim) return false;
+  }
+  return true;
+}
+
 static int igemm_fill(const lic_igemm_desc* d, IgemmPlan& pl) {
   IgemmParams& p = pl.p;
   int rc = conv_desc_check(d);
@@ -1053,7 +1102,11 @@ static int igemm_fill(const lic_igemm_desc* d, IgemmPlan& pl) {
   pl.BM = BM;
   pl.TN = TN;
   pl.full = p.Npad % (64 * TN) == 0;
-  pl.glds = fuse || (pl.full && p.vec && p.prologue == 0);
+  // a pitch beyond the DMA loop's 32-bit lane offsets takes the register-staged loop (64-bit addresses per lane);
+  // the fused kernel has no such twin
+  const bool dma = igemm_dma_addressable(d, g, BM);
+  if (fuse && !dma) return LIC_ERR_UNSUPPORTED;
+  pl.glds = fuse || (pl.full && p.vec && p.prologue == 0 && dma);
   p.NT = (p.Npad + 64 * TN - 1) / (64 * TN);
   const PhaseOrder po = phase_order(p.nphase, p.ntaps, (int)((maxP + BM - 1) / BM));
   p.MT = po.MT;
@@ -1364,7 +1417,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
 }
 
 // LDS-DMA variant of wgrad_kernel for full tiles: both operands go
-// global -> LDS with `global_load_lds_dwordx4` (no staging registers, no ds_write pass, no vmcnt
+// global -> LDS with `buffer_load_dwordx4 ... lds` (no staging registers, no ds_write pass, no vmcnt
 // wait in front of an LDS store).  The LDS image is [64-channel sub-tile][16 px][64 ch]: thread t
 // owns pixel t/16, channels (t%16)*4.. of every sub-tile, i.e. byte t*16 of it -- exactly the
 // wave-linear destination the DMA writes.  Two buffers; each iteration is
@@ -1372,8 +1425,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
 //   done reading chunk c-1)  ->  issue DMA of chunk c+1  ->  MFMAs of chunk c.
 // SQB: the column operand is squared at the fragment read (GDN d-gamma: t^T . x^2).  A template flag, not a
 // runtime select: 48 multiplies + 48 selects per chunk in every launch cost the plain ones ~5 %.
-// FULL: every tile is complete (channel counts multiples of the tile); otherwise channels past C are
-// DMA'd from the zero page and the slab writes are guarded (288- and 640-channel layers).
+// FULL: every tile is complete (channel counts multiples of the tile); otherwise channels past C get an
+// out-of-range DMA offset (zeros) and the slab writes are guarded (288- and 640-channel layers).
 template <int TM, int TN, bool SQB = false, bool FULL = true>
 __global__ __launch_bounds__(256, (TM * TN >= 6 ? 2 : 1)) void wgrad_glds_kernel(const WgradParams p) {
   constexpr int BMt = 64 * TM, BNt = 64 * TN, NS = TM + TN;
@@ -1397,27 +1450,75 @@ __global__ __launch_bounds__(256, (TM * TN >= 6 ? 2 : 1)) void wgrad_glds_kernel
       for (int q = 0; q < 16; ++q) acc[a][b][q] = 0.0f;
 
   const int kr = tid >> 4, c16 = (tid & 15) * 4;
+  // ---- DMA addressing: `buffer_load_dwordx4 ... lds` on one descriptor per operand, rebuilt per chunk with scalar
+  // arithmetic.  A lane's 32-bit byte offset is all the vector ALU contributes; a lane that must read zeros gets an
+  // offset at or past num_records and the hardware writes zeros without touching memory (lic_halo_bf16.h).
+  //  * an operand that is not gathered walks memory linearly: the base moves 16 pixels on per chunk, the lane offset
+  //    kr * pitch + channel bytes is a loop constant, and num_records ends behind the last live pixel of the chunk --
+  //    no vector instruction per chunk;
+  //  * the gathered operand's base is the large-grid pixel that tap (r, s) pairs with the chunk's first pixel, less
+  //    WG_GBIAS bytes; a lane decodes its own pixel, and its offset is the pixel difference times the pitch plus the
+  //    bias (the difference may be negative across a row or image seam), or WG_OOB outside the large grid.
+  // wgrad_dma_addressable() (host) guarantees that every such offset stays below 2^30 + WG_GBIAS.
+  constexpr unsigned WG_OOB = 0x80000000u, WG_GBIAS = 0x40000000u;
+  const unsigned row_ld4 = (unsigned)p.row.ld * 4u, col_ld4 = (unsigned)p.col.ld * 4u;
+  const unsigned row_lin = (unsigned)kr * row_ld4 + (unsigned)c16 * 4u;
+  const unsigned col_lin = (unsigned)kr * col_ld4 + (unsigned)c16 * 4u;
+  const bool row_g = p.row.gathered != 0, col_g = p.col.gathered != 0;
+  const unsigned g_ld4 = row_g ? row_ld4 : col_ld4;  // (at most one operand is gathered: wgrad_fill)
+  const unsigned HWl = (unsigned)(p.Hl * p.Wl);
+  const int tap_h = wt.r - p.pad, tap_w = wt.s - p.pad;
+  bool row_live[TM], col_live[TN];  // !FULL: this lane's channels of sub-tile j exist
+#pragma unroll
+  for (int j = 0; j < TM; ++j) row_live[j] = FULL || m0 + c16 + 64 * j < p.row.C;
+#pragma unroll
+  for (int j = 0; j < TN; ++j) col_live[j] = FULL || n0 + c16 + 64 * j < p.col.C;
+  const float* const row_base = p.row.ptr + m0;
+  const float* const col_base = p.col.ptr + n0;
   // chunk indices past the end are clamped to the last one (harmless duplicate DMA into the idle buffer)
   auto issue = [&](int c, int buf) {
-    const WgradPixel w = wgrad_pixel(p, (long)(c < c_end ? c : c_end - 1) * WG_BK + kr, wt.r, wt.s);
-    const float* rowp = (p.row.gathered ? w.gok : w.inb)
-                            ? p.row.ptr + (p.row.gathered ? w.gpix : (long)w.pix) * p.row.ld + m0 + c16
-                            : nullptr;
-    const float* colp = (p.col.gathered ? w.gok : w.inb)
-                            ? p.col.ptr + (p.col.gathered ? w.gpix : (long)w.pix) * p.col.ld + n0 + c16
-                            : nullptr;
+    const int cc = c < c_end ? c : c_end - 1;
+    const int pk0 = cc * WG_BK;  // wave-uniform: everything derived from it alone is scalar
+    // the chunk's first pixel and its large-grid partner (scalar)
+    const int b0 = fdiv(pk0, p.dHW);
+    const int rem0 = pk0 - b0 * p.Hs * p.Ws;
+    const int hs0 = fdiv(rem0, p.dW), ws0 = rem0 - hs0 * p.Ws;
+    const long g0 = ((long)b0 * p.Hl + (hs0 * p.stride + tap_h)) * p.Wl + (ws0 * p.stride + tap_w);
+    // this lane's pixel: one decode per chunk serves all its DMAs
+    const unsigned pk = (unsigned)pk0 + (unsigned)kr;
+    const int pix = pk < (unsigned)p.Ps ? (int)pk : 0;
+    const int b = fdiv(pix, p.dHW);
+    const int rem = pix - b * p.Hs * p.Ws;
+    const int hs = fdiv(rem, p.dW), ws = rem - hs * p.Ws;
+    const int hl = hs * p.stride + tap_h, wl = ws * p.stride + tap_w;
+    const bool gok = pk < (unsigned)p.Ps && (unsigned)hl < (unsigned)p.Hl && (unsigned)wl < (unsigned)p.Wl;
+    // (modulo 2^32: the difference itself is small)
+    const unsigned dpix = (unsigned)b * HWl + (unsigned)hl * (unsigned)p.Wl + (unsigned)wl - (unsigned)g0;
+    // (arithmetic on an all-ones / zero mask, not a select: hipcc turns the select into a branch around the multiply)
+    const unsigned gokm = (unsigned)(-(int)gok);
+    const unsigned g_off = ((dpix * g_ld4 + (WG_GBIAS + (unsigned)c16 * 4u)) & gokm) | (~gokm & WG_OOB);
+    const long left = p.Ps - pk0;  // live pixels from pk0 on (>= 1)
+    const unsigned lin_rec = (unsigned)(left < WG_BK ? left : WG_BK);
+    auto rsrc = [&](const float* base, long ld, unsigned ld4, bool gathered) {
+      // (the select picks the multiplicand: one scalar 64-bit product per operand, no branch)
+      const long px = gathered ? g0 : (long)pk0;
+      const float* b_ = base + (px * ld - (gathered ? (long)(WG_GBIAS / 4) : 0L));
+      return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(b_), 0, gathered ? (int)WG_OOB : (int)(lin_rec * ld4),
+                                               0x00020000);
+    };
+    const __amdgpu_buffer_rsrc_t rs_row = rsrc(row_base, p.row.ld, row_ld4, row_g);
+    const __amdgpu_buffer_rsrc_t rs_col = rsrc(col_base, p.col.ld, col_ld4, col_g);
+    const unsigned row_off = row_g ? g_off : row_lin, col_off = col_g ? g_off : col_lin;
+    // (the 64-channel step of DMA j is the SCALAR offset: the instruction's immediate offset would move the LDS
+    // destination as well; the range check sees the lane offset alone)
 #pragma unroll
-    for (int j = 0; j < TM; ++j) {
-      const bool ok = rowp && (FULL || m0 + c16 + 64 * j < p.row.C);
-      __builtin_amdgcn_global_load_lds((lic_gptr_t)(ok ? rowp + 64 * j : g_lic_zero16),
-                                       (lic_lptr_t)&smem[buf][j][wave * 256], 16, 0, 0);
-    }
+    for (int j = 0; j < TM; ++j)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_row, (lic_lptr_t)&smem[buf][j][wave * 256], 16,
+                                               (int)(row_live[j] ? row_off : WG_OOB), 256 * j, 0, 0);
 #pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const bool ok = colp && (FULL || n0 + c16 + 64 * j < p.col.C);
-      __builtin_amdgcn_global_load_lds((lic_gptr_t)(ok ? colp + 64 * j : g_lic_zero16),
-                                       (lic_lptr_t)&smem[buf][TM + j][wave * 256], 16, 0, 0);
-    }
+    for (int j = 0; j < TN; ++j)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_col, (lic_lptr_t)&smem[buf][TM + j][wave * 256], 16,
+                                               (int)(col_live[j] ? col_off : WG_OOB), 256 * j, 0, 0);
   };
   auto compute = [&](int buf) {
     float af[TM][8], bf[TN][8];
@@ -1523,8 +1624,32 @@ long lic_pick_splits(long base, long slots, long max_sk) {
   return best;
 }
 
+// wgrad_glds_kernel addresses an operand as descriptor base (64-bit, scalar, rebuilt per chunk) + a 32-bit lane offset
+// that must stay below 2^30 (+ the bias of the gathered operand).  True when both operands of `d` can be addressed so:
+//  * linear operand: the 16 pixels of a chunk, 16 * pitch bytes;
+//  * gathered operand: from one small-grid pixel to the next its large-grid partner moves by `stride`, by
+//    stride + stride (Wl - Ws) where the small grid wraps to its next line, and by Wl (Hl - stride Hs) more where it
+//    wraps to the next image (as igemm_dma_addressable, with chunks of 16 for tiles); with n = min(16, Ps) - 1
+//      D = n stride + lines * stride |Wl - Ws| + images * Wl |Hl - stride Hs|
+//    pixels -- a line of the large grid or two, whatever the batch.
+// What fails is a PIXEL pitch above 2^28 / D floats (2^24 floats for the linear operand); such operands take the
+// register-staged kernel, whose addresses are 64-bit per lane.
+static bool wgrad_dma_addressable(const lic_wgrad_desc* d) {
+  const long lim = 1L << 30;
+  if (d->p_ld < 0 || d->g_ld < 0 || d->p_ld > lim || d->g_ld > lim) return false;
+  if (16 * d->p_ld * 4 > lim) return false;
+  const long HWs = (long)d->Hs * d->Ws, HWl = (long)d->Hl * d->Wl, st = d->stride;
+  const long n = std::min<long>(16, d->B * HWs) - 1;
+  const long lines = std::min<long>((long)d->B * d->Hs - 1, dma_wraps(n, 16, d->Ws));
+  const long images = std::min<long>(d->B - 1, dma_wraps(n, 16, HWs));
+  const long D = n * st + lines * st * labs((long)d->Wl - d->Ws) + images * d->Wl * labs((long)d->Hl - st * d->Hs);
+  if (D > lim || HWl > 0x7FFFFFFFL) return false;
+  return std::max<long>(D, 16) * d->g_ld * 4 + (long)d->Cg * 4 <= lim;
+}
+
 static int wg_plan(const lic_wgrad_desc* d, WgPlan* pl) {
   if (wgrad_desc_check(d) != LIC_OK) return LIC_ERR_INVALID;
+  pl->dma = wgrad_dma_addressable(d);
   pl->Cm = d->g_is_row ? d->Cg : d->Cp;
   pl->Cn = d->g_is_row ? d->Cp : d->Cg;
   pl->ntaps = d->kh * d->kw;
@@ -1540,7 +1665,8 @@ static int wg_plan(const lic_wgrad_desc* d, WgPlan* pl) {
   // 192 x 192 tiles (LDS-DMA kernel only) when both channel counts are multiples of 192: half the
   // L2 -> LDS bytes per MFMA of the 64 x 192 tile
   const long chunks16 = ((long)d->B * d->Hs * d->Ws + 255) / 256;  // splits of >= 16 chunks available
-  if (pl->vec && pl->Cm % 192 == 0 && pl->Cn % 192 == 0 && chunks16 * pl->ntaps >= 512 &&  // else too few workgroups
+  if (pl->vec && pl->dma && pl->Cm % 192 == 0 && pl->Cn % 192 == 0 &&
+      chunks16 * pl->ntaps >= 512 &&  // else too few workgroups
       !(d->g_is_row ? d->sq_g : d->sq_p)) {  // (the DMA kernel squares the column operand only)
     pl->TM = 3;
     pl->TN = 3;
@@ -1548,7 +1674,7 @@ static int wg_plan(const lic_wgrad_desc* d, WgPlan* pl) {
   if (d->force_tm || d->force_tn) {  // descriptor override: one of the instantiated shapes
     const int tm = d->force_tm, tn = d->force_tn;
     const bool sq_row = d->g_is_row ? d->sq_g : d->sq_p;
-    const bool t33 = tm == 3 && tn == 3 && pl->Cm % 192 == 0 && pl->Cn % 192 == 0 && !sq_row;
+    const bool t33 = tm == 3 && tn == 3 && pl->dma && pl->Cm % 192 == 0 && pl->Cn % 192 == 0 && !sq_row;
     const bool listed = (tm == 1 && (tn == 1 || tn == 3)) || (tm == 2 && tn >= 1 && tn <= 3);
     if (!pl->vec || !(t33 || listed)) return LIC_ERR_UNSUPPORTED;
     pl->TM = tm;
@@ -1620,7 +1746,8 @@ static const KernelVariant<WgradParams>* find_variant(const lic_wgrad_desc* d, c
   if (!pl.vec) return lic_find_variant(g_wgrad_variants, wgrad_key(false, 1, 1, false, false));
   const bool full = (pl.Cm % (64 * pl.TM) == 0) && (pl.Cn % (64 * pl.TN) == 0);
   const bool sq_row = d->g_is_row ? d->sq_g : d->sq_p, sq_col = d->g_is_row ? d->sq_p : d->sq_g;
-  if (sq_row) return lic_find_variant(g_wgrad_variants, wgrad_key(false, pl.TM, pl.TN, true, full));
+  // (a pitch beyond the DMA kernel's 32-bit lane offsets: the register-staged kernel forms 64-bit addresses)
+  if (sq_row || !pl.dma) return lic_find_variant(g_wgrad_variants, wgrad_key(false, pl.TM, pl.TN, true, full));
   return lic_find_variant(g_wgrad_variants, wgrad_key(true, pl.TM, pl.TN, sq_col, full));
 }
 
