@@ -52,7 +52,9 @@ the per-pixel layers, one table launch and one launch of each encoder kernel (`l
 with their own rANS sub-streams, the container (LICBITS6) puts the base layer first, and `decompress_base` /
 `decompress_base_image` decode z and the base layer alone.  `_LayeredCodec` holds what it shares with `ContextCodec`,
 the one-layer case: gather, front end and step loop over a list of layers (`lic_ctx_gather_layers`,
-`lic_rans_decode_step_layers`: all layers of a step in one launch each).
+`lic_rans_decode_step_layers`: all layers of a step in one launch each), the decode of many bitstreams in one loop
+(`_decompress_many`) and the z coder.  The layouts of the ragged calls are pure numpy functions here: `merged_wavefront`,
+`ragged_encode_plan`, `plane_layout`, `z_plan`.
 """
 from __future__ import annotations
 
@@ -501,6 +503,88 @@ def z_encode_plan(pixels, M: int, G: int):
     return images, blocks, np.array([int(P) * M for P in pixels], np.int64), row0, word_off, esc_off
 
 
+class PlaneLayout(NamedTuple):
+    """what `plane_layout` returns: where the planes of every item lie in the two flat fp32 buffers of a ragged call"""
+    y_at: np.ndarray          # [items] int64: the float of the latent buffer item i's first plane starts at
+    psi_at: np.ndarray        # [items] int64: likewise in the psi buffer
+    y_len: int                # floats of the latent buffer
+    psi_len: int              # floats of the psi buffer
+    desc: np.ndarray          # [nimg][CTX_IMAGE_WORDS] int64 (lic.h): Y_BASE, Y_ROW, Y_ORIGIN, PSI_BASE, H, W, R, 0
+    pixels: np.ndarray        # [nimg] int64: the pixels of every framed plane, (h + 2 frame)(w + 2 frame)
+
+
+def plane_layout(items, y_pix: int, cpsi: int, frame: int, slice_rows_list) -> PlaneLayout:
+    """The flat buffers of the ragged kernels.  items: [(B, h, w)]; item after item, each on a multiple of 4 floats of
+    either buffer, its B planes one behind the other: latent planes of y_pix floats per pixel inside a zero frame of
+    `frame` pixels (the codec's pad when decoding, 0 when encoding: plain NHWC planes), psi planes of cpsi floats per
+    pixel without a frame.  slice_rows_list: the slice_rows of every IMAGE (None: no slices), items' images in order.
+    Image b of an item gets the descriptor (first float of its plane, floats per framed row, the float of pixel (0, 0)
+    inside the plane, first float of its psi plane, h, w, min(R, h))."""
+    items = [(int(B), int(h), int(w)) for B, h, w in items]
+    slice_rows_list = list(slice_rows_list)
+    nimg = sum(B for B, _, _ in items)
+    if len(slice_rows_list) != nimg:
+        raise CodecError("one slice_rows entry per image expected")
+    y_at, psi_at = np.zeros(len(items), np.int64), np.zeros(len(items), np.int64)
+    desc, pixels = np.zeros((nimg, L.CTX_IMAGE_WORDS), np.int64), np.zeros(nimg, np.int64)
+    y_len = psi_len = img = 0
+    for i, (B, h, w) in enumerate(items):
+        y_at[i], psi_at[i] = (y_len + 3) // 4 * 4, (psi_len + 3) // 4 * 4
+        Wp, plane = w + 2 * frame, (h + 2 * frame) * (w + 2 * frame)
+        for b in range(B):
+            R = slice_rows_list[img]
+            desc[img, :7] = (y_at[i] + b * plane * y_pix, Wp * y_pix, (frame * Wp + frame) * y_pix,
+                             psi_at[i] + b * h * w * cpsi, h, w, h if R is None else min(R, h))
+            pixels[img] = plane
+            img += 1
+        y_len, psi_len = int(y_at[i]) + B * plane * y_pix, int(psi_at[i]) + B * h * w * cpsi
+    return PlaneLayout(y_at, psi_at, y_len, psi_len, desc, pixels)
+
+
+class ZPlan(NamedTuple):
+    """what `z_plan` returns: `lic_rans_z_decode`'s per-image arguments and where every item's z lies"""
+    windows: list             # (z_lo, z_S) per image
+    nsyms: list               # its symbols
+    bases: list               # the float of the flat z buffer its plane starts at
+    z_len: int                # floats of that buffer
+    at: list                  # per item: the float its first plane starts at; None for an item without rANS-coded z
+
+
+def z_plan(z_items, M: int) -> ZPlan:
+    """The flat buffer the rANS-coded hyper-latents of a call are decoded into.  z_items: per item (z_shape, (z_lo,
+    z_S)), or None for an item whose z is range-coded and takes no room.  Item after item, each on a multiple of 4
+    floats, its B planes of h4 * w4 * M floats (pixel by pixel, channel by channel) one behind the other."""
+    windows, nsyms, bases, at, z_len = [], [], [], [], 0
+    for entry in z_items:
+        if entry is None:
+            at.append(None)
+            continue
+        (B, _, h4, w4), win = entry
+        z_len = (z_len + 3) // 4 * 4
+        at.append(z_len)
+        for b in range(B):
+            windows.append((int(win[0]), int(win[1])))
+            nsyms.append(h4 * w4 * M)
+            bases.append(z_len)
+            z_len += h4 * w4 * M
+    return ZPlan(windows, nsyms, bases, z_len, at)
+
+
+def _crc32_of(a) -> int:
+    """CRC-32 of an array's elements in C order: the checksum of an image's latent symbols (int32)"""
+    return zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
+
+
+def _check_latents(got: np.ndarray, c0: int, c1: int, want, what: str = ""):
+    """got [B, h, w, channels] int32: the rounded decoded latents; want [B]: the encoder's CRC-32 of channels [c0, c1)
+    of every image.  A decoder whose tables differ from the encoder's by one count decodes garbage silently; with the
+    checksum it fails loudly instead, naming the image and `what` (", layer l" for a layered codec)."""
+    for b in range(got.shape[0]):
+        if _crc32_of(got[b, :, :, c0:c1]) != int(want[b]):
+            raise CodecError(f"image {b}{what}: decoded latents do not match the encoder's checksum "
+                             "(encoder and decoder built different probability tables, or the stream is damaged)")
+
+
 def table_chunks(costs, budget: int):
     """Consecutive runs [(first, end)] of whole items whose costs (table bytes) add up to `budget` at the most; an
     item that is larger than the budget runs alone."""
@@ -576,6 +660,14 @@ def _z_coder_of(strings) -> str:
     if z_coder == "rans" and strings.get("coder", "range") != "rans":
         raise CodecError("the strings name z_coder 'rans' without coder 'rans': only 'rans' streams carry rANS z streams")
     return z_coder
+
+
+def _z_streams(strings, n: int):
+    """the n rANS sub-streams of the hyper-latent in `strings` and their escape lists, or CodecError"""
+    zs, zescs = strings["z"], strings.get("z_esc")
+    if zescs is None or isinstance(zs, (bytes, bytearray)) or len(zs) != n or len(zescs) != n:
+        raise CodecError("one z stream and one escape list per image and group expected")
+    return list(zs), list(zescs)
 
 
 def _stage_y_and_z(ys, escs, nimg: int, zs, zescs, nz: int, G: int, name=_image_name, zname=None) -> _RansStaging:
@@ -759,9 +851,18 @@ class _LayeredCodec:
     layer's rows from the one latent plane, the per-step front end and the rANS step loop, written once over
     `self.layers`.  A single layer that covers the whole plane goes through `lic_ctx_gather` and
     `lic_rans_decode_step_groups`; anything else through `lic_ctx_gather_layers` and `lic_rans_decode_step_layers`,
-    one launch each for all layers of a step.  `_run_merged_steps` is that loop for many latents of different sizes
-    (`lic_ctx_gather_layers_ragged`, `lic_rans_decode_step_layers_ragged`); `ContextCodec.decompress_many` keeps its
-    own one-layer entries."""
+    one launch each for all layers of a step.
+
+    `_decompress_many` is `decompress_many` of both: many bitstreams of different sizes in one loop,
+    `_run_merged_steps`, whose gather (`_gather_rows`) and decode launch are `lic_ctx_gather_ragged` and
+    `lic_rans_decode_step_ragged` for the codec of one layer, `lic_ctx_gather_layers_ragged` and
+    `lic_rans_decode_step_layers_ragged` for a layered one.  A class adds `_item_streams` (an item's refusals, where its
+    streams sit in its strings, whether z may be range-coded) and `_finish` (checksums and what a result holds).
+    The layouts are module functions: `plane_layout`, `z_plan`, `merged_wavefront`.
+
+    Also here, because they do not know how many layers y has: the rANS coder of z (`_z_symbols`, `_encode_z`,
+    `_decode_z`), the device encoder of one layer's y streams (`_encode_y_device`), and what the containers of both
+    codecs share (`_family`, `_shapes`, `_one_window_one_G`)."""
 
     # False: the layered entries are launched once per layer instead of once per step (tools/bench_codec.py measures
     # what the merged launches save); bytes and results are the same
@@ -904,36 +1005,70 @@ class _LayeredCodec:
                     shift(state, l, 4 * L.RANS_STATE_WORDS), (L.RansLayer * 1)(t), 1, nimg, G, n, self.y_W, F_._ptr(own),
                     F_._ptr(yflat), npad, y_pix, F_._stream()), "lic_rans_decode_step_layers")
 
-    def _run_merged_steps(self, sched: MergedSchedule, layers, blocks, G: int, yflat: torch.Tensor, y_pix: int,
-                          d_desc: torch.Tensor, d_pixels: torch.Tensor, psiflat: torch.Tensor, cpsi: int):
-        """The step loop of many latents of different sizes (`merged_wavefront`), every layer of `layers` in it: per
-        step ONE `lic_ctx_gather_layers_ragged` from the flat buffers `yflat` (zero-framed planes of y_pix channels per
-        pixel) and `psiflat`, per layer the per-pixel layers and the table kernel over the step's rows of every image,
-        and ONE `lic_rans_decode_step_layers_ragged`, which writes the values where the next gather reads them.
-        d_desc [nimg, CTX_IMAGE_WORDS] (device): the planes; d_pixels [nimg]: their framed pixel counts; blocks: the six
-        staging arguments, one block per layer, image and group, layer-major.  The schedule goes up once; nothing in
-        the loop copies, waits for the device or computes on the host."""
+    def _one_layer_ragged(self, layers, y_pix: int) -> bool:
+        """Which entries a ragged call launches: `_whole_plane`'s rule for a codec of one layer.  A layered codec keeps
+        the `_layers_ragged` entries for its base layer alone too, which `_whole_plane` alone would hand to the
+        one-layer entries: the same bytes, but they are the launches tests/test_gpu_scalable_decode_many.py counts."""
+        return len(self.layers) == 1 and self._whole_plane(layers, y_pix)
+
+    def _gather_rows(self, layers, yflat: torch.Tensor, y_pix: int, d_desc: torch.Tensor, row_image: torch.Tensor,
+                     row_pix: torch.Tensor, psiflat: torch.Tensor, cpsi: int):
+        """One gather launch for rows of different images: `_gather_layers` over the flat buffers of `plane_layout`.
+        yflat, psiflat: the buffers all planes lie in; d_desc [nimg, CTX_IMAGE_WORDS] int64 (device): where, and h, w,
+        R of each; row_image, row_pix [n] int64 (device): the image and raster index of every row
+        -> per layer (windows [n, 12 M_l, 1, 1], comb [n, cctx_l + cpsi]) as `_gather_layers`.  `lic_ctx_gather_ragged`
+        for the codec of one layer, `lic_ctx_gather_layers_ragged` for a layered one (`_one_layer_ragged`)."""
+        n, nt, nimg, dev = row_pix.numel(), len(self.taps), d_desc.shape[0], yflat.device
+        taps = self._taps_on(dev)
+        rows = [(torch.empty((n, nt * ly.M, 1, 1), device=dev, dtype=torch.float32),
+                 torch.empty((n, ly.cctx + cpsi), device=dev, dtype=torch.float32)) for ly in layers]
+        if self._one_layer_ragged(layers, y_pix):
+            (win, comb), ly = rows[0], layers[0]
+            L.check(L.load().lic_ctx_gather_ragged(
+                F_._ptr(yflat), yflat.numel(), y_pix, F_._ptr(d_desc), nimg, ly.M, F_._ptr(taps), nt, F_._ptr(row_image),
+                F_._ptr(row_pix), n, F_._ptr(win), F_._ptr(psiflat), psiflat.numel(), cpsi,
+                C.c_void_p(comb.data_ptr() + 4 * ly.cctx), comb.shape[1], L.CTX_AUTO, F_._stream()), "lic_ctx_gather_ragged")
+            return rows
         if len(layers) > L.MAX_LAYERS:
             raise CodecError(f"{len(layers)} layers: the layered kernels take {L.MAX_LAYERS} at the most")
-        dev, nt, nimg, lib = yflat.device, len(self.taps), d_desc.shape[0], L.load()
-        taps = self._taps_on(dev)
+        ctx = (L.CtxLayer * len(layers))()
+        for c, ly, (win, comb) in zip(ctx, layers, rows):
+            c.win, c.comb, c.comb_ld, c.c0, c.M = win.data_ptr(), comb.data_ptr() + 4 * ly.cctx, comb.shape[1], ly.c0, ly.M
+        L.check(L.load().lic_ctx_gather_layers_ragged(
+            F_._ptr(yflat), yflat.numel(), y_pix, F_._ptr(d_desc), nimg, F_._ptr(taps), nt, F_._ptr(row_image),
+            F_._ptr(row_pix), n, F_._ptr(psiflat), psiflat.numel(), cpsi, ctx, len(layers), L.CTX_AUTO, F_._stream()),
+            "lic_ctx_gather_layers_ragged")
+        return rows
+
+    def _run_merged_steps(self, sched: MergedSchedule, layers, blocks, G: int, yflat: torch.Tensor, y_pix: int,
+                          layout: PlaneLayout, psiflat: torch.Tensor, cpsi: int):
+        """The step loop of many latents of different sizes (`merged_wavefront`), every layer of `layers` in it: per
+        step ONE gather (`_gather_rows`) from the flat buffers `yflat` (zero-framed planes of y_pix channels per pixel)
+        and `psiflat`, per layer the per-pixel layers and the table kernel over the step's rows of every image, and ONE
+        decode launch, which writes the values where the next gather reads them: `lic_rans_decode_step_ragged` for the
+        codec of one layer, `lic_rans_decode_step_layers_ragged` for a layered one (`_one_layer_ragged`).  layout: the
+        buffers' `plane_layout`; blocks: the six staging arguments, one block per layer, image and group, layer-major.
+        Schedule and layout go up once; nothing in the loop copies, waits for the device or computes on the host."""
+        dev, nimg, lib = yflat.device, layout.desc.shape[0], L.load()
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        d_rows, d_seg, d_ybase = up(sched.rows), up(sched.seg), d_desc[:, 0].contiguous()
+        one = self._one_layer_ragged(layers, y_pix)
+        d_desc, d_rows, d_seg, d_pixels = up(layout.desc), up(sched.rows), up(sched.seg), up(layout.pixels)
+        # the planes' first floats: an upload for the one-layer entries, a device copy of the column for the layered
+        # ones, as each loop did before they became one (their kernel traces stay what they were)
+        d_ybase = up(layout.desc[:, 0]) if one else d_desc[:, 0].contiguous()
         packed = [ly.prepack() for ly in layers]
-        ctx, rans, off = (L.CtxLayer * len(layers))(), (L.RansLayer * len(layers))(), sched.step_off
+        rans, off = (L.RansLayer * len(layers))(), sched.step_off
         for t in range(sched.T):
             a, e = int(off[t]), int(off[t + 1])
-            rows = []
-            for c, ly in zip(ctx, layers):
-                win = torch.empty((e - a, nt * ly.M, 1, 1), device=dev, dtype=torch.float32)
-                comb = torch.empty((e - a, ly.cctx + cpsi), device=dev, dtype=torch.float32)
-                c.win, c.comb, c.comb_ld, c.c0, c.M = win.data_ptr(), comb.data_ptr() + 4 * ly.cctx, comb.shape[1], ly.c0, ly.M
-                rows.append((win, comb))
-            L.check(lib.lic_ctx_gather_layers_ragged(
-                F_._ptr(yflat), yflat.numel(), y_pix, F_._ptr(d_desc), nimg, F_._ptr(taps), nt, F_._ptr(d_rows[0, a:e]),
-                F_._ptr(d_rows[1, a:e]), e - a, F_._ptr(psiflat), psiflat.numel(), cpsi, ctx, len(layers), L.CTX_AUTO,
-                F_._stream()), "lic_ctx_gather_layers_ragged")
+            rows = self._gather_rows(layers, yflat, y_pix, d_desc, d_rows[0, a:e], d_rows[1, a:e], psiflat, cpsi)
             params = [ly.params_at(win, None, pk, comb, self.y_W) for ly, pk, (win, comb) in zip(layers, packed, rows)]
+            if one:
+                ((center, tables),) = params
+                L.check(lib.lic_rans_decode_step_ragged(
+                    *blocks, F_._ptr(tables), F_._ptr(center), F_._ptr(d_seg[t]), nimg, G, e - a, y_pix, self.y_W,
+                    F_._ptr(d_rows[2, a:e]), F_._ptr(yflat), F_._ptr(d_ybase), F_._ptr(d_pixels), yflat.numel(),
+                    F_._stream()), "lic_rans_decode_step_ragged")
+                continue
             for r, ly, (center, tables) in zip(rans, layers, params):
                 r.tables, r.center, r.c0, r.M = tables.data_ptr(), center.data_ptr(), ly.c0, ly.M
             L.check(lib.lic_rans_decode_step_layers_ragged(
@@ -941,188 +1076,130 @@ class _LayeredCodec:
                 F_._ptr(yflat), F_._ptr(d_ybase), F_._ptr(d_pixels), yflat.numel(), y_pix, F_._stream()),
                 "lic_rans_decode_step_layers_ragged")
 
+    # ---- many bitstreams in one step loop -------------------------------------------------------
+    def _what(self, l: int) -> str:
+        """how a message names layer l of an image: not at all in the codec of one layer"""
+        return f", layer {l}" if len(self.layers) > 1 else ""
 
-class ContextCodec(_LayeredCodec):
-    """compress(x) -> byte strings, decompress(strings) -> x_hat, through the model's masked-conv
-    context (ContextModels.py:3-36): the parameters of pixel (i, j) of y depend on the already decoded
-    pixels above / left of it, so decoding is serial -- but only along a wavefront: pixels with equal
-    j + 3 i are independent (see _wavefront), so it takes w + 3 (h - 1) dependent steps of {12-tap context
-    GEMM -> entropy-parameter MLP -> table kernel} on the GPU, each over a batch of pixels, and their
-    symbols on the host coder in between.
+    def _decompress_many(self, items, use, z_windows, names) -> List[Dict]:
+        """`decompress_many` of both codecs, for the layers `use` (the codec's first ones).  A class supplies
+        `_item_streams` (an item's refusals and its streams) and `_finish` (its result).
 
-    Encoder and decoder must build BIT-IDENTICAL tables, so both evaluate the context as the same
-    per-pixel GEMM over the 12 live taps ([N, 12M, 1, 1] "images": the kernels' results for one row do
-    not depend on the batch it sits in, and their split-K choice depends on per-image geometry only --
-    the property tests/test_gpu_fullsize.py pins); the encoder simply has all N = B*h*w pixels at
-    once.  One y stream per image (symbols step by step, pixel by pixel, channel by channel) + one z stream
-    for the batch.
-
-    `coder`: "range" (the default) codes y with the host range coder as described above; "rans" codes y with
-    the 64-lane interleaved rANS coder of lic_codec.h, whose decoder is a device kernel
-    (`lic_rans_decode_step`): the step loop is then {gather -> per-pixel layers -> tables -> decode}, all
-    asynchronous launches, and the host reads back one small block after the last step.  z keeps the range coder
-    unless `z_coder` says otherwise.
-    Its kernels take `y_W` from 1 to 64 (RANS_MAX_W); the constructor refuses a wider window for this coder.
-
-    `encoder`: where `compress` codes the y streams.  "host" (the default) gathers the tables into wavefront order,
-    copies them to the host and runs the C++ encoder, one image after the other; "device" (coder "rans" only) runs
-    `lic_rans_encode_pick` + `lic_rans_encode` on the tables where they were built and copies back state blocks,
-    streams and escape lists only.  Both write the same bytes.
-
-    `groups`: sub-streams per image of the "rans" coder (1 to 8, `rans_deal`).  1 (the default) is the rANS-64
-    format; with G > 1 `strings["groups"]` is G and `strings["y"]`, `strings["y_esc"]` hold B * G entries,
-    image-major (entry b * G + g), coded and decoded by G waves per image.  `decompress` reads G from the strings.
-
-    `slice_rows`: None (the default) or R >= 1, coder "rans" only: latent rows per slice.  A context tap (dr, ds) with
-    dr < 0 of pixel (i, j) contributes y_hat[i + dr, j + ds] only if (i mod R) + dr >= 0 and zero otherwise, exactly
-    as a tap above the image does; taps of the pixel's own row are untouched.  The slices then advance together
-    (`wavefront`): fewer, wider steps, for the rate the first rows of every slice lose with their context.  The model
-    is not told: encoder and decoder evaluate the same layers on the same masked windows, so their tables agree and
-    y_hat, x_hat are what the codec without slices reconstructs; only the bytes differ.  R >= h is that codec, byte
-    for byte.  `strings["slice_rows"]` is R when slicing is on; `decompress` reads it from the strings.
-
-    `z_coder`: "range" (the default: one host range-coder stream for the batch's z) or "rans" (coder "rans" only): every
-    image's z as `groups` rANS-64 sub-streams of its own, coded by kernels (`_encode_z`, `_decode_z`) for any window
-    z_S >= 2.  Then `strings["z_coder"]` is "rans" and `strings["z"]`, `strings["z_esc"]` are lists of B * G byte
-    strings, image-major; the decoders read `z_coder` from the strings.  Nothing else changes: y streams, `y_crc32`
-    and the decoded z_hat, y_hat, x_hat are bit for bit those of "range"."""
-
-    def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range",
-                 encoder: str = "host", groups: int = 1, slice_rows: int = None, z_coder: str = "range"):
-        if z_coder not in Z_CODERS:
-            raise CodecError(f"unknown z_coder {z_coder!r}: expected one of {Z_CODERS}")
-        if z_coder == "rans" and coder != "rans":
-            raise CodecError(f"z_coder='rans' needs coder='rans': the {coder!r} coder has no container for rANS z streams")
-        if z_coder == "rans" and int(z_S) < 2:
-            raise CodecError(f"z_S = {int(z_S)}: z_coder='rans' needs a window of at least 2 symbols")
-        self.z_coder = z_coder
-        if coder not in CODERS:
-            raise CodecError(f"unknown coder {coder!r}: expected one of {CODERS}")
-        if encoder not in ENCODERS:
-            raise CodecError(f"unknown encoder {encoder!r}: expected one of {ENCODERS}")
-        if encoder == "device" and coder != "rans":
-            raise CodecError(f"encoder='device' needs coder='rans': the {coder!r} coder has no device encoder")
-        if int(y_W) < 1:
-            raise CodecError(f"y_W = {int(y_W)}: the window half-width must be at least 1")
-        if coder == "rans" and int(y_W) > RANS_MAX_W:
-            # the only rANS decoder is the device kernel: a wider stream could be written but never read
-            raise CodecError(f"y_W = {int(y_W)}: coder='rans' takes windows of 1 to {RANS_MAX_W} "
-                             "(the limit of its device kernels); the range coder has no such limit")
-        self.model, self.z_lo, self.z_S, self.y_W, self.coder = model, int(z_lo), int(z_S), int(y_W), coder
-        self.encoder = encoder
-        self.groups = _groups(groups)
-        if self.groups > 1 and coder != "rans":
-            raise CodecError(f"groups={self.groups} needs coder='rans': the {coder!r} coder has one stream per image")
-        self.slice_rows = None if slice_rows is None else _slice_rows(slice_rows)
-        if self.slice_rows is not None and coder != "rans":
-            raise CodecError(f"slice_rows={self.slice_rows} needs coder='rans': the {coder!r} coder has no sliced format")
-        # the one-layer case of `_LayeredCodec`: all M channels, the model's one context model and MLP
-        self._set_layers([CodecLayer(model, "context_model", "entropy_parameters")])
-
-    def _ctx_weight(self):
-        return self.layers[0].ctx_weight()
-
-    def _prepack(self):
-        """the per-pixel layers of the codec's one layer, packed once (`CodecLayer.prepack`)"""
-        return self.layers[0].prepack()
-
-    def _act_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None) -> torch.Tensor:
-        """`CodecLayer.act_at` of the codec's one layer; `layers` is what `_prepack` gave"""
-        return self.layers[0].act_at(windows, psi_px, layers, comb)
-
-    def _params_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None):
-        """`_act_at`'s arguments -> (center [N, M], tables [N*M, S+1]) on the device"""
-        return self.layers[0].params_at(windows, psi_px, layers, comb, self.y_W)
-
-    def _gather_ragged(self, yflat: torch.Tensor, images: torch.Tensor, row_image: torch.Tensor, row_pix: torch.Tensor,
-                       psiflat: torch.Tensor, cpsi: int):
-        """One `lic_ctx_gather_ragged` launch: `_gather` for rows of different images.  yflat, psiflat: the flat
-        buffers all planes lie in; images [nimg, CTX_IMAGE_WORDS] int64 (device): where, and h, w, R of each;
-        row_image, row_pix [n] int64 (device): the image and raster index of every row -> (windows, comb) as `_gather`"""
-        M, n, nt, dev = self.model.M, row_pix.numel(), len(self.taps), yflat.device
-        cctx = self.model.context_model.masked.out_channels
-        win = torch.empty((n, nt * M, 1, 1), device=dev, dtype=torch.float32)
-        comb = torch.empty((n, cctx + cpsi), device=dev, dtype=torch.float32)
-        L.check(L.load().lic_ctx_gather_ragged(
-            F_._ptr(yflat), yflat.numel(), M, F_._ptr(images), images.shape[0], M, F_._ptr(self._taps_on(dev)), nt,
-            F_._ptr(row_image), F_._ptr(row_pix), n, F_._ptr(win), F_._ptr(psiflat), psiflat.numel(), cpsi,
-            C.c_void_p(comb.data_ptr() + 4 * cctx), comb.shape[1], L.CTX_AUTO, F_._stream()), "lic_ctx_gather_ragged")
-        return win, comb
-
-    def _gather(self, y: torch.Tensor, geometry, h: int, w: int, pix: torch.Tensor, slice_rows, psi_flat=None):
-        """One `lic_ctx_gather` launch.  y: fp32 latents of B images, pixel (i, j) of image b at float
-        b * batch + origin + i * row + j * M for geometry = (batch, row, origin); pix: int64 raster indices (device)
-        of the n pixels wanted; psi_flat [B, h*w, 2M] or None.
-        -> (windows [B*n, 12M, 1, 1] with zeros for taps outside the image or the pixel's slice,
-            comb [B*n, 4M] whose last 2M columns hold the pixels' psi, the first 2M still unwritten; None without psi)"""
-        return self._gather_layers(y, self.model.M, geometry, h, w, pix, slice_rows, psi_flat)[0]
-
-    def _windows_all(self, y_hat: torch.Tensor, slice_rows: int = None, psi: torch.Tensor = None):
-        """[B, M, h, w] -> [B*h*w, 12M, 1, 1]: the live taps of every pixel (zeros outside the image and, with
-        `slice_rows`, outside the pixel's slice).  With psi [B, 2M, h, w]: -> (those windows, `_gather`'s comb)"""
-        F_._require_cuda(y_hat, psi)
-        B, M, h, w = y_hat.shape
-        y = F_._nhwc(y_hat)
-        pix = torch.arange(h * w, device=y.device, dtype=torch.int64)
-        win, comb = self._gather(y, (h * w * M, w * M, 0), h, w, pix, slice_rows,
-                                 None if psi is None else F_._nhwc(psi).view(B, h * w, -1))
-        return win if psi is None else (win, comb)
-
-    @torch.no_grad()
-    def compress(self, x: torch.Tensor) -> Dict:
-        m = self.model
-        out = m.analysis_hyperprior(x, training=False)
-        y_in, z_in = out["y_in"].contiguous(), out["z_in"]
-        B, M, h, w = y_in.shape
-        if self.z_coder == "rans":
-            z_bytes, z_esc = self._encode_z(list(self._z_symbols(z_in)))
+        Host first, item by item, lowest index first and inside an item G, then y, then z: every refusal, the blocks of all
+        layers staged layer-major (block (l * nimg + image) * G + g) with the z blocks of the items whose hyper-latent
+        is rANS-coded behind them (`_stage_y_and_z`), the schedule (`merged_wavefront`) and the z buffer (`z_plan`).
+        Then the device: those z in one `lic_rans_z_decode` launch per window (`_decode_z`), a range-coded z on the
+        host, the hyper-decoder per item exactly as `decompress` runs it; all psi planes and all zero-framed latent
+        planes in two flat buffers (`plane_layout`); ONE loop of T steps (`_run_merged_steps`): no copy, no
+        synchronisation, no host arithmetic; one read-back of the state blocks; `_finish` per item on a view of its
+        planes."""
+        m, p, M = self.model, self.pad, self.model.M
+        items = list(items)
+        if not items:
+            return []
+        y_pix = sum(ly.M for ly in use)                    # the layers are consecutive from channel 0
+        names = [f"item {i}" for i in range(len(items))] if names is None else list(names)
+        z_windows = [(self.z_lo, self.z_S)] * len(items) if z_windows is None else list(z_windows)
+        G, shapes, Rs, owner, zowner, z_items = None, [], [], [], [], []
+        ys, escs, zs, zescs = [[] for _ in use], [[] for _ in use], [], []
+        for i, ((strings, shape, z_shape), win) in enumerate(zip(items, z_windows)):
+            try:
+                g = _groups(strings.get("groups", 1))
+                if G is not None and g != G:
+                    raise CodecError(f"{g} sub-streams per image, {names[0]} has {G}: one call decodes one G")
+                coded, z = self._item_streams(strings, shape, z_shape, g, len(use))
+                R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
+            except CodecError as err:
+                raise CodecError(f"{names[i]}: {err}") from None
+            G, (B, _, h, w) = g, shape
+            shapes += [(h, w)] * B
+            Rs += [R] * B
+            owner += [(i, b) for b in range(B)]
+            for l, (y, esc, _) in enumerate(coded):
+                ys[l] += list(y)
+                escs[l] += list(esc)
+            z_items.append(None if z is None else (z_shape, win))
+            if z is not None:                              # its z blocks ride behind the y blocks in the one staging
+                zowner += [(i, b) for b in range(B)]
+                zs += z[0]
+                zescs += z[1]
+        nimg = len(shapes)
+        of = lambda own: (lambda img: f"{names[own[img][0]]}: image {own[img][1]}")
+        yname = lambda img: of(owner)(img % nimg) + self._what(img // nimg)
+        ys, escs = [s for y in ys for s in y], [e for esc in escs for e in esc]
+        if zowner:
+            staged = _stage_y_and_z(ys, escs, len(use) * nimg, zs, zescs, len(zowner), G, yname, of(zowner))
         else:
-            z_bytes = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in)
-        psi = m.hyper_decoder(z_in).float()
-        win, comb = self._windows_all(out["y_in"], self.slice_rows, psi)
-        center, tables = self._params_at(win, None, self._prepack(), comb)
-        y_sym = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
-        # symbols leave in the decoder's wavefront order (see _wavefront), M channels per pixel
-        steps = self._wavefront(h, w, self.slice_rows)
-        order = np.concatenate([ii * w + jj for ii, jj in steps])
-        step_len = [len(ii) * M for ii, _ in steps]
-        strings = {"z": z_bytes}
-        if self.z_coder == "rans":
-            strings.update(z_coder="rans", z_esc=z_esc)
-        if self.groups > 1:
-            strings["groups"] = self.groups
-        if self.slice_rows is not None:
-            strings["slice_rows"] = self.slice_rows
-        if self.encoder == "device":
-            y_streams, y_esc = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, M)
-            strings.update(coder="rans", y_esc=y_esc)
-            return self._compressed(x, out, strings, y_streams, y_esc, y_sym, y_in, z_in)
-        perm = torch.from_numpy(order).to(y_in.device)
-        idx = (y_sym - center + self.y_W).view(B, h * w, M)[:, perm].cpu().numpy().reshape(B, h * w * M)
-        tabs = tables.view(B, h * w, M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * M, -1)
-        if self.coder == "rans":
-            pairs = [rans_encode_grouped(tabs[b], idx[b], step_len, self.groups) for b in range(B)]
-            y_streams, y_esc = [s for p in pairs for s in p[0]], [e for p in pairs for e in p[1]]
-            strings.update(coder="rans", y_esc=y_esc)
-        else:
-            y_streams, y_esc = [rc_encode(tabs[b], idx[b]) for b in range(B)], []
-        return self._compressed(x, out, strings, y_streams, y_esc, y_sym, y_in, z_in)
+            staged = _RansStaging(ys, escs, len(use) * nimg, G, yname)
+        sched = merged_wavefront(shapes, p, Rs)
+        zp = z_plan(z_items, M)
+        # ---- the device from here on
+        dev = next(m.parameters()).device
+        blocks = staged.upload(dev)
+        if zowner:
+            zflat = self._decode_z(staged, len(use) * nimg * G, zp, dev)          # every such item's z, one launch
+        z_hats, psis = [], []
+        for i, ((strings, _, z_shape), (z_lo, z_S)) in enumerate(zip(items, z_windows)):
+            if zp.at[i] is not None:
+                z_hat = self._z_view(zflat, zp.at[i], z_shape)
+            else:
+                try:
+                    z_hat = LatentCodec(m, z_lo, z_S, self.y_W).decompress_z(strings["z"], z_shape)
+                except CodecError as err:
+                    raise CodecError(f"{names[i]}: {err}") from None
+            z_hats.append(z_hat.contiguous(memory_format=torch.channels_last))
+            psis.append(m.hyper_decoder(z_hats[-1]).float())
+        cpsi = psis[0].shape[1]
+        lay = plane_layout([(B, h, w) for _, (B, _, h, w), _ in items], y_pix, cpsi, p, Rs)
+        yflat = torch.zeros(lay.y_len, device=dev, dtype=torch.float32)            # decoded latents inside zero frames
+        psiflat = torch.empty(lay.psi_len, device=dev, dtype=torch.float32)
+        for (_, (B, _, h, w), _), at, psi in zip(items, lay.psi_at.tolist(), psis):
+            psiflat[at:at + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psi).view(B, h * w, -1))
+        self._run_merged_steps(sched, use, blocks, G, yflat, y_pix, lay, psiflat, cpsi)
+        staged.check()
+        out = []
+        for (strings, (B, _, h, w), _), at, z_hat, name in zip(items, lay.y_at.tolist(), z_hats, names):
+            ypad = yflat[at:at + B * (h + 2 * p) * (w + 2 * p) * y_pix].view(B, h + 2 * p, w + 2 * p, y_pix)
+            try:
+                out.append(self._finish(strings, ypad, z_hat, (B, M, h, w)))
+            except CodecError as err:
+                raise CodecError(f"{name}: {err}") from None
+        return out
 
-    def _compressed(self, x, out, strings, y_streams, y_esc, y_sym, y_in, z_in) -> Dict:
-        """what `compress` returns, from the coded streams: sizes, the estimate and the symbol checksums"""
-        B, M, h, w = y_in.shape
-        npix = x.shape[0] * x.shape[2] * x.shape[3]
-        coded = 8.0 * (_z_size(strings) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
-        est = float(-(out["logp_y"].double().sum() + out["logp_z"].double().sum()) / np.log(2.0) / npix)
-        # CRC-32 of every image's latent symbols: a decoder whose tables differ from the encoder's by one count
-        # decodes garbage silently; with the checksum it fails loudly instead
-        y_crc = [zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
-                 for a in y_sym.reshape(B, h * w * M).cpu().numpy().astype(np.int32)]
-        strings.update(y=y_streams, y_crc32=y_crc)
-        return {"strings": strings, "shape": (B, M, h, w),
-                "z_shape": tuple(z_in.shape),
-                "bpp_coded": coded, "bpp_est": est, "y_in": y_in, "z_in": z_in}
+    def _z_view(self, zflat: torch.Tensor, at: int, z_shape) -> torch.Tensor:
+        """an item's z_hat [B, M, h4, w4] inside the flat buffer `_decode_z` filled (`z_plan`)"""
+        B, _, h4, w4 = z_shape
+        M = self.model.M
+        return zflat[at:at + B * h4 * w4 * M].view(B, h4, w4, M).permute(0, 3, 1, 2)
 
+    # ---- what the containers of both codecs share ---------------------------------------------------
+    @staticmethod
+    def _shapes(head, M: int):
+        """a container header -> (shape, z_shape) of the image padded to multiples of 64, as `decompress` takes them"""
+        Hp, Wp = -(-head["H"] // 64) * 64, -(-head["W"] // 64) * 64
+        return (head["B"], M, Hp // 16, Wp // 16), (head["B"], M, Hp // 64, Wp // 64)
+
+    @staticmethod
+    def _one_window_one_G(opened) -> int:
+        """opened: [(header, strings)] of the blobs of one batched decode, at least one.  CodecError, naming the blob,
+        for a y_W, then for a G (sub-streams per image), that is not blob 0's -> the y_W of them all"""
+        y_W, G = opened[0][0]["y_W"], opened[0][1].get("groups", 1)
+        for i, (head, strings) in enumerate(opened):
+            if head["y_W"] != y_W:
+                raise CodecError(f"blob {i}: y_W = {head['y_W']}, blob 0 has y_W = {y_W}: one call decodes one window")
+        for i, (head, strings) in enumerate(opened):
+            if strings.get("groups", 1) != G:
+                raise CodecError(f"blob {i}: G = {strings.get('groups', 1)} sub-streams per image, blob 0 has G = {G}: "
+                                 "one call decodes one G")
+        return y_W
+
+    def _family(self) -> int:
+        name = type(self.model).__name__
+        if name not in BITSTREAM_FAMILIES:
+            raise CodecError(f"no bitstream family id for {name}")
+        return BITSTREAM_FAMILIES[name]
+
+    # ---- the z coder and the device y encoder: they do not know how many layers y has ---------------
     @staticmethod
     def _z_symbols(z_in: torch.Tensor):
         """z_in [B,M,h4,w4] -> [B][h4*w4*M] int32 on its device: every image's rounded hyper-latents, pixel by pixel,
@@ -1182,29 +1259,29 @@ class ContextCodec(_LayeredCodec):
             escs.append(h_esc[blocks[i, 2]:blocks[i, 2] + ne].astype("<u4").tobytes())
         return streams, escs
 
-    def _decode_z(self, staged, first: int, windows, nsyms, bases, z_len: int, dev) -> torch.Tensor:
-        """The hyper-latents of `len(nsyms)` images from their staged "rANS-64 x G" blocks (blocks `first` on of
-        `staged`, after `upload`), every image in ONE `lic_rans_z_decode` launch per z window (one launch when all share
-        it: an image of another window has 0 symbols in that launch and its blocks stay as they are).  windows:
-        (z_lo, z_S) per image; nsyms: its symbols; bases: where its plane starts in the flat fp32 buffer of z_len
-        floats that is returned.  Nothing waits: the blocks are checked with the y blocks, by `staged.check()`."""
-        M, G, nz, lib = self.model.M, staged.G, len(nsyms), L.load()
-        zflat = torch.zeros(z_len, device=dev, dtype=torch.float32)
-        kinds = list(dict.fromkeys(windows))
-        desc = np.array([[n if win == kind else 0 for n, win in zip(nsyms, windows)] for kind in kinds] + [list(bases)],
-                        np.int64)
+    def _decode_z(self, staged, first: int, plan: ZPlan, dev) -> torch.Tensor:
+        """The hyper-latents of the images of `plan` (`z_plan`) from their staged "rANS-64 x G" blocks (blocks `first`
+        on of `staged`, after `upload`), every image in ONE `lic_rans_z_decode` launch per z window (one launch when
+        all share it: an image of another window has 0 symbols in that launch and its blocks stay as they are)
+        -> the flat fp32 buffer of plan.z_len floats (`_z_view` cuts an item out of it).  Nothing waits: the blocks
+        are checked with the y blocks, by `staged.check()`."""
+        M, G, nz, lib = self.model.M, staged.G, len(plan.nsyms), L.load()
+        zflat = torch.zeros(plan.z_len, device=dev, dtype=torch.float32)
+        kinds = list(dict.fromkeys(plan.windows))
+        desc = np.array([[n if win == kind else 0 for n, win in zip(plan.nsyms, plan.windows)] for kind in kinds]
+                        + [list(plan.bases)], np.int64)
         d_desc = torch.from_numpy(desc).to(dev)
         blocks = staged.blocks_from(first)
         for i, (z_lo, z_S) in enumerate(kinds):
             tables = factorized_tables(self.model.factorized_entropy_model, z_lo, z_S)
             L.check(lib.lic_rans_z_decode(*blocks, F_._ptr(tables), M, int(z_lo), int(z_S), nz, G, F_._ptr(d_desc[i]),
-                                          F_._ptr(d_desc[len(kinds)]), F_._ptr(zflat), z_len, L.RANS_Z_AUTO, F_._stream()),
-                    "lic_rans_z_decode")
+                                          F_._ptr(d_desc[len(kinds)]), F_._ptr(zflat), plan.z_len, L.RANS_Z_AUTO,
+                                          F_._stream()), "lic_rans_z_decode")
         return zflat
 
     def _encode_y_device(self, tables, center, y_sym, order, step_len, B: int, P: int, M: int):
         """The y streams of the "rans" coder without the host encoder: `lic_rans_encode_pick` turns tables (raster
-        order, where `_params_at` left them), centres and symbols into one start|freq word and one escape word per
+        order, where `params_at` left them), centres and symbols into one start|freq word and one escape word per
         symbol in wavefront order, `lic_rans_encode` (`lic_rans_encode_groups` for G > 1) codes them, one wave per image
         and group.  Order and step
         lengths go up once; the state blocks (final states, word count, escape count, error word) come back once,
@@ -1248,6 +1325,160 @@ class ContextCodec(_LayeredCodec):
             streams.append(states.astype("<u4").tobytes() + words[i, slot - 2 * nw:].cpu().numpy().tobytes())
             escs.append(esc[i, :ne].cpu().numpy().view(np.uint32).astype("<u4").tobytes())
         return streams, escs
+
+
+class ContextCodec(_LayeredCodec):
+    """compress(x) -> byte strings, decompress(strings) -> x_hat, through the model's masked-conv
+    context (ContextModels.py:3-36): the parameters of pixel (i, j) of y depend on the already decoded
+    pixels above / left of it, so decoding is serial -- but only along a wavefront: pixels with equal
+    j + 3 i are independent (see _wavefront), so it takes w + 3 (h - 1) dependent steps of {12-tap context
+    GEMM -> entropy-parameter MLP -> table kernel} on the GPU, each over a batch of pixels, and their
+    symbols on the host coder in between.
+
+    Encoder and decoder must build BIT-IDENTICAL tables, so both evaluate the context as the same
+    per-pixel GEMM over the 12 live taps ([N, 12M, 1, 1] "images": the kernels' results for one row do
+    not depend on the batch it sits in, and their split-K choice depends on per-image geometry only --
+    the property tests/test_gpu_fullsize.py pins); the encoder simply has all N = B*h*w pixels at
+    once.  One y stream per image (symbols step by step, pixel by pixel, channel by channel) + one z stream
+    for the batch.
+
+    `coder`: "range" (the default) codes y with the host range coder as described above; "rans" codes y with
+    the 64-lane interleaved rANS coder of lic_codec.h, whose decoder is a device kernel
+    (`lic_rans_decode_step`): the step loop is then {gather -> per-pixel layers -> tables -> decode}, all
+    asynchronous launches, and the host reads back one small block after the last step.  z keeps the range coder
+    unless `z_coder` says otherwise.
+    Its kernels take `y_W` from 1 to 64 (RANS_MAX_W); the constructor refuses a wider window for this coder.
+
+    `encoder`: where `compress` codes the y streams.  "host" (the default) gathers the tables into wavefront order,
+    copies them to the host and runs the C++ encoder, one image after the other; "device" (coder "rans" only) runs
+    `lic_rans_encode_pick` + `lic_rans_encode` on the tables where they were built and copies back state blocks,
+    streams and escape lists only.  Both write the same bytes.
+
+    `groups`: sub-streams per image of the "rans" coder (1 to 8, `rans_deal`).  1 (the default) is the rANS-64
+    format; with G > 1 `strings["groups"]` is G and `strings["y"]`, `strings["y_esc"]` hold B * G entries,
+    image-major (entry b * G + g), coded and decoded by G waves per image.  `decompress` reads G from the strings.
+
+    `slice_rows`: None (the default) or R >= 1, coder "rans" only: latent rows per slice.  A context tap (dr, ds) with
+    dr < 0 of pixel (i, j) contributes y_hat[i + dr, j + ds] only if (i mod R) + dr >= 0 and zero otherwise, exactly
+    as a tap above the image does; taps of the pixel's own row are untouched.  The slices then advance together
+    (`wavefront`): fewer, wider steps, for the rate the first rows of every slice lose with their context.  The model
+    is not told: encoder and decoder evaluate the same layers on the same masked windows, so their tables agree and
+    y_hat, x_hat are what the codec without slices reconstructs; only the bytes differ.  R >= h is that codec, byte
+    for byte.  `strings["slice_rows"]` is R when slicing is on; `decompress` reads it from the strings.
+
+    `z_coder`: "range" (the default: one host range-coder stream for the batch's z) or "rans" (coder "rans" only): every
+    image's z as `groups` rANS-64 sub-streams of its own, coded by kernels (`_encode_z`, `_decode_z`) for any window
+    z_S >= 2.  Then `strings["z_coder"]` is "rans" and `strings["z"]`, `strings["z_esc"]` are lists of B * G byte
+    strings, image-major; the decoders read `z_coder` from the strings.  Nothing else changes: y streams, `y_crc32`
+    and the decoded z_hat, y_hat, x_hat are bit for bit those of "range".
+
+    This is the one-layer case of `_LayeredCodec`, which holds the gathers, the step loops and the whole of
+    `decompress_many`; what is written here is what one layer makes different: the range coder's loop, the containers
+    LICBITS1 to 5, the batched encoder, and for `decompress_many` `_item_streams` and `_finish`."""
+
+    def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range",
+                 encoder: str = "host", groups: int = 1, slice_rows: int = None, z_coder: str = "range"):
+        if z_coder not in Z_CODERS:
+            raise CodecError(f"unknown z_coder {z_coder!r}: expected one of {Z_CODERS}")
+        if z_coder == "rans" and coder != "rans":
+            raise CodecError(f"z_coder='rans' needs coder='rans': the {coder!r} coder has no container for rANS z streams")
+        if z_coder == "rans" and int(z_S) < 2:
+            raise CodecError(f"z_S = {int(z_S)}: z_coder='rans' needs a window of at least 2 symbols")
+        self.z_coder = z_coder
+        if coder not in CODERS:
+            raise CodecError(f"unknown coder {coder!r}: expected one of {CODERS}")
+        if encoder not in ENCODERS:
+            raise CodecError(f"unknown encoder {encoder!r}: expected one of {ENCODERS}")
+        if encoder == "device" and coder != "rans":
+            raise CodecError(f"encoder='device' needs coder='rans': the {coder!r} coder has no device encoder")
+        if int(y_W) < 1:
+            raise CodecError(f"y_W = {int(y_W)}: the window half-width must be at least 1")
+        if coder == "rans" and int(y_W) > RANS_MAX_W:
+            # the only rANS decoder is the device kernel: a wider stream could be written but never read
+            raise CodecError(f"y_W = {int(y_W)}: coder='rans' takes windows of 1 to {RANS_MAX_W} "
+                             "(the limit of its device kernels); the range coder has no such limit")
+        self.model, self.z_lo, self.z_S, self.y_W, self.coder = model, int(z_lo), int(z_S), int(y_W), coder
+        self.encoder = encoder
+        self.groups = _groups(groups)
+        if self.groups > 1 and coder != "rans":
+            raise CodecError(f"groups={self.groups} needs coder='rans': the {coder!r} coder has one stream per image")
+        self.slice_rows = None if slice_rows is None else _slice_rows(slice_rows)
+        if self.slice_rows is not None and coder != "rans":
+            raise CodecError(f"slice_rows={self.slice_rows} needs coder='rans': the {coder!r} coder has no sliced format")
+        # the one-layer case of `_LayeredCodec`: all M channels, the model's one context model and MLP
+        self._set_layers([CodecLayer(model, "context_model", "entropy_parameters")])
+
+    def _prepack(self):
+        """the per-pixel layers of the codec's one layer, packed once (`CodecLayer.prepack`)"""
+        return self.layers[0].prepack()
+
+    def _act_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None) -> torch.Tensor:
+        """`CodecLayer.act_at` of the codec's one layer; `layers` is what `_prepack` gave"""
+        return self.layers[0].act_at(windows, psi_px, layers, comb)
+
+    def _params_at(self, windows: torch.Tensor, psi_px: torch.Tensor, layers, comb: torch.Tensor = None):
+        """`_act_at`'s arguments -> (center [N, M], tables [N*M, S+1]) on the device"""
+        return self.layers[0].params_at(windows, psi_px, layers, comb, self.y_W)
+
+    def _windows_all(self, y_hat: torch.Tensor, slice_rows: int = None, psi: torch.Tensor = None):
+        """[B, M, h, w] -> [B*h*w, 12M, 1, 1]: the live taps of every pixel (zeros outside the image and, with
+        `slice_rows`, outside the pixel's slice).  With psi [B, 2M, h, w]: -> (those windows, the comb [B*h*w, 4M] whose
+        last 2M columns hold the pixels' psi, the first 2M still unwritten): `_windows_layers` for the one layer"""
+        ((win, comb),) = self._windows_layers(y_hat, slice_rows, psi)
+        return win if psi is None else (win, comb)
+
+    @torch.no_grad()
+    def compress(self, x: torch.Tensor) -> Dict:
+        m = self.model
+        out = m.analysis_hyperprior(x, training=False)
+        y_in, z_in = out["y_in"].contiguous(), out["z_in"]
+        B, M, h, w = y_in.shape
+        if self.z_coder == "rans":
+            z_bytes, z_esc = self._encode_z(list(self._z_symbols(z_in)))
+        else:
+            z_bytes = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in)
+        psi = m.hyper_decoder(z_in).float()
+        win, comb = self._windows_all(out["y_in"], self.slice_rows, psi)
+        center, tables = self._params_at(win, None, self._prepack(), comb)
+        y_sym = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
+        # symbols leave in the decoder's wavefront order (see _wavefront), M channels per pixel
+        steps = self._wavefront(h, w, self.slice_rows)
+        order = np.concatenate([ii * w + jj for ii, jj in steps])
+        step_len = [len(ii) * M for ii, _ in steps]
+        strings = {"z": z_bytes}
+        if self.z_coder == "rans":
+            strings.update(z_coder="rans", z_esc=z_esc)
+        if self.groups > 1:
+            strings["groups"] = self.groups
+        if self.slice_rows is not None:
+            strings["slice_rows"] = self.slice_rows
+        if self.encoder == "device":
+            y_streams, y_esc = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, M)
+            strings.update(coder="rans", y_esc=y_esc)
+            return self._compressed(x, out, strings, y_streams, y_esc, y_sym, y_in, z_in)
+        perm = torch.from_numpy(order).to(y_in.device)
+        idx = (y_sym - center + self.y_W).view(B, h * w, M)[:, perm].cpu().numpy().reshape(B, h * w * M)
+        tabs = tables.view(B, h * w, M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * M, -1)
+        if self.coder == "rans":
+            pairs = [rans_encode_grouped(tabs[b], idx[b], step_len, self.groups) for b in range(B)]
+            y_streams, y_esc = [s for p in pairs for s in p[0]], [e for p in pairs for e in p[1]]
+            strings.update(coder="rans", y_esc=y_esc)
+        else:
+            y_streams, y_esc = [rc_encode(tabs[b], idx[b]) for b in range(B)], []
+        return self._compressed(x, out, strings, y_streams, y_esc, y_sym, y_in, z_in)
+
+    def _compressed(self, x, out, strings, y_streams, y_esc, y_sym, y_in, z_in) -> Dict:
+        """what `compress` returns, from the coded streams: sizes, the estimate and the symbol checksums"""
+        B, M, h, w = y_in.shape
+        npix = x.shape[0] * x.shape[2] * x.shape[3]
+        coded = 8.0 * (_z_size(strings) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
+        est = float(-(out["logp_y"].double().sum() + out["logp_z"].double().sum()) / np.log(2.0) / npix)
+        # CRC-32 of every image's latent symbols, which the decoder checks (`_check_latents`)
+        y_crc = [_crc32_of(a) for a in y_sym.reshape(B, h * w * M).cpu().numpy().astype(np.int32)]
+        strings.update(y=y_streams, y_crc32=y_crc)
+        return {"strings": strings, "shape": (B, M, h, w),
+                "z_shape": tuple(z_in.shape),
+                "bpp_coded": coded, "bpp_est": est, "y_in": y_in, "z_in": z_in}
 
     # ---- many images in one encode pass -----------------------------------------------------------
     @torch.no_grad()
@@ -1319,40 +1550,30 @@ class ContextCodec(_LayeredCodec):
                 n = z.numel()
                 z_bytes.append(rc_encode(zt, z_all[at:at + n], np.tile(np.arange(len(zt), dtype=np.int32), n // len(zt))))
                 at += n
-        # the layout: item after item, each on a multiple of 4 floats, its B planes one behind the other
         cpsi = psis[0].shape[1]
-        shapes, y_at, psi_at, y_len, psi_len = [], [], [], 0, 0
-        for y_in, _, _ in outs:
-            B, _, h, w = y_in.shape
-            y_at.append((y_len + 3) // 4 * 4)
-            psi_at.append((psi_len + 3) // 4 * 4)
-            shapes += [(h, w)] * B
-            y_len, psi_len = y_at[-1] + B * h * w * M, psi_at[-1] + B * h * w * cpsi
+        shapes = [(y_in.shape[2], y_in.shape[3]) for y_in, _, _ in outs for _ in range(y_in.shape[0])]
         nimg = len(shapes)
         plan = ragged_encode_plan(shapes, M, self.pad, R, G)
-        desc, img = np.zeros((nimg, L.CTX_IMAGE_WORDS), np.int64), 0
-        for i, (y_in, _, _) in enumerate(outs):
-            B, _, h, w = y_in.shape
-            for b in range(B):
-                desc[img, :7] = (y_at[i] + b * h * w * M, w * M, 0, psi_at[i] + b * h * w * cpsi, h, w,
-                                 h if R is None else min(R, h))
-                img += 1
-        yflat = torch.empty(y_len, device=dev, dtype=torch.float32)       # no frame: the gather never leaves a plane
-        psiflat = torch.empty(psi_len, device=dev, dtype=torch.float32)
+        lay = plane_layout([(y_in.shape[0], y_in.shape[2], y_in.shape[3]) for y_in, _, _ in outs], M, cpsi, 0,
+                           [R] * nimg)                                     # no frame: the gather never leaves a plane
+        yflat = torch.empty(lay.y_len, device=dev, dtype=torch.float32)
+        psiflat = torch.empty(lay.psi_len, device=dev, dtype=torch.float32)
         y_syms = []
-        for i, (y_in, _, y_raw) in enumerate(outs):
+        for (y_in, _, y_raw), psi, y_at, psi_at in zip(outs, psis, lay.y_at.tolist(), lay.psi_at.tolist()):
             B, _, h, w = y_in.shape
-            yflat[y_at[i]:y_at[i] + B * h * w * M].view(B, h, w, M).copy_(F_._nhwc(y_raw))
-            psiflat[psi_at[i]:psi_at[i] + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psis[i]).view(B, h * w, -1))
+            yflat[y_at:y_at + B * h * w * M].view(B, h, w, M).copy_(F_._nhwc(y_raw))
+            psiflat[psi_at:psi_at + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psi).view(B, h * w, -1))
             y_syms.append(y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32))
         y_sym = torch.cat(y_syms) if len(y_syms) > 1 else y_syms[0].contiguous()
         # one upload of everything the kernels index with; every part is int64, so every part is 8-byte aligned
         row_pix = np.concatenate([np.arange(h * w, dtype=np.int64) for h, w in shapes])
-        parts = [desc.ravel(), plan.images.ravel(), plan.blocks.ravel(), plan.row_image, row_pix, plan.order, plan.step_len]
+        parts = [lay.desc.ravel(), plan.images.ravel(), plan.blocks.ravel(), plan.row_image, row_pix, plan.order,
+                 plan.step_len]
         d_all = torch.from_numpy(np.concatenate(parts)).to(dev)
         d_desc, d_images, d_blocks, d_row_image, d_row_pix, d_order, d_steps = torch.split(d_all, [a.size for a in parts])
         rows, nsym = plan.total_rows, plan.total_rows * M
-        win, comb = self._gather_ragged(yflat, d_desc.view(nimg, -1), d_row_image, d_row_pix, psiflat, cpsi)
+        ((win, comb),) = self._gather_rows(self.layers, yflat, M, d_desc.view(nimg, -1), d_row_image, d_row_pix, psiflat,
+                                           cpsi)
         center, tables = self._params_at(win, None, self._prepack(), comb)
         sf = torch.empty(nsym, device=dev, dtype=torch.int32)
         exc = torch.empty_like(sf)
@@ -1402,8 +1623,7 @@ class ContextCodec(_LayeredCodec):
                 strings["slice_rows"] = R
             y_streams, y_esc = streams[img * G:(img + B) * G], escs[img * G:(img + B) * G]
             row0 = int(plan.images[img, 0])
-            y_crc = [zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
-                     for a in h_sym[row0:row0 + B * h * w].reshape(B, h * w * M)]
+            y_crc = [_crc32_of(a) for a in h_sym[row0:row0 + B * h * w].reshape(B, h * w * M)]
             strings.update(coder="rans", y_esc=y_esc, y=y_streams, y_crc32=y_crc)
             npix = x.shape[0] * x.shape[2] * x.shape[3]
             coded = 8.0 * (_z_size(strings) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
@@ -1422,13 +1642,10 @@ class ContextCodec(_LayeredCodec):
             # y and z blocks are staged together: z decodes in one launch ahead of the step loop and its state blocks
             # come back with the y blocks', in the one read-back after the last step
             G = _groups(strings.get("groups", 1))
-            _, _, h4, w4 = z_shape
             staged = _stage_y_and_z(strings["y"], strings.get("y_esc"), B, strings["z"], strings.get("z_esc"), B, G)
             staged.upload(dev)
-            n = h4 * w4 * M
-            zflat = self._decode_z(staged, B * G, [(self.z_lo, self.z_S)] * B, [n] * B, [b * n for b in range(B)], B * n,
-                                   dev)
-            z_hat = zflat.view(B, h4, w4, M).permute(0, 3, 1, 2)
+            zflat = self._decode_z(staged, B * G, z_plan([(z_shape, (self.z_lo, self.z_S))], M), dev)
+            z_hat = self._z_view(zflat, 0, z_shape)
         else:
             z_hat = LatentCodec(m, self.z_lo, self.z_S, self.y_W).decompress_z(strings["z"], z_shape)
         z_hat = z_hat.contiguous(memory_format=torch.channels_last)
@@ -1489,10 +1706,7 @@ class ContextCodec(_LayeredCodec):
         B, M, h, w = shape
         if "y_crc32" in strings:
             got = ypad[:, p:p + h, p:p + w, :].reshape(B, h * w * M).round().to(torch.int32).cpu().numpy()
-            for b in range(B):
-                if (zlib.crc32(np.ascontiguousarray(got[b]).tobytes()) & 0xFFFFFFFF) != int(strings["y_crc32"][b]):
-                    raise CodecError(f"image {b}: decoded latents do not match the encoder's checksum "
-                                     "(encoder and decoder built different probability tables, or the stream is damaged)")
+            _check_latents(got.reshape(B, h, w, M), 0, M, strings["y_crc32"])
         y_hat = ypad[:, p:p + h, p:p + w, :].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
         x_hat = m.decoder(y_hat)
         return {"x_hat": x_hat, "y_hat": y_hat, "z_hat": z_hat}
@@ -1505,141 +1719,34 @@ class ContextCodec(_LayeredCodec):
         z_windows: [(z_lo, z_S)] per item (default: this codec's); names: what to call an item in a message (default
         "item i").  -> one `decompress` result per item, bit for bit what `decompress` gives for it alone.
 
-        Per item the hyper-latent is decoded and the hyper-decoder run exactly as `decompress` does; the items whose z
-        is rANS-coded (`strings["z_coder"]`) have it decoded together, in one `lic_rans_z_decode` launch into one flat
-        buffer the hyper-decoders read views of (`_decode_z`), their z blocks staged behind the y blocks.  All psi planes
-        and all zero-framed latent planes lie in two flat buffers, every item's on a multiple of 4 floats; streams,
-        escape lists and state blocks of all images are staged once.  Then ONE loop of T steps (`merged_wavefront`),
-        each {lic_ctx_gather_ragged -> per-pixel layers and tables over the step's rows of every image ->
-        lic_rans_decode_step_ragged}: no copy, no synchronisation, no host arithmetic.  Then one read-back of the state
-        blocks, and `_finish` per item on a view of its planes.  Everything the host can refuse is refused before
-        the device is touched."""
-        m, p = self.model, self.pad
-        M = m.M
+        `_LayeredCodec._decompress_many` is the body, here with the one layer: every step of its loop is
+        {lic_ctx_gather_ragged -> per-pixel layers and tables over the step's rows of every image ->
+        lic_rans_decode_step_ragged}.  An item's z may be range-coded (decoded on the host, as `decompress` does) or
+        rANS-coded (`strings["z_coder"]`; those decode together).  Everything the host can refuse is refused before the
+        device is touched."""
         items = list(items)
-        if not items:
-            return []
-        names = [f"item {i}" for i in range(len(items))] if names is None else list(names)
-        z_windows = [(self.z_lo, self.z_S)] * len(items) if z_windows is None else list(z_windows)
-        G, shapes, Rs, owner, ys, escs = None, [], [], [], [], []
-        for i, (strings, shape, _) in enumerate(items):
+        for i, (strings, _, _) in enumerate(items):
             if strings.get("coder", "range") != "rans":
-                raise CodecError(f"{names[i]}: only streams of the 'rans' coder decode together (the range coder's "
-                                 "loop waits for the host at every step)")
-            g = _groups(strings.get("groups", 1))
-            if G is not None and g != G:
-                raise CodecError(f"{names[i]}: {g} sub-streams per image, {names[0]} has {G}: one call decodes one G")
-            G = g
-            B, Mi, h, w = shape
-            if Mi != M:
-                raise CodecError(f"{names[i]}: {Mi} latent channels, this model has {M}")
-            try:
-                R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
-            except CodecError as err:
-                raise CodecError(f"{names[i]}: {err}") from None
-            if strings.get("y_esc") is None or len(strings["y"]) != B * G or len(strings["y_esc"]) != B * G:
-                raise CodecError(f"{names[i]}: one y stream and one escape list per image and group expected")
-            shapes += [(h, w)] * B
-            Rs += [R] * B
-            owner += [(i, b) for b in range(B)]
-            ys += list(strings["y"])
-            escs += list(strings["y_esc"])
-        nimg = len(shapes)
-        # the items whose hyper-latent is rANS-coded: their z blocks ride behind the y blocks in the one staging
-        zs, zescs, zowner, zwin, znsym, zbase, zitem, z_len = [], [], [], [], [], [], {}, 0
-        for i, ((strings, shape, z_shape), win) in enumerate(zip(items, z_windows)):
-            try:
-                if _z_coder_of(strings) != "rans":
-                    continue
-                B, _, h4, w4 = z_shape
-                if B != shape[0]:
-                    raise CodecError("z_shape and shape name different batch sizes")
-                if strings.get("z_esc") is None or isinstance(strings["z"], (bytes, bytearray)) or \
-                        len(strings["z"]) != B * G or len(strings["z_esc"]) != B * G:
-                    raise CodecError("one z stream and one escape list per image and group expected")
-            except CodecError as err:
-                raise CodecError(f"{names[i]}: {err}") from None
-            z_len = (z_len + 3) // 4 * 4                                          # every item on a multiple of 4 floats
-            zitem[i] = z_len
-            for b in range(B):
-                zowner.append((i, b))
-                zwin.append((int(win[0]), int(win[1])))
-                znsym.append(h4 * w4 * M)
-                zbase.append(z_len)
-                z_len += h4 * w4 * M
-            zs += list(strings["z"])
-            zescs += list(strings["z_esc"])
-        label = lambda own: (lambda img: f"{names[own[img][0]]}: image {own[img][1]}")
-        if zowner:
-            staged = _stage_y_and_z(ys, escs, nimg, zs, zescs, len(zowner), G, label(owner), label(zowner))
-        else:
-            staged = _RansStaging(ys, escs, nimg, G, label(owner))
-        sched = merged_wavefront(shapes, p, Rs)
-        # ---- the device from here on
-        dev = next(m.parameters()).device
-        blocks = staged.upload(dev)
-        if zowner:
-            zflat = self._decode_z(staged, nimg * G, zwin, znsym, zbase, z_len, dev)      # every such item's z, one launch
-        z_hats, psis = [], []
-        for i, ((strings, _, z_shape), (z_lo, z_S)) in enumerate(zip(items, z_windows)):
-            try:
-                if i in zitem:
-                    B, _, h4, w4 = z_shape
-                    z_hat = zflat[zitem[i]:zitem[i] + B * h4 * w4 * M].view(B, h4, w4, M).permute(0, 3, 1, 2)
-                else:
-                    z_hat = LatentCodec(m, z_lo, z_S, self.y_W).decompress_z(strings["z"], z_shape)
-            except CodecError as err:
-                raise CodecError(f"{names[i]}: {err}") from None
-            z_hats.append(z_hat.contiguous(memory_format=torch.channels_last))
-            psis.append(m.hyper_decoder(z_hats[-1]).float())
-        cpsi = psis[0].shape[1]
-        # the layout: item after item, each on a multiple of 4 floats, its B planes one behind the other
-        y_at, psi_at, y_len, psi_len, img = [], [], 0, 0, 0
-        desc = np.zeros((nimg, L.CTX_IMAGE_WORDS), np.int64)
-        for _, (B, _, h, w), _ in items:
-            y_at.append((y_len + 3) // 4 * 4)
-            psi_at.append((psi_len + 3) // 4 * 4)
-            Wp, plane = w + 2 * p, (h + 2 * p) * (w + 2 * p) * M
-            for b in range(B):
-                desc[img, :7] = (y_at[-1] + b * plane, Wp * M, (p * Wp + p) * M, psi_at[-1] + b * h * w * cpsi, h, w,
-                                 h if Rs[img] is None else min(Rs[img], h))
-                img += 1
-            y_len, psi_len = y_at[-1] + B * plane, psi_at[-1] + B * h * w * cpsi
-        yflat = torch.zeros(y_len, device=dev, dtype=torch.float32)                # decoded latents inside zero frames
-        psiflat = torch.empty(psi_len, device=dev, dtype=torch.float32)
-        for i, (_, (B, _, h, w), _) in enumerate(items):
-            psiflat[psi_at[i]:psi_at[i] + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psis[i]).view(B, h * w, -1))
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        d_desc, d_rows, d_seg = up(desc), up(sched.rows), up(sched.seg)
-        d_ybase = up(desc[:, 0])
-        d_pixels = up(np.array([(h + 2 * p) * (w + 2 * p) for h, w in shapes], np.int64))
-        layers, lib, off = self._prepack(), L.load(), sched.step_off
-        for t in range(sched.T):
-            a, e = int(off[t]), int(off[t + 1])
-            win, comb = self._gather_ragged(yflat, d_desc, d_rows[0, a:e], d_rows[1, a:e], psiflat, cpsi)
-            center, tables = self._params_at(win, None, layers, comb)
-            L.check(lib.lic_rans_decode_step_ragged(*blocks, F_._ptr(tables), F_._ptr(center), F_._ptr(d_seg[t]), nimg,
-                                                    G, e - a, M, self.y_W, F_._ptr(d_rows[2, a:e]), F_._ptr(yflat),
-                                                    F_._ptr(d_ybase), F_._ptr(d_pixels), y_len, F_._stream()),
-                    "lic_rans_decode_step_ragged")
-        staged.check()
-        out = []
-        for i, (strings, shape, _) in enumerate(items):
-            B, _, h, w = shape
-            ypad = yflat[y_at[i]:y_at[i] + B * (h + 2 * p) * (w + 2 * p) * M].view(B, h + 2 * p, w + 2 * p, M)
-            try:
-                out.append(self._finish(strings, ypad, z_hats[i], shape))
-            except CodecError as err:
-                raise CodecError(f"{names[i]}: {err}") from None
-        return out
+                raise CodecError(f"{f'item {i}' if names is None else names[i]}: only streams of the 'rans' coder decode "
+                                 "together (the range coder's loop waits for the host at every step)")
+        return self._decompress_many(items, self.layers, z_windows, names)
+
+    def _item_streams(self, strings, shape, z_shape, G: int, nlayers: int):
+        """`_decompress_many`'s view of one item, after this codec's refusals -> ([(y streams, escape lists, checksums
+        or None)] for the one layer, (z streams, escape lists) or None for a range-coded z)"""
+        B, Mi = shape[0], shape[1]
+        if Mi != self.model.M:
+            raise CodecError(f"{Mi} latent channels, this model has {self.model.M}")
+        if strings.get("y_esc") is None or len(strings["y"]) != B * G or len(strings["y_esc"]) != B * G:
+            raise CodecError("one y stream and one escape list per image and group expected")
+        y = [(strings["y"], strings["y_esc"], strings.get("y_crc32"))]
+        if _z_coder_of(strings) != "rans":
+            return y, None
+        if z_shape[0] != B:
+            raise CodecError("z_shape and shape name different batch sizes")
+        return y, _z_streams(strings, B * G)
 
     # ---- self-describing container: one byte string per batch, any image size ---------------------
-    def _family(self) -> int:
-        name = type(self.model).__name__
-        if name not in BITSTREAM_FAMILIES:
-            raise CodecError(f"no bitstream family id for {name}")
-        return BITSTREAM_FAMILIES[name]
-
     @torch.no_grad()
     def compress_image(self, x: torch.Tensor, mode: str = "replicate", align: str = "topleft",
                        coder: str = None) -> bytes:
@@ -1720,13 +1827,11 @@ class ContextCodec(_LayeredCodec):
         model's.  The magic selects the coder, whatever this codec's own is."""
         head, strings = self._open_blob(data)
         m = self.model
-        B, H, W, top, left = (head[k] for k in ("B", "H", "W", "top", "left"))
-        Hp, Wp = -(-H // 64) * 64, -(-W // 64) * 64
         dec = self
         if (head["z_lo"], head["z_S"], head["y_W"]) != (self.z_lo, self.z_S, self.y_W):
             dec = ContextCodec(m, head["z_lo"], head["z_S"], head["y_W"], strings.get("coder", "range"))
-        out = dec.decompress(strings, (B, m.M, Hp // 16, Wp // 16), (B, m.M, Hp // 64, Wp // 64))
-        return F_.crop_window(out["x_hat"], top, left, H, W)
+        out = dec.decompress(strings, *self._shapes(head, m.M))
+        return F_.crop_window(out["x_hat"], head["top"], head["left"], head["H"], head["W"])
 
     def _open_blob(self, data: bytes):
         """`decompress_image`'s host half -> (header, the strings `decompress` takes).  Its refusals, in order: the
@@ -1774,19 +1879,9 @@ class ContextCodec(_LayeredCodec):
             if strings.get("coder", "range") != "rans":
                 raise CodecError(f"blob {i}: a LICBITS1 blob (range coder) cannot join a batched decode: its loop waits "
                                  "for the host at every step; decode it with decompress_image")
-        y_W, G = opened[0][0]["y_W"], opened[0][1].get("groups", 1)
-        for i, (head, strings) in enumerate(opened):
-            if head["y_W"] != y_W:
-                raise CodecError(f"blob {i}: y_W = {head['y_W']}, blob 0 has y_W = {y_W}: one call decodes one window")
-        for i, (head, strings) in enumerate(opened):
-            if strings.get("groups", 1) != G:
-                raise CodecError(f"blob {i}: G = {strings.get('groups', 1)} sub-streams per image, blob 0 has G = {G}: "
-                                 "one call decodes one G")
+        y_W = self._one_window_one_G(opened)
         m = self.model
-        items = []
-        for head, strings in opened:
-            Hp, Wp = -(-head["H"] // 64) * 64, -(-head["W"] // 64) * 64
-            items.append((strings, (head["B"], m.M, Hp // 16, Wp // 16), (head["B"], m.M, Hp // 64, Wp // 64)))
+        items = [(strings, *self._shapes(head, m.M)) for head, strings in opened]
         dec = self if y_W == self.y_W else ContextCodec(m, self.z_lo, self.z_S, y_W, "rans")
         outs = dec.decompress_many(items, [(head["z_lo"], head["z_S"]) for head, _ in opened],
                                    [f"blob {i}" for i in range(len(opened))])
@@ -1814,11 +1909,11 @@ class ScalableCodec(_LayeredCodec):
     first `base_bytes` (header, z and layer 0).
 
     Many blobs decode in ONE step loop: `decompress_images` (the pictures) and `decompress_base_images` (whole blobs or
-    base prefixes, the base layer alone) advance step t of every image of every blob together (`decompress_many`,
-    `merged_wavefront`): per step one `lic_ctx_gather_layers_ragged` and one `lic_rans_decode_step_layers_ragged` for
-    all images and layers, so N blobs cost about one blob's step loop plus every blob's transforms; every entry is bit
-    for bit the single-blob call's.  One call decodes one depth.  Several images are still encoded one after the
-    other (`compress_images`)."""
+    base prefixes, the base layer alone) advance step t of every image of every blob together (`decompress_many`, which
+    is `_LayeredCodec._decompress_many` with this codec's `_item_streams` and `_finish`): per step one
+    `lic_ctx_gather_layers_ragged` and one `lic_rans_decode_step_layers_ragged` for all images and layers, so N blobs
+    cost about one blob's step loop plus every blob's transforms; every entry is bit for bit the single-blob call's.
+    One call decodes one depth.  Several images are still encoded one after the other (`compress_images`)."""
 
     def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, encoder: str = "device", groups: int = 1,
                  slice_rows: int = None):
@@ -1841,11 +1936,6 @@ class ScalableCodec(_LayeredCodec):
         self.slice_rows = None if slice_rows is None else _slice_rows(slice_rows)
         self._set_layers([CodecLayer(model, "context_model_1", "entropy_parameters_1", 0, "M1"),
                           CodecLayer(model, "context_model_2", "entropy_parameters_2", model.M1, "M2")])
-
-    # the z coder, the device y encoder and the family id do not know how many layers y has: ContextCodec's serve
-    _z_symbols = staticmethod(ContextCodec._z_symbols)
-    _encode_z, _decode_z = ContextCodec._encode_z, ContextCodec._decode_z
-    _encode_y_device, _family = ContextCodec._encode_y_device, ContextCodec._family
 
     @torch.no_grad()
     def compress(self, x: torch.Tensor) -> Dict:
@@ -1877,8 +1967,7 @@ class ScalableCodec(_LayeredCodec):
                 tabs = tables.view(B, h * w, ly.M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * ly.M, -1)
                 pairs = [rans_encode_grouped(tabs[b], idx[b], step_len, G) for b in range(B)]
                 streams, escs = [s for p in pairs for s in p[0]], [e for p in pairs for e in p[1]]
-            crc = [zlib.crc32(np.ascontiguousarray(a).tobytes()) & 0xFFFFFFFF
-                   for a in y_sym.reshape(B, h * w * ly.M).cpu().numpy().astype(np.int32)]
+            crc = [_crc32_of(a) for a in y_sym.reshape(B, h * w * ly.M).cpu().numpy().astype(np.int32)]
             coded.append({"y": streams, "y_esc": escs, "y_crc32": crc})
             y_l = y_in[:, ly.c0:ly.c0 + ly.M]
             logp = logp + m.conditional.packed_likelihood_and_log(
@@ -1895,38 +1984,38 @@ class ScalableCodec(_LayeredCodec):
                 "bpp_coded": 8.0 * len(blob) / npix, "bpp_coded_base": 8.0 * base_bytes / npix,
                 "bpp_est": float(-logp / np.log(2.0) / npix), "y_in": y_in, "z_in": z_in}
 
-    def _decode(self, strings: Dict, shape, z_shape, nlayers: int):
-        """z, then the first `nlayers` layers in one step loop -> (ypad [B, h+2p, w+2p, channels of those layers]
-        zero-framed, z_hat).  Strings of later layers are not touched."""
-        m, p = self.model, self.pad
-        B, M, h, w = shape
-        _, _, h4, w4 = z_shape
-        if M != m.M or z_shape[0] != B:
-            raise CodecError(f"shape names {M} latent channels and z_shape {z_shape[0]} images; this model has {m.M} "
-                             f"channels and shape {B} images")
-        dev = next(m.parameters()).device
-        use = self.layers[:nlayers]
-        G = _groups(strings.get("groups", 1))
-        R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
+    def _item_streams(self, strings, shape, z_shape, G: int, nlayers: int):
+        """One item's streams after this codec's refusals, for `_decode` and `_decompress_many` -> ([(y streams, escape
+        lists, checksums)] of the first `nlayers` layers, (z streams, escape lists)).  Later layers are not touched."""
+        B, M = shape[0], shape[1]
+        if M != self.model.M or z_shape[0] != B:
+            raise CodecError(f"shape names {M} latent channels and z_shape {z_shape[0]} images; this model has "
+                             f"{self.model.M} channels and shape {B} images")
         coded = strings.get("layers")
         if not isinstance(coded, (list, tuple)) or len(coded) < nlayers:
             raise CodecError(f"the strings hold {0 if not isinstance(coded, (list, tuple)) else len(coded)} layers; "
                              f"{nlayers} are to be decoded")
-        ys, escs = [], []
         for l, c in enumerate(coded[:nlayers]):
             if c.get("y_esc") is None or len(c["y"]) != B * G or len(c["y_esc"]) != B * G or len(c["y_crc32"]) != B:
                 raise CodecError(f"layer {l}: one y stream and one escape list per image and group and one checksum "
                                  "per image expected")
-            ys += list(c["y"])
-            escs += list(c["y_esc"])
+        return [(c["y"], c["y_esc"], c["y_crc32"]) for c in coded[:nlayers]], _z_streams(strings, B * G)
+
+    def _decode(self, strings: Dict, shape, z_shape, nlayers: int) -> Dict:
+        """z, then the first `nlayers` layers in one step loop, then `_finish`"""
+        m, p = self.model, self.pad
+        B, M, h, w = shape
+        dev = next(m.parameters()).device
+        use = self.layers[:nlayers]
+        G = _groups(strings.get("groups", 1))
+        coded, (zs, zescs) = self._item_streams(strings, shape, z_shape, G, nlayers)
+        R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
         # layer-major blocks, the z blocks behind them: one upload, one read-back
-        staged = _stage_y_and_z(ys, escs, nlayers * B, strings["z"], strings.get("z_esc"), B, G,
-                                lambda i: f"image {i % B}, layer {i // B}", _image_name)
+        staged = _stage_y_and_z([s for y, _, _ in coded for s in y], [e for _, esc, _ in coded for e in esc], nlayers * B,
+                                zs, zescs, B, G, lambda i: f"image {i % B}{self._what(i // B)}", _image_name)
         blocks = staged.upload(dev)
-        n = h4 * w4 * M
-        zflat = self._decode_z(staged, nlayers * B * G, [(self.z_lo, self.z_S)] * B, [n] * B, [b * n for b in range(B)],
-                               B * n, dev)
-        z_hat = zflat.view(B, h4, w4, M).permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
+        zflat = self._decode_z(staged, nlayers * B * G, z_plan([(z_shape, (self.z_lo, self.z_S))], M), dev)
+        z_hat = self._z_view(zflat, 0, z_shape).contiguous(memory_format=torch.channels_last)
         psi = m.hyper_decoder(z_hat).float()
         y_pix = sum(ly.M for ly in use)                    # the layers are consecutive from channel 0
         ypad = torch.zeros((B, h + 2 * p, w + 2 * p, y_pix), device=dev, dtype=torch.float32)
@@ -1934,32 +2023,32 @@ class ScalableCodec(_LayeredCodec):
         front = self._step_front_end(self._wavefront(h, w, R), yflat, psi, R, use)
         self._run_steps(front, yflat, blocks, G, use)
         staged.check()
-        got = ypad[:, p:p + h, p:p + w, :].round().to(torch.int32).cpu().numpy()
-        for l, (ly, c) in enumerate(zip(use, coded)):
-            for b in range(B):
-                sym = np.ascontiguousarray(got[b, :, :, ly.c0:ly.c0 + ly.M])
-                if (zlib.crc32(sym.tobytes()) & 0xFFFFFFFF) != int(c["y_crc32"][b]):
-                    raise CodecError(f"image {b}, layer {l}: decoded latents do not match the encoder's checksum "
-                                     "(encoder and decoder built different probability tables, or the stream is damaged)")
-        return ypad, z_hat
+        return self._finish(strings, ypad, z_hat, shape)
+
+    def _finish(self, strings, ypad, z_hat, shape) -> Dict:
+        """The checksums of the layers whose channels `ypad` holds, then what `decompress` returns for both layers
+        (after the synthesis transform) and `decompress_base` for the base layer alone"""
+        m, p = self.model, self.pad
+        B, _, h, w = shape
+        use = [ly for ly in self.layers if ly.c0 + ly.M <= ypad.shape[3]]
+        inner = ypad[:, p:p + h, p:p + w, :]
+        got = inner.round().to(torch.int32).cpu().numpy()
+        for l, (ly, c) in enumerate(zip(use, strings["layers"])):
+            _check_latents(got, ly.c0, ly.c0 + ly.M, c["y_crc32"], self._what(l))
+        y_hat = inner.permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
+        if len(use) == 1:
+            return {"y1_hat": y_hat, "z_hat": z_hat, "F_tilde": m.LST(y_hat)}
+        return {"x_hat": m.decoder(y_hat), "y_hat": y_hat, "z_hat": z_hat, "F_tilde": m.LST(y_hat[:, :m.M1])}
 
     @torch.no_grad()
     def decompress(self, strings: Dict, shape, z_shape) -> Dict:
         """-> {"x_hat", "y_hat", "z_hat", "F_tilde"}: both layers, the picture and the base layer's vision features"""
-        m, p = self.model, self.pad
-        B, M, h, w = shape
-        ypad, z_hat = self._decode(strings, shape, z_shape, 2)
-        y_hat = ypad[:, p:p + h, p:p + w, :].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
-        return {"x_hat": m.decoder(y_hat), "y_hat": y_hat, "z_hat": z_hat, "F_tilde": m.LST(y_hat[:, :m.M1])}
+        return self._decode(strings, shape, z_shape, 2)
 
     @torch.no_grad()
     def decompress_base(self, strings: Dict, shape, z_shape) -> Dict:
         """-> {"y1_hat", "z_hat", "F_tilde"} from z and layer 0 alone; layer 1's strings may be absent"""
-        m, p = self.model, self.pad
-        B, M, h, w = shape
-        ypad, z_hat = self._decode(strings, shape, z_shape, 1)
-        y1_hat = ypad[:, p:p + h, p:p + w, :].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
-        return {"y1_hat": y1_hat, "z_hat": z_hat, "F_tilde": m.LST(y1_hat)}
+        return self._decode(strings, shape, z_shape, 1)
 
     # ---- the LICBITS6 container ---------------------------------------------------------------------
     def _pack_image(self, s: Dict, B: int, H: int, W: int, top: int, left: int) -> bytes:
@@ -2009,11 +2098,6 @@ class ScalableCodec(_LayeredCodec):
             dec = ScalableCodec(m, head["z_lo"], head["z_S"], head["y_W"])
         return head, strings, dec
 
-    @staticmethod
-    def _shapes(head, M: int):
-        Hp, Wp = -(-head["H"] // 64) * 64, -(-head["W"] // 64) * 64
-        return (head["B"], M, Hp // 16, Wp // 16), (head["B"], M, Hp // 64, Wp // 64)
-
     @torch.no_grad()
     def decompress_image(self, data: bytes) -> torch.Tensor:
         """The inverse of `compress_image`: x_hat [B,3,H,W], cropped back.  CodecError before any GPU work for a bad
@@ -2042,120 +2126,14 @@ class ScalableCodec(_LayeredCodec):
         slice_rows.  z_windows: [(z_lo, z_S)] per item (default: this codec's); names: what to call an item in a message
         (default "item i").  -> one result per item, bit for bit what the single call gives for it alone.
 
-        All layers' y blocks are staged layer-major (block (l * nimg + image) * G + g) with the z blocks behind them;
-        z decodes in one `lic_rans_z_decode` launch per window and the hyper-decoder runs per item.  All psi planes and
-        all zero-framed latent planes -- the channels of the first `nlayers` layers -- lie in two flat buffers, every
-        item's on a multiple of 4 floats.  Then ONE loop of T steps (`merged_wavefront`, `_run_merged_steps`), then one
-        read-back of the state blocks, the checksums per layer and image, and the synthesis transforms per item.
-        Everything the host can refuse is refused before the device is touched."""
-        m, p = self.model, self.pad
-        M = m.M
+        `_LayeredCodec._decompress_many` is the body, here with the first `nlayers` layers: the latent planes hold their
+        channels, and every step of its loop is {lic_ctx_gather_layers_ragged -> per-pixel layers and tables per layer
+        -> lic_rans_decode_step_layers_ragged}, for one layer as for two.  Everything the host can refuse is refused
+        before the device is touched."""
         items = list(items)
-        if not items:
-            return []
-        if nlayers not in (1, 2):
+        if items and nlayers not in (1, 2):
             raise CodecError(f"nlayers = {nlayers!r}: 1 decodes the base layer, 2 both layers")
-        use = self.layers[:nlayers]
-        y_pix = sum(ly.M for ly in use)                    # the layers are consecutive from channel 0
-        names = [f"item {i}" for i in range(len(items))] if names is None else list(names)
-        z_windows = [(self.z_lo, self.z_S)] * len(items) if z_windows is None else list(z_windows)
-        G, shapes, Rs, owner = None, [], [], []
-        per_layer = [([], []) for _ in use]                # (streams, escape lists) of every image, per layer
-        zs, zescs, zwin, znsym, zbase, zitem, z_len = [], [], [], [], [], [], 0
-        for i, ((strings, shape, z_shape), win) in enumerate(zip(items, z_windows)):
-            try:
-                g = _groups(strings.get("groups", 1))
-                if G is not None and g != G:
-                    raise CodecError(f"{g} sub-streams per image, {names[0]} has {G}: one call decodes one G")
-                G = g
-                B, Mi, h, w = shape
-                _, _, h4, w4 = z_shape
-                if Mi != M or z_shape[0] != B:
-                    raise CodecError(f"shape names {Mi} latent channels and z_shape {z_shape[0]} images; this model has "
-                                     f"{M} channels and shape {B} images")
-                R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
-                coded = strings.get("layers")
-                if not isinstance(coded, (list, tuple)) or len(coded) < nlayers:
-                    raise CodecError(f"the strings hold {0 if not isinstance(coded, (list, tuple)) else len(coded)} "
-                                     f"layers; {nlayers} are to be decoded")
-                for l, c in enumerate(coded[:nlayers]):
-                    if c.get("y_esc") is None or len(c["y"]) != B * G or len(c["y_esc"]) != B * G or len(c["y_crc32"]) != B:
-                        raise CodecError(f"layer {l}: one y stream and one escape list per image and group and one "
-                                         "checksum per image expected")
-                    per_layer[l][0].extend(c["y"])
-                    per_layer[l][1].extend(c["y_esc"])
-                if strings.get("z_esc") is None or isinstance(strings["z"], (bytes, bytearray)) or \
-                        len(strings["z"]) != B * G or len(strings["z_esc"]) != B * G:
-                    raise CodecError("one z stream and one escape list per image and group expected")
-            except CodecError as err:
-                raise CodecError(f"{names[i]}: {err}") from None
-            shapes += [(h, w)] * B
-            Rs += [R] * B
-            owner += [(i, b) for b in range(B)]
-            z_len = (z_len + 3) // 4 * 4                                          # every item on a multiple of 4 floats
-            zitem.append(z_len)
-            for b in range(B):
-                zwin.append((int(win[0]), int(win[1])))
-                znsym.append(h4 * w4 * M)
-                zbase.append(z_len)
-                z_len += h4 * w4 * M
-            zs += list(strings["z"])
-            zescs += list(strings["z_esc"])
-        nimg = len(shapes)
-        of = lambda img: f"{names[owner[img][0]]}: image {owner[img][1]}"
-        staged = _stage_y_and_z([s for ys, _ in per_layer for s in ys], [e for _, es in per_layer for e in es],
-                                nlayers * nimg, zs, zescs, nimg, G,
-                                lambda i: f"{of(i % nimg)}, layer {i // nimg}", of)
-        sched = merged_wavefront(shapes, p, Rs)
-        # ---- the device from here on
-        dev = next(m.parameters()).device
-        blocks = staged.upload(dev)
-        zflat = self._decode_z(staged, nlayers * nimg * G, zwin, znsym, zbase, z_len, dev)
-        z_hats, psis = [], []
-        for i, (_, _, (B, _, h4, w4)) in enumerate(items):
-            z_hat = zflat[zitem[i]:zitem[i] + B * h4 * w4 * M].view(B, h4, w4, M).permute(0, 3, 1, 2)
-            z_hats.append(z_hat.contiguous(memory_format=torch.channels_last))
-            psis.append(m.hyper_decoder(z_hats[-1]).float())
-        cpsi = psis[0].shape[1]
-        # the layout: item after item, each on a multiple of 4 floats, its B planes one behind the other
-        y_at, psi_at, y_len, psi_len, img = [], [], 0, 0, 0
-        desc = np.zeros((nimg, L.CTX_IMAGE_WORDS), np.int64)
-        for _, (B, _, h, w), _ in items:
-            y_at.append((y_len + 3) // 4 * 4)
-            psi_at.append((psi_len + 3) // 4 * 4)
-            Wp, plane = w + 2 * p, (h + 2 * p) * (w + 2 * p) * y_pix
-            for b in range(B):
-                desc[img, :7] = (y_at[-1] + b * plane, Wp * y_pix, (p * Wp + p) * y_pix, psi_at[-1] + b * h * w * cpsi,
-                                 h, w, h if Rs[img] is None else min(Rs[img], h))
-                img += 1
-            y_len, psi_len = y_at[-1] + B * plane, psi_at[-1] + B * h * w * cpsi
-        yflat = torch.zeros(y_len, device=dev, dtype=torch.float32)                # decoded latents inside zero frames
-        psiflat = torch.empty(psi_len, device=dev, dtype=torch.float32)
-        for i, (_, (B, _, h, w), _) in enumerate(items):
-            psiflat[psi_at[i]:psi_at[i] + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psis[i]).view(B, h * w, -1))
-        d_desc = torch.from_numpy(desc).to(dev)
-        d_pixels = torch.from_numpy(np.array([(h + 2 * p) * (w + 2 * p) for h, w in shapes], np.int64)).to(dev)
-        self._run_merged_steps(sched, use, blocks, G, yflat, y_pix, d_desc, d_pixels, psiflat, cpsi)
-        staged.check()
-        out = []
-        for i, (strings, (B, _, h, w), _) in enumerate(items):
-            ypad = yflat[y_at[i]:y_at[i] + B * (h + 2 * p) * (w + 2 * p) * y_pix].view(B, h + 2 * p, w + 2 * p, y_pix)
-            inner = ypad[:, p:p + h, p:p + w, :]
-            got = inner.round().to(torch.int32).cpu().numpy()
-            for l, (ly, c) in enumerate(zip(use, strings["layers"])):
-                for b in range(B):
-                    sym = np.ascontiguousarray(got[b, :, :, ly.c0:ly.c0 + ly.M])
-                    if (zlib.crc32(sym.tobytes()) & 0xFFFFFFFF) != int(c["y_crc32"][b]):
-                        raise CodecError(f"{names[i]}: image {b}, layer {l}: decoded latents do not match the encoder's "
-                                         "checksum (encoder and decoder built different probability tables, or the "
-                                         "stream is damaged)")
-            y_hat = inner.permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
-            if nlayers == 1:
-                out.append({"y1_hat": y_hat, "z_hat": z_hats[i], "F_tilde": m.LST(y_hat)})
-            else:
-                out.append({"x_hat": m.decoder(y_hat), "y_hat": y_hat, "z_hat": z_hats[i],
-                            "F_tilde": m.LST(y_hat[:, :m.M1])})
-        return out
+        return self._decompress_many(items, self.layers[:nlayers], z_windows, names)
 
     def _open_blobs(self, blobs, base_only: bool):
         """The host half of `decompress_images` / `decompress_base_images` -> ([(header, strings)], the codec that
@@ -2169,14 +2147,7 @@ class ScalableCodec(_LayeredCodec):
                 raise CodecError(f"blob {i}: {err}") from None
         if not opened:
             return [], self
-        y_W, G = opened[0][0]["y_W"], opened[0][1].get("groups", 1)
-        for i, (head, strings) in enumerate(opened):
-            if head["y_W"] != y_W:
-                raise CodecError(f"blob {i}: y_W = {head['y_W']}, blob 0 has y_W = {y_W}: one call decodes one window")
-        for i, (head, strings) in enumerate(opened):
-            if strings.get("groups", 1) != G:
-                raise CodecError(f"blob {i}: G = {strings.get('groups', 1)} sub-streams per image, blob 0 has G = {G}: "
-                                 "one call decodes one G")
+        y_W = self._one_window_one_G(opened)
         return opened, (self if y_W == self.y_W else ScalableCodec(self.model, self.z_lo, self.z_S, y_W))
 
     def _decompress_blobs(self, blobs, nlayers: int):
