@@ -163,6 +163,7 @@ class _ConvBF16Fn(torch.autograd.Function):
                     pad=pad, transposed=transposed, bias=bias, epilogue=L.EPI_LEAKY if leaky else L.EPI_NONE,
                     slope=slope, tap_mask=tap_mask, out_ld=out_ld)
         ctx.save_for_backward(xh, weight, out if leaky else None)
+        ctx.bias_param = bias   # (identity only: can_defer asks whether ITS gradient is kept, too)
         ctx.cfg = (stride, pad, transposed, bias is not None, x.dtype, leaky, slope, tap_mask)
         return _nchw_view(out)
 
@@ -173,15 +174,17 @@ class _ConvBF16Fn(torch.autograd.Function):
         g = _as_bf16_nhwc(gy)
         need = ctx.needs_input_grad
         dx, dw, db = _conv_backward_bf16(xh, weight, g, stride, pad, transposed, in_dtype, tap_mask, need[0], need[1],
-                                         has_bias and need[2], leaky_y=yh if leaky else None, slope=slope)
+                                         has_bias and need[2], leaky_y=yh if leaky else None, slope=slope,
+                                         bias=ctx.bias_param)
         return dx, dw, db, None, None, None, None, None, None, None, None, None
 
 
 def _conv_backward_bf16(xh, weight, g, stride, pad, transposed, in_dtype, tap_mask, need_dx, need_dw, need_db,
-                        leaky_y=None, slope=0.01):
+                        leaky_y=None, slope=0.01, bias=None):
     """input / weight / bias gradients of a bf16-storage convolution from g = dL/d(conv output), bf16 NHWC.
     `leaky_y`: the layer's output went through a fused LeakyReLU (that output): g is the gradient behind it and passes
-    the LeakyReLU's backward first -- in the same pass as the bias sum when there is one"""
+    the LeakyReLU's backward first -- in the same pass as the bias sum when there is one.  `bias`: the bias parameter,
+    so that its column sum is left pending only where autograd keeps ITS gradient as well (functional.can_defer)"""
     B, Hi, Wi, Cin = xh.shape
     _, Ho, Wo, Cout = g.shape
     kh, kw = weight.shape[2], weight.shape[3]
@@ -189,7 +192,7 @@ def _conv_backward_bf16(xh, weight, g, stride, pad, transposed, in_dtype, tap_ma
     dx = dw = db = None
     # the slab reduction of the weight gradient and the second stage of the bias sum wait for the end of the backward
     # pass when nothing can read these gradients earlier (functional.can_defer): one batched launch instead of ~40
-    dfr = (need_dw or need_db) and F_.can_defer(weight)
+    dfr = (need_dw or need_db) and F_.can_defer(weight if need_dw else None, bias if need_db else None)
     if leaky_y is not None:
         if need_db and Cout % 8 == 0 and g.is_contiguous() and leaky_y.is_contiguous():
             g, db = _leaky_bwd_colsum_bf16(leaky_y, g, slope, B * Ho * Wo, Cout, dfr=dfr)
@@ -233,6 +236,7 @@ class _ImageConvBF16Fn(torch.autograd.Function):
         _igemm_bf16(col, wpk, out, B=1, Hi=1, Wi=P, Cin=Kp, Ho=1, Wo=P, Cout=Cout,
                     kh=1, kw=1, stride=1, pad=0, transposed=False, bias=bias)
         ctx.save_for_backward(col, weight)
+        ctx.bias_param = bias
         ctx.cfg = (Cin, bias is not None)
         return _nchw_view(out)
 
@@ -241,7 +245,7 @@ class _ImageConvBF16Fn(torch.autograd.Function):
         col, weight = ctx.saved_tensors
         Cin, has_bias = ctx.cfg
         dw, db = _stem_backward_bf16(col, weight, _as_bf16_nhwc(gy), Cin, ctx.needs_input_grad[1],
-                                     has_bias and ctx.needs_input_grad[2])
+                                     has_bias and ctx.needs_input_grad[2], bias=ctx.bias_param)
         return None, dw, db, None, None
 
 
@@ -263,12 +267,12 @@ def _stem_columns_bf16(x, weight, stride, pad):
     return col, wpk, (B, Ho, Wo, Cout, Cin, Kp, P)
 
 
-def _stem_backward_bf16(col, weight, g, Cin, need_dw, need_db):
+def _stem_backward_bf16(col, weight, g, Cin, need_dw, need_db, bias=None):
     B, Ho, Wo, Cout = g.shape
     _, _, kh, kw = weight.shape
     taps, Kp, P = kh * kw, col.shape[1], B * Ho * Wo
     dw = db = None
-    dfr = (need_dw or need_db) and F_.can_defer(weight)
+    dfr = (need_dw or need_db) and F_.can_defer(weight if need_dw else None, bias if need_db else None)
     if need_dw:
         dw = grad_like(weight)
         if dfr:
@@ -444,10 +448,11 @@ def _gdn_operands_bf16(beta, gamma, beta_bound, gamma_bound, pedestal, kperm=Fal
 
 
 def _gdn_backward_bf16(xh, norm, beta, gamma, g, inverse, beta_bound, gamma_bound, pedestal, need_dx, need_dbeta,
-                       need_dgamma, bias_from_dx=False):
+                       need_dgamma, bias_from_dx=False, conv_bias=None):
     """gradients of y = x * norm^-1/2 (or ^1/2), norm = beta_eff + x^2 . gamma_eff^T, from g = dL/dy (bf16 NHWC);
     dx comes back as a bf16 NHWC tensor.  `bias_from_dx`: also return the column sums of dx -- the bias gradient of
-    the convolution in front -- from the same launch pair as d-beta's (a 4th result)"""
+    the convolution in front -- from the same launch pair as d-beta's (a 4th result); `conv_bias`: that bias parameter
+    (its sum is left pending with d-beta's only where autograd keeps its gradient too)"""
     beta_c, gamma_c = beta.contiguous(), gamma.contiguous()
     lib = L.load()
     B, H, W, Cc = xh.shape
@@ -496,7 +501,8 @@ def _gdn_backward_bf16(xh, norm, beta, gamma, g, inverse, beta_bound, gamma_boun
     dbe = dge = db_conv = None
     # deferred, the reductions below end in the re-parametrisation's backward: d-beta, d-gamma (and the convolution's bias
     # gradient) come out of the backward pass's one batched launch, with no lic_gdn_reparam_bwd2 launch here
-    dfr = (need_dbeta or need_dgamma) and F_.can_defer(beta if need_dbeta else None, gamma if need_dgamma else None)
+    dfr = (need_dbeta or need_dgamma) and F_.can_defer(beta if need_dbeta else None, gamma if need_dgamma else None,
+                                                         conv_bias if bias_from_dx else None)
     reparam = (beta_c, beta_bound) if dfr else None
     if need_dbeta and part_t is not None:
         dbe = _rows_sum(part_t, dfr, reparam)
@@ -597,6 +603,7 @@ class _ConvGDNBF16Fn(torch.autograd.Function):
                 cols.record_stream(cur)
                 ctx.cols = (cols, ev)
         ctx.save_for_backward(src, weight, conv_out, norm, beta, gamma)
+        ctx.bias_param = bias
         ctx.cfg = (stride, pad, transposed, inverse, beta_bound, gamma_bound, pedestal, bias is not None, x.dtype, stem,
                    Cin, direct)
         return _nchw_view(y)
@@ -610,7 +617,7 @@ class _ConvGDNBF16Fn(torch.autograd.Function):
         want_db = has_bias and need[2]
         g_conv, dbeta, dgamma, db_pre = _gdn_backward_bf16(conv_out, norm, beta, gamma, _as_bf16_nhwc(gy), inverse,
                                                            beta_bound, gamma_bound, pedestal, True, need[3], need[4],
-                                                           bias_from_dx=want_db)
+                                                           bias_from_dx=want_db, conv_bias=ctx.bias_param)
         if direct and (need[1] or (has_bias and need[2])):   # src is the image: its columns for the weight gradient
             if ctx.cols is not None:     # built beside the forward pass
                 src, ev = ctx.cols
@@ -621,10 +628,10 @@ class _ConvGDNBF16Fn(torch.autograd.Function):
         # (the bias gradient = column sums of g_conv: already there when it shared d-beta's launch pair)
         if stem:
             dx = None
-            dw, db = _stem_backward_bf16(src, weight, g_conv, Cin, need[1], want_db and db_pre is None)
+            dw, db = _stem_backward_bf16(src, weight, g_conv, Cin, need[1], want_db and db_pre is None, bias=ctx.bias_param)
         else:
             dx, dw, db = _conv_backward_bf16(src, weight, g_conv, stride, pad, transposed, in_dtype, 0, need[0], need[1],
-                                             want_db and db_pre is None)
+                                             want_db and db_pre is None, bias=ctx.bias_param)
         if db_pre is not None:
             db = db_pre
         return dx, dw, db, dbeta, dgamma, None, None, None, None, None, None, None, None, None

@@ -73,6 +73,27 @@ def flush_point(t: torch.Tensor, stream):
     return _FlushPointFn.apply(t, stream)
 
 
+_WILL_EXECUTE = getattr(torch._C, "_will_engine_execute_node", None)
+_GRADIENT_EDGE = getattr(torch.autograd.graph, "get_gradient_edge", None)
+
+
+def _gradient_kept(p) -> bool:
+    """Will the running backward pass hand the gradient of leaf `p` to its AccumulateGrad node, which keeps the tensor
+    alive until the pending reduction has written it?  Not in a pass restricted to other inputs
+    (torch.autograd.grad(y, [x]), backward(inputs=[x])): ctx.needs_input_grad still asks for the gradient, the engine
+    drops the returned tensor at once, and a reduction left pending would write into memory the allocator has handed to
+    someone else by then.  Nor where the gradient is captured for the caller (torch.autograd.grad(y, [p]): the engine
+    refuses the question for a captured leaf) or outside a backward pass: those reduce at once as well.  The engine's
+    answer comes from torch._C._will_engine_execute_node (private; checked against torch 2.10): where a build lacks it,
+    nothing is deferred."""
+    if _WILL_EXECUTE is None or _GRADIENT_EDGE is None:
+        return False
+    try:
+        return bool(_WILL_EXECUTE(_GRADIENT_EDGE(p).node))
+    except RuntimeError:
+        return False
+
+
 def can_defer(*params) -> bool:
     """May the reductions behind the gradients of `params` wait for the end of this backward pass?  Only if nothing
     reads such a gradient earlier: no data-parallel bucket hooks (they fire per gradient), the parameter has no
@@ -80,11 +101,17 @@ def can_defer(*params) -> bool:
     parameter are summed when the second arrives: everything pending is flushed first), and we are inside a backward
     pass of the autograd engine (the flush is its final callback).  The pending job names the gradient tensor's memory
     but holds no reference to the tensor: autograd adopts a returned gradient as `.grad` only while nobody else holds it
-    (otherwise it would COPY it -- before the reduction has run)."""
+    (otherwise it would COPY it -- before the reduction has run).  `params` must name EVERY leaf whose reduction the
+    caller leaves pending under this answer (a layer's bias beside its weight): one of them dropped by a pass restricted
+    to the others is enough to refuse."""
     if not DEFER_REDUCTIONS or F_.GRAD_VIEWS:
         return False
     ps = [p for p in params if p is not None]
+    if not ps:
+        return False
     if not all(p.is_leaf for p in ps):   # a derived weight: its gradient is READ by the next backward node
+        return False
+    if not all(_gradient_kept(p) for p in ps):
         return False
     if any(p.grad is not None or id(p) in _PENDING_SEEN for p in ps):
         flush_reductions()

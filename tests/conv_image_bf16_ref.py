@@ -284,19 +284,20 @@ def err_beyond_half_ulp(dev, y64, S):
     return float((e / S.clamp_min(1e-300))[S > 0].max()) if bool((S > 0).any()) else 0.0
 
 
-def column_route_half_ulps(x, w):
-    """[B,3,2Hi,2Wi]: per output element, the sum of ulp_bf16(col64) / 2 over the column terms it gathers, col64[b, (ky, kx,
-    colour), iy, ix] = sum_ci x[b, ci, iy, ix] w_q[ci, colour, ky, kx] -- the bf16 rounding of the [P][80] column matrix the
-    column-matrix route of the head stores between lic_igemm_bf16 and lic_col2im_bf16"""
+def column_route_half_ulps(x, w, k=5, s=2, p=2, op=1):
+    """[B,3,Ho,Wo]: per output element, the sum of ulp_bf16(col64) / 2 over the column terms it gathers, col64[b, (ky, kx,
+    colour), iy, ix] = sum_ci x[b, ci, iy, ix] w_q[ci, colour, ky, kx] -- the bf16 rounding of the [P][Kp] column matrix the
+    column-matrix route of the head stores between lic_igemm_bf16 and lic_col2im_bf16 ([P][80] at the default 5x5 stride-2
+    geometry; k, s, p, op: another head geometry)"""
     x, wq = f64(x), rne_bf16(w)
     out = None
-    for ky in range(5):
-        for kx in range(5):
+    for ky in range(k):
+        for kx in range(k):
             col = torch.einsum("bchw,cd->bdhw", x, wq[:, :, ky, kx])
             hu = 0.5 * ulp_bf16(col)
-            one = torch.zeros((3, 1, 5, 5), dtype=torch.float64)
+            one = torch.zeros((3, 1, k, k), dtype=torch.float64)
             one[:, 0, ky, kx] = 1.0
-            t = F.conv_transpose2d(hu, one, None, stride=2, padding=2, output_padding=1, groups=3)
+            t = F.conv_transpose2d(hu, one, None, stride=s, padding=p, output_padding=op, groups=3)
             out = t if out is None else out + t
     return out
 

@@ -298,6 +298,11 @@ IGEMM_CASES = [
     _ic("c1-192", "conv", 1, 1, 0, 0, 1, 13, 11, 192, 192, tiles="all", dgrad=True),         # 12 chunks
     _ic("c1-16-64", "conv", 1, 1, 0, 0, 1, 9, 7, 16, 64, tiles="all"),                       # one chunk: the ring's shortest tail
     _ic("c1-32-64", "conv", 1, 1, 0, 0, 1, 9, 7, 32, 64, tiles="all"),                       # two chunks
+    # the 1x1 stride-2 padding-0 skip of ResidualBlockWithStride (odd sides: 9 x 7 -> 5 x 4; its data gradient reaches every
+    # input pixel of even row and column and must leave the others exactly zero); Cin = 20: a ragged K
+    _ic("c1s2-128", "conv", 1, 2, 0, 0, 2, 9, 7, 128, 128, tiles="all", dgrad=True),
+    _ic("c1s2-64-192", "conv", 1, 2, 0, 0, 2, 9, 7, 64, 192, tiles="all", dgrad=True),
+    _ic("c1s2-k20-64", "conv", 1, 2, 0, 0, 2, 9, 7, 20, 64, tiles="all", dgrad=True),
     # prologue 1 (the operand squared on load) keeps the register-staged kernels: every tile of those
     _ic("sq1-128", "conv", 1, 1, 0, 0, 1, 13, 11, 128, 128, sq=True, tiles="all", bias=False),
     _ic("sq1-192", "conv", 1, 1, 0, 0, 1, 13, 11, 192, 192, sq=True, tiles="all"),
@@ -435,6 +440,8 @@ COL_CASES = [
     ("k3-even-tight", 2, 12, 10, 3, 3, 2, 1, 1, 0),    # Kpad 27 = kh*kw*C (not a multiple of 4: the scalar kernel)
     ("k3-odd-pad", 1, 11, 9, 3, 3, 2, 1, 0, 5),        # Kpad 32
     ("k5-c4-tight", 1, 9, 11, 4, 5, 2, 2, 0, 0),       # Kpad 100 = kh*kw*C, a multiple of 4
+    ("k1-s2-rgb", 2, 12, 10, 3, 1, 2, 0, 1, 1),        # the RGB skip of the 3x3 model: Kpad 4 = functional._kpad(1, 1, 3), one
+                                                       # 16-byte store per pixel (im2col_vec_kernel<float, 4>, col2im_fast_kernel)
 ]
 
 

@@ -353,12 +353,15 @@ def test_case_tables():
     assert {(c.Ho % 2, c.Wo % 2) for c in ic if c.kind == "convT" and c.s == 2} >= {(0, 0), (1, 1)}
     assert any(c.tap_mask == R.mask_a_bits(5) for c in ic)
     assert {c.epi for c in ic} == {"none", "leaky", "leaky_res", "mulmask"}
+    # the 1x1 stride-2 skip of the 3x3 model: full and ragged K, forward and data gradient on every tile
+    skips = [c for c in ic if (c.kind, c.k, c.s, c.p) == ("conv", 1, 2, 0)]
+    assert {(c.cin, c.cout) for c in skips} >= {(128, 128), (64, 192), (20, 64)} and all(c.dgrad and c.tiles == "all" for c in skips)
     wc = R.WGRAD_CASES
     assert {c.tile for c in wc} >= {(1, 1), (1, 3), (2, 1), (2, 2), (2, 3), (3, 3)}
     assert {c.g["g_is_row"] for c in wc} == {0, 1} and any(c.g["sq_g"] for c in wc) and any(c.g["scale"] != 1 for c in wc)
     assert {c.layout for c in wc} >= {"conv", "convT", "conv-gap", "convT-gap", "dense"}
     assert {s for c in wc for s in c.splits} >= {1, 2, 3, 99}
     cc = [R.col_geom(c) for c in R.COL_CASES]
-    assert {(q["k"], q["s"], q["p"]) for q in cc if q["C"] == 3} == {(5, 2, 2), (3, 2, 1)}
+    assert {(q["k"], q["s"], q["p"]) for q in cc if q["C"] == 3} == {(5, 2, 2), (3, 2, 1), (1, 2, 0)}
     assert {q["op"] for q in cc} == {0, 1} and {q["H"] % 2 for q in cc} == {0, 1}
     assert any(q["Kpad"] == q["k"] ** 2 * q["C"] for q in cc) and any(q["Kpad"] > q["k"] ** 2 * q["C"] for q in cc)

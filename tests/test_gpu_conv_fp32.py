@@ -342,6 +342,39 @@ def test_rgb_route_end_to_end(env, c):
             assert rc == OK and r <= R.A_RGB
 
 
+@pytest.mark.parametrize("c", [c for c in R.COL_CASES if c[4] == 3], ids=lambda c: c[0])
+def test_rgb_route_with_fused_leaky(env, c):
+    """functional.image_conv2d with the LeakyReLU fused into the dense launch (the first block of the 3x3 model): exact on
+    integers (the slope is a power of two), banded on normal inputs (the LeakyReLU is 1-Lipschitz)"""
+    F_, L, lib, dev = env
+    q = R.col_geom(c)
+    B, H, W, Cc, k, s, p, Ho, Wo = (q[n] for n in ("B", "H", "W", "C", "k", "s", "p", "Ho", "Wo"))
+    N = 64
+    for exact in (True, False):
+        inp = R.col_inputs(c, exact)
+        g_ = torch.Generator().manual_seed(23 + exact)
+        if exact:
+            w = torch.randint(-2, 3, (N, Cc, k, k), generator=g_).float()
+            bias_n = torch.randint(-4, 5, (N,), generator=g_).float()
+        else:
+            w = torch.randn((N, Cc, k, k), generator=g_) / (Cc * k * k) ** 0.5
+            bias_n = torch.randn(N, generator=g_)
+        x = inp["x"].reshape(B, H, W, Cc).to(dev).permute(0, 3, 1, 2)
+        y = F_.image_conv2d(x, w.to(dev), bias_n.to(dev), s, p, True, R.SLOPE)
+        sync_clean(lib)
+        geo = dict(B=B, Hi=H, Wi=W, Cin=Cc, Ho=Ho, Wo=Wo, Cout=N, kh=k, kw=k, stride=s, pad=p, transposed=0)
+        ref, S = R.igemm(inp["x"], R.logical_weight(w, "conv", False), geo, bias_n)
+        ref = torch.where(ref > 0, ref, ref * R.SLOPE)
+        got = y.detach().permute(0, 2, 3, 1).cpu().reshape(ref.shape)
+        assert bool((ref < 0).any()) and bool((ref > 0).any())
+        if exact:
+            assert R.exact_ok(S) and R.same_bits(got, ref), int((got.double() != ref).sum())
+        else:
+            r = R.err_over_S(got, ref, S)
+            note("rgb", r, f"stem+leaky {c[0]}")
+            assert r <= R.A_RGB
+
+
 # ---------------------------------------------------------------------------------------------
 # b. banded cases: every element within A S
 # ---------------------------------------------------------------------------------------------
