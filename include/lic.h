@@ -137,6 +137,15 @@ int lic_pack_weight(const float* src, float* dst, int32_t taps, int32_t K, int32
 /* which workgroup tile lic_igemm will launch for `d` (kernel name igemm_kernel<BM,BN>) and how
  * many multiply-adds it will issue on live taps: lets a profiler attribute time and FLOPs. */
 int lic_igemm_plan(const lic_igemm_desc* d, int32_t* BM, int32_t* BN, int64_t* live_macs);
+/* Which tile every workgroup of lic_igemm's launch for `d` takes: order[4*id .. 4*id+3] = (K split, N tile, phase,
+ * M tile) of hardware workgroup id, id = 0 .. nwg-1, computed on the host by the functions the kernel itself calls
+ * (nothing is launched and no pointer of `d` is read through).  A workgroup whose M tile lies past its phase's last
+ * row (M tile * BM >= pixels of the phase) exits at once.  `order` may be NULL to ask for the sizes alone; `capacity`
+ * counts workgroups (LIC_ERR_INVALID when it is below nwg).  taps4 (may be NULL) receives the live taps of the four
+ * phases, shape4 (may be NULL) BM, ksplit, chunks per split and chunks per tap.  The hardware deals ids round-robin
+ * over the 8 XCDs (id % 8), in the order id / 8: a developer and test aid for the balance of that deal. */
+int lic_igemm_tile_order(const lic_igemm_desc* d, int32_t* order, int64_t capacity, int64_t* nwg, int32_t* taps4,
+                         int32_t* shape4);
 
 /* ------------------------------------------------------------------------------------------
  * lic_wgrad -- weight-gradient contraction over pixels on fp32 MFMA, split-K + slab reduce.

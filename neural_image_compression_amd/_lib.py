@@ -123,6 +123,8 @@ SIGNATURES = {
     "lic_wgrad_stage": (C.c_int, [C.POINTER(WgradDesc), _vp, _sz, _i32, _vp]),
     "lic_wgrad_kernel_name": (C.c_int, [C.POINTER(WgradDesc), C.c_char_p, _sz]),
     "lic_igemm_plan": (C.c_int, [C.POINTER(IgemmDesc), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)]),
+    "lic_igemm_tile_order": (C.c_int, [C.POINTER(IgemmDesc), _vp, _i64, C.POINTER(_i64), C.POINTER(_i32),
+                                       C.POINTER(_i32)]),
     "lic_packed_weight_floats": (_i64, [_i32, _i32, _i32]),
     "lic_pack_weight": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp]),
     "lic_wgrad_workspace_bytes": (_sz, [C.POINTER(WgradDesc)]),

@@ -132,9 +132,14 @@ static inline void store_phases(Params& p, const PhaseGeometry& g) {
 }
 
 // Phase order of a 4-phase launch of MT tiles in M.  From 128 tiles on, phases are sorted by tap count inside groups
-// of 64 M tiles (an XCD's 64 slots run a round of 9-tap workgroups, then the 6-tap ones, then the 4-tap ones); MT is
-// rounded up to whole groups, the padding tiles exit at once.  Below that the kernels rotate phases tile by tile
-// (pgroup 0).
+// of `pgroup` M tiles (an XCD's slots run a round of 9-tap workgroups, then the 6-tap ones, then the 4-tap ones).  The
+// groups are sized to the XCD ranges of xcd_contiguous(): every XCD takes k = ceil(MT / 512) whole groups of
+// pgroup = ceil(MT / 8k) <= 64 tiles, MT is rounded up to 8 * k * pgroup (at most 8k - 1 padding tiles, which exit at
+// once) and the grid is a multiple of 8, so all eight XCDs get the same number of M tiles of every phase whatever NT
+// and the K split are.  (Groups of a fixed 64 tiles left an XCD half a group at MT = 256 -- nine- and six-tap
+// workgroups on the even XCDs, six- and four-tap ones on the odd: 960 against 640 tap-tiles -- and one tap class per
+// XCD at MT = 128.)  MT a multiple of 512 gives groups of 64, k per XCD.  Below 128 tiles the kernels rotate phases
+// tile by tile (pgroup 0).
 struct PhaseOrder {
   int porder;  // phase ids by decreasing tap count, 2 bits each
   int pgroup;  // M tiles per phase-sorted group
@@ -152,8 +157,9 @@ static inline PhaseOrder phase_order(int nphase, const int ntaps[4], int MT) {
         ord[j] = t;
       }
   o.porder = ord[0] | (ord[1] << 2) | (ord[2] << 4) | (ord[3] << 6);
-  o.pgroup = 64;
-  o.MT = ((MT + 63) / 64) * 64;
+  const int per_xcd = (MT + 511) / 512;  // groups in each XCD's range
+  o.pgroup = (MT + 8 * per_xcd - 1) / (8 * per_xcd);
+  o.MT = 8 * per_xcd * o.pgroup;
   return o;
 }
 

@@ -1068,6 +1068,15 @@ static int igemm_fill(const lic_igemm_desc* d, IgemmPlan& pl) {
       // 225 vs 260 us; not taken: 0.3 % of the step, and two HBM-bound launches per step would share the kernel
       // name whose MFMA roofline the benchmark reports)
       if (bm == 128 && g.max_taps * p.cpt <= 16) continue;
+      // a phase-sorted launch (phase_order(): four phases, >= 128 M tiles) takes 128-row tiles only from 512 M tiles
+      // on, where an XCD's share is whole groups of 64 -- full rounds of one tap class on its 64 slots.  Below that
+      // the groups are smaller than a round and rounds mix tap classes; 64-row tiles double the tiles per group
+      // (64 x 64 outputs at batch 32: groups of 32 -> 64; bm_unfused follows, so lic_igemm_fused_gdn_preferred fuses
+      // such a layer with the GDN behind it)
+      if (bm == 128 && g.nphase == 4) {
+        const long mt = (maxP + bm - 1) / bm;
+        if (mt >= 128 && mt < 512) continue;
+      }
       if (p.Npad < 64 * tn && tn > 1 && p.Npad <= 64 * (tn - 1)) continue;  // wider than the problem
       if (pass == 0 && p.Npad % (64 * tn) != 0) continue;
       long wgs = ((maxP + bm - 1) / bm) * ((p.Npad + 64 * tn - 1) / (64 * tn)) * p.nphase;
@@ -1198,6 +1207,35 @@ LIC_EXPORT int lic_igemm_plan(const lic_igemm_desc* d, int32_t* BM, int32_t* BN,
   if (BM) *BM = pl.BM;
   if (BN) *BN = 64 * pl.TN;
   if (live_macs) *live_macs = pl.live_macs;
+  return LIC_OK;
+}
+
+// The tile of every hardware workgroup id of the launch, from the kernel's own conv_tile(xcd_contiguous()) run on the
+// host: what tests/test_phase_order_host.py and tools/xcd_load.py read the balance over the XCDs from.
+LIC_EXPORT int lic_igemm_tile_order(const lic_igemm_desc* d, int32_t* order, int64_t capacity, int64_t* nwg,
+                                    int32_t* taps4, int32_t* shape4) {
+  const IgemmPlan pl = igemm_plan(d);
+  if (pl.status < 0) return pl.status;
+  const IgemmParams& p = pl.p;
+  const long n = pl.status == 1 ? 0 : pl.nwg;
+  if (nwg) *nwg = n;
+  if (taps4)
+    for (int ph = 0; ph < 4; ++ph) taps4[ph] = ph < p.nphase ? p.ntaps[ph] : 0;
+  if (shape4) {
+    shape4[0] = pl.BM;
+    shape4[1] = p.ksplit;
+    shape4[2] = p.cps;
+    shape4[3] = p.cpt;
+  }
+  if (!order) return LIC_OK;
+  if (capacity < n) return LIC_ERR_INVALID;
+  for (long id = 0; id < n; ++id) {
+    const ConvTile t = conv_tile(p, xcd_contiguous((int)id, (int)n));
+    order[4 * id + 0] = t.ks;
+    order[4 * id + 1] = t.nt;
+    order[4 * id + 2] = t.phase;
+    order[4 * id + 3] = t.mt;
+  }
   return LIC_OK;
 }
 

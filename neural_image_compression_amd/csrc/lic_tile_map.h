@@ -15,7 +15,8 @@ typedef __attribute__((address_space(3))) void* lic_lptr_t;
 // the shared data through the fabric.  The remap hands XCD x the contiguous range of logical ids
 // [x * q + min(x, r), +q + (x < r)), q = n / 8, r = n % 8 (the first r XCDs hold one id more), and walks it in the
 // order the XCD receives its workgroups (idx = id / 8).  What the neighbours share is said at each call site.
-__device__ __forceinline__ int xcd_contiguous(int id, int n) {
+// (__host__ too, like conv_tile below: lic_igemm_tile_order evaluates the pair on the host.)
+__host__ __device__ __forceinline__ int xcd_contiguous(int id, int n) {
   const int q = n >> 3, r = n & 7, xcd = id & 7, idx = id >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
@@ -28,7 +29,7 @@ struct ConvTile {
   int ks, nt, phase, mt;
 };
 template <class Params>
-__device__ __forceinline__ ConvTile conv_tile(const Params& p, int wg) {
+__host__ __device__ __forceinline__ ConvTile conv_tile(const Params& p, int wg) {
   ConvTile t;
   t.ks = 0;
   if (p.ksplit > 1) {
@@ -41,10 +42,11 @@ __device__ __forceinline__ ConvTile conv_tile(const Params& p, int wg) {
   t.mt = kq;
   if (p.nphase == 4) {
     if (p.pgroup > 0) {
-      // phases sorted by tap count inside groups of `pgroup` M tiles (phase_order()): an XCD's 64 slots run a round
+      // phases sorted by tap count inside groups of `pgroup` M tiles (phase_order()): an XCD's slots run a round
       // of 9-tap workgroups, then the 6-tap ones, then the 4-tap ones -- homogeneous rounds, short tail (all-equal
-      // neighbours also avoid the period-4 pattern described below).  MT is padded to whole groups: the caller's
-      // `m0 >= P` exit retires the padding tiles.
+      // neighbours also avoid the period-4 pattern described below).  phase_order() sizes the groups so that each
+      // XCD's range under xcd_contiguous() is a whole number of them, and pads MT to that: the caller's `m0 >= P`
+      // exit retires the padding tiles.
       const int span = 4 * p.pgroup;
       const int grp = kq / span, loc = kq - grp * span;
       const int rank = loc / p.pgroup;
