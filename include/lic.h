@@ -228,6 +228,16 @@ int lic_gdn_dnorm(const float* g, const float* x, const float* norm, float* t, i
 /* training: out = v + (u - 0.5); eval: out = rint(v)   (Models.py:55-64) */
 int lic_quantize(const float* v, const float* u, float* out, int64_t n, int32_t training,
                  lic_stream_t stream);
+/* The checkerboard context.  v, u, out, out_anchor: NHWC [B][h][w][C], any C; pixel (i, j) is an anchor
+ * when i + j is even.  lic_quantize, and in the same launch out_anchor = anchor(out): out at the anchors, +0 elsewhere
+ * (what the checkerboard context model convolves).  NULL v / out / out_anchor (u when training) or a non-positive
+ * extent: LIC_ERR_INVALID, nothing launched. */
+int lic_quantize_anchor(const float* v, const float* u, float* out, float* out_anchor, int32_t B, int32_t h, int32_t w,
+                        int32_t C, int32_t training, lic_stream_t stream);
+/* out = g + anchor(g_anchor), same layout: the backward of lic_quantize_anchor's two outputs (training: the gradient of
+ * additive noise is the identity) in one launch.  NULL or non-positive arguments: LIC_ERR_INVALID. */
+int lic_anchor_add(const float* g, const float* g_anchor, float* out, int32_t B, int32_t h, int32_t w, int32_t C,
+                   lic_stream_t stream);
 
 /* ---- entropy models (NHWC, P = B*h*w pixels) ------------------------------------------------ */
 /* ParametersModels.py:43-64.  raw/out rows hold G*K*M channels (G = 2 if K == 1 else 3):
@@ -366,6 +376,12 @@ int lic_gdn_dnorm_bf16(const void* g, const void* x, const void* norm, void* t, 
  * hyper-encoder's input), out_bf16 = bf16(out) (decoder, context model, hyper-decoder); either may be NULL; n % 4 == 0 */
 int lic_quantize_bf16(const float* v, const float* u, float* out, void* v_bf16, void* out_bf16, int64_t n,
                       int32_t training, lic_stream_t stream);
+/* lic_quantize_anchor that also writes the bf16 copies: v_bf16 = bf16(v), out_bf16 = bf16(out), anchor_bf16 =
+ * bf16(out_anchor); any of the three may be NULL.  LIC_ERR_UNSUPPORTED exactly where lic_quantize_bf16 returns it:
+ * B*h*w*C % 4 != 0, an fp32 pointer off 16 bytes, a bf16 pointer off 8.  C itself need not be a multiple of 4. */
+int lic_quantize_anchor_bf16(const float* v, const float* u, float* out, float* out_anchor, void* v_bf16, void* out_bf16,
+                             void* anchor_bf16, int32_t B, int32_t h, int32_t w, int32_t C, int32_t training,
+                             lic_stream_t stream);
 
 /* ---- misc ---------------------------------------------------------------------------------- */
 /* ------------------------------------------------------------------------------------------

@@ -142,6 +142,8 @@ SIGNATURES = {
     "lic_gdn_reparam_bwd2": (C.c_int, [_vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _i64, _f32, _vp]),
     "lic_gdn_dnorm": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "lic_quantize": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
+    "lic_quantize_anchor": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "lic_anchor_add": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "lic_entropy_params_fwd": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "lic_entropy_params_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "lic_gmm_likelihood_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
@@ -173,6 +175,7 @@ SIGNATURES = {
     "lic_colsum_bf16_workspace_bytes": (_sz, [_i64, _i32]),
     "lic_colsum_bf16": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _vp, _vp, _sz, _vp]),
     "lic_quantize_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
+    "lic_quantize_anchor_bf16": (C.c_int, [_vp] * 7 + [_i32] * 5 + [_vp]),
     "lic_wgrad_bf16_partial": (C.c_int, [C.POINTER(WgradDesc), _vp, _sz, C.POINTER(ReduceJob), _vp]),
     "lic_colsum_bf16_partial": (C.c_int, [_vp, _i64, _i64, _i32, _f32, _vp, _vp, _sz, C.POINTER(ReduceJob), _vp]),
     "lic_colsum2_bf16_partial": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _sz, C.POINTER(ReduceJob), _vp]),

@@ -1,7 +1,7 @@
 """The self-describing container of `ContextCodec.compress_image` (host only, no torch): one byte string per batch
-of images of any size.  Five formats, one per (coder, grouping) pair of the y streams and one for rANS-coded z;
-`_FORMATS` and `_FORMAT_ZRANS_ROW` below describe them, `_pack` writes and `_unpack` reads all five, and the ten public
-functions are their wrappers.
+of images of any size.  Six formats, one per (coder, grouping) pair of the y streams, one for rANS-coded z and one for
+the checkerboard schedule; `_FORMATS`, `_FORMAT_ZRANS_ROW` and `_FORMAT_CHECKER_ROW` below describe them, `_pack` writes
+and `_unpack` reads all six, and the twelve public functions are their wrappers.
 
 Every format, little endian:
   magic (8 bytes) | uint32 family (1 = JointAutoregressiveHierarchical, 2 = HierarchicalMixtureResidual)
@@ -17,6 +17,7 @@ The padded size is the next multiple of 64 of (H, W); the latent is [B, M, Hp/16
   LICBITS3  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G ("rANS-64 x G", `rans_deal`)
   LICBITS4  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G, and the slice_rows word
   LICBITS5  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G, slice_rows word, z section
+  LICBITS7  rans   64 G, G in 1..8   symbol CRC-32     sub-stream length, escapes         G, slice_rows word = 0, z section
 
 "symbol CRC-32" is `compress`'s y_crc32 of that image's latent symbols, "escapes" the number of uint32 in the block's
 escape list.  `lanes` is the interleaving of an image's y streams.  A LICBITS2 reader refuses any value but 64: wider
@@ -33,6 +34,10 @@ the z stream LICBITS5 has a z SECTION, and the header's "z-stream length" is the
   z block table: B*G rows (sub-stream length, escapes), image-major | for every z block: its stream, then its escape list
 Its reader refuses what LICBITS3's does, for the z blocks too -- a z sub-stream shorter than its 64 states or of odd
 length -- and a z section whose table and blocks do not add up to its length.
+LICBITS7 is byte for byte LICBITS5's layout under its own magic, and names the SCHEDULE of the y symbols: the two passes
+of the checkerboard context (codec.two_pass: the anchors, latent pixels with i + j even, in raster order, then the
+others) where LICBITS1 to 5 mean the raster wavefront.  A checkerboard model has no slices: its slice_rows word is 0,
+and its reader refuses anything else as a damaged header, besides what LICBITS5's reader refuses.
 
 LICBITS6 is the layered container of codec.ScalableCodec (family 3 = ScalableImageCoding): the latent's M channels are
 two layers, the base one of M1 channels, each coded as "rANS-64 x G" sub-streams of its own.  Its header is LICBITS5's
@@ -92,24 +97,32 @@ _FORMAT_OF_MAGIC = {f[0]: key for key, f in _FORMATS.items()}
 _FORMAT_ZRANS = ("rans", "zrans")
 _FORMAT_ZRANS_ROW = (BITSTREAM_MAGIC_ZRANS, _BITS_HEAD_SLICED, ("crc",), ("len", "esc"),
                      "one y and one z sub-stream and escape list per image and group, one checksum per image")
+# LICBITS7: LICBITS5's layout for the two-pass schedule of a checkerboard context model
+BITSTREAM_MAGIC_CHECKER = b"LICBITS7"
+_FORMAT_CHECKER = ("rans", "checker")
+_FORMAT_CHECKER_ROW = (BITSTREAM_MAGIC_CHECKER,) + _FORMAT_ZRANS_ROW[1:]
+_Z_SECTION_FORMATS = (_FORMAT_ZRANS, _FORMAT_CHECKER)
 
 
 def _format_of_magic(magic: bytes):
     """the key `_pack` / `_unpack` take for a blob that starts with `magic`; an unknown magic: LICBITS1's reader says so"""
-    return _FORMAT_ZRANS if bytes(magic) == BITSTREAM_MAGIC_ZRANS else _FORMAT_OF_MAGIC.get(bytes(magic), ("range", False))
+    beside = {BITSTREAM_MAGIC_ZRANS: _FORMAT_ZRANS, BITSTREAM_MAGIC_CHECKER: _FORMAT_CHECKER}
+    return beside.get(bytes(magic)) or _FORMAT_OF_MAGIC.get(bytes(magic), ("range", False))
 
 
 def _format(fmt):
-    return _FORMAT_ZRANS_ROW if fmt == _FORMAT_ZRANS else _FORMATS[fmt]
+    return {_FORMAT_ZRANS: _FORMAT_ZRANS_ROW, _FORMAT_CHECKER: _FORMAT_CHECKER_ROW}.get(fmt) or _FORMATS[fmt]
 
 
 def _pack(fmt, head: Dict, z_bytes: bytes, ys, escs, crcs, G: int = 1, lanes: int = None) -> bytes:
     """`head`: the _BITS_FIELDS; B * G y streams and escape lists (bytes; None where the format has none), image-major,
     and one symbol checksum per image.  The sliced format takes head["slice_rows"] as well."""
     magic, st, img_cols, blk_cols, expects = _format(fmt)
-    zrans = fmt == _FORMAT_ZRANS
+    zrans = fmt in _Z_SECTION_FORMATS
     R = head.get("slice_rows", 0) if st is _BITS_HEAD_SLICED else 0
     R = 0 if zrans and R is None else R
+    if fmt == _FORMAT_CHECKER and not (isinstance(R, (int, np.integer)) and not isinstance(R, bool) and int(R) == 0):
+        raise CodecError(f"slice_rows = {R!r}: a checkerboard bitstream has no slices")
     if st is _BITS_HEAD_SLICED and (isinstance(R, bool) or not isinstance(R, (int, np.integer))
                                     or not (0 if zrans else 1) <= int(R) <= 0xFFFFFFFF):
         raise CodecError(f"slice_rows = {R!r}: a sliced bitstream needs a whole number of rows per slice, at least 1")
@@ -200,10 +213,12 @@ def _unpack(fmt, data: bytes):
         raise CodecError(f"bitstream interleaves {lanes} coder states; this decoder implements {RANS_LANES}")
     if fmt[1] and any(r["len"] < 4 * RANS_LANES or r["len"] % 2 for r in blocks):
         raise CodecError("bitstream names a sub-stream shorter than its 64 states or of odd length")
-    zrans = fmt == _FORMAT_ZRANS
+    zrans = fmt in _Z_SECTION_FORMATS
     if st is _BITS_HEAD_SLICED:
         if vals[14] < 1 and not zrans:
             raise CodecError("bitstream header is damaged (slice_rows = 0)")
+        if vals[14] and fmt == _FORMAT_CHECKER:
+            raise CodecError(f"bitstream header is damaged (slice_rows = {vals[14]} in a checkerboard bitstream)")
         if vals[14] >= 1:
             head["slice_rows"] = vals[14]
     payload = [data[a:b] for a, b in zip(cuts, cuts[1:])]
@@ -402,3 +417,15 @@ def unpack_bitstream_zrans(data: bytes):
     [y escape list likewise], [symbol checksum per image], groups, slice_rows or None)"""
     head, (zs, zes), ys, escs, crcs, G = _unpack(_FORMAT_ZRANS, data)
     return head, zs, zes, ys, escs, crcs, G, head.get("slice_rows")
+
+
+def pack_bitstream_checker(head: Dict, z_streams, z_esc, y_streams, y_esc, y_crc32, groups: int) -> bytes:
+    """LICBITS7: `pack_bitstream_zrans` without slices, for y symbols in the two-pass order of a checkerboard context"""
+    return _pack(_FORMAT_CHECKER, dict(head, slice_rows=0), (z_streams, z_esc), y_streams, y_esc, y_crc32, _groups(groups))
+
+
+def unpack_bitstream_checker(data: bytes):
+    """-> `unpack_bitstream_zrans`'s first seven: (head dict, [z sub-stream per image and group], [z escape list
+    likewise], [y sub-stream likewise], [y escape list likewise], [symbol checksum per image], groups)"""
+    head, (zs, zes), ys, escs, crcs, G = _unpack(_FORMAT_CHECKER, data)
+    return head, zs, zes, ys, escs, crcs, G

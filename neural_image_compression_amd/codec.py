@@ -48,6 +48,13 @@ checksums, z_hat, y_hat and x_hat are those of `z_coder="range"`, only the z byt
 the per-pixel layers, one table launch and one launch of each encoder kernel (`lic_rans_encode_pick_ragged`,
 `lic_rans_encode_ragged`); entry i is byte for byte `compress_image(images[i])`.
 
+A model built with `context="checkerboard"` decodes in TWO steps whatever its size (`two_pass`): the
+anchors -- latent pixels with i + j even -- from the hyperprior alone, then the others from the anchors around them.
+Both sides gather every pixel's window from anchor(y_hat); the decoder's plane starts as zeros, so step 0 reads zeros
+and step 1 only anchors, through the same gather, per-pixel layers, table and rANS kernels as the raster schedule.
+`CodecLayer` reads the schedule off the mask; such a codec needs coder="rans", has no slices, and its container is
+LICBITS7, which a raster codec refuses as this one refuses LICBITS1 to 5.
+
 `ScalableCodec` is the codec of `models.ScalableImageCoding`: base and enhancement latent are two layers (`CodecLayer`)
 with their own rANS sub-streams, the container (LICBITS6) puts the base layer first, and `decompress_base` /
 `decompress_base_image` decode z and the base layer alone.  `_LayeredCodec` holds what it shares with `ContextCodec`,
@@ -72,7 +79,8 @@ from . import _lib as L
 from . import functional as F_
 from .bitstream import (BITSTREAM_FAMILIES, BITSTREAM_MAGIC, BITSTREAM_MAGIC_GROUPED,  # noqa: F401
                         BITSTREAM_MAGIC_RANS, BITSTREAM_MAGIC_SLICED, BITSTREAM_MAGIC_ZRANS, RANS_LANES, RANS_MAX_GROUPS,
-                        CodecError,
+                        CodecError, BITSTREAM_MAGIC_CHECKER, _FORMAT_CHECKER, pack_bitstream_checker,
+                        unpack_bitstream_checker,
                         BITSTREAM_MAGIC_LAYERED, _BITS_HEAD_LAYERED,
                         _BITS_FIELDS, _BITS_HEAD, _BITS_HEAD_RANS, _FORMAT_OF_MAGIC, _FORMAT_ZRANS, _FORMATS,
                         _check_crc_and_head, _format_of_magic,
@@ -355,6 +363,33 @@ def wavefront(h: int, w: int, pad: int, slice_rows: int = None):
     return steps
 
 
+SCHEDULES = ("raster", "checkerboard")
+
+
+def two_pass(h: int, w: int):
+    """The decode schedule of an h x w latent plane under the checkerboard context: step 0 holds the anchors (i + j
+    even), step 1 the other pixels, each in raster order; a plane of one pixel has one step.  -> [(rows, cols)] per
+    step, as `wavefront`."""
+    i, j = np.repeat(np.arange(h, dtype=np.int64), w), np.tile(np.arange(w, dtype=np.int64), h)
+    odd = ((i + j) & 1).astype(bool)
+    return [(i[keep], j[keep]) for keep in (~odd, odd) if keep.any()]
+
+
+def _schedule(schedule) -> str:
+    if schedule not in SCHEDULES:
+        raise CodecError(f"unknown schedule {schedule!r}: expected one of {SCHEDULES}")
+    return schedule
+
+
+def _steps_of(h: int, w: int, pad: int, slice_rows, schedule: str):
+    """`wavefront` or `two_pass`, by the schedule (a checkerboard plane has no slices)"""
+    if _schedule(schedule) == "raster":
+        return wavefront(h, w, pad, slice_rows)
+    if slice_rows is not None:
+        raise CodecError(f"slice_rows = {slice_rows!r}: the checkerboard schedule has no slices")
+    return two_pass(h, w)
+
+
 def _z_size(strings) -> int:
     """bytes of the coded hyper-latent in `compress`'s strings: one stream, or sub-streams and escape lists"""
     if strings.get("z_coder", "range") == "rans":
@@ -390,11 +425,12 @@ class MergedSchedule(NamedTuple):
     step_off: np.ndarray      # [T + 1] int64: step t's rows are rows[:, step_off[t]:step_off[t + 1]]
 
 
-def merged_wavefront(shapes, pad: int, slice_rows_list) -> MergedSchedule:
+def merged_wavefront(shapes, pad: int, slice_rows_list, schedule: str = "raster") -> MergedSchedule:
     """The decode schedule of several latent planes advanced together.  shapes: [(h, w)] per image; slice_rows_list:
     each image's slice_rows (None: no slices).  Step t of the call is step t of every image that still has one, images
-    in list order; inside an image the order is exactly `wavefront(h, w, pad, R)`'s.  An image that has finished keeps
-    a segment of 0 rows whose first row is the running sum, so every segment is well defined.
+    in list order; inside an image the order is exactly `wavefront(h, w, pad, R)`'s -- `two_pass(h, w)`'s for
+    schedule "checkerboard" (every entry of slice_rows_list None), so T = 2 unless every plane is one pixel.  An image
+    that has finished keeps a segment of 0 rows whose first row is the running sum, so every segment is well defined.
     No loop over steps: every pixel gets its step number, and one stable sort by (step, image) of the pixels in
     raster order, image after image, leaves them step by step, image by image, rows ascending."""
     shapes = [(int(h), int(w)) for h, w in shapes]
@@ -402,13 +438,17 @@ def merged_wavefront(shapes, pad: int, slice_rows_list) -> MergedSchedule:
     if len(slice_rows_list) != len(shapes):
         raise CodecError("one slice_rows entry per image expected")
     nimg, k = len(shapes), pad + 1
+    checker = _schedule(schedule) == "checkerboard"
+    if checker and any(R is not None for R in slice_rows_list):
+        raise CodecError("slice_rows: the checkerboard schedule has no slices")
     kinds, per = {}, []                                          # images of one shape and slice height share their arrays
     for (h, w), R in zip(shapes, slice_rows_list):
         if (h, w, R) not in kinds:
             Reff = h if R is None else min(_slice_rows(R), h)
             i, j = np.repeat(np.arange(h, dtype=np.int64), w), np.tile(np.arange(w, dtype=np.int64), h)
             # `wavefront` leaves out the steps that hold no pixel (w < pad + 1 only): number the ones that remain
-            _, t = np.unique(j + k * (i % Reff), return_inverse=True)
+            # (`two_pass`: the parity is the step; a plane of one pixel has step 0 only)
+            _, t = np.unique((i + j) & 1 if checker else j + k * (i % Reff), return_inverse=True)
             kinds[h, w, R] = (t.astype(np.int64).ravel(), i * w + j, (i + pad) * (w + 2 * pad) + j + pad)
         per.append(kinds[h, w, R])
     if not per:
@@ -447,10 +487,10 @@ class RaggedEncodePlan(NamedTuple):
 
 
 @functools.lru_cache(maxsize=64)
-def _encode_layout_of(h: int, w: int, M: int, pad: int, slice_rows, G: int):
+def _encode_layout_of(h: int, w: int, M: int, pad: int, slice_rows, G: int, schedule: str = "raster"):
     """what `ragged_encode_plan` needs of one image shape, kept between calls (a folder has few shapes; the arrays
     are read only): (raster pixel of every coding position, step lengths, slot bytes, escape entries)"""
-    steps = wavefront(h, w, pad, slice_rows)
+    steps = _steps_of(h, w, pad, slice_rows, schedule)
     step_len = np.array([len(ii) * M for ii, _ in steps], np.int64)
     fullest = max(int(rans_group_sizes(step_len, G).max()), 1)
     order = np.concatenate([ii * w + jj for ii, jj in steps]).astype(np.int64)
@@ -459,8 +499,9 @@ def _encode_layout_of(h: int, w: int, M: int, pad: int, slice_rows, G: int):
     return order, step_len, (2 * fullest + 3) // 4 * 4, fullest
 
 
-def ragged_encode_plan(shapes, M: int, pad: int, slice_rows, G: int) -> RaggedEncodePlan:
-    """The layout of one ragged encode.  shapes: [(h, w)] per image, all coded with this `slice_rows` and G.  Image b
+def ragged_encode_plan(shapes, M: int, pad: int, slice_rows, G: int, schedule: str = "raster") -> RaggedEncodePlan:
+    """The layout of one ragged encode.  shapes: [(h, w)] per image, all coded with this `slice_rows` and G (schedule
+    "checkerboard": `two_pass(h, w)` where this text says `wavefront`, slice_rows None).  Image b
     owns rows [ROW0, ROW0 + h w) of the tables, centres and symbols, in raster order, and the same range of coding
     positions: position ROW0 + q is pixel `wavefront(h, w, pad, slice_rows)`[concatenated][q], its step lengths are
     len(rows_t) * M, exactly `compress`'s.  Every block gets the smallest slot and escape list that cannot run out
@@ -468,7 +509,7 @@ def ragged_encode_plan(shapes, M: int, pad: int, slice_rows, G: int) -> RaggedEn
     the other, so every slot starts on a multiple of 4 bytes."""
     G = _groups(G)
     shapes = [(int(h), int(w)) for h, w in shapes]
-    kinds = {(h, w): _encode_layout_of(h, w, int(M), int(pad), slice_rows, G) for h, w in set(shapes)}
+    kinds = {(h, w): _encode_layout_of(h, w, int(M), int(pad), slice_rows, G, _schedule(schedule)) for h, w in set(shapes)}
     nimg = len(shapes)
     images, blocks = np.zeros((nimg, L.RANS_IMAGE_WORDS), np.int64), np.zeros((nimg * G, L.RANS_BLOCK_WORDS), np.int64)
     row0 = step0 = word_off = esc_off = 0
@@ -790,9 +831,15 @@ class CodecLayer:
         k = mc.kernel_size[0]
         self.taps = [(r, s) for r in range(k) for s in range(k) if (mc._tap_mask >> (r * k + s)) & 1]
         self.k, self.pad = k, mc.padding[0]
-        # the wavefront schedule (`wavefront`) needs every live tap strictly earlier: ds + (pad + 1) * dr < 0
-        if any((s - self.pad) + (self.pad + 1) * (r - self.pad) >= 0 for (r, s) in self.taps):
-            raise CodecError("context mask is not causal in raster order")
+        # the wavefront schedule (`wavefront`) needs every live tap strictly earlier: ds + (pad + 1) * dr < 0; the
+        # two-pass schedule (`two_pass`) needs every live tap to change the parity of i + j: dr + ds odd
+        if not any((s - self.pad) + (self.pad + 1) * (r - self.pad) >= 0 for (r, s) in self.taps):
+            self.kind = "raster"
+        elif all(((r - self.pad) + (s - self.pad)) % 2 == 1 for (r, s) in self.taps):
+            self.kind = "checkerboard"
+        else:
+            raise CodecError("context mask is not causal in raster order and not a checkerboard mask (every live tap "
+                             "(dr, ds) with dr + ds odd): the codec has a schedule for these two kinds only")
 
     context_model = property(lambda self: getattr(self.model, self._context))
     entropy_parameters = property(lambda self: getattr(self.model, self._mlp))
@@ -867,6 +914,8 @@ class _LayeredCodec:
     # False: the layered entries are launched once per layer instead of once per step (tools/bench_codec.py measures
     # what the merged launches save); bytes and results are the same
     merge_layers = True
+    # what the layers' masks say (`CodecLayer.kind`, `_set_layers`): "raster" (`wavefront`) or "checkerboard" (`two_pass`)
+    schedule = "raster"
 
     def _set_layers(self, layers):
         """the codec's layers; they share one wavefront schedule and one tap table, so their masks must agree"""
@@ -876,7 +925,10 @@ class _LayeredCodec:
             if (ly.taps, ly.k, ly.pad) != (first.taps, first.k, first.pad):
                 raise CodecError("the layers' context masks differ in their live taps: one gather and one wavefront "
                                  "schedule serve all layers, so they must agree")
-        self.taps, self.k, self.pad = first.taps, first.k, first.pad
+            if ly.kind != first.kind:
+                raise CodecError(f"the layers' context masks differ in kind ({first.kind} and {ly.kind}): one schedule "
+                                 "serves all layers")
+        self.taps, self.k, self.pad, self.schedule = first.taps, first.k, first.pad, first.kind
 
     @staticmethod
     def _whole_plane(layers, y_pix: int) -> bool:
@@ -888,8 +940,21 @@ class _LayeredCodec:
         step are independent and go through the GPU as one batch -- w + (pad + 1)(h - 1) dependent steps
         instead of h * w (141 instead of 1536 for a 512x768 image).  With slices of `slice_rows` rows i counts
         inside the pixel's slice (`wavefront`).  Returns [(rows, cols)] per step, rows
-        ascending; encoder and decoder order the symbols step by step, pixel by pixel, channel by channel."""
-        return wavefront(h, w, self.pad, slice_rows)
+        ascending; encoder and decoder order the symbols step by step, pixel by pixel, channel by channel.
+        A checkerboard mask has `two_pass`'s two steps instead, and no slices."""
+        return _steps_of(h, w, self.pad, slice_rows, self.schedule)
+
+    def _context_plane(self, y_in: torch.Tensor) -> torch.Tensor:
+        """the plane the ENCODER gathers every pixel's window from: y_hat itself, or anchor(y_hat) under a checkerboard
+        mask (lic_quantize_anchor on rounded values: rint changes nothing) -- what the decoder's plane holds when it
+        reaches the pixel: zeros in step 0, the anchors alone in step 1"""
+        return F_.quantize_anchor(y_in, None, False)[1] if self.schedule == "checkerboard" else y_in
+
+    def _refuse_other_schedule(self, strings):
+        got = strings.get("schedule", "raster")
+        if got != self.schedule:
+            raise CodecError(f"schedule mismatch: the strings were coded in the {got} schedule, this codec's context "
+                             f"model decodes the {self.schedule} schedule")
 
     def _taps_on(self, dev) -> torch.Tensor:
         """the live taps as (dr, ds) int32 pairs on `dev`, uploaded once"""
@@ -1107,6 +1172,7 @@ class _LayeredCodec:
                 g = _groups(strings.get("groups", 1))
                 if G is not None and g != G:
                     raise CodecError(f"{g} sub-streams per image, {names[0]} has {G}: one call decodes one G")
+                self._refuse_other_schedule(strings)
                 coded, z = self._item_streams(strings, shape, z_shape, g, len(use))
                 R = None if strings.get("slice_rows") is None else _slice_rows(strings["slice_rows"])
             except CodecError as err:
@@ -1131,7 +1197,7 @@ class _LayeredCodec:
             staged = _stage_y_and_z(ys, escs, len(use) * nimg, zs, zescs, len(zowner), G, yname, of(zowner))
         else:
             staged = _RansStaging(ys, escs, len(use) * nimg, G, yname)
-        sched = merged_wavefront(shapes, p, Rs)
+        sched = merged_wavefront(shapes, p, Rs, self.schedule)
         zp = z_plan(z_items, M)
         # ---- the device from here on
         dev = next(m.parameters()).device
@@ -1372,6 +1438,11 @@ class ContextCodec(_LayeredCodec):
     strings, image-major; the decoders read `z_coder` from the strings.  Nothing else changes: y streams, `y_crc32`
     and the decoded z_hat, y_hat, x_hat are bit for bit those of "range".
 
+    A model with a checkerboard context (`context="checkerboard"`) is coded in the two steps of `two_pass` instead of
+    the wavefront: every window is gathered from anchor(y_hat), nothing else differs.  It takes coder="rans" only and no
+    `slice_rows`; `strings["schedule"]` is "checkerboard", the container is LICBITS7 (which needs z_coder="rans"), and
+    either kind of codec refuses the other's strings and blobs on the host.
+
     This is the one-layer case of `_LayeredCodec`, which holds the gathers, the step loops and the whole of
     `decompress_many`; what is written here is what one layer makes different: the range coder's loop, the containers
     LICBITS1 to 5, the batched encoder, and for `decompress_many` `_item_streams` and `_finish`."""
@@ -1407,6 +1478,13 @@ class ContextCodec(_LayeredCodec):
             raise CodecError(f"slice_rows={self.slice_rows} needs coder='rans': the {coder!r} coder has no sliced format")
         # the one-layer case of `_LayeredCodec`: all M channels, the model's one context model and MLP
         self._set_layers([CodecLayer(model, "context_model", "entropy_parameters")])
+        if self.schedule == "checkerboard":
+            if coder != "rans":
+                raise CodecError(f"coder={coder!r}: a checkerboard context model needs coder='rans' (its two wide steps "
+                                 "are for the device coder; the range coder has no container for them)")
+            if self.slice_rows is not None:
+                raise CodecError(f"slice_rows={self.slice_rows}: a checkerboard context model has no slices (slice_rows "
+                                 "must be None): it decodes in two steps already")
 
     def _prepack(self):
         """the per-pixel layers of the codec's one layer, packed once (`CodecLayer.prepack`)"""
@@ -1438,7 +1516,7 @@ class ContextCodec(_LayeredCodec):
         else:
             z_bytes = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in)
         psi = m.hyper_decoder(z_in).float()
-        win, comb = self._windows_all(out["y_in"], self.slice_rows, psi)
+        win, comb = self._windows_all(self._context_plane(out["y_in"]), self.slice_rows, psi)
         center, tables = self._params_at(win, None, self._prepack(), comb)
         y_sym = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
         # symbols leave in the decoder's wavefront order (see _wavefront), M channels per pixel
@@ -1452,6 +1530,8 @@ class ContextCodec(_LayeredCodec):
             strings["groups"] = self.groups
         if self.slice_rows is not None:
             strings["slice_rows"] = self.slice_rows
+        if self.schedule != "raster":
+            strings["schedule"] = self.schedule
         if self.encoder == "device":
             y_streams, y_esc = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, M)
             strings.update(coder="rans", y_esc=y_esc)
@@ -1527,7 +1607,7 @@ class ContextCodec(_LayeredCodec):
         outs, psis, sums = [], [], []
         for x in xs:
             out = m.analysis_hyperprior(x, training=False)
-            outs.append((out["y_in"].contiguous(), out["z_in"], out["y_in"]))
+            outs.append((out["y_in"].contiguous(), out["z_in"], self._context_plane(out["y_in"])))
             psis.append(m.hyper_decoder(out["z_in"]).float())
             sums.append(out["logp_y"].double().sum() + out["logp_z"].double().sum())
         # z: the symbols of all items in one read-back, one host range coder run per item as `compress` has it -- or,
@@ -1553,7 +1633,7 @@ class ContextCodec(_LayeredCodec):
         cpsi = psis[0].shape[1]
         shapes = [(y_in.shape[2], y_in.shape[3]) for y_in, _, _ in outs for _ in range(y_in.shape[0])]
         nimg = len(shapes)
-        plan = ragged_encode_plan(shapes, M, self.pad, R, G)
+        plan = ragged_encode_plan(shapes, M, self.pad, R, G, self.schedule)
         lay = plane_layout([(y_in.shape[0], y_in.shape[2], y_in.shape[3]) for y_in, _, _ in outs], M, cpsi, 0,
                            [R] * nimg)                                     # no frame: the gather never leaves a plane
         yflat = torch.empty(lay.y_len, device=dev, dtype=torch.float32)
@@ -1621,6 +1701,8 @@ class ContextCodec(_LayeredCodec):
                 strings["groups"] = G
             if R is not None:
                 strings["slice_rows"] = R
+            if self.schedule != "raster":
+                strings["schedule"] = self.schedule
             y_streams, y_esc = streams[img * G:(img + B) * G], escs[img * G:(img + B) * G]
             row0 = int(plan.images[img, 0])
             y_crc = [_crc32_of(a) for a in h_sym[row0:row0 + B * h * w].reshape(B, h * w * M)]
@@ -1636,6 +1718,7 @@ class ContextCodec(_LayeredCodec):
     def decompress(self, strings: Dict, shape, z_shape) -> Dict:
         m = self.model
         B, M, h, w = shape
+        self._refuse_other_schedule(strings)
         dev = next(m.parameters()).device
         z_coder, staged = _z_coder_of(strings), None
         if z_coder == "rans":
@@ -1765,6 +1848,7 @@ class ContextCodec(_LayeredCodec):
             # has a device encoder
             enc, G = (self.encoder, self.groups) if (coder, True) in _FORMATS else ("host", 1)
             return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder, enc, G).compress_image(x, mode, align)
+        self._refuse_checkerboard_without_zrans()
         B, _, H, W = x.shape
         _, _, top, left = F_.pad_geometry(H, W, 64, align)
         r = self.compress(F_.pad_to_multiple(x, 64, mode, align))
@@ -1774,6 +1858,10 @@ class ContextCodec(_LayeredCodec):
         """the container of `compress_image` around the strings `compress` gave for the padded image"""
         head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
                 "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
+        if self.schedule == "checkerboard":
+            self._refuse_checkerboard_without_zrans()
+            return _pack(_FORMAT_CHECKER, dict(head, slice_rows=0), (s["z"], s["z_esc"]), s["y"], s["y_esc"],
+                         s["y_crc32"], self.groups)
         if self.z_coder == "rans":
             return _pack(_FORMAT_ZRANS, dict(head, slice_rows=self.slice_rows or 0), (s["z"], s["z_esc"]), s["y"],
                          s["y_esc"], s["y_crc32"], self.groups)
@@ -1781,6 +1869,11 @@ class ContextCodec(_LayeredCodec):
             return _pack((self.coder, "sliced"), dict(head, slice_rows=self.slice_rows), s["z"], s["y"], s["y_esc"],
                          s["y_crc32"], self.groups)
         return _pack((self.coder, self.groups > 1), head, s["z"], s["y"], s.get("y_esc"), s["y_crc32"], self.groups)
+
+    def _refuse_checkerboard_without_zrans(self):
+        if self.schedule == "checkerboard" and self.z_coder != "rans":
+            raise CodecError(f"z_coder={self.z_coder!r}: the container of the checkerboard schedule (LICBITS7) carries z as "
+                             "rANS sub-streams, as LICBITS5 does: build the codec with z_coder='rans'")
 
     def _refuse_unless_batched_encoder(self):
         if self.coder != "rans" or self.encoder != "device":
@@ -1803,6 +1896,7 @@ class ContextCodec(_LayeredCodec):
         for i, x in enumerate(images):
             try:
                 self._refuse_unless_batched_encoder()
+                self._refuse_checkerboard_without_zrans()
                 if not isinstance(x, torch.Tensor) or x.dim() != 4:
                     raise CodecError("expected a [B,3,H,W] tensor")
                 if not x.is_cuda:
@@ -1839,7 +1933,13 @@ class ContextCodec(_LayeredCodec):
         fmt = _format_of_magic(data[:8])                                      # an unknown magic: LICBITS1's reader says so
         head, z_bytes, y_streams, y_esc, y_crc, G = _unpack(fmt, data)
         strings = {"y": y_streams, "z": z_bytes, "y_crc32": y_crc}
-        if fmt == _FORMAT_ZRANS:
+        if (fmt == _FORMAT_CHECKER) != (self.schedule == "checkerboard"):
+            raise CodecError(f"schedule mismatch: a {bytes(data[:8]).decode()} bitstream is coded in the "
+                             f"{'checkerboard' if fmt == _FORMAT_CHECKER else 'raster'} schedule, this codec's context "
+                             f"model decodes the {self.schedule} schedule")
+        if fmt == _FORMAT_CHECKER:
+            strings["schedule"] = "checkerboard"
+        if fmt in (_FORMAT_ZRANS, _FORMAT_CHECKER):
             if not 2 <= head["z_S"] <= L.RANS_Z_MAX_S:
                 raise CodecError(f"bitstream names z_S = {head['z_S']}; the rANS decoder of z takes windows of 2 to "
                                  f"{L.RANS_Z_MAX_S} symbols")
@@ -1936,6 +2036,8 @@ class ScalableCodec(_LayeredCodec):
         self.slice_rows = None if slice_rows is None else _slice_rows(slice_rows)
         self._set_layers([CodecLayer(model, "context_model_1", "entropy_parameters_1", 0, "M1"),
                           CodecLayer(model, "context_model_2", "entropy_parameters_2", model.M1, "M2")])
+        if self.schedule != "raster":
+            raise CodecError(f"the layered codec has the raster schedule only, these context masks are {self.schedule}")
 
     @torch.no_grad()
     def compress(self, x: torch.Tensor) -> Dict:

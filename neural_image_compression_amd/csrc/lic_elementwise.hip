@@ -339,6 +339,39 @@ LIC_EXPORT int lic_quantize(const float* v, const float* u, float* out, int64_t 
   return ew_launch(n, stream, [=] __device__(long i) { out[i] = rintf(v[i]); });
 }
 
+// The checkerboard context: pixel (i, j) of an NHWC [B][h][w][C] latent is an anchor when i + j is even
+__device__ __forceinline__ bool lic_is_anchor(long pix, int h, int w) {
+  const long row = pix / w;
+  return (((row % h) + (pix - row * w)) & 1) == 0;
+}
+// lic_quantize whose launch also writes anchor(out): out at the anchors, +0 elsewhere (what the checkerboard context
+// model convolves)
+LIC_EXPORT int lic_quantize_anchor(const float* v, const float* u, float* out, float* out_anchor, int32_t B, int32_t h,
+                                   int32_t w, int32_t C, int32_t training, lic_stream_t stream) {
+  if (!v || !out || !out_anchor || B <= 0 || h <= 0 || w <= 0 || C <= 0 || (training && !u)) return LIC_ERR_INVALID;
+  const long n = (long)B * h * w * C;
+  return ew_launch(n, stream, [=] __device__(long i) {
+    const float q = training ? v[i] + (u[i] - 0.5f) : rintf(v[i]);
+    out[i] = q;
+    out_anchor[i] = lic_is_anchor(i / C, h, w) ? q : 0.0f;
+  });
+}
+// out = g + anchor(g_anchor): the backward of the two outputs of lic_quantize_anchor (training) in one launch
+LIC_EXPORT int lic_anchor_add(const float* g, const float* g_anchor, float* out, int32_t B, int32_t h, int32_t w, int32_t C,
+                              lic_stream_t stream) {
+  if (!g || !g_anchor || !out || B <= 0 || h <= 0 || w <= 0 || C <= 0) return LIC_ERR_INVALID;
+  const long n = (long)B * h * w * C;
+  return ew_launch_vec(
+      n, C % 4 == 0 && al16(g) && al16(g_anchor) && al16(out), stream,
+      [=] __device__(long i) {  // C % 4 == 0: the four floats are one pixel's
+        const f32x4 a = reinterpret_cast<const f32x4*>(g)[i];
+        f32x4 b = {};
+        if (lic_is_anchor(4 * i / C, h, w)) b = reinterpret_cast<const f32x4*>(g_anchor)[i];
+        reinterpret_cast<f32x4*>(out)[i] = a + b;
+      },
+      [=] __device__(long i) { out[i] = g[i] + (lic_is_anchor(i / C, h, w) ? g_anchor[i] : 0.0f); });
+}
+
 // ---------------------------------------------------------------------------------------------
 // entropy-parameter activations (ParametersModels.py:43-64), NHWC rows of G*K*M channels
 // ---------------------------------------------------------------------------------------------

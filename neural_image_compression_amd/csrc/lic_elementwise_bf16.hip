@@ -297,6 +297,53 @@ LIC_EXPORT int lic_quantize_bf16(const float* v, const float* u, float* out, voi
                      (bf16_t*)v_bf16, (bf16_t*)out_bf16, (long)(n / 4), training);
   return lic_check_launch();
 }
+// quantize_bf16_kernel for the checkerboard context: the same launch also writes anchor(out) -- out where
+// pixel (i, j) of the NHWC [B][h][w][C] tensor has i + j even, +0 elsewhere -- as fp32 and, where asked for, as bf16.
+// The four floats of a lane are one pixel's when C % 4 == 0; otherwise each finds its own pixel.
+__global__ __launch_bounds__(256) void quantize_anchor_bf16_kernel(const float* v, const float* u, float* out, float* anc,
+                                                                   bf16_t* v16, bf16_t* out16, bf16_t* anc16, long n4, int h,
+                                                                   int w, int C, int training) {
+  typedef float q_f32x4 __attribute__((ext_vector_type(4)));
+  typedef bf16_t q_bf16x4 __attribute__((ext_vector_type(4)));
+  const bool whole = C % 4 == 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const q_f32x4 a = reinterpret_cast<const q_f32x4*>(v)[i];
+    q_f32x4 o, m;
+    if (training) {
+      const q_f32x4 r = reinterpret_cast<const q_f32x4*>(u)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = a[e] + (r[e] - 0.5f);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = rintf(a[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const long pix = (4 * i + (whole ? 0 : e)) / C;
+      const long row = pix / w;
+      m[e] = ((((row % h) + (pix - row * w)) & 1) == 0) ? o[e] : 0.0f;
+    }
+    reinterpret_cast<q_f32x4*>(out)[i] = o;
+    reinterpret_cast<q_f32x4*>(anc)[i] = m;
+    if (v16) reinterpret_cast<q_bf16x4*>(v16)[i] = __builtin_convertvector(a, q_bf16x4);
+    if (out16) reinterpret_cast<q_bf16x4*>(out16)[i] = __builtin_convertvector(o, q_bf16x4);
+    if (anc16) reinterpret_cast<q_bf16x4*>(anc16)[i] = __builtin_convertvector(m, q_bf16x4);
+  }
+}
+LIC_EXPORT int lic_quantize_anchor_bf16(const float* v, const float* u, float* out, float* out_anchor, void* v_bf16,
+                                        void* out_bf16, void* anchor_bf16, int32_t B, int32_t h, int32_t w, int32_t C,
+                                        int32_t training, lic_stream_t stream) {
+  if (!v || !out || !out_anchor || B <= 0 || h <= 0 || w <= 0 || C <= 0 || (training && !u)) return LIC_ERR_INVALID;
+  const int64_t n = (int64_t)B * h * w * C;
+  if (n % 4 || (reinterpret_cast<uintptr_t>(v) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) ||
+      (reinterpret_cast<uintptr_t>(out_anchor) & 15) || (u && (reinterpret_cast<uintptr_t>(u) & 15)) ||
+      (reinterpret_cast<uintptr_t>(v_bf16) & 7) || (reinterpret_cast<uintptr_t>(out_bf16) & 7) ||
+      (reinterpret_cast<uintptr_t>(anchor_bf16) & 7))
+    return LIC_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(quantize_anchor_bf16_kernel, dim3(ew_grid(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, v, u, out,
+                     out_anchor, (bf16_t*)v_bf16, (bf16_t*)out_bf16, (bf16_t*)anchor_bf16, (long)(n / 4), h, w, C, training);
+  return lic_check_launch();
+}
 
 // stage 1 only; `job` (two of them for the pair variant) receives stage 2 for a later lic_reduce_batch
 LIC_EXPORT int lic_colsum_bf16_partial(const void* in, int64_t ld, int64_t P, int32_t C, float scale, float* out,

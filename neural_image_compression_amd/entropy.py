@@ -142,18 +142,25 @@ class MaskedConv2d(Conv2d):
 
     def __init__(self, mask_type, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        assert mask_type in ('A', 'B')
+        assert mask_type in ('A', 'B', 'checkerboard')
         self.register_buffer('mask', self.weight.data.clone())
         _, _, kH, kW = self.weight.size()
-        self.mask.fill_(1)
-        self.mask[:, :, kH // 2, kW // 2 + (mask_type == 'B'):] = 0
-        self.mask[:, :, kH // 2 + 1:] = 0
+        if mask_type == 'checkerboard':
+            # He et al. 2021: tap (r, s) is live when (r - kH//2) + (s - kW//2) is odd -- on a plane whose non-anchors
+            # (i + j odd) are zeroed, an anchor sees only zeros and a non-anchor only anchors (12 of 25 taps for 5x5)
+            assert kH % 2 == 1 and kW % 2 == 1
+            is_live = lambda r, s: ((r - kH // 2) + (s - kW // 2)) % 2 == 1
+        else:
+            is_live = lambda r, s: r < kH // 2 or (r == kH // 2 and s < kW // 2 + (mask_type == 'B'))
+        self.mask.fill_(0)
         live = 0
         for r in range(kH):
             for s in range(kW):
-                if r < kH // 2 or (r == kH // 2 and s < kW // 2 + (mask_type == 'B')):
+                if is_live(r, s):
+                    self.mask[:, :, r, s] = 1
                     live |= 1 << (r * kW + s)
         self._tap_mask = live
+        self.mask_type = mask_type
 
     def forward(self, x: Tensor, bf16: bool = False, out=None) -> Tensor:
         if F_.prepared(self.weight, "masked") is None:  # else this step's lic_prep_run already masked it in place
@@ -167,9 +174,9 @@ class MaskedConv2d(Conv2d):
 class ContextModel(nn.Module):
     precision = "fp32"  # "bf16": bf16 operands / features (models.set_precision)
 
-    def __init__(self, latent_channels=192):
+    def __init__(self, latent_channels=192, mask_type="A"):
         super().__init__()
-        self.masked = MaskedConv2d("A", in_channels=latent_channels, out_channels=2 * latent_channels,
+        self.masked = MaskedConv2d(mask_type, in_channels=latent_channels, out_channels=2 * latent_channels,
                                    kernel_size=5, stride=1, padding=2)
 
     def forward(self, x, out=None):

@@ -970,6 +970,60 @@ def quantize(v, u=None, training=True, cast_in=False, cast_out=False):
     return res
 
 
+_QUANT_ANCHOR_CASTS = [None, None, None]   # as _QUANT_CASTS, of _QuantizeAnchorFn: bf16 of the input, the result, its anchors
+
+
+class _QuantizeAnchorFn(torch.autograd.Function):
+    """`_QuantizeFn` with a second output, anchor(result): the result where pixel (i, j) has i + j even, +0 elsewhere
+    (the checkerboard context model's input), out of the same launch (lic_quantize_anchor)."""
+
+    @staticmethod
+    def forward(ctx, v, u, training, cast_in=False, cast_out=False):
+        _require_cuda(v, u)
+        vh = _nhwc(v)
+        uh = None if u is None else _nhwc(u)
+        B, h, w, Cc = vh.shape
+        out, anc = torch.empty_like(vh), torch.empty_like(vh)
+        _QUANT_ANCHOR_CASTS[:] = [None, None, None]
+        if (cast_in or cast_out) and vh.numel() % 4 == 0:
+            v16 = torch.empty_like(vh, dtype=torch.bfloat16) if cast_in else None
+            o16 = torch.empty_like(vh, dtype=torch.bfloat16) if cast_out else None
+            a16 = torch.empty_like(vh, dtype=torch.bfloat16) if cast_out else None
+            L.check(L.load().lic_quantize_anchor_bf16(_ptr(vh), _ptr(uh), _ptr(out), _ptr(anc), _ptr(v16), _ptr(o16),
+                                                      _ptr(a16), B, h, w, Cc, int(training), _stream()),
+                    "lic_quantize_anchor_bf16")
+            _QUANT_ANCHOR_CASTS[:] = [v16, o16, a16]
+        else:
+            L.check(L.load().lic_quantize_anchor(_ptr(vh), _ptr(uh), _ptr(out), _ptr(anc), B, h, w, Cc, int(training),
+                                                 _stream()), "lic_quantize_anchor")
+        ctx.training = training
+        return _nchw_view(out), _nchw_view(anc)
+
+    @staticmethod
+    def backward(ctx, g, g_anchor):
+        # additive noise: dv = g + anchor(g_anchor) in one launch; round(): zero gradient (as torch.round)
+        if not ctx.training:
+            return torch.zeros_like(g), None, None, None, None
+        _require_cuda(g, g_anchor)
+        gh, ah = _nhwc(g), _nhwc(g_anchor)
+        B, h, w, Cc = gh.shape
+        dv = torch.empty_like(gh)
+        L.check(L.load().lic_anchor_add(_ptr(gh), _ptr(ah), _ptr(dv), B, h, w, Cc, _stream()), "lic_anchor_add")
+        return _nchw_view(dv), None, None, None, None
+
+
+def quantize_anchor(v, u=None, training=True, cast_in=False, cast_out=False):
+    """-> (y_in, y_anchor): `quantize`'s result and anchor(y_in) out of one launch.  `cast_in` / `cast_out` as there;
+    `cast_out` attaches the bf16 copies of both outputs."""
+    res, anc = _QuantizeAnchorFn.apply(v, u, training, cast_in, cast_out)
+    if cast_in or cast_out:
+        attach_bf16(v, _QUANT_ANCHOR_CASTS[0])
+        attach_bf16(res, _QUANT_ANCHOR_CASTS[1])
+        attach_bf16(anc, _QUANT_ANCHOR_CASTS[2])
+        _QUANT_ANCHOR_CASTS[:] = [None, None, None]
+    return res, anc
+
+
 # ------------------------------------------------------------------------------------------
 # entropy-parameter activations + conditional likelihood
 # ------------------------------------------------------------------------------------------

@@ -16,13 +16,21 @@ from .entropy import (ContextModel, EntropyParameters, FactorizedEntropyBottlene
 
 class _HyperpriorContextModel(nn.Module):
     _stacks = None  # (Encoder, Decoder, HyperEncoder, HyperDecoder)
+    context = "raster"
 
-    def __init__(self, latent_channels: int = 192, K: int = 1):
+    def __init__(self, latent_channels: int = 192, K: int = 1, context: str = "raster"):
+        """`context`: "raster" (the reference's type-A masked convolution over y_in) or "checkerboard" (He et al. 2021,
+        DESIGN 8(f).2: phi = masked_conv(anchor(y_in)) with the checkerboard mask; anchors -- latent pixels with i + j
+        even -- get phi = bias and are coded from the hyperprior alone, the others from the anchors around them, so a
+        codec decodes in two steps).  Same modules and state-dict keys either way."""
         super().__init__()
         if not isinstance(latent_channels, int) or latent_channels < 1:
             raise ValueError(f"latent_channels must be int >= 1, got {latent_channels}")
         if not isinstance(K, int) or K < 1:
             raise ValueError(f"K must be int >= 1, got {K}")
+        if context not in ("raster", "checkerboard"):
+            raise ValueError(f"context must be 'raster' or 'checkerboard', got {context!r}")
+        self.context = context
         self.M = latent_channels
         self.K = K
         self.H = latent_channels
@@ -34,7 +42,8 @@ class _HyperpriorContextModel(nn.Module):
         self.hyper_encoder = HEnc(latent_channels=self.M)
         self.hyper_decoder = HDec(latent_channels=self.M)
         self.factorized_entropy_model = FactorizedEntropyBottleneck(self.M)
-        self.context_model = ContextModel(latent_channels=self.M)
+        self.context_model = ContextModel(latent_channels=self.M,
+                                          mask_type="checkerboard" if context == "checkerboard" else "A")
         self.entropy_parameters = EntropyParameters(latent_channels=self.M, hyper_latent_channels=self.H,
                                                     K=self.K)
 
@@ -91,9 +100,13 @@ class _HyperpriorContextModel(nn.Module):
                 uy = u[nz:].view(Bn, hy, wy, Mc).permute(0, 3, 1, 2)
             else:
                 uz, uy = noise
-            y_in = F_.quantize(y, uy, True, cast_in=lat16, cast_out=dec16 or lat16)
         else:
-            y_in = F_.quantize(y, None, False, cast_in=lat16, cast_out=dec16 or lat16)
+            uz = uy = None
+        if self.context == "checkerboard":
+            # the context model convolves anchor(y_in); decoder and likelihood keep y_in (one launch writes both)
+            y_in, y_ctx = F_.quantize_anchor(y, uy, training, cast_in=lat16, cast_out=dec16 or lat16)
+        else:
+            y_in = y_ctx = F_.quantize(y, uy, training, cast_in=lat16, cast_out=dec16 or lat16)
         if _fork is not None:
             _fork(y_in)
         z = self.hyper_encoder(y)
@@ -122,11 +135,11 @@ class _HyperpriorContextModel(nn.Module):
             comb = torch.empty((Bn, hh, ww, c_phi + c_psi), device=x.device,
                                dtype=torch.float32 if both[0] == "fp32" else torch.bfloat16)
             psi = self.hyper_decoder(z_in, out=comb[..., c_phi:])
-            phi = self.context_model(y_in, out=comb[..., :c_phi])
+            phi = self.context_model(y_ctx, out=comb[..., :c_phi])
             combined = F_.join_channels(phi, psi, comb)
         else:
             psi = self.hyper_decoder(z_in)
-            phi = self.context_model(y_in)
+            phi = self.context_model(y_ctx)
             combined = torch.cat([phi, psi], dim=1)  # (bf16 features: a 6 MB layout copy, phi first)
         act = self.entropy_parameters.packed(combined)
         if self.K == 1:

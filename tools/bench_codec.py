@@ -8,6 +8,10 @@ bash keeps a variable GROUPS of its own and ignores an assignment to it: from ba
 and SLICE_ROWS (comma list of latent rows per slice, 0 = no slices, applied to the rans coder outside GROUPS:
 `SLICE_ROWS=0,16,8,4`).  A line names the decode steps per image as well.
 
+`--context {raster,checkerboard}` (default raster) builds the model with that context model.  A checkerboard model
+decodes in two steps; it has the rans coder only and no slices, so CODERS keeps "rans" alone and
+SLICE_ROWS is ignored; its blob modes write LICBITS7 (z_coder="rans").
+
 BLOBS (comma list of blob counts, `BLOBS=1,4,16`) selects the batched-decode mode instead: for every SLICE_ROWS and GROUPS
 entry, N `compress_image` blobs of 512x768, 768x512 and 384x512 in turn are decoded once with `decompress_images` and
 once as a loop of `decompress_image`, alternating, warm, median of RUNS.  PROFILE=many:3 (or seq:3) skips the timing and
@@ -22,6 +26,7 @@ for every SLICE_ROWS and GROUPS entry -- compress, full decode, base-only decode
 the layered entries per layer -- beside ContextCodec(coder="rans", z_coder="rans") on the one-layer model.  A second
 line per BLOBS entry (8 if BLOBS is not set) decodes N blobs of that image: `decompress_images` and
 `decompress_base_images` (one merged step loop) against loops of `decompress_image` / `decompress_base_image`."""
+import argparse
 import os
 import statistics
 import sys
@@ -33,6 +38,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import neural_image_compression_amd as nic  # noqa: E402
 from neural_image_compression_amd.codec import ContextCodec  # noqa: E402
 
+_ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+_ap.add_argument("--context", choices=("raster", "checkerboard"), default="raster")
+CONTEXT = _ap.parse_args().context
 M, K = int(os.environ.get("M", "192")), int(os.environ.get("K", "3"))
 H, W = int(os.environ.get("H", "512")), int(os.environ.get("W", "768"))
 CODERS = os.environ.get("CODERS", "range,rans").split(",")
@@ -44,6 +52,10 @@ BLOBS = [int(n) for n in os.environ.get("BLOBS", "").split(",") if n]
 ENCODE_BLOBS = [int(n) for n in os.environ.get("ENCODE_BLOBS", "").split(",") if n]
 PROFILE = os.environ.get("PROFILE", "")
 BLOB_SIZES = [(512, 768), (768, 512), (384, 512)]
+CHECKER = CONTEXT == "checkerboard"
+if CHECKER:
+    CODERS, SLICE_ROWS = [c for c in CODERS if c == "rans"], [0]
+Z_CODER = {"z_coder": "rans"} if CHECKER else {}       # the container of the checkerboard schedule carries rANS z
 
 
 def timed(fn):
@@ -57,7 +69,7 @@ def timed(fn):
 def blob_mode(model):
     """decompress_images against a loop of decompress_image on the same N blobs, in one process"""
     for rows, groups in [(r, g) for r in SLICE_ROWS for g in GROUPS]:
-        cc = ContextCodec(model, coder="rans", encoder="device", groups=groups, slice_rows=rows or None)
+        cc = ContextCodec(model, coder="rans", encoder="device", groups=groups, slice_rows=rows or None, **Z_CODER)
         pool = [cc.compress_image(torch.rand(1, 3, h, w, device="cuda")) for h, w in BLOB_SIZES]
         for n in BLOBS:
             blobs = [pool[i % len(pool)] for i in range(n)]
@@ -87,7 +99,7 @@ def encode_blob_mode(model):
     """compress_images against a loop of compress_image on the same N images, in one process"""
     from neural_image_compression_amd.codec import ragged_encode_plan
     for rows, groups in [(r, g) for r in SLICE_ROWS for g in GROUPS]:
-        cc = ContextCodec(model, coder="rans", encoder="device", groups=groups, slice_rows=rows or None)
+        cc = ContextCodec(model, coder="rans", encoder="device", groups=groups, slice_rows=rows or None, **Z_CODER)
         pool = [torch.rand(1, 3, h, w, device="cuda") for h, w in BLOB_SIZES]
         for n in ENCODE_BLOBS:
             xs = [pool[i % len(pool)] for i in range(n)]
@@ -180,7 +192,7 @@ if os.environ.get("SCALABLE"):
     scalable_mode(int(os.environ["SCALABLE"]))
     sys.exit(0)
 torch.manual_seed(0)
-model = nic.JointAutoregressiveHierarchical(M, K).cuda().eval()
+model = nic.JointAutoregressiveHierarchical(M, K, context=CONTEXT).cuda().eval()
 if BLOBS:
     blob_mode(model)
     sys.exit(0)
@@ -203,7 +215,7 @@ for coder, encoder, rows, groups in [(c, e, r, g) for c in CODERS for e in (ENCO
     npx = enc["shape"][2] * enc["shape"][3]
     md = statistics.median(t_dec)
     steps = len(cc._wavefront(enc["shape"][2], enc["shape"][3], rows or None))
-    print(f"JAH({M},{K}) {H}x{W} coder={coder} encoder={encoder} groups={groups} slice_rows={rows} steps={steps}: compress {statistics.median(t_enc):8.2f} ms "
+    print(f"JAH({M},{K}) {H}x{W} context={CONTEXT} coder={coder} encoder={encoder} groups={groups} slice_rows={rows} steps={steps}: compress {statistics.median(t_enc):8.2f} ms "
           f"(min {min(t_enc):.2f}, max {max(t_enc):.2f}), decompress {md:8.2f} ms "
           f"(min {min(t_dec):.2f}, max {max(t_dec):.2f}, median of {RUNS}; {1e3 * md / npx:6.1f} us per latent pixel, "
           f"{npx} pixels), round trip {'ok' if ok else 'MISMATCH'}, {nbytes} bytes, bpp coded {enc['bpp_coded']:.4f} "
