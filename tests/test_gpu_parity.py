@@ -514,20 +514,10 @@ def test_model_vs_oracle(env, kind, M, K, B, H, W):
 
 
 def _pack_layout_ref(w, taps, K, N, s_tap, s_k, s_n):
-    """numpy restatement of include/lic.h's fp32 packed layout [tap][K/16][Npad/32][2][64][4]"""
-    flat = w.reshape(-1)
-    npad = 32 if N <= 32 else (N + 63) // 64 * 64     # whole 64-column wave pairs (lic_common.h lic_npad_f32)
-    cpt, ntile = (K + 15) // 16, npad // 32
-    out = np.zeros((taps, cpt, ntile, 2, 64, 4), np.float32)
-    for tap in range(taps):
-        for k in range(K):
-            for n in range(N):
-                cb, kl = divmod(k, 16)
-                tile, nl = divmod(n, 32)
-                lh, r = divmod(kl, 8)
-                q, e = divmod(r, 4)
-                out[tap, cb, tile, q, lh * 32 + nl, e] = flat[tap * s_tap + k * s_k + n * s_n]
-    return out.reshape(-1)
+    """include/lic.h's fp32 packed layout [tap][K/16][Npad/32][2][64][4] as tests/prep_ref.py states it"""
+    import prep_ref
+    job = prep_ref.Case("w", prep_ref.PACK_F32, "w", taps=taps, K=K, N=N, s_tap=s_tap, s_kq=s_k, s_nq=s_n)
+    return prep_ref.expected(job, w.reshape(-1)).view(np.float32)
 
 
 @pytest.mark.parametrize("d0,d1,kh", [(80, 75, 3), (64, 96, 5), (33, 20, 1), (192, 192, 5), (48, 48, 5), (16, 40, 3)])
