@@ -1126,6 +1126,34 @@ int lic_adam_run_scaled(const lic_adam_job* jobs_device, int32_t njobs, int64_t 
                         int32_t skip_nonfinite, lic_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * lic_adam_run_ema / lic_swap_run -- the exponential moving average (EMA) of the weights that models of this kind are
+ *   evaluated, checkpointed and shipped with (the usual recipe: torch._foreach_lerp_ over every parameter behind
+ *   optimizer.step()), kept inside the optimizer's one launch, and its exchange with the live weights.
+ *   lic_adam_run_ema   lic_adam_run (clip_state NULL: no scaling, no guard, skip_nonfinite ignored) or
+ *       lic_adam_run_scaled (clip_state given) on the same job table, partition and `grads_host`, with one more
+ *       stream per element.  ema_device: a DEVICE array of njobs float* in job order -- the averages are persistent
+ *       buffers, so their addresses do not travel per step; a NULL entry means that tensor has no average.  After the
+ *       new p has been formed exactly as those two entries form it,
+ *           e = e + w * (p_new - e),   w = (float)ema_weight
+ *       in three separately rounded fp32 operations (subtract, multiply, add; never a fused multiply-add), stored
+ *       with the vector width of p (an average that is not 16-byte aligned is read and written element by element;
+ *       which path p / g / m / v take does not depend on it).  skip_nonfinite with clip_state[2] set leaves e
+ *       untouched like p / m / v.  ema_weight outside [0, 1] (or NaN), ema_device NULL or not aligned to a pointer:
+ *       LIC_ERR_INVALID, nothing launched; the limits (448 jobs) and the other rules are lic_adam_run_scaled's.
+ *       One launch, no allocation, no synchronisation; 36 bytes per element (p, g, m, v, e read; p, m, v, e written)
+ *       where lic_adam_run moves 28.
+ *   lic_swap_run       p <-> e, element by element, for every job with a non-NULL entry, in one launch on the same
+ *       partition; m, v and the gradients are not touched.  Calling it twice restores both sides bit for bit.  The
+ *       caller owns what is derived from p (packed weights, version counters).
+ * ------------------------------------------------------------------------------------------ */
+int lic_adam_run_ema(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
+                     const float* const* grads_host, double lr, double beta1, double beta2, double eps,
+                     double weight_decay, double bias_correction1, double bias_correction2, float* const* ema_device,
+                     double ema_weight, const float* clip_state, int32_t skip_nonfinite, lic_stream_t stream);
+int lic_swap_run(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks, float* const* ema_device,
+                 lic_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * lic_reduce_batch -- every pending reduction of a backward pass (Trainer.py:84 `loss.backward()`) in ONE launch.
  *   The weight-gradient launches end in a slab reduction and the column sums (bias / GDN beta gradients) in a second
  *   stage: 41 launches of 5-15 us per config-3 step.  lic_wgrad_bf16_partial / lic_colsum_bf16_partial /

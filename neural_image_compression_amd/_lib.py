@@ -239,6 +239,8 @@ SIGNATURES = {
     "lic_grad_norm_partial": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp]),
     "lic_grad_norm_finish": (C.c_int, [_vp, _i64, C.c_double, _i32, _vp, _vp]),
     "lic_adam_run_scaled": (C.c_int, [_vp, _i32, _i64, _vp] + [C.c_double] * 7 + [_vp, _i32, _vp]),
+    "lic_adam_run_ema": (C.c_int, [_vp, _i32, _i64, _vp] + [C.c_double] * 7 + [_vp, C.c_double, _vp, _i32, _vp]),
+    "lic_swap_run": (C.c_int, [_vp, _i32, _i64, _vp, _vp]),
     "lic_head_convt_bf16_supported": (C.c_int, [_i32] * 7),
     "lic_head_convt_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "lic_stem_conv_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -21,33 +21,55 @@ struct AdamGrads {
   const float* g[NG];
 };
 
-template <int NG>
-__global__ __launch_bounds__(256) void adam_kernel(const lic_adam_job* jobs, int njobs, const AdamGrads<NG> grads,
-                                                   float lerp_w, float beta2, float one_minus_beta2, float eps,
-                                                   float weight_decay, float step_size, float bc2_sqrt) {
-  __shared__ lic_adam_job job;
-  __shared__ int s_blk;
-  __shared__ const float* s_g;
-  if (threadIdx.x == 0) {
-    int lo = 0, hi = njobs - 1;
-    const int b = blockIdx.x;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (jobs[mid].block0 <= b) lo = mid;
-      else hi = mid - 1;
-    }
-    job = jobs[lo];
-    s_blk = b - jobs[lo].block0;
-    s_g = grads.g[lo];
+// the one rounding of g * coefficient that an unfused `grad.mul_(coefficient)` performs.  The empty asm makes the
+// product a value the optimiser cannot look into: hipcc would otherwise contract it into the multiply-adds of the
+// update, or pair it with `weight_decay * p` in one packed multiply and so undo the contraction adam_kernel gets
+// there -- either way other bits than the unfused order gives
+__device__ __forceinline__ float scale_once(float g, float coef) {
+  float r = g * coef;
+  asm volatile("" : "+v"(r));
+  return r;
+}
+
+// e + w * (p - e) in three separately rounded fp32 operations (lic.h: lic_adam_run_ema).  `p` arrives as a value
+// the optimiser cannot look into, so nothing of the average reaches back into how p itself was formed, and the
+// product is opaque as in scale_once: a fused multiply-add would round once where the statement rounds twice
+__device__ __forceinline__ float ema_once(float e, float p, float w) {
+  asm volatile("" : "+v"(p));
+  float s = __fmul_rn(w, __fsub_rn(p, e));
+  asm volatile("" : "+v"(s));
+  return __fadd_rn(e, s);
+}
+
+struct AdamScalars {
+  float lerp_w, beta2, one_minus_beta2, eps, weight_decay, step_size, bc2_sqrt;
+};
+
+// the job whose block range [block0, block0 + nblocks) holds this block (asked by thread 0 of every kernel here)
+__device__ __forceinline__ int adam_job_of_block(const lic_adam_job* jobs, int njobs) {
+  int lo = 0, hi = njobs - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].block0 <= b) lo = mid;
+    else hi = mid - 1;
   }
-  __syncthreads();
-  float* __restrict__ p = job.p;
-  const float* __restrict__ g = s_g;
-  float* __restrict__ m = job.m;
-  float* __restrict__ v = job.v;
-  const long n = job.n;
-  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
-  auto upd = [&](float& pw, float gw, float& mw, float& vw) {
+  return lo;
+}
+
+// The update of one block's <= AD_ITEMS elements: the ONE body of adam_kernel, adam_scaled_kernel (SCALED: the
+// gradient times `coef`, rounded once, on the way in) and adam_ema_kernel (EMA: one more stream `e`, read and
+// written beside p).  Whether p / g / m / v take the 16-byte path does not depend on `e`: a misaligned average
+// is read and written element by element inside it.  (The pointers carry no __restrict__: as function arguments
+// it would be honoured, unlike on the locals the kernels had before this body was shared, and the scalar loops of
+// the existing kernels would be interleaved and fused differently -- other bits.)
+template <bool SCALED, bool EMA>
+__device__ __forceinline__ void adam_block(float* p, const float* g, float* m, float* v, float* ea, long begin,
+                                           long end, const AdamScalars k, float coef, float ema_w) {
+  const float lerp_w = k.lerp_w, beta2 = k.beta2, one_minus_beta2 = k.one_minus_beta2, eps = k.eps;
+  const float weight_decay = k.weight_decay, step_size = k.step_size, bc2_sqrt = k.bc2_sqrt;
+  auto upd = [&](float& pw, float graw, float& mw, float& vw) {
+    float gw = SCALED ? scale_once(graw, coef) : graw;
     if (weight_decay != 0.0f) gw += weight_decay * pw;
     mw = lerp_w < 0.5f ? mw + lerp_w * (gw - mw) : gw - (gw - mw) * (1.0f - lerp_w);  // torch.lerp
     vw = vw * beta2;
@@ -55,11 +77,20 @@ __global__ __launch_bounds__(256) void adam_kernel(const lic_adam_job* jobs, int
     const float denom = sqrtf(vw) / bc2_sqrt + eps;
     pw = pw - step_size * (mw / denom);
   };
+  auto one = [&](long i) {
+    upd(p[i], g[i], m[i], v[i]);
+    if (EMA) ea[i] = ema_once(ea[i], p[i], ema_w);
+  };
   const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
                      reinterpret_cast<uintptr_t>(v)) & 15) == 0;
   if (vec) {
+    const bool evec = EMA && (reinterpret_cast<uintptr_t>(ea) & 15) == 0;
     const long e4 = begin + ((end - begin) & ~3L);
     for (long i = begin + threadIdx.x * 4L; i < e4; i += 256 * 4) {
+      // (the average is loaded in front of, and updated behind, the statements the three kernels share, under
+      // branches of its own: what the compiler pairs and fuses among those statements stays what it is without it)
+      f32x4 ew = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (evec) ew = *reinterpret_cast<const f32x4*>(ea + i);
       f32x4 pw = *reinterpret_cast<const f32x4*>(p + i), mw = *reinterpret_cast<const f32x4*>(m + i);
       f32x4 vw = *reinterpret_cast<const f32x4*>(v + i);
       const f32x4 gw = *reinterpret_cast<const f32x4*>(g + i);
@@ -74,11 +105,39 @@ __global__ __launch_bounds__(256) void adam_kernel(const lic_adam_job* jobs, int
       *reinterpret_cast<f32x4*>(p + i) = pw;
       *reinterpret_cast<f32x4*>(m + i) = mw;
       *reinterpret_cast<f32x4*>(v + i) = vw;
+      if (evec) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ew[e] = ema_once(ew[e], pw[e], ema_w);
+        *reinterpret_cast<f32x4*>(ea + i) = ew;
+      } else if (EMA) {  // an average off the 16-byte grid: element by element, from the p just stored
+#pragma unroll 1
+        for (int e = 0; e < 4; ++e) ea[i + e] = ema_once(ea[i + e], p[i + e], ema_w);
+      }
     }
-    for (long i = e4 + threadIdx.x; i < end; i += 256) upd(p[i], g[i], m[i], v[i]);
+    for (long i = e4 + threadIdx.x; i < end; i += 256) one(i);
   } else {
-    for (long i = begin + threadIdx.x; i < end; i += 256) upd(p[i], g[i], m[i], v[i]);
+    for (long i = begin + threadIdx.x; i < end; i += 256) one(i);
   }
+}
+
+template <int NG>
+__global__ __launch_bounds__(256) void adam_kernel(const lic_adam_job* jobs, int njobs, const AdamGrads<NG> grads,
+                                                   float lerp_w, float beta2, float one_minus_beta2, float eps,
+                                                   float weight_decay, float step_size, float bc2_sqrt) {
+  __shared__ lic_adam_job job;
+  __shared__ int s_blk;
+  __shared__ const float* s_g;
+  if (threadIdx.x == 0) {
+    const int lo = adam_job_of_block(jobs, njobs);
+    job = jobs[lo];
+    s_blk = blockIdx.x - jobs[lo].block0;
+    s_g = grads.g[lo];
+  }
+  __syncthreads();
+  const long n = job.n;
+  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
+  adam_block<false, false>(job.p, s_g, job.m, job.v, nullptr, begin, end,
+                           AdamScalars{lerp_w, beta2, one_minus_beta2, eps, weight_decay, step_size, bc2_sqrt}, 1.0f, 0.0f);
 }
 // lic_grad_norm_partial / lic_grad_norm_finish / lic_adam_run_scaled: the global-norm clipping of the usual recipe
 // for these models (torch.nn.utils.clip_grad_norm_ before optimizer.step(): a handful of foreach launches that
@@ -102,15 +161,9 @@ __global__ __launch_bounds__(256) void grad_norm_partial_kernel(const lic_adam_j
   __shared__ const float* s_g;
   __shared__ double s_wave[4];
   if (threadIdx.x == 0) {
-    int lo = 0, hi = njobs - 1;
-    const int b = blockIdx.x;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (jobs[mid].block0 <= b) lo = mid;
-      else hi = mid - 1;
-    }
+    const int lo = adam_job_of_block(jobs, njobs);
     s_n = jobs[lo].n;
-    s_blk = b - jobs[lo].block0;
+    s_blk = blockIdx.x - jobs[lo].block0;
     s_g = grads.g[lo];
   }
   __syncthreads();
@@ -157,16 +210,6 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
   }
 }
 
-// the one rounding of g * coefficient that an unfused `grad.mul_(coefficient)` performs.  The empty asm makes the
-// product a value the optimiser cannot look into: hipcc would otherwise contract it into the multiply-adds of the
-// update, or pair it with `weight_decay * p` in one packed multiply and so undo the contraction adam_kernel gets
-// there -- either way other bits than the unfused order gives
-__device__ __forceinline__ float scale_once(float g, float coef) {
-  float r = g * coef;
-  asm volatile("" : "+v"(r));
-  return r;
-}
-
 // adam_kernel with the gradient scaled by clip_state[1] on the way in, and nothing done at all when the caller
 // asked for non-finite steps to be skipped and clip_state[2] says this one is
 template <int NG>
@@ -180,56 +223,87 @@ __global__ __launch_bounds__(256) void adam_scaled_kernel(const lic_adam_job* jo
   __shared__ int s_blk;
   __shared__ const float* s_g;
   if (threadIdx.x == 0) {
-    int lo = 0, hi = njobs - 1;
-    const int b = blockIdx.x;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (jobs[mid].block0 <= b) lo = mid;
-      else hi = mid - 1;
-    }
+    const int lo = adam_job_of_block(jobs, njobs);
     job = jobs[lo];
-    s_blk = b - jobs[lo].block0;
+    s_blk = blockIdx.x - jobs[lo].block0;
     s_g = grads.g[lo];
   }
   __syncthreads();
-  float* __restrict__ p = job.p;
-  const float* __restrict__ g = s_g;
-  float* __restrict__ m = job.m;
-  float* __restrict__ v = job.v;
   const long n = job.n;
   const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
-  auto upd = [&](float& pw, float graw, float& mw, float& vw) {
-    float gw = scale_once(graw, coef);
-    if (weight_decay != 0.0f) gw += weight_decay * pw;
-    mw = lerp_w < 0.5f ? mw + lerp_w * (gw - mw) : gw - (gw - mw) * (1.0f - lerp_w);  // torch.lerp
-    vw = vw * beta2;
-    vw = vw + (one_minus_beta2 * gw) * gw;
-    const float denom = sqrtf(vw) / bc2_sqrt + eps;
-    pw = pw - step_size * (mw / denom);
+  adam_block<true, false>(job.p, s_g, job.m, job.v, nullptr, begin, end,
+                          AdamScalars{lerp_w, beta2, one_minus_beta2, eps, weight_decay, step_size, bc2_sqrt}, coef, 0.0f);
+}
+
+// lic_adam_run_ema: either of the two kernels above (SCALED: adam_scaled_kernel with its guard, else adam_kernel)
+// with the exponential moving average of every parameter updated from the new p while it is in registers.  The
+// averages are persistent buffers: their addresses live in a device table `ema` (one per job, NULL = no average for
+// that tensor) and do not travel per step.  36 bytes per element instead of 28: e is read and written once.
+template <int NG, bool SCALED>
+__global__ __launch_bounds__(256) void adam_ema_kernel(const lic_adam_job* jobs, int njobs, const AdamGrads<NG> grads,
+                                                       float lerp_w, float beta2, float one_minus_beta2, float eps,
+                                                       float weight_decay, float step_size, float bc2_sqrt,
+                                                       const float* __restrict__ clip_state, int skip_nonfinite,
+                                                       float* const* __restrict__ ema, float ema_w) {
+  float coef = 1.0f;
+  if (SCALED) {
+    if (skip_nonfinite && reinterpret_cast<const unsigned*>(clip_state)[2] != 0u) return;  // (uniform over the grid)
+    coef = clip_state[1];
+  }
+  __shared__ lic_adam_job job;
+  __shared__ int s_blk;
+  __shared__ const float* s_g;
+  __shared__ float* s_e;
+  if (threadIdx.x == 0) {
+    const int lo = adam_job_of_block(jobs, njobs);
+    job = jobs[lo];
+    s_blk = blockIdx.x - jobs[lo].block0;
+    s_g = grads.g[lo];
+    s_e = ema[lo];
+  }
+  __syncthreads();
+  const long n = job.n;
+  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
+  const AdamScalars k{lerp_w, beta2, one_minus_beta2, eps, weight_decay, step_size, bc2_sqrt};
+  float* e = s_e;
+  if (e) adam_block<SCALED, true>(job.p, s_g, job.m, job.v, e, begin, end, k, coef, ema_w);
+  else adam_block<SCALED, false>(job.p, s_g, job.m, job.v, nullptr, begin, end, k, coef, 0.0f);
+}
+
+// lic_swap_run: p <-> e for every job that has an average, on the lic_adam_plan partition; loads and stores only
+__global__ __launch_bounds__(256) void swap_kernel(const lic_adam_job* jobs, int njobs, float* const* __restrict__ ema) {
+  __shared__ float* s_p;
+  __shared__ float* s_e;
+  __shared__ long s_n;
+  __shared__ int s_blk;
+  if (threadIdx.x == 0) {
+    const int lo = adam_job_of_block(jobs, njobs);
+    s_p = jobs[lo].p;
+    s_e = ema[lo];
+    s_n = jobs[lo].n;
+    s_blk = blockIdx.x - jobs[lo].block0;
+  }
+  __syncthreads();
+  float* __restrict__ p = s_p;
+  float* __restrict__ e = s_e;
+  if (!e) return;  // (uniform over the block)
+  const long n = s_n;
+  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
+  auto one = [&](long i) {
+    const float t = p[i];
+    p[i] = e[i];
+    e[i] = t;
   };
-  const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                     reinterpret_cast<uintptr_t>(v)) & 15) == 0;
-  if (vec) {
+  if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(e)) & 15) == 0) {
     const long e4 = begin + ((end - begin) & ~3L);
     for (long i = begin + threadIdx.x * 4L; i < e4; i += 256 * 4) {
-      f32x4 pw = *reinterpret_cast<const f32x4*>(p + i), mw = *reinterpret_cast<const f32x4*>(m + i);
-      f32x4 vw = *reinterpret_cast<const f32x4*>(v + i);
-      const f32x4 gw = *reinterpret_cast<const f32x4*>(g + i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pw[e], me = mw[e], ve = vw[e];
-        upd(pe, gw[e], me, ve);
-        pw[e] = pe;
-        mw[e] = me;
-        vw[e] = ve;
-      }
-      *reinterpret_cast<f32x4*>(p + i) = pw;
-      *reinterpret_cast<f32x4*>(m + i) = mw;
-      *reinterpret_cast<f32x4*>(v + i) = vw;
+      const f32x4 pw = *reinterpret_cast<const f32x4*>(p + i), ew = *reinterpret_cast<const f32x4*>(e + i);
+      *reinterpret_cast<f32x4*>(p + i) = ew;
+      *reinterpret_cast<f32x4*>(e + i) = pw;
     }
-    for (long i = e4 + threadIdx.x; i < end; i += 256) upd(p[i], g[i], m[i], v[i]);
+    for (long i = e4 + threadIdx.x; i < end; i += 256) one(i);
   } else {
-    for (long i = begin + threadIdx.x; i < end; i += 256) upd(p[i], g[i], m[i], v[i]);
+    for (long i = begin + threadIdx.x; i < end; i += 256) one(i);
   }
 }
 }  // namespace
@@ -349,5 +423,64 @@ LIC_EXPORT int lic_adam_run_scaled(const lic_adam_job* jobs_device, int32_t njob
     adam_scaled_launch<224>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, clip_state, sk, s);
   else
     adam_scaled_launch<448>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, clip_state, sk, s);
+  return lic_check_launch();
+}
+
+template <int NG, bool SCALED>
+static void adam_ema_launch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads,
+                            const AdamScalars& k, float* const* ema, float ema_w, const float* clip_state, int skip,
+                            hipStream_t s) {
+  AdamGrads<NG> a;
+  for (int i = 0; i < NG; ++i) a.g[i] = i < njobs ? grads[i] : nullptr;
+  hipLaunchKernelGGL((adam_ema_kernel<NG, SCALED>), dim3((unsigned)blocks), dim3(256), 0, s, jobs_device, njobs, a,
+                     k.lerp_w, k.beta2, k.one_minus_beta2, k.eps, k.weight_decay, k.step_size, k.bc2_sqrt, clip_state, skip,
+                     ema, ema_w);
+}
+
+template <bool SCALED>
+static void adam_ema_dispatch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads,
+                              const AdamScalars& k, float* const* ema, float ema_w, const float* clip_state, int skip,
+                              hipStream_t s) {
+  if (njobs <= 96) adam_ema_launch<96, SCALED>(jobs_device, njobs, blocks, grads, k, ema, ema_w, clip_state, skip, s);
+  else if (njobs <= 224) adam_ema_launch<224, SCALED>(jobs_device, njobs, blocks, grads, k, ema, ema_w, clip_state, skip, s);
+  else adam_ema_launch<448, SCALED>(jobs_device, njobs, blocks, grads, k, ema, ema_w, clip_state, skip, s);
+}
+
+// lic_adam_run (clip_state NULL) or lic_adam_run_scaled (clip_state given) that also moves the exponential moving
+// average of every parameter: e += w * (p_new - e), w = (float)ema_weight, three fp32 roundings.  ema_device: DEVICE
+// array of njobs float* (NULL entry: that tensor has no average); a skipped step leaves e alone as it does p / m / v
+LIC_EXPORT int lic_adam_run_ema(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
+                                const float* const* grads_host, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, double bias_correction1, double bias_correction2,
+                                float* const* ema_device, double ema_weight, const float* clip_state,
+                                int32_t skip_nonfinite, lic_stream_t stream) {
+  if (!jobs_device || !grads_host || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL) return LIC_ERR_INVALID;
+  if (!ema_device || (reinterpret_cast<uintptr_t>(ema_device) & (sizeof(float*) - 1)) != 0) return LIC_ERR_INVALID;
+  if (!(ema_weight >= 0.0 && ema_weight <= 1.0)) return LIC_ERR_INVALID;  // (a NaN too)
+  if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) return LIC_ERR_INVALID;
+  if (njobs > 448) return LIC_ERR_UNSUPPORTED;
+  for (int i = 0; i < njobs; ++i)
+    if (!grads_host[i]) return LIC_ERR_INVALID;
+  const AdamScalars k{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay,
+                      (float)(lr / bias_correction1), (float)sqrt(bias_correction2)};
+  const float w = (float)ema_weight;
+  hipStream_t s = (hipStream_t)stream;
+  if (clip_state)
+    adam_ema_dispatch<true>(jobs_device, njobs, total_blocks, grads_host, k, ema_device, w, clip_state,
+                            skip_nonfinite ? 1 : 0, s);
+  else
+    adam_ema_dispatch<false>(jobs_device, njobs, total_blocks, grads_host, k, ema_device, w, nullptr, 0, s);
+  return lic_check_launch();
+}
+
+// p <-> e, element by element, for every job whose ema_device entry is not NULL: the averaged weights become the
+// live ones (and back).  The job table and partition of lic_adam_run; m / v / g are not touched
+LIC_EXPORT int lic_swap_run(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
+                            float* const* ema_device, lic_stream_t stream) {
+  if (!jobs_device || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL) return LIC_ERR_INVALID;
+  if (!ema_device || (reinterpret_cast<uintptr_t>(ema_device) & (sizeof(float*) - 1)) != 0) return LIC_ERR_INVALID;
+  if (njobs > 448) return LIC_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(swap_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_device,
+                     njobs, ema_device);
   return lic_check_launch();
 }

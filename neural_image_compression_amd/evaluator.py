@@ -7,6 +7,8 @@ computed on the device by `functional.ms_ssim` / `lic_msssim`, which follows tha
 published 0.2.1 algorithm (parity unpinned).  The reference's aggregation reports
 `BPP` = mean(bpp_y) (Evaluator.py:81 uses bpp_y_values); this class reproduces that under 'BPP'
 for drop-in compatibility and adds the intended value as 'BPP(total)'.
+`load_checkpoint_weights(model, path)` puts the averaged weights of a checkpoint into the model to be
+evaluated when the checkpoint has them, the trained ones otherwise.
 """
 from __future__ import annotations
 
@@ -21,6 +23,17 @@ _LUMA = (0.299, 0.587, 0.114)   # BT.601 weights the reference uses for its luma
 
 def _psnr_unit_range(mse: float) -> float:
     return float("inf") if mse <= 0 else -10.0 * math.log10(mse)
+
+
+def load_checkpoint_weights(model, checkpoint, ema: bool = True, map_location=None):
+    """Load the weights a checkpoint of `trainer.Trainer` (or of the reference's Trainer) holds into `model`: the moving
+    average of the weights (`ema_state_dict`, written when the optimizer keeps one) when `ema` is set and the checkpoint
+    has it, else the trained weights (`model`).  `checkpoint`: a path or the loaded dict.  Returns the key it used."""
+    if not isinstance(checkpoint, dict):
+        checkpoint = torch.load(checkpoint, map_location=map_location)
+    key = "ema_state_dict" if ema and checkpoint.get("ema_state_dict") is not None else "model"
+    model.load_state_dict(checkpoint[key])
+    return key
 
 
 class _RunningMeans:

@@ -18,10 +18,24 @@ the number of steps the guard dropped.  ONE deviation from GradScaler-style skip
 parameters and moments untouched but still advances the step count, because the bias corrections are computed on
 the host from that count and the host does not know the flag.  (The fallback path reads the norm back anyway and
 skips before torch's step, so there the count stays.)  `grad_norm(parameters)` is the norm alone, for any optimizer.
+
+`FusedAdam(..., ema_decay=d, ema_warmup=True)` keeps the exponential moving average of the weights these models are
+evaluated and shipped with, in `state[p]["ema"]`, inside the same launch (`lic_adam_run_ema`: the parameter is in
+registers when its average moves -- no foreach launches, no second read of every parameter):
+    e += w * (p_new - e),  w = 1 - d_t,  d_t = min(d, (1 + t) / (10 + t)) with warm-up, d without
+with t the 1-based step count the bias corrections use, w formed in double on the host and rounded to fp32 once, and
+three fp32 roundings per element.  The torch path applies the same three operations after torch's step and gives the
+same bits for the same p.  `swap_ema()` exchanges weights and averages (`lic_swap_run`) and bumps the version
+counter of every tensor it wrote, so whatever is derived from the parameters (prep.StepPrep, functional.PREPARED,
+the masked context weight, the bf16 packs) is derived again; `with opt.ema_weights():` swaps in and back,
+`ema_state_dict(model)` is the model's state dict under the averages.  `step()` refuses to run while swapped.
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes as C
+import struct
 
 import torch
 
@@ -33,18 +47,25 @@ class FusedAdam(torch.optim.Adam):
     MAX_TENSORS = 448   # per parameter group (include/lic.h: lic_adam_run)
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
-                 max_grad_norm=None, skip_nonfinite=False, **kw):
+                 max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=True, **kw):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
         # global-norm clipping over ALL groups (torch.nn.utils.clip_grad_norm_'s max_norm) / leave the step out when
         # the norm is not finite.  Attributes of the optimizer, not of param_groups: the state dict stays torch's
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
             raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        # the moving average of the weights: state[p]["ema"], part of the state dict only when it is on
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
+        self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
+        self.swapped = False      # True while the averages are the live weights (swap_ema)
+        self._swap_tabs = {}      # group index -> (key, device job table, njobs, blocks, device table of averages)
         self._clip_state = None   # 4 dwords on the device: norm, coefficient, not-finite flag, skipped steps (lic.h)
         self._partials = None     # one double per block of every group (lic_grad_norm_partial), allocated per plan
         self._last_norm = None    # what grad_norm() returns
         self._skipped_host = 0    # steps skipped on the fallback path
         self._tables = {}   # group index -> (key, device job table, njobs, blocks, ctypes array of gradient pointers)
+        self._ema_tabs = {}  # group index -> device array of the averages' addresses, built with (and for) _tables[gi]
         self._fast = None   # the last planned step, re-used while nothing it depends on changed
         self._t0, self._lazy = 0.0, 0   # step count the plan started from / fast steps not yet written to the state
         self.fused_steps = 0
@@ -85,10 +106,17 @@ class FusedAdam(torch.optim.Adam):
                 "lic_grad_norm_finish")
         self._last_norm = self._clip_state[0]
 
-    def _launch(self, lib, group, tab, t, clip):
+    def _launch(self, lib, group, tab, t, clip, etab=None):
         _, dev_tab, njobs, blocks, gptrs = tab
         beta1, beta2 = group["betas"]
-        if not clip:
+        if etab is not None:
+            state = C.c_void_p(self._clip_state.data_ptr()) if clip else None
+            L.check(lib.lic_adam_run_ema(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]),
+                                         float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
+                                         1.0 - beta1 ** t, 1.0 - beta2 ** t, C.c_void_p(etab.data_ptr()),
+                                         self._ema_weight(t), state, int(self.skip_nonfinite), F_._stream()),
+                    "lic_adam_run_ema")
+        elif not clip:
             L.check(lib.lic_adam_run(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]),
                                      float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
                                      1.0 - beta1 ** t, 1.0 - beta2 ** t, F_._stream()), "lic_adam_run")
@@ -98,6 +126,24 @@ class FusedAdam(torch.optim.Adam):
                                             float(group["weight_decay"]), 1.0 - beta1 ** t, 1.0 - beta2 ** t,
                                             C.c_void_p(self._clip_state.data_ptr()), int(self.skip_nonfinite),
                                             F_._stream()), "lic_adam_run_scaled")
+
+    def _ema_weight(self, t):
+        """w of e += w * (p - e) at the 1-based step count t, in double (lic.h: lic_adam_run_ema rounds it once)"""
+        d = self.ema_decay
+        if self.ema_warmup:
+            d = min(d, (1.0 + t) / (10.0 + t))
+        return 1.0 - d
+
+    def _ema_buffers(self, params):
+        """state[p]["ema"] of every parameter, created as a copy of p where the state has none yet (a new state, or
+        one loaded from a state dict without averages)"""
+        out = []
+        for p in params:
+            st = self.state[p]
+            if "ema" not in st:
+                st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)
+            out.append(st["ema"])
+        return out
 
     def grad_norm(self):
         """global L2 norm of the gradients of the last step(): a 0-dim tensor on the parameters' device (a view of the
@@ -118,6 +164,9 @@ class FusedAdam(torch.optim.Adam):
 
     @torch.no_grad()
     def step(self, closure=None):
+        if self.swapped:
+            raise RuntimeError("step() while the averaged weights are swapped in: call swap_ema() first (or leave the "
+                               "ema_weights() context)")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -129,7 +178,7 @@ class FusedAdam(torch.optim.Adam):
         fast = self._fast
         if fast is not None and len(fast) == len(self.param_groups):
             ok = True
-            for (group, plist, params, hyper, (tab, _, _)), g in zip(fast, self.param_groups):
+            for (group, plist, params, hyper, (tab, _, _, _)), g in zip(fast, self.param_groups):
                 if g is not group or g["params"] is not plist or len(plist) != len(params) or \
                         (g["lr"], g["betas"], g["eps"], g["weight_decay"], g["amsgrad"], g.get("maximize"),
                          g.get("capturable"), g.get("differentiable")) != hyper:
@@ -145,15 +194,15 @@ class FusedAdam(torch.optim.Adam):
             if ok:
                 lib = L.load()
                 clip = self._clipping()
-                for group, plist, params, hyper, (tab, moments, steps) in fast:
+                for group, plist, params, hyper, (tab, moments, steps, etab) in fast:
                     gptrs = tab[4]
                     for i, p in enumerate(params):
                         gptrs[i] = p.grad.data_ptr()
                 if clip:    # (the norm is global: every group's partial sums before the first update)
                     self._clip_prologue(lib, [f[4][0] for f in fast])
                 t = self._t0 + self._lazy + 1.0
-                for group, plist, params, hyper, (tab, moments, steps) in fast:
-                    self._launch(lib, group, tab, t, clip)
+                for group, plist, params, hyper, (tab, moments, steps, etab) in fast:
+                    self._launch(lib, group, tab, t, clip, etab)
                     torch.autograd.graph.increment_version(moments)
                 # the per-parameter `step` tensors of the state (CPU scalars, one per parameter: bumping them is ~240
                 # small ATen calls per step) are brought up to date lazily: _flush_steps() before anything reads them
@@ -166,16 +215,22 @@ class FusedAdam(torch.optim.Adam):
         for gi, group in enumerate(self.param_groups):
             params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps = [], [], [], [], [], []
             self._init_group(group, params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps)
+            emas = self._ema_buffers(params) if self.ema_decay is not None else None
             if len(params) != len([p for p in group["params"]]) or not self._eligible(group, params, grads) or \
                     not all(m.is_contiguous() and v.is_contiguous() for m, v in zip(exp_avgs, exp_avg_sqs)) or \
                     len({float(s) for s in steps}) != 1:
                 return self._fallback(loss)
-            plans.append((gi, group, params, grads, exp_avgs, exp_avg_sqs, steps))
+            if emas is not None and not all(e.is_contiguous() and e.dtype == torch.float32 and e.device == p.device
+                                            for p, e in zip(params, emas)):
+                return self._fallback(loss)
+            plans.append((gi, group, params, grads, exp_avgs, exp_avg_sqs, steps, emas))
         lib = L.load()
         clip = self._clipping()
         tabs = []
-        for gi, group, params, grads, exp_avgs, exp_avg_sqs, steps in plans:
+        for gi, group, params, grads, exp_avgs, exp_avg_sqs, steps, emas in plans:
             key = tuple((p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) for p, m, v in zip(params, exp_avgs, exp_avg_sqs))
+            if emas is not None:    # (the averages' addresses are part of what the plan was made for)
+                key = tuple(k + (e.data_ptr(),) for k, e in zip(key, emas))
             tab = self._tables.get(gi)
             if tab is None or tab[0] != key:
                 arr = (L.AdamJob * len(params))()
@@ -186,6 +241,8 @@ class FusedAdam(torch.optim.Adam):
                     raise L.LicError(f"lic_adam_plan failed: {blocks}")
                 dev_tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(params[0].device)
                 tab = self._tables[gi] = (key, dev_tab, len(params), int(blocks), (C.c_void_p * len(params))())
+                self._ema_tabs[gi] = None if emas is None else \
+                    torch.tensor([e.data_ptr() for e in emas], dtype=torch.int64).to(params[0].device)
             gptrs = tab[4]
             for i, g in enumerate(grads):       # gradients are fresh tensors every step: their addresses go along
                 gptrs[i] = g.data_ptr()         # as kernel arguments (copied at launch)
@@ -193,19 +250,20 @@ class FusedAdam(torch.optim.Adam):
         if clip:
             self._clip_prologue(lib, tabs)
         fast = []
-        for (gi, group, params, grads, exp_avgs, exp_avg_sqs, steps), tab in zip(plans, tabs):
-            self._launch(lib, group, tab, float(steps[0]) + 1.0, clip)
+        for (gi, group, params, grads, exp_avgs, exp_avg_sqs, steps, emas), tab in zip(plans, tabs):
+            etab = self._ema_tabs.get(gi) if emas is not None else None
+            self._launch(lib, group, tab, float(steps[0]) + 1.0, clip, etab)
             for s in steps:     # (only once the launch went out: a refused launch leaves the state untouched)
                 s += 1
             # the kernel wrote through raw pointers: tell autograd (and prep.StepPrep, which re-derives the packed
             # weights when a parameter's version moves) that the parameters and moments changed
-            moments = params + exp_avgs + exp_avg_sqs
+            moments = params + exp_avgs + exp_avg_sqs + (emas or [])
             torch.autograd.graph.increment_version(moments)
             hyper = (group["lr"], group["betas"], group["eps"], group["weight_decay"], group["amsgrad"],
                      group.get("maximize"), group.get("capturable"), group.get("differentiable"))
             # (the job table holds the parameter / moment addresses: valid while these very tensors are the state)
             if all(p.data_ptr() == k[0] for p, k in zip(params, tab[0])) and len(params) == len(group["params"]):
-                fast.append((group, group["params"], list(params), hyper, (tab, moments, list(steps))))
+                fast.append((group, group["params"], list(params), hyper, (tab, moments, list(steps), etab)))
         if len(fast) == len(self.param_groups) and len({float(f[4][2][0]) for f in fast}) == 1:
             self._fast = fast
             self._t0, self._lazy = float(fast[0][4][2][0]), 0
@@ -216,7 +274,7 @@ class FusedAdam(torch.optim.Adam):
         """apply the step counts the fast path has not yet written into the state's `step` tensors"""
         n, fast = getattr(self, "_lazy", 0), self._fast
         if n and fast is not None:
-            for _, _, _, _, (_, _, steps) in fast:
+            for _, _, _, _, (_, _, steps, _) in fast:
                 for s in steps:
                     s += n
             self._t0 += n
@@ -238,7 +296,7 @@ class FusedAdam(torch.optim.Adam):
     def load_state_dict(self, state_dict):
         self._flush_steps()
         self._fast = None          # (new state tensors: plan again)
-        self._tables = {}
+        self._tables, self._ema_tabs, self._swap_tabs = {}, {}, {}
         return super().load_state_dict(state_dict)
 
     def add_param_group(self, param_group):
@@ -260,9 +318,107 @@ class FusedAdam(torch.optim.Adam):
             self._last_norm = norm
             if self.skip_nonfinite and not bool(torch.isfinite(norm)):   # (the one synchronisation of this path)
                 self._skipped_host += 1
-                return loss
+                return loss    # (the averages stay as they are, like everything else)
+        if self.ema_decay is None:
+            super().step()
+            return loss
+        # torch creates a parameter's state only where it finds none at all: the copies the averages start from
+        # are taken before the step and entered behind it
+        start = {p: p.detach().clone(memory_format=torch.contiguous_format) for group in self.param_groups
+                 for p in group["params"] if p.grad is not None and "ema" not in self.state.get(p, {})}
+        stepped = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
         super().step()
+        by_count = collections.defaultdict(list)
+        for p in stepped:
+            st = self.state[p]
+            if "ema" not in st:
+                st["ema"] = start[p]
+            by_count[float(st["step"])].append(p)
+        for t, ps in by_count.items():
+            # lic_adam_run_ema's three roundings: p - e, w * (...), e + (...), w rounded to fp32 once
+            w = struct.unpack("f", struct.pack("f", self._ema_weight(t)))[0]
+            es = [self.state[p]["ema"] for p in ps]
+            diff = torch._foreach_sub([p.detach() for p in ps], es)
+            torch._foreach_mul_(diff, w)
+            torch._foreach_add_(es, diff)
         return loss
+
+    # -- the averaged weights ------------------------------------------------------------------------------------
+    def _swap_fused(self, pairs):
+        if len(pairs) > self.MAX_TENSORS:
+            return False
+        dev = pairs[0][0].device
+        for p, e in pairs:
+            if p.device != dev or not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or \
+                    e.device != dev or e.dtype != torch.float32 or not e.is_contiguous() or p.numel() == 0:
+                return False
+        return dev.index == torch.cuda.current_device()
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange every parameter with its average, bit for bit: one `lic_swap_run` per group that a fused step can
+        take, torch copies otherwise.  Every tensor written gets its version counter bumped, so step preparation and
+        every cache keyed on a parameter's version derive their buffers again on the next forward -- nothing for the
+        caller to remember.  `swapped` says which side is live."""
+        if self.ema_decay is None:
+            raise RuntimeError("the moving average is off: construct FusedAdam with ema_decay=")
+        written = []
+        for gi, group in enumerate(self.param_groups):
+            pairs = [(p, self.state[p]["ema"]) for p in group["params"] if "ema" in self.state.get(p, {})]
+            if not pairs:
+                continue
+            if self._swap_fused(pairs):
+                lib = L.load()
+                key = tuple((p.data_ptr(), e.data_ptr(), p.numel()) for p, e in pairs)
+                tab = self._swap_tabs.get(gi)
+                if tab is None or tab[0] != key:
+                    arr = (L.AdamJob * len(pairs))()
+                    for j, (p, e) in zip(arr, pairs):   # (only p and n are read: lic_adam_plan wants m / v non-null)
+                        j.p = j.m = j.v = p.data_ptr()
+                        j.n = p.numel()
+                    blocks = lib.lic_adam_plan(arr, len(pairs))
+                    if blocks <= 0:
+                        raise L.LicError(f"lic_adam_plan failed: {blocks}")
+                    dev = pairs[0][0].device
+                    tab = self._swap_tabs[gi] = (
+                        key, torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), len(pairs), int(blocks),
+                        torch.tensor([e.data_ptr() for _, e in pairs], dtype=torch.int64).to(dev))
+                L.check(lib.lic_swap_run(C.c_void_p(tab[1].data_ptr()), tab[2], tab[3], C.c_void_p(tab[4].data_ptr()),
+                                         F_._stream()), "lic_swap_run")
+                for p, e in pairs:      # (written through raw pointers: tell autograd and everything keyed on versions)
+                    written += [p, e]
+            else:
+                for p, e in pairs:      # (in-place ops on a detached view bump the parameter's own counter)
+                    keep = p.detach().clone()
+                    p.detach().copy_(e)
+                    e.copy_(keep)
+        if written:
+            torch.autograd.graph.increment_version(written)
+        self.swapped = not self.swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with opt.ema_weights():` -- the averaged weights are the live ones inside (validation, coding), the trained
+        ones again behind it, whatever happens inside"""
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    @torch.no_grad()
+    def ema_state_dict(self, model):
+        """`model.state_dict()` with every averaged parameter replaced by its average (copies; buffers and parameters
+        without an average as they are).  The model is not touched."""
+        if self.ema_decay is None:
+            raise RuntimeError("the moving average is off: construct FusedAdam with ema_decay=")
+        out = collections.OrderedDict((k, v.detach().clone()) for k, v in model.state_dict().items())
+        if not self.swapped:    # (while swapped the model already holds the averages)
+            for name, p in model.named_parameters(remove_duplicate=False):
+                e = self.state.get(p, {}).get("ema")
+                if e is not None and name in out:
+                    out[name] = e.detach().clone().view_as(out[name])
+        return out
 
 
 _norm_tables = {}   # (device, tensor lengths) -> [(device job table, njobs, blocks)] of grad_norm()

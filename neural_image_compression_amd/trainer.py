@@ -16,7 +16,10 @@ installed, otherwise to <log_dir>/scalars.jsonl (summaries as JSON objects).
 Added to the reference's contract as trailing keyword arguments: `clip_max_norm` (global-norm gradient clipping, the
 `torch.nn.utils.clip_grad_norm_(model.parameters(), clip_max_norm)` of the usual recipe for these models) and
 `skip_nonfinite` (a step whose gradient norm is not finite is left out); `train/grad_norm` and
-`train/skipped_steps` are logged every `log_interval`.
+`train/skipped_steps` are logged every `log_interval`; `ema_eval` (with a FusedAdam(ema_decay=...)): validation runs on
+the moving average of the weights, swapped in for its duration.  Whenever the optimizer averages, the checkpoint
+holds the averaged model under one more key, `ema_state_dict`, which loaders of the reference's format ignore; the
+averages themselves travel in the optimizer's state dict.
 """
 from __future__ import annotations
 
@@ -74,7 +77,7 @@ class Trainer:
                  scheduler=None, max_steps=10000, resume=False, log_interval=None, img_interval=None,
                  val_interval=None, log_dir="runs/experiment", checkpoint_path="./checkpoints/checkpoint.pth",
                  device="cuda", distributed: Optional[bool] = None, writer=None, step_plan: bool = False,
-                 clip_max_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 clip_max_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_eval: bool = False):
         if rd_loss is None:
             raise ValueError("You must provide a rate-distortion loss function (`rd_loss`)")
         self.device = device
@@ -89,6 +92,7 @@ class Trainer:
         self.log_statistics = True  # latent / likelihood summaries every log_interval (Trainer.py:88-92)
         self.scheduler, self.use_plateau = _build_scheduler(scheduler, optimizer, max_steps)
         self.resume, self.checkpoint_path = resume, checkpoint_path
+        self.ema_eval = bool(ema_eval)
         if resume and checkpoint_path is not None and os.path.exists(checkpoint_path):
             self.load_checkpoint()
         # data parallel: one process per GPU; gradients all-reduced (mean) once per step
@@ -129,8 +133,15 @@ class Trainer:
     # -- checkpointing: the reference's file format (Trainer.py:52-71) ---------------------------
     def _checkpoint_state(self):
         sched = None if self.scheduler is None else self.scheduler.state_dict()
-        return {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "step": self.step,
-                "scheduler": sched}
+        state = {"model": self.model.state_dict(), "optimizer": self.optimizer.state_dict(), "step": self.step,
+                 "scheduler": sched}
+        if self._averages():
+            state["ema_state_dict"] = self.optimizer.ema_state_dict(self.model)
+        return state
+
+    def _averages(self):
+        """does the optimizer keep a moving average of the weights (optim.FusedAdam(ema_decay=...))"""
+        return getattr(self.optimizer, "ema_decay", None) is not None and hasattr(self.optimizer, "ema_weights")
 
     def save_checkpoint(self):
         if self.rank != 0:   # replicas are identical: one writer
@@ -295,9 +306,17 @@ class Trainer:
             used = (model_out['weights'].detach() > 1e-4).float().sum(dim=1).mean()
             self.writer.add_scalar("entropy_params/used_components_mean", float(used), self.step)
 
+    def validate(self):
+        """one validation pass (as `train()` runs every `val_interval`): on the averaged weights when `ema_eval` is set
+        and the optimizer averages, with the trained weights back in place behind it"""
+        return self._validate()
+
     def _validate(self):
         """mean loss / bpp / PSNR over the validation loader in eval mode (Trainer.py:145-165); under data
         parallelism the three means are averaged over the ranks"""
+        if self.ema_eval and self._averages() and not self.optimizer.swapped:
+            with self.optimizer.ema_weights():
+                return self._validate()
         sums = [0.0, 0.0, 0.0]
         self.model.eval()
         with torch.no_grad():
