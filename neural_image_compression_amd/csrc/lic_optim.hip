@@ -11,6 +11,8 @@
 #include "lic_common.h"
 #include <math.h>
 
+#include <type_traits>
+
 namespace {
 constexpr int AD_ITEMS = 4096;  // elements per block
 
@@ -57,9 +59,40 @@ __device__ __forceinline__ int adam_job_of_block(const lic_adam_job* jobs, int n
   return lo;
 }
 
-// The update of one block's <= AD_ITEMS elements: the ONE body of adam_kernel, adam_scaled_kernel (SCALED: the
-// gradient times `coef`, rounded once, on the way in) and adam_ema_kernel (EMA: one more stream `e`, read and
-// written beside p).  Whether p / g / m / v take the 16-byte path does not depend on `e`: a misaligned average
+// What a block works on: its job, that job's gradient and average (nullptr where the kernel reads no such table, or
+// the table has no entry), and the block's elements [begin, end) of the job's n.
+struct AdamWork {
+  float *p, *m, *v, *e;
+  const float* g;
+  long begin, end;
+};
+
+// The ONE prologue of every kernel on the lic_adam_plan partition: thread 0 finds the job, hands it to the block
+// through shared memory with the addresses that travel beside the table (GRADS / EMA: which of the two tables the
+// kernel reads), and every thread derives its range.
+template <bool GRADS, bool EMA>
+__device__ __forceinline__ AdamWork adam_work_of_block(const lic_adam_job* jobs, int njobs, const float* const* grads,
+                                                       float* const* ema) {
+  __shared__ lic_adam_job job;
+  __shared__ int s_blk;
+  __shared__ const float* s_g;
+  __shared__ float* s_e;
+  if (threadIdx.x == 0) {
+    const int lo = adam_job_of_block(jobs, njobs);
+    job = jobs[lo];
+    s_blk = blockIdx.x - jobs[lo].block0;
+    s_g = GRADS ? grads[lo] : nullptr;
+    s_e = EMA ? ema[lo] : nullptr;
+  }
+  __syncthreads();
+  const long n = job.n;
+  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
+  return AdamWork{job.p, job.m, job.v, s_e, s_g, begin, end};
+}
+
+// The update of one block's <= AD_ITEMS elements: the ONE body of every adam_kernel<NG, SCALED, EMA> (SCALED: the
+// gradient times `coef`, rounded once, on the way in; EMA: one more stream `e`, read and written beside p).
+// Whether p / g / m / v take the 16-byte path does not depend on `e`: a misaligned average
 // is read and written element by element inside it.  (The pointers carry no __restrict__: as function arguments
 // it would be honoured, unlike on the locals the kernels had before this body was shared, and the scalar loops of
 // the existing kernels would be interleaved and fused differently -- other bits.)
@@ -120,25 +153,31 @@ __device__ __forceinline__ void adam_block(float* p, const float* g, float* m, f
   }
 }
 
-template <int NG>
+// lic_adam_run (neither), lic_adam_run_scaled (SCALED) and lic_adam_run_ema (EMA, with or without SCALED).
+// SCALED: the gradient is scaled by clip_state[1] (layout below, at grad_norm_finish_kernel) on the way in, and
+// nothing is done at all when the caller asked for non-finite steps to be skipped and clip_state[2] says this one is.
+// EMA: the exponential moving average of every parameter is updated from the new p while it is in registers.  The
+// averages are persistent buffers: their addresses live in a device table `ema` (one per job, NULL = no average for
+// that tensor) and do not travel per step.  36 bytes per element instead of 28: e is read and written once.
+// (The seven scalars travel as seven arguments: with an AdamScalars passed by value hipcc contracts a multiply and
+// an add of the scalar loops into a multiply-add in every instantiation -- other bits.)
+template <int NG, bool SCALED, bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(const lic_adam_job* jobs, int njobs, const AdamGrads<NG> grads,
                                                    float lerp_w, float beta2, float one_minus_beta2, float eps,
-                                                   float weight_decay, float step_size, float bc2_sqrt) {
-  __shared__ lic_adam_job job;
-  __shared__ int s_blk;
-  __shared__ const float* s_g;
-  if (threadIdx.x == 0) {
-    const int lo = adam_job_of_block(jobs, njobs);
-    job = jobs[lo];
-    s_blk = blockIdx.x - jobs[lo].block0;
-    s_g = grads.g[lo];
+                                                   float weight_decay, float step_size, float bc2_sqrt,
+                                                   const float* __restrict__ clip_state, int skip_nonfinite,
+                                                   float* const* __restrict__ ema, float ema_w) {
+  const AdamScalars k{lerp_w, beta2, one_minus_beta2, eps, weight_decay, step_size, bc2_sqrt};
+  float coef = 1.0f;
+  if (SCALED) {
+    if (skip_nonfinite && reinterpret_cast<const unsigned*>(clip_state)[2] != 0u) return;  // (uniform over the grid)
+    coef = clip_state[1];
   }
-  __syncthreads();
-  const long n = job.n;
-  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
-  adam_block<false, false>(job.p, s_g, job.m, job.v, nullptr, begin, end,
-                           AdamScalars{lerp_w, beta2, one_minus_beta2, eps, weight_decay, step_size, bc2_sqrt}, 1.0f, 0.0f);
+  const AdamWork w = adam_work_of_block<true, EMA>(jobs, njobs, grads.g, ema);
+  if (EMA && w.e) adam_block<SCALED, true>(w.p, w.g, w.m, w.v, w.e, w.begin, w.end, k, coef, ema_w);
+  else adam_block<SCALED, false>(w.p, w.g, w.m, w.v, nullptr, w.begin, w.end, k, coef, 0.0f);
 }
+
 // lic_grad_norm_partial / lic_grad_norm_finish / lic_adam_run_scaled: the global-norm clipping of the usual recipe
 // for these models (torch.nn.utils.clip_grad_norm_ before optimizer.step(): a handful of foreach launches that
 // read every gradient twice and write it once, and ~240 small host-side calls) as one more read of the gradients
@@ -156,20 +195,10 @@ __device__ __forceinline__ double block_sum_d(double acc, double* s_wave) {
 template <int NG>
 __global__ __launch_bounds__(256) void grad_norm_partial_kernel(const lic_adam_job* jobs, int njobs,
                                                                 const AdamGrads<NG> grads, double* partials) {
-  __shared__ long s_n;
-  __shared__ int s_blk;
-  __shared__ const float* s_g;
   __shared__ double s_wave[4];
-  if (threadIdx.x == 0) {
-    const int lo = adam_job_of_block(jobs, njobs);
-    s_n = jobs[lo].n;
-    s_blk = blockIdx.x - jobs[lo].block0;
-    s_g = grads.g[lo];
-  }
-  __syncthreads();
-  const float* __restrict__ g = s_g;
-  const long n = s_n;
-  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
+  const AdamWork w = adam_work_of_block<true, false>(jobs, njobs, grads.g, nullptr);
+  const float* __restrict__ g = w.g;
+  const long begin = w.begin, end = w.end;
   double acc = 0.0;
   auto add = [&](float gw) { acc += (double)gw * (double)gw; };  // (the product of two floats is exact in double)
   if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
@@ -210,85 +239,13 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
   }
 }
 
-// adam_kernel with the gradient scaled by clip_state[1] on the way in, and nothing done at all when the caller
-// asked for non-finite steps to be skipped and clip_state[2] says this one is
-template <int NG>
-__global__ __launch_bounds__(256) void adam_scaled_kernel(const lic_adam_job* jobs, int njobs, const AdamGrads<NG> grads,
-                                                          float lerp_w, float beta2, float one_minus_beta2, float eps,
-                                                          float weight_decay, float step_size, float bc2_sqrt,
-                                                          const float* __restrict__ clip_state, int skip_nonfinite) {
-  if (skip_nonfinite && reinterpret_cast<const unsigned*>(clip_state)[2] != 0u) return;  // (uniform over the grid)
-  const float coef = clip_state[1];
-  __shared__ lic_adam_job job;
-  __shared__ int s_blk;
-  __shared__ const float* s_g;
-  if (threadIdx.x == 0) {
-    const int lo = adam_job_of_block(jobs, njobs);
-    job = jobs[lo];
-    s_blk = blockIdx.x - jobs[lo].block0;
-    s_g = grads.g[lo];
-  }
-  __syncthreads();
-  const long n = job.n;
-  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
-  adam_block<true, false>(job.p, s_g, job.m, job.v, nullptr, begin, end,
-                          AdamScalars{lerp_w, beta2, one_minus_beta2, eps, weight_decay, step_size, bc2_sqrt}, coef, 0.0f);
-}
-
-// lic_adam_run_ema: either of the two kernels above (SCALED: adam_scaled_kernel with its guard, else adam_kernel)
-// with the exponential moving average of every parameter updated from the new p while it is in registers.  The
-// averages are persistent buffers: their addresses live in a device table `ema` (one per job, NULL = no average for
-// that tensor) and do not travel per step.  36 bytes per element instead of 28: e is read and written once.
-template <int NG, bool SCALED>
-__global__ __launch_bounds__(256) void adam_ema_kernel(const lic_adam_job* jobs, int njobs, const AdamGrads<NG> grads,
-                                                       float lerp_w, float beta2, float one_minus_beta2, float eps,
-                                                       float weight_decay, float step_size, float bc2_sqrt,
-                                                       const float* __restrict__ clip_state, int skip_nonfinite,
-                                                       float* const* __restrict__ ema, float ema_w) {
-  float coef = 1.0f;
-  if (SCALED) {
-    if (skip_nonfinite && reinterpret_cast<const unsigned*>(clip_state)[2] != 0u) return;  // (uniform over the grid)
-    coef = clip_state[1];
-  }
-  __shared__ lic_adam_job job;
-  __shared__ int s_blk;
-  __shared__ const float* s_g;
-  __shared__ float* s_e;
-  if (threadIdx.x == 0) {
-    const int lo = adam_job_of_block(jobs, njobs);
-    job = jobs[lo];
-    s_blk = blockIdx.x - jobs[lo].block0;
-    s_g = grads.g[lo];
-    s_e = ema[lo];
-  }
-  __syncthreads();
-  const long n = job.n;
-  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
-  const AdamScalars k{lerp_w, beta2, one_minus_beta2, eps, weight_decay, step_size, bc2_sqrt};
-  float* e = s_e;
-  if (e) adam_block<SCALED, true>(job.p, s_g, job.m, job.v, e, begin, end, k, coef, ema_w);
-  else adam_block<SCALED, false>(job.p, s_g, job.m, job.v, nullptr, begin, end, k, coef, 0.0f);
-}
-
 // lic_swap_run: p <-> e for every job that has an average, on the lic_adam_plan partition; loads and stores only
 __global__ __launch_bounds__(256) void swap_kernel(const lic_adam_job* jobs, int njobs, float* const* __restrict__ ema) {
-  __shared__ float* s_p;
-  __shared__ float* s_e;
-  __shared__ long s_n;
-  __shared__ int s_blk;
-  if (threadIdx.x == 0) {
-    const int lo = adam_job_of_block(jobs, njobs);
-    s_p = jobs[lo].p;
-    s_e = ema[lo];
-    s_n = jobs[lo].n;
-    s_blk = blockIdx.x - jobs[lo].block0;
-  }
-  __syncthreads();
-  float* __restrict__ p = s_p;
-  float* __restrict__ e = s_e;
+  const AdamWork w = adam_work_of_block<false, true>(jobs, njobs, nullptr, ema);
+  float* __restrict__ p = w.p;
+  float* __restrict__ e = w.e;
   if (!e) return;  // (uniform over the block)
-  const long n = s_n;
-  const long begin = (long)s_blk * AD_ITEMS, end = begin + AD_ITEMS < n ? begin + AD_ITEMS : n;
+  const long begin = w.begin, end = w.end;
   auto one = [&](long i) {
     const float t = p[i];
     p[i] = e[i];
@@ -322,43 +279,79 @@ LIC_EXPORT int64_t lic_adam_plan(lic_adam_job* jobs, int32_t njobs) {
   return blocks;
 }
 
+namespace {
+// the kernel-argument block of one launch: njobs gradient addresses (HOST array of DEVICE pointers), the rest null
 template <int NG>
-static void adam_launch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads, float lerp_w,
-                        float beta2, float one_minus_beta2, float eps, float wd, float step_size, float bc2_sqrt,
-                        hipStream_t s) {
+AdamGrads<NG> adam_grads(const float* const* grads, int njobs) {
   AdamGrads<NG> a;
   for (int i = 0; i < NG; ++i) a.g[i] = i < njobs ? grads[i] : nullptr;
-  hipLaunchKernelGGL((adam_kernel<NG>), dim3((unsigned)blocks), dim3(256), 0, s, jobs_device, njobs, a, lerp_w, beta2,
-                     one_minus_beta2, eps, wd, step_size, bc2_sqrt);
+  return a;
 }
 
-// grads_host: njobs gradient pointers (HOST array of DEVICE pointers), in job order; njobs <= 448
-// (scalars are doubles: torch derives 1 - beta, lr / bias_correction1 and sqrt(bias_correction2) in Python doubles
-// and rounds once to fp32; 1.0f - 0.999f is 1.7e-5 away from float(0.001))
-LIC_EXPORT int lic_adam_run(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
-                            const float* const* grads_host, double lr, double beta1, double beta2, double eps,
-                            double weight_decay, double bias_correction1, double bias_correction2, lic_stream_t stream) {
-  if (!jobs_device || !grads_host || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL) return LIC_ERR_INVALID;
-  if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) return LIC_ERR_INVALID;
+// f(std::integral_constant<int, NG>) for the smallest argument block that holds njobs (<= 448) addresses
+template <class F>
+void with_grads_tier(int njobs, F&& f) {
+  if (njobs <= 96) f(std::integral_constant<int, 96>{});
+  else if (njobs <= 224) f(std::integral_constant<int, 224>{});
+  else f(std::integral_constant<int, 448>{});
+}
+
+// What the entries refuse.  Where two rules apply to one call: every null pointer, size and range of an entry's own
+// arguments is LIC_ERR_INVALID and is looked at before grads_status, whose LIC_ERR_UNSUPPORTED for more than 448
+// jobs in turn comes before a null entry among the gradients.
+bool bad_partition(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks) {
+  return !jobs_device || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL;
+}
+
+bool bad_ema_table(float* const* ema_device) {
+  return !ema_device || (reinterpret_cast<uintptr_t>(ema_device) & (sizeof(float*) - 1)) != 0;
+}
+
+int grads_status(const float* const* grads_host, int32_t njobs) {
   if (njobs > 448) return LIC_ERR_UNSUPPORTED;
   for (int i = 0; i < njobs; ++i)
     if (!grads_host[i]) return LIC_ERR_INVALID;
-  const float lw = (float)(1.0 - beta1), ss = (float)(lr / bias_correction1), bs = (float)sqrt(bias_correction2);
-  const float b2 = (float)beta2, omb2 = (float)(1.0 - beta2), ep = (float)eps, wd = (float)weight_decay;
-  hipStream_t s = (hipStream_t)stream;
-  if (njobs <= 96) adam_launch<96>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, s);
-  else if (njobs <= 224) adam_launch<224>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, s);
-  else adam_launch<448>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, s);
-  return lic_check_launch();
+  return LIC_OK;
 }
 
-template <int NG>
-static void grad_norm_partial_launch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads,
-                                     double* partials, hipStream_t s) {
-  AdamGrads<NG> a;
-  for (int i = 0; i < NG; ++i) a.g[i] = i < njobs ? grads[i] : nullptr;
-  hipLaunchKernelGGL((grad_norm_partial_kernel<NG>), dim3((unsigned)blocks), dim3(256), 0, s, jobs_device, njobs, a,
-                     partials);
+// The one launch path of lic_adam_run, lic_adam_run_scaled and lic_adam_run_ema: clip_state and ema_device may each
+// be NULL, and pick the kernel.  grads_host: njobs gradient pointers, in job order; njobs <= 448.
+// (scalars are doubles: torch derives 1 - beta, lr / bias_correction1 and sqrt(bias_correction2) in Python doubles
+// and rounds once to fp32; 1.0f - 0.999f is 1.7e-5 away from float(0.001))
+int adam_run(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks, const float* const* grads_host,
+             double lr, double beta1, double beta2, double eps, double weight_decay, double bias_correction1,
+             double bias_correction2, float* const* ema_device, double ema_weight, const float* clip_state,
+             int32_t skip_nonfinite, lic_stream_t stream) {
+  if (bad_partition(jobs_device, njobs, total_blocks) || !grads_host) return LIC_ERR_INVALID;
+  if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) return LIC_ERR_INVALID;
+  if (const int status = grads_status(grads_host, njobs)) return status;
+  const AdamScalars k{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay,
+                      (float)(lr / bias_correction1), (float)sqrt(bias_correction2)};
+  const float w = (float)ema_weight;
+  const int skip = clip_state && skip_nonfinite ? 1 : 0;
+  with_grads_tier(njobs, [&](auto tier) {
+    constexpr int NG = decltype(tier)::value;
+    const AdamGrads<NG> a = adam_grads<NG>(grads_host, njobs);
+    auto launch = [&](auto scaled, auto ema) {
+      hipLaunchKernelGGL((adam_kernel<NG, decltype(scaled)::value, decltype(ema)::value>), dim3((unsigned)total_blocks),
+                         dim3(256), 0, (hipStream_t)stream, jobs_device, (int)njobs, a, k.lerp_w, k.beta2,
+                         k.one_minus_beta2, k.eps, k.weight_decay, k.step_size, k.bc2_sqrt, clip_state, skip, ema_device,
+                         w);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (clip_state) ema_device ? launch(yes, yes) : launch(yes, no);
+    else ema_device ? launch(no, yes) : launch(no, no);
+  });
+  return lic_check_launch();
+}
+}  // namespace
+
+LIC_EXPORT int lic_adam_run(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
+                            const float* const* grads_host, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, double bias_correction1, double bias_correction2, lic_stream_t stream) {
+  return adam_run(jobs_device, njobs, total_blocks, grads_host, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                  bias_correction2, nullptr, 0.0, nullptr, 0, stream);
 }
 
 // the first half of torch.nn.utils.clip_grad_norm_ (torch._foreach_norm over every gradient): block b of the
@@ -366,15 +359,13 @@ static void grad_norm_partial_launch(const lic_adam_job* jobs_device, int njobs,
 // Same job table, same grads_host as lic_adam_run; partials: total_blocks doubles (DEVICE)
 LIC_EXPORT int lic_grad_norm_partial(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
                                      const float* const* grads_host, double* partials, lic_stream_t stream) {
-  if (!jobs_device || !grads_host || !partials || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL)
-    return LIC_ERR_INVALID;
-  if (njobs > 448) return LIC_ERR_UNSUPPORTED;
-  for (int i = 0; i < njobs; ++i)
-    if (!grads_host[i]) return LIC_ERR_INVALID;
-  hipStream_t s = (hipStream_t)stream;
-  if (njobs <= 96) grad_norm_partial_launch<96>(jobs_device, njobs, total_blocks, grads_host, partials, s);
-  else if (njobs <= 224) grad_norm_partial_launch<224>(jobs_device, njobs, total_blocks, grads_host, partials, s);
-  else grad_norm_partial_launch<448>(jobs_device, njobs, total_blocks, grads_host, partials, s);
+  if (bad_partition(jobs_device, njobs, total_blocks) || !grads_host || !partials) return LIC_ERR_INVALID;
+  if (const int status = grads_status(grads_host, njobs)) return status;
+  with_grads_tier(njobs, [&](auto tier) {
+    constexpr int NG = decltype(tier)::value;
+    hipLaunchKernelGGL((grad_norm_partial_kernel<NG>), dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       jobs_device, (int)njobs, adam_grads<NG>(grads_host, njobs), partials);
+  });
   return lic_check_launch();
 }
 
@@ -390,16 +381,6 @@ LIC_EXPORT int lic_grad_norm_finish(const double* partials, int64_t nparts, doub
   return lic_check_launch();
 }
 
-template <int NG>
-static void adam_scaled_launch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads,
-                               float lerp_w, float beta2, float one_minus_beta2, float eps, float wd, float step_size,
-                               float bc2_sqrt, const float* clip_state, int skip, hipStream_t s) {
-  AdamGrads<NG> a;
-  for (int i = 0; i < NG; ++i) a.g[i] = i < njobs ? grads[i] : nullptr;
-  hipLaunchKernelGGL((adam_scaled_kernel<NG>), dim3((unsigned)blocks), dim3(256), 0, s, jobs_device, njobs, a, lerp_w,
-                     beta2, one_minus_beta2, eps, wd, step_size, bc2_sqrt, clip_state, skip);
-}
-
 // lic_adam_run on gradients scaled by clip_state[1] (the `g.mul_(clip_coef_clamped)` of clip_grad_norm_, rounded to
 // fp32 once as there, without the pass over memory); skip_nonfinite: leave p / m / v alone when clip_state[2] is set.
 // clip_state is read on the device: the host does not wait for the norm
@@ -407,43 +388,9 @@ LIC_EXPORT int lic_adam_run_scaled(const lic_adam_job* jobs_device, int32_t njob
                                    const float* const* grads_host, double lr, double beta1, double beta2, double eps,
                                    double weight_decay, double bias_correction1, double bias_correction2,
                                    const float* clip_state, int32_t skip_nonfinite, lic_stream_t stream) {
-  if (!jobs_device || !grads_host || !clip_state || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL)
-    return LIC_ERR_INVALID;
-  if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) return LIC_ERR_INVALID;
-  if (njobs > 448) return LIC_ERR_UNSUPPORTED;
-  for (int i = 0; i < njobs; ++i)
-    if (!grads_host[i]) return LIC_ERR_INVALID;
-  const float lw = (float)(1.0 - beta1), ss = (float)(lr / bias_correction1), bs = (float)sqrt(bias_correction2);
-  const float b2 = (float)beta2, omb2 = (float)(1.0 - beta2), ep = (float)eps, wd = (float)weight_decay;
-  const int sk = skip_nonfinite ? 1 : 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (njobs <= 96)
-    adam_scaled_launch<96>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, clip_state, sk, s);
-  else if (njobs <= 224)
-    adam_scaled_launch<224>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, clip_state, sk, s);
-  else
-    adam_scaled_launch<448>(jobs_device, njobs, total_blocks, grads_host, lw, b2, omb2, ep, wd, ss, bs, clip_state, sk, s);
-  return lic_check_launch();
-}
-
-template <int NG, bool SCALED>
-static void adam_ema_launch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads,
-                            const AdamScalars& k, float* const* ema, float ema_w, const float* clip_state, int skip,
-                            hipStream_t s) {
-  AdamGrads<NG> a;
-  for (int i = 0; i < NG; ++i) a.g[i] = i < njobs ? grads[i] : nullptr;
-  hipLaunchKernelGGL((adam_ema_kernel<NG, SCALED>), dim3((unsigned)blocks), dim3(256), 0, s, jobs_device, njobs, a,
-                     k.lerp_w, k.beta2, k.one_minus_beta2, k.eps, k.weight_decay, k.step_size, k.bc2_sqrt, clip_state, skip,
-                     ema, ema_w);
-}
-
-template <bool SCALED>
-static void adam_ema_dispatch(const lic_adam_job* jobs_device, int njobs, long blocks, const float* const* grads,
-                              const AdamScalars& k, float* const* ema, float ema_w, const float* clip_state, int skip,
-                              hipStream_t s) {
-  if (njobs <= 96) adam_ema_launch<96, SCALED>(jobs_device, njobs, blocks, grads, k, ema, ema_w, clip_state, skip, s);
-  else if (njobs <= 224) adam_ema_launch<224, SCALED>(jobs_device, njobs, blocks, grads, k, ema, ema_w, clip_state, skip, s);
-  else adam_ema_launch<448, SCALED>(jobs_device, njobs, blocks, grads, k, ema, ema_w, clip_state, skip, s);
+  if (!clip_state) return LIC_ERR_INVALID;
+  return adam_run(jobs_device, njobs, total_blocks, grads_host, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                  bias_correction2, nullptr, 0.0, clip_state, skip_nonfinite, stream);
 }
 
 // lic_adam_run (clip_state NULL) or lic_adam_run_scaled (clip_state given) that also moves the exponential moving
@@ -454,31 +401,17 @@ LIC_EXPORT int lic_adam_run_ema(const lic_adam_job* jobs_device, int32_t njobs, 
                                 double weight_decay, double bias_correction1, double bias_correction2,
                                 float* const* ema_device, double ema_weight, const float* clip_state,
                                 int32_t skip_nonfinite, lic_stream_t stream) {
-  if (!jobs_device || !grads_host || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL) return LIC_ERR_INVALID;
-  if (!ema_device || (reinterpret_cast<uintptr_t>(ema_device) & (sizeof(float*) - 1)) != 0) return LIC_ERR_INVALID;
+  if (bad_ema_table(ema_device)) return LIC_ERR_INVALID;
   if (!(ema_weight >= 0.0 && ema_weight <= 1.0)) return LIC_ERR_INVALID;  // (a NaN too)
-  if (!(bias_correction1 > 0.0) || !(bias_correction2 > 0.0)) return LIC_ERR_INVALID;
-  if (njobs > 448) return LIC_ERR_UNSUPPORTED;
-  for (int i = 0; i < njobs; ++i)
-    if (!grads_host[i]) return LIC_ERR_INVALID;
-  const AdamScalars k{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay,
-                      (float)(lr / bias_correction1), (float)sqrt(bias_correction2)};
-  const float w = (float)ema_weight;
-  hipStream_t s = (hipStream_t)stream;
-  if (clip_state)
-    adam_ema_dispatch<true>(jobs_device, njobs, total_blocks, grads_host, k, ema_device, w, clip_state,
-                            skip_nonfinite ? 1 : 0, s);
-  else
-    adam_ema_dispatch<false>(jobs_device, njobs, total_blocks, grads_host, k, ema_device, w, nullptr, 0, s);
-  return lic_check_launch();
+  return adam_run(jobs_device, njobs, total_blocks, grads_host, lr, beta1, beta2, eps, weight_decay, bias_correction1,
+                  bias_correction2, ema_device, ema_weight, clip_state, skip_nonfinite, stream);
 }
 
 // p <-> e, element by element, for every job whose ema_device entry is not NULL: the averaged weights become the
 // live ones (and back).  The job table and partition of lic_adam_run; m / v / g are not touched
 LIC_EXPORT int lic_swap_run(const lic_adam_job* jobs_device, int32_t njobs, int64_t total_blocks,
                             float* const* ema_device, lic_stream_t stream) {
-  if (!jobs_device || njobs <= 0 || total_blocks <= 0 || total_blocks > 0x7FFFFFFFL) return LIC_ERR_INVALID;
-  if (!ema_device || (reinterpret_cast<uintptr_t>(ema_device) & (sizeof(float*) - 1)) != 0) return LIC_ERR_INVALID;
+  if (bad_partition(jobs_device, njobs, total_blocks) || bad_ema_table(ema_device)) return LIC_ERR_INVALID;
   if (njobs > 448) return LIC_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(swap_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, jobs_device,
                      njobs, ema_device);

@@ -36,11 +36,77 @@ import collections
 import contextlib
 import ctypes as C
 import struct
+from typing import NamedTuple
 
 import torch
 
 from . import _lib as L
 from . import functional as F_
+
+
+class JobTable(NamedTuple):
+    """one lic_adam_plan partition on the device, and what it was built for"""
+    key: object         # the addresses and lengths the table holds: built again when they differ
+    dev: torch.Tensor   # the lic_adam_job array; behind it the averages' addresses, where the table has any
+    njobs: int
+    blocks: int
+    gptrs: object       # ctypes array of njobs gradient addresses, filled per launch (None: no gradients travel)
+
+    def ema_ptr(self):
+        """the device table of the averages' addresses (lic_adam_run_ema, lic_swap_run: 8-byte aligned)"""
+        return self.dev.data_ptr() + self.njobs * C.sizeof(L.AdamJob)
+
+
+def _upload_jobs(jobs, dev, emas=()):
+    """(p, m, v, n) address tuples -> (their lic_adam_job array, partitioned by lic_adam_plan, on `dev`; its block
+    count).  `emas`: one address per job, uploaded behind the array in the same copy (JobTable.ema_ptr)"""
+    arr = (L.AdamJob * len(jobs))()
+    for j, job in zip(arr, jobs):
+        j.p, j.m, j.v, j.n = job
+    blocks = L.load().lic_adam_plan(arr, len(jobs))
+    if blocks <= 0:
+        raise L.LicError(f"lic_adam_plan failed: {blocks}")
+    raw = bytearray(bytes(arr) + struct.pack(f"{len(emas)}q", *emas))
+    return torch.frombuffer(raw, dtype=torch.uint8).to(dev), int(blocks)
+
+
+def _launch_norm(lib, tabs, partials, max_norm, count_skip, state):
+    """lic_grad_norm_partial over the gradients each table's `gptrs` point at, one lic_grad_norm_finish over all"""
+    stream, at = F_._stream(), 0
+    for tab in tabs:
+        L.check(lib.lic_grad_norm_partial(C.c_void_p(tab.dev.data_ptr()), tab.njobs, tab.blocks, tab.gptrs,
+                                          C.c_void_p(partials.data_ptr() + 8 * at), stream), "lic_grad_norm_partial")
+        at += tab.blocks
+    L.check(lib.lic_grad_norm_finish(C.c_void_p(partials.data_ptr()), at, max_norm, count_skip,
+                                     C.c_void_p(state.data_ptr()), stream), "lic_grad_norm_finish")
+
+
+def clip_gradients(parameters, max_norm, skip_nonfinite):
+    """torch's clipping, where the kernels do not do it: torch.nn.utils.clip_grad_norm_ over the parameters that have
+    a gradient (max_norm None: the norm alone).  Returns (norm, skip): skip says that skip_nonfinite is on and the
+    norm is not finite -- reading that back is the one synchronisation, made only when skip_nonfinite is on."""
+    params = [p for p in parameters if p.grad is not None]
+    if max_norm is not None:
+        norm = torch.nn.utils.clip_grad_norm_(params, float(max_norm))
+    else:
+        norm = torch.nn.utils.get_total_norm([p.grad for p in params])
+    return norm, bool(skip_nonfinite) and not bool(torch.isfinite(norm))
+
+
+def _hyper(group):
+    """what a cached plan was made for besides the tensors: a change of any of these plans the step again"""
+    return (group["lr"], group["betas"], group["eps"], group["weight_decay"], group["amsgrad"], group.get("maximize"),
+            group.get("capturable"), group.get("differentiable"))
+
+
+class _GroupPlan:
+    """one parameter group's part of a planned step"""
+    __slots__ = ("group", "plist", "params", "hyper", "table", "bumped", "steps", "ema")
+
+    def __init__(self, group, params, table, bumped, steps, ema):
+        self.group, self.plist, self.params, self.hyper = group, group["params"], params, _hyper(group)
+        self.table, self.bumped, self.steps = table, bumped, steps   # bumped: the tensors a launch writes
+        self.ema = ema      # address of the device table of averages, None without
 
 
 class FusedAdam(torch.optim.Adam):
@@ -59,14 +125,13 @@ class FusedAdam(torch.optim.Adam):
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
         self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
         self.swapped = False      # True while the averages are the live weights (swap_ema)
-        self._swap_tabs = {}      # group index -> (key, device job table, njobs, blocks, device table of averages)
+        self._swap_tabs = {}      # group index -> JobTable of swap_ema() (with the averages' addresses, no gradients)
         self._clip_state = None   # 4 dwords on the device: norm, coefficient, not-finite flag, skipped steps (lic.h)
         self._partials = None     # one double per block of every group (lic_grad_norm_partial), allocated per plan
         self._last_norm = None    # what grad_norm() returns
         self._skipped_host = 0    # steps skipped on the fallback path
-        self._tables = {}   # group index -> (key, device job table, njobs, blocks, ctypes array of gradient pointers)
-        self._ema_tabs = {}  # group index -> device array of the averages' addresses, built with (and for) _tables[gi]
-        self._fast = None   # the last planned step, re-used while nothing it depends on changed
+        self._tables = {}   # group index -> JobTable of step(), kept while its key holds
+        self._fast = None   # the last planned step (a _GroupPlan per group), re-used while nothing it depends on changed
         self._t0, self._lazy = 0.0, 0   # step count the plan started from / fast steps not yet written to the state
         self.fused_steps = 0
 
@@ -87,45 +152,33 @@ class FusedAdam(torch.optim.Adam):
 
     def _clip_prologue(self, lib, tabs):
         """the norm of the gradients `tabs` (one job table per group) point at -> self._clip_state, no read-back"""
-        dev = tabs[0][1].device
-        total = sum(t[3] for t in tabs)
+        dev = tabs[0].dev.device
+        total = sum(t.blocks for t in tabs)
         if self._clip_state is None or self._clip_state.device != dev:
             self._skipped_host = self.skipped_steps()
             self._clip_state = torch.zeros(4, dtype=torch.float32, device=dev)
         if self._partials is None or self._partials.numel() != total or self._partials.device != dev:
             self._partials = torch.empty(total, dtype=torch.float64, device=dev)
-        stream, at = F_._stream(), 0
-        for _, dev_tab, njobs, blocks, gptrs in tabs:
-            L.check(lib.lic_grad_norm_partial(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs,
-                                              C.c_void_p(self._partials.data_ptr() + 8 * at), stream),
-                    "lic_grad_norm_partial")
-            at += blocks
         max_norm = float("inf") if self.max_grad_norm is None else float(self.max_grad_norm)
-        L.check(lib.lic_grad_norm_finish(C.c_void_p(self._partials.data_ptr()), total, max_norm,
-                                         int(self.skip_nonfinite), C.c_void_p(self._clip_state.data_ptr()), stream),
-                "lic_grad_norm_finish")
+        _launch_norm(lib, tabs, self._partials, max_norm, int(self.skip_nonfinite), self._clip_state)
         self._last_norm = self._clip_state[0]
 
-    def _launch(self, lib, group, tab, t, clip, etab=None):
-        _, dev_tab, njobs, blocks, gptrs = tab
+    def _launch(self, lib, plan, t, clip):
+        """the update of one group at the 1-based step count t: lic_adam_run, or the entry that adds what is on"""
+        group, tab = plan.group, plan.table
         beta1, beta2 = group["betas"]
-        if etab is not None:
-            state = C.c_void_p(self._clip_state.data_ptr()) if clip else None
-            L.check(lib.lic_adam_run_ema(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]),
-                                         float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                                         1.0 - beta1 ** t, 1.0 - beta2 ** t, C.c_void_p(etab.data_ptr()),
-                                         self._ema_weight(t), state, int(self.skip_nonfinite), F_._stream()),
-                    "lic_adam_run_ema")
-        elif not clip:
-            L.check(lib.lic_adam_run(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]),
-                                     float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                                     1.0 - beta1 ** t, 1.0 - beta2 ** t, F_._stream()), "lic_adam_run")
+        args = [C.c_void_p(tab.dev.data_ptr()), tab.njobs, tab.blocks, tab.gptrs, float(group["lr"]), float(beta1),
+                float(beta2), float(group["eps"]), float(group["weight_decay"]), 1.0 - beta1 ** t, 1.0 - beta2 ** t]
+        state = C.c_void_p(self._clip_state.data_ptr()) if clip else None
+        if plan.ema is not None:
+            name = "lic_adam_run_ema"
+            args += [C.c_void_p(plan.ema), self._ema_weight(t), state, int(self.skip_nonfinite)]
+        elif clip:
+            name = "lic_adam_run_scaled"
+            args += [state, int(self.skip_nonfinite)]
         else:
-            L.check(lib.lic_adam_run_scaled(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs, float(group["lr"]),
-                                            float(beta1), float(beta2), float(group["eps"]),
-                                            float(group["weight_decay"]), 1.0 - beta1 ** t, 1.0 - beta2 ** t,
-                                            C.c_void_p(self._clip_state.data_ptr()), int(self.skip_nonfinite),
-                                            F_._stream()), "lic_adam_run_scaled")
+            name = "lic_adam_run"
+        L.check(getattr(lib, name)(*args, F_._stream()), name)
 
     def _ema_weight(self, t):
         """w of e += w * (p - e) at the 1-based step count t, in double (lic.h: lic_adam_run_ema rounds it once)"""
@@ -175,107 +228,99 @@ class FusedAdam(torch.optim.Adam):
         # torch's `_init_group` and re-deriving the job-table key cost 0.5 ms of a 4.4 ms step): once a step has
         # been planned, the next one only checks that the groups' parameter lists and hyper-parameters are the very
         # objects / values it planned for and that every gradient is there, then gathers the gradient addresses.
-        fast = self._fast
-        if fast is not None and len(fast) == len(self.param_groups):
-            ok = True
-            for (group, plist, params, hyper, (tab, _, _, _)), g in zip(fast, self.param_groups):
-                if g is not group or g["params"] is not plist or len(plist) != len(params) or \
-                        (g["lr"], g["betas"], g["eps"], g["weight_decay"], g["amsgrad"], g.get("maximize"),
-                         g.get("capturable"), g.get("differentiable")) != hyper:
-                    ok = False
-                    break
-                for p, k in zip(params, tab[0]):
-                    gr = p.grad
-                    if gr is None or gr.dtype != torch.float32 or not gr.is_contiguous() or p.data_ptr() != k[0]:
-                        ok = False   # (a missing gradient, or parameter storage that moved: plan again)
-                        break
-                if not ok:
-                    break
-            if ok:
-                lib = L.load()
-                clip = self._clipping()
-                for group, plist, params, hyper, (tab, moments, steps, etab) in fast:
-                    gptrs = tab[4]
-                    for i, p in enumerate(params):
-                        gptrs[i] = p.grad.data_ptr()
-                if clip:    # (the norm is global: every group's partial sums before the first update)
-                    self._clip_prologue(lib, [f[4][0] for f in fast])
-                t = self._t0 + self._lazy + 1.0
-                for group, plist, params, hyper, (tab, moments, steps, etab) in fast:
-                    self._launch(lib, group, tab, t, clip, etab)
-                    torch.autograd.graph.increment_version(moments)
-                # the per-parameter `step` tensors of the state (CPU scalars, one per parameter: bumping them is ~240
-                # small ATen calls per step) are brought up to date lazily: _flush_steps() before anything reads them
-                self._lazy += 1
-                self.fused_steps += 1
-                return loss
+        plans = self._fast
+        if plans is not None and self._plan_holds(plans):
+            self._run(plans, self._t0 + self._lazy + 1.0)
+            # the per-parameter `step` tensors of the state (CPU scalars, one per parameter: bumping them is ~240
+            # small ATen calls per step) are brought up to date lazily: _flush_steps() before anything reads them
+            self._lazy += 1
+        else:
+            plans = self._plan()
+            if plans is None:
+                return self._fallback(loss)
+            self._run(plans, None)
+            # (the job tables hold the parameter / moment addresses: valid while these very tensors are the state.
+            # _plan() took whole groups only and made the tables' keys from these tensors a moment ago, so what is
+            # left to ask before the plan is kept is that all groups share one step count)
+            if len({float(pl.steps[0]) for pl in plans}) == 1:
+                self._fast = plans
+                self._t0, self._lazy = float(plans[0].steps[0]), 0
+        self.fused_steps += 1
+        return loss
+
+    def _plan_holds(self, plans):
+        """is every group what `plans` was made for, and every gradient there"""
+        if len(plans) != len(self.param_groups):
+            return False
+        for plan, g in zip(plans, self.param_groups):
+            if g is not plan.group or g["params"] is not plan.plist or len(plan.plist) != len(plan.params) or \
+                    _hyper(g) != plan.hyper:
+                return False
+            for p, k in zip(plan.params, plan.table.key):
+                gr = p.grad
+                if gr is None or gr.dtype != torch.float32 or not gr.is_contiguous() or p.data_ptr() != k[0]:
+                    return False   # (a missing gradient, or parameter storage that moved: plan again)
+        return True
+
+    def _plan(self):
+        """a _GroupPlan per group from the state as it is now, the job tables built or re-used; None when any group
+        has to take torch's path.  Whatever was cached is flushed and dropped first."""
         self._flush_steps()
         self._fast = None
-        plans = []
-        for gi, group in enumerate(self.param_groups):
+        found = []
+        for group in self.param_groups:
             params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps = [], [], [], [], [], []
             self._init_group(group, params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps)
             emas = self._ema_buffers(params) if self.ema_decay is not None else None
             if len(params) != len([p for p in group["params"]]) or not self._eligible(group, params, grads) or \
                     not all(m.is_contiguous() and v.is_contiguous() for m, v in zip(exp_avgs, exp_avg_sqs)) or \
                     len({float(s) for s in steps}) != 1:
-                return self._fallback(loss)
+                return None
             if emas is not None and not all(e.is_contiguous() and e.dtype == torch.float32 and e.device == p.device
                                             for p, e in zip(params, emas)):
-                return self._fallback(loss)
-            plans.append((gi, group, params, grads, exp_avgs, exp_avg_sqs, steps, emas))
-        lib = L.load()
-        clip = self._clipping()
-        tabs = []
-        for gi, group, params, grads, exp_avgs, exp_avg_sqs, steps, emas in plans:
+                return None
+            found.append((group, params, exp_avgs, exp_avg_sqs, steps, emas))
+        plans = []
+        for gi, (group, params, exp_avgs, exp_avg_sqs, steps, emas) in enumerate(found):
             key = tuple((p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) for p, m, v in zip(params, exp_avgs, exp_avg_sqs))
             if emas is not None:    # (the averages' addresses are part of what the plan was made for)
                 key = tuple(k + (e.data_ptr(),) for k, e in zip(key, emas))
             tab = self._tables.get(gi)
-            if tab is None or tab[0] != key:
-                arr = (L.AdamJob * len(params))()
-                for j, (p, m, v) in zip(arr, zip(params, exp_avgs, exp_avg_sqs)):
-                    j.p, j.m, j.v, j.n = p.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-                blocks = lib.lic_adam_plan(arr, len(params))
-                if blocks <= 0:
-                    raise L.LicError(f"lic_adam_plan failed: {blocks}")
-                dev_tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(params[0].device)
-                tab = self._tables[gi] = (key, dev_tab, len(params), int(blocks), (C.c_void_p * len(params))())
-                self._ema_tabs[gi] = None if emas is None else \
-                    torch.tensor([e.data_ptr() for e in emas], dtype=torch.int64).to(params[0].device)
-            gptrs = tab[4]
-            for i, g in enumerate(grads):       # gradients are fresh tensors every step: their addresses go along
-                gptrs[i] = g.data_ptr()         # as kernel arguments (copied at launch)
-            tabs.append(tab)
-        if clip:
-            self._clip_prologue(lib, tabs)
-        fast = []
-        for (gi, group, params, grads, exp_avgs, exp_avg_sqs, steps, emas), tab in zip(plans, tabs):
-            etab = self._ema_tabs.get(gi) if emas is not None else None
-            self._launch(lib, group, tab, float(steps[0]) + 1.0, clip, etab)
-            for s in steps:     # (only once the launch went out: a refused launch leaves the state untouched)
-                s += 1
-            # the kernel wrote through raw pointers: tell autograd (and prep.StepPrep, which re-derives the packed
-            # weights when a parameter's version moves) that the parameters and moments changed
-            moments = params + exp_avgs + exp_avg_sqs + (emas or [])
-            torch.autograd.graph.increment_version(moments)
-            hyper = (group["lr"], group["betas"], group["eps"], group["weight_decay"], group["amsgrad"],
-                     group.get("maximize"), group.get("capturable"), group.get("differentiable"))
-            # (the job table holds the parameter / moment addresses: valid while these very tensors are the state)
-            if all(p.data_ptr() == k[0] for p, k in zip(params, tab[0])) and len(params) == len(group["params"]):
-                fast.append((group, group["params"], list(params), hyper, (tab, moments, list(steps), etab)))
-        if len(fast) == len(self.param_groups) and len({float(f[4][2][0]) for f in fast}) == 1:
-            self._fast = fast
-            self._t0, self._lazy = float(fast[0][4][2][0]), 0
-        self.fused_steps += 1
-        return loss
+            if tab is None or tab.key != key:
+                dev_tab, blocks = _upload_jobs([k[:4] for k in key], params[0].device,
+                                               () if emas is None else [k[4] for k in key])
+                tab = self._tables[gi] = JobTable(key, dev_tab, len(params), blocks, (C.c_void_p * len(params))())
+            # the kernel writes through raw pointers: autograd (and prep.StepPrep, which re-derives the packed
+            # weights when a parameter's version moves) is told that the parameters and moments changed
+            written = params + exp_avgs + exp_avg_sqs + (emas or [])
+            ema = None if emas is None else tab.ema_ptr()
+            plans.append(_GroupPlan(group, list(params), tab, written, list(steps), ema))
+        return plans
+
+    def _run(self, plans, t):
+        """the launches of one step.  t: the 1-based step count all groups share (the cached plan), or None: each
+        group's own, from its `step` tensors, which are then incremented behind its launch"""
+        lib = L.load()
+        clip = self._clipping()
+        for plan in plans:
+            gptrs = plan.table.gptrs
+            for i, p in enumerate(plan.params):    # gradients are fresh tensors every step: their addresses go along
+                gptrs[i] = p.grad.data_ptr()       # as kernel arguments (copied at launch)
+        if clip:    # (the norm is global: every group's partial sums before the first update)
+            self._clip_prologue(lib, [plan.table for plan in plans])
+        for plan in plans:
+            self._launch(lib, plan, float(plan.steps[0]) + 1.0 if t is None else t, clip)
+            if t is None:
+                for s in plan.steps:     # (only once the launch went out: a refused launch leaves the state untouched)
+                    s += 1
+            torch.autograd.graph.increment_version(plan.bumped)
 
     def _flush_steps(self):
         """apply the step counts the fast path has not yet written into the state's `step` tensors"""
         n, fast = getattr(self, "_lazy", 0), self._fast
         if n and fast is not None:
-            for _, _, _, _, (_, _, steps, _) in fast:
-                for s in steps:
+            for plan in fast:
+                for s in plan.steps:
                     s += n
             self._t0 += n
         self._lazy = 0
@@ -287,8 +332,8 @@ class FusedAdam(torch.optim.Adam):
     def zero_grad(self, set_to_none: bool = True):
         # (torch's zero_grad walks every group through a profiler scope and foreach bookkeeping: 0.1 ms for 59 tensors)
         if set_to_none and self._fast is not None:
-            for _, _, params, _, _ in self._fast:
-                for p in params:
+            for plan in self._fast:
+                for p in plan.params:
                     p.grad = None
             return
         return super().zero_grad(set_to_none)
@@ -296,7 +341,7 @@ class FusedAdam(torch.optim.Adam):
     def load_state_dict(self, state_dict):
         self._flush_steps()
         self._fast = None          # (new state tensors: plan again)
-        self._tables, self._ema_tabs, self._swap_tabs = {}, {}, {}
+        self._tables, self._swap_tabs = {}, {}
         return super().load_state_dict(state_dict)
 
     def add_param_group(self, param_group):
@@ -310,13 +355,9 @@ class FusedAdam(torch.optim.Adam):
         self._flush_steps()
         self._fast = None
         if self._clipping():
-            params = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
-            if self.max_grad_norm is not None:
-                norm = torch.nn.utils.clip_grad_norm_(params, float(self.max_grad_norm))
-            else:
-                norm = torch.nn.utils.get_total_norm([p.grad for p in params])
-            self._last_norm = norm
-            if self.skip_nonfinite and not bool(torch.isfinite(norm)):   # (the one synchronisation of this path)
+            self._last_norm, skip = clip_gradients([p for group in self.param_groups for p in group["params"]],
+                                                   self.max_grad_norm, self.skip_nonfinite)
+            if skip:
                 self._skipped_host += 1
                 return loss    # (the averages stay as they are, like everything else)
         if self.ema_decay is None:
@@ -371,20 +412,13 @@ class FusedAdam(torch.optim.Adam):
                 lib = L.load()
                 key = tuple((p.data_ptr(), e.data_ptr(), p.numel()) for p, e in pairs)
                 tab = self._swap_tabs.get(gi)
-                if tab is None or tab[0] != key:
-                    arr = (L.AdamJob * len(pairs))()
-                    for j, (p, e) in zip(arr, pairs):   # (only p and n are read: lic_adam_plan wants m / v non-null)
-                        j.p = j.m = j.v = p.data_ptr()
-                        j.n = p.numel()
-                    blocks = lib.lic_adam_plan(arr, len(pairs))
-                    if blocks <= 0:
-                        raise L.LicError(f"lic_adam_plan failed: {blocks}")
-                    dev = pairs[0][0].device
-                    tab = self._swap_tabs[gi] = (
-                        key, torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), len(pairs), int(blocks),
-                        torch.tensor([e.data_ptr() for _, e in pairs], dtype=torch.int64).to(dev))
-                L.check(lib.lic_swap_run(C.c_void_p(tab[1].data_ptr()), tab[2], tab[3], C.c_void_p(tab[4].data_ptr()),
-                                         F_._stream()), "lic_swap_run")
+                if tab is None or tab.key != key:
+                    # (only p and n are read: lic_adam_plan wants m / v non-null)
+                    dev_tab, blocks = _upload_jobs([(p, p, p, n) for p, _, n in key], pairs[0][0].device,
+                                                   [e for _, e, _ in key])
+                    tab = self._swap_tabs[gi] = JobTable(key, dev_tab, len(pairs), blocks, None)
+                L.check(lib.lic_swap_run(C.c_void_p(tab.dev.data_ptr()), tab.njobs, tab.blocks,
+                                         C.c_void_p(tab.ema_ptr()), F_._stream()), "lic_swap_run")
                 for p, e in pairs:      # (written through raw pointers: tell autograd and everything keyed on versions)
                     written += [p, e]
             else:
@@ -446,27 +480,18 @@ def grad_norm(parameters):
     if tabs is None:
         tabs = []
         for at in range(0, len(grads), FusedAdam.MAX_TENSORS):    # (one kernel-argument block per launch)
-            chunk = grads[at:at + FusedAdam.MAX_TENSORS]
-            arr = (L.AdamJob * len(chunk))()
-            for j, g in zip(arr, chunk):     # only the lengths are read: lic_adam_plan wants the pointers non-null
-                j.p = j.m = j.v = g.data_ptr()
-                j.n = g.numel()
-            blocks = lib.lic_adam_plan(arr, len(chunk))
-            if blocks <= 0:
-                raise L.LicError(f"lic_adam_plan failed: {blocks}")
-            tabs.append((torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev), len(chunk), int(blocks)))
+            # only the lengths are read: lic_adam_plan wants the pointers non-null
+            jobs = [(g.data_ptr(),) * 3 + (g.numel(),) for g in grads[at:at + FusedAdam.MAX_TENSORS]]
+            dev_tab, blocks = _upload_jobs(jobs, dev)
+            tabs.append(JobTable(key, dev_tab, len(jobs), blocks, None))
         if len(_norm_tables) >= 8:
             _norm_tables.clear()
         _norm_tables[key] = tabs
-    total = sum(t[2] for t in tabs)
-    partials = torch.empty(total, dtype=torch.float64, device=dev)
+    partials = torch.empty(sum(t.blocks for t in tabs), dtype=torch.float64, device=dev)
     state = torch.zeros(4, dtype=torch.float32, device=dev)
-    stream, at, g0 = F_._stream(), 0, 0
-    for dev_tab, njobs, blocks in tabs:
-        gptrs = (C.c_void_p * njobs)(*[g.data_ptr() for g in grads[g0:g0 + njobs]])
-        L.check(lib.lic_grad_norm_partial(C.c_void_p(dev_tab.data_ptr()), njobs, blocks, gptrs,
-                                          C.c_void_p(partials.data_ptr() + 8 * at), stream), "lic_grad_norm_partial")
-        at, g0 = at + blocks, g0 + njobs
-    L.check(lib.lic_grad_norm_finish(C.c_void_p(partials.data_ptr()), total, float("inf"), 0,
-                                     C.c_void_p(state.data_ptr()), stream), "lic_grad_norm_finish")
+    launches, at = [], 0
+    for tab in tabs:
+        launches.append(tab._replace(gptrs=(C.c_void_p * tab.njobs)(*[g.data_ptr() for g in grads[at:at + tab.njobs]])))
+        at += tab.njobs
+    _launch_norm(lib, launches, partials, float("inf"), 0, state)
     return state[0]

@@ -31,6 +31,7 @@ import torch
 import torch.distributed as dist
 from torch.optim.lr_scheduler import CosineAnnealingLR, ReduceLROnPlateau
 
+from .optim import FusedAdam, clip_gradients
 from .parallel import GradientAllReducer, all_reduce_mean_scalars, broadcast_parameters
 
 
@@ -122,7 +123,6 @@ class Trainer:
         # no extra pass over the gradients); any other optimizer gets torch's clip_grad_norm_ in front of its step.
         # Either way after the reducer, so every rank clips the same averaged gradient; the optimizer step is outside
         # the step plan, so step_plan=True needs nothing of its own.
-        from .optim import FusedAdam
         self.clip_max_norm, self.skip_nonfinite = clip_max_norm, bool(skip_nonfinite)
         self._clip = clip_max_norm is not None or self.skip_nonfinite
         self._fused_clip = self._clip and isinstance(optimizer, FusedAdam)
@@ -165,12 +165,9 @@ class Trainer:
     # -- the step (Trainer.py:78-86) -------------------------------------------------------------
     def _optimizer_step(self):
         if self._clip and not self._fused_clip:
-            params = [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]
-            if self.clip_max_norm is not None:
-                self._grad_norm = torch.nn.utils.clip_grad_norm_(params, float(self.clip_max_norm))
-            else:
-                self._grad_norm = torch.nn.utils.get_total_norm([p.grad for p in params])
-            if self.skip_nonfinite and not bool(torch.isfinite(self._grad_norm)):   # (one synchronisation)
+            self._grad_norm, skip = clip_gradients([p for g in self.optimizer.param_groups for p in g["params"]],
+                                                   self.clip_max_norm, self.skip_nonfinite)
+            if skip:
                 self._skipped += 1
                 return
         self.optimizer.step()
