@@ -1241,12 +1241,34 @@ int lic_stem_conv_bf16(const float* x, const void* w_packed, const float* bias, 
  *   optimizer outside).
  *   Errors: LIC_ERR_UNSUPPORTED for a node kind that cannot be replayed (host, event, child-graph, allocation nodes;
  *   1-D copy nodes, whose parameters this ROCm does not hand back); lic_plan_last_error() names it.
+ *   Read-back (so that a test can hold a schedule to HIP's ordering rules edge by edge, tests/plan_sched_ref.py):
+ *   lic_plan_dag: sizes[0..1] = operations n, edges; with buffers of cap_ops (+1 for pred_ptr) and cap_edges entries
+ *     the operations in capture order: the predecessors of k are pred_idx[pred_ptr[k] .. pred_ptr[k+1]) (all < k),
+ *     kind[k] = 0 kernel, 1 memset, 2 memcpy, 3 empty, flags[k] = 1 (wide: >= 192 workgroups) | 2 (filler: the batched
+ *     reduction, which capture order sends to the last stream), us[k] = the time lic_plan_tune measured (0 before).
+ *   lic_plan_commands: the HIP calls lic_plan_replay makes for the schedule in use when given `n_sides` (0..2) side
+ *     streams that differ from `main` and from each other, in order, as *n_cmds triples (kind, stream, argument):
+ *     kind 0 = hipStreamWaitEvent, 1 = the launch of an operation, 2 = hipEventRecord; stream 0 = main, i = sides[i-1];
+ *     argument = the operation for a launch, else an event id (0 the fork, 1 and 2 the joins, 3.. the schedule's
+ *     cross-stream events).  `cmds` holds 3 * cap values.
+ *   lic_plan_sched_host: the same list for a caller's DAG (n_ops operations in topological order, CSR predecessors,
+ *     us, flags as above): mode 0 = lic_plan_create's capture-order schedule, mode 1 = lic_plan_tune's list scheduler
+ *     on `ns` (1..3) streams with `wide_min_us` its bound for "long".  info (optional) [0..1] = operations not on main,
+ *     cross-stream events, as lic_plan_info would report them.  Makes no HIP call: works without a GPU.
+ *   All three always write the sizes; with every buffer null and every capacity 0 that is all they do (LIC_OK).  A
+ *   null buffer otherwise is LIC_ERR_INVALID, one too small LIC_ERR_WORKSPACE.
  * ------------------------------------------------------------------------------------------ */
 typedef struct lic_plan lic_plan;
 int lic_plan_create(void* hip_graph, lic_plan** out);
 int lic_plan_info(const lic_plan* plan, int64_t* info);
 int lic_plan_replay(lic_plan* plan, lic_stream_t main, const lic_stream_t* sides, int32_t n_sides);
 int lic_plan_tune(lic_plan* plan, lic_stream_t main, const lic_stream_t* sides, int32_t n_sides, double* result);
+int lic_plan_dag(const lic_plan* plan, int64_t cap_ops, int64_t cap_edges, int64_t* sizes, int32_t* pred_ptr,
+                 int32_t* pred_idx, int32_t* kind, int32_t* flags, double* us);
+int lic_plan_commands(lic_plan* plan, int32_t n_sides, int64_t cap, int64_t* n_cmds, int32_t* cmds);
+int lic_plan_sched_host(int64_t n_ops, const int32_t* pred_ptr, const int32_t* pred_idx, const double* us,
+                        const int32_t* flags, int32_t mode, int32_t ns, double wide_min_us, int32_t n_sides,
+                        int64_t cap, int64_t* n_cmds, int32_t* cmds, int64_t* info);
 void lic_plan_destroy(lic_plan* plan);
 const char* lic_plan_last_error(void);
 

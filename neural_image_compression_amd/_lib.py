@@ -248,6 +248,10 @@ SIGNATURES = {
     "lic_plan_info": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "lic_plan_replay": (C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32]),
     "lic_plan_tune": (C.c_int, [_vp, _vp, C.POINTER(C.c_void_p), _i32, C.POINTER(C.c_double)]),
+    "lic_plan_dag": (C.c_int, [_vp, _i64, _i64, C.POINTER(C.c_int64), _vp, _vp, _vp, _vp, _vp]),
+    "lic_plan_commands": (C.c_int, [_vp, _i32, _i64, C.POINTER(C.c_int64), _vp]),
+    "lic_plan_sched_host": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i32, _i32, C.c_double, _i32, _i64,
+                                      C.POINTER(C.c_int64), _vp, _vp]),
     "lic_plan_destroy": (None, [_vp]),
     "lic_plan_last_error": (C.c_char_p, []),
     "lic_version": (C.c_int, []),

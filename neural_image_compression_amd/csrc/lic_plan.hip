@@ -23,7 +23,11 @@
 // Either way every edge of the capture is honoured (same-stream order or an event), so results are those of the
 // eager step bit for bit.  Nothing here knows the model: any capture of kernel, memset, memcpy and empty nodes on
 // one device works.
+// The schedulers and the builder of the command list a replay walks are host code without HIP: lic_plan_sched.h.  This
+// file reads the graph, issues the commands and measures; lic_plan_dag / lic_plan_commands / lic_plan_sched_host hand DAG
+// and commands out as data, so that tests/plan_sched_ref.py can check "every edge is honoured" without a race to lose.
 #include "lic_common.h"
+#include "lic_plan_sched.h"
 #include <cstring>
 
 #include <stdio.h>
@@ -43,64 +47,21 @@ struct PlanOp {
   hipKernelNodeParams kp;  // (the argument storage belongs to the graph: the caller keeps the graph alive)
   hipMemsetParams ms;
   hipMemcpy3DParms mc;
-  std::vector<int> preds, succs;  // indices into lic_plan::ops (capture order: preds < own index)
-  double us = 0.0;                // measured duration (lic_plan_tune)
-  bool wide = false;              // fills the chip: does not overlap with another wide operation
 };
 
-constexpr int NS = 3;  // streams a schedule may use: the caller's and up to two more
-
-struct Slot {
-  int op;
-  int stream;
-  int record = -1;         // event recorded right after this operation (a successor on the other stream waits for it)
-  std::vector<int> waits;  // events the operation's stream waits for first
-};
-
-struct Schedule {
-  std::vector<Slot> slots;  // issue order
-  int n_events = 0;
-  int on_side = 0;
-};
-
-// events for every cross-stream edge that earlier waits do not cover
-void add_events(const std::vector<PlanOp>& ops, Schedule& sc) {
-  const size_t n = sc.slots.size();
-  std::vector<int> slot_of(n, -1), pos(n, -1);
-  int len[NS] = {0, 0, 0};
-  int waited[NS][NS];  // waited[s][o]: position on stream o that stream s has already waited for
-  for (auto& row : waited)
-    for (int& w : row) w = -1;
-  sc.n_events = 0;
-  sc.on_side = 0;
-  for (size_t k = 0; k < n; ++k) {
-    Slot& sl = sc.slots[k];
-    sl.record = -1;
-    sl.waits.clear();
-    slot_of[sl.op] = (int)k;
-  }
-  for (size_t k = 0; k < n; ++k) {
-    Slot& sl = sc.slots[k];
-    const int s = sl.stream;
-    for (int q : ops[sl.op].preds) {
-      Slot& pq = sc.slots[slot_of[q]];
-      if (pq.stream == s || pos[slot_of[q]] <= waited[s][pq.stream]) continue;
-      if (pq.record < 0) pq.record = sc.n_events++;
-      sl.waits.push_back(pq.record);
-      waited[s][pq.stream] = pos[slot_of[q]];
-    }
-    pos[k] = len[s]++;
-    if (s != 0) ++sc.on_side;
-  }
-}
+// the schedules themselves are plain host code over the DAG: lic_plan_sched.h
+using lic_sched::Cmd;
+using lic_sched::Node;
+using lic_sched::NS;
+using lic_sched::Schedule;
 
 }  // namespace
 
 struct lic_plan {
   std::vector<PlanOp> ops;  // topological (capture) order
+  std::vector<Node> dag;    // the same operations as the schedulers see them
   Schedule sched;
-  std::vector<hipEvent_t> events;
-  hipEvent_t fork = nullptr, join[NS - 1] = {nullptr, nullptr};
+  std::vector<hipEvent_t> events;  // by the event ids of a command list: the fork, the two joins, the schedule's own
   int64_t count[4] = {0, 0, 0, 0};  // kernels, memsets, memcpys, empty
   int tuned = 0;
 };
@@ -113,8 +74,9 @@ static int plan_fail(lic_plan* p, int rc, const std::string& why) {
   return rc;
 }
 
+// events for a schedule with `n` events of its own (and the fork and the joins)
 static bool ensure_events(lic_plan* p, int n) {
-  while ((int)p->events.size() < n) {
+  while ((int)p->events.size() < lic_sched::EV_FIRST + n) {
     hipEvent_t ev;
     if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return false;
     p->events.push_back(ev);
@@ -164,17 +126,20 @@ LIC_EXPORT int lic_plan_create(void* hip_graph, lic_plan** out) {
 
   lic_plan* p = new lic_plan();
   p->ops.resize(n);
+  p->dag.resize(n);
   for (size_t k = 0; k < n; ++k) {
     const int u = order[k];
     PlanOp& op = p->ops[k];
-    for (int q : preds[u]) op.preds.push_back(rank[q]);
-    for (int q : succs[u]) op.succs.push_back(rank[q]);
+    Node& nd = p->dag[k];
+    for (int q : preds[u]) nd.preds.push_back(rank[q]);
+    for (int q : succs[u]) nd.succs.push_back(rank[q]);
     if (hipGraphNodeGetType(nodes[u], &op.type) != hipSuccess) return plan_fail(p, LIC_ERR_INVALID, "hipGraphNodeGetType failed");
     switch (op.type) {
       case hipGraphNodeTypeKernel:
         if (hipGraphKernelNodeGetParams(nodes[u], &op.kp) != hipSuccess) return plan_fail(p, LIC_ERR_INVALID, "hipGraphKernelNodeGetParams failed");
         if (!op.kp.func || (!op.kp.kernelParams && !op.kp.extra)) return plan_fail(p, LIC_ERR_UNSUPPORTED, "a kernel node without a function or arguments");
-        op.wide = (long)op.kp.gridDim.x * op.kp.gridDim.y * op.kp.gridDim.z >= 192;
+        nd.wide = (long)op.kp.gridDim.x * op.kp.gridDim.y * op.kp.gridDim.z >= 192;
+        if (const char* nm = hipKernelNameRefByPtr(op.kp.func, nullptr)) nd.filler = strstr(nm, "reduce_batch_kernel") != nullptr;
         ++p->count[0];
         break;
       case hipGraphNodeTypeMemset:
@@ -202,53 +167,9 @@ LIC_EXPORT int lic_plan_create(void* hip_graph, lic_plan** out) {
         return plan_fail(p, LIC_ERR_UNSUPPORTED, "node type " + std::to_string((int)op.type) + " (only kernel, memset, memcpy and empty nodes are replayed)");
     }
   }
-  // capture-order schedule.  The capture's streams are chains of the graph (consecutive launches of a stream depend on
-  // each other); where a chain forks, the successor with the longest way to go continues the stream and the others
-  // start (or resume) another one: a stream that was never used, else the one that has been quiet longest.
-  p->sched.slots.resize(n);
-  std::vector<int> stream(n, 0), depth(n, 1);
-  for (size_t k = n; k-- > 0;)
-    for (int v : p->ops[k].succs) depth[k] = std::max(depth[k], depth[v] + 1);
-  int tail[NS] = {-1, -1, -1};
-  for (size_t k = 0; k < n; ++k) {
-    int s = -1;
-    for (int q : p->ops[k].preds) {
-      if (tail[stream[q]] != q) continue;
-      bool continues = true;   // k continues q's stream unless a sibling has the longer way to go
-      for (int v : p->ops[q].succs)
-        if (v != (int)k && (depth[v] > depth[k] || (depth[v] == depth[k] && v < (int)k))) continues = false;
-      if (continues && (s < 0 || stream[q] < s)) s = stream[q];
-    }
-    if (s < 0) {
-      if (p->ops[k].preds.empty()) {
-        s = 0;
-      } else {
-        int latest = -1;
-        for (int q : p->ops[k].preds) latest = std::max(latest, q);
-        const int avoid = stream[latest];
-        int pick = -1;
-        for (int c = 0; c < NS; ++c)
-          if (c != avoid && (pick < 0 || tail[c] < tail[pick])) pick = c;   // (-1 = never used sorts first)
-        // the batched reduction forked off beside a chain (functional.flush_point) is a filler: it goes to the LAST stream --
-        // the callers give the first extra stream a high priority for the chain it carries, and a high-priority launch
-        // of ~6000 blocks takes the chip from the other chain's small launches (a 4 MB cast measured 69 us beside it)
-        if (avoid != NS - 1 && p->ops[k].type == hipGraphNodeTypeKernel) {
-          const char* nm = hipKernelNameRefByPtr(p->ops[k].kp.func, nullptr);
-          if (nm && strstr(nm, "reduce_batch_kernel")) pick = NS - 1;
-        }
-        s = pick;
-      }
-    }
-    stream[k] = s;
-    tail[s] = (int)k;
-    p->sched.slots[k].op = (int)k;
-    p->sched.slots[k].stream = s;
-  }
-  add_events(p->ops, p->sched);
-  if (!ensure_events(p, p->sched.n_events) || hipEventCreateWithFlags(&p->fork, hipEventDisableTiming) != hipSuccess)
-    return plan_fail(p, LIC_ERR_LAUNCH, "hipEventCreate failed");
-  for (auto& j : p->join)
-    if (hipEventCreateWithFlags(&j, hipEventDisableTiming) != hipSuccess) return plan_fail(p, LIC_ERR_LAUNCH, "hipEventCreate failed");
+  // the capture-order schedule (lic_plan_sched.h)
+  p->sched = lic_sched::capture_order_schedule(p->dag);
+  if (!ensure_events(p, p->sched.n_events)) return plan_fail(p, LIC_ERR_LAUNCH, "hipEventCreate failed");
   *out = p;
   return LIC_OK;
 }
@@ -307,34 +228,31 @@ static int issue_op(const PlanOp& op, hipStream_t s, long k_) {
   return LIC_OK;
 }
 
-static int replay_schedule(lic_plan* p, const Schedule& sc, hipStream_t main, const hipStream_t* sides, int n_sides) {
+static int replay_schedule(lic_plan* p, Schedule& sc, hipStream_t main, const hipStream_t* sides, int n_sides) {
   // streams the caller did not provide fold onto the last one it did (no side stream at all: everything on `main`)
   hipStream_t st[NS];
   st[0] = main;
   for (int i = 1; i < NS; ++i) st[i] = (i <= n_sides && sides && sides[i - 1]) ? sides[i - 1] : st[i - 1];
-  long k_ = -1;
-  bool distinct[NS] = {false, false, false};   // side streams that are really other streams (each once)
+  int phys[NS] = {0, 0, 0};   // the first stream that is the same HIP stream: side streams that are really others fork and join
   for (int i = 1; i < NS; ++i) {
-    distinct[i] = st[i] != st[0];
-    for (int j = 1; j < i; ++j)
-      if (st[j] == st[i]) distinct[i] = false;
+    phys[i] = i;
+    for (int j = i; j-- > 0;)
+      if (st[j] == st[i]) phys[i] = j;
   }
-  if (distinct[1] || distinct[2]) PLAN_TRY(hipEventRecord(p->fork, st[0]));
-  for (int i = 1; i < NS; ++i)
-    if (distinct[i]) PLAN_TRY(hipStreamWaitEvent(st[i], p->fork, 0));
-  for (const Slot& sl : sc.slots) {
-    ++k_;
-    hipStream_t s = st[sl.stream];
-    for (int w : sl.waits) PLAN_TRY(hipStreamWaitEvent(s, p->events[w], 0));   // (same stream after folding: a no-op for the GPU)
-    const int rc = issue_op(p->ops[sl.op], s, sl.op);
-    if (rc != LIC_OK) return rc;
-    if (sl.record >= 0) PLAN_TRY(hipEventRecord(p->events[sl.record], s));
-  }
-  for (int i = 1; i < NS; ++i)
-    if (distinct[i]) {
-      PLAN_TRY(hipEventRecord(p->join[i - 1], st[i]));
-      PLAN_TRY(hipStreamWaitEvent(st[0], p->join[i - 1], 0));
+  long k_ = -1;
+  const hipEvent_t* ev = p->events.data();
+  for (const Cmd& c : lic_sched::commands_of(sc, phys)) {   // (built by the first replay of this folding)
+    hipStream_t s = st[c.stream];
+    if (c.kind == lic_sched::CMD_LAUNCH) {
+      k_ = c.arg;
+      const int rc = issue_op(p->ops[c.arg], s, c.arg);
+      if (rc != LIC_OK) return rc;
+    } else if (c.kind == lic_sched::CMD_WAIT) {
+      PLAN_TRY(hipStreamWaitEvent(s, ev[c.arg], 0));
+    } else {
+      PLAN_TRY(hipEventRecord(ev[c.arg], s));
     }
+  }
   return LIC_OK;
 }
 
@@ -347,7 +265,7 @@ LIC_EXPORT int lic_plan_replay(lic_plan* p, lic_stream_t main, const lic_stream_
 }
 
 // wall time of `reps` back-to-back replays of a schedule, in microseconds per replay (the device is idle before and after)
-static int time_schedule(lic_plan* p, const Schedule& sc, hipStream_t main, const hipStream_t* sides, int n_sides, int reps, double* us) {
+static int time_schedule(lic_plan* p, Schedule& sc, hipStream_t main, const hipStream_t* sides, int n_sides, int reps, double* us) {
   long k_ = -1;
   hipEvent_t e0, e1;
   PLAN_TRY(hipEventCreate(&e0));
@@ -382,7 +300,7 @@ LIC_EXPORT int lic_plan_tune(lic_plan* p, lic_stream_t main_, const lic_stream_t
   // ---- 1. operation times: one stream, an event between operations, best of three passes
   std::vector<hipEvent_t> ev(n + 1);
   for (auto& e : ev) PLAN_TRY(hipEventCreate(&e));
-  for (PlanOp& op : p->ops) op.us = 1e30;
+  for (Node& nd : p->dag) nd.us = 1e30;
   int rc = LIC_OK;
   for (int pass = 0; pass < 3 && rc == LIC_OK; ++pass) {
     PLAN_TRY(hipEventRecord(ev[0], main));
@@ -394,89 +312,23 @@ LIC_EXPORT int lic_plan_tune(lic_plan* p, lic_stream_t main_, const lic_stream_t
     for (size_t k = 0; k < n && rc == LIC_OK; ++k) {
       float ms = 0.f;
       PLAN_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-      p->ops[k].us = std::min(p->ops[k].us, std::max((double)ms * 1e3, 0.5));
+      p->dag[k].us = std::min(p->dag[k].us, std::max((double)ms * 1e3, 0.5));
     }
   }
   for (auto& e : ev) (void)hipEventDestroy(e);
   if (rc != LIC_OK) return rc;
   double total = 0.0;
-  for (const PlanOp& op : p->ops) total += op.us;
+  for (const Node& nd : p->dag) total += nd.us;
   if (const char* dbg = getenv("LIC_PLAN_DEBUG"))
     if (dbg[0] == '2')   // the step as a list of stand-alone operation times (capture order)
       for (size_t k = 0; k < n; ++k) {
         const PlanOp& op = p->ops[k];
         const char* nm = op.type == hipGraphNodeTypeKernel ? hipKernelNameRefByPtr(op.kp.func, main) : "(memset / memcpy / empty)";
-        fprintf(stderr, "[lic_plan] op %3zu %8.1f us  grid %6u  %s\n", k, op.us,
+        fprintf(stderr, "[lic_plan] op %3zu %8.1f us  grid %6u  %s\n", k, p->dag[k].us,
                 op.type == hipGraphNodeTypeKernel ? op.kp.gridDim.x * op.kp.gridDim.y * op.kp.gridDim.z : 0u, nm ? nm : "?");
       }
-  // ---- 2. list scheduling.  Priority = longest path to the end (own time included).  Repeatedly the (ready
-  //         operation, stream) pair that can START earliest is placed (ties: the more critical operation; a
-  //         cross-stream dependency costs SYNC_US, so a chain stays on its stream unless the other one is clearly
-  //         free earlier) -- weight-gradient and reduction launches, which nothing but the optimizer waits for, fill
-  //         whichever stream is idle instead of sitting in the data-gradient chain's queue.  Long kernels of >= 192
-  //         workgroups take turns (two of them side by side gain nothing); candidates differ in what "long" means.
-  const double SYNC_US = 6.0;
-  std::vector<double> up(n, 0.0);
-  for (size_t k = n; k-- > 0;) {
-    double m = 0.0;
-    for (int v : p->ops[k].succs) m = std::max(m, up[v]);
-    up[k] = p->ops[k].us + m;
-  }
-  auto list_schedule = [&](double wide_min_us, double* modelled) {
-    Schedule sc;
-    sc.slots.reserve(n);
-    std::vector<double> finish(n, 0.0);
-    std::vector<int> stream(n, -1), missing(n, 0);
-    std::vector<int> ready;
-    for (size_t k = 0; k < n; ++k) {
-      missing[k] = (int)p->ops[k].preds.size();
-      if (!missing[k]) ready.push_back((int)k);
-    }
-    double avail[NS] = {0.0, 0.0, 0.0}, wide_until = 0.0;
-    while (!ready.empty()) {
-      // earliest possible start over all (ready operation, stream) pairs; among the pairs within 1 us of it the most
-      // critical operation, then the earlier start, then stream 0
-      auto start_of = [&](int k, int s2) {
-        const PlanOp& op = p->ops[k];
-        double start = avail[s2];
-        for (int q : op.preds) start = std::max(start, finish[q] + (stream[q] != s2 ? SYNC_US : 0.0));
-        if (op.wide && op.us >= wide_min_us) start = std::max(start, wide_until);
-        return start;
-      };
-      double min_start = 1e300;
-      for (int k : ready)
-        for (int s2 = 0; s2 < ns; ++s2) min_start = std::min(min_start, start_of(k, s2));
-      int bi = -1, bs = 0;
-      double b_start = 1e300;
-      for (size_t i = 0; i < ready.size(); ++i)
-        for (int s2 = 0; s2 < ns; ++s2) {
-          const double st = start_of(ready[i], s2);
-          if (st > min_start + 1.0) continue;
-          const bool better = bi < 0 || up[ready[i]] > up[ready[bi]] + 1e-9 ||
-                              (ready[i] == ready[bi] && st < b_start - 1e-9);
-          if (better) bi = (int)i, bs = s2, b_start = st;
-        }
-      const int k = ready[bi];
-      const PlanOp& op = p->ops[k];
-      double start = avail[bs];
-      for (int q : op.preds) start = std::max(start, finish[q] + (stream[q] != bs ? SYNC_US : 0.0));
-      if (op.wide && op.us >= wide_min_us) start = std::max(start, wide_until);
-      stream[k] = bs;
-      finish[k] = start + op.us;
-      avail[bs] = finish[k];
-      if (op.wide && op.us >= wide_min_us) wide_until = finish[k];
-      Slot sl;
-      sl.op = k;
-      sl.stream = bs;
-      sc.slots.push_back(sl);
-      ready.erase(ready.begin() + bi);
-      for (int v : op.succs)
-        if (--missing[v] == 0) ready.push_back(v);
-    }
-    add_events(p->ops, sc);
-    *modelled = std::max(avail[0], std::max(avail[1], avail[2]));
-    return sc;
-  };
+  // ---- 2. list scheduling (lic_plan_sched.h): long kernels of >= 192 workgroups take turns; candidates differ in what
+  //         "long" means
   // ---- 3. measure: the capture-order schedule and the candidates, keep the fastest (a tuned one must win by 2 %)
   double t_cap = 0.0, t_tuned = 1e300, modelled_best = 0.0;
   if ((rc = time_schedule(p, p->sched, main, sides, n_sides, 6, &t_cap)) != LIC_OK) return rc;
@@ -484,7 +336,7 @@ LIC_EXPORT int lic_plan_tune(lic_plan* p, lic_stream_t main_, const lic_stream_t
   const double wide_opts[3] = {25.0, 80.0, 1e30};
   for (double wm : wide_opts) {
     double modelled = 0.0, t = 0.0;
-    Schedule cand = list_schedule(wm, &modelled);
+    Schedule cand = lic_sched::list_schedule(p->dag, ns, wm, &modelled);
     if (!ensure_events(p, std::max(cand.n_events, p->sched.n_events))) return LIC_ERR_LAUNCH;
     if ((rc = time_schedule(p, cand, main, sides, n_sides, 6, &t)) != LIC_OK) return rc;
     if (getenv("LIC_PLAN_DEBUG"))
@@ -511,11 +363,87 @@ LIC_EXPORT int lic_plan_tune(lic_plan* p, lic_stream_t main_, const lic_stream_t
 }
 #undef PLAN_TRY
 
+// ---- read-back: what the schedulers were given and what a replay issues, as data (tests/plan_sched_ref.py checks it)
+
+static int put_commands(const std::vector<Cmd>& cmds, int64_t cap, int64_t* n_cmds, int32_t* out) {
+  *n_cmds = (int64_t)cmds.size();
+  if (!out && cap == 0) return LIC_OK;   // (a size query)
+  if (!out) return LIC_ERR_INVALID;
+  if (cap < (int64_t)cmds.size()) return LIC_ERR_WORKSPACE;
+  for (size_t i = 0; i < cmds.size(); ++i) {
+    out[3 * i] = cmds[i].kind;
+    out[3 * i + 1] = cmds[i].stream;
+    out[3 * i + 2] = cmds[i].arg;
+  }
+  return LIC_OK;
+}
+
+LIC_EXPORT int lic_plan_dag(const lic_plan* p, int64_t cap_ops, int64_t cap_edges, int64_t* sizes, int32_t* pred_ptr,
+                            int32_t* pred_idx, int32_t* kind, int32_t* flags, double* us) {
+  if (!p || !sizes || cap_ops < 0 || cap_edges < 0) return LIC_ERR_INVALID;
+  const int64_t n = (int64_t)p->dag.size();
+  int64_t ne = 0;
+  for (const Node& nd : p->dag) ne += (int64_t)nd.preds.size();
+  sizes[0] = n;
+  sizes[1] = ne;
+  if (!pred_ptr && !pred_idx && !kind && !flags && !us && cap_ops == 0 && cap_edges == 0) return LIC_OK;   // (a size query)
+  if (!pred_ptr || (!pred_idx && ne > 0) || !kind || !flags || !us) return LIC_ERR_INVALID;
+  if (cap_ops < n || cap_edges < ne) return LIC_ERR_WORKSPACE;
+  int64_t e = 0;
+  for (int64_t k = 0; k < n; ++k) {
+    const Node& nd = p->dag[k];
+    pred_ptr[k] = (int32_t)e;
+    for (int q : nd.preds) pred_idx[e++] = q;
+    const hipGraphNodeType t = p->ops[k].type;
+    kind[k] = t == hipGraphNodeTypeKernel ? 0 : t == hipGraphNodeTypeMemset ? 1 : t == hipGraphNodeTypeMemcpy ? 2 : 3;
+    flags[k] = (nd.wide ? 1 : 0) | (nd.filler ? 2 : 0);
+    us[k] = nd.us;
+  }
+  pred_ptr[n] = (int32_t)e;
+  return LIC_OK;
+}
+
+LIC_EXPORT int lic_plan_commands(lic_plan* p, int32_t n_sides, int64_t cap, int64_t* n_cmds, int32_t* cmds) {
+  if (!p || !n_cmds || n_sides < 0 || n_sides > NS - 1 || cap < 0) return LIC_ERR_INVALID;
+  int phys[NS];
+  lic_sched::fold_of_sides(n_sides, phys);
+  return put_commands(lic_sched::commands_of(p->sched, phys), cap, n_cmds, cmds);
+}
+
+// the schedulers and the command-list builder on a caller's DAG: no HIP call, runs without a GPU
+LIC_EXPORT int lic_plan_sched_host(int64_t n_ops, const int32_t* pred_ptr, const int32_t* pred_idx, const double* us,
+                                   const int32_t* flags, int32_t mode, int32_t ns, double wide_min_us, int32_t n_sides,
+                                   int64_t cap, int64_t* n_cmds, int32_t* cmds, int64_t* info) {
+  if (n_ops < 1 || n_ops > (1 << 24) || !pred_ptr || !us || !flags || !n_cmds || cap < 0) return LIC_ERR_INVALID;
+  if ((mode != 0 && mode != 1) || (mode == 1 && (ns < 1 || ns > NS)) || n_sides < 0 || n_sides > NS - 1) return LIC_ERR_INVALID;
+  if (pred_ptr[0] != 0) return LIC_ERR_INVALID;
+  std::vector<Node> dag((size_t)n_ops);
+  for (int64_t k = 0; k < n_ops; ++k) {
+    if (pred_ptr[k + 1] < pred_ptr[k] || (pred_ptr[k + 1] > pred_ptr[k] && !pred_idx)) return LIC_ERR_INVALID;
+    if (!(us[k] >= 0.0) || !(us[k] < 1e30)) return LIC_ERR_INVALID;
+    Node& nd = dag[k];
+    for (int32_t e = pred_ptr[k]; e < pred_ptr[k + 1]; ++e) {
+      const int32_t q = pred_idx[e];
+      if (q < 0 || q >= k) return LIC_ERR_INVALID;   // capture order: predecessors first
+      nd.preds.push_back(q);
+      dag[q].succs.push_back((int)k);
+    }
+    nd.us = us[k];
+    nd.wide = (flags[k] & 1) != 0;
+    nd.filler = (flags[k] & 2) != 0;
+  }
+  Schedule sc = mode == 0 ? lic_sched::capture_order_schedule(dag) : lic_sched::list_schedule(dag, ns, wide_min_us, nullptr);
+  if (info) {
+    info[0] = sc.on_side;
+    info[1] = sc.n_events;
+  }
+  int phys[NS];
+  lic_sched::fold_of_sides(n_sides, phys);
+  return put_commands(lic_sched::command_list(sc, phys), cap, n_cmds, cmds);
+}
+
 LIC_EXPORT void lic_plan_destroy(lic_plan* p) {
   if (!p) return;
   for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
-  if (p->fork) (void)hipEventDestroy(p->fork);
-  for (hipEvent_t j : p->join)
-    if (j) (void)hipEventDestroy(j);
   delete p;
 }

@@ -28,7 +28,41 @@ from . import functional as F_
 from .functional import _stream
 
 
-class StepPlan:
+def _read_dag(lib, plan):
+    sizes = (C.c_int64 * 2)()
+    L.check(lib.lic_plan_dag(plan, 0, 0, sizes, None, None, None, None, None), "lic_plan_dag")
+    n, ne = sizes[0], sizes[1]
+    ptr, idx = (C.c_int32 * (n + 1))(), (C.c_int32 * max(ne, 1))()
+    kind, flags, us = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_double * n)()
+    L.check(lib.lic_plan_dag(plan, n, ne, sizes, ptr, idx, kind, flags, us), "lic_plan_dag")
+    return {"preds": [list(idx[ptr[k]:ptr[k + 1]]) for k in range(n)],
+            "kind": [("kernel", "memset", "memcpy", "empty")[k] for k in kind],
+            "wide": [bool(f & 1) for f in flags], "filler": [bool(f & 2) for f in flags], "us": list(us)}
+
+
+def _read_commands(lib, plan, n_sides):
+    n = C.c_int64(0)
+    L.check(lib.lic_plan_commands(plan, n_sides, 0, C.byref(n), None), "lic_plan_commands")
+    buf = (C.c_int32 * (3 * n.value))()
+    L.check(lib.lic_plan_commands(plan, n_sides, n.value, C.byref(n), buf), "lic_plan_commands")
+    flat = list(buf)
+    return list(zip(flat[0::3], flat[1::3], flat[2::3]))
+
+
+class _ReadBack:
+    """what the plan holds, as data (include/lic.h: lic_plan_dag, lic_plan_commands)"""
+
+    def dag(self):
+        """the captured operations in capture order: {'preds': [[...]], 'kind', 'wide', 'filler', 'us'}, one entry each"""
+        return _read_dag(self._lib, self._plan)
+
+    def commands(self, n_sides: int):
+        """the HIP calls one replay makes with `n_sides` distinct side streams: [(kind, stream, argument)], kind
+        0 = wait for an event, 1 = launch of an operation, 2 = record of an event"""
+        return _read_commands(self._lib, self._plan, n_sides)
+
+
+class StepPlan(_ReadBack):
     def __init__(self, model, loss_fn: Callable, lambda_val: float, example: torch.Tensor, warmup: int = 2,
                  side_stream: Optional[torch.cuda.Stream] = None, tune: bool = False):
         """`loss_fn(model_out, x, lambda_val, sync=False)` -> dict with 'loss' (loss.rd_loss); `example`: a batch
@@ -160,7 +194,7 @@ class StepPlan:
             pass
 
 
-class ForwardPlan:
+class ForwardPlan(_ReadBack):
     """The analysis + hyperprior forward (models.analysis_hyperprior: the scope BASELINE's north star quotes its roofline
     on; also what a serving process runs before the entropy coder) captured once under no_grad and replayed by the
     library -- StepPlan without the backward pass.  `training`: with the quantiser's uniform noise (drawn per call into a
