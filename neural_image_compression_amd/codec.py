@@ -60,8 +60,11 @@ with their own rANS sub-streams, the container (LICBITS6) puts the base layer fi
 `decompress_base_image` decode z and the base layer alone.  `_LayeredCodec` holds what it shares with `ContextCodec`,
 the one-layer case: gather, front end and step loop over a list of layers (`lic_ctx_gather_layers`,
 `lic_rans_decode_step_layers`: all layers of a step in one launch each), the decode of many bitstreams in one loop
-(`_decompress_many`) and the z coder.  The layouts of the ragged calls are pure numpy functions here: `merged_wavefront`,
-`ragged_encode_plan`, `plane_layout`, `z_plan`.
+(`_decompress_many`), the z coder and the y encoders.  The layouts of the ragged calls are pure numpy functions here:
+`merged_wavefront`, `ragged_encode_plan`, `plane_layout`, `z_plan`, and `rans_block_layout` for the slots of every
+encode.  Every device encode (y of one item, y of a chunk, z) builds its inputs and leaves buffers and launches to
+`_RansEncoding` and the one read-back to `rans_read_back` (host half: `rans_streams_of`), as every decode leaves them to
+`_RansStaging`.
 """
 from __future__ import annotations
 
@@ -486,17 +489,30 @@ class RaggedEncodePlan(NamedTuple):
     esc_len: int              # entries of all escape lists
 
 
+def rans_block_layout(fullest, G: int, head: int = 0):
+    """The block table of one encode: the one rule for slots and escape lists.  fullest: per image, the symbols of its
+    fullest sub-stream (`rans_group_sizes(step_len, G).max()`; an image without symbols counts as 1).  Every one of an
+    image's G blocks gets the smallest slot and escape list that cannot run out -- one 16-bit word and one escape per
+    symbol at the most (lic.h): head + 2 * fullest bytes rounded up to 4, and fullest entries --, one behind the other,
+    so every slot starts on a multiple of 4 bytes.  head: 0 for the ragged entries; 4 * RANS_LANES for the single-item
+    kernels, whose slots are `lic_rans_bound`'s and, the images being of one size, uniform.
+    -> (blocks [nimg * G][4] int64, image-major: WORD_OFF (bytes), SLOT (bytes), ESC_OFF, ESC_CAP (entries);
+        words_len: bytes of all slots; esc_len: entries of all escape lists)"""
+    cap = np.repeat(np.maximum(np.asarray(fullest, np.int64).ravel(), 1), _groups(G))
+    slot = (head + 2 * cap + 3) // 4 * 4
+    return np.stack([np.cumsum(slot) - slot, slot, np.cumsum(cap) - cap, cap], 1), int(slot.sum()), int(cap.sum())
+
+
 @functools.lru_cache(maxsize=64)
 def _encode_layout_of(h: int, w: int, M: int, pad: int, slice_rows, G: int, schedule: str = "raster"):
-    """what `ragged_encode_plan` needs of one image shape, kept between calls (a folder has few shapes; the arrays
-    are read only): (raster pixel of every coding position, step lengths, slot bytes, escape entries)"""
+    """what `compress` and `ragged_encode_plan` need of one image shape, kept between calls (a folder has few shapes;
+    the arrays are read only): (raster pixel of every coding position, step lengths, symbols of the fullest sub-stream)"""
     steps = _steps_of(h, w, pad, slice_rows, schedule)
     step_len = np.array([len(ii) * M for ii, _ in steps], np.int64)
-    fullest = max(int(rans_group_sizes(step_len, G).max()), 1)
     order = np.concatenate([ii * w + jj for ii, jj in steps]).astype(np.int64)
     order.setflags(write=False)
     step_len.setflags(write=False)
-    return order, step_len, (2 * fullest + 3) // 4 * 4, fullest
+    return order, step_len, int(rans_group_sizes(step_len, G).max())
 
 
 def ragged_encode_plan(shapes, M: int, pad: int, slice_rows, G: int, schedule: str = "raster") -> RaggedEncodePlan:
@@ -504,44 +520,35 @@ def ragged_encode_plan(shapes, M: int, pad: int, slice_rows, G: int, schedule: s
     "checkerboard": `two_pass(h, w)` where this text says `wavefront`, slice_rows None).  Image b
     owns rows [ROW0, ROW0 + h w) of the tables, centres and symbols, in raster order, and the same range of coding
     positions: position ROW0 + q is pixel `wavefront(h, w, pad, slice_rows)`[concatenated][q], its step lengths are
-    len(rows_t) * M, exactly `compress`'s.  Every block gets the smallest slot and escape list that cannot run out
-    (`rans_group_sizes`): 2 * max_g n_g bytes rounded up to 4, and max_g n_g entries; slots and lists lie one behind
-    the other, so every slot starts on a multiple of 4 bytes."""
+    len(rows_t) * M, exactly `compress`'s.  Slots and escape lists are `rans_block_layout`'s."""
     G = _groups(G)
     shapes = [(int(h), int(w)) for h, w in shapes]
     kinds = {(h, w): _encode_layout_of(h, w, int(M), int(pad), slice_rows, G, _schedule(schedule)) for h, w in set(shapes)}
     nimg = len(shapes)
-    images, blocks = np.zeros((nimg, L.RANS_IMAGE_WORDS), np.int64), np.zeros((nimg * G, L.RANS_BLOCK_WORDS), np.int64)
-    row0 = step0 = word_off = esc_off = 0
+    images = np.zeros((nimg, L.RANS_IMAGE_WORDS), np.int64)
+    row0 = step0 = 0
     for b, (h, w) in enumerate(shapes):
-        order, step_len, slot, cap = kinds[h, w]
+        order, step_len, _ = kinds[h, w]
         images[b] = (row0, order.size, step0, step_len.size)
-        for g in range(G):
-            blocks[b * G + g] = (word_off, slot, esc_off, cap)
-            word_off, esc_off = word_off + slot, esc_off + cap
         row0, step0 = row0 + order.size, step0 + step_len.size
+    blocks, words_len, esc_len = rans_block_layout([kinds[s][2] for s in shapes], G)
     cat = lambda k: (np.concatenate([kinds[s][k] for s in shapes]) if nimg else np.zeros(0, np.int64))
     return RaggedEncodePlan(images, blocks, np.repeat(np.arange(nimg, dtype=np.int64), images[:, 1]), cat(0), cat(1),
-                            row0, word_off, esc_off)
+                            row0, words_len, esc_len)
 
 
 def z_encode_plan(pixels, M: int, G: int):
     """`lic_rans_encode_ragged`'s layout for the hyper-latents of several images (z_coder="rans"): image b is pixels[b]
-    rows of M symbols in raster order and ONE step of pixels[b] * M symbols; slots and escape lists are the smallest
-    that cannot run out (`rans_group_sizes`), one behind the other.
+    rows of M symbols in raster order and ONE step of pixels[b] * M symbols; slots and escape lists are
+    `rans_block_layout`'s.
     -> (images [nimg][4], blocks [nimg * G][4], step_len [nimg], total_rows, words_len, esc_len), as RaggedEncodePlan"""
     G = _groups(G)
-    nimg = len(pixels)
-    images, blocks = np.zeros((nimg, L.RANS_IMAGE_WORDS), np.int64), np.zeros((nimg * G, L.RANS_BLOCK_WORDS), np.int64)
-    row0 = word_off = esc_off = 0
-    for b, P in enumerate(pixels):
-        fullest = max(int(rans_group_sizes([int(P) * M], G).max()), 1)
-        images[b] = (row0, int(P), b, 1)
-        for g in range(G):
-            blocks[b * G + g] = (word_off, (2 * fullest + 3) // 4 * 4, esc_off, fullest)
-            word_off, esc_off = word_off + (2 * fullest + 3) // 4 * 4, esc_off + fullest
-        row0 += int(P)
-    return images, blocks, np.array([int(P) * M for P in pixels], np.int64), row0, word_off, esc_off
+    step_len = np.array([int(P) * M for P in pixels], np.int64)
+    images = np.zeros((len(pixels), L.RANS_IMAGE_WORDS), np.int64)
+    images[:, 1], images[:, 2], images[:, 3] = step_len // M, np.arange(len(pixels)), 1
+    images[:, 0] = np.cumsum(images[:, 1]) - images[:, 1]
+    blocks, words_len, esc_len = rans_block_layout([rans_group_sizes([n], G).max() for n in step_len], G)
+    return images, blocks, step_len, int(images[:, 1].sum()), words_len, esc_len
 
 
 class PlaneLayout(NamedTuple):
@@ -693,6 +700,107 @@ class _RansStaging:
         _state_blocks(self.dev[5], self.G, problem, self.name)                            # the one read-back
 
 
+# what an encoder's error word means, by the coder the message speaks of
+_ENCODER_FAULTS = {
+    "the rANS encoder": "a malformed table, a pixel index outside the image or step lengths that do not add up",
+    "the rANS encoder of z": "a malformed table or step lengths that do not add up"}
+
+
+def rans_streams_of(h_state, h_words, h_esc, blocks, G: int, picked=None, name=_image_name, coder="the rANS encoder"):
+    """The host half of an encode's read-back, pure numpy: what the encoder kernels left -> the bytes, or CodecError.
+    h_state: the encoder's state blocks [nimg * G][RANS_STATE_WORDS] uint32, image-major (`_state_blocks` has the
+    words); blocks: their table (`rans_block_layout`); picked: pick's error words -- None, one for the call, or one
+    per image --, OR-ed into every block of their image.  First every block's error word, then every block's counts
+    against its slot and list: the first block that fails raises, named `name(image)`.  h_words: the word buffer
+    (uint8), a block's words right-aligned in its slot; h_esc: the escape buffer (uint32).  Either may be a function,
+    called once the counts have passed -- h_words(lo) -> the buffer from byte lo, the first used one, on; h_esc(used)
+    -> the entries at the indices `used` --, so `rans_read_back` copies from the device no more than is used.
+    -> ([stream bytes per image and group, image-major], [escape-list bytes likewise, little-endian uint32])"""
+    h_state, nb = np.asarray(h_state).view(np.uint32), blocks.shape[0]
+    pick = np.broadcast_to(np.asarray(0 if picked is None else picked).astype(np.uint32).ravel(), (nb // G,))
+    err = h_state[:nb, RANS_LANES + 2] | np.repeat(pick, G)
+    nw, ne = h_state[:nb, RANS_LANES].astype(np.int64), h_state[:nb, RANS_LANES + 1].astype(np.int64)
+    for i in np.flatnonzero(err)[:1]:
+        raise CodecError(f"{name(i // G)}: {coder} met {_ENCODER_FAULTS[coder]} (error word {err[i]})")
+    for i in np.flatnonzero((2 * nw > blocks[:, 1]) | (ne > blocks[:, 3]))[:1]:
+        raise CodecError(f"{name(i // G)}: {coder} reports impossible counts ({nw[i]} words, {ne[i]} escapes)")
+    end = blocks[:, 0] + blocks[:, 1]
+    lo = int((end - 2 * nw).min())
+    h_words = h_words(lo) if callable(h_words) else h_words[lo:]
+    used = np.concatenate([off + np.arange(n, dtype=np.int64) for off, n in zip(blocks[:, 2], ne)])
+    if used.size:
+        h_esc = np.asarray(h_esc(used) if callable(h_esc) else h_esc[used]).view(np.uint32)
+    e_at = np.cumsum(ne) - ne
+    return ([h_state[i, :RANS_LANES].astype("<u4").tobytes() + h_words[end[i] - 2 * nw[i] - lo:end[i] - lo].tobytes()
+             for i in range(nb)],
+            [h_esc[e_at[i]:e_at[i] + ne[i]].astype("<u4").tobytes() if ne[i] else b"" for i in range(nb)])
+
+
+class _RansEncoding:
+    """The device side of one pick + encode over the nimg * G blocks of a block table (`rans_block_layout`), as
+    `_RansStaging` is of a decode.  kind "single": `lic_rans_encode_pick` + `lic_rans_encode` (`lic_rans_encode_groups`
+    for G > 1) over `images` images of one size; "ragged": `lic_rans_encode_pick_ragged` + `lic_rans_encode_ragged`;
+    "z": `lic_rans_z_pick` + `lic_rans_encode_ragged`.  The constructor allocates what they write -- a start|freq and an
+    escape word per symbol, slots, escape lists, and the zeroed state blocks: the encoder's, then pick's (one per image;
+    one for the whole z pick), so one read-back brings both -- and uploads the int64 arrays of `index` in ONE copy."""
+
+    def __init__(self, dev, kind: str, layout, G: int, nsym: int, images: int, index: Dict):
+        self.kind, self.G, self.images, (self.blocks, self.words_len, self.esc_len) = kind, G, images, layout
+        parts = [np.ascontiguousarray(a, np.int64).ravel() for a in index.values()]     # int64: all 8-byte aligned
+        self.d = dict(zip(index, torch.split(torch.from_numpy(np.concatenate(parts)).to(dev), [a.size for a in parts])))
+        self.sf = torch.empty(nsym, device=dev, dtype=torch.int32)
+        self.exc = torch.empty_like(self.sf)
+        self.words = torch.empty(self.words_len, device=dev, dtype=torch.uint8)
+        self.esc = torch.empty(self.esc_len, device=dev, dtype=torch.int32)
+        self.state = torch.zeros((len(self.blocks) + (1 if kind == "z" else images), L.RANS_STATE_WORDS), device=dev,
+                                 dtype=torch.int32)
+
+    def launch(self, tables, center, syms, M: int, window, rows: int):
+        """The two launches; nothing waits.  tables, center (None for z), syms: what pick reads; window: y_W, or (z_lo,
+        z_S); rows: pixels of one image ("single") or of all.  `index` held "steps", and what the entries index with."""
+        lib, d, G, nimg, st = L.load(), self.d, self.G, self.images, F_._stream()
+        sf, exc, words, esc, state = (F_._ptr(t) for t in (self.sf, self.exc, self.words, self.esc, self.state))
+        picked, steps, nsteps = F_._ptr(self.state[len(self.blocks):]), F_._ptr(d["steps"]), d["steps"].numel()
+        if self.kind == "single":
+            nsym, (_, slot, _, cap) = rows * M, self.blocks[0].tolist()
+            L.check(lib.lic_rans_encode_pick(F_._ptr(tables), F_._ptr(center), F_._ptr(syms), F_._ptr(d["order"]), nimg,
+                                             rows, M, window, sf, exc, picked, st), "lic_rans_encode_pick")
+            if G == 1:
+                return L.check(lib.lic_rans_encode(sf, exc, steps, nsteps, nimg, nsym, words, slot, esc, state, st),
+                               "lic_rans_encode")
+            return L.check(lib.lic_rans_encode_groups(sf, exc, steps, nsteps, nimg, G, nsym, words, slot, esc, cap, state,
+                                                      st), "lic_rans_encode_groups")
+        if self.kind == "z":
+            L.check(lib.lic_rans_z_pick(F_._ptr(tables), M, window[0], window[1], F_._ptr(syms), syms.numel(), sf, exc,
+                                        picked, st), "lic_rans_z_pick")
+        else:
+            L.check(lib.lic_rans_encode_pick_ragged(
+                F_._ptr(tables), F_._ptr(center), F_._ptr(syms), rows, F_._ptr(d["images"]), nimg, F_._ptr(d["row_image"]),
+                F_._ptr(d["order"]), M, window, sf, exc, picked, st), "lic_rans_encode_pick_ragged")
+        L.check(lib.lic_rans_encode_ragged(sf, exc, steps, nsteps, F_._ptr(d["images"]), F_._ptr(d["blocks"]), nimg, G, rows,
+                                           M, words, self.words_len, esc, self.esc_len, state, st), "lic_rans_encode_ragged")
+
+    def read_back(self, name=_image_name):
+        """`rans_read_back` of these buffers -> (streams, escape lists), image-major"""
+        z = self.kind == "z"
+        return rans_read_back(self.state, self.words, self.esc, self.blocks, self.G, 0 if z else RANS_LANES + 2, name,
+                              "the rANS encoder of z" if z else "the rANS encoder")
+
+
+def rans_read_back(state, words, esc, blocks, G: int, pick_word: int, name=_image_name, coder="the rANS encoder"):
+    """The one read-back of an encode, `_RansStaging.check`'s sibling.  state, words, esc: the device buffers the
+    encoder kernels wrote (`_RansEncoding`); state holds the encoder's nimg * G blocks and behind them pick's, whose
+    word `pick_word` is pick's error word (0 of the z pick's one block, RANS_LANES + 2 of the y picks' one per image).
+    The waiting copy of the state blocks, then `rans_streams_of`: pick's words OR-ed in on the host, the refusals, ONE
+    copy of the word buffer from its first used byte on, ONE gather of the used escape entries (none when there is no
+    escape), the cut."""
+    nb = blocks.shape[0]
+    h_state = state.cpu().numpy()                                                 # the read-back that waits
+    return rans_streams_of(h_state[:nb], lambda lo: words[lo:].cpu().numpy(),
+                           lambda used: esc[torch.from_numpy(used).to(esc.device)].cpu().numpy(), blocks, G,
+                           h_state[nb:, pick_word], name, coder)
+
+
 def _z_coder_of(strings) -> str:
     """who coded the hyper-latent of these strings: "range" if they do not say; CodecError for what cannot be"""
     z_coder = strings.get("z_coder", "range")
@@ -723,6 +831,17 @@ def _stage_y_and_z(ys, escs, nimg: int, zs, zescs, nz: int, G: int, name=_image_
                         lambda img: name(img) if img < nimg else zname(img - nimg) + " (hyper-latent)")
 
 
+def _rounded_nhwc(t: torch.Tensor) -> torch.Tensor:
+    """[B,C,h,w] latents -> [B,h,w,C] int32: the symbols, pixel by pixel, channel by channel"""
+    return t.permute(0, 2, 3, 1).contiguous().round().to(torch.int32)
+
+
+def rc_encode_z(zt: np.ndarray, z_idx: np.ndarray) -> bytes:
+    """the range coder's one call for z: symbol k (value - z_lo, `_rounded_nhwc`'s order) uses row k % M of the
+    factorised tables zt [M][z_S+1]"""
+    return rc_encode(zt, z_idx, np.tile(np.arange(len(zt), dtype=np.int32), z_idx.size // len(zt)))
+
+
 class LatentCodec:
     """compress / decompress the (y, z) latents of a JointAutoregressiveHierarchical /
     HierarchicalMixtureResidual model.  `z_lo`, `z_S`: symbol window of the hyper-latent tables;
@@ -738,11 +857,10 @@ class LatentCodec:
         y_in, z_in = out["y_in"], out["z_in"]                      # NCHW-logical, NHWC-physical, integer valued
         B, M, h, w = y_in.shape
         zt, z_idx, z_tab = self._z_symbols(z_in)
-        z_bytes = rc_encode(zt, z_idx, z_tab)
+        z_bytes = rc_encode_z(zt, z_idx)
         act = out["_act"]
         center, yt = gmm_tables(act, M, m.K, self.y_W)
-        y_nhwc = y_in.permute(0, 2, 3, 1).contiguous().round().to(torch.int32)
-        y_idx = (y_nhwc.reshape(-1, M) - center + self.y_W).cpu().numpy().ravel()
+        y_idx = (_rounded_nhwc(y_in).reshape(-1, M) - center + self.y_W).cpu().numpy().ravel()
         yt_h = yt.cpu().numpy().view(np.uint32)
         y_bytes = rc_encode(yt_h, y_idx)
         npix = x.shape[0] * x.shape[2] * x.shape[3]
@@ -762,10 +880,10 @@ class LatentCodec:
     def _z_symbols(self, z_in: torch.Tensor):
         """z_in [B,M,h4,w4] -> `rc_encode`'s arguments: (tables, symbol - z_lo in coding order, table of each symbol)"""
         zt, z_tab = self._z_tables(z_in.numel())
-        return zt, (z_in.permute(0, 2, 3, 1).contiguous().round().to(torch.int32) - self.z_lo).cpu().numpy().ravel(), z_tab
+        return zt, (_rounded_nhwc(z_in) - self.z_lo).cpu().numpy().ravel(), z_tab
 
     def encode_z(self, z_in: torch.Tensor) -> bytes:
-        return rc_encode(*self._z_symbols(z_in))
+        return rc_encode_z(*self._z_symbols(z_in)[:2])
 
     @torch.no_grad()
     def decompress_z(self, z_bytes: bytes, z_shape) -> torch.Tensor:
@@ -908,8 +1026,10 @@ class _LayeredCodec:
     The layouts are module functions: `plane_layout`, `z_plan`, `merged_wavefront`.
 
     Also here, because they do not know how many layers y has: the rANS coder of z (`_z_symbols`, `_encode_z`,
-    `_decode_z`), the device encoder of one layer's y streams (`_encode_y_device`), and what the containers of both
-    codecs share (`_family`, `_shapes`, `_one_window_one_G`)."""
+    `_decode_z`), the two encoders of one layer's y streams (`_encode_y_device`, `_encode_y_host` over `_coding_order`:
+    the same arguments, the same bytes), the optional keys of the strings (`_optional_keys`), and what the containers
+    of both codecs share (`_family`, `_shapes`, `_one_window_one_G`, `_pack_padded`).  The device encoders build their
+    inputs only: buffers and launches are `_RansEncoding`'s, the read-back is `rans_read_back`."""
 
     # False: the layered entries are launched once per layer instead of once per step (tools/bench_codec.py measures
     # what the merged launches save); bytes and results are the same
@@ -1259,6 +1379,12 @@ class _LayeredCodec:
                                  "one call decodes one G")
         return y_W
 
+    def _pack_padded(self, x: torch.Tensor, strings: Dict, align: str) -> bytes:
+        """the codec's container (`_pack_image`) around the strings `compress` gave for x padded to multiples of 64"""
+        B, _, H, W = x.shape
+        _, _, top, left = F_.pad_geometry(H, W, 64, align)
+        return self._pack_image(strings, B, H, W, top, left)
+
     def _family(self) -> int:
         name = type(self.model).__name__
         if name not in BITSTREAM_FAMILIES:
@@ -1270,7 +1396,7 @@ class _LayeredCodec:
     def _z_symbols(z_in: torch.Tensor):
         """z_in [B,M,h4,w4] -> [B][h4*w4*M] int32 on its device: every image's rounded hyper-latents, pixel by pixel,
         channel by channel (`LatentCodec._z_symbols`' order)"""
-        return z_in.permute(0, 2, 3, 1).contiguous().round().to(torch.int32).reshape(z_in.shape[0], -1)
+        return _rounded_nhwc(z_in).reshape(z_in.shape[0], -1)
 
     def _encode_z(self, z_syms, name=_image_name):
         """The hyper-latents as "rANS-64 x G" streams (z_coder="rans").  z_syms: one flat int32 tensor per image
@@ -1282,48 +1408,17 @@ class _LayeredCodec:
         tables = factorized_tables(self.model.factorized_entropy_model, self.z_lo, self.z_S)
         if self.encoder != "device":
             zt = tables.cpu().numpy().view(np.uint32)
-            streams, escs = [], []
-            for z in z_syms:
-                idx = (z.reshape(-1) - self.z_lo).cpu().numpy()
-                for pos, steps_g in rans_deal([idx.size], G):
-                    s, e = rans_encode_shared(zt, idx[pos], steps_g, (pos % M).astype(np.int32))
-                    streams.append(s)
-                    escs.append(e)
-            return streams, escs
-        dev = tables.device
-        nimg = len(z_syms)
+            pairs = [rans_encode_shared(zt, idx[pos], steps_g, (pos % M).astype(np.int32))
+                     for idx in ((z.reshape(-1) - self.z_lo).cpu().numpy() for z in z_syms)
+                     for pos, steps_g in rans_deal([idx.size], G)]
+            return [p[0] for p in pairs], [p[1] for p in pairs]
+        dev, nimg = tables.device, len(z_syms)
         images, blocks, step_len, rows, words_len, esc_len = z_encode_plan([z.numel() // M for z in z_syms], M, G)
         z_all = torch.cat([z.reshape(-1) for z in z_syms]) if nimg > 1 else z_syms[0].reshape(-1).contiguous()
-        n = z_all.numel()
-        parts = [images.ravel(), blocks.ravel(), step_len]
-        d_images, d_blocks, d_steps = torch.split(torch.from_numpy(np.concatenate(parts)).to(dev), [a.size for a in parts])
-        sf = torch.empty(n, device=dev, dtype=torch.int32)
-        exc = torch.empty_like(sf)
-        words = torch.empty(words_len, device=dev, dtype=torch.uint8)
-        esc = torch.empty(esc_len, device=dev, dtype=torch.int32)
-        # the encoder's nimg * G blocks, then one row whose first word is pick's call-level error word
-        state = torch.zeros((nimg * G + 1, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
-        lib = L.load()
-        L.check(lib.lic_rans_z_pick(F_._ptr(tables), M, self.z_lo, self.z_S, F_._ptr(z_all), n, F_._ptr(sf), F_._ptr(exc),
-                                    F_._ptr(state[nimg * G:]), F_._stream()), "lic_rans_z_pick")
-        L.check(lib.lic_rans_encode_ragged(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), nimg, F_._ptr(d_images),
-                                           F_._ptr(d_blocks), nimg, G, rows, M, F_._ptr(words), words_len, F_._ptr(esc),
-                                           esc_len, F_._ptr(state), F_._stream()), "lic_rans_encode_ragged")
-        h_state = state.cpu()                                                     # the read-back that waits
-        picked = int(h_state[nimg * G, 0])
-        found = _state_blocks(h_state[:nimg * G], G, lambda i, states, nw, ne, err: (err or picked) and (
-            f"the rANS encoder of z met a malformed table or step lengths that do not add up (error word {err | picked})"),
-            name)
-        h_words, h_esc = words.cpu().numpy(), esc.cpu().numpy().view(np.uint32)
-        streams, escs = [], []
-        for i, (states, nw, ne) in enumerate(found):
-            if 2 * nw > blocks[i, 1] or ne > blocks[i, 3]:
-                raise CodecError(f"{name(i // G)}: the rANS encoder of z reports impossible counts ({nw} words, "
-                                 f"{ne} escapes)")
-            end = int(blocks[i, 0] + blocks[i, 1])
-            streams.append(states.astype("<u4").tobytes() + h_words[end - 2 * nw:end].tobytes())
-            escs.append(h_esc[blocks[i, 2]:blocks[i, 2] + ne].astype("<u4").tobytes())
-        return streams, escs
+        enc = _RansEncoding(dev, "z", (blocks, words_len, esc_len), G, z_all.numel(), nimg,
+                            dict(images=images, blocks=blocks, steps=step_len))
+        enc.launch(tables, None, z_all, M, (self.z_lo, self.z_S), rows)
+        return enc.read_back(name)
 
     def _decode_z(self, staged, first: int, plan: ZPlan, dev) -> torch.Tensor:
         """The hyper-latents of the images of `plan` (`z_plan`) from their staged "rANS-64 x G" blocks (blocks `first`
@@ -1349,48 +1444,37 @@ class _LayeredCodec:
         """The y streams of the "rans" coder without the host encoder: `lic_rans_encode_pick` turns tables (raster
         order, where `params_at` left them), centres and symbols into one start|freq word and one escape word per
         symbol in wavefront order, `lic_rans_encode` (`lic_rans_encode_groups` for G > 1) codes them, one wave per image
-        and group.  Order and step
-        lengths go up once; the state blocks (final states, word count, escape count, error word) come back once,
-        then exactly the used bytes of every slot and escape list.
+        and group.  Here: the slot rule of these kernels as a block table; buffers, the one upload
+        of order and step lengths and the launches are `_RansEncoding`'s, the read-back is `rans_read_back`.
         -> ([stream bytes per image and group, image-major], [escape-list bytes likewise])"""
-        dev = tables.device
-        nsym, G = P * M, self.groups
-        # one word and one escape per symbol at the most (lic.h): the fullest sub-stream sets both sizes
-        cap = nsym if G == 1 else max(int(rans_group_sizes(step_len, G).max()), 1)
-        slot = (4 * RANS_LANES + 2 * cap + 3) // 4 * 4                          # lic_rans_bound, whole dwords
-        d_order = torch.from_numpy(np.ascontiguousarray(order, np.int64)).to(dev)
-        d_steps = torch.from_numpy(np.asarray(step_len, np.int64)).to(dev)
-        sf = torch.empty((B, nsym), device=dev, dtype=torch.int32)
-        exc = torch.empty_like(sf)
-        esc = torch.empty((B * G, cap), device=dev, dtype=torch.int32)
-        words = torch.empty((B * G, slot), device=dev, dtype=torch.uint8)
-        state = torch.zeros((B * G, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
-        # pick strides its blocks by image: with one block per image it shares the encoder's
-        picked = state if G == 1 else torch.zeros((B, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
-        y_sym = y_sym.contiguous()
-        lib = L.load()
-        L.check(lib.lic_rans_encode_pick(F_._ptr(tables), F_._ptr(center), F_._ptr(y_sym), F_._ptr(d_order), B, P, M,
-                                         self.y_W, F_._ptr(sf), F_._ptr(exc), F_._ptr(picked), F_._stream()),
-                "lic_rans_encode_pick")
-        if G == 1:
-            L.check(lib.lic_rans_encode(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), len(step_len), B, nsym,
-                                        F_._ptr(words), slot, F_._ptr(esc), F_._ptr(state), F_._stream()),
-                    "lic_rans_encode")
-        else:
-            L.check(lib.lic_rans_encode_groups(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), len(step_len), B, G, nsym,
-                                               F_._ptr(words), slot, F_._ptr(esc), cap, F_._ptr(state), F_._stream()),
-                    "lic_rans_encode_groups")
-            state[::G, RANS_LANES + 2] |= picked[:, RANS_LANES + 2]
-        blocks = _state_blocks(state, G, lambda i, states, nw, ne, err: err and (
-            "the rANS encoder met a malformed table, a pixel index outside the image or step lengths that do not add up "
-            f"(error word {err})"))                                               # the one read-back that waits
-        streams, escs = [], []
-        for i, (states, nw, ne) in enumerate(blocks):
-            if 2 * nw > slot or ne > cap:
-                raise CodecError(f"image {i // G}: the rANS encoder reports impossible counts ({nw} words, {ne} escapes)")
-            streams.append(states.astype("<u4").tobytes() + words[i, slot - 2 * nw:].cpu().numpy().tobytes())
-            escs.append(esc[i, :ne].cpu().numpy().view(np.uint32).astype("<u4").tobytes())
-        return streams, escs
+        G = self.groups
+        # B images of one size: uniform slots, with room for the states (lic_rans_bound); G = 1: cap = all symbols
+        layout = rans_block_layout([rans_group_sizes(step_len, G).max()] * B, G, 4 * RANS_LANES)
+        enc = _RansEncoding(tables.device, "single", layout, G, B * P * M, B, dict(order=order, steps=step_len))
+        enc.launch(tables, center, y_sym.contiguous(), M, self.y_W, P)
+        return enc.read_back()
+
+    def _coding_order(self, tables, center, y_sym, order, B: int, P: int, M: int):
+        """tables and symbols of B images on the host, in coding order: (tables [B][P * M][S + 1] uint32, symbol -
+        window start [B][P * M] int32), what the host coders take"""
+        perm = torch.from_numpy(np.array(order, np.int64)).to(tables.device)
+        idx = (y_sym - center + self.y_W).view(B, P, M)[:, perm].cpu().numpy().reshape(B, P * M)
+        return tables.view(B, P, M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, P * M, -1), idx
+
+    def _encode_y_host(self, tables, center, y_sym, order, step_len, B: int, P: int, M: int):
+        """`_encode_y_device`'s arguments and result from the host encoder: tables and symbols are permuted into
+        coding order on the device, copied, and coded image by image (`rans_encode_grouped`).  The same bytes."""
+        tabs, idx = self._coding_order(tables, center, y_sym, order, B, P, M)
+        pairs = [rans_encode_grouped(tabs[b], idx[b], step_len, self.groups) for b in range(B)]
+        return [s for p in pairs for s in p[0]], [e for p in pairs for e in p[1]]
+
+    def _optional_keys(self, z_esc=None) -> Dict:
+        """the keys of `compress`'s strings that are there only when they say something: z_coder and z_esc, groups,
+        slice_rows, schedule, coder"""
+        keys = {"z_coder": "rans", "z_esc": z_esc} if self.z_coder == "rans" else {}
+        said = {"groups": self.groups > 1, "slice_rows": self.slice_rows is not None,
+                "schedule": self.schedule != "raster", "coder": self.coder == "rans"}
+        return dict(keys, **{key: getattr(self, key) for key, yes in said.items() if yes})
 
 
 class ContextCodec(_LayeredCodec):
@@ -1444,8 +1528,10 @@ class ContextCodec(_LayeredCodec):
     either kind of codec refuses the other's strings and blobs on the host.
 
     This is the one-layer case of `_LayeredCodec`, which holds the gathers, the step loops and the whole of
-    `decompress_many`; what is written here is what one layer makes different: the range coder's loop, the containers
-    LICBITS1 to 5, the batched encoder, and for `decompress_many` `_item_streams` and `_finish`."""
+    `decompress_many`, and both y encoders; what is written here is what one layer makes different: the range coder's
+    loop, the containers LICBITS1 to 5, the batched encoder (`_compress_chunk`: its inputs only), the result of a
+    compress (`_compressed`, for `compress` and `compress_many`), and for `decompress_many` `_item_streams` and
+    `_finish`."""
 
     def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, coder: str = "range",
                  encoder: str = "host", groups: int = 1, slice_rows: int = None, z_coder: str = "range"):
@@ -1514,51 +1600,36 @@ class ContextCodec(_LayeredCodec):
         if self.z_coder == "rans":
             z_bytes, z_esc = self._encode_z(list(self._z_symbols(z_in)))
         else:
-            z_bytes = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in)
+            z_bytes, z_esc = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in), None
         psi = m.hyper_decoder(z_in).float()
         win, comb = self._windows_all(self._context_plane(out["y_in"]), self.slice_rows, psi)
         center, tables = self._params_at(win, None, self._prepack(), comb)
-        y_sym = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
+        y_sym = _rounded_nhwc(y_in).reshape(B * h * w, M)
         # symbols leave in the decoder's wavefront order (see _wavefront), M channels per pixel
-        steps = self._wavefront(h, w, self.slice_rows)
-        order = np.concatenate([ii * w + jj for ii, jj in steps])
-        step_len = [len(ii) * M for ii, _ in steps]
-        strings = {"z": z_bytes}
-        if self.z_coder == "rans":
-            strings.update(z_coder="rans", z_esc=z_esc)
-        if self.groups > 1:
-            strings["groups"] = self.groups
-        if self.slice_rows is not None:
-            strings["slice_rows"] = self.slice_rows
-        if self.schedule != "raster":
-            strings["schedule"] = self.schedule
-        if self.encoder == "device":
-            y_streams, y_esc = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, M)
-            strings.update(coder="rans", y_esc=y_esc)
-            return self._compressed(x, out, strings, y_streams, y_esc, y_sym, y_in, z_in)
-        perm = torch.from_numpy(order).to(y_in.device)
-        idx = (y_sym - center + self.y_W).view(B, h * w, M)[:, perm].cpu().numpy().reshape(B, h * w * M)
-        tabs = tables.view(B, h * w, M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * M, -1)
+        order, step_len, _ = _encode_layout_of(h, w, M, self.pad, self.slice_rows, self.groups, self.schedule)
         if self.coder == "rans":
-            pairs = [rans_encode_grouped(tabs[b], idx[b], step_len, self.groups) for b in range(B)]
-            y_streams, y_esc = [s for p in pairs for s in p[0]], [e for p in pairs for e in p[1]]
-            strings.update(coder="rans", y_esc=y_esc)
+            encode = self._encode_y_device if self.encoder == "device" else self._encode_y_host
+            y_streams, y_esc = encode(tables, center, y_sym, order, step_len, B, h * w, M)
         else:
+            tabs, idx = self._coding_order(tables, center, y_sym, order, B, h * w, M)
             y_streams, y_esc = [rc_encode(tabs[b], idx[b]) for b in range(B)], []
-        return self._compressed(x, out, strings, y_streams, y_esc, y_sym, y_in, z_in)
+        return self._compressed(x, dict(self._optional_keys(z_esc), z=z_bytes), y_streams, y_esc, y_sym.cpu().numpy(),
+                                out["logp_y"].double().sum() + out["logp_z"].double().sum(), y_in, z_in)
 
-    def _compressed(self, x, out, strings, y_streams, y_esc, y_sym, y_in, z_in) -> Dict:
-        """what `compress` returns, from the coded streams: sizes, the estimate and the symbol checksums"""
+    def _compressed(self, x, strings, y_streams, y_esc, h_sym: np.ndarray, logp, y_in, z_in) -> Dict:
+        """What `compress` and `compress_many` return for one item, from its coded streams.  strings: z and the
+        optional keys; h_sym: the item's latent symbols on the host, int32 in raster order; logp: the fp64 sum of its
+        log-likelihoods -- a device scalar from `compress`, a host one from `compress_many`, and the estimate is
+        divided where the sum lies (the two differ in the last bit now and then)."""
         B, M, h, w = y_in.shape
         npix = x.shape[0] * x.shape[2] * x.shape[3]
+        if self.coder == "rans":
+            strings["y_esc"] = y_esc
         coded = 8.0 * (_z_size(strings) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
-        est = float(-(out["logp_y"].double().sum() + out["logp_z"].double().sum()) / np.log(2.0) / npix)
         # CRC-32 of every image's latent symbols, which the decoder checks (`_check_latents`)
-        y_crc = [_crc32_of(a) for a in y_sym.reshape(B, h * w * M).cpu().numpy().astype(np.int32)]
-        strings.update(y=y_streams, y_crc32=y_crc)
-        return {"strings": strings, "shape": (B, M, h, w),
-                "z_shape": tuple(z_in.shape),
-                "bpp_coded": coded, "bpp_est": est, "y_in": y_in, "z_in": z_in}
+        strings.update(y=y_streams, y_crc32=[_crc32_of(a) for a in h_sym.reshape(B, h * w * M)])
+        return {"strings": strings, "shape": (B, M, h, w), "z_shape": tuple(z_in.shape), "bpp_coded": coded,
+                "bpp_est": float(-logp / np.log(2.0) / npix), "y_in": y_in, "z_in": z_in}
 
     # ---- many images in one encode pass -----------------------------------------------------------
     @torch.no_grad()
@@ -1575,15 +1646,7 @@ class ContextCodec(_LayeredCodec):
         before the device is touched."""
         xs = list(xs)
         names = [f"item {i}" for i in range(len(xs))] if names is None else list(names)
-        for i, x in enumerate(xs):
-            try:
-                self._refuse_unless_batched_encoder()
-                if not isinstance(x, torch.Tensor) or x.dim() != 4:
-                    raise CodecError("expected a [B,3,H,W] tensor")
-                if not x.is_cuda:
-                    raise CodecError("expected a tensor on the GPU: the device encoder runs where the tables are built")
-            except CodecError as err:
-                raise CodecError(f"{names[i]}: {err}") from None
+        self._refuse_items(xs, names)
         if not xs:
             return []
         M = self.model.M
@@ -1598,10 +1661,11 @@ class ContextCodec(_LayeredCodec):
         """One pass of `compress_many`.  After every item's transforms: all y_in and psi planes in two flat buffers
         (every item on a multiple of 4 floats, plain NHWC planes), ONE `lic_ctx_gather_ragged` over every pixel of
         every image (rows image-major, raster order inside an image), ONE `_params_at` over all rows, ONE
-        `lic_rans_encode_pick_ragged` and ONE `lic_rans_encode_ragged` (`ragged_encode_plan` lays their buffers out).
-        The device -> host copies that wait do not grow with the images: the z symbols of all items, the state
-        blocks, the word buffer, the used escape entries (one gather by an index built from the counts; none if there
-        is no escape), the symbols for the checksums and the rate estimates."""
+        `lic_rans_encode_pick_ragged` and ONE `lic_rans_encode_ragged`.  Written here: the inputs of those calls
+        (`ragged_encode_plan`, `plane_layout`).  Buffers, the one upload and the launches are `_RansEncoding`'s, the
+        read-back is `rans_read_back`, every item's result is `_compressed`'s.  The device -> host copies that wait do
+        not grow with the images: the z symbols of all items, the state blocks, the word buffer, the used escape
+        entries, the symbols for the checksums and the rate estimates."""
         m, G, R = self.model, self.groups, self.slice_rows
         M, dev = m.M, xs[0].device
         outs, psis, sums = [], [], []
@@ -1610,26 +1674,19 @@ class ContextCodec(_LayeredCodec):
             outs.append((out["y_in"].contiguous(), out["z_in"], self._context_plane(out["y_in"])))
             psis.append(m.hyper_decoder(out["z_in"]).float())
             sums.append(out["logp_y"].double().sum() + out["logp_z"].double().sum())
+        owner = [(i, b) for i, (y_in, _, _) in enumerate(outs) for b in range(y_in.shape[0])]
+        name = lambda im: f"{names[owner[im][0]]}: image {owner[im][1]}"
         # z: the symbols of all items in one read-back, one host range coder run per item as `compress` has it -- or,
-        # with z_coder="rans", the kernels on all of them at once
-        z_bytes, z_escs, at = [], [], 0
+        # with z_coder="rans", every image of every item in one pick and one encode launch, cut per item below
+        zs, zes, at = [], None, 0
         if self.z_coder == "rans":
-            # every image of every item in one pick and one encode launch; the strings are cut per item below
-            owner_z = [(i, b) for i, (_, z, _) in enumerate(outs) for b in range(z.shape[0])]
-            zs, zes = self._encode_z([row for _, z, _ in outs for row in self._z_symbols(z)],
-                                     lambda im: f"{names[owner_z[im][0]]}: image {owner_z[im][1]}")
-            for _, z, _ in outs:
-                z_bytes.append(zs[at:at + z.shape[0] * G])
-                z_escs.append(zes[at:at + z.shape[0] * G])
-                at += z.shape[0] * G
+            zs, zes = self._encode_z([row for _, z, _ in outs for row in self._z_symbols(z)], name)
         else:
-            z_sym = [(z.permute(0, 2, 3, 1).contiguous().round().to(torch.int32) - self.z_lo).reshape(-1)
-                     for _, z, _ in outs]
+            z_sym = [(_rounded_nhwc(z) - self.z_lo).reshape(-1) for _, z, _ in outs]
             z_all = torch.cat(z_sym).cpu().numpy()
             for z in z_sym:
-                n = z.numel()
-                z_bytes.append(rc_encode(zt, z_all[at:at + n], np.tile(np.arange(len(zt), dtype=np.int32), n // len(zt))))
-                at += n
+                zs.append(rc_encode_z(zt, z_all[at:at + z.numel()]))
+                at += z.numel()
         cpsi = psis[0].shape[1]
         shapes = [(y_in.shape[2], y_in.shape[3]) for y_in, _, _ in outs for _ in range(y_in.shape[0])]
         nimg = len(shapes)
@@ -1643,74 +1700,27 @@ class ContextCodec(_LayeredCodec):
             B, _, h, w = y_in.shape
             yflat[y_at:y_at + B * h * w * M].view(B, h, w, M).copy_(F_._nhwc(y_raw))
             psiflat[psi_at:psi_at + B * h * w * cpsi].view(B, h * w, cpsi).copy_(F_._nhwc(psi).view(B, h * w, -1))
-            y_syms.append(y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32))
-        y_sym = torch.cat(y_syms) if len(y_syms) > 1 else y_syms[0].contiguous()
-        # one upload of everything the kernels index with; every part is int64, so every part is 8-byte aligned
+            y_syms.append(_rounded_nhwc(y_in).reshape(B * h * w, M))
+        y_sym = torch.cat(y_syms) if len(y_syms) > 1 else y_syms[0]
+        # one upload of everything the kernels index with, the gather's descriptors and rows included
         row_pix = np.concatenate([np.arange(h * w, dtype=np.int64) for h, w in shapes])
-        parts = [lay.desc.ravel(), plan.images.ravel(), plan.blocks.ravel(), plan.row_image, row_pix, plan.order,
-                 plan.step_len]
-        d_all = torch.from_numpy(np.concatenate(parts)).to(dev)
-        d_desc, d_images, d_blocks, d_row_image, d_row_pix, d_order, d_steps = torch.split(d_all, [a.size for a in parts])
-        rows, nsym = plan.total_rows, plan.total_rows * M
-        ((win, comb),) = self._gather_rows(self.layers, yflat, M, d_desc.view(nimg, -1), d_row_image, d_row_pix, psiflat,
-                                           cpsi)
+        enc = _RansEncoding(dev, "ragged", (plan.blocks, plan.words_len, plan.esc_len), G, plan.total_rows * M, nimg,
+                            dict(desc=lay.desc, images=plan.images, blocks=plan.blocks, row_image=plan.row_image,
+                                 row_pix=row_pix, order=plan.order, steps=plan.step_len))
+        ((win, comb),) = self._gather_rows(self.layers, yflat, M, enc.d["desc"].view(nimg, -1), enc.d["row_image"],
+                                           enc.d["row_pix"], psiflat, cpsi)
         center, tables = self._params_at(win, None, self._prepack(), comb)
-        sf = torch.empty(nsym, device=dev, dtype=torch.int32)
-        exc = torch.empty_like(sf)
-        words = torch.empty(plan.words_len, device=dev, dtype=torch.uint8)
-        esc = torch.empty(plan.esc_len, device=dev, dtype=torch.int32)
-        # the encoder's nimg * G blocks, then pick's one block per image: one buffer, one read-back
-        state = torch.zeros((nimg * G + nimg, L.RANS_STATE_WORDS), device=dev, dtype=torch.int32)
-        lib = L.load()
-        L.check(lib.lic_rans_encode_pick_ragged(F_._ptr(tables), F_._ptr(center), F_._ptr(y_sym), rows, F_._ptr(d_images),
-                                                nimg, F_._ptr(d_row_image), F_._ptr(d_order), M, self.y_W, F_._ptr(sf),
-                                                F_._ptr(exc), F_._ptr(state[nimg * G:]), F_._stream()),
-                "lic_rans_encode_pick_ragged")
-        L.check(lib.lic_rans_encode_ragged(F_._ptr(sf), F_._ptr(exc), F_._ptr(d_steps), plan.step_len.size,
-                                           F_._ptr(d_images), F_._ptr(d_blocks), nimg, G, rows, M, F_._ptr(words),
-                                           plan.words_len, F_._ptr(esc), plan.esc_len, F_._ptr(state), F_._stream()),
-                "lic_rans_encode_ragged")
-        owner = [(i, b) for i, (y_in, _, _) in enumerate(outs) for b in range(y_in.shape[0])]
-        h_state = state.cpu()                                                     # the first read-back that waits
-        picked = h_state[nimg * G:, RANS_LANES + 2].numpy()
-        blocks = _state_blocks(h_state[:nimg * G], G, lambda i, states, nw, ne, err: (err or picked[i // G]) and (
-            "the rANS encoder met a malformed table, a pixel index outside the image or step lengths that do not add up "
-            f"(error word {err | int(picked[i // G])})"), lambda im: f"{names[owner[im][0]]}: image {owner[im][1]}")
-        for i, (_, nw, ne) in enumerate(blocks):
-            if 2 * nw > plan.blocks[i, 1] or ne > plan.blocks[i, 3]:
-                raise CodecError(f"{names[owner[i // G][0]]}: image {owner[i // G][1]}: the rANS encoder reports "
-                                 f"impossible counts ({nw} words, {ne} escapes)")
-        h_words = words.cpu().numpy()
-        used = np.concatenate([plan.blocks[i, 2] + np.arange(ne, dtype=np.int64) for i, (_, _, ne) in enumerate(blocks)])
-        h_esc = (esc[torch.from_numpy(used).to(dev)].cpu().numpy() if used.size else np.zeros(0, np.int32)).view(np.uint32)
+        enc.launch(tables, center, y_sym, M, self.y_W, plan.total_rows)
+        streams, escs = enc.read_back(name)
         h_sym = y_sym.cpu().numpy()
         h_sums = torch.stack(sums).cpu().numpy()
-        streams, escs, e_at = [], [], 0
-        for i, (states, nw, ne) in enumerate(blocks):
-            end = int(plan.blocks[i, 0] + plan.blocks[i, 1])
-            streams.append(states.astype("<u4").tobytes() + h_words[end - 2 * nw:end].tobytes())
-            escs.append(h_esc[e_at:e_at + ne].astype("<u4").tobytes())
-            e_at += ne
         res, img = [], 0
         for i, ((y_in, z_in, _), x) in enumerate(zip(outs, xs)):
             B, _, h, w = y_in.shape
-            strings = {"z": z_bytes[i]}
-            if self.z_coder == "rans":
-                strings.update(z_coder="rans", z_esc=z_escs[i])
-            if G > 1:
-                strings["groups"] = G
-            if R is not None:
-                strings["slice_rows"] = R
-            if self.schedule != "raster":
-                strings["schedule"] = self.schedule
-            y_streams, y_esc = streams[img * G:(img + B) * G], escs[img * G:(img + B) * G]
-            row0 = int(plan.images[img, 0])
-            y_crc = [_crc32_of(a) for a in h_sym[row0:row0 + B * h * w].reshape(B, h * w * M)]
-            strings.update(coder="rans", y_esc=y_esc, y=y_streams, y_crc32=y_crc)
-            npix = x.shape[0] * x.shape[2] * x.shape[3]
-            coded = 8.0 * (_z_size(strings) + sum(len(s) for s in y_streams) + sum(len(e) for e in y_esc)) / npix
-            res.append({"strings": strings, "shape": (B, M, h, w), "z_shape": tuple(z_in.shape), "bpp_coded": coded,
-                        "bpp_est": float(-h_sums[i] / np.log(2.0) / npix), "y_in": y_in, "z_in": z_in})
+            row0, cut = int(plan.images[img, 0]), slice(img * G, (img + B) * G)
+            strings = self._optional_keys(zes[cut]) if zes is not None else self._optional_keys()
+            res.append(self._compressed(x, dict(strings, z=zs[cut] if zes is not None else zs[i]), streams[cut], escs[cut],
+                                        h_sym[row0:row0 + B * h * w], h_sums[i], y_in, z_in))
             img += B
         return res
 
@@ -1849,10 +1859,7 @@ class ContextCodec(_LayeredCodec):
             enc, G = (self.encoder, self.groups) if (coder, True) in _FORMATS else ("host", 1)
             return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder, enc, G).compress_image(x, mode, align)
         self._refuse_checkerboard_without_zrans()
-        B, _, H, W = x.shape
-        _, _, top, left = F_.pad_geometry(H, W, 64, align)
-        r = self.compress(F_.pad_to_multiple(x, 64, mode, align))
-        return self._pack_image(r["strings"], B, H, W, top, left)
+        return self._pack_padded(x, self.compress(F_.pad_to_multiple(x, 64, mode, align))["strings"], align)
 
     def _pack_image(self, s: Dict, B: int, H: int, W: int, top: int, left: int) -> bytes:
         """the container of `compress_image` around the strings `compress` gave for the padded image"""
@@ -1875,6 +1882,20 @@ class ContextCodec(_LayeredCodec):
             raise CodecError(f"z_coder={self.z_coder!r}: the container of the checkerboard schedule (LICBITS7) carries z as "
                              "rANS sub-streams, as LICBITS5 does: build the codec with z_coder='rans'")
 
+    def _refuse_items(self, xs, names, also=lambda: None):
+        """what `compress_many` refuses of its items before the device is touched, item by item, named; `also`: what a
+        caller refuses of the codec besides"""
+        for x, name in zip(xs, names):
+            try:
+                self._refuse_unless_batched_encoder()
+                also()
+                if not isinstance(x, torch.Tensor) or x.dim() != 4:
+                    raise CodecError("expected a [B,3,H,W] tensor")
+                if not x.is_cuda:
+                    raise CodecError("expected a tensor on the GPU: the device encoder runs where the tables are built")
+            except CodecError as err:
+                raise CodecError(f"{name}: {err}") from None
+
     def _refuse_unless_batched_encoder(self):
         if self.coder != "rans" or self.encoder != "device":
             raise CodecError(f"this codec has coder={self.coder!r}, encoder={self.encoder!r}: images are encoded "
@@ -1893,26 +1914,12 @@ class ContextCodec(_LayeredCodec):
         coder or encoder, an entry that is not a [B,3,H,W] tensor, a tensor that is not on the GPU.  An empty list
         gives an empty list."""
         images = list(images)
-        for i, x in enumerate(images):
-            try:
-                self._refuse_unless_batched_encoder()
-                self._refuse_checkerboard_without_zrans()
-                if not isinstance(x, torch.Tensor) or x.dim() != 4:
-                    raise CodecError("expected a [B,3,H,W] tensor")
-                if not x.is_cuda:
-                    raise CodecError("expected a tensor on the GPU: the device encoder runs where the tables are built")
-            except CodecError as err:
-                raise CodecError(f"image {i}: {err}") from None
+        names = [f"image {i}" for i in range(len(images))]
+        self._refuse_items(images, names, self._refuse_checkerboard_without_zrans)
         if not images:
             return []
-        names = [f"image {i}" for i in range(len(images))]
         rs = self.compress_many([F_.pad_to_multiple(x, 64, mode, align) for x in images], table_budget_bytes, names)
-        blobs = []
-        for x, r in zip(images, rs):
-            B, _, H, W = x.shape
-            _, _, top, left = F_.pad_geometry(H, W, 64, align)
-            blobs.append(self._pack_image(r["strings"], B, H, W, top, left))
-        return blobs
+        return [self._pack_padded(x, r["strings"], align) for x, r in zip(images, rs)]
 
     @torch.no_grad()
     def decompress_image(self, data: bytes) -> torch.Tensor:
@@ -2041,7 +2048,7 @@ class ScalableCodec(_LayeredCodec):
 
     @torch.no_grad()
     def compress(self, x: torch.Tensor) -> Dict:
-        m, G = self.model, self.groups
+        m = self.model
         if x.dim() != 4 or x.shape[2] % 64 or x.shape[3] % 64:
             raise CodecError("expected a [B,3,H,W] tensor with H and W multiples of 64 (compress_image pads any size)")
         if m.use_step_prep and x.is_cuda:
@@ -2051,34 +2058,22 @@ class ScalableCodec(_LayeredCodec):
         B, M, h, w = y_in.shape
         z_bytes, z_esc = self._encode_z(list(self._z_symbols(z_in)))
         psi = m.hyper_decoder(z_in).float()
-        steps = self._wavefront(h, w, self.slice_rows)
-        order = np.concatenate([ii * w + jj for ii, jj in steps])
-        y_sym_all = y_in.permute(0, 2, 3, 1).reshape(B * h * w, M).round().to(torch.int32)
+        y_sym_all = _rounded_nhwc(y_in).reshape(B * h * w, M)
+        encode = self._encode_y_device if self.encoder == "device" else self._encode_y_host
         logp = m.factorized_entropy_model.likelihood_and_log(z_in)[1].double().sum()
         coded = []
         for ly, (win, comb) in zip(self.layers, self._windows_layers(y_in, self.slice_rows, psi)):
             act = ly.act_at(win, None, ly.prepack(), comb)
             center, tables = gmm_tables(act, ly.M, ly.K, self.y_W)
             y_sym = y_sym_all[:, ly.c0:ly.c0 + ly.M].contiguous()
-            step_len = [len(ii) * ly.M for ii, _ in steps]
-            if self.encoder == "device":
-                streams, escs = self._encode_y_device(tables, center, y_sym, order, step_len, B, h * w, ly.M)
-            else:
-                perm = torch.from_numpy(order).to(y_in.device)
-                idx = (y_sym - center + self.y_W).view(B, h * w, ly.M)[:, perm].cpu().numpy().reshape(B, h * w * ly.M)
-                tabs = tables.view(B, h * w, ly.M, -1)[:, perm].cpu().numpy().view(np.uint32).reshape(B, h * w * ly.M, -1)
-                pairs = [rans_encode_grouped(tabs[b], idx[b], step_len, G) for b in range(B)]
-                streams, escs = [s for p in pairs for s in p[0]], [e for p in pairs for e in p[1]]
-            crc = [_crc32_of(a) for a in y_sym.reshape(B, h * w * ly.M).cpu().numpy().astype(np.int32)]
-            coded.append({"y": streams, "y_esc": escs, "y_crc32": crc})
+            order, step_len, _ = _encode_layout_of(h, w, ly.M, self.pad, self.slice_rows, self.groups, self.schedule)
+            streams, escs = encode(tables, center, y_sym, order, step_len, B, h * w, ly.M)
+            coded.append({"y": streams, "y_esc": escs,
+                          "y_crc32": [_crc32_of(a) for a in y_sym.reshape(B, h * w * ly.M).cpu().numpy()]})
             y_l = y_in[:, ly.c0:ly.c0 + ly.M]
             logp = logp + m.conditional.packed_likelihood_and_log(
                 y_l, act.reshape(B, h, w, -1).permute(0, 3, 1, 2), ly.K)[1].double().sum()
-        strings = {"layers": coded, "z": z_bytes, "z_esc": z_esc, "z_coder": "rans", "coder": "rans"}
-        if G > 1:
-            strings["groups"] = G
-        if self.slice_rows is not None:
-            strings["slice_rows"] = self.slice_rows
+        strings = dict(self._optional_keys(z_esc), layers=coded, z=z_bytes)
         npix = B * x.shape[2] * x.shape[3]
         blob = self._pack_image(strings, B, x.shape[2], x.shape[3], 0, 0)      # the ledger counts the container
         base_bytes = self.base_bytes_of(blob)
@@ -2165,10 +2160,7 @@ class ScalableCodec(_LayeredCodec):
         first `base_bytes` (header word; `base_bytes_of(blob)`) `decompress_base_image` decodes by themselves"""
         if x.dim() != 4:
             raise CodecError("expected a [B,3,H,W] tensor")
-        B, _, H, W = x.shape
-        _, _, top, left = F_.pad_geometry(H, W, 64, align)
-        r = self.compress(F_.pad_to_multiple(x, 64, mode, align))
-        return self._pack_image(r["strings"], B, H, W, top, left)
+        return self._pack_padded(x, self.compress(F_.pad_to_multiple(x, 64, mode, align))["strings"], align)
 
     @staticmethod
     def base_bytes_of(blob: bytes) -> int:
