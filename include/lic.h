@@ -239,6 +239,46 @@ int lic_quantize_anchor(const float* v, const float* u, float* out, float* out_a
 int lic_anchor_add(const float* g, const float* g_anchor, float* out, int32_t B, int32_t h, int32_t w, int32_t C,
                    lic_stream_t stream);
 
+/* ---- gain units (variable rate; Cui et al. 2021) ------------------------------- */
+/* A per-channel scale in front of a quantiser (gain) or behind it (inverse gain).  v, u, vg, out, out_anchor: NHWC
+ * [B][h][w][C] fp32, any C >= 1.  The scale is read as s[b * s_stride + c]: s_stride = 0 is one row for every image,
+ * otherwise s_stride >= C and every image has its own row.
+ *   vg = fl32(v * s), always written;
+ *   LIC_GAIN_SCALE: nothing else (u, out, out_anchor, out_bf16, anchor_bf16 must be NULL);
+ *   LIC_GAIN_NOISE: out = fl32(vg + fl32(u - 0.5f));
+ *   LIC_GAIN_ROUND: out = rint(vg), u is not read;
+ *   out_anchor (may be NULL): out where pixel (i, j) has i + j even, +0 elsewhere (lic_quantize_anchor's rule);
+ *   vg_bf16, out_bf16, anchor_bf16 (each may be NULL): the round-to-nearest-even bf16 of vg, out, out_anchor.
+ * The product is rounded to fp32 before the sum: the multiply and the add are never contracted into one FMA, so every
+ * output is a float32 numpy statement bit for bit.  16-byte pieces where C % 4 == 0, s_stride % 4 == 0 and every
+ * pointer given is aligned (fp32 16 bytes, bf16 8), single floats otherwise; both write the same bytes.
+ *   NULL v / s / vg (out, and u for NOISE), a non-positive extent, 0 < s_stride < C or s_stride < 0, an unknown mode:
+ *   LIC_ERR_INVALID; h * w * C >= 2^31 or more than 2^31 - 1 workgroups: LIC_ERR_UNSUPPORTED.  Nothing launched then.
+ *   One launch on `stream`, no allocation, no synchronisation, graph-capturable. */
+#define LIC_GAIN_SCALE 0
+#define LIC_GAIN_NOISE 1
+#define LIC_GAIN_ROUND 2
+int lic_gain_quantize(const float* v, const float* u, const float* s, int64_t s_stride, float* vg, float* out,
+                      float* out_anchor, void* vg_bf16, void* out_bf16, void* anchor_bf16, int32_t B, int32_t h, int32_t w,
+                      int32_t C, int32_t mode, lic_stream_t stream);
+/* The backward of lic_gain_quantize.  t = d_vg + d_out + anchor(d_anchor), summed in that order; any of the three may be
+ * NULL (it is left out of the sum), at least one is given.  dv = fl32(t * s);  ds[b][c] = sum over the pixels of image b
+ * of fl32(t * v), accumulated in fp32 and written as [B][C] whatever s_stride is.
+ * The sum has two stages in a fixed order, no float atomics, the same bits on every run and on either path (16-byte
+ * pieces or single floats, chosen as above): a workgroup sums one slab of LIC_GAIN_SLAB_PIXELS consecutive pixels of one
+ * image -- LIC_GAIN_SLAB_ROWS running sums, sum r over the slab's pixels r, r + ROWS, ... in rising order, then added
+ * r = 0, 1, ... -- into a partial row of the workspace, [B][slabs][C] with slabs = ceil(h * w / LIC_GAIN_SLAB_PIXELS);
+ * one pass then adds the partial rows of an image slab 0, 1, ...  (One slab: its row goes straight into ds.)
+ *   NULL v / s / dv / ds / workspace, no gradient given, a non-positive extent, 0 < s_stride < C or s_stride < 0, a
+ *   workspace below lic_gain_bwd_workspace_bytes(B, h * w, C): LIC_ERR_INVALID, nothing launched; the size limits of
+ *   lic_gain_quantize: LIC_ERR_UNSUPPORTED.  No allocation, no synchronisation, graph-capturable. */
+#define LIC_GAIN_SLAB_PIXELS 32
+#define LIC_GAIN_SLAB_ROWS 4
+size_t lic_gain_bwd_workspace_bytes(int32_t B, int64_t hw, int32_t C); /* 0 for a non-positive argument */
+int lic_gain_bwd(const float* v, const float* s, int64_t s_stride, const float* d_vg, const float* d_out,
+                 const float* d_anchor, float* dv, float* ds, int32_t B, int32_t h, int32_t w, int32_t C, void* workspace,
+                 size_t workspace_bytes, lic_stream_t stream);
+
 /* ---- entropy models (NHWC, P = B*h*w pixels) ------------------------------------------------ */
 /* ParametersModels.py:43-64.  raw/out rows hold G*K*M channels (G = 2 if K == 1 else 3):
  * K==1: [mu | sigma]; K>1: [w | mu | sigma] with channel k*M+m inside each third. */

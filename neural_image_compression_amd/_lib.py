@@ -87,6 +87,10 @@ RANS_IMAGE_WORDS = RANS_BLOCK_WORDS = 4
 RANS_Z_AUTO, RANS_Z_RESIDENT, RANS_Z_GLOBAL = range(3)
 RANS_Z_MAX_S, RANS_Z_MAX_M, RANS_Z_LDS_BYTES = 4096, 65535, 65536
 
+# lic_gain_quantize's `mode`; lic_gain_bwd's slab of pixels per partial row
+GAIN_SCALE, GAIN_NOISE, GAIN_ROUND = range(3)
+GAIN_SLAB_PIXELS, GAIN_SLAB_ROWS = 32, 4
+
 # the layered codec's entries take a host array of at most MAX_LAYERS rows, which they copy into the launch
 MAX_LAYERS = 4
 
@@ -144,6 +148,9 @@ SIGNATURES = {
     "lic_quantize": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "lic_quantize_anchor": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "lic_anchor_add": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "lic_gain_quantize": (C.c_int, [_vp, _vp, _vp, _i64] + [_vp] * 6 + [_i32] * 5 + [_vp]),
+    "lic_gain_bwd_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "lic_gain_bwd": (C.c_int, [_vp, _vp, _i64] + [_vp] * 5 + [_i32] * 4 + [_vp, _sz, _vp]),
     "lic_entropy_params_fwd": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "lic_entropy_params_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "lic_gmm_likelihood_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),

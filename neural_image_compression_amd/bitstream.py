@@ -429,3 +429,69 @@ def unpack_bitstream_checker(data: bytes):
     likewise], [y sub-stream likewise], [y escape list likewise], [symbol checksum per image], groups)"""
     head, (zs, zes), ys, escs, crcs, G = _unpack(_FORMAT_CHECKER, data)
     return head, zs, zes, ys, escs, crcs, G
+
+
+# ---- LICRATE1: the quality envelope of a rate-level codec ----------------------------------------------------------
+# A variable-rate model (models: rate_levels = Q) codes at any real quality q in [0, Q-1], and its decoder needs q for the
+# two inverse gains.  q travels AROUND the container, not in it: the tables above stay what they are.  Little endian:
+#   magic LICRATE1 | float32 q | uint16 Q | uint16 zero | uint32 inner length | the inner LICBITS1-5/7 blob, verbatim
+#   | uint32 CRC-32 of all before it
+BITSTREAM_MAGIC_RATE = b"LICRATE1"
+_RATE_HEAD = struct.Struct("<8sfHHI")
+
+
+def _rate_quality(quality, Q):
+    """(q as the float32 the envelope holds, Q) or CodecError"""
+    if isinstance(Q, bool) or not isinstance(Q, (int, np.integer)) or not 2 <= int(Q) <= 0xFFFF:
+        raise CodecError(f"rate_levels = {Q!r}: expected an integer from 2 to 65535")
+    try:
+        q = float(np.float32(quality))
+    except (TypeError, ValueError):
+        raise CodecError(f"quality = {quality!r}: expected a number") from None
+    if not 0.0 <= q <= int(Q) - 1:
+        raise CodecError(f"quality {quality!r} outside [0, {int(Q) - 1}]")
+    return q, int(Q)
+
+
+def pack_rate_envelope(inner: bytes, quality: float, rate_levels: int) -> bytes:
+    q, Q = _rate_quality(quality, rate_levels)
+    inner = bytes(inner)
+    if len(inner) > 0xFFFFFFFF:
+        raise CodecError("the bitstream is too long for its 32-bit length")
+    body = _RATE_HEAD.pack(BITSTREAM_MAGIC_RATE, q, Q, 0, len(inner)) + inner
+    return body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+
+
+def is_rate_envelope(data: bytes) -> bool:
+    return bytes(data[:8]) == BITSTREAM_MAGIC_RATE
+
+
+def unpack_rate_envelope(data: bytes, rate_levels: int = None):
+    """-> (quality, Q, inner blob).  CodecError, in this order, for a buffer shorter than the envelope, another magic (a
+    bare LICBITS blob), an inner length that is not the buffer's, a failing CRC-32, a non-zero pad, Q < 2, q outside
+    [0, Q-1] (or no number), and -- `rate_levels` given -- a Q that is not the model's."""
+    data = bytes(data)
+    if len(data) < _RATE_HEAD.size + 4:
+        raise CodecError("rate envelope is truncated (shorter than its header)")
+    magic, q, Q, pad, n = _RATE_HEAD.unpack_from(data, 0)
+    if magic != BITSTREAM_MAGIC_RATE:
+        raise CodecError(f"not a {BITSTREAM_MAGIC_RATE.decode()} rate envelope (bad magic): a rate-level codec reads "
+                         "only envelopes")
+    if len(data) != _RATE_HEAD.size + n + 4:
+        raise CodecError("rate envelope is truncated or has trailing bytes (its length does not match its header)")
+    if zlib.crc32(data[:-4]) & 0xFFFFFFFF != struct.unpack_from("<I", data, len(data) - 4)[0]:
+        raise CodecError("rate envelope is damaged (CRC-32 mismatch)")
+    if pad != 0:
+        raise CodecError(f"rate envelope header is damaged (pad word = {pad}, not zero)")
+    if Q < 2:
+        raise CodecError(f"rate envelope header is damaged (Q = {Q} rate levels)")
+    if not 0.0 <= q <= Q - 1:
+        raise CodecError(f"rate envelope names quality {q} outside [0, {Q - 1}]")
+    if rate_levels is not None and Q != rate_levels:
+        raise CodecError(f"rate envelope was written by a model of {Q} rate levels; this model has {rate_levels}")
+    return float(q), int(Q), data[_RATE_HEAD.size:_RATE_HEAD.size + n]
+
+
+def quality_of(blob: bytes) -> float:
+    """the quality a rate envelope was coded at"""
+    return unpack_rate_envelope(blob)[0]

@@ -86,7 +86,8 @@ from .bitstream import (BITSTREAM_FAMILIES, BITSTREAM_MAGIC, BITSTREAM_MAGIC_GRO
                         unpack_bitstream_checker,
                         BITSTREAM_MAGIC_LAYERED, _BITS_HEAD_LAYERED,
                         _BITS_FIELDS, _BITS_HEAD, _BITS_HEAD_RANS, _FORMAT_OF_MAGIC, _FORMAT_ZRANS, _FORMATS,
-                        _check_crc_and_head, _format_of_magic,
+                        _check_crc_and_head, _format_of_magic, is_rate_envelope, pack_rate_envelope, quality_of,
+                        unpack_rate_envelope,
                         _groups, _pack, _unpack, pack_bitstream, pack_bitstream_grouped, pack_bitstream_layered,
                         pack_bitstream_rans,
                         pack_bitstream_sliced, pack_bitstream_zrans, unpack_bitstream, unpack_bitstream_grouped,
@@ -1037,6 +1038,48 @@ class _LayeredCodec:
     # what the layers' masks say (`CodecLayer.kind`, `_set_layers`): "raster" (`wavefront`) or "checkerboard" (`two_pass`)
     schedule = "raster"
 
+    # ---- rate levels (models: rate_levels = Q): the quality an item is coded at rides in its strings ----
+    @property
+    def rate_levels(self):
+        return getattr(self.model, "rate_levels", None)
+
+    def _quality(self, quality):
+        """one item's quality as this codec's model takes it: None for a plain model, a float in [0, Q-1] for a
+        rate-level one; CodecError otherwise"""
+        Q = self.rate_levels
+        if Q is None:
+            if quality is not None:
+                raise CodecError(f"quality = {quality!r}: this codec's model has no rate levels")
+            return None
+        if quality is None:
+            raise CodecError(f"this codec's model has {Q} rate levels: a quality in [0, {Q - 1}] is needed")
+        if isinstance(quality, bool) or not isinstance(quality, (int, float, np.integer, np.floating)):
+            raise CodecError(f"quality = {quality!r}: expected one number per item")
+        q = float(np.float32(quality))          # what the envelope holds: encoder and decoder scale by the same gains
+        if not 0.0 <= q <= Q - 1:
+            raise CodecError(f"quality {quality!r} outside [0, {Q - 1}]")
+        return q
+
+    def _qualities(self, quality, n: int, what: str = "item"):
+        """`quality` of a many-item call -> one per item: a number for all of them or a list of n"""
+        if quality is None or isinstance(quality, (int, float, np.integer, np.floating)):
+            return [self._quality(quality)] * n
+        qs = list(quality)
+        if len(qs) != n:
+            raise CodecError(f"{len(qs)} qualities for {n} {what}s: one number, or one per {what}")
+        out = []
+        for i, q in enumerate(qs):
+            try:
+                out.append(self._quality(q))
+            except CodecError as err:
+                raise CodecError(f"{what} {i}: {err}") from None
+        return out
+
+    def _hyper_synthesis(self, z_hat: torch.Tensor, quality=None) -> torch.Tensor:
+        """psi of one item: the hyper-decoder behind the inverse gain of its quality (the bare module for a plain model)"""
+        m = self.model
+        return m.hyper_synthesis(z_hat, quality) if hasattr(m, "hyper_synthesis") else m.hyper_decoder(z_hat)
+
     def _set_layers(self, layers):
         """the codec's layers; they share one wavefront schedule and one tap table, so their masks must agree"""
         self.layers = list(layers)
@@ -1334,7 +1377,7 @@ class _LayeredCodec:
                 except CodecError as err:
                     raise CodecError(f"{names[i]}: {err}") from None
             z_hats.append(z_hat.contiguous(memory_format=torch.channels_last))
-            psis.append(m.hyper_decoder(z_hats[-1]).float())
+            psis.append(self._hyper_synthesis(z_hats[-1], strings.get("quality")).float())
         cpsi = psis[0].shape[1]
         lay = plane_layout([(B, h, w) for _, (B, _, h, w), _ in items], y_pix, cpsi, p, Rs)
         yflat = torch.zeros(lay.y_len, device=dev, dtype=torch.float32)            # decoded latents inside zero frames
@@ -1527,6 +1570,12 @@ class ContextCodec(_LayeredCodec):
     `slice_rows`; `strings["schedule"]` is "checkerboard", the container is LICBITS7 (which needs z_coder="rans"), and
     either kind of codec refuses the other's strings and blobs on the host.
 
+    A rate-level model (`rate_levels=Q`) codes at the quality given to `compress(x, quality)` and its kin:
+    `strings["quality"]` holds it (as the float32 the container keeps), the decoders read it there, and
+    `compress_image` wraps its container in a LICRATE1 envelope (bitstream.py) that carries q and Q.  Such a codec
+    writes and reads envelopes only; a plain codec refuses them.  Blobs of different qualities decode together: only
+    the two inverse gains are per item.
+
     This is the one-layer case of `_LayeredCodec`, which holds the gathers, the step loops and the whole of
     `decompress_many`, and both y encoders; what is written here is what one layer makes different: the range coder's
     loop, the containers LICBITS1 to 5, the batched encoder (`_compress_chunk`: its inputs only), the result of a
@@ -1592,16 +1641,17 @@ class ContextCodec(_LayeredCodec):
         return win if psi is None else (win, comb)
 
     @torch.no_grad()
-    def compress(self, x: torch.Tensor) -> Dict:
+    def compress(self, x: torch.Tensor, quality: float = None) -> Dict:
         m = self.model
-        out = m.analysis_hyperprior(x, training=False)
+        q = self._quality(quality)
+        out = m.analysis_hyperprior(x, training=False, quality=q)
         y_in, z_in = out["y_in"].contiguous(), out["z_in"]
         B, M, h, w = y_in.shape
         if self.z_coder == "rans":
             z_bytes, z_esc = self._encode_z(list(self._z_symbols(z_in)))
         else:
             z_bytes, z_esc = LatentCodec(m, self.z_lo, self.z_S, self.y_W).encode_z(z_in), None
-        psi = m.hyper_decoder(z_in).float()
+        psi = self._hyper_synthesis(z_in, q).float()
         win, comb = self._windows_all(self._context_plane(out["y_in"]), self.slice_rows, psi)
         center, tables = self._params_at(win, None, self._prepack(), comb)
         y_sym = _rounded_nhwc(y_in).reshape(B * h * w, M)
@@ -1613,8 +1663,12 @@ class ContextCodec(_LayeredCodec):
         else:
             tabs, idx = self._coding_order(tables, center, y_sym, order, B, h * w, M)
             y_streams, y_esc = [rc_encode(tabs[b], idx[b]) for b in range(B)], []
-        return self._compressed(x, dict(self._optional_keys(z_esc), z=z_bytes), y_streams, y_esc, y_sym.cpu().numpy(),
-                                out["logp_y"].double().sum() + out["logp_z"].double().sum(), y_in, z_in)
+        return self._compressed(x, dict(self._optional_keys(z_esc), z=z_bytes, **self._quality_key(q)), y_streams, y_esc,
+                                y_sym.cpu().numpy(), out["logp_y"].double().sum() + out["logp_z"].double().sum(), y_in, z_in)
+
+    @staticmethod
+    def _quality_key(q) -> Dict:
+        return {} if q is None else {"quality": q}
 
     def _compressed(self, x, strings, y_streams, y_esc, h_sym: np.ndarray, logp, y_in, z_in) -> Dict:
         """What `compress` and `compress_many` return for one item, from its coded streams.  strings: z and the
@@ -1633,7 +1687,8 @@ class ContextCodec(_LayeredCodec):
 
     # ---- many images in one encode pass -----------------------------------------------------------
     @torch.no_grad()
-    def compress_many(self, xs: Sequence[torch.Tensor], table_budget_bytes: int = 2 << 30, names=None) -> List[Dict]:
+    def compress_many(self, xs: Sequence[torch.Tensor], table_budget_bytes: int = 2 << 30, names=None,
+                      quality=None) -> List[Dict]:
         """`compress` for several inputs at once (coder "rans", encoder "device").  xs: [B_i, 3, H_i, W_i] tensors as
         `compress` takes them (sides already multiples of 64), of any sizes; names: what to call an item in a message
         (default "item i").  -> one `compress` result per item: the same strings byte for byte, shape, z_shape,
@@ -1642,11 +1697,12 @@ class ContextCodec(_LayeredCodec):
         Per item the transforms run exactly as in `compress`; the factorised z tables are built and copied once per
         call.  `table_budget_bytes` cuts the list into chunks, consecutive runs of whole items whose y tables
         (rows * M * (2 y_W + 2) * 4 bytes) fit the budget together, an item above it alone (`table_chunks`); a chunk
-        is one pass of `_compress_chunk`, and chunking changes no byte.  Everything the host can refuse is refused
-        before the device is touched."""
+        is one pass of `_compress_chunk`, and chunking changes no byte.  `quality` (a rate-level model): one number for
+        all items or one per item.  Everything the host can refuse is refused before the device is touched."""
         xs = list(xs)
         names = [f"item {i}" for i in range(len(xs))] if names is None else list(names)
         self._refuse_items(xs, names)
+        qs = self._qualities(quality, len(xs))
         if not xs:
             return []
         M = self.model.M
@@ -1654,10 +1710,10 @@ class ContextCodec(_LayeredCodec):
         zt = factorized_tables(self.model.factorized_entropy_model, self.z_lo, self.z_S).cpu().numpy().view(np.uint32)
         out = []
         for first, end in table_chunks(costs, int(table_budget_bytes)):
-            out += self._compress_chunk(xs[first:end], zt, names[first:end])
+            out += self._compress_chunk(xs[first:end], zt, names[first:end], qs[first:end])
         return out
 
-    def _compress_chunk(self, xs, zt: np.ndarray, names) -> List[Dict]:
+    def _compress_chunk(self, xs, zt: np.ndarray, names, qs) -> List[Dict]:
         """One pass of `compress_many`.  After every item's transforms: all y_in and psi planes in two flat buffers
         (every item on a multiple of 4 floats, plain NHWC planes), ONE `lic_ctx_gather_ragged` over every pixel of
         every image (rows image-major, raster order inside an image), ONE `_params_at` over all rows, ONE
@@ -1669,10 +1725,10 @@ class ContextCodec(_LayeredCodec):
         m, G, R = self.model, self.groups, self.slice_rows
         M, dev = m.M, xs[0].device
         outs, psis, sums = [], [], []
-        for x in xs:
-            out = m.analysis_hyperprior(x, training=False)
+        for x, q in zip(xs, qs):
+            out = m.analysis_hyperprior(x, training=False, quality=q)
             outs.append((out["y_in"].contiguous(), out["z_in"], self._context_plane(out["y_in"])))
-            psis.append(m.hyper_decoder(out["z_in"]).float())
+            psis.append(self._hyper_synthesis(out["z_in"], q).float())
             sums.append(out["logp_y"].double().sum() + out["logp_z"].double().sum())
         owner = [(i, b) for i, (y_in, _, _) in enumerate(outs) for b in range(y_in.shape[0])]
         name = lambda im: f"{names[owner[im][0]]}: image {owner[im][1]}"
@@ -1719,16 +1775,21 @@ class ContextCodec(_LayeredCodec):
             B, _, h, w = y_in.shape
             row0, cut = int(plan.images[img, 0]), slice(img * G, (img + B) * G)
             strings = self._optional_keys(zes[cut]) if zes is not None else self._optional_keys()
+            strings.update(self._quality_key(qs[i]))
             res.append(self._compressed(x, dict(strings, z=zs[cut] if zes is not None else zs[i]), streams[cut], escs[cut],
                                         h_sym[row0:row0 + B * h * w], h_sums[i], y_in, z_in))
             img += B
         return res
 
     @torch.no_grad()
-    def decompress(self, strings: Dict, shape, z_shape) -> Dict:
+    def decompress(self, strings: Dict, shape, z_shape, quality: float = None) -> Dict:
+        """`quality` (a rate-level model): the quality the strings were coded at; default: strings["quality"]"""
         m = self.model
         B, M, h, w = shape
         self._refuse_other_schedule(strings)
+        if quality is not None:
+            strings = dict(strings, quality=quality)
+        strings = self._with_quality(strings)
         dev = next(m.parameters()).device
         z_coder, staged = _z_coder_of(strings), None
         if z_coder == "rans":
@@ -1742,7 +1803,7 @@ class ContextCodec(_LayeredCodec):
         else:
             z_hat = LatentCodec(m, self.z_lo, self.z_S, self.y_W).decompress_z(strings["z"], z_shape)
         z_hat = z_hat.contiguous(memory_format=torch.channels_last)
-        psi = m.hyper_decoder(z_hat).float()
+        psi = self._hyper_synthesis(z_hat, strings.get("quality")).float()
         p = self.pad
         # decoded latents, pixel-major, inside a zero frame
         ypad = torch.zeros((B, h + 2 * p, w + 2 * p, M), device=dev, dtype=torch.float32)
@@ -1801,8 +1862,13 @@ class ContextCodec(_LayeredCodec):
             got = ypad[:, p:p + h, p:p + w, :].reshape(B, h * w * M).round().to(torch.int32).cpu().numpy()
             _check_latents(got.reshape(B, h, w, M), 0, M, strings["y_crc32"])
         y_hat = ypad[:, p:p + h, p:p + w, :].permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last)
-        x_hat = m.decoder(y_hat)
+        x_hat = m.synthesis(y_hat, strings.get("quality"))
         return {"x_hat": x_hat, "y_hat": y_hat, "z_hat": z_hat}
+
+    def _with_quality(self, strings: Dict) -> Dict:
+        """the strings with their quality as this codec's model takes it (`_quality`'s refusals)"""
+        q = self._quality(strings.get("quality"))
+        return strings if q is None else dict(strings, quality=q)
 
     # ---- many bitstreams in one step loop -------------------------------------------------------
     @torch.no_grad()
@@ -1818,10 +1884,14 @@ class ContextCodec(_LayeredCodec):
         rANS-coded (`strings["z_coder"]`; those decode together).  Everything the host can refuse is refused before the
         device is touched."""
         items = list(items)
-        for i, (strings, _, _) in enumerate(items):
-            if strings.get("coder", "range") != "rans":
-                raise CodecError(f"{f'item {i}' if names is None else names[i]}: only streams of the 'rans' coder decode "
-                                 "together (the range coder's loop waits for the host at every step)")
+        for i, (strings, shape, z_shape) in enumerate(items):
+            try:
+                if strings.get("coder", "range") != "rans":
+                    raise CodecError("only streams of the 'rans' coder decode together (the range coder's loop waits for "
+                                     "the host at every step)")
+                items[i] = (self._with_quality(strings), shape, z_shape)
+            except CodecError as err:
+                raise CodecError(f"{f'item {i}' if names is None else names[i]}: {err}") from None
         return self._decompress_many(items, self.layers, z_windows, names)
 
     def _item_streams(self, strings, shape, z_shape, G: int, nlayers: int):
@@ -1842,7 +1912,7 @@ class ContextCodec(_LayeredCodec):
     # ---- self-describing container: one byte string per batch, any image size ---------------------
     @torch.no_grad()
     def compress_image(self, x: torch.Tensor, mode: str = "replicate", align: str = "topleft",
-                       coder: str = None) -> bytes:
+                       coder: str = None, quality: float = None) -> bytes:
         """x [B,3,H,W] of ANY size -> one byte string that `decompress_image` decodes by itself.  The image is padded
         to multiples of 64 (`functional.pad_to_multiple`) and the payload is exactly what `compress` produces for
         the padded tensor; the header (bitstream.py) carries everything the decoder needs to rebuild the
@@ -1850,19 +1920,29 @@ class ContextCodec(_LayeredCodec):
         included, per ORIGINAL pixel.  `coder`: None = this codec's own; the container is the one `_FORMATS` has for
         (coder, groups > 1): LICBITS1 for "range", LICBITS2 for "rans", LICBITS3 for "rans" with groups -- and LICBITS4
         for a codec with slices, whatever its groups, LICBITS5 for one with z_coder="rans", whatever its groups and
-        slices.  Slices, groups and z_coder do not follow to another coder."""
+        slices.  Slices, groups and z_coder do not follow to another coder.  A rate-level model: coded at `quality`, and
+        the container sits in a LICRATE1 envelope that carries it."""
         if x.dim() != 4:
             raise CodecError("expected a [B,3,H,W] tensor")
+        quality = self._quality(quality)
         if coder is not None and coder != self.coder:
             # encoder and groups go with the coder they belong to: only a coder that has a grouped format ("rans")
             # has a device encoder
             enc, G = (self.encoder, self.groups) if (coder, True) in _FORMATS else ("host", 1)
-            return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder, enc, G).compress_image(x, mode, align)
+            return ContextCodec(self.model, self.z_lo, self.z_S, self.y_W, coder, enc, G).compress_image(
+                x, mode, align, quality=quality)
         self._refuse_checkerboard_without_zrans()
-        return self._pack_padded(x, self.compress(F_.pad_to_multiple(x, 64, mode, align))["strings"], align)
+        return self._pack_padded(x, self.compress(F_.pad_to_multiple(x, 64, mode, align), quality)["strings"], align)
 
     def _pack_image(self, s: Dict, B: int, H: int, W: int, top: int, left: int) -> bytes:
-        """the container of `compress_image` around the strings `compress` gave for the padded image"""
+        """the container of `compress_image` around the strings `compress` gave for the padded image; for a rate-level
+        model inside the envelope that carries the quality"""
+        inner = self._pack_container(s, B, H, W, top, left)
+        if self.rate_levels is None:
+            return inner
+        return pack_rate_envelope(inner, s["quality"], self.rate_levels)
+
+    def _pack_container(self, s: Dict, B: int, H: int, W: int, top: int, left: int) -> bytes:
         head = {"family": self._family(), "M": self.model.M, "K": self.model.K, "z_lo": self.z_lo, "z_S": self.z_S,
                 "y_W": self.y_W, "B": B, "H": H, "W": W, "top": top, "left": left}
         if self.schedule == "checkerboard":
@@ -1904,7 +1984,7 @@ class ContextCodec(_LayeredCodec):
 
     @torch.no_grad()
     def compress_images(self, images: Sequence[torch.Tensor], mode: str = "replicate", align: str = "topleft",
-                        table_budget_bytes: int = 2 << 30) -> List[bytes]:
+                        table_budget_bytes: int = 2 << 30, quality=None) -> List[bytes]:
         """Many images of any sizes in one encode pass: entry i is byte for byte `compress_image(images[i], mode,
         align)`, the container of this codec's groups, slice_rows and z_coder (LICBITS2 / 3 / 4 / 5).  All images of a
         chunk share
@@ -1912,14 +1992,48 @@ class ContextCodec(_LayeredCodec):
         (`compress_many`, which also says what `table_budget_bytes` does).  Needs coder="rans", encoder="device".
         Raises CodecError before any GPU work, every message naming its entry ("image i: ..."): a codec with another
         coder or encoder, an entry that is not a [B,3,H,W] tensor, a tensor that is not on the GPU.  An empty list
-        gives an empty list."""
+        gives an empty list.  `quality` (a rate-level model): one number for all images or a list, one per image."""
         images = list(images)
         names = [f"image {i}" for i in range(len(images))]
         self._refuse_items(images, names, self._refuse_checkerboard_without_zrans)
+        qs = self._qualities(quality, len(images), "image")
         if not images:
             return []
-        rs = self.compress_many([F_.pad_to_multiple(x, 64, mode, align) for x in images], table_budget_bytes, names)
+        rs = self.compress_many([F_.pad_to_multiple(x, 64, mode, align) for x in images], table_budget_bytes, names, qs)
         return [self._pack_padded(x, r["strings"], align) for x, r in zip(images, rs)]
+
+    @torch.no_grad()
+    def compress_image_to(self, x: torch.Tensor, max_bytes: int, steps: int = 16, **kw):
+        """-> (blob, quality): `compress_image(x, quality=q, **kw)` at the highest q of the grid k (Q-1) / steps,
+        k = 0..steps, whose blob has at most `max_bytes` bytes (a rate-level model).  Bisection over k, which assumes
+        that the size grows with q; the blob returned is measured, and if it does not fit the grid is walked down from
+        it until one does.  CodecError when not even q = 0 fits."""
+        Q = self.rate_levels
+        if Q is None:
+            raise CodecError("compress_image_to picks a quality: this codec's model has no rate levels")
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 1:
+            raise CodecError(f"steps = {steps!r}: expected an integer >= 1")
+        blobs = {}
+
+        def at(k):
+            if k not in blobs:
+                blobs[k] = self.compress_image(x, quality=k * (Q - 1) / steps, **kw)
+            return blobs[k]
+
+        lo, hi = 0, int(steps)                    # the bisection keeps: grid point lo is the answer so far
+        if len(at(hi)) <= max_bytes:
+            lo = hi
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if len(at(mid)) <= max_bytes:
+                lo = mid
+            else:
+                hi = mid
+        while lo > 0 and len(at(lo)) > max_bytes:  # (the size did not grow with q after all)
+            lo -= 1
+        if len(at(lo)) > max_bytes:
+            raise CodecError(f"the image takes {len(at(0))} bytes at quality 0: it does not fit max_bytes = {max_bytes}")
+        return at(lo), quality_of(at(lo))
 
     @torch.no_grad()
     def decompress_image(self, data: bytes) -> torch.Tensor:
@@ -1937,9 +2051,15 @@ class ContextCodec(_LayeredCodec):
     def _open_blob(self, data: bytes):
         """`decompress_image`'s host half -> (header, the strings `decompress` takes).  Its refusals, in order: the
         container reader's (`_unpack`), a window the rANS decoder does not take, a model that is not this one."""
+        quality = None
+        if self.rate_levels is not None:
+            quality, _, data = unpack_rate_envelope(data, self.rate_levels)
+        elif is_rate_envelope(data):
+            raise CodecError("a LICRATE1 rate envelope: this codec's model has no rate levels (rate_levels=None) and reads "
+                             "bare bitstreams only")
         fmt = _format_of_magic(data[:8])                                      # an unknown magic: LICBITS1's reader says so
         head, z_bytes, y_streams, y_esc, y_crc, G = _unpack(fmt, data)
-        strings = {"y": y_streams, "z": z_bytes, "y_crc32": y_crc}
+        strings = {"y": y_streams, "z": z_bytes, "y_crc32": y_crc, **self._quality_key(quality)}
         if (fmt == _FORMAT_CHECKER) != (self.schedule == "checkerboard"):
             raise CodecError(f"schedule mismatch: a {bytes(data[:8]).decode()} bitstream is coded in the "
                              f"{'checkerboard' if fmt == _FORMAT_CHECKER else 'raster'} schedule, this codec's context "
@@ -2025,6 +2145,9 @@ class ScalableCodec(_LayeredCodec):
     def __init__(self, model, z_lo: int = -64, z_S: int = 129, y_W: int = 32, encoder: str = "device", groups: int = 1,
                  slice_rows: int = None):
         from .models import ScalableImageCoding
+        if getattr(model, "rate_levels", None) is not None:
+            raise CodecError(f"ScalableCodec takes no rate-level model (rate_levels={model.rate_levels}): the layered "
+                             "bitstream has one rate; ContextCodec codes a rate-level model")
         if not isinstance(model, ScalableImageCoding):
             raise CodecError(f"ScalableCodec codes a ScalableImageCoding model, not a {type(model).__name__}: "
                              "the one-layer models have ContextCodec")

@@ -1025,6 +1025,120 @@ def quantize_anchor(v, u=None, training=True, cast_in=False, cast_out=False):
 
 
 # ------------------------------------------------------------------------------------------
+# gain units of the variable-rate model: per-channel scale + quantisation surrogate in one launch
+# ------------------------------------------------------------------------------------------
+_GAIN_CASTS = [None, None, None]   # bf16 of vg, of the result, of its anchors, of the _GainQuantizeFn.forward that just ran
+
+
+def _gain_rows(s: torch.Tensor, B: int, Cc: int):
+    """the scale `s` [1 or B][C] as the kernels read it: (contiguous tensor, s_stride)"""
+    if s.dim() != 2 or s.shape[1] != Cc or s.shape[0] not in (1, B):
+        raise L.LicError(f"a gain of shape [1 or {B}][{Cc}] expected, got {tuple(s.shape)}")
+    return s.contiguous(), (0 if s.shape[0] == 1 else Cc)
+
+
+def _gain_backward(vh, sh, s_stride, s_rows, d_vg, d_out, d_anchor, need_dv, need_ds):
+    """lic_gain_bwd: -> (dv NCHW view, ds shaped like the scale); the gradients are NCHW-logical or None"""
+    gs = [None if g is None else _nhwc(g) for g in (d_vg, d_out, d_anchor)]
+    _require_cuda(*gs)
+    B, h, w, Cc = vh.shape
+    dv = torch.empty_like(vh)
+    ds = torch.empty((B, Cc), device=vh.device, dtype=torch.float32)
+    nbytes = L.load().lic_gain_bwd_workspace_bytes(B, h * w, Cc)
+    ws = torch.empty(nbytes // 4, device=vh.device, dtype=torch.float32)
+    L.check(L.load().lic_gain_bwd(_ptr(vh), _ptr(sh), s_stride, _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(dv), _ptr(ds),
+                                  B, h, w, Cc, _ptr(ws), nbytes, _stream()), "lic_gain_bwd")
+    if s_rows == 1:
+        ds = ds.sum(0, keepdim=True) if B > 1 else ds
+    return (_nchw_view(dv) if need_dv else None), (ds if need_ds else None)
+
+
+class _GainQuantizeFn(torch.autograd.Function):
+    """(vg, out[, anchor(out)]) = lic_gain_quantize(v, u, s): vg = v * s, out = vg + (u - 0.5) (training) or rint(vg).
+    Backward, one lic_gain_bwd: through vg always; through out and its anchors as `_QuantizeFn` / `_QuantizeAnchorFn`
+    (identity for the noise, zero for rint)."""
+
+    @staticmethod
+    def forward(ctx, v, u, s, training, anchor, cast_in, cast_out):
+        _require_cuda(v, u, s)
+        vh = _nhwc(v)
+        uh = None if (u is None or not training) else _nhwc(u)
+        B, h, w, Cc = vh.shape
+        sh, s_stride = _gain_rows(s, B, Cc)
+        vg, out = torch.empty_like(vh), torch.empty_like(vh)
+        anc = torch.empty_like(vh) if anchor else None
+        g16 = torch.empty_like(vh, dtype=torch.bfloat16) if cast_in else None
+        o16 = torch.empty_like(vh, dtype=torch.bfloat16) if cast_out else None
+        a16 = torch.empty_like(vh, dtype=torch.bfloat16) if (cast_out and anchor) else None
+        L.check(L.load().lic_gain_quantize(_ptr(vh), _ptr(uh), _ptr(sh), s_stride, _ptr(vg), _ptr(out), _ptr(anc), _ptr(g16),
+                                           _ptr(o16), _ptr(a16), B, h, w, Cc, L.GAIN_NOISE if training else L.GAIN_ROUND,
+                                           _stream()), "lic_gain_quantize")
+        _GAIN_CASTS[:] = [g16, o16, a16]
+        ctx.training, ctx.s_stride, ctx.s_rows = training, s_stride, s.shape[0]
+        ctx.save_for_backward(vh, sh)
+        ctx.set_materialize_grads(False)
+        if anchor:
+            return _nchw_view(vg), _nchw_view(out), _nchw_view(anc)
+        return _nchw_view(vg), _nchw_view(out)
+
+    @staticmethod
+    def backward(ctx, d_vg, d_out, d_anchor=None):
+        if not ctx.training:
+            d_out = d_anchor = None
+        if d_vg is None and d_out is None and d_anchor is None:
+            return (None,) * 7
+        vh, sh = ctx.saved_tensors
+        dv, ds = _gain_backward(vh, sh, ctx.s_stride, ctx.s_rows, d_vg, d_out, d_anchor, ctx.needs_input_grad[0],
+                                ctx.needs_input_grad[2])
+        return dv, None, ds, None, None, None, None
+
+
+def gain_quantize(v, u, s, training, anchor=False, cast_in=False, cast_out=False):
+    """-> (vg, out) or, with `anchor`, (vg, out, anchor(out)): the gained latent vg = v * s (`s` [1 or B][C], one row for
+    the batch or one per image), its quantisation surrogate and that one's anchors out of one launch.  `cast_in` attaches
+    bf16(vg) to vg, `cast_out` bf16 of the other results to them (attach_bf16)."""
+    res = _GainQuantizeFn.apply(v, u, s, training, anchor, cast_in, cast_out)
+    for t, t16 in zip(res, _GAIN_CASTS):
+        attach_bf16(t, t16)
+    _GAIN_CASTS[:] = [None, None, None]
+    return res
+
+
+class _ChannelScaleFn(torch.autograd.Function):
+    """vg = v * s alone (lic_gain_quantize, LIC_GAIN_SCALE): the inverse gain behind a quantiser"""
+
+    @staticmethod
+    def forward(ctx, v, s, cast_out):
+        _require_cuda(v, s)
+        vh = _nhwc(v)
+        B, h, w, Cc = vh.shape
+        sh, s_stride = _gain_rows(s, B, Cc)
+        vg = torch.empty_like(vh)
+        g16 = torch.empty_like(vh, dtype=torch.bfloat16) if cast_out else None
+        L.check(L.load().lic_gain_quantize(_ptr(vh), None, _ptr(sh), s_stride, _ptr(vg), None, None, _ptr(g16), None, None,
+                                           B, h, w, Cc, L.GAIN_SCALE, _stream()), "lic_gain_quantize")
+        _GAIN_CASTS[0] = g16
+        ctx.s_stride, ctx.s_rows = s_stride, s.shape[0]
+        ctx.save_for_backward(vh, sh)
+        return _nchw_view(vg)
+
+    @staticmethod
+    def backward(ctx, d_vg):
+        vh, sh = ctx.saved_tensors
+        dv, ds = _gain_backward(vh, sh, ctx.s_stride, ctx.s_rows, d_vg, None, None, ctx.needs_input_grad[0],
+                                ctx.needs_input_grad[1])
+        return dv, ds, None
+
+
+def channel_scale(v, s, cast_out=False):
+    """v * s per channel (`s` [1 or B][C]); `cast_out` attaches the bf16 copy of the result to it"""
+    res = _ChannelScaleFn.apply(v, s, cast_out)
+    attach_bf16(res, _GAIN_CASTS[0])
+    _GAIN_CASTS[0] = None
+    return res
+
+
+# ------------------------------------------------------------------------------------------
 # entropy-parameter activations + conditional likelihood
 # ------------------------------------------------------------------------------------------
 class _EntropyParamsActFn(torch.autograd.Function):

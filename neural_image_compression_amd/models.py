@@ -4,6 +4,7 @@ three one-line repairs that let it run, listed in its docstring."""
 from __future__ import annotations
 
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -18,8 +19,10 @@ class _HyperpriorContextModel(nn.Module):
     _stacks = None  # (Encoder, Decoder, HyperEncoder, HyperDecoder)
     context = "raster"
 
-    def __init__(self, latent_channels: int = 192, K: int = 1, context: str = "raster"):
-        """`context`: "raster" (the reference's type-A masked convolution over y_in) or "checkerboard" (He et al. 2021,
+    def __init__(self, latent_channels: int = 192, K: int = 1, context: str = "raster", rate_levels: int = None):
+        """`rate_levels` = Q >= 2: a variable-rate model (gain units, DESIGN 8(f).5) with Q trained quality levels;
+        `forward(x, quality=q)` then takes any real q in [0, Q-1].  None: no gain units, no parameters of theirs.
+        `context`: "raster" (the reference's type-A masked convolution over y_in) or "checkerboard" (He et al. 2021,
         DESIGN 8(f).2: phi = masked_conv(anchor(y_in)) with the checkerboard mask; anchors -- latent pixels with i + j
         even -- get phi = bias and are coded from the hyperprior alone, the others from the anchors around them, so a
         codec decodes in two steps).  Same modules and state-dict keys either way."""
@@ -46,6 +49,76 @@ class _HyperpriorContextModel(nn.Module):
                                           mask_type="checkerboard" if context == "checkerboard" else "A")
         self.entropy_parameters = EntropyParameters(latent_channels=self.M, hyper_latent_channels=self.H,
                                                     K=self.K)
+        if rate_levels is not None and (not isinstance(rate_levels, int) or isinstance(rate_levels, bool)
+                                        or rate_levels < 2):
+            raise ValueError(f"rate_levels must be None or an int >= 2, got {rate_levels!r}")
+        self.rate_levels = rate_levels
+        if rate_levels is not None:
+            # log of the gain in front of each quantiser and of the inverse gain behind it, one row per level
+            for name in self.GAIN_TABLES:
+                setattr(self, name, nn.Parameter(torch.zeros(rate_levels, self.M)))
+
+    def check_quality(self, quality, batch: int = None):
+        """`quality` as the model takes it: None for a plain model; a float (the whole batch) or a [B] tensor, every
+        value in [0, Q-1], for a rate-level model.  -> None, or a host list of 1 or B floats.  ValueError otherwise."""
+        if self.rate_levels is None:
+            if quality is not None:
+                raise ValueError("this model has no rate levels (rate_levels=None): it takes no `quality`")
+            return None
+        if quality is None:
+            raise ValueError(f"a model with rate_levels={self.rate_levels} needs `quality` in [0, {self.rate_levels - 1}]")
+        if torch.is_tensor(quality):
+            if quality.dim() != 1 or (batch is not None and quality.shape[0] != batch):
+                raise ValueError(f"`quality` must be a float or a tensor [B], got shape {tuple(quality.shape)}")
+            qs = [float(v) for v in quality.tolist()]
+        else:
+            qs = [float(quality)]
+        for q in qs:
+            if not 0.0 <= q <= self.rate_levels - 1:   # (a NaN fails both comparisons)
+                raise ValueError(f"quality {q} outside [0, {self.rate_levels - 1}]")
+        return qs
+
+    GAIN_TABLES = ("log_gain_y", "log_inv_gain_y", "log_gain_z", "log_inv_gain_z")
+
+    def gain_rows(self, qs, *tables):
+        """the rows [len(qs)][M] of each of `tables` ([Q][M] log gains) at the qualities `qs` (check_quality's list):
+        geometric interpolation between the neighbouring levels, exp((1 - l) * log_g[i] + l * log_g[i + 1]) with
+        i = floor(q) clamped to Q-2 and l = q - i, both weights float32.  Plain torch ops, the same handful for any number
+        of tables (they are stacked), and for one quality nothing but slices: autograd carries the rows' gradients back
+        to the tables.  One quality and a constant list give the same bits."""
+        T = tables[0].unsqueeze(0) if len(tables) == 1 else torch.stack(tables)           # [k][Q][M]
+        idx = [min(int(q), self.rate_levels - 2) for q in qs]
+        lf = [np.float32(q - i) for q, i in zip(qs, idx)]
+        if len(qs) == 1:
+            i, l = idx[0], lf[0]
+            rows = torch.exp(float(np.float32(1) - l) * T[:, i:i + 1] + float(l) * T[:, i + 1:i + 2])
+        else:
+            it = torch.tensor(idx, device=T.device, dtype=torch.long)
+            lt = torch.tensor(lf, device=T.device, dtype=T.dtype).unsqueeze(1)
+            rows = torch.exp((1.0 - lt) * T[:, it] + lt * T[:, it + 1])
+        return rows.unbind(0)
+
+    def _gains(self, qs):
+        """all four rows of one forward, by table name, from one pass of `gain_rows`"""
+        return dict(zip(self.GAIN_TABLES, self.gain_rows(qs, *(getattr(self, n) for n in self.GAIN_TABLES))))
+
+    def hyper_synthesis(self, z_in: torch.Tensor, quality=None, _gains=None, **kw):
+        """psi = hyper_decoder(z_in * inverse gain of z at `quality`); the bare module call for a plain model"""
+        qs = self.check_quality(quality, z_in.shape[0])
+        if qs is None:
+            return self.hyper_decoder(z_in, **kw)
+        inv = _gains["log_inv_gain_z"] if _gains is not None else self.gain_rows(qs, self.log_inv_gain_z)[0]
+        lat16 = z_in.is_cuda and self.hyper_decoder.precision == "bf16"
+        return self.hyper_decoder(F_.channel_scale(z_in, inv, cast_out=lat16), **kw)
+
+    def synthesis(self, y_in: torch.Tensor, quality=None, _gains=None):
+        """x_hat = decoder(y_in * inverse gain of y at `quality`); the bare module call for a plain model"""
+        qs = self.check_quality(quality, y_in.shape[0])
+        if qs is None:
+            return self.decoder(y_in)
+        inv = _gains["log_inv_gain_y"] if _gains is not None else self.gain_rows(qs, self.log_inv_gain_y)[0]
+        dec16 = y_in.is_cuda and self.decoder.precision == "bf16"
+        return self.decoder(F_.channel_scale(y_in, inv, cast_out=dec16))
 
     def set_precision(self, precision: str = "fp32", latent: str = None):
         """"fp32" (default, the reference's arithmetic) or "bf16": bf16 activation storage and bf16 MFMA with
@@ -64,11 +137,18 @@ class _HyperpriorContextModel(nn.Module):
         return self
 
     def analysis_hyperprior(self, x: torch.Tensor, training: bool = True, noise=None, with_packed_params=False,
-                            _fork=None):
+                            _fork=None, quality=None, _gains=None):
         """Everything of `forward` except the synthesis transform (Models.py:49-97): the scope the
         north star quotes its roofline target on.  Returns the out-dict without 'x_hat'
         (`with_packed_params`: plus '_act', the activated entropy parameters as the one packed tensor
-        the likelihood / coder-table kernels read).  `_fork(y_in)` is called as soon as y_in exists."""
+        the likelihood / coder-table kernels read).  `_fork(y_in)` is called as soon as y_in exists.
+        A rate-level model (`quality`): y and z are scaled by their gains in the quantisation launches --
+        'y' and 'z' of the out-dict are the gained latents, which is what the hyper-encoder reads -- and z_in by its
+        inverse gain in front of the hyper-decoder; the context model, the entropy parameters and both likelihoods see
+        y_in / z_in as ever."""
+        qs = self.check_quality(quality, x.shape[0])
+        if qs is not None and _gains is None:
+            _gains = self._gains(qs)        # (`forward` hands in the rows it made: one pass of torch ops per step)
         if x.shape[2] % 64 or x.shape[3] % 64:
             raise RuntimeError("H and W must be multiples of 64 (phi/psi shapes must agree, Models.py:73)")
         if self.use_step_prep and x.is_cuda:
@@ -102,7 +182,15 @@ class _HyperpriorContextModel(nn.Module):
                 uz, uy = noise
         else:
             uz = uy = None
-        if self.context == "checkerboard":
+        if qs is not None:
+            # (y_in's bf16 copy serves the context model alone: the decoder reads the inverse-gained y_in)
+            if self.context == "checkerboard":
+                y, y_in, y_ctx = F_.gain_quantize(y, uy, _gains["log_gain_y"], training, anchor=True, cast_in=lat16,
+                                                  cast_out=lat16)
+            else:
+                y, y_in = F_.gain_quantize(y, uy, _gains["log_gain_y"], training, cast_in=lat16, cast_out=lat16)
+                y_ctx = y_in
+        elif self.context == "checkerboard":
             # the context model convolves anchor(y_in); decoder and likelihood keep y_in (one launch writes both)
             y_in, y_ctx = F_.quantize_anchor(y, uy, training, cast_in=lat16, cast_out=dec16 or lat16)
         else:
@@ -110,7 +198,10 @@ class _HyperpriorContextModel(nn.Module):
         if _fork is not None:
             _fork(y_in)
         z = self.hyper_encoder(y)
-        z_in = F_.quantize(z, uz, True, cast_out=lat16) if training else F_.quantize(z, None, False, cast_out=lat16)
+        if qs is not None:
+            z, z_in = F_.gain_quantize(z, uz, _gains["log_gain_z"], training)
+        else:
+            z_in = F_.quantize(z, uz, True, cast_out=lat16) if training else F_.quantize(z, None, False, cast_out=lat16)
         pz_side = None
         if _fork is not None and x.is_cuda and self.overlap_branches and F_.PLAN_RECORDING:
             # the factorised likelihood of z_in depends on nothing else of the latent side: it goes behind the decoder on the
@@ -134,11 +225,11 @@ class _HyperpriorContextModel(nn.Module):
             c_psi = self.hyper_decoder.net[-1].out_channels
             comb = torch.empty((Bn, hh, ww, c_phi + c_psi), device=x.device,
                                dtype=torch.float32 if both[0] == "fp32" else torch.bfloat16)
-            psi = self.hyper_decoder(z_in, out=comb[..., c_phi:])
+            psi = self.hyper_synthesis(z_in, quality, _gains, out=comb[..., c_phi:])
             phi = self.context_model(y_ctx, out=comb[..., :c_phi])
             combined = F_.join_channels(phi, psi, comb)
         else:
-            psi = self.hyper_decoder(z_in)
+            psi = self.hyper_synthesis(z_in, quality, _gains)
             phi = self.context_model(y_ctx)
             combined = torch.cat([phi, psi], dim=1)  # (bf16 features: a 6 MB layout copy, phi first)
         act = self.entropy_parameters.packed(combined)
@@ -155,6 +246,8 @@ class _HyperpriorContextModel(nn.Module):
         out.update(params)
         if with_packed_params:
             out['_act'] = act
+        if qs is not None:
+            out['quality'] = quality
         return out
 
     # The synthesis transform depends only on y_in; the hyper / context / likelihood branch only on
@@ -189,12 +282,15 @@ class _HyperpriorContextModel(nn.Module):
             self._side_stream = torch.cuda.Stream(priority=-1)
         return self._side_stream
 
-    def forward(self, x: torch.Tensor, training: bool = True, noise=None):
+    def forward(self, x: torch.Tensor, training: bool = True, noise=None, quality=None):
         """`noise` (test hook, not in the reference): (u_z, u_y) uniform [0,1) tensors used instead
-        of torch.rand_like, in the reference's draw order (z first, Models.py:57-58)."""
+        of torch.rand_like, in the reference's draw order (z first, Models.py:57-58).  `quality`: required by a
+        rate-level model, a float for the whole batch or a tensor [B], in [0, rate_levels - 1]."""
+        qs = self.check_quality(quality, x.shape[0])
+        gains = None if qs is None else self._gains(qs)
         if not (self.overlap_branches and x.is_cuda):
-            out = self.analysis_hyperprior(x, training, noise)
-            return {'x_hat': self.decoder(out['y_in']), **out}
+            out = self.analysis_hyperprior(x, training, noise, quality=quality, _gains=gains)
+            return {'x_hat': self.synthesis(out['y_in'], quality, gains), **out}
         main = torch.cuda.current_stream()
         side = self.side_stream()
         box = {}
@@ -202,10 +298,10 @@ class _HyperpriorContextModel(nn.Module):
         def fork(y_in):
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                box['x_hat'] = self.decoder(y_in)
+                box['x_hat'] = self.synthesis(y_in, quality, gains)
             y_in.record_stream(side)
 
-        out = self.analysis_hyperprior(x, training, noise, _fork=fork)
+        out = self.analysis_hyperprior(x, training, noise, _fork=fork, quality=quality, _gains=gains)
         main.wait_stream(side)
         box['x_hat'].record_stream(main)
         return {'x_hat': box['x_hat'], **out}

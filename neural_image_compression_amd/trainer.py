@@ -20,11 +20,15 @@ Added to the reference's contract as trailing keyword arguments: `clip_max_norm`
 the moving average of the weights, swapped in for its duration.  Whenever the optimizer averages, the checkpoint
 holds the averaged model under one more key, `ema_state_dict`, which loaders of the reference's format ignore; the
 averages themselves travel in the optimizer's state dict.
+`rate_points=[(q, lambda), ...]` trains a rate-level model (models: rate_levels): every step draws one pair
+from a host generator seeded with `rate_seed`, runs the model at quality q and the loss at that lambda; the generator's
+state travels in the checkpoint (key `rate_rng`), and validation runs once per pair, logged under `val/q<i>/...`.
 """
 from __future__ import annotations
 
 import json
 import os
+import random
 from typing import Optional
 
 import torch
@@ -78,9 +82,24 @@ class Trainer:
                  scheduler=None, max_steps=10000, resume=False, log_interval=None, img_interval=None,
                  val_interval=None, log_dir="runs/experiment", checkpoint_path="./checkpoints/checkpoint.pth",
                  device="cuda", distributed: Optional[bool] = None, writer=None, step_plan: bool = False,
-                 clip_max_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_eval: bool = False):
+                 clip_max_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_eval: bool = False,
+                 rate_points=None, rate_seed: int = 0):
         if rd_loss is None:
             raise ValueError("You must provide a rate-distortion loss function (`rd_loss`)")
+        self.rate_points = None if rate_points is None else [(float(q), float(lam)) for q, lam in rate_points]
+        if self.rate_points is not None:
+            if not self.rate_points:
+                raise ValueError("rate_points must hold at least one (quality, lambda) pair")
+            if step_plan:
+                raise ValueError("rate_points with step_plan=True: the recorded step bakes one lambda and one quality in; "
+                                 "a rate-level model trains with the eager step")
+            if getattr(model, "rate_levels", None) is None:
+                raise ValueError("rate_points need a model with rate_levels")
+            for q, _ in self.rate_points:
+                model.check_quality(q)
+        # (the same seed on every rank of a data-parallel run: all ranks draw the same pair)
+        self._rate_rng = random.Random(rate_seed)
+        self.last_rate_point = None
         self.device = device
         self.model = model.to(device)
         self.optimizer, self.rd_loss, self.lambda_val = optimizer, rd_loss, lambda_val
@@ -137,6 +156,9 @@ class Trainer:
                  "scheduler": sched}
         if self._averages():
             state["ema_state_dict"] = self.optimizer.ema_state_dict(self.model)
+        if self.rate_points is not None:
+            version, words, gauss = self._rate_rng.getstate()
+            state["rate_rng"] = {"version": version, "words": list(words), "gauss": gauss}
         return state
 
     def _averages(self):
@@ -158,6 +180,9 @@ class Trainer:
         self.optimizer.load_state_dict(state["optimizer"])
         if self.scheduler is not None and state["scheduler"] is not None:
             self.scheduler.load_state_dict(state["scheduler"])
+        if self.rate_points is not None and state.get("rate_rng") is not None:
+            rng = state["rate_rng"]
+            self._rate_rng.setstate((rng["version"], tuple(rng["words"]), rng["gauss"]))
         self.step = state["step"]
         self.max_steps += self.step   # `max_steps` counts the steps of THIS run (Trainer.py:70)
         print(f"[trainer] resumed from {self.checkpoint_path} at step {self.step}")
@@ -206,8 +231,13 @@ class Trainer:
             if done is not None:
                 return done
         self.optimizer.zero_grad()
-        model_out = self.model(imgs)
-        results = self.rd_loss(model_out, imgs, self.lambda_val)
+        if self.rate_points is not None:
+            q, lam = self.last_rate_point = self._rate_rng.choice(self.rate_points)
+            model_out = self.model(imgs, quality=q)
+            results = self.rd_loss(model_out, imgs, lam)
+        else:
+            model_out = self.model(imgs)
+            results = self.rd_loss(model_out, imgs, self.lambda_val)
         results['loss'].backward()
         if self.reducer is not None:
             self.reducer.finish()
@@ -314,12 +344,19 @@ class Trainer:
         if self.ema_eval and self._averages() and not self.optimizer.swapped:
             with self.optimizer.ema_weights():
                 return self._validate()
+        if self.rate_points is not None:
+            # once per pair, each under its own tags; the scheduler sees the mean of the pairs' losses
+            losses = [self._validate_at(f"val/q{i}/", {"quality": q}, lam) for i, (q, lam) in enumerate(self.rate_points)]
+            return sum(losses) / len(losses)
+        return self._validate_at("validation/", {}, self.lambda_val)
+
+    def _validate_at(self, prefix, model_kw, lam):
         sums = [0.0, 0.0, 0.0]
         self.model.eval()
         with torch.no_grad():
             for imgs in self.val_loader:
                 imgs = imgs.to(self.device)
-                res = self.rd_loss(self.model(imgs, training=False), imgs, self.lambda_val)
+                res = self.rd_loss(self.model(imgs, training=False, **model_kw), imgs, lam)
                 for i, v in enumerate((res["loss"], res["bpp_total"], res["psnr"])):
                     sums[i] += float(v)
         self.model.train()
@@ -331,5 +368,5 @@ class Trainer:
         if self.writer is not None:
             # (tag spelling as in the reference, Trainer.py:162-164)
             for tag, v in zip(("validation_loss", "validation_bpp", "validation_pnsr"), means):
-                self.writer.add_scalar("validation/" + tag, v, self.step)
+                self.writer.add_scalar(prefix + tag, v, self.step)
         return means[0]
