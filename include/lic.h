@@ -278,6 +278,26 @@ size_t lic_gain_bwd_workspace_bytes(int32_t B, int64_t hw, int32_t C); /* 0 for 
 int lic_gain_bwd(const float* v, const float* s, int64_t s_stride, const float* d_vg, const float* d_out,
                  const float* d_anchor, float* dv, float* ds, int32_t B, int32_t h, int32_t w, int32_t C, void* workspace,
                  size_t workspace_bytes, lic_stream_t stream);
+/* The gain rows of a batch from qualities that live on the device: one launch, nothing read back, nothing checked on the
+ * host.  q: float[B]; tables: float[k][Q][M], the k stacked log-gain tables (1 <= k <= LIC_GAIN_ROWS_MAX_TABLES, Q >= 2);
+ * rows: float[k][B][M].  Per image: qc = min(max(q, 0), Q-1), a NaN counting as 0 -- the clamp is this path's contract,
+ * a quality outside [0, Q-1] is the nearest end, not an error --, i = min((int)floor(qc), Q-2), l = qc - i.  Per element
+ *   rows = expf(fl32(fl32(fl32(1 - l) * T[i]) + fl32(l * T[i+1]))),
+ * no product contracted with the sum.  lvl: int32[B] followed by float[B]; image b's i and l are written there for
+ * lic_gain_rows_bwd.
+ *   NULL q / tables / rows / lvl, k outside 1..4, Q < 2, M < 1, B < 1: LIC_ERR_INVALID; k * M * max(B, Q) >= 2^31:
+ *   LIC_ERR_UNSUPPORTED.  Nothing launched then.  No allocation, no synchronisation, graph-capturable. */
+#define LIC_GAIN_ROWS_MAX_TABLES 4
+int lic_gain_rows_fwd(const float* q, const float* tables, float* rows, void* lvl, int32_t k, int32_t Q, int32_t M, int32_t B,
+                      lic_stream_t stream);
+/* The tables' gradient.  d_tables[t][j][c] (float[k][Q][M], every element written) is a running fp32 sum from zero over
+ * b = 0, 1, ..., B-1: when i_b == j it takes fl32(fl32(fl32(1 - l_b) * rows[t][b][c]) * d_rows_t[b][c]), then, when
+ * i_b + 1 == j, fl32(fl32(l_b * rows[t][b][c]) * d_rows_t[b][c]).  One thread per element, no atomics, nothing contracted:
+ * the same bits on every run, exact zeros for a level no image touches.  d_rows0..3: float[B][M] each, the gradient of
+ * table t's rows; NULL = none, that table's slice is zeros; those at index >= k must be NULL.  lvl, rows: as
+ * lic_gain_rows_fwd left them.  Errors and limits as lic_gain_rows_fwd. */
+int lic_gain_rows_bwd(const void* lvl, const float* rows, const float* d_rows0, const float* d_rows1, const float* d_rows2,
+                      const float* d_rows3, float* d_tables, int32_t k, int32_t Q, int32_t M, int32_t B, lic_stream_t stream);
 
 /* ---- entropy models (NHWC, P = B*h*w pixels) ------------------------------------------------ */
 /* ParametersModels.py:43-64.  raw/out rows hold G*K*M channels (G = 2 if K == 1 else 3):
@@ -325,6 +345,22 @@ int lic_rd_loss_fwd(const float* logp_y, int64_t ny, const float* logp_z, int64_
 int lic_rd_loss_bwd(const float* x_hat, const float* x, int64_t ny, int64_t nz, int64_t nx,
                     int32_t B, int64_t num_pixels, float lambda_rd, const float* gl, float* dlogp_y,
                     float* dlogp_z, float* dx_hat, lic_stream_t stream);
+/* The same loss with one lambda per image, read from device memory (lambda_img: float[B]), so that a captured launch
+ * serves any lambdas.  Forward: the launches, the workspace and slots 1..8 and 16.. of lic_rd_loss_fwd;
+ *   out[9] = (float)(sum_b (double)lambda_b * 65025.0 * (double)mse_b / B), the distortion term, summed as `mse` is;
+ *   out[0] = fl32(out[3] + out[9]);  out[10..15] = 0.
+ * Backward: dlogp_y, dlogp_z as lic_rd_loss_bwd; dx_hat of image b = (x_hat - x) * (gl[0] * kx_b) with
+ *   kx_b = fl32(fl32(fl32(lambda_b * 65025f) * 2f) / fl32((float)nx * (float)B)),
+ * lic_rd_loss_bwd's host expression evaluated on the device with nothing contracted: with all lambdas equal the three
+ * gradients are that entry's bytes.  One launch; 16-byte pieces when nx % 4 == 0 and x_hat, x, dx_hat are 16-byte
+ * aligned, single floats otherwise, the same bytes either way.
+ *   NULL pointers, non-positive extents: LIC_ERR_INVALID.  No allocation, no synchronisation, graph-capturable. */
+int lic_rd_loss_fwd_lam(const float* logp_y, int64_t ny, const float* logp_z, int64_t nz, const float* x_hat, const float* x,
+                        int64_t nx, int32_t B, int64_t num_pixels, const float* lambda_img, float* out, void* workspace,
+                        size_t workspace_bytes, lic_stream_t stream);
+int lic_rd_loss_bwd_lam(const float* x_hat, const float* x, int64_t ny, int64_t nz, int64_t nx, int32_t B,
+                        int64_t num_pixels, const float* lambda_img, const float* gl, float* dlogp_y, float* dlogp_z,
+                        float* dx_hat, lic_stream_t stream);
 
 /* ---- bf16-storage variants (BASELINE config 3) --------------------------------------------------
  * Activations / auxiliaries are bf16 NHWC (pitches and channel counts multiples of 8), weights are

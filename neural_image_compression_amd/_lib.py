@@ -90,6 +90,7 @@ RANS_Z_MAX_S, RANS_Z_MAX_M, RANS_Z_LDS_BYTES = 4096, 65535, 65536
 # lic_gain_quantize's `mode`; lic_gain_bwd's slab of pixels per partial row
 GAIN_SCALE, GAIN_NOISE, GAIN_ROUND = range(3)
 GAIN_SLAB_PIXELS, GAIN_SLAB_ROWS = 32, 4
+GAIN_ROWS_MAX_TABLES = 4   # lic_gain_rows_fwd / lic_gain_rows_bwd: tables per launch
 
 # the layered codec's entries take a host array of at most MAX_LAYERS rows, which they copy into the launch
 MAX_LAYERS = 4
@@ -151,6 +152,8 @@ SIGNATURES = {
     "lic_gain_quantize": (C.c_int, [_vp, _vp, _vp, _i64] + [_vp] * 6 + [_i32] * 5 + [_vp]),
     "lic_gain_bwd_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "lic_gain_bwd": (C.c_int, [_vp, _vp, _i64] + [_vp] * 5 + [_i32] * 4 + [_vp, _sz, _vp]),
+    "lic_gain_rows_fwd": (C.c_int, [_vp] * 4 + [_i32] * 4 + [_vp]),
+    "lic_gain_rows_bwd": (C.c_int, [_vp] * 7 + [_i32] * 4 + [_vp]),
     "lic_entropy_params_fwd": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "lic_entropy_params_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "lic_gmm_likelihood_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _vp]),
@@ -163,6 +166,8 @@ SIGNATURES = {
     "lic_rd_loss_workspace_bytes": (_sz, [_i32]),
     "lic_rd_loss_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i64, _f32, _vp, _vp, _sz, _vp]),
     "lic_rd_loss_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _i64, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "lic_rd_loss_fwd_lam": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "lic_rd_loss_bwd_lam": (C.c_int, [_vp, _vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lic_packed_weight_bf16_elems": (_i64, [_i32, _i32, _i32]),
     "lic_pack_weight_bf16": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp]),
     "lic_pack_weight_bf16_kperm": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _vp]),

@@ -917,11 +917,20 @@ __global__ __launch_bounds__(256) void rd_partial_kernel(const float* logp_y, lo
     o[2] = se;
   }
 }
+// slot 9 of the per-image-lambda loss: one image's share of the distortion term, in double
+__device__ __forceinline__ double rd_lam_term(float lambda_b, float mse_b) {
+#pragma clang fp contract(off)
+  const double t = (double)lambda_b * 65025.0;
+  return t * (double)mse_b;
+}
+// PER_IMAGE: lambda_img[b] from device memory (lic_rd_loss_fwd_lam) instead of the by-value lambda_rd; every other slot is
+// the same code
+template <bool PER_IMAGE>
 __global__ __launch_bounds__(64) void rd_final_kernel(const double* partial, int B, long nx, long num_pixels,
-                                                      float lambda_rd, float* out) {
+                                                      float lambda_rd, const float* lambda_img, float* out) {
   // one wave; lane b handles image b (looping when B > 64)
   const float ln2 = 0.693147180559945309f;
-  double sby = 0, sbz = 0, sbpy = 0, sbpz = 0, smse = 0;
+  double sby = 0, sbz = 0, sbpy = 0, sbpz = 0, smse = 0, sdist = 0;
   for (int b = threadIdx.x; b < B; b += 64) {
     double sy = 0, sz = 0, se = 0;
     for (int c = 0; c < RD_CHUNKS; ++c) {
@@ -937,6 +946,7 @@ __global__ __launch_bounds__(64) void rd_final_kernel(const double* partial, int
     sbpy += bits_y / (float)num_pixels;
     sbpz += bits_z / (float)num_pixels;
     smse += mse_b;
+    if constexpr (PER_IMAGE) sdist += rd_lam_term(lambda_img[b], mse_b);
     out[16 + b] = mse_b;
     out[16 + B + b] = -10.0f * log10f(mse_b + 1e-8f);
   }
@@ -945,10 +955,13 @@ __global__ __launch_bounds__(64) void rd_final_kernel(const double* partial, int
   sbpy = wave_sum_d(sbpy);
   sbpz = wave_sum_d(sbpz);
   smse = wave_sum_d(smse);
+  if constexpr (PER_IMAGE) sdist = wave_sum_d(sdist);
   if (threadIdx.x == 0) {
     const float bpp_y = (float)(sbpy / B), bpp_z = (float)(sbpz / B), mse = (float)(smse / B);
     const float bpp_total = bpp_y + bpp_z;
-    out[0] = bpp_total + lambda_rd * (255.0f * 255.0f) * mse;
+    const float dist = PER_IMAGE ? (float)(sdist / B) : 0.0f;
+    if constexpr (PER_IMAGE) out[0] = bpp_total + dist;
+    else out[0] = bpp_total + lambda_rd * (255.0f * 255.0f) * mse;
     out[1] = bpp_y;
     out[2] = bpp_z;
     out[3] = bpp_total;
@@ -959,15 +972,16 @@ __global__ __launch_bounds__(64) void rd_final_kernel(const double* partial, int
     out[8] = (float)((sby + sbz) / B);
 #pragma unroll
     for (int k = 9; k < 16; ++k) out[k] = 0.0f;   // (unused slots: the caller need not clear the buffer first)
+    if constexpr (PER_IMAGE) out[9] = dist;
   }
 }
 LIC_EXPORT size_t lic_rd_loss_workspace_bytes(int32_t B) {
   return B > 0 ? (size_t)B * RD_CHUNKS * 3 * sizeof(double) : 0;
 }
-LIC_EXPORT int lic_rd_loss_fwd(const float* logp_y, int64_t ny, const float* logp_z, int64_t nz,
-                               const float* x_hat, const float* x, int64_t nx, int32_t B, int64_t num_pixels,
-                               float lambda_rd, float* out, void* workspace, size_t workspace_bytes,
-                               lic_stream_t stream) {
+// both forward entries: lambda_img == nullptr is the by-value lambda_rd
+static int rd_loss_fwd(const float* logp_y, int64_t ny, const float* logp_z, int64_t nz, const float* x_hat, const float* x,
+                       int64_t nx, int32_t B, int64_t num_pixels, float lambda_rd, const float* lambda_img, float* out,
+                       void* workspace, size_t workspace_bytes, lic_stream_t stream) {
   if (!logp_y || !logp_z || !x_hat || !x || !out || !workspace || B <= 0 || ny <= 0 || nz <= 0 || nx <= 0 ||
       num_pixels <= 0)
     return LIC_ERR_INVALID;
@@ -977,9 +991,24 @@ LIC_EXPORT int lic_rd_loss_fwd(const float* logp_y, int64_t ny, const float* log
                      x_hat, x, (long)nx, (double*)workspace);
   int rc = lic_check_launch();
   if (rc != LIC_OK) return rc;
-  hipLaunchKernelGGL(rd_final_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, B, (long)nx,
-                     (long)num_pixels, lambda_rd, out);
+  auto kern = lambda_img ? rd_final_kernel<true> : rd_final_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, s, (const double*)workspace, B, (long)nx, (long)num_pixels, lambda_rd,
+                     lambda_img, out);
   return lic_check_launch();
+}
+LIC_EXPORT int lic_rd_loss_fwd(const float* logp_y, int64_t ny, const float* logp_z, int64_t nz,
+                               const float* x_hat, const float* x, int64_t nx, int32_t B, int64_t num_pixels,
+                               float lambda_rd, float* out, void* workspace, size_t workspace_bytes,
+                               lic_stream_t stream) {
+  return rd_loss_fwd(logp_y, ny, logp_z, nz, x_hat, x, nx, B, num_pixels, lambda_rd, nullptr, out, workspace,
+                     workspace_bytes, stream);
+}
+LIC_EXPORT int lic_rd_loss_fwd_lam(const float* logp_y, int64_t ny, const float* logp_z, int64_t nz, const float* x_hat,
+                                   const float* x, int64_t nx, int32_t B, int64_t num_pixels, const float* lambda_img,
+                                   float* out, void* workspace, size_t workspace_bytes, lic_stream_t stream) {
+  if (!lambda_img) return LIC_ERR_INVALID;
+  return rd_loss_fwd(logp_y, ny, logp_z, nz, x_hat, x, nx, B, num_pixels, 0.0f, lambda_img, out, workspace,
+                     workspace_bytes, stream);
 }
 LIC_EXPORT int lic_rd_loss_bwd(const float* x_hat, const float* x, int64_t ny, int64_t nz, int64_t nx,
                                int32_t B, int64_t num_pixels, float lambda_rd, const float* gl, float* dlogp_y,
@@ -1018,4 +1047,46 @@ LIC_EXPORT int lic_rd_loss_bwd(const float* x_hat, const float* x, int64_t ny, i
         reinterpret_cast<f32x4*>(dx_hat)[i] = (a - c) * k;
       },
       [=] __device__(long i) { dx_hat[i] = gl[0] * kx * (x_hat[i] - x[i]); });
+}
+// lic_rd_loss_bwd's host expression for kx, evaluated per image on the device: every operation rounded on its own
+__device__ __forceinline__ float rd_kx(float lambda_b, float count) {
+#pragma clang fp contract(off)
+  const float a = lambda_b * (255.0f * 255.0f);
+  const float b = a * 2.0f;
+  return b / count;
+}
+LIC_EXPORT int lic_rd_loss_bwd_lam(const float* x_hat, const float* x, int64_t ny, int64_t nz, int64_t nx, int32_t B,
+                                   int64_t num_pixels, const float* lambda_img, const float* gl, float* dlogp_y,
+                                   float* dlogp_z, float* dx_hat, lic_stream_t stream) {
+  if (!x_hat || !x || !lambda_img || !gl || !dlogp_y || !dlogp_z || !dx_hat || B <= 0 || ny <= 0 || nz <= 0 || nx <= 0 ||
+      num_pixels <= 0)
+    return LIC_ERR_INVALID;
+  const float ln2 = 0.693147180559945309f;
+  const float ky = -1.0f / (ln2 * (float)num_pixels * (float)B);
+  const float count = (float)nx * (float)B;
+  // one launch for the three gradients on either path: index ranges image gradient (16 bytes or one float per lane,
+  // whole pieces inside one image), then dlogp_y, then dlogp_z
+  const bool vec = al16(x_hat) && al16(x) && al16(dx_hat) && nx % 4 == 0;
+  const long per = vec ? nx / 4 : nx, e0 = per * B, e1 = e0 + ny * B, e2 = e1 + nz * B;
+  if (vec)
+    return ew_launch(e2, stream, [=] __device__(long i) {
+      if (i < e0) {
+        const f32x4 a = reinterpret_cast<const f32x4*>(x_hat)[i], c = reinterpret_cast<const f32x4*>(x)[i];
+        const float k = gl[0] * rd_kx(lambda_img[i / per], count);
+        reinterpret_cast<f32x4*>(dx_hat)[i] = (a - c) * k;
+      } else if (i < e1) {
+        dlogp_y[i - e0] = gl[0] * ky;
+      } else {
+        dlogp_z[i - e1] = gl[0] * ky;
+      }
+    });
+  return ew_launch(e2, stream, [=] __device__(long i) {
+    if (i < e0) {
+      dx_hat[i] = gl[0] * rd_kx(lambda_img[i / per], count) * (x_hat[i] - x[i]);
+    } else if (i < e1) {
+      dlogp_y[i - e0] = gl[0] * ky;
+    } else {
+      dlogp_z[i - e1] = gl[0] * ky;
+    }
+  });
 }

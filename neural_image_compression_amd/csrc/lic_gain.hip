@@ -4,6 +4,9 @@
 //   lic_gain_bwd       dv = t * s and ds[b][c] = sum_pixels t * v, a two-stage sum in a fixed order.
 // Each has a 16-byte path (C % 4 == 0, aligned operands) and a single-float path that write the same bytes.  No
 // multiply is contracted with the add behind it (gain_point, gain_grad_point): the rounding points are lic.h's.
+// And the scales themselves from qualities that stay on the device (a few thousand elements, one launch each):
+//   lic_gain_rows_fwd  rows[t][b] = exp((1 - l_b) T_t[i_b] + l_b T_t[i_b + 1]) for up to four stacked tables;
+//   lic_gain_rows_bwd  the tables' gradient, one thread per element summing over the images in rising order.
 #include "lic_common.h"
 
 #define GAIN_BLOCK 256
@@ -258,5 +261,122 @@ LIC_EXPORT int lic_gain_bwd(const float* v, const float* s, int64_t s_stride, co
   const int64_t BC = (int64_t)B * C;
   hipLaunchKernelGGL(gain_bwd_finish_kernel, dim3((unsigned)cdiv64(BC, GAIN_BLOCK)), dim3(GAIN_BLOCK), 0, (hipStream_t)stream,
                      (const float*)part, ds, (long)BC, (unsigned)C, (unsigned)nslab);
+  return lic_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// gain rows from device qualities (lic.h: lic_gain_rows_fwd / lic_gain_rows_bwd)
+// ---------------------------------------------------------------------------------------------
+// the level i and the weight l of one image: qc = min(max(q, 0), Q-1) (NaN -> 0), i = min(floor(qc), Q-2), l = qc - i
+__device__ __forceinline__ void gain_level(float q, int Q, int& i, float& l) {
+  const float top = (float)(Q - 1);
+  const float qc = q != q ? 0.0f : (q < 0.0f ? 0.0f : (q > top ? top : q));
+  const int f = (int)floorf(qc);
+  i = f < Q - 2 ? f : Q - 2;
+  l = qc - (float)i;
+}
+
+// rows = expf(fl32(fl32(fl32(1 - l) * T[i]) + fl32(l * T[i+1]))): no product is contracted with the sum
+__device__ __forceinline__ float gain_row_point(float l, float t0, float t1) {
+#pragma clang fp contract(off)
+  const float w0 = 1.0f - l;
+  const float a = w0 * t0;
+  const float b = l * t1;
+  const float e = a + b;
+  return expf(e);
+}
+
+// one thread per element of rows [k][B][M]; the threads of table 0, channel 0 write their image's level
+__global__ __launch_bounds__(GAIN_BLOCK) void gain_rows_fwd_kernel(const float* __restrict__ q, const float* __restrict__ tables,
+                                                                   float* __restrict__ rows, int* __restrict__ lvl_i,
+                                                                   float* __restrict__ lvl_l, long total, int Q, int M,
+                                                                   int B) {
+  const long e = (long)blockIdx.x * GAIN_BLOCK + threadIdx.x;
+  if (e >= total) return;
+  const int c = (int)(e % M);
+  const long kb = e / M;
+  const int b = (int)(kb % B), kk = (int)(kb / B);
+  int i;
+  float l;
+  gain_level(q[b], Q, i, l);
+  const float* T = tables + ((long)kk * Q + i) * M + c;
+  rows[e] = gain_row_point(l, T[0], T[M]);
+  if (kk == 0 && c == 0) {
+    lvl_i[b] = i;
+    lvl_l[b] = l;
+  }
+}
+
+struct gain_rows_grads {
+  const float* p[LIC_GAIN_ROWS_MAX_TABLES];
+};
+
+// one thread per element of d_tables [k][Q][M]: a running sum over the images in rising order, level i first, then i + 1
+__global__ __launch_bounds__(GAIN_BLOCK) void gain_rows_bwd_kernel(const int* __restrict__ lvl_i, const float* __restrict__ lvl_l,
+                                                                   const float* __restrict__ rows, gain_rows_grads d_rows,
+                                                                   float* __restrict__ d_tables, long total, int Q, int M,
+                                                                   int B) {
+#pragma clang fp contract(off)
+  const long e = (long)blockIdx.x * GAIN_BLOCK + threadIdx.x;
+  if (e >= total) return;
+  const int c = (int)(e % M);
+  const long kj = e / M;
+  const int j = (int)(kj % Q), kk = (int)(kj / Q);
+  const float* g = d_rows.p[kk];
+  float sum = 0.0f;
+  if (g) {
+    const float* r = rows + (long)kk * B * M + c;
+    for (int b = 0; b < B; ++b) {
+      const int i = lvl_i[b];
+      if (i != j && i + 1 != j) continue;
+      const float l = lvl_l[b], rv = r[(long)b * M], gv = g[(long)b * M + c];
+      if (i == j) {
+        const float w0 = 1.0f - l;
+        const float t = w0 * rv;
+        const float u = t * gv;
+        sum = sum + u;
+      }
+      if (i + 1 == j) {
+        const float t = l * rv;
+        const float u = t * gv;
+        sum = sum + u;
+      }
+    }
+  }
+  d_tables[e] = sum;
+}
+
+static int gain_rows_extents(int32_t k, int32_t Q, int32_t M, int32_t B) {
+  if (k < 1 || k > LIC_GAIN_ROWS_MAX_TABLES || Q < 2 || M < 1 || B < 1) return LIC_ERR_INVALID;
+  if ((int64_t)k * M * (B > Q ? B : Q) >= 0x7FFFFFFFLL) return LIC_ERR_UNSUPPORTED;
+  return LIC_OK;
+}
+
+LIC_EXPORT int lic_gain_rows_fwd(const float* q, const float* tables, float* rows, void* lvl, int32_t k, int32_t Q, int32_t M,
+                                 int32_t B, lic_stream_t stream) {
+  if (!q || !tables || !rows || !lvl) return LIC_ERR_INVALID;
+  if (const int rc = gain_rows_extents(k, Q, M, B)) return rc;
+  for (const void* p : {(const void*)q, (const void*)tables, (const void*)rows, (const void*)lvl})
+    if (!gain_al(p, 4)) return LIC_ERR_INVALID;
+  const int64_t total = (int64_t)k * B * M;
+  hipLaunchKernelGGL(gain_rows_fwd_kernel, dim3((unsigned)cdiv64(total, GAIN_BLOCK)), dim3(GAIN_BLOCK), 0, (hipStream_t)stream,
+                     q, tables, rows, (int*)lvl, (float*)lvl + B, (long)total, (int)Q, (int)M, (int)B);
+  return lic_check_launch();
+}
+
+LIC_EXPORT int lic_gain_rows_bwd(const void* lvl, const float* rows, const float* d_rows0, const float* d_rows1,
+                                 const float* d_rows2, const float* d_rows3, float* d_tables, int32_t k, int32_t Q, int32_t M,
+                                 int32_t B, lic_stream_t stream) {
+  if (!lvl || !rows || !d_tables) return LIC_ERR_INVALID;
+  if (const int rc = gain_rows_extents(k, Q, M, B)) return rc;
+  gain_rows_grads g = {{d_rows0, d_rows1, d_rows2, d_rows3}};
+  for (int t = k; t < LIC_GAIN_ROWS_MAX_TABLES; ++t)
+    if (g.p[t]) return LIC_ERR_INVALID;
+  for (const void* p : {(const void*)lvl, (const void*)rows, (const void*)d_rows0, (const void*)d_rows1, (const void*)d_rows2,
+                        (const void*)d_rows3, (const void*)d_tables})
+    if (!gain_al(p, 4)) return LIC_ERR_INVALID;
+  const int64_t total = (int64_t)k * Q * M;
+  hipLaunchKernelGGL(gain_rows_bwd_kernel, dim3((unsigned)cdiv64(total, GAIN_BLOCK)), dim3(GAIN_BLOCK), 0, (hipStream_t)stream,
+                     (const int*)lvl, (const float*)lvl + B, rows, g, d_tables, (long)total, (int)Q, (int)M, (int)B);
   return lic_check_launch();
 }

@@ -1138,6 +1138,53 @@ def channel_scale(v, s, cast_out=False):
     return res
 
 
+class _GainRowsFn(torch.autograd.Function):
+    """rows [k][B][M] = lic_gain_rows_fwd(q, stacked tables): the gain rows of a batch from qualities on the device, one
+    launch, nothing read back.  Backward, one lic_gain_rows_bwd: the tables' gradients, summed over the images in a fixed
+    order (no atomics); `q` carries none."""
+
+    @staticmethod
+    def forward(ctx, q, *tables):
+        _require_cuda(q, *tables)
+        k, (Qn, M), B = len(tables), tables[0].shape, q.shape[0]
+        T = tables[0].contiguous() if k == 1 else torch.stack(tables)
+        rows = torch.empty((k, B, M), device=q.device, dtype=torch.float32)
+        lvl = torch.empty((2 * B,), device=q.device, dtype=torch.int32)   # int32 i[B], then float l[B]
+        L.check(L.load().lic_gain_rows_fwd(_ptr(q), _ptr(T), _ptr(rows), _ptr(lvl), k, Qn, M, B, _stream()),
+                "lic_gain_rows_fwd")
+        ctx.save_for_backward(rows, lvl)
+        ctx.dims = (k, Qn, M, B)
+        ctx.set_materialize_grads(False)
+        return rows.unbind(0)
+
+    @staticmethod
+    def backward(ctx, *d_rows):
+        rows, lvl = ctx.saved_tensors
+        k, Qn, M, B = ctx.dims
+        gs = [None if g is None else g.contiguous() for g in d_rows[:k]]
+        if all(g is None for g in gs):
+            return (None,) * (1 + k)
+        _require_cuda(*gs)
+        d_tables = torch.empty((k, Qn, M), device=rows.device, dtype=torch.float32)
+        ptrs = [_ptr(g) for g in gs] + [None] * (L.GAIN_ROWS_MAX_TABLES - k)
+        L.check(L.load().lic_gain_rows_bwd(_ptr(lvl), _ptr(rows), *ptrs, _ptr(d_tables), k, Qn, M, B, _stream()),
+                "lic_gain_rows_bwd")
+        return (None, *[d_tables[t] if ctx.needs_input_grad[1 + t] else None for t in range(k)])
+
+
+def gain_rows_device(q: torch.Tensor, *tables):
+    """-> one rows tensor [B][M] per table ([Q][M] log gains, 1..4 of them, one shape), views of one [k][B][M] buffer:
+    exp((1 - l) * T[i] + l * T[i + 1]) at the qualities `q` (CUDA float32 [B]), which are clamped to [0, Q-1] on the
+    device (a NaN counts as 0) and never read by the host."""
+    if not 1 <= len(tables) <= L.GAIN_ROWS_MAX_TABLES:
+        raise L.LicError(f"1 to {L.GAIN_ROWS_MAX_TABLES} tables expected, got {len(tables)}")
+    if not (torch.is_tensor(q) and q.is_cuda and q.dtype == torch.float32 and q.dim() == 1 and q.is_contiguous()):
+        raise L.LicError("`q` must be a contiguous CUDA float32 tensor [B]")
+    if any(t.dim() != 2 or t.shape != tables[0].shape or t.dtype != torch.float32 for t in tables) or tables[0].shape[0] < 2:
+        raise L.LicError("the tables must be float32 [Q >= 2][M] tensors of one shape")
+    return _GainRowsFn.apply(q.detach(), *tables)
+
+
 # ------------------------------------------------------------------------------------------
 # entropy-parameter activations + conditional likelihood
 # ------------------------------------------------------------------------------------------
@@ -1318,11 +1365,15 @@ class _RdLossFn(torch.autograd.Function):
         nbytes = lib.lic_rd_loss_workspace_bytes(B)
         ws = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
         num_pixels = xx.shape[1] * xx.shape[2]
-        L.check(lib.lic_rd_loss_fwd(_ptr(ly), ly.numel() // B, _ptr(lz), lz.numel() // B, _ptr(xh), _ptr(xx),
-                                    xx.numel() // B, B, num_pixels, lambda_rd, _ptr(out), _ptr(ws), nbytes,
-                                    _stream()), "lic_rd_loss_fwd")
-        ctx.save_for_backward(xh, xx)
-        ctx.cfg = (tuple(ly.shape), tuple(lz.shape), lambda_rd, num_pixels)
+        per_image = torch.is_tensor(lambda_rd)   # (rd_loss_buffer checked it: CUDA float32 [B])
+        fwd, name = (lib.lic_rd_loss_fwd_lam, "lic_rd_loss_fwd_lam") if per_image else (lib.lic_rd_loss_fwd, "lic_rd_loss_fwd")
+        L.check(fwd(_ptr(ly), ly.numel() // B, _ptr(lz), lz.numel() // B, _ptr(xh), _ptr(xx), xx.numel() // B, B, num_pixels,
+                    _ptr(lambda_rd) if per_image else lambda_rd, _ptr(out), _ptr(ws), nbytes, _stream()), name)
+        if per_image:
+            ctx.save_for_backward(xh, xx, lambda_rd)
+        else:
+            ctx.save_for_backward(xh, xx)
+        ctx.cfg = (tuple(ly.shape), tuple(lz.shape), None if per_image else lambda_rd, num_pixels)
         # the loss as a tensor of its own on element 0 of the buffer: a `buf[0]` in the caller would make every
         # backward start with select_backward's zero-fill and a 4-byte device copy (a memcpy node, which a launch
         # plan -- plan.StepPlan -- cannot read back from the captured graph)
@@ -1333,7 +1384,7 @@ class _RdLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _gbuf, gloss):
-        xh, xx = ctx.saved_tensors
+        xh, xx, *lam_img = ctx.saved_tensors
         shy, shz, lam, num_pixels = ctx.cfg
         B = xx.shape[0]
         if gloss is None:
@@ -1342,14 +1393,30 @@ class _RdLossFn(torch.autograd.Function):
         dly = torch.empty(shy, device=xx.device, dtype=torch.float32)
         dlz = torch.empty(shz, device=xx.device, dtype=torch.float32)
         dxh = torch.empty_like(xh)
-        L.check(L.load().lic_rd_loss_bwd(_ptr(xh), _ptr(xx), dly.numel() // B, dlz.numel() // B,
-                                         xx.numel() // B, B, num_pixels, lam, _ptr(gl), _ptr(dly), _ptr(dlz),
-                                         _ptr(dxh), _stream()), "lic_rd_loss_bwd")
+        lib = L.load()
+        bwd, name = (lib.lic_rd_loss_bwd_lam, "lic_rd_loss_bwd_lam") if lam_img else (lib.lic_rd_loss_bwd, "lic_rd_loss_bwd")
+        L.check(bwd(_ptr(xh), _ptr(xx), dly.numel() // B, dlz.numel() // B, xx.numel() // B, B, num_pixels,
+                    _ptr(lam_img[0]) if lam_img else lam, _ptr(gl), _ptr(dly), _ptr(dlz), _ptr(dxh), _stream()), name)
         return _nchw_view(dly), _nchw_view(dlz), _nchw_view(dxh), None, None
 
 
+def is_per_image(lam, B: int) -> bool:
+    """is `lam` (a loss's lambda) one value per image on the device: a CUDA float32 [B] tensor.  Any other tensor raises;
+    a number is the scalar path."""
+    if not torch.is_tensor(lam):
+        return False
+    if not (lam.is_cuda and lam.dtype == torch.float32 and tuple(lam.shape) == (B,) and lam.is_contiguous()):
+        raise L.LicError(f"a per-image lambda must be a contiguous CUDA float32 tensor [{B}], got {lam.dtype} "
+                         f"{tuple(lam.shape)} on {lam.device}")
+    return True
+
+
 def rd_loss_buffer(logp_y, logp_z, x_hat, x, lambda_rd):
-    """(result buffer [16 + 2B] -- no gradient --, loss: 0-d tensor on its element 0, differentiable)"""
+    """(result buffer [16 + 2B] -- no gradient --, loss: 0-d tensor on its element 0, differentiable).  `lambda_rd`: a
+    number, or a CUDA float32 [B] tensor -- one lambda per image, read on the device (lic_rd_loss_fwd_lam); slot 9 of the
+    buffer then holds the distortion term."""
+    if is_per_image(lambda_rd, x.shape[0]):
+        return _RdLossFn.apply(logp_y, logp_z, x_hat, x, lambda_rd.detach())
     return _RdLossFn.apply(logp_y, logp_z, x_hat, x, float(lambda_rd))
 
 

@@ -10,17 +10,21 @@ _KEYS = ("loss", "bpp_y", "bpp_z", "bpp_total", "mse", "psnr", "bits_y", "bits_z
 
 
 def rd_loss(model_out: dict, x: torch.Tensor, lambda_rd: float, sync: bool = True):
-    """sync=False returns 0-d device tensors instead of Python floats (no host sync at all)."""
+    """sync=False returns 0-d device tensors instead of Python floats (no host sync at all).
+    `lambda_rd` as a CUDA float32 [B] tensor is one lambda per image, read on the device (a recorded step then serves any
+    lambdas): loss = bpp_total + mean_b lambda_b * 255^2 * mse_b, and the result gains 'distortion_term', that mean."""
     B = x.size(0)
+    per_image = F_.is_per_image(lambda_rd, B)
     buf, loss = F_.rd_loss_buffer(model_out['logp_y'], model_out['logp_z'], model_out['x_hat'], x, lambda_rd)
     det = buf.detach()
     res = {'loss': loss}
+    keys = _KEYS + ('distortion_term',) if per_image else _KEYS   # (slot 9 of the buffer)
     if sync:
-        host = det[:9].tolist()
-        for i, k in enumerate(_KEYS[1:], start=1):
+        host = det[:len(keys)].tolist()
+        for i, k in enumerate(keys[1:], start=1):
             res[k] = host[i]
     else:
-        for i, k in enumerate(_KEYS[1:], start=1):
+        for i, k in enumerate(keys[1:], start=1):
             res[k] = det[i]
         res['_buffer'] = det   # (all of the above in one tensor: `det[:9].tolist()` is ONE device-to-host copy)
     res['mse_per_image'] = det[16:16 + B]
@@ -44,18 +48,29 @@ def rd_loss_msssim(model_out: dict, x: torch.Tensor, lambda_rd: float, sync: boo
     buf, rate = F_.rd_loss_buffer(model_out['logp_y'], model_out['logp_z'], x_hat, x, 0.0)   # rate = bpp_total
     ms_img = F_.ms_ssim(x_hat, x, data_range=1.0, size_average=False)
     ms = ms_img.mean()
-    loss = rate + lambda_rd * (1.0 - ms)
+    dist = None
+    if F_.is_per_image(lambda_rd, B):
+        # one lambda per image, on the device: loss = rate + mean_b lambda_b * (1 - ms_b)
+        dist = (lambda_rd.detach() * (1.0 - ms_img)).mean()
+        loss = rate + dist
+    else:
+        loss = rate + lambda_rd * (1.0 - ms)
     det, ms_det = buf.detach(), ms.detach()
     res = {'loss': loss}
     if sync:
-        host = torch.cat([det[:9], ms_det.reshape(1)]).tolist()
+        extra = [ms_det.reshape(1)] + ([] if dist is None else [dist.detach().reshape(1)])
+        host = torch.cat([det[:9], *extra]).tolist()
         for i, k in enumerate(_KEYS[1:], start=1):
             res[k] = host[i]
         res['ms_ssim'] = host[9]
+        if dist is not None:
+            res['distortion_term'] = host[10]
     else:
         for i, k in enumerate(_KEYS[1:], start=1):
             res[k] = det[i]
         res['ms_ssim'] = ms_det
+        if dist is not None:
+            res['distortion_term'] = dist.detach()
         res['_buffer'] = det   # (slot 0 holds bpp_total, not this loss; Trainer reads the slots after it)
     res['mse_per_image'] = det[16:16 + B]
     res['psnr_per_image'] = det[16 + B:16 + 2 * B]

@@ -58,15 +58,23 @@ class _HyperpriorContextModel(nn.Module):
             for name in self.GAIN_TABLES:
                 setattr(self, name, nn.Parameter(torch.zeros(rate_levels, self.M)))
 
-    def check_quality(self, quality, batch: int = None):
+    def check_quality(self, quality, batch: int = None, device_quality: bool = False):
         """`quality` as the model takes it: None for a plain model; a float (the whole batch) or a [B] tensor, every
-        value in [0, Q-1], for a rate-level model.  -> None, or a host list of 1 or B floats.  ValueError otherwise."""
+        value in [0, Q-1], for a rate-level model.  -> None, or a host list of 1 or B floats.  ValueError otherwise.
+        `device_quality`: the qualities stay on the device -- a CUDA float32 [B] tensor, of which only shape and dtype are
+        checked here; the values are never read back and the kernel clamps them to [0, Q-1].  -> the
+        tensor."""
         if self.rate_levels is None:
-            if quality is not None:
+            if quality is not None or device_quality:
                 raise ValueError("this model has no rate levels (rate_levels=None): it takes no `quality`")
             return None
         if quality is None:
             raise ValueError(f"a model with rate_levels={self.rate_levels} needs `quality` in [0, {self.rate_levels - 1}]")
+        if device_quality:
+            if not (torch.is_tensor(quality) and quality.is_cuda and quality.dtype == torch.float32 and quality.dim() == 1
+                    and quality.is_contiguous() and (batch is None or quality.shape[0] == batch)):
+                raise ValueError("device_quality=True takes `quality` as a contiguous CUDA float32 tensor [B]")
+            return quality.detach()
         if torch.is_tensor(quality):
             if quality.dim() != 1 or (batch is not None and quality.shape[0] != batch):
                 raise ValueError(f"`quality` must be a float or a tensor [B], got shape {tuple(quality.shape)}")
@@ -85,7 +93,10 @@ class _HyperpriorContextModel(nn.Module):
         geometric interpolation between the neighbouring levels, exp((1 - l) * log_g[i] + l * log_g[i + 1]) with
         i = floor(q) clamped to Q-2 and l = q - i, both weights float32.  Plain torch ops, the same handful for any number
         of tables (they are stacked), and for one quality nothing but slices: autograd carries the rows' gradients back
-        to the tables.  One quality and a constant list give the same bits."""
+        to the tables.  One quality and a constant list give the same bits.
+        `qs` as a device tensor (check_quality with `device_quality`): one launch, functional.gain_rows_device."""
+        if torch.is_tensor(qs):
+            return F_.gain_rows_device(qs, *tables)
         T = tables[0].unsqueeze(0) if len(tables) == 1 else torch.stack(tables)           # [k][Q][M]
         idx = [min(int(q), self.rate_levels - 2) for q in qs]
         lf = [np.float32(q - i) for q, i in zip(qs, idx)]
@@ -102,18 +113,18 @@ class _HyperpriorContextModel(nn.Module):
         """all four rows of one forward, by table name, from one pass of `gain_rows`"""
         return dict(zip(self.GAIN_TABLES, self.gain_rows(qs, *(getattr(self, n) for n in self.GAIN_TABLES))))
 
-    def hyper_synthesis(self, z_in: torch.Tensor, quality=None, _gains=None, **kw):
+    def hyper_synthesis(self, z_in: torch.Tensor, quality=None, _gains=None, device_quality=False, **kw):
         """psi = hyper_decoder(z_in * inverse gain of z at `quality`); the bare module call for a plain model"""
-        qs = self.check_quality(quality, z_in.shape[0])
+        qs = self.check_quality(quality, z_in.shape[0], device_quality)
         if qs is None:
             return self.hyper_decoder(z_in, **kw)
         inv = _gains["log_inv_gain_z"] if _gains is not None else self.gain_rows(qs, self.log_inv_gain_z)[0]
         lat16 = z_in.is_cuda and self.hyper_decoder.precision == "bf16"
         return self.hyper_decoder(F_.channel_scale(z_in, inv, cast_out=lat16), **kw)
 
-    def synthesis(self, y_in: torch.Tensor, quality=None, _gains=None):
+    def synthesis(self, y_in: torch.Tensor, quality=None, _gains=None, device_quality=False):
         """x_hat = decoder(y_in * inverse gain of y at `quality`); the bare module call for a plain model"""
-        qs = self.check_quality(quality, y_in.shape[0])
+        qs = self.check_quality(quality, y_in.shape[0], device_quality)
         if qs is None:
             return self.decoder(y_in)
         inv = _gains["log_inv_gain_y"] if _gains is not None else self.gain_rows(qs, self.log_inv_gain_y)[0]
@@ -137,7 +148,7 @@ class _HyperpriorContextModel(nn.Module):
         return self
 
     def analysis_hyperprior(self, x: torch.Tensor, training: bool = True, noise=None, with_packed_params=False,
-                            _fork=None, quality=None, _gains=None):
+                            _fork=None, quality=None, _gains=None, device_quality=False):
         """Everything of `forward` except the synthesis transform (Models.py:49-97): the scope the
         north star quotes its roofline target on.  Returns the out-dict without 'x_hat'
         (`with_packed_params`: plus '_act', the activated entropy parameters as the one packed tensor
@@ -145,8 +156,8 @@ class _HyperpriorContextModel(nn.Module):
         A rate-level model (`quality`): y and z are scaled by their gains in the quantisation launches --
         'y' and 'z' of the out-dict are the gained latents, which is what the hyper-encoder reads -- and z_in by its
         inverse gain in front of the hyper-decoder; the context model, the entropy parameters and both likelihoods see
-        y_in / z_in as ever."""
-        qs = self.check_quality(quality, x.shape[0])
+        y_in / z_in as ever.  `device_quality`: `quality` is a CUDA float32 [B] tensor that stays on the device."""
+        qs = self.check_quality(quality, x.shape[0], device_quality)
         if qs is not None and _gains is None:
             _gains = self._gains(qs)        # (`forward` hands in the rows it made: one pass of torch ops per step)
         if x.shape[2] % 64 or x.shape[3] % 64:
@@ -225,11 +236,11 @@ class _HyperpriorContextModel(nn.Module):
             c_psi = self.hyper_decoder.net[-1].out_channels
             comb = torch.empty((Bn, hh, ww, c_phi + c_psi), device=x.device,
                                dtype=torch.float32 if both[0] == "fp32" else torch.bfloat16)
-            psi = self.hyper_synthesis(z_in, quality, _gains, out=comb[..., c_phi:])
+            psi = self.hyper_synthesis(z_in, quality, _gains, device_quality, out=comb[..., c_phi:])
             phi = self.context_model(y_ctx, out=comb[..., :c_phi])
             combined = F_.join_channels(phi, psi, comb)
         else:
-            psi = self.hyper_synthesis(z_in, quality, _gains)
+            psi = self.hyper_synthesis(z_in, quality, _gains, device_quality)
             phi = self.context_model(y_ctx)
             combined = torch.cat([phi, psi], dim=1)  # (bf16 features: a 6 MB layout copy, phi first)
         act = self.entropy_parameters.packed(combined)
@@ -282,15 +293,17 @@ class _HyperpriorContextModel(nn.Module):
             self._side_stream = torch.cuda.Stream(priority=-1)
         return self._side_stream
 
-    def forward(self, x: torch.Tensor, training: bool = True, noise=None, quality=None):
+    def forward(self, x: torch.Tensor, training: bool = True, noise=None, quality=None, device_quality: bool = False):
         """`noise` (test hook, not in the reference): (u_z, u_y) uniform [0,1) tensors used instead
         of torch.rand_like, in the reference's draw order (z first, Models.py:57-58).  `quality`: required by a
-        rate-level model, a float for the whole batch or a tensor [B], in [0, rate_levels - 1]."""
-        qs = self.check_quality(quality, x.shape[0])
+        rate-level model, a float for the whole batch or a tensor [B], in [0, rate_levels - 1].  `device_quality`: `quality`
+        is a CUDA float32 [B] tensor that is never read back -- no host sync, legal inside a recorded step; the gain rows
+        come from one launch, which clamps each value to [0, rate_levels - 1]."""
+        qs = self.check_quality(quality, x.shape[0], device_quality)
         gains = None if qs is None else self._gains(qs)
         if not (self.overlap_branches and x.is_cuda):
-            out = self.analysis_hyperprior(x, training, noise, quality=quality, _gains=gains)
-            return {'x_hat': self.synthesis(out['y_in'], quality, gains), **out}
+            out = self.analysis_hyperprior(x, training, noise, quality=quality, _gains=gains, device_quality=device_quality)
+            return {'x_hat': self.synthesis(out['y_in'], quality, gains, device_quality), **out}
         main = torch.cuda.current_stream()
         side = self.side_stream()
         box = {}
@@ -298,10 +311,11 @@ class _HyperpriorContextModel(nn.Module):
         def fork(y_in):
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                box['x_hat'] = self.synthesis(y_in, quality, gains)
+                box['x_hat'] = self.synthesis(y_in, quality, gains, device_quality)
             y_in.record_stream(side)
 
-        out = self.analysis_hyperprior(x, training, noise, _fork=fork, quality=quality, _gains=gains)
+        out = self.analysis_hyperprior(x, training, noise, _fork=fork, quality=quality, _gains=gains,
+                                       device_quality=device_quality)
         main.wait_stream(side)
         box['x_hat'].record_stream(main)
         return {'x_hat': box['x_hat'], **out}

@@ -62,28 +62,81 @@ class _ReadBack:
         return _read_commands(self._lib, self._plan, n_sides)
 
 
+class _RatePoint:
+    """The per-image values a recorded step reads from device memory -- the qualities and / or the lambdas of a rate-level
+    model -- as rows of one resident [rows][B] tensor.  The capture bakes the tensor's address in, not its
+    contents: `set` puts new values there in front of a replay, through one pinned staging tensor and ONE non-blocking
+    copy (not part of the record, no host synchronisation).  The staging tensor has two halves used in turn, each behind
+    the event of the copy that last read it: the host may run ahead of the device by a step without touching values
+    still on their way."""
+
+    def __init__(self, dev, batch: int, **initial):
+        self.names = [k for k, v in initial.items() if v is not None]
+        for k in self.names:
+            v = initial[k]
+            if not (torch.is_tensor(v) and v.is_cuda and v.dtype == torch.float32 and tuple(v.shape) == (batch,)):
+                raise L.LicError(f"`{k}` of a plan must be a CUDA float32 tensor [{batch}]")
+        self.resident = torch.stack([initial[k].detach() for k in self.names]) if self.names else None
+        if self.names:
+            self.host = self.resident.cpu()                          # the values in place, for the arguments `set` omits
+            self.stage = torch.empty((2,) + tuple(self.host.shape), dtype=torch.float32).pin_memory()
+            self.events, self.turn = [None, None], 0
+
+    def row(self, name):
+        """the resident [B] tensor of `name`, or None when the plan holds it as a constant"""
+        return self.resident[self.names.index(name)] if name in self.names else None
+
+    def set(self, **values):
+        """new values (host sequences or CPU tensors of B floats) for the rows named; None keeps what is there"""
+        given = {k: v for k, v in values.items() if v is not None}
+        if not given:
+            return
+        for k, v in given.items():
+            if k not in self.names:
+                raise L.LicError(f"this plan was captured without a resident `{k}`: it cannot change between replays")
+            if torch.is_tensor(v) and v.is_cuda:
+                raise L.LicError(f"`{k}` goes through a pinned host tensor: pass host values, or write the plan's resident "
+                                 "tensor yourself")
+            self.host[self.names.index(k)].copy_(torch.as_tensor(v, dtype=torch.float32).reshape(-1))
+        slot, self.turn = self.turn, self.turn ^ 1
+        if self.events[slot] is not None:
+            self.events[slot].synchronize()   # (the copy of two calls ago: long done unless the host is far ahead)
+        self.stage[slot].copy_(self.host)
+        self.resident.copy_(self.stage[slot], non_blocking=True)
+        self.events[slot] = torch.cuda.Event()
+        self.events[slot].record()
+
+
 class StepPlan(_ReadBack):
-    def __init__(self, model, loss_fn: Callable, lambda_val: float, example: torch.Tensor, warmup: int = 2,
-                 side_stream: Optional[torch.cuda.Stream] = None, tune: bool = False):
+    def __init__(self, model, loss_fn: Callable, lambda_val, example: torch.Tensor, warmup: int = 2,
+                 side_stream: Optional[torch.cuda.Stream] = None, tune: bool = False, quality=None):
         """`loss_fn(model_out, x, lambda_val, sync=False)` -> dict with 'loss' (loss.rd_loss); `example`: a batch
         of the shape every later batch will have.  Runs `warmup` eager steps WITHOUT an optimizer step (they fill
-        the caches: packed-weight plan, gradient buffers, allocator), then captures one."""
+        the caches: packed-weight plan, gradient buffers, allocator), then captures one.
+        A rate-level model: `quality` and `lambda_val` as CUDA float32 [B] tensors.  The plan keeps resident copies
+        (`self.quality`, `self.lam`), records `model(x, quality=self.quality, device_quality=True)` and
+        `loss_fn(out, x, self.lam, sync=False)`, and `step(x, quality=, lam=)` then serves any rate points, one per
+        image.  (A float `lambda_val` is baked into the record as ever.)"""
         if not example.is_cuda:
             raise L.LicError("StepPlan needs a CUDA batch (there is no CPU fallback)")
         if torch.distributed.is_available() and torch.distributed.is_initialized() and \
                 torch.distributed.get_world_size() > 1:
             raise L.LicError("StepPlan replays one GPU's step; data-parallel training uses the eager step "
                              "(the gradient all-reduce runs from autograd hooks)")
-        self.model, self.loss_fn, self.lam = model, loss_fn, lambda_val
+        self.model, self.loss_fn = model, loss_fn
         self.x = example.clone(memory_format=torch.preserve_format)
         self._plan = C.c_void_p()
         self._lib = L.load()
         dev = example.device
+        self._rate = _RatePoint(dev, example.shape[0], quality=quality, lam=lambda_val if torch.is_tensor(lambda_val) else None)
+        self.quality = self._rate.row("quality")
+        self.lam = self._rate.row("lam") if torch.is_tensor(lambda_val) else lambda_val
+        self._model_kw = {} if quality is None else {"quality": self.quality, "device_quality": True}
         self._one = torch.ones((), device=dev, dtype=torch.float32)
         gen_state = torch.cuda.get_rng_state(dev)   # (the probe and the warm-up draw noise: restored below)
         with torch.no_grad():
-            probe = model.analysis_hyperprior(self.x, training=True) if hasattr(model, "analysis_hyperprior") \
-                else model(self.x)
+            probe = model.analysis_hyperprior(self.x, training=True, **self._model_kw) \
+                if hasattr(model, "analysis_hyperprior") else model(self.x)
         y, z = probe["y"], probe["z"]
         Bn, Mc, hy, wy = y.shape
         _, Mz, hz, wz = z.shape
@@ -152,7 +205,7 @@ class StepPlan(_ReadBack):
         # second stream: functional.flush_point -- worth ~1 % replayed, harmful eager)
         F_.PLAN_RECORDING = True
         try:
-            out = self.model(self.x, noise=self.noise)
+            out = self.model(self.x, noise=self.noise, **self._model_kw)
             res = self.loss_fn(out, self.x, self.lam, sync=False)
             res["loss"].backward(self._one)   # (a resident 1.0: `backward()` alone launches a fill for it every step)
         finally:
@@ -164,14 +217,16 @@ class StepPlan(_ReadBack):
         self.u.uniform_()
         return self._body()
 
-    def step(self, x: torch.Tensor):
+    def step(self, x: torch.Tensor, quality=None, lam=None):
         """forward + loss + backward of `x` (same shape as the example): gradients land in `p.grad` of every
         parameter (the tensors of the captured step: same addresses every time); returns (model_out, results), the
-        captured step's output tensors, rewritten by every call."""
+        captured step's output tensors, rewritten by every call.  `quality`, `lam` (a plan captured with resident ones):
+        B host values each for this and the following steps; omitted, the previous values stay."""
         if x.shape != self.x.shape:
             raise L.LicError(f"StepPlan was captured for batches of shape {tuple(self.x.shape)}, got {tuple(x.shape)}")
         if x.data_ptr() != self.x.data_ptr():
             self.x.copy_(x, non_blocking=True)
+        self._rate.set(quality=quality, lam=lam)
         for p, g in zip(self._params, self._grads):   # (an optimizer.zero_grad(set_to_none=True) in between)
             if p.grad is not g:
                 p.grad = g
@@ -198,9 +253,10 @@ class ForwardPlan(_ReadBack):
     """The analysis + hyperprior forward (models.analysis_hyperprior: the scope BASELINE's north star quotes its roofline
     on; also what a serving process runs before the entropy coder) captured once under no_grad and replayed by the
     library -- StepPlan without the backward pass.  `training`: with the quantiser's uniform noise (drawn per call into a
-    fixed buffer, the reference's order) or with rounding."""
+    fixed buffer, the reference's order) or with rounding.  `quality` (a rate-level model): a CUDA float32 [B] tensor; the
+    plan keeps a resident copy (`self.quality`) which the record reads, and `plan(x, quality=...)` serves any qualities."""
 
-    def __init__(self, model, example: torch.Tensor, training: bool = True, warmup: int = 2):
+    def __init__(self, model, example: torch.Tensor, training: bool = True, warmup: int = 2, quality=None):
         if not example.is_cuda:
             raise L.LicError("ForwardPlan needs a CUDA batch (there is no CPU fallback)")
         self.model, self.training = model, training
@@ -208,9 +264,12 @@ class ForwardPlan(_ReadBack):
         self._plan = C.c_void_p()
         self.x = example.clone(memory_format=torch.preserve_format)
         dev = example.device
+        self._rate = _RatePoint(dev, example.shape[0], quality=quality)
+        self.quality = self._rate.row("quality")
+        kw = {} if quality is None else {"quality": self.quality, "device_quality": True}
         gen_state = torch.cuda.get_rng_state(dev)
         with torch.no_grad():
-            probe = model.analysis_hyperprior(self.x, training=training)
+            probe = model.analysis_hyperprior(self.x, training=training, **kw)
         y, z = probe["y"], probe["z"]
         Bn, Mc, hy, wy = y.shape
         _, Mz, hz, wz = z.shape
@@ -226,12 +285,12 @@ class ForwardPlan(_ReadBack):
         with torch.cuda.stream(cap), torch.no_grad():
             for _ in range(max(warmup, 1)):
                 self.u.uniform_()
-                model.analysis_hyperprior(self.x, training=training, noise=self.noise)
+                model.analysis_hyperprior(self.x, training=training, noise=self.noise, **kw)
         torch.cuda.current_stream(dev).wait_stream(cap)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph(keep_graph=True)
         with torch.no_grad(), torch.cuda.graph(self.graph, stream=cap):
-            self.out = model.analysis_hyperprior(self.x, training=training, noise=self.noise)
+            self.out = model.analysis_hyperprior(self.x, training=training, noise=self.noise, **kw)
         torch.cuda.set_rng_state(gen_state, dev)
         rc = self._lib.lic_plan_create(C.c_void_p(self.graph.raw_cuda_graph()), C.byref(self._plan))
         if rc != 0:
@@ -242,11 +301,12 @@ class ForwardPlan(_ReadBack):
         L.check(self._lib.lic_plan_info(self._plan, info), "lic_plan_info")
         self.info = dict(zip(("nodes", "kernels", "memsets", "memcpys", "on_side_stream", "events", "tuned"), list(info)))
 
-    def __call__(self, x: torch.Tensor):
+    def __call__(self, x: torch.Tensor, quality=None):
         if x.shape != self.x.shape:
             raise L.LicError(f"ForwardPlan was captured for batches of shape {tuple(self.x.shape)}, got {tuple(x.shape)}")
         if x.data_ptr() != self.x.data_ptr():
             self.x.copy_(x, non_blocking=True)
+        self._rate.set(quality=quality)
         if self.training:
             self.u.uniform_()
         rc = self._lib.lic_plan_replay(self._plan, _stream(), self._sides, 1)

@@ -23,6 +23,9 @@ averages themselves travel in the optimizer's state dict.
 `rate_points=[(q, lambda), ...]` trains a rate-level model (models: rate_levels): every step draws one pair
 from a host generator seeded with `rate_seed`, runs the model at quality q and the loss at that lambda; the generator's
 state travels in the checkpoint (key `rate_rng`), and validation runs once per pair, logged under `val/q<i>/...`.
+`rate_per_image=True` draws one pair per IMAGE from the same generator (`draw_rate_points`), so a batch holds rate points
+side by side; qualities and lambdas go to the device as [B] tensors, the model runs with `device_quality=True` and the
+loss with its per-image lambda, and `step_plan=True` is allowed: the recorded step reads both from device memory.
 """
 from __future__ import annotations
 
@@ -77,22 +80,30 @@ def _build_scheduler(kind, optimizer, max_steps):
     return None, False
 
 
+def draw_rate_points(rng: random.Random, rate_points, batch: int):
+    """the (quality, lambda) pairs of one batch under `rate_per_image`: one `rng.choice` per image, in image order"""
+    return [rng.choice(rate_points) for _ in range(batch)]
+
+
 class Trainer:
     def __init__(self, model, optimizer, train_loader, val_loader=None, rd_loss=None, lambda_val=0.005,
                  scheduler=None, max_steps=10000, resume=False, log_interval=None, img_interval=None,
                  val_interval=None, log_dir="runs/experiment", checkpoint_path="./checkpoints/checkpoint.pth",
                  device="cuda", distributed: Optional[bool] = None, writer=None, step_plan: bool = False,
                  clip_max_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_eval: bool = False,
-                 rate_points=None, rate_seed: int = 0):
+                 rate_points=None, rate_seed: int = 0, rate_per_image: bool = False):
         if rd_loss is None:
             raise ValueError("You must provide a rate-distortion loss function (`rd_loss`)")
         self.rate_points = None if rate_points is None else [(float(q), float(lam)) for q, lam in rate_points]
+        self.rate_per_image = bool(rate_per_image)
+        if self.rate_per_image and self.rate_points is None:
+            raise ValueError("rate_per_image=True needs rate_points")
         if self.rate_points is not None:
             if not self.rate_points:
                 raise ValueError("rate_points must hold at least one (quality, lambda) pair")
-            if step_plan:
+            if step_plan and not self.rate_per_image:
                 raise ValueError("rate_points with step_plan=True: the recorded step bakes one lambda and one quality in; "
-                                 "a rate-level model trains with the eager step")
+                                 "a rate-level model trains with the eager step, or with rate_per_image=True")
             if getattr(model, "rate_levels", None) is None:
                 raise ValueError("rate_points need a model with rate_levels")
             for q, _ in self.rate_points:
@@ -207,14 +218,19 @@ class Trainer:
             skipped = self.optimizer.skipped_steps() if self._fused_clip else self._skipped
             self.writer.add_scalar("train/skipped_steps", skipped, self.step)
 
-    def _planned_step(self, imgs):
+    def _planned_step(self, imgs, pairs=None):
         from .loss import _KEYS
         from .plan import StepPlan
+        rate = {} if pairs is None else {"quality": [q for q, _ in pairs], "lam": [lam for _, lam in pairs]}
         if self._plan is None:
-            self._plan = StepPlan(self.model, self.rd_loss, self.lambda_val, imgs)
+            if pairs is None:
+                self._plan = StepPlan(self.model, self.rd_loss, self.lambda_val, imgs)
+            else:
+                up = lambda v: torch.tensor(v, dtype=torch.float32, device=imgs.device)
+                self._plan = StepPlan(self.model, self.rd_loss, up(rate["lam"]), imgs, quality=up(rate["quality"]))
         if imgs.shape != self._plan.x.shape:
             return None
-        model_out, res = self._plan.step(imgs)
+        model_out, res = self._plan.step(imgs, **rate)
         self._optimizer_step()
         results = dict(res)
         buf = results.pop('_buffer', None)
@@ -226,12 +242,20 @@ class Trainer:
 
     def train_step(self, imgs):
         imgs = imgs.to(self.device)
+        pairs = None
+        if self.rate_per_image:
+            pairs = self.last_rate_point = draw_rate_points(self._rate_rng, self.rate_points, imgs.shape[0])
         if self.step_plan and imgs.is_cuda:
-            done = self._planned_step(imgs)
+            done = self._planned_step(imgs, pairs)
             if done is not None:
                 return done
         self.optimizer.zero_grad()
-        if self.rate_points is not None:
+        if pairs is not None:
+            q = torch.tensor([q for q, _ in pairs], dtype=torch.float32, device=imgs.device)
+            lam = torch.tensor([lam for _, lam in pairs], dtype=torch.float32, device=imgs.device)
+            model_out = self.model(imgs, quality=q, device_quality=True)
+            results = self.rd_loss(model_out, imgs, lam)
+        elif self.rate_points is not None:
             q, lam = self.last_rate_point = self._rate_rng.choice(self.rate_points)
             model_out = self.model(imgs, quality=q)
             results = self.rd_loss(model_out, imgs, lam)
