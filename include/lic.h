@@ -222,6 +222,24 @@ int lic_gdn_reparam_bwd(const float* p, const float* dout, float* dp, int64_t n,
 /* lic_gdn_reparam_bwd for beta [nb] and gamma [ng] of one GDN in one launch (either count may be 0) */
 int lic_gdn_reparam_bwd2(const float* pb, const float* dob, float* dpb, int64_t nb, float bound_b, const float* pg,
                          const float* dog, float* dpg, int64_t ng, float bound_g, lic_stream_t stream);
+/* lic_gdn_reparam_bwd2 for data-parallel ranks.  The pass-through is one-sided in the gradient's sign, so the mean of
+ * the ranks' passed gradients is not the passed gradient of the whole batch: a half with its `late` flag set gets
+ * dp = dout*2*max(p,bound) alone (linear in dout, so the ranks' mean is the whole batch's), and after the all-reduce
+ * lic_gdn_pass_batch applies g = pass ? g : 0 in place, pass = (p >= bound) | (g < 0), to every such gradient in one
+ * launch.  On one rank the two steps give the bits of lic_gdn_reparam_bwd2.  `jobs` is a HOST array, copied into the
+ * kernel arguments, LIC_PASS_MAX_JOBS per launch; block0 is filled by the call. */
+#define LIC_PASS_MAX_JOBS 32
+typedef struct {
+  const float* p; /* the parameter */
+  float* g;       /* its gradient, rewritten in place */
+  int64_t n;
+  float bound;
+  int32_t block0;
+} lic_pass_job;
+int lic_gdn_reparam_bwd2_late(const float* pb, const float* dob, float* dpb, int64_t nb, float bound_b, const float* pg,
+                              const float* dog, float* dpg, int64_t ng, float bound_g, int32_t late_b, int32_t late_g,
+                              lic_stream_t stream);
+int lic_gdn_pass_batch(const lic_pass_job* jobs, int32_t njobs, lic_stream_t stream);
 /* t = dL/dnorm: inverse ? 0.5*g*x*rsqrt(n) : -0.5*g*x*rsqrt(n)/n   (dense [n] tensors) */
 int lic_gdn_dnorm(const float* g, const float* x, const float* norm, float* t, int64_t n,
                   int32_t inverse, lic_stream_t stream);

@@ -70,6 +70,10 @@ class ReduceJob(C.Structure):
                 ("block0", _i32), ("nblocks", _i32)]
 
 
+class PassJob(C.Structure):
+    _fields_ = [("p", _vp), ("g", _vp), ("n", _i64), ("bound", _f32), ("block0", _i32)]
+
+
 class AdamJob(C.Structure):
     _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", _i64), ("block0", _i32), ("nblocks", _i32)]
 
@@ -145,6 +149,8 @@ SIGNATURES = {
     "lic_gdn_reparam": (C.c_int, [_vp, _vp, _i64, _f32, _f32, _vp]),
     "lic_gdn_reparam_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _f32, _vp]),
     "lic_gdn_reparam_bwd2": (C.c_int, [_vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _i64, _f32, _vp]),
+    "lic_gdn_reparam_bwd2_late": (C.c_int, [_vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _i64, _f32, _i32, _i32, _vp]),
+    "lic_gdn_pass_batch": (C.c_int, [C.POINTER(PassJob), _i32, _vp]),
     "lic_gdn_dnorm": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "lic_quantize": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
     "lic_quantize_anchor": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

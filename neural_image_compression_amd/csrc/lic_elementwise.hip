@@ -296,10 +296,11 @@ LIC_EXPORT int lic_gdn_reparam_bwd(const float* p, const float* dout, float* dp,
 }
 
 // the same for the two parameters of one GDN (beta [C], gamma [C][C]) in ONE launch: element i < nb is beta's,
-// the rest gamma's (either half may be absent: n = 0)
-LIC_EXPORT int lic_gdn_reparam_bwd2(const float* pb, const float* dob, float* dpb, int64_t nb, float bound_b,
-                                    const float* pg, const float* dog, float* dpg, int64_t ng, float bound_g,
-                                    lic_stream_t stream) {
+// the rest gamma's (either half may be absent: n = 0).  A `late` half gets the product alone: its one-sided pass-through
+// depends on the gradient's sign, so data-parallel ranks apply it to the averaged gradient (lic_gdn_pass_batch)
+static int reparam_bwd2(const float* pb, const float* dob, float* dpb, int64_t nb, float bound_b, const float* pg,
+                        const float* dog, float* dpg, int64_t ng, float bound_g, bool late_b, bool late_g,
+                        lic_stream_t stream) {
   if (nb < 0 || ng < 0 || (nb > 0 && (!pb || !dob || !dpb)) || (ng > 0 && (!pg || !dog || !dpg))) return LIC_ERR_INVALID;
   if (nb + ng == 0) return LIC_OK;
   return ew_launch(nb + ng, stream, [=] __device__(long i) {
@@ -308,8 +309,56 @@ LIC_EXPORT int lic_gdn_reparam_bwd2(const float* pb, const float* dob, float* dp
     const float pv = isb ? pb[j] : pg[j], dv = isb ? dob[j] : dog[j], bound = isb ? bound_b : bound_g;
     const float v = pv > bound ? pv : bound;
     const float g = dv * 2.0f * v;
-    (isb ? dpb : dpg)[j] = (pv >= bound || g < 0.0f) ? g : 0.0f;
+    (isb ? dpb : dpg)[j] = ((isb ? late_b : late_g) || pv >= bound || g < 0.0f) ? g : 0.0f;
   });
+}
+LIC_EXPORT int lic_gdn_reparam_bwd2(const float* pb, const float* dob, float* dpb, int64_t nb, float bound_b,
+                                    const float* pg, const float* dog, float* dpg, int64_t ng, float bound_g,
+                                    lic_stream_t stream) {
+  return reparam_bwd2(pb, dob, dpb, nb, bound_b, pg, dog, dpg, ng, bound_g, false, false, stream);
+}
+LIC_EXPORT int lic_gdn_reparam_bwd2_late(const float* pb, const float* dob, float* dpb, int64_t nb, float bound_b,
+                                         const float* pg, const float* dog, float* dpg, int64_t ng, float bound_g,
+                                         int32_t late_b, int32_t late_g, lic_stream_t stream) {
+  return reparam_bwd2(pb, dob, dpb, nb, bound_b, pg, dog, dpg, ng, bound_g, late_b != 0, late_g != 0, stream);
+}
+
+// the pass-through lic_gdn_reparam_bwd2_late left out, in place, for a table of gradients in one launch
+struct PassTable {
+  lic_pass_job j[LIC_PASS_MAX_JOBS];
+  int nblocks[LIC_PASS_MAX_JOBS];
+  int n;
+};
+__global__ __launch_bounds__(EW_BLOCK) void gdn_pass_batch_kernel(const PassTable tb) {
+  int k = 0;
+  while (k + 1 < tb.n && (int)blockIdx.x >= tb.j[k + 1].block0) ++k;
+  const float* p = tb.j[k].p;
+  float* g = tb.j[k].g;
+  const long n = tb.j[k].n;
+  const float bound = tb.j[k].bound;
+  const long step = (long)tb.nblocks[k] * EW_BLOCK;
+  for (long i = (long)((int)blockIdx.x - tb.j[k].block0) * EW_BLOCK + threadIdx.x; i < n; i += step)
+    if (!(p[i] >= bound || g[i] < 0.0f)) g[i] = 0.0f;
+}
+LIC_EXPORT int lic_gdn_pass_batch(const lic_pass_job* jobs, int32_t njobs, lic_stream_t stream) {
+  if (njobs < 0 || (njobs > 0 && !jobs)) return LIC_ERR_INVALID;
+  for (int i = 0; i < njobs; ++i)
+    if (!jobs[i].p || !jobs[i].g || jobs[i].n <= 0) return LIC_ERR_INVALID;
+  for (int base = 0; base < njobs; base += LIC_PASS_MAX_JOBS) {
+    PassTable tb;
+    tb.n = njobs - base < LIC_PASS_MAX_JOBS ? njobs - base : LIC_PASS_MAX_JOBS;
+    int blocks = 0;
+    for (int i = 0; i < tb.n; ++i) {
+      tb.j[i] = jobs[base + i];
+      tb.nblocks[i] = ew_grid(tb.j[i].n, EW_BLOCK);
+      tb.j[i].block0 = blocks;
+      blocks += tb.nblocks[i];
+    }
+    hipLaunchKernelGGL(gdn_pass_batch_kernel, dim3(blocks), dim3(EW_BLOCK), 0, (hipStream_t)stream, tb);
+    const int rc = lic_check_launch();
+    if (rc != LIC_OK) return rc;
+  }
+  return LIC_OK;
 }
 
 __device__ __forceinline__ float gdn_t1(float g, float x, float n, int inverse) {

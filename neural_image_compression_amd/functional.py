@@ -288,11 +288,29 @@ def _reparam_bwd2(beta_c, dbe, beta_bound, gamma_c, dge, gamma_bound):
     dgamma = torch.empty_like(gamma_c) if gamma_c is not None else None
     if dbeta is None and dgamma is None:
         return None, None
-    L.check(L.load().lic_gdn_reparam_bwd2(_ptr(beta_c), _ptr(dbe), _ptr(dbeta), 0 if dbeta is None else dbeta.numel(),
-                                          beta_bound, _ptr(gamma_c), _ptr(dge), _ptr(dgamma),
-                                          0 if dgamma is None else dgamma.numel(), gamma_bound, _stream()),
-            "lic_gdn_reparam_bwd2")
+    nb, ng = 0 if dbeta is None else dbeta.numel(), 0 if dgamma is None else dgamma.numel()
+    late_b, late_g = _pass_late(beta_c, beta_bound), _pass_late(gamma_c, gamma_bound)
+    if late_b or late_g:
+        L.check(L.load().lic_gdn_reparam_bwd2_late(_ptr(beta_c), _ptr(dbe), _ptr(dbeta), nb, beta_bound, _ptr(gamma_c),
+                                                   _ptr(dge), _ptr(dgamma), ng, gamma_bound, int(late_b), int(late_g),
+                                                   _stream()), "lic_gdn_reparam_bwd2_late")
+        return dbeta, dgamma
+    L.check(L.load().lic_gdn_reparam_bwd2(_ptr(beta_c), _ptr(dbe), _ptr(dbeta), nb, beta_bound, _ptr(gamma_c), _ptr(dge),
+                                          _ptr(dgamma), ng, gamma_bound, _stream()), "lic_gdn_reparam_bwd2")
     return dbeta, dgamma
+
+
+def _pass_late(param, bound) -> bool:
+    """Is `param`'s gradient averaged over data-parallel ranks before anything reads it?  The lower bound's backward
+    lets a gradient through one-sidedly (below the bound only if negative), which is not linear in the gradient: the
+    mean of the ranks' passed gradients is not the passed gradient of the whole batch wherever the ranks disagree in
+    sign.  Such a parameter gets the product alone here and the bound is left with its bucket slot (entry[3]):
+    GradientAllReducer.finish() applies the pass-through to the averaged gradient, on every rank alike."""
+    e = GRAD_VIEWS.get(id(param)) if (GRAD_VIEWS and param is not None) else None
+    if e is None or e[0]() is not param:
+        return False
+    e[3] = float(bound)
+    return True
 
 
 def _leaky_bwd(y, dy, slope):

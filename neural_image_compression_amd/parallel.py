@@ -10,7 +10,10 @@ destination: 99 % of the gradient bytes never move again); a gradient that autog
 (small vectors, split views) is copied into its slot when it arrives.  A bucket's all-reduce is launched
 from an autograd hook as soon as its last gradient exists, so it overlaps the rest of backward;
 `finish()` waits (and, for back-ends without an averaging collective, scales each bucket with one
-multiply).  No per-step concatenation, no per-step allocation.  Works with any torch.distributed
+multiply).  One step of the backward pass is not linear in the gradient -- below its lower bound a GDN parameter
+lets only a negative gradient through -- so the mean of the ranks' results would not be the whole batch's there: the
+ranks exchange those gradients in front of that step and `finish()` applies it to the mean (`_pass_through`, one
+launch).  No per-step concatenation, no per-step allocation.  Works with any torch.distributed
 back-end ("nccl" = RCCL on ROCm; "gloo" in the CPU tests).
 """
 from __future__ import annotations
@@ -81,7 +84,8 @@ class GradientAllReducer:
                 for i, o in zip(idxs, offs):
                     p = self.params[i]
                     self._views[i] = flat[o:o + p.numel()].view(p.shape)
-                    F_.GRAD_VIEWS[id(p)] = [weakref.ref(p), self._views[i], False]   # [param, slot, handed out this step]
+                    # [param, slot, handed out this step, lower bound whose pass-through finish() applies (or None)]
+                    F_.GRAD_VIEWS[id(p)] = [weakref.ref(p), self._views[i], False, None]
         self._pending = [0] * len(self.buckets)
         self._work = [None] * len(self.buckets)
         self._events = [[] for _ in self.buckets]  # one per gradient: backward may run on several streams
@@ -166,7 +170,25 @@ class GradientAllReducer:
             self._work[b].wait()
             if not self._avg and self.world > 1:
                 self._flat[b].mul_(1.0 / self.world)
+        self._pass_through()
         self.reset()
+
+    def _pass_through(self):
+        """The GDN parameters' lower bound lets a gradient through one-sidedly (functional._pass_late): their backward
+        left that step out, it is applied here to the AVERAGED gradient -- what the whole batch would have given, and
+        the same on every rank -- in one launch over all of them."""
+        jobs = []
+        for i, p in enumerate(self.params):
+            e = F_.GRAD_VIEWS.get(id(p))
+            if e is not None and e[3] is not None and e[0]() is p and p.is_cuda:
+                jobs.append((p.data_ptr(), self._views[i].data_ptr(), p.numel(), e[3]))
+        if not jobs:
+            return
+        from . import _lib as L
+        arr = (L.PassJob * len(jobs))()
+        for a, (pp, gp, n, bound) in zip(arr, jobs):
+            a.p, a.g, a.n, a.bound = pp, gp, n, bound
+        L.check(L.load().lic_gdn_pass_batch(arr, len(jobs), F_._stream()), "lic_gdn_pass_batch")
 
     def remove(self):
         for h in self._hooks:

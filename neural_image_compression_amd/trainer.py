@@ -131,6 +131,8 @@ class Trainer:
         self.rank = dist.get_rank() if self.distributed else 0
         self.reducer = None
         if self.distributed and dist.get_world_size() > 1:
+            if step_plan:   # (refused before the reducer registers its bucket slots: they would outlive this object)
+                raise ValueError("step_plan replays one GPU's step; data-parallel training uses the eager step")
             broadcast_parameters(self.model)
             if hasattr(self.model, "overlap_branches") and dist.get_backend() != "nccl":
                 self.model.overlap_branches = False  # ranks time-sharing one GPU (gloo rehearsals) stall with it
@@ -147,8 +149,6 @@ class Trainer:
         # another shape (the last one of an epoch) takes the eager step.
         self.step_plan = bool(step_plan)
         self._plan = None
-        if self.step_plan and self.reducer is not None:
-            raise ValueError("step_plan replays one GPU's step; data-parallel training uses the eager step")
         # gradient clipping / non-finite guard: a FusedAdam does both inside its own launches (optim.py: no read-back,
         # no extra pass over the gradients); any other optimizer gets torch's clip_grad_norm_ in front of its step.
         # Either way after the reducer, so every rank clips the same averaged gradient; the optimizer step is outside

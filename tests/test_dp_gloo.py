@@ -1,6 +1,11 @@
 """N > 1 path on CPU: two gloo ranks, bucketed gradient all-reduce (mean) must reproduce the
-big-batch gradient of one process (the only correctness pin for data parallelism).
-Uses a small torch model: the reducer is model-agnostic and the HIP kernels need a GPU."""
+big-batch gradient of one process.  Uses a small torch model: the reducer is model-agnostic and
+the HIP kernels need a GPU (tests/test_00_dp_modes_gpu.py holds the real models to the same two statements).
+
+  S1  one rank, forced reducer: a mean over one rank is the identity, so gradients and parameters are bit for bit
+      those of the plain run (a parameter without a gradient: None there, an all-zero slot here);
+  S2  two gloo ranks: SUM, then one multiply by 1/2 -- every rank holds exactly (g0 + g1) * 0.5 in fp32, g_r the plain
+      gradient of shard r."""
 import os
 import socket
 
@@ -41,6 +46,14 @@ def _worker(rank, world, port, overlap, q):
             net.zero_grad(set_to_none=True)
             _loss(net, x[lo:hi]).backward()
             red.finish()
+        # S2: the plain gradients of both shards, from a twin without a reducer, in this process
+        twin, shards = _net(), []
+        for r in range(world):
+            twin.zero_grad(set_to_none=True)
+            _loss(twin, x[slice(*shard_batch(8, r, world))]).backward()
+            shards.append([p.grad.clone() for p in twin.parameters()])
+        for p, g0, g1 in zip(net.parameters(), *shards):
+            assert torch.equal(p.grad, (g0 + g1) * 0.5), "the averaged gradient is not (g0 + g1) * 0.5 bit for bit"
         q.put((rank, [p.grad.detach().numpy().tolist() for p in net.parameters()]))  # plain data: no fd passing
     finally:
         dist.barrier()
@@ -78,6 +91,66 @@ def test_single_process_is_a_noop():
     g = [p.grad.clone() for p in net.parameters()]
     red.finish()
     assert all(torch.equal(a, p.grad) for a, p in zip(g, net.parameters()))
+
+
+class _OddNet(torch.nn.Module):
+    """everything the reducer treats specially, in one small net: `twice` is used by two nodes of the graph (its slot
+    goes out once, autograd adds the second contribution), `unused` gets no gradient (an all-zero slot), `wt` is read
+    transposed and `halves` through a split (their gradients arrive as views and are copied into their slots)"""
+
+    def __init__(self):
+        super().__init__()
+        torch.manual_seed(8)
+        self.twice = torch.nn.Linear(6, 6)
+        self.wt = torch.nn.Parameter(torch.randn(5, 6) * 0.3)
+        self.halves = torch.nn.Parameter(torch.randn(8, 5) * 0.3)
+        self.unused = torch.nn.Parameter(torch.randn(7))
+
+    def forward(self, x):
+        h = torch.tanh(self.twice(torch.tanh(self.twice(x))))
+        h = torch.tanh(h @ self.wt.t())
+        a, b = self.halves.split([3, 5], dim=0)
+        return (h @ a.t()).sum(dim=1, keepdim=True) + (h @ b.t()).mean(dim=1, keepdim=True)
+
+
+@pytest.mark.parametrize("overlap", [True, False])
+def test_one_rank_forced_reducer_is_the_plain_run_bit_for_bit(tmp_path, overlap):
+    """S1 in this process: a one-rank gloo group on a FileStore (no sockets of our own, no child process)"""
+    from neural_image_compression_amd import functional as F_
+    assert not F_.GRAD_VIEWS
+    dist.init_process_group("gloo", store=dist.FileStore(str(tmp_path / "store"), 1), rank=0, world_size=1)
+    try:
+        plain, net = _OddNet(), _OddNet()
+        names = [n for n, _ in net.named_parameters()]
+        opt_p, opt_r = torch.optim.Adam(plain.parameters(), lr=0.01), torch.optim.Adam(net.parameters(), lr=0.01)
+        red = GradientAllReducer(net.parameters(), bucket_mb=0.0001, overlap=overlap, force=True)
+        assert red.active and len(red.buckets) >= 3 and len(F_.GRAD_VIEWS) == len(names)
+        torch.manual_seed(12)
+        for step in range(2):               # the second step reuses the buckets, on stepped parameters
+            x = torch.randn(4, 6)
+            for m, opt in ((plain, opt_p), (net, opt_r)):
+                opt.zero_grad(set_to_none=True)
+                _loss(m, x).backward()
+            red.finish()
+            for i, (n, p, q) in enumerate(zip(names, plain.parameters(), net.parameters())):
+                slot = red._views[i]
+                assert q.grad.data_ptr() == slot.data_ptr() and q.grad.is_contiguous(), (step, n)
+                if n == "unused":
+                    assert p.grad is None and not q.grad.any(), (step, n)
+                else:
+                    assert torch.equal(p.grad, q.grad), (step, n)
+            copied = {names[i] for i in red.copied_last_step}
+            assert {"wt", "halves", "twice.weight"} <= copied and "unused" not in copied, (step, copied)
+            opt_p.step()
+            opt_r.step()
+            for n, p, q in zip(names, plain.parameters(), net.parameters()):
+                assert torch.equal(p, q), (step, n)
+        red.remove()
+        assert not F_.GRAD_VIEWS
+    finally:
+        for p in list(F_.GRAD_VIEWS):       # (a failure above must not leak slots into the tests that follow)
+            F_.GRAD_VIEWS.pop(p)
+        dist.destroy_process_group()
 
 
 # ---- Trainer under data parallelism: validation numbers are averaged over the ranks (ADVICE r1) -----------

@@ -301,6 +301,39 @@ def test_gdn_reparam_bwd2_exact(env, n):
     assert torch.equal(bits(dgamma), bits(want[1])), int((bits(dgamma) != bits(want[1])).sum())
 
 
+@pytest.mark.parametrize("late", [(1, 0), (0, 1), (1, 1)], ids=str)
+def test_gdn_reparam_late_pass_through_exact(env, late):
+    """the data-parallel split of the same backward: lic_gdn_reparam_bwd2_late leaves a late half as the product
+    dout * 2 * max(p, bound), lic_gdn_pass_batch zeroes what the bound does not let through -- together the bits of
+    lic_gdn_reparam_bwd2 (more elements than one grid covers in gamma's half, 1001 in beta's)"""
+    import ctypes as C
+    nic, F_, L, dev = env
+    sizes = (1001, TAILS[1] - 1001)
+    ps = [_reparam_inputs(m, b, 530 + i) for i, (m, b) in enumerate(zip(sizes, BOUNDS))]
+    ds = [randn(m, 540 + i) for i, m in enumerate(sizes)]
+    lin = [d * 2.0 * torch.clamp_min(p, b) for p, b, d in zip(ps, BOUNDS, ds)]
+    want = [torch.where((p >= b) | (g < 0), g, torch.zeros_like(g)) for p, b, g in zip(ps, BOUNDS, lin)]
+    tp, td = [p.to(dev) for p in ps], [d.to(dev) for d in ds]
+    out = [torch.empty_like(p) for p in tp]
+    L.check(L.load().lic_gdn_reparam_bwd2_late(F_._ptr(tp[0]), F_._ptr(td[0]), F_._ptr(out[0]), sizes[0], BOUNDS[0],
+                                               F_._ptr(tp[1]), F_._ptr(td[1]), F_._ptr(out[1]), sizes[1], BOUNDS[1],
+                                               late[0], late[1], F_._stream()), "lic_gdn_reparam_bwd2_late")
+    for k in range(2):
+        assert torch.equal(bits(out[k]), bits(lin[k] if late[k] else want[k])), k
+    jobs = (L.PassJob * 2)()
+    n = 0
+    for k in range(2):
+        if late[k]:
+            jobs[n].p, jobs[n].g, jobs[n].n, jobs[n].bound = tp[k].data_ptr(), out[k].data_ptr(), sizes[k], BOUNDS[k]
+            n += 1
+    guard = [o.clone() for o in out]
+    L.check(L.load().lic_gdn_pass_batch(jobs, n, F_._stream()), "lic_gdn_pass_batch")
+    for k in range(2):
+        assert torch.equal(bits(out[k]), bits(want[k])), k
+        assert late[k] or torch.equal(bits(out[k]), bits(guard[k]))      # (a half that was not named is not touched)
+    assert L.load().lic_gdn_pass_batch(None, 1, None) == -1 and L.load().lic_gdn_pass_batch(jobs, 0, None) == 0
+
+
 @pytest.mark.parametrize("n", TAILS)
 def test_mul_inplace_exact(env, n):
     nic, F_, L, dev = env
